@@ -26,9 +26,15 @@ iterations.  Default: 3 at 512 lanes, more for smaller device batches (the scena
 most 12 batches).  Every step is a full, independent solve and all K steps complete inside the timed region.
 
 value = total Newton-Raphson iterations (sum over all scenarios, all ranks, all K steps) / seconds; inputs are resident in HBM
-when the timed region starts.  The JSON line also carries `roofline` (the factorisation: algorithmic bytes / HIP-event time /
-8 TB/s), `cpu_baseline` (the C oracle on one host core, bounded sample of the same scenarios) and, at N = 1, `config4_se`
-(BASELINE config 4: Gauss-Newton WLS state estimation on the 9241-bus PEGASE-shaped grid).
+when the timed region starts.  A plain run sets up, warms up, times ONE region of exactly K steps and prints the line; nothing else.
+
+  --full: everything beyond the headline as well -- the K-step region repeated until about a second has been timed (value and
+      ms_per_step are then the median region), the steady-state and full-refactorisation regions, single-instance latency and
+      set-up costs, `roofline` (the factorisation: algorithmic bytes / HIP-event time / 8 TB/s) and per-kernel timings,
+      `cpu_baseline` (the C oracle on one host core, bounded sample of the same scenarios) and, at N = 1, `config4_se`
+      (BASELINE config 4: Gauss-Newton WLS state estimation on the 9241-bus PEGASE-shaped grid).
+  --dump-outputs DIR: after the timed steps, the record the timed path delivered for the scenarios of its LAST step is written
+      as DIR/<name>.npy (float64; see dump_outputs).  The inputs are seeded: the same arguments give the same scenarios.
 """
 import argparse
 import json
@@ -451,8 +457,9 @@ def device_state(index):
         return {"error": repr(e)}
 
 
-def timed_regions(torch, dist, world, force_dist, cdev, run, steps):
-    """The K-step region (fenced on both sides, max over ranks), repeated until about a second has been timed; (regions, iterations of one region, last status)."""
+def timed_regions(torch, dist, world, force_dist, cdev, run, steps, repeat=True):
+    """The K-step region (fenced on both sides, max over ranks), repeated until about a second has been timed (repeat=False: timed once);
+    (regions, iterations of one region, last status)."""
     def fence():
         if world > 1 or force_dist:
             dist.barrier()
@@ -471,6 +478,8 @@ def timed_regions(torch, dist, world, force_dist, cdev, run, steps):
         return dt, it, st
 
     dt0, iters_local, last_status = region()
+    if not repeat:
+        return [dt0], iters_local, last_status
     repeats = max(3, min(int(os.environ.get("JG_BENCH_MAX_REPEATS", "50")), int(np.ceil(float(os.environ.get("JG_BENCH_MIN_SECONDS", "1.0")) / max(dt0, 1e-6)))))
     regions = [dt0]
     for _ in range(repeats - 1):
@@ -478,6 +487,43 @@ def timed_regions(torch, dist, world, force_dist, cdev, run, steps):
         assert it_r == iters_local, "the same scenarios take the same iterations in every region"
         regions.append(dtr)
     return regions, iters_local, last_status
+
+
+DUMP_LIMIT_BYTES = 60_000_000       # --dump-outputs writes at most this much (the .npy headers stay far below the rest of 64 MB)
+
+
+def last_step_record(dist, rank, world, packed, ring, steps, merge, B):
+    """Host copy of the record the pipeline delivered for the LAST step of a run of `steps` steps (call it after the region's closing fence):
+    this rank's share sits in job (steps - 1) // merge at lanes m B .. (m + 1) B; with N > 1 ranks rank 0 receives every rank's share, in
+    scenario order (None on the other ranks)."""
+    j = (steps - 1) // merge
+    m = steps - 1 - j * merge
+    rows = packed[j % ring][m * B:(m + 1) * B].cpu().numpy()
+    if world < 2:
+        return rows
+    parts = [None] * world if rank == 0 else None
+    dist.gather_object(rows, parts, dst=0)
+    return np.concatenate(parts) if rank == 0 else None
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES, seed=0):
+    """Writes every array as out_dir/<name>.npy in float64.  Arrays of two dimensions are per-scenario rows (scenario x bus): when everything
+    together would exceed `limit` bytes, the same fixed, seeded sample of scenarios -- sorted, written as sample_rows.npy -- is kept of each."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    wide = [k for k, a in arrays.items() if a.ndim == 2]
+    total = sum(a.nbytes for a in arrays.values())
+    if wide and total > limit:
+        rows = arrays[wide[0]].shape[0]
+        per_row = sum(arrays[k].nbytes for k in wide) // rows
+        keep = max(1, min(rows, (limit - (total - per_row * rows) - 8 * rows) // per_row))
+        sample = np.sort(np.random.default_rng(seed).choice(rows, size=keep, replace=False))
+        for k in wide:
+            arrays[k] = arrays[k][sample]
+        arrays["sample_rows"] = sample.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
+    return sorted(arrays)
 
 
 def live_pmc_traffic(case, batch, n):
@@ -639,12 +685,13 @@ def workload_se(jg, torch, dist, args, rank, local, world, cdev, force_dist):
         return int(sum(int(np.sum(it[:r])) for (it, _), r in zip(out, real))), out[-1][1][:B]
 
     run(args.warmup)
-    regions, iters_local, last_status = timed_regions(torch, dist, world, force_dist, cdev, run, args.steps)
+    regions, iters_local, last_status = timed_regions(torch, dist, world, force_dist, cdev, run, args.steps, repeat=args.full)
+    record = last_step_record(dist, rank, world, packed, ring, args.steps, merge, B) if args.dump_outputs else None
     dt = float(np.median(regions))
     jobs_per_region = -(-args.steps // merge)
     steady = jobs_per_region >= 3 * len(pipe.handles)
     steady_extra = None
-    if not steady:                                    # K as given measures fill + drain of the pipeline: ALSO a region long enough for its steady state
+    if not steady and args.full:                      # K as given measures fill + drain of the pipeline: ALSO a region long enough for its steady state
         ks = 3 * len(pipe.handles) * merge
         rs, it_s, _ = timed_regions(torch, dist, world, force_dist, cdev, run, ks)
         steady_extra = (ks, float(np.median(rs)), it_s)
@@ -658,30 +705,6 @@ def workload_se(jg, torch, dist, args, rank, local, world, cdev, force_dist):
     if rank == 0:
         d = an.dims
         L = an.batch
-        algo = {"rows": L * (16 * d["slots"] + 16 * d["m"] + 16 * n), "gain": L * (16 * d["slots"] + 8 * d["m"] + 32 * d["gain_blocks"] + 16 * n),
-                "factor": L * (64 * ((d["lu_blocks"] + n) // 2)), "backward": L * (32 * ((d["lu_blocks"] + n) // 2) + 64 * n)}
-        kern = {}
-        for k, name in enumerate(("rows", "gain", "factor", "backward")):
-            ms = float(np.median([an.time_kernel(k, 6 if name == "factor" else 12) for _ in range(5)]))
-            kern[name] = {"ms": ms, "bytes": algo[name], "GBps": algo[name] / ms / 1e6, "frac": algo[name] / ms / 1e6 / HBM_PEAK_GBS}
-        dom = max(kern, key=lambda k: kern[k]["ms"])
-        traffic = traffic_source = None
-        live = live_pmc_traffic_se(L) if (world == 1 and not args.no_cpu and case == "case9241synth") else None
-        pmc = os.path.join(ROOT, "profiles", "pmc_traffic_se.json")
-        try:
-            per = None
-            if live is not None:
-                per, traffic_source = live, "two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of tools/profile_se.py inside this bench run"
-            elif os.path.exists(pmc):
-                pj = json.load(open(pmc))
-                if int(pj.get("batch_ld", 0)) == L and pj.get("grid") == case:
-                    per, traffic_source = pj["traffic_per_increment"], "profiles/pmc_traffic_se.json (committed: the same two passes on an earlier box)"
-            if per:
-                for kk in kern:
-                    kern[kk]["hbm_traffic_bytes_pmc"] = per.get(kk)
-                traffic = per.get(dom)
-        except Exception:
-            traffic = None
         nsc = total * args.steps
         line = {
             "metric": "GN iterations/sec (sharded Monte-Carlo WLS state estimation, PMU + legacy, 9241-bus PEGASE-shaped grid)",
@@ -699,11 +722,36 @@ def workload_se(jg, torch, dist, args, rank, local, world, cdev, force_dist):
                        "parallelism": f"realisation-sharded x{world}, one all-gather of the packed record per device batch"},
             "scenarios_per_s": nsc / dt, "ms_per_solve_batched": 1e3 * dt / nsc, "iterations_per_scenario": counts[0] / nsc,
             "converged_fraction": counts[1] / total, "pipeline_construction_ms": 1e3 * t_pipe,
-            "roofline": {"bound": "hbm", "kernel": {"rows": "k_gn_rows", "gain": "k_gn_gain", "factor": "k_fact_task + k_fact_top (symmetric plan)", "backward": "k_bwd_level"}[dom],
-                         "achieved": kern[dom]["GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": kern[dom]["frac"], "traffic": traffic,
-                         "traffic_source": traffic_source if traffic is not None else None, "algorithmic_bytes": kern[dom]["bytes"]},
-            "kernels": kern,
         }
+        if args.full:
+            algo = {"rows": L * (16 * d["slots"] + 16 * d["m"] + 16 * n), "gain": L * (16 * d["slots"] + 8 * d["m"] + 32 * d["gain_blocks"] + 16 * n),
+                    "factor": L * (64 * ((d["lu_blocks"] + n) // 2)), "backward": L * (32 * ((d["lu_blocks"] + n) // 2) + 64 * n)}
+            kern = {}
+            for k, name in enumerate(("rows", "gain", "factor", "backward")):
+                ms = float(np.median([an.time_kernel(k, 6 if name == "factor" else 12) for _ in range(5)]))
+                kern[name] = {"ms": ms, "bytes": algo[name], "GBps": algo[name] / ms / 1e6, "frac": algo[name] / ms / 1e6 / HBM_PEAK_GBS}
+            dom = max(kern, key=lambda k: kern[k]["ms"])
+            traffic = traffic_source = None
+            live = live_pmc_traffic_se(L) if (world == 1 and not args.no_cpu and case == "case9241synth") else None
+            pmc = os.path.join(ROOT, "profiles", "pmc_traffic_se.json")
+            try:
+                per = None
+                if live is not None:
+                    per, traffic_source = live, "two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of tools/profile_se.py inside this bench run"
+                elif os.path.exists(pmc):
+                    pj = json.load(open(pmc))
+                    if int(pj.get("batch_ld", 0)) == L and pj.get("grid") == case:
+                        per, traffic_source = pj["traffic_per_increment"], "profiles/pmc_traffic_se.json (committed: the same two passes on an earlier box)"
+                if per:
+                    for kk in kern:
+                        kern[kk]["hbm_traffic_bytes_pmc"] = per.get(kk)
+                    traffic = per.get(dom)
+            except Exception:
+                traffic = None
+            line["roofline"] = {"bound": "hbm", "kernel": {"rows": "k_gn_rows", "gain": "k_gn_gain", "factor": "k_fact_task + k_fact_top (symmetric plan)", "backward": "k_bwd_level"}[dom],
+                                "achieved": kern[dom]["GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": kern[dom]["frac"], "traffic": traffic,
+                                "traffic_source": traffic_source if traffic is not None else None, "algorithmic_bytes": kern[dom]["bytes"]}
+            line["kernels"] = kern
         if steady_extra:
             ks, dts, _ = steady_extra
             line["value_steady"] = counts[2] / dts
@@ -711,12 +759,16 @@ def workload_se(jg, torch, dist, args, rank, local, world, cdev, force_dist):
             line["steady_ms_per_step"] = 1e3 * dts / ks
             line["steady_what"] = (f"the K = {args.steps}-step region is {jobs_per_region} device batch(es) with {len(pipe.handles)} in flight (fill + drain); value_steady is the same "
                                    f"measurement over {ks} steps (three rounds of the batches in flight).  value, ms_per_step: the K of the caller, unchanged")
-        pred = predicted_from_shards("se", world, total)
-        if pred:
-            line["predicted"] = pred
-        if world == 1 and not args.no_cpu:
-            line["cpu_baseline"] = cpu_baseline_se(jg, s, case, pf, budget_s=10.0)
-            line["speedup_vs_cpu_baseline"] = line["value"] / line["cpu_baseline"]["value"]
+        if args.full:
+            pred = predicted_from_shards("se", world, total)
+            if pred:
+                line["predicted"] = pred
+            if world == 1 and not args.no_cpu:
+                line["cpu_baseline"] = cpu_baseline_se(jg, s, case, pf, budget_s=10.0)
+                line["speedup_vs_cpu_baseline"] = line["value"] / line["cpu_baseline"]["value"]
+        if record is not None:                        # the realisations of the last step: magnitude | angle | iterations | status | objective
+            dump_outputs(args.dump_outputs, {"voltage_magnitude": record[:, :n], "voltage_angle": record[:, n:2 * n], "iterations": record[:, 2 * n],
+                                             "status": record[:, 2 * n + 1], "objective": record[:, 2 * n + 2]})
     gather_close()
     pipe.close()
     pf.close()
@@ -744,8 +796,11 @@ def main():
                          "per step of the PMU + legacy measurement set on the 9241-bus grid, Gauss-Newton WLS, the same line shape (GN iterations/s)")
     ap.add_argument("--full-refactor", action="store_true", help="no base case: the first iteration of every batch refactorises like the others (the path of rounds 1-5)")
     ap.add_argument("--top-cap", type=int, default=0, help="pivots in the dense top of the shared-factor sweeps (0: the library's default, < 0: none)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline legs")
-    ap.add_argument("--no-se", action="store_true", help="skip the config4_se object")
+    ap.add_argument("--full", action="store_true", help="measure beyond the headline as well: repeated regions (median), steady-state and full-refactorisation "
+                    "regions, single-instance latency and set-up, per-kernel timings and roofline, the cpu_baseline legs and config4_se")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline legs")
+    ap.add_argument("--no-se", action="store_true", help="with --full: skip the config4_se object")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the record of the last step's scenarios as DIR/<name>.npy")
     args = ap.parse_args()
 
     import torch
@@ -828,17 +883,19 @@ def main():
         screen_rating = np.maximum(1.2 * np.maximum(sf, st_), 0.05)
     # single-instance latency (BASELINE config 2/3 "ms/solve"): the SAME handle again from the case's start point (warm: what the
     # reference's reused analysis is); what a first solve pays on top is reported as setup_ms
+    # (measured with --full, as everything up to the scenario selection below)
     t_single = []
-    for _ in range(7):
-        jg.setInitialPoint_(base)
-        t0 = time.perf_counter()
-        jg.powerFlow_(base, fetch=False)
-        t_single.append(time.perf_counter() - t0)
-    base_jacobian = base.jacobian if (rank == 0 and not args.no_cpu) else None     # for the splu leg (CSC of the reference, base state)
+    if args.full:
+        for _ in range(7):
+            jg.setInitialPoint_(base)
+            t0 = time.perf_counter()
+            jg.powerFlow_(base, fetch=False)
+            t_single.append(time.perf_counter() - t0)
+    base_jacobian = base.jacobian if (args.full and rank == 0 and not args.no_cpu) else None     # for the splu leg (CSC of the reference, base state)
     base.close()
     # the same solve through the level launches of a small batch (JG_SINGLE=0: what a single instance ran until round 6 -- a wave with one live lane per item)
     t_single_levels = []
-    if rank == 0:
+    if rank == 0 and args.full:
         os.environ["JG_SINGLE"] = "0"
         try:
             lv = jg.newtonRaphson(jg.powerSystem(tables), batch=1, device=local)
@@ -856,28 +913,29 @@ def main():
     # The first handle of a process also pays the HIP context and the load of the library's code object.  What ONE MORE analysis costs in a
     # warm process (what a reference user pays per newtonRaphson() call) is measured twice: of the SAME grid while the library still holds
     # its plan (engines of one pattern share the symbolic analysis and the device tables), and after jg_plan_cache_clear (a full analysis):
-    def prebuilt():                                  # a system whose AC model exists (acModel! is not part of what is compared: the CPU leg's
-        ps = jg.powerSystem(tables)                  # OracleSystem holds its Ybus as well)
-        jg.acModel_(ps)
-        return ps
+    if args.full:
+        def prebuilt():                                  # a system whose AC model exists (acModel! is not part of what is compared: the CPU leg's
+            ps = jg.powerSystem(tables)                  # OracleSystem holds its Ybus as well)
+            jg.acModel_(ps)
+            return ps
 
-    s1 = prebuilt()
-    t0 = time.perf_counter()
-    again = jg.newtonRaphson(s1, batch=1, device=local)
-    t_create_cached = time.perf_counter() - t0
-    t0 = time.perf_counter()
-    jg.powerFlow_(again)
-    t_first_cached = time.perf_counter() - t0
-    again.close()
-    jg._lib.lib().jg_plan_cache_clear()
-    s2 = prebuilt()
-    t0 = time.perf_counter()
-    again = jg.newtonRaphson(s2, batch=1, device=local)
-    t_create2 = time.perf_counter() - t0
-    t0 = time.perf_counter()
-    jg.powerFlow_(again)
-    t_first2 = time.perf_counter() - t0
-    again.close()
+        s1 = prebuilt()
+        t0 = time.perf_counter()
+        again = jg.newtonRaphson(s1, batch=1, device=local)
+        t_create_cached = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        jg.powerFlow_(again)
+        t_first_cached = time.perf_counter() - t0
+        again.close()
+        jg._lib.lib().jg_plan_cache_clear()
+        s2 = prebuilt()
+        t0 = time.perf_counter()
+        again = jg.newtonRaphson(s2, batch=1, device=local)
+        t_create2 = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        jg.powerFlow_(again)
+        t_first2 = time.perf_counter() - t0
+        again.close()
 
     # Scenario selection (untimed, identical on every rank): the first scenarios of a seeded shuffle of the non-bridge branches
     # THAT HAVE A POWER FLOW.  A contingency without a solution runs to the iteration limit (20 iterations for one lane while the
@@ -965,16 +1023,18 @@ def main():
     # mostly the fill and drain of the batches in flight plus whatever the box does in that instant.  So the SAME region -- K steps, fenced on
     # both sides, max over ranks -- is repeated until about a second has been timed (every rank takes the count from the max-reduced first
     # region: same number of collectives everywhere) and the line reports the MEDIAN region; min / max travel with it (timed_regions).
-    dev_state0 = device_state(local) if rank == 0 else None
-    regions, iters_local, last_status = timed_regions(torch, dist, world, force_dist, cdev, run, args.steps)
-    dev_state1 = device_state(local) if rank == 0 else None
+    # (a plain run times that region ONCE: K steps exactly; --full repeats it)
+    dev_state0 = device_state(local) if (rank == 0 and args.full) else None
+    regions, iters_local, last_status = timed_regions(torch, dist, world, force_dist, cdev, run, args.steps, repeat=args.full)
+    dev_state1 = device_state(local) if (rank == 0 and args.full) else None
+    record = last_step_record(dist, rank, world, packed, ring, args.steps, merge, B) if args.dump_outputs else None
     dt = float(np.median(regions))
     #  when the K-step region cannot reach the pipeline's steady state (N = 8 at K = 20: 4 device batches, all in flight at once) the line
     # ALSO carries the same measurement over three rounds of the batches in flight -- value_steady; value stays the K of the caller
     jobs_per_region = -(-args.steps // merge)
     steady = jobs_per_region >= 3 * len(pipe.handles)
     steady_extra = None
-    if not steady:
+    if not steady and args.full:
         ks = 3 * len(pipe.handles) * merge
         rs, it_s, _ = timed_regions(torch, dist, world, force_dist, cdev, run, ks)
         steady_extra = [ks, float(np.median(rs)), it_s]
@@ -990,6 +1050,7 @@ def main():
         for h in pipe.handles:
             c = jg.firstIterationCounts(h)
             first_counts[0] += c[0]; first_counts[1] += c[1]
+    if pipe.base is not None and args.full:
         pipe.setFirstIteration(False)
         run(min(args.steps, 3 * len(pipe.handles) * merge))
         rf, it_f, _ = timed_regions(torch, dist, world, force_dist, cdev, run, args.steps)
@@ -1011,73 +1072,14 @@ def main():
 
     if rank == 0:
         d = an.dims
-        ab = algorithmic_bytes(d, an.batch)
-        # live kernel timing with HIP events on the library's own stream (one handle, nothing else in flight, all scenarios active)
-        # (median of five event-bracketed groups of launches: one stalled group -- seen once in ~30 runs, an 11 ms gap inside a
-        # group of 10 backward sweeps -- must not become the per-launch figure)
-        def timed(kernel, reps):
-            return float(np.median([an.time_kernel(kernel, reps) for _ in range(5)]))
-        # (repetitions: the first launches of a group run on a chip that has just been idle -- 4 / 8 / 20 assemblies per group measure
-        # 0.156 / 0.144 / 0.137 ms per launch on the same handle; the groups are long enough that this start-up does not set the figure)
-        t_asm = timed(0, 24)
-        t_lu = timed(1, 8)
-        t_sol = timed(2, 12)
-        kern = {
-            "assembly": {"ms": t_asm, "bytes": ab["assembly"], "launches": 1},
-            "lu": {"ms": t_lu, "bytes": ab["lu"], "launches": d["lu_launches"]},
-            "solve": {"ms": t_sol, "bytes": ab["solve"], "launches": d["solve_launches"]},
-        }
-        first_kern = None
-        if pipe.base is not None:
-            binfo = pipe.base.info
-            t_first_lin = timed(4, 12)
-            t_mis = timed(5, 24)
-            # algorithmic bytes of the shared-factor step: the right-hand side read once and the solution written once per scenario (the factor is shared:
-            # 2.2 MB per batch), the state read and written by the fused update; of the mismatch pass: SURVEY 8(d)'s assembly figure without the Jacobian stream
-            nn, bb = d["n"], an.batch
-            first_kern = {"shared_factor_step": {"ms": t_first_lin, "bytes": bb * (16 * nn + 16 * nn + 32 * nn) + 32 * d["lu_blocks"],
-                                                 "launches": binfo["forward_launches"] + binfo["backward_launches"] + 2},
-                          "mismatch_pass": {"ms": t_mis, "bytes": bb * (16 * nn + 32 * nn), "launches": 1}}
-            for k in first_kern.values():
-                k["GBps"] = k["bytes"] / (k["ms"] * 1e-3) / 1e9
-                k["frac"] = k["GBps"] / HBM_PEAK_GBS
-        for k in kern.values():
-            k["GBps"] = k["bytes"] / (k["ms"] * 1e-3) / 1e9
-            k["frac"] = k["GBps"] / HBM_PEAK_GBS
-        dom = max(kern, key=lambda k: kern[k]["ms"])
-        names = {"assembly": "k_assemble", "lu": "k_fact_task + k_fact_top (one factorisation: task launches of the bottom levels -- k_fact_level where a plan keeps wave records -- and the multifrontal top)", "solve": "k_bwd_level (one backward sweep)"}
-        # HBM bytes per logical launch from the committed PMC passes (profiles/pmc_traffic.json: FETCH_SIZE x2 +
-        # WRITE_SIZE, calibrated on a kernel of known byte count); only valid for the grid and batch it was collected at
-        traffic = None
-        traffic_source = None
-        pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        pj_live = live_pmc_traffic(args.case, an.batch, n) if (world == 1 and not args.no_cpu) else None
-        if pj_live is not None or os.path.exists(pmc):
-            try:
-                pj = pj_live if pj_live is not None else json.load(open(pmc))
-                traffic_source = ("two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of tools/profile_kernels.py inside this bench run" if pj_live is not None
-                                  else "profiles/pmc_traffic.json (committed: the same two passes on an earlier box; rocprofv3 not run in this bench run)")
-                if int(pj.get("batch_ld", 0)) == an.batch and pj.get("grid") == args.case:
-                    key = {"assembly": "k_assemble", "lu": "k_fact", "solve": "k_fwd+k_bwd"}[dom]
-                    traffic = pj["traffic_per_logical_launch"].get(key)
-                    for kk, nm in (("assembly", "k_assemble"), ("lu", "k_fact"), ("solve", "k_fwd+k_bwd")):
-                        tr = pj["traffic_per_logical_launch"].get(nm)
-                        kern[kk]["hbm_traffic_bytes_pmc"] = tr
-                        if tr is not None:            # 8(d)'s sanity rule: the counters cannot be below the algorithmic bytes
-                            kern[kk]["pmc_at_least_algorithmic"] = bool(tr >= 0.98 * kern[kk]["bytes"])
-            except Exception:
-                traffic = None
-        roofline = {"bound": "hbm", "kernel": names[dom], "achieved": kern[dom]["GBps"], "peak": HBM_PEAK_GBS,
-                    "unit": "GB/s", "frac": kern[dom]["frac"], "traffic": traffic, "traffic_source": traffic_source if traffic is not None else None,
-                    "per_launch_ms": kern[dom]["ms"] / kern[dom]["launches"], "launches": kern[dom]["launches"],
-                    "algorithmic_bytes": kern[dom]["bytes"]}
         nsc = total * args.steps
         line = {
             "metric": "NR iterations/sec (batched N-1 AC power flow, 10k-bus grid)",
             "value": iters_total / dt, "unit": "NR iterations/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True,
             "region_repeats": len(regions), "region_ms_min": 1e3 * float(np.min(regions)), "region_ms_median": 1e3 * dt, "region_ms_max": 1e3 * float(np.max(regions)),
-            "region_what": f"the K = {args.steps}-step region (fenced on both sides, max over ranks) repeated {len(regions)} times; value and ms_per_step are its MEDIAN",
+            "region_what": (f"the K = {args.steps}-step region (fenced on both sides, max over ranks) repeated {len(regions)} times; value and ms_per_step are its MEDIAN"
+                            if args.full else f"ONE K = {args.steps}-step region (fenced on both sides, max over ranks); value and ms_per_step are its figures"),
             "scaling": args.scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
             "config": {"workload": f"{args.case} batched N-1 contingency Newton-Raphson, {total} scenarios per step "
                                    f"({B} per GPU), start = base-case solution, tol 1e-8, max 20 iterations",
@@ -1107,51 +1109,7 @@ def main():
             "ms_per_solve_batched": 1e3 * dt / nsc,
             "iterations_per_scenario": iters_total / nsc,
             "converged_fraction": conv_total / total,
-            "single_instance": {"ms_per_solve": 1e3 * float(np.median(t_single)), "iterations": base_iters,
-                                "ms_per_iteration": 1e3 * float(np.median(t_single)) / max(base_iters, 1),
-                                "what": "warm solves of ONE handle from the case's start point (setInitialPoint! between them, outside the clock): kernels whose lanes are items of the one "
-                                        "scenario, the whole solve as one hipGraph from the second solve on (DESIGN.md 3.5)",
-                                "ms_per_solve_level_launches": 1e3 * float(np.median(t_single_levels)) if t_single_levels else None,
-                                "level_launches_what": "the same warm solve with JG_SINGLE=0: the level launches of a small batch (a wave per item, one live lane) instead of the "
-                                                       "item-per-lane / row-per-lane kernels of ONE scenario (k_fact1_*, k_bwd1_*), same run",
-                                "setup_ms": 1e3 * (t_create2 + t_first2) - 1e3 * float(np.median(t_single)),
-                                "setup_what": f"a further analysis in a warm process with the library's plan cache emptied, on a system whose AC model exists: newtonRaphson() {1e3 * t_create2:.1f} ms (reference maps, "
-                                              f"symbolic analysis of the block LU, replay tables, upload) + first powerFlow!() {1e3 * t_first2:.1f} ms (hipGraph capture) - one warm solve",
-                                "setup_cached_ms": 1e3 * (t_create_cached + t_first_cached) - 1e3 * float(np.median(t_single)),
-                                "setup_cached_what": f"the same while the plan of this grid is cached (second handle of a grid): newtonRaphson() {1e3 * t_create_cached:.1f} ms "
-                                                     f"+ first powerFlow!() {1e3 * t_first_cached:.1f} ms - one warm solve",
-                                "pipeline_construction_ms": 1e3 * t_pipe,
-                                "setup_first_in_process_ms": 1e3 * (t_create + t_first) - 1e3 * float(np.median(t_single)),
-                                "setup_first_what": f"the first analysis of the process (HIP context, code object load on top): newtonRaphson() {1e3 * t_create:.1f} ms "
-                                                    f"+ first powerFlow!() {1e3 * t_first:.1f} ms - one warm solve"},
-            "roofline": roofline,
-            "kernels": kern,
         }
-        # what a step costs by its kernels alone (each timed alone on one handle, all lanes active) against what the pipeline delivers: a batch of mean m iterations
-        # runs m + 1 assemblies and m factorisations + sweeps when every iteration refactorises; with the shared first iteration a mismatch pass, the shared-factor
-        # step, m assemblies and m - 1 factorisations + sweeps
-        m_it = iters_total / nsc
-        ksum_full = (m_it + 1) * t_asm + m_it * (t_lu + t_sol)
-        if first_kern is not None:
-            ksum = first_kern["mismatch_pass"]["ms"] + first_kern["shared_factor_step"]["ms"] + m_it * t_asm + (m_it - 1) * (t_lu + t_sol)
-            line["kernels_first_iteration"] = first_kern
-        else:
-            ksum = ksum_full
-        line["kernel_sum_ms"] = ksum / max(merge, 1)      # (the kernels were timed on a handle of B x merge lanes: `merge` steps of this rank)
-        # the same weighting for the ALGORITHMIC bytes of a step (SURVEY 8(d) per kernel): what the whole path moves per step against what the step takes
-        by_full = (m_it + 1) * ab["assembly"] + m_it * (ab["lu"] + ab["solve"])
-        by = (first_kern["mismatch_pass"]["bytes"] + first_kern["shared_factor_step"]["bytes"] + m_it * ab["assembly"] + (m_it - 1) * (ab["lu"] + ab["solve"])) if first_kern is not None else by_full
-        line["path_roofline"] = {"algorithmic_bytes_per_step": by / max(merge, 1) * world, "achieved_GBps": by / max(merge, 1) * world / (line["ms_per_step"] * 1e-3) / 1e9 / world,
-                                 "frac": by / max(merge, 1) / (line["ms_per_step"] * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                                 "what": "algorithmic bytes of one step (per GPU: achieved_GBps, frac) -- the kernels' SURVEY 8(d) figures weighted by the mean iteration count -- over ms_per_step; "
-                                         "the compensated first iteration lowers the bytes a step needs, so this fraction is not comparable across first-iteration modes: "
-                                         "algorithmic_bytes_per_step_full_refactor is what the same step moves when every iteration refactorises",
-                                 "algorithmic_bytes_per_step_full_refactor": by_full / max(merge, 1) * world}
-        line["kernel_sum_full_refactor_ms"] = ksum_full / max(merge, 1)
-        line["step_over_kernels"] = line["ms_per_step"] / line["kernel_sum_ms"]
-        line["kernel_sum_what"] = ("per step and GPU: the kernels of one device batch timed ALONE (HIP events, one handle, every lane active, no compaction) weighted by the mean "
-                                   "iteration count, divided by the steps a device batch holds; step_over_kernels = ms_per_step / kernel_sum_ms -- below 1 the batches in flight "
-                                   "overlap and finished lanes drop out, above 1 the pipeline loses time to launches, verdicts and compaction")
         line["config"]["first_iteration"] = (
             (f"shared base factor (compensation): ONE factorisation of the base-case Jacobian per pipeline, per scenario a 4 x 4 correction and one sweep pair on it "
              f"({pipe.base.info['top_pivots']} pivots of the tree's top as a dense inverse, {pipe.base.info['forward_launches']} + {pipe.base.info['backward_launches']} level launches); "
@@ -1167,7 +1125,115 @@ def main():
             line["gather_exposed_ms"] = float(np.median(gather_ms[jobs_per_region - 1::jobs_per_region])) if len(gather_ms) >= jobs_per_region else float(gather_ms[-1])
             line["gather_what"] = ("wall time of the ONE collective per device batch on rank 0 (pack + all-gather + stream synchronisation); gather_exposed_ms: that of the LAST "
                                    "batch of a region, which no other batch in flight hides")
-        line["device_state"] = {"region_start": dev_state0, "region_end": dev_state1}
+        if args.full:
+            ab = algorithmic_bytes(d, an.batch)
+            # live kernel timing with HIP events on the library's own stream (one handle, nothing else in flight, all scenarios active)
+            # (median of five event-bracketed groups of launches: one stalled group -- seen once in ~30 runs, an 11 ms gap inside a
+            # group of 10 backward sweeps -- must not become the per-launch figure)
+            def timed(kernel, reps):
+                return float(np.median([an.time_kernel(kernel, reps) for _ in range(5)]))
+            # (repetitions: the first launches of a group run on a chip that has just been idle -- 4 / 8 / 20 assemblies per group measure
+            # 0.156 / 0.144 / 0.137 ms per launch on the same handle; the groups are long enough that this start-up does not set the figure)
+            t_asm = timed(0, 24)
+            t_lu = timed(1, 8)
+            t_sol = timed(2, 12)
+            kern = {
+                "assembly": {"ms": t_asm, "bytes": ab["assembly"], "launches": 1},
+                "lu": {"ms": t_lu, "bytes": ab["lu"], "launches": d["lu_launches"]},
+                "solve": {"ms": t_sol, "bytes": ab["solve"], "launches": d["solve_launches"]},
+            }
+            first_kern = None
+            if pipe.base is not None:
+                binfo = pipe.base.info
+                t_first_lin = timed(4, 12)
+                t_mis = timed(5, 24)
+                # algorithmic bytes of the shared-factor step: the right-hand side read once and the solution written once per scenario (the factor is shared:
+                # 2.2 MB per batch), the state read and written by the fused update; of the mismatch pass: SURVEY 8(d)'s assembly figure without the Jacobian stream
+                nn, bb = d["n"], an.batch
+                first_kern = {"shared_factor_step": {"ms": t_first_lin, "bytes": bb * (16 * nn + 16 * nn + 32 * nn) + 32 * d["lu_blocks"],
+                                                     "launches": binfo["forward_launches"] + binfo["backward_launches"] + 2},
+                              "mismatch_pass": {"ms": t_mis, "bytes": bb * (16 * nn + 32 * nn), "launches": 1}}
+                for k in first_kern.values():
+                    k["GBps"] = k["bytes"] / (k["ms"] * 1e-3) / 1e9
+                    k["frac"] = k["GBps"] / HBM_PEAK_GBS
+            for k in kern.values():
+                k["GBps"] = k["bytes"] / (k["ms"] * 1e-3) / 1e9
+                k["frac"] = k["GBps"] / HBM_PEAK_GBS
+            dom = max(kern, key=lambda k: kern[k]["ms"])
+            names = {"assembly": "k_assemble", "lu": "k_fact_task + k_fact_top (one factorisation: task launches of the bottom levels -- k_fact_level where a plan keeps wave records -- and the multifrontal top)", "solve": "k_bwd_level (one backward sweep)"}
+            # HBM bytes per logical launch from the committed PMC passes (profiles/pmc_traffic.json: FETCH_SIZE x2 +
+            # WRITE_SIZE, calibrated on a kernel of known byte count); only valid for the grid and batch it was collected at
+            traffic = None
+            traffic_source = None
+            pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+            pj_live = live_pmc_traffic(args.case, an.batch, n) if (world == 1 and not args.no_cpu) else None
+            if pj_live is not None or os.path.exists(pmc):
+                try:
+                    pj = pj_live if pj_live is not None else json.load(open(pmc))
+                    traffic_source = ("two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of tools/profile_kernels.py inside this bench run" if pj_live is not None
+                                      else "profiles/pmc_traffic.json (committed: the same two passes on an earlier box; rocprofv3 not run in this bench run)")
+                    if int(pj.get("batch_ld", 0)) == an.batch and pj.get("grid") == args.case:
+                        key = {"assembly": "k_assemble", "lu": "k_fact", "solve": "k_fwd+k_bwd"}[dom]
+                        traffic = pj["traffic_per_logical_launch"].get(key)
+                        for kk, nm in (("assembly", "k_assemble"), ("lu", "k_fact"), ("solve", "k_fwd+k_bwd")):
+                            tr = pj["traffic_per_logical_launch"].get(nm)
+                            kern[kk]["hbm_traffic_bytes_pmc"] = tr
+                            if tr is not None:            # 8(d)'s sanity rule: the counters cannot be below the algorithmic bytes
+                                kern[kk]["pmc_at_least_algorithmic"] = bool(tr >= 0.98 * kern[kk]["bytes"])
+                except Exception:
+                    traffic = None
+            roofline = {"bound": "hbm", "kernel": names[dom], "achieved": kern[dom]["GBps"], "peak": HBM_PEAK_GBS,
+                        "unit": "GB/s", "frac": kern[dom]["frac"], "traffic": traffic, "traffic_source": traffic_source if traffic is not None else None,
+                        "per_launch_ms": kern[dom]["ms"] / kern[dom]["launches"], "launches": kern[dom]["launches"],
+                        "algorithmic_bytes": kern[dom]["bytes"]}
+            line["single_instance"] = {"ms_per_solve": 1e3 * float(np.median(t_single)), "iterations": base_iters,
+                                       "ms_per_iteration": 1e3 * float(np.median(t_single)) / max(base_iters, 1),
+                                       "what": "warm solves of ONE handle from the case's start point (setInitialPoint! between them, outside the clock): kernels whose lanes are items of the one "
+                                               "scenario, the whole solve as one hipGraph from the second solve on (DESIGN.md 3.5)",
+                                       "ms_per_solve_level_launches": 1e3 * float(np.median(t_single_levels)) if t_single_levels else None,
+                                       "level_launches_what": "the same warm solve with JG_SINGLE=0: the level launches of a small batch (a wave per item, one live lane) instead of the "
+                                                              "item-per-lane / row-per-lane kernels of ONE scenario (k_fact1_*, k_bwd1_*), same run",
+                                       "setup_ms": 1e3 * (t_create2 + t_first2) - 1e3 * float(np.median(t_single)),
+                                       "setup_what": f"a further analysis in a warm process with the library's plan cache emptied, on a system whose AC model exists: newtonRaphson() {1e3 * t_create2:.1f} ms (reference maps, "
+                                                     f"symbolic analysis of the block LU, replay tables, upload) + first powerFlow!() {1e3 * t_first2:.1f} ms (hipGraph capture) - one warm solve",
+                                       "setup_cached_ms": 1e3 * (t_create_cached + t_first_cached) - 1e3 * float(np.median(t_single)),
+                                       "setup_cached_what": f"the same while the plan of this grid is cached (second handle of a grid): newtonRaphson() {1e3 * t_create_cached:.1f} ms "
+                                                            f"+ first powerFlow!() {1e3 * t_first_cached:.1f} ms - one warm solve",
+                                       "pipeline_construction_ms": 1e3 * t_pipe,
+                                       "setup_first_in_process_ms": 1e3 * (t_create + t_first) - 1e3 * float(np.median(t_single)),
+                                       "setup_first_what": f"the first analysis of the process (HIP context, code object load on top): newtonRaphson() {1e3 * t_create:.1f} ms "
+                                                           f"+ first powerFlow!() {1e3 * t_first:.1f} ms - one warm solve"}
+            line["roofline"] = roofline
+            line["kernels"] = kern
+            # what a step costs by its kernels alone (each timed alone on one handle, all lanes active) against what the pipeline delivers: a batch of mean m iterations
+            # runs m + 1 assemblies and m factorisations + sweeps when every iteration refactorises; with the shared first iteration a mismatch pass, the shared-factor
+            # step, m assemblies and m - 1 factorisations + sweeps
+            m_it = iters_total / nsc
+            ksum_full = (m_it + 1) * t_asm + m_it * (t_lu + t_sol)
+            if first_kern is not None:
+                ksum = first_kern["mismatch_pass"]["ms"] + first_kern["shared_factor_step"]["ms"] + m_it * t_asm + (m_it - 1) * (t_lu + t_sol)
+                line["kernels_first_iteration"] = first_kern
+            else:
+                ksum = ksum_full
+            line["kernel_sum_ms"] = ksum / max(merge, 1)      # (the kernels were timed on a handle of B x merge lanes: `merge` steps of this rank)
+            # the same weighting for the ALGORITHMIC bytes of a step (SURVEY 8(d) per kernel): what the whole path moves per step against what the step takes
+            by_full = (m_it + 1) * ab["assembly"] + m_it * (ab["lu"] + ab["solve"])
+            by = (first_kern["mismatch_pass"]["bytes"] + first_kern["shared_factor_step"]["bytes"] + m_it * ab["assembly"] + (m_it - 1) * (ab["lu"] + ab["solve"])) if first_kern is not None else by_full
+            line["path_roofline"] = {"algorithmic_bytes_per_step": by / max(merge, 1) * world, "achieved_GBps": by / max(merge, 1) * world / (line["ms_per_step"] * 1e-3) / 1e9 / world,
+                                     "frac": by / max(merge, 1) / (line["ms_per_step"] * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                     "what": "algorithmic bytes of one step (per GPU: achieved_GBps, frac) -- the kernels' SURVEY 8(d) figures weighted by the mean iteration count -- over ms_per_step; "
+                                             "the compensated first iteration lowers the bytes a step needs, so this fraction is not comparable across first-iteration modes: "
+                                             "algorithmic_bytes_per_step_full_refactor is what the same step moves when every iteration refactorises",
+                                     "algorithmic_bytes_per_step_full_refactor": by_full / max(merge, 1) * world}
+            line["kernel_sum_full_refactor_ms"] = ksum_full / max(merge, 1)
+            line["step_over_kernels"] = line["ms_per_step"] / line["kernel_sum_ms"]
+            line["kernel_sum_what"] = ("per step and GPU: the kernels of one device batch timed ALONE (HIP events, one handle, every lane active, no compaction) weighted by the mean "
+                                       "iteration count, divided by the steps a device batch holds; step_over_kernels = ms_per_step / kernel_sum_ms -- below 1 the batches in flight "
+                                       "overlap and finished lanes drop out, above 1 the pipeline loses time to launches, verdicts and compaction")
+            line["device_state"] = {"region_start": dev_state0, "region_end": dev_state1}
+            pred = predicted_from_shards("nr", world, total)
+            if pred:
+                line["predicted"] = pred
         if steady_extra:
             ks, dts, its = steady_extra
             line["value_steady"] = its / dts
@@ -1175,19 +1241,17 @@ def main():
             line["steady_ms_per_step"] = 1e3 * dts / ks
             line["steady_what"] = (f"the K = {args.steps}-step region is {jobs_per_region} device batch(es) with {len(pipe.handles)} in flight (fill + drain of the pipeline); "
                                    f"value_steady is the same measurement over {ks} steps (three rounds of the batches in flight).  value, ms_per_step: the K of the caller, unchanged")
-        pred = predicted_from_shards("nr", world, total)
-        if pred:
-            line["predicted"] = pred
         gather_close()
         pipe.close()
-        try:
-            hbm = hbm_measured_gbps(torch)
-            line["roofline"]["hbm_measured_GBps"] = hbm
-            line["roofline"]["hbm_measured_what"] = "device-to-device copy of 1 GiB (read + written bytes / time), torch copy kernel, this run"
-            line["roofline"]["frac_of_measured"] = line["roofline"]["achieved"] / hbm
-        except Exception as e:
-            line["roofline"]["hbm_measured_GBps"] = None
-        if world == 1 and not args.no_cpu:
+        if args.full:
+            try:
+                hbm = hbm_measured_gbps(torch)
+                line["roofline"]["hbm_measured_GBps"] = hbm
+                line["roofline"]["hbm_measured_what"] = "device-to-device copy of 1 GiB (read + written bytes / time), torch copy kernel, this run"
+                line["roofline"]["frac_of_measured"] = line["roofline"]["achieved"] / hbm
+            except Exception as e:
+                line["roofline"]["hbm_measured_GBps"] = None
+        if world == 1 and args.full and not args.no_cpu:
             cb = cpu_baseline(tables, labels[: max(64, min(B, 512))], vm0, va0)
             line["cpu_baseline"] = cb
             line["speedup_vs_cpu_baseline"] = line["value"] / cb["value"]
@@ -1207,7 +1271,7 @@ def main():
                 if allc:
                     line["cpu_baseline_all_cores"] = allc
                     line["speedup_vs_cpu_all_cores"] = line["value"] / allc["value"]
-        if world == 1 and not args.no_se:
+        if world == 1 and args.full and not args.no_se:
             try:
                 se = se_config4(jg, cpu=not args.no_cpu)
                 line["config4_se"] = {"metric": se["metric"], "value": se["value"], "unit": se["unit"], "ms_per_step": se["ms_per_step"],
@@ -1217,6 +1281,13 @@ def main():
                                       "cpu_baseline": se.get("cpu_baseline"), "speedup_vs_cpu_baseline": se.get("speedup_vs_cpu_baseline")}
             except Exception as e:                      # the NR line is the contract; the SE object must never break it
                 line["config4_se"] = {"error": repr(e)}
+        if record is not None:                        # the scenarios of the last step in scenario order, and the branch each of them had out of service
+            outs = {"outage_branch": chosen[((args.steps - 1) * total + np.arange(total)) % chosen.size]}
+            if summary:
+                outs["screen_summary"] = record
+            else:
+                outs.update(voltage_magnitude=record[:, :n], voltage_angle=record[:, n:2 * n], iterations=record[:, 2 * n], status=record[:, 2 * n + 1])
+            dump_outputs(args.dump_outputs, outs)
     else:
         gather_close()
         pipe.close()

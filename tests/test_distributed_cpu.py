@@ -175,3 +175,46 @@ def test_predicted_value_of_an_n_gpu_run_comes_from_the_shard_emulation():
             assert p["per_gpu_value"] == row["value"] and abs(p["value"] - world * row["value"]) < 1e-9 * p["value"]
             assert 0.8 * shards[wl][0]["value"] < row["value"] < 1.2 * shards[wl][0]["value"], "a rank's merged share runs at about the N = 1 rate"
     assert b.predicted_from_shards("nr", 3, 512) is None                       # no measured share for that N
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("_bench", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    return b
+
+
+def test_dump_outputs_samples_a_fixed_set_of_scenarios_below_the_limit(tmp_path):
+    """bench.py --dump-outputs: float64 .npy files; the per-scenario rows (scenario x bus) are cut to the SAME seeded sample of scenarios when everything
+    together would exceed the limit, and the sample is written beside them."""
+    b = _bench_module()
+    rng = np.random.default_rng(1)
+    vm, va, it = rng.random((512, 1000)), rng.random((512, 1000)), rng.integers(1, 9, 512)
+    names = b.dump_outputs(str(tmp_path / "a"), {"voltage_magnitude": vm, "voltage_angle": va, "iterations": it}, limit=2_000_000)
+    assert names == ["iterations", "sample_rows", "voltage_angle", "voltage_magnitude"]
+    a = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in names}
+    assert all(x.dtype == np.float64 for x in a.values())
+    rows = a["sample_rows"].astype(int)
+    assert 0 < rows.size < 512 and np.all(np.diff(rows) > 0) and sum(x.nbytes for x in a.values()) <= 2_000_000
+    assert np.array_equal(a["voltage_magnitude"], vm[rows]) and np.array_equal(a["voltage_angle"], va[rows]) and np.array_equal(a["iterations"], it)
+    b.dump_outputs(str(tmp_path / "b"), {"voltage_magnitude": vm, "voltage_angle": va, "iterations": it}, limit=2_000_000)
+    assert np.array_equal(np.load(tmp_path / "b" / "sample_rows.npy"), a["sample_rows"])
+    assert b.dump_outputs(str(tmp_path / "c"), {"voltage_magnitude": vm[:8], "iterations": it[:8]}) == ["iterations", "voltage_magnitude"]
+    assert np.array_equal(np.load(tmp_path / "c" / "voltage_magnitude.npy"), vm[:8])
+
+
+def test_last_step_record_is_the_share_of_the_last_step():
+    """The K-th step of a region sits in device batch (K - 1) // merge of the record ring, lanes m B .. (m + 1) B of it."""
+    import torch
+    b = _bench_module()
+    B, merge, ring, steps = 3, 2, 4, 7                                   # 4 device batches: steps (0, 1) (2, 3) (4, 5) (6, -)
+    packed = [torch.full((merge * B, 5), float(j)) for j in range(ring)]
+    for j in range(ring):
+        packed[j][:, 0] = torch.arange(merge * B, dtype=torch.float64)
+    r = b.last_step_record(None, 0, 1, packed, ring, steps, merge, B)
+    assert r.shape == (B, 5) and np.all(r[:, 1] == 3) and list(r[:, 0]) == [0, 1, 2]
+    r = b.last_step_record(None, 0, 1, packed, ring, 6, merge, B)
+    assert np.all(r[:, 1] == 2) and list(r[:, 0]) == [3, 4, 5]
+    r = b.last_step_record(None, 0, 1, packed, 2, 6, merge, B)         # job 2 of a ring of two
+    assert np.all(r[:, 1] == 0) and list(r[:, 0]) == [3, 4, 5]

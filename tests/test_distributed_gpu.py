@@ -57,7 +57,7 @@ def _bench(args, **env):
 def test_bench_starts_by_itself_with_two_ranks():
     """`python bench.py --gpus 2` without a launcher: it re-executes itself under torch.distributed.run; two ranks share the one GPU
     over gloo (JG_BENCH_BACKEND: the measured configuration is RCCL), 512 scenarios per step sharded 256 + 256."""
-    d = _bench(["--gpus", "2", "--steps", "4", "--warmup", "1", "--no-cpu", "--no-se"], JG_BENCH_BACKEND="gloo", JG_BENCH_MAX_REPEATS="3")
+    d = _bench(["--gpus", "2", "--steps", "4", "--warmup", "1", "--full", "--no-cpu", "--no-se"], JG_BENCH_BACKEND="gloo", JG_BENCH_MAX_REPEATS="3")
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["steps"] == 4 and d["region_repeats"] == 3
     assert d["config"]["scenarios_per_step"] == 512 and d["config"]["batch_per_gpu"] == 256
     assert d["value"] > 0 and d["converged_fraction"] == 1.0
@@ -74,7 +74,7 @@ def test_bench_at_the_drivers_flags_with_four_ranks():
     """The driver's command shape for N = 4 (`--steps 20 --warmup 3`), four ranks sharing the one GPU over gloo: 512 scenarios sharded 4 x 128, a
     rank solves its shares of 4 steps as one 512-lane device batch; the K-step region is repeated and the line carries the median and the spread,
     and says whether a region reaches the steady state of the pipeline (5 device batches with 3 in flight: it does not)."""
-    d = _bench(["--gpus", "4", "--steps", "20", "--warmup", "3", "--no-cpu", "--no-se"], JG_BENCH_BACKEND="gloo", JG_BENCH_MAX_REPEATS="4")
+    d = _bench(["--gpus", "4", "--steps", "20", "--warmup", "3", "--full", "--no-cpu", "--no-se"], JG_BENCH_BACKEND="gloo", JG_BENCH_MAX_REPEATS="4")
     assert d["n_gpus"] == 4 and d["steps"] == 20 and d["warmup"] == 3 and d["scaling"] == "strong"
     assert d["config"]["batch_per_gpu"] == 128 and d["config"]["lanes_per_device_batch"] == 512 and d["config"]["steps_per_device_batch"] == 4
     assert 3 <= d["region_repeats"] <= 4 and d["region_ms_min"] <= d["region_ms_median"] <= d["region_ms_max"]
@@ -85,7 +85,7 @@ def test_bench_at_the_drivers_flags_with_four_ranks():
 
 def test_bench_region_statistics_at_one_gpu():
     """N = 1 at the driver's flags: 20 device batches per region with three in flight (steady state), the region repeated until ~1 s is timed."""
-    d = _bench(["--steps", "20", "--warmup", "3", "--no-cpu", "--no-se"])
+    d = _bench(["--steps", "20", "--warmup", "3", "--full", "--no-cpu", "--no-se"])
     assert d["n_gpus"] == 1 and d["region_repeats"] >= 3 and d["config"]["pipeline_steady_state"] is True
     assert d["region_ms_max"] < 1.5 * d["region_ms_min"], "regions of the same work on an otherwise idle GPU"
     assert d["region_repeats"] * d["region_ms_median"] > 500.0 or d["region_repeats"] == 50
@@ -104,7 +104,7 @@ def test_bench_at_the_drivers_flags_with_eight_ranks():
     """ The driver's command shape for the 8-GPU run -- `--gpus 8 --steps 20 --warmup 5` -- as a dry run: eight ranks share the one GPU over gloo.
     512 scenarios shard 8 x 64; deviceBatching(64, 20) = 10 steps per device batch = 640 lanes, the rank's whole region as TWO device batches, both in flight: the K-step
     region cannot reach the pipeline's steady state, so the line ALSO carries value_steady (three rounds of the batches in flight); value keeps the caller's K."""
-    d = _bench(["--gpus", "8", "--steps", "20", "--warmup", "5", "--no-cpu", "--no-se"], JG_BENCH_BACKEND="gloo", JG_BENCH_MAX_REPEATS="3", JG_BENCH_MIN_SECONDS="0.2")
+    d = _bench(["--gpus", "8", "--steps", "20", "--warmup", "5", "--full", "--no-cpu", "--no-se"], JG_BENCH_BACKEND="gloo", JG_BENCH_MAX_REPEATS="3", JG_BENCH_MIN_SECONDS="0.2")
     assert d["n_gpus"] == 8 and d["steps"] == 20 and d["warmup"] == 5 and d["scaling"] == "strong"
     c = d["config"]
     assert c["batch_per_gpu"] == 64 and c["steps_per_device_batch"] == 10 and c["lanes_per_device_batch"] == 640 and c["device_batches_per_region"] == 2
@@ -117,7 +117,7 @@ def test_bench_at_the_drivers_flags_with_eight_ranks():
 def test_bench_state_estimation_workload_sharded():
     """`--workload se`: BASELINE config 4 as a sharded Monte-Carlo run with the NR line's shape -- two ranks over gloo (128 + 128 realisations of the 9241-bus
     set's little brother would hide nothing: the real grid, a small batch), and one rank through the C ABI's RCCL gather of the [., 2 n + 3] record."""
-    d = _bench(["--workload", "se", "--gpus", "2", "--batch", "256", "--steps", "2", "--warmup", "1", "--no-cpu"], JG_BENCH_BACKEND="gloo", JG_BENCH_MAX_REPEATS="3",
+    d = _bench(["--workload", "se", "--gpus", "2", "--batch", "256", "--steps", "2", "--warmup", "1", "--full", "--no-cpu"], JG_BENCH_BACKEND="gloo", JG_BENCH_MAX_REPEATS="3",
                JG_BENCH_MIN_SECONDS="0.1")
     assert d["n_gpus"] == 2 and d["unit"] == "GN iterations/s" and d["scaling"] == "strong" and d["dtype"] == "f64"
     c = d["config"]
@@ -128,3 +128,37 @@ def test_bench_state_estimation_workload_sharded():
     d1 = _bench(["--workload", "se", "--batch", "256", "--steps", "4", "--warmup", "1", "--no-cpu"], JG_BENCH_FORCE_DIST="1", JG_BENCH_GATHER="abi",
                 JG_BENCH_MAX_REPEATS="3", JG_BENCH_MIN_SECONDS="0.1")
     assert d1["n_gpus"] == 1 and d1["config"]["gather"] == "abi" and d1["converged_fraction"] == 1.0 and d1["config"]["record"].startswith("magnitude | angle")
+
+
+def test_plain_bench_times_exactly_k_steps_and_dumps_the_last_one(tmp_path):
+    """A plain run (no --full) times ONE region of exactly --steps steps and carries the headline only; --dump-outputs writes the record of the
+    last step's scenarios (512 x 2 n + 2 doubles would be 82 MB: a fixed sample of the voltage rows), and the same arguments give the same outputs."""
+    outs = []
+    for k in range(2):
+        d = _bench(["--steps", "4", "--warmup", "1", "--dump-outputs", str(tmp_path / f"run{k}")])
+        assert d["steps"] == 4 and d["warmup"] == 1 and d["region_repeats"] == 1 and d["unit"] == "NR iterations/s" and d["dtype"] == "f64"
+        assert abs(d["ms_per_step"] * 4 - d["region_ms_median"]) < 1e-6 * d["region_ms_median"] and d["higher_is_better"] is True
+        assert not {"cpu_baseline", "kernels", "roofline", "single_instance", "config4_se", "value_full_refactor"} & set(d)
+        files = sorted(p.name for p in (tmp_path / f"run{k}").iterdir())
+        assert files == ["iterations.npy", "outage_branch.npy", "sample_rows.npy", "status.npy", "voltage_angle.npy", "voltage_magnitude.npy"]
+        arrs = {f[:-4]: np.load(tmp_path / f"run{k}" / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert sum((tmp_path / f"run{k}" / f).stat().st_size for f in files) <= 64_000_000
+        n, rows = d["config"]["buses"], arrs["sample_rows"].size
+        assert arrs["voltage_magnitude"].shape == arrs["voltage_angle"].shape == (rows, n) and 0 < rows < 512
+        assert arrs["iterations"].shape == arrs["status"].shape == arrs["outage_branch"].shape == (512,)
+        assert np.all(arrs["status"] == 0) and np.all(arrs["iterations"] >= 1)
+        assert np.all(np.abs(arrs["voltage_magnitude"] - 1.0) < 0.5)
+        outs.append(arrs)
+    for k in ("outage_branch", "sample_rows", "iterations", "status"):
+        assert np.array_equal(outs[0][k], outs[1][k]), k
+    for k in ("voltage_magnitude", "voltage_angle"):
+        assert np.abs(outs[0][k] - outs[1][k]).max() < 1e-9, k
+
+
+def test_plain_bench_of_the_state_estimation_workload_dumps_the_last_step(tmp_path):
+    d = _bench(["--workload", "se", "--batch", "256", "--steps", "4", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    assert d["steps"] == 4 and d["region_repeats"] == 1 and d["unit"] == "GN iterations/s" and not {"kernels", "roofline", "cpu_baseline"} & set(d)
+    arrs = {p.name[:-4]: np.load(p) for p in tmp_path.iterdir()}
+    assert set(arrs) == {"voltage_magnitude", "voltage_angle", "iterations", "status", "objective"}
+    assert arrs["voltage_magnitude"].shape == (256, d["config"]["buses"]) and np.all(arrs["status"] == 0)

@@ -97,17 +97,24 @@ def test_matpower_reader_matches_fixture(jg, tmp_path):
     assert np.abs(s.branch.parameter.reactance - t["br_x"]).max() == 0
 
 
-def test_hdf5_reader_matches_the_fixtures(jg):
+def test_hdf5_reader_matches_the_fixtures(jg, tmp_path):
     """N1: the pure-Python reader of the reference's HDF5 case layout (compact and dense groups, contiguous datasets,
     one-element datasets broadcast) gives bit-identical tables to the converter that went through h5dump."""
     import glob
+    import lzma
     import os
     from juliagrid.jl_amd.hdf5 import H5File, case_tables
     here = os.path.join(ROOT, "tests", "golden", "h5")
     files = {os.path.basename(p)[:-3]: p for p in glob.glob(os.path.join(here, "case*.h5"))}
     assert set(files) == {"case14", "case_ieee30"}
-    for p in glob.glob("/root/reference/docs/src/examples/cases/hdf5/*.h5"):      # build container only: every shipped case
-        files.setdefault(os.path.basename(p)[:-3], p)
+    for p in glob.glob(os.path.join(here, "cases", "case*.h5*")):                 # every other case the reference ships (the 10k-bus one xz-compressed)
+        name = os.path.basename(p).split(".h5")[0]
+        if p.endswith(".xz"):
+            with open(p, "rb") as fh:
+                (tmp_path / f"{name}.h5").write_bytes(lzma.decompress(fh.read()))
+            p = str(tmp_path / f"{name}.h5")
+        files.setdefault(name, p)
+    assert set(files) == {"case14", "case_ieee30", "case118", "case300", "case1354pegase", "case1951rte", "case_ACTIVSg10k"}
     for name, p in files.items():
         t = case_tables(p)
         ref = load_case(name)
