@@ -39,7 +39,7 @@ using JuliaGrid
 using SparseArrays
 import JuliaGrid: newtonRaphson, fastNewtonRaphsonBX, fastNewtonRaphsonXB, gaussNewton, pmuStateEstimation, mismatch!, solve!, increment!,
                   powerFlow!, stateEstimation!, setInitialPoint!, power!, current!, chiTest,
-                  updateBus!, updateBranch!, updateGenerator!,
+                  updateBus!, updateBranch!, updateGenerator!, reactiveLimit!, adjustAngle!,
                   updateVoltmeter!, updateAmmeter!, updateWattmeter!, updateVarmeter!, updatePmu!,
                   AcPowerFlow, AcStateEstimation, PmuStateEstimation, NewtonRaphson, FastNewtonRaphson, FastNewtonRaphsonModel, GaussNewton, WLS,
                   PowerSystem, Measurement, LU
@@ -1106,6 +1106,54 @@ function iterations(analysis::HipStateEstimation)
     return Int(it[1])
 end
 
+"""
+    setBusType!(b, scenario0, type)
+    busType(b)
+
+Bus types per scenario (jg_nr_set_bus_type / jg_nr_get_bus_type): scenarios `scenario0 + 1 : scenario0 + size(type, 2)` take the columns of
+`type` ([n, count] Int8: 1 PQ, 2 PV, 3 slack, one slack each); `setBusType!(b, scenario0, count)` returns them to the types the batch was built
+with.  `busType` gives the types [n, batch] and the slack bus of every scenario.
+"""
+setBusType!(b::NewtonRaphsonBatch, scenario0::Int, type::Matrix{Int8}) =
+    check(ccall((:jg_nr_set_bus_type, lib), Cint, (Ptr{Cvoid}, Int64, Int64, Ptr{Int8}), b.handle.ptr, scenario0, size(type, 2), type))
+setBusType!(b::NewtonRaphsonBatch, scenario0::Int, count::Int) =
+    check(ccall((:jg_nr_set_bus_type, lib), Cint, (Ptr{Cvoid}, Int64, Int64, Ptr{Int8}), b.handle.ptr, scenario0, count, C_NULL))
+function busType(b::NewtonRaphsonBatch)
+    type = Matrix{Int8}(undef, b.system.bus.number, b.batch)
+    slack = Vector{Int64}(undef, b.batch)
+    check(ccall((:jg_nr_get_bus_type, lib), Cint, (Ptr{Cvoid}, Ptr{Int8}, Ptr{Int64}), b.handle.ptr, type, slack))
+    return type, slack
+end
+
+"""
+    reactiveLimit!(b; restart = true)
+
+reactiveLimit! (acPowerFlow.jl:1081-1155) for every scenario of the batch on the device (jg_nr_set_generators once, then jg_nr_reactive_limit): the
+scenarios with a violation take their new bus types and injections and, `restart`, start again from the system's initial point.  Returns the
+violate matrix [ng, batch] (Int8); a scenario left without a slack reports status 5 from the next powerFlow! on.  `system` is not modified.
+"""
+const QLIM_TABLES = WeakKeyDict{NewtonRaphsonBatch, Any}()   # what jg_nr_set_generators last received per batch (sent again only when it changed)
+
+function reactiveLimit!(b::NewtonRaphsonBatch; restart::Bool = true)
+    system = b.system
+    gen, bus = system.generator, system.bus
+    key = (copy(gen.layout.bus), copy(gen.layout.status), copy(gen.output.active), copy(gen.capability.minReactive), copy(gen.capability.maxReactive),
+           copy(gen.voltage.magnitude), copy(bus.voltage.magnitude), copy(bus.voltage.angle), copy(bus.demand.active), copy(bus.demand.reactive))
+    get(QLIM_TABLES, b, nothing) == key || (QLIM_TABLES[b] = key; check(ccall((:jg_nr_set_generators, lib), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int8}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Float64),
+        b.handle.ptr, gen.number, Vector{Int64}(gen.layout.bus), Vector{Int8}(gen.layout.status), gen.output.active, gen.capability.minReactive,
+        gen.capability.maxReactive, gen.voltage.magnitude, bus.voltage.magnitude, bus.voltage.angle, bus.demand.active, bus.demand.reactive,
+        system.base.power.value * system.base.power.prefix * 1e-6)))
+    violate = Matrix{Int8}(undef, gen.number, b.batch)
+    count = Vector{Int32}(undef, b.batch)
+    check(ccall((:jg_nr_reactive_limit, lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Int8}, Ptr{Int32}), b.handle.ptr, restart ? 1 : 0, violate, count))
+    return violate
+end
+
+"adjustAngle! (acPowerFlow.jl:1196-1206) of every scenario on the device state: the angle of bus `slack` becomes the system's (jg_nr_adjust_angle)"
+adjustAngle!(b::NewtonRaphsonBatch; slack::Int) =
+    check(ccall((:jg_nr_adjust_angle, lib), Cint, (Ptr{Cvoid}, Int64, Float64), b.handle.ptr, slack, b.system.bus.voltage.angle[slack]))
+
 "V and theta of every scenario into DEVICE buffers of the caller ([n, batch] each, e.g. AMDGPU.jl arrays: pass their pointers)"
 voltageDevice!(b::NewtonRaphsonBatch, magnitude::Ptr{Float64}, angle::Ptr{Float64}) =
     check(ccall((:jg_nr_get_voltage_device, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), b.handle.ptr, magnitude, angle))
@@ -1142,6 +1190,6 @@ end
 export HIP, HIPOrthogonal, NewtonRaphsonBatch, BaseCase, baseInfo, baseInverseOnPattern, attach!, startFromBase!, firstIteration!, firstIterationCounts, setOutages!, shareDevice!, branchQuantities, screenSummary, powerFlowDefer!, moveLanes!, finish!, resume!, jacobian!,
        largestNormalizedResidual, normalizedResiduals, commUniqueId, Comm, shard, contingencyAnalysis, clearPlanCache,
        deviceCount, dims, setRefinement!, deviceMaps, setOutage!, snapshotVoltage!, restoreVoltage!, iterations, voltageDevice!, packResults!, packRows!,
-       allgatherDevice, commRank, commWorld, timeKernel, GaussNewtonBatch, setRealisations!, monteCarloEstimation, fastPatch!, setReadings!, drawNoise!, measurementDevice
+       allgatherDevice, commRank, commWorld, timeKernel, setBusType!, busType, GaussNewtonBatch, setRealisations!, monteCarloEstimation, fastPatch!, setReadings!, drawNoise!, measurementDevice
 
 end # module

@@ -121,7 +121,8 @@ int jg_nr_set_refine(jg_nr* h, int mode);
 int jg_nr_set_shared(jg_nr* h, int mode);
 /* powerFlow!(analysis; iteration, tolerance) -- acPowerFlow.jl:1389-1433, per scenario, with the
  * reference's loop accounting.  iters/status: [batch]; status 0 converged, 1 iteration limit,
- * 3 numeric failure. */
+ * 3 numeric failure, 4 deferred to a pool (jg_nr_run_defer), 5 no slack bus left after jg_nr_reactive_limit (the reference's
+ * errorSlackDefinition, src/powerFlow/acPowerFlow.jl:1151-1153; the scenario keeps its state and types, the others are unaffected). */
 int jg_nr_run(jg_nr* h, int64_t max_iter, double tol, int32_t* iters, int32_t* status);
 /* Straggler hand-off between batches of the same grid (no counterpart in the reference, which has no batch: its loop runs one
  * scenario at a time, acPowerFlow.jl:1389-1433).  A batch advances in lockstep until its slowest scenario is done; the last
@@ -197,6 +198,44 @@ int jg_nr_get_jacobian(jg_nr* h, double* nzval);
 int jg_nr_get_maps(jg_nr* h, int64_t* pq, int64_t* pvpq, int64_t* pcount, int64_t* jcolptr, int64_t* jrowval);
 /* analysis.method.iteration per scenario. */
 int jg_nr_get_iteration(jg_nr* h, int32_t* iters);
+
+/*
+ * Bus types per scenario of a batched handle (batch >= 2, not fast Newton-Raphson, no iterative refinement).  The symbolic analysis, the factor
+ * pattern and the plan depend on the Ybus pattern alone; a type that differs per scenario is a change of VALUES in the same plan: the assembly reads
+ * the types of its lane (2 bits per bus in the lane layout, moved with the lanes by the compaction) and pads PV / slack rows and columns with identity
+ * as for the create-time types, and every variable is updated (a masked one has an increment of exactly 0).  While any scenario has types of its own,
+ * jg_nr_get_jacobian / _mismatch / _increment / _maps (reference layout: depends on the types), jg_nr_set_refine(h, 1), jg_nr_move_lanes and
+ * jg_nr_fast_setup return 1; the next run after a change refactorises (no first iteration on an attached base's factor).
+ *   jg_nr_set_bus_type  scenarios scenario0 .. scenario0 + count - 1 take type [count][n] (1 PQ, 2 PV, 3 slack; exactly one slack per scenario);
+ *                       type == NULL: the create-time types again.  Replaces, per scenario, what reactiveLimit! does to system.bus.layout.type
+ *                       and the newtonRaphson(system) built on it (src/powerFlow/acPowerFlow.jl:39-87, 1081-1155).  Refused (1): a fast handle,
+ *                       a handle of batch 1, a scenario without exactly one slack.
+ *   jg_nr_get_bus_type  type [batch][n] (nullable) and the 1-based slack bus of every scenario, slack [batch] (nullable).
+ */
+int jg_nr_set_bus_type(jg_nr* h, int64_t scenario0, int64_t count, const int8_t* type);
+int jg_nr_get_bus_type(jg_nr* h, int8_t* type, int64_t* slack);
+
+/*
+ * reactiveLimit!(analysis) (src/powerFlow/acPowerFlow.jl:1081-1155) for EVERY scenario of a batched handle, on the device (csrc/jg_qlim.hip).
+ *   jg_nr_set_generators  one-time set-up: the generator table in label order -- bus [ng] 1-based, status [ng] (1 in service), pg (gen.output.active),
+ *                         qmin, qmax (gen.capability, may be infinite), vg (gen.voltage.magnitude) -- and the buses' bus_vm, bus_va (bus.voltage),
+ *                         pd, qd (bus.demand) [n], base_mva = system.base.power in MVA.  The per-bus generator lists and their finite Q-limit sums
+ *                         are built here; the initial point is that of initializeACPowerFlow / setInitialPoint! (acPowerFlow.jl:1226-1249, 1312-1358).
+ *   jg_nr_reactive_limit  per scenario (not those left without a slack before): the generator outputs of generatorPower
+ *                         (src/postprocessing/acAnalysis.jl:538-633) at the scenario's state, bus.supply with the slack's P from that state, the
+ *                         violating PV / slack buses turned PQ with Q pinned at the limit, the slack handed over to the first bus that is PV at that
+ *                         point of the reference's loop; the new types and the P / Q injections of the generator buses are written to the lanes.
+ *                         flags & 1: the scenarios with a violation restart from the initial point under their NEW types (the newtonRaphson(system)
+ *                         the reference's user builds next); the others keep their state (the next jg_nr_run confirms them in 0 iterations).
+ *                         violate [batch][ng] (nullable): -1 / 0 / +1 per generator, the reference's return value; count [batch] (nullable): violations.
+ *                         A scenario left without a slack keeps its types and state and reports status 5 from the next run on.
+ *   jg_nr_adjust_angle    adjustAngle!(analysis; slack = bus) (acPowerFlow.jl:1196-1206) per scenario: theta += angle - theta[bus] (bus 1-based,
+ *                         angle = system.bus.voltage.angle of that bus), on the device state.
+ */
+int jg_nr_set_generators(jg_nr* h, int64_t ng, const int64_t* bus, const int8_t* status, const double* pg, const double* qmin, const double* qmax,
+                         const double* vg, const double* bus_vm, const double* bus_va, const double* pd, const double* qd, double base_mva);
+int jg_nr_reactive_limit(jg_nr* h, int flags, int8_t* violate, int32_t* count);
+int jg_nr_adjust_angle(jg_nr* h, int64_t bus, double angle);
 
 /*
  * Fast Newton-Raphson (fastNewtonRaphsonBX / XB) on the same handle -- acPowerFlow.jl:215-537 (model), 687-730

@@ -75,6 +75,11 @@ def lib():
         "jg_nr_get_jacobian": [VP, F64P],
         "jg_nr_get_maps": [VP, I64P, I64P, I64P, I64P, I64P],
         "jg_nr_get_iteration": [VP, I32P],
+        "jg_nr_set_bus_type": [VP, C.c_int64, C.c_int64, VP],
+        "jg_nr_get_bus_type": [VP, I8P, I64P],
+        "jg_nr_set_generators": [VP, C.c_int64, I64P, I8P, F64P, F64P, F64P, F64P, F64P, F64P, F64P, F64P, C.c_double],
+        "jg_nr_reactive_limit": [VP, C.c_int, VP, VP],
+        "jg_nr_adjust_angle": [VP, C.c_int64, C.c_double],
         "jg_nr_time_kernel": [VP, C.c_int, C.c_int, C.POINTER(C.c_double)],
         "jg_nr_fast_setup": [VP, F64P, F64P],
         "jg_nr_fast_mismatch": [VP, F64P, F64P],

@@ -109,10 +109,15 @@ def deviceBatching(share: int, steps: int, lanes: int = 512) -> int:
     return min(range(max(1, (m_max + 1) // 2), m_max + 1), key=lambda m: (-(-steps // m) * m - steps, -m))
 
 
-def contingencyAnalysis(system: PowerSystem, labels, device: int = 0, method: str = "nr") -> AcPowerFlow:
+def contingencyAnalysis(system: PowerSystem, labels, device: int = 0, method: str = "nr", reactiveLimit: int = 0, start=None,
+                        iteration: int = 20, tolerance: float = 1e-8) -> AcPowerFlow:
     """Batched analysis with scenario s = outage of branch labels[s] (None / 0 = base case).  method: "nr" Newton-Raphson, "bx" / "xb" fast
-    Newton-Raphson (constant matrices with per-scenario edits, ONE factorisation for the batch: jg_nr_fast_patch_batch)."""
+    Newton-Raphson (constant matrices with per-scenario edits, ONE factorisation for the batch: jg_nr_fast_patch_batch).
+    reactiveLimit = k > 0 (Newton-Raphson, two or more scenarios): the analysis is also SOLVED -- from `start` (V, theta) when given -- with up to k rounds
+    of reactiveLimit! + powerFlow! per scenario (powerflow.powerFlowLimits_); method.iteration sums the solves of each scenario (test/powerFlow/limits.jl)."""
     labels = list(labels)
+    if reactiveLimit and (method != "nr" or len(labels) < 2):
+        raise ValueError("contingencyAnalysis: reactiveLimit needs method='nr' and two or more scenarios")
     if method in ("bx", "xb"):
         from .powerflow import fastNewtonRaphsonBX, fastNewtonRaphsonXB
         an = (fastNewtonRaphsonBX if method == "bx" else fastNewtonRaphsonXB)(system, batch=len(labels), device=device, max_patch=4)
@@ -121,6 +126,11 @@ def contingencyAnalysis(system: PowerSystem, labels, device: int = 0, method: st
     else:
         raise ValueError("method: nr | bx | xb")
     setOutages_(an, [int(lab) if lab else 0 for lab in labels])
+    if reactiveLimit:
+        from .powerflow import powerFlowLimits_
+        if start is not None:
+            _push_voltage(an, *start)
+        powerFlowLimits_(an, int(reactiveLimit), iteration=iteration, tolerance=tolerance)
     return an
 
 
@@ -157,10 +167,15 @@ class ContingencyPipeline:
     job: results are delivered through `record` (see run)."""
 
     def __init__(self, system: PowerSystem, batch: int, inflight: int = 3, device: int = 0, start=None, pool: int = 0, defer_at: int = 64,
-                 shared_first: bool = True, top_cap: int = 0):
+                 shared_first: bool = True, top_cap: int = 0, reactive_limit: int = 0):
         """shared_first (with a `start`): the start is a BASE CASE -- its Jacobian is factorised once (BaseCase) and the first Newton iteration of every
         scenario is a sweep pair on that shared factor plus a 4 x 4 correction instead of a batched refactorisation (jgrid.h: jg_nr_base_*; the reference
         refactorises per scenario, branch.jl:453-459 + acPowerFlow.jl:890-897).  The handles decide per run whether the conditions hold."""
+        if reactive_limit and pool:
+            raise ValueError("ContingencyPipeline: reactive_limit > 0 with a straggler pool (pool > 0) is not supported")
+        if reactive_limit and int(batch) < 2:
+            raise ValueError("ContingencyPipeline: reactive_limit needs batches of two or more scenarios")
+        self.reactive_limit = max(0, int(reactive_limit))    # rounds of reactiveLimit! + powerFlow! per batch (powerflow.powerFlowLimits_)
         self.system, self.batch = system, int(batch)
         self.base = None
         self._shared_first, self._top_cap, self._device = bool(shared_first), int(top_cap), int(device)
@@ -313,6 +328,15 @@ class ContingencyPipeline:
                         return
                     an = self.handles[k]
                     job = jobs[j]
+                    if getattr(an, "_limits_applied", False):     # the last job's reactive limits: create-time types and injections again
+                        from .powerflow import setBusType_, setInjection_
+                        setBusType_(an, None)
+                        an._lane_types = False
+                        if an._injection is not None:
+                            setInjection_(an, *an._injection)
+                        else:
+                            setInjection_(an)
+                        an._limits_applied = False
                     if isinstance(job, dict):                     # a Monte-Carlo job: per-scenario injections (load / generation variations), outages optional
                         if job.get("labels") is not None:
                             labels = [int(x) if x else 0 for x in job["labels"]]
@@ -350,6 +374,10 @@ class ContingencyPipeline:
                         an.finish()
                         if fetch:
                             an._pull_voltage()
+                    elif self.reactive_limit:
+                        from .powerflow import powerFlowLimits_
+                        an._limits_applied = True
+                        powerFlowLimits_(an, self.reactive_limit, iteration=iteration, tolerance=tolerance, fetch=fetch)
                     else:
                         powerFlow_(an, iteration=iteration, tolerance=tolerance, fetch=fetch)
                     results[j] = (np.array(an.method.iteration), np.array(an.status))

@@ -31,6 +31,7 @@
 #include "../../include/jgrid.h"
 #include "jg_engine.hpp"
 #include "jg_comp.hpp"
+#include "jg_qlim.hpp"
 
 namespace {
 
@@ -61,7 +62,11 @@ struct AsmArgs {
                                // turns the row's mismatch into NaN instead, which k_check reports as status 3)
                                // level 0 of the engine's prefactor plan (jg_symbolic.hpp): where rowtype carries (pivot + 1) << 2 the diagonal block
                                // leaves FACTORISED and the mismatch row is also written as the rhs row W[pivot]
+    const unsigned long long* lt;   // per-lane bus types (k_assemble<.., LT = true>): [ceil(n / 32)][ld], 2 bits per bus (jg_nr_set_bus_type)
 };
+
+// The type of bus i in the lane whose word of row i / 32 is w (2 bits per bus: 1 PQ, 2 PV, 3 slack)
+__device__ __forceinline__ int lane_type(unsigned long long w, int i) { return (int)((w >> ((i & 31) * 2)) & 3ull); }
 
 __device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ void store_vec_nt(double* base, size_t item, size_t b, size_t ld, double v0, double v1) {
@@ -75,7 +80,10 @@ __device__ __forceinline__ void store_vec_nt(double* base, size_t item, size_t b
 // WAVES: waves of a workgroup (which always takes ASM_ROWS bus rows).  4: a wave walks four rows one after the other -- the throughput form; 16 (round 6, a handful of
 // scenarios): one row per wave -- a row is three dependent round trips (row header, Ybus entries, V / theta gathers), and with nothing else on the chip to hide them
 // four rows in sequence made the pass of a single instance 23 us long.
-template <int MP, bool JAC, int WAVES = ASM_WAVES>
+// LT = true: the bus types come from the lanes (a.lt) instead of rowtype / the host's existence bits -- a batch whose scenarios have types of their own
+// (PV -> PQ after reactive limits, a slack handed over); the 4 existence bits of each entry follow from the lane's types of row i and column j with
+// the host's rule (jg_nr_create), the pattern and the plan stay those of the handle.
+template <int MP, bool JAC, int WAVES = ASM_WAVES, bool LT = false>
 __global__ __launch_bounds__(64 * WAVES) void k_assemble(AsmArgs a) {
     __shared__ double red[2][WAVES][64];
     int grp, bx;
@@ -94,7 +102,9 @@ __global__ __launch_bounds__(64 * WAVES) void k_assemble(AsmArgs a) {
     for (int i = r0 + wave; i < r1; i += WAVES) {
         const int p0 = uniform(a.rowptr[i]), p1 = uniform(a.rowptr[i + 1]);
         const int tfull = (int)((unsigned)uniform(a.rowtype[i]));   // bus type | (pivot + 1) << 2 where this pass also finishes the plan's level 0
-        const int ti = tfull & 3, pre = tfull >> 2;
+        int ti = tfull & 3;
+        const int pre = tfull >> 2;
+        if constexpr (LT) ti = lane_type(a.lt[(size_t)(i >> 5) * ld + b], i);
         const double vi = a.vm[(size_t)i * ld + b];
         const double thi = a.va[(size_t)i * ld + b];
         const double pinj = a.p[(size_t)i * ld + b], qinj = a.q[(size_t)i * ld + b];   // issued early, used after the row
@@ -105,6 +115,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_assemble(AsmArgs a) {
         for (int pc = p0; pc < p1; pc += CH) {
             const int cnt = min(CH, p1 - pc);
             int cm[CH], de[CH]; double2 gb[CH]; double vv[CH], tt[CH];
+            unsigned long long lw[LT ? CH : 1];
 #pragma unroll
             for (int k = 0; k < CH; ++k) {                       // scalar loads of the whole chunk first ...
                 const int p = pc + (k < cnt ? k : 0);
@@ -117,13 +128,19 @@ __global__ __launch_bounds__(64 * WAVES) void k_assemble(AsmArgs a) {
                 const size_t j = (size_t)(cm[k] & 0xffffff);
                 vv[k] = a.vm[j * ld + b];
                 tt[k] = a.va[j * ld + b];
+                if constexpr (LT) lw[k] = a.lt[(j >> 5) * ld + b];
             }
 #pragma unroll
             for (int k = 0; k < CH; ++k) {
                 if (k >= cnt) break;
                 const int p = pc + k;
                 const int j = cm[k] & 0xffffff;
-                const int mk = cm[k] >> 24;                    // bit0 dP/dth, bit1 dP/dV, bit2 dQ/dth, bit3 dQ/dV exist
+                int mk = cm[k] >> 24;                          // bit0 dP/dth, bit1 dP/dV, bit2 dQ/dth, bit3 dQ/dV exist
+                if constexpr (LT) {                            // the host's rule (jg_nr_create) on the lane's types
+                    const int tj = lane_type(lw[k], j);
+                    const int rpm = ti != 3, rq = ti == 1, ct = tj != 3, cv = tj == 1;
+                    mk = (rpm & ct) | ((rpm & cv) << 1) | ((rq & ct) << 2) | ((rq & cv) << 3);
+                }
                 double g = gb[k].x, bb = gb[k].y;
 #pragma unroll
                 for (int m = 0; m < MP; ++m)
@@ -962,6 +979,15 @@ struct jg_nr {
     hipGraph_t graphA2 = nullptr, graphC = nullptr;
     hipGraphExec_t execA2 = nullptr, execC = nullptr;
     long long first_comp = 0, first_full = 0;         // runs whose first iteration went the one / the other way (jg_nr_first_iteration_counts)
+    // ---- bus types per scenario (jg_nr_set_bus_type, jg_nr_reactive_limit) ----
+    unsigned long long* d_lt = nullptr;               // [ceil(n / 32)][ld] lane words, 2 bits per bus; moves with the lanes (launch_compact)
+    signed char* d_flags_all = nullptr;               // [n] = 3: while types differ per lane every variable is updated (a masked one has an increment of exactly 0)
+    std::vector<unsigned char> lt_set;                // [batch] the scenario's types differ from the create-time ones
+    std::vector<unsigned char> dead;                  // [batch] the last jg_nr_reactive_limit left the scenario without a slack (status 5)
+    bool lt_on = false;                               // some scenario has types of its own: lane-typed assembly, all-variable update, lane words compacted
+    jg::QlimTables qt;                                // generator table and initial point (jg_nr_set_generators; jg_qlim.hpp)
+    int* d_skip = nullptr;                            // [ld] lanes jg_nr_reactive_limit leaves alone (no slack left)
+    double* d_shift = nullptr;                        // [ld] jg_nr_adjust_angle
 };
 
 // The base case of a screen: ONE factorisation of the Jacobian at the common start state and what the per-scenario corrections read (jg_comp.hpp).
@@ -1009,8 +1035,9 @@ void launch_assemble(jg_nr* h, const jg::GroupSel& sel = jg::GroupSel{}, bool ja
     const bool pre = jac && level0 && h->eng.plan->S.prefactor && h->d_rowtype_pre;
     AsmArgs a{h->d_rowptr, h->d_col, h->d_GB, pre ? h->d_rowtype_pre : h->d_rowtype, h->d_dst, h->d_vm, h->d_va, h->d_p, h->d_q,
               h->d_ppos, h->d_pdg, h->d_pdb, h->eng.X, h->d_F, h->d_part, pq_out, sel, fd_mode ? h->d_R : nullptr, fd_mode, h->n, h->ld, h->mp, h->nchunk, h->batch, only_if,
-              h->eng.W, h->eng.status};
+              h->eng.W, h->eng.status, h->lt_on ? h->d_lt : nullptr};
     if (jac && !only_if) h->level0_done = pre;
+    const bool lt = h->lt_on;                                     // scenarios with bus types of their own (jg_nr_set_bus_type): the lane-typed variant
     dim3 grid(jg::grid_blocks(h->ld / 64, h->nchunk)), block(64, ASM_WAVES);
     const bool single_env = jg::knob("SINGLE", 1) != 0;           // (read at every capture: bench.py holds the two forms against each other in one process)
     if (h->ld == 64 && h->batch == 1 && !fd_mode && !pq_out && !only_if && single_env) {      // ONE scenario: a quad of lanes per bus row (k_assemble1)
@@ -1033,7 +1060,8 @@ void launch_assemble(jg_nr* h, const jg::GroupSel& sel = jg::GroupSel{}, bool ja
     if (h->ld == 64 && h->batch <= 32 && !fd_mode && !pq_out) {      // a handful of scenarios: one row per wave (k_assemble: WAVES = 16); same arithmetic per row, same chunk maxima
         const bool w16 = h->nchunk <= 512;                          // grids whose workgroups are all resident at once: one row per wave; larger ones: two
         const dim3 wide(64, w16 ? 16 : 8);
-#define JG_ASM_WIDE(MPV, JACV) do { if (w16) hipLaunchKernelGGL((k_assemble<MPV, JACV, 16>), grid, wide, 0, h->stream, a); else hipLaunchKernelGGL((k_assemble<MPV, JACV, 8>), grid, wide, 0, h->stream, a); } while (0)
+#define JG_ASM_WIDE1(MPV, JACV, LTV) do { if (w16) hipLaunchKernelGGL((k_assemble<MPV, JACV, 16, LTV>), grid, wide, 0, h->stream, a); else hipLaunchKernelGGL((k_assemble<MPV, JACV, 8, LTV>), grid, wide, 0, h->stream, a); } while (0)
+#define JG_ASM_WIDE(MPV, JACV) do { if (lt) JG_ASM_WIDE1(MPV, JACV, true); else JG_ASM_WIDE1(MPV, JACV, false); } while (0)
         if (jac) {
             switch (h->mp) {
                 case 0: JG_ASM_WIDE(0, true); break;
@@ -1048,21 +1076,25 @@ void launch_assemble(jg_nr* h, const jg::GroupSel& sel = jg::GroupSel{}, bool ja
             }
         }
 #undef JG_ASM_WIDE
+#undef JG_ASM_WIDE1
         return;
     }
+#define JG_ASM(MPV, JACV) do { if (lt) hipLaunchKernelGGL((k_assemble<MPV, JACV, ASM_WAVES, true>), grid, block, 0, h->stream, a); \
+                               else hipLaunchKernelGGL((k_assemble<MPV, JACV>), grid, block, 0, h->stream, a); } while (0)
     if (jac) {
         switch (h->mp) {
-            case 0: hipLaunchKernelGGL((k_assemble<0, true>), grid, block, 0, h->stream, a); break;
-            case 4: hipLaunchKernelGGL((k_assemble<4, true>), grid, block, 0, h->stream, a); break;
-            default: hipLaunchKernelGGL((k_assemble<8, true>), grid, block, 0, h->stream, a); break;
+            case 0: JG_ASM(0, true); break;
+            case 4: JG_ASM(4, true); break;
+            default: JG_ASM(8, true); break;
         }
     } else {
         switch (h->mp) {
-            case 0: hipLaunchKernelGGL((k_assemble<0, false>), grid, block, 0, h->stream, a); break;
-            case 4: hipLaunchKernelGGL((k_assemble<4, false>), grid, block, 0, h->stream, a); break;
-            default: hipLaunchKernelGGL((k_assemble<8, false>), grid, block, 0, h->stream, a); break;
+            case 0: JG_ASM(0, false); break;
+            case 4: JG_ASM(4, false); break;
+            default: JG_ASM(8, false); break;
         }
     }
+#undef JG_ASM
 }
 
 // The verdict of a handle of ONE lane group in one launch (round 6): k_check's norms and loop control, then what k_compact comes to when there is nothing to pack --
@@ -1203,6 +1235,7 @@ void launch_compact(jg_nr* h, int restore, bool report = false) {
         add(h->d_vm, h->n, 1); add(h->d_va, h->n, 1); add(h->d_p, h->n, 1); add(h->d_q, h->n, 1);
         if (h->mp > 0) { add(h->d_pdg, h->mp, 1); add(h->d_pdb, h->mp, 1); }
         add(h->d_inc, h->n, 2);                    // a finished scenario keeps ITS last increment (method.increment) wherever its lane goes
+        if (h->lt_on) add((double*)h->d_lt, (h->n + 31) / 32, 1);      // the types of a scenario travel with it (8th and last slot)
         static const bool inplace_env = jg::knob("LANES_INPLACE", 1) != 0;
         if (h->ld <= LANES_INPLACE && inplace_env) {                      // one launch, in place (k_lanes_permute); JG_LANES_INPLACE=0: the two-pass move
             hipLaunchKernelGGL(k_lanes_permute, dim3((unsigned)std::min(max_rows, 2048), 1, (unsigned)na), dim3((unsigned)std::min(1024, h->ld)), 0, h->stream, ls, h->d_dest, h->d_cflags, h->ld);
@@ -1228,13 +1261,14 @@ void launch_compact(jg_nr* h, int restore, bool report = false) {
     permute(h->d_vm, h->n); permute(h->d_va, h->n); permute(h->d_p, h->n); permute(h->d_q, h->n);
     if (h->mp > 0) { permute(h->d_pdg, h->mp); permute(h->d_pdb, h->mp); }
     permute2(h->d_inc, h->n);
+    if (h->lt_on) permute((double*)h->d_lt, (h->n + 31) / 32);
 }
 
 // solve! numerics on the groups of `sel`: factorise the Jacobian that is in place, solve, update the state (active: nullable)
 int newton_step(jg_nr* h, const jg::GroupSel& sel, const int* active) {
     if (int rc = h->eng.factor(h->stream, nullptr, h->d_F, sel, h->level0_done)) return rc;
     if (!h->refine) {
-        jg::StateUpdate upd{h->d_va, h->d_vm, h->d_flags, active, -1.0};
+        jg::StateUpdate upd{h->d_va, h->d_vm, h->lt_on ? h->d_flags_all : h->d_flags, active, -1.0};
         return h->eng.backsolve(h->stream, h->d_inc, upd, sel);
     }
     // the plain solve goes to a scratch vector: method.increment (d_inc) is written for ACTIVE scenarios only, by k_refine_apply -- a
@@ -1422,7 +1456,7 @@ __global__ void k_cmp_injection(const double* p, const double* q, const double* 
 // Does the next run start with the compensated iteration?  (every condition the algebra of jg_comp.hpp rests on)
 int comp_ready(jg_nr* h, bool& ready) {
     ready = false;
-    if (!h->base || !h->first_mode || !h->start_is_base || h->refine || h->fast) return 0;
+    if (!h->base || !h->first_mode || !h->start_is_base || h->refine || h->fast || h->lt_on) return 0;   // (the base's factor has the create-time types)
     bool patched = false;
     for (unsigned char c : h->patch_state) { if (c == 2) return 0; patched |= c == 1; }
     if (patched) {                                               // an outage moves the mismatch of its two buses only if the injections are the base's
@@ -1437,6 +1471,58 @@ int comp_ready(jg_nr* h, bool& ready) {
     }
     if (int rc = build_comp_graphs(h)) return rc;
     ready = true;
+    return 0;
+}
+
+
+// ---- bus types per scenario (jg_nr_set_bus_type, jg_nr_reactive_limit) -------------------------------------------------------------------
+int lt_rows(const jg_nr* h) { return (h->n + 31) / 32; }
+
+// 2 bits per bus, 32 buses per word (row r holds buses 32 r .. 32 r + 31); a bus beyond n is 0
+void pack_types(const int8_t* type, int n, unsigned long long* words, int rows, size_t stride) {
+    for (int r = 0; r < rows; ++r) {
+        unsigned long long w = 0;
+        for (int q = 0; q < 32 && r * 32 + q < n; ++q) w |= (unsigned long long)(type[r * 32 + q] & 3) << (2 * q);
+        words[(size_t)r * stride] = w;
+    }
+}
+
+// the lane words exist (every lane: the create-time types) and so does the all-variable update flag array
+int ensure_lane_types(jg_nr* h) {
+    if (h->d_lt) return 0;
+    const int rows = lt_rows(h);
+    std::vector<unsigned long long> one(rows), all((size_t)rows * h->ld);
+    pack_types(h->type.data(), h->n, one.data(), rows, 1);
+    for (int r = 0; r < rows; ++r) for (int b = 0; b < h->ld; ++b) all[(size_t)r * h->ld + b] = one[r];
+    std::string err;
+    if (jg::upload(&h->d_lt, all, err, h->stream) || jg::upload(&h->d_flags_all, std::vector<signed char>(h->n, 3), err, h->stream)) return fail(2, err);
+    h->lt_set.assign(h->batch, 0);
+    h->dead.assign(h->batch, 0);
+    return 0;
+}
+
+// the assembly, the compaction and the state update are captured for one choice: a change of it drops the graphs
+void set_lane_types_on(jg_nr* h) {
+    bool on = false;
+    for (unsigned char c : h->lt_set) on |= c != 0;
+    if (on != h->lt_on) {
+        hipStreamSynchronize(h->stream);
+        drop_iteration_graphs(h);
+        drop_comp_graphs(h);
+    }
+    h->lt_on = on;
+}
+
+// a scenario that jg_nr_reactive_limit left without a slack reports status 5 (the reference's errorSlackDefinition) on the host and on the device
+int mark_dead(jg_nr* h, int32_t* status) {
+    if (h->dead.empty()) return 0;
+    const int five = 5;
+    for (int b = 0; b < h->batch; ++b) {
+        if (!h->dead[b]) continue;
+        if (status) status[b] = 5;
+        NR_HIP(hipMemcpyAsync(h->d_status + b, &five, sizeof(int), hipMemcpyHostToDevice, h->stream));
+    }
+    NR_HIP(hipStreamSynchronize(h->stream));
     return 0;
 }
 
@@ -1659,6 +1745,8 @@ void jg_nr_destroy(jg_nr* h) {
     hipFree(h->d_arena);                                         // V, theta, P, Q, patches, mismatch, increment, norms, lane bookkeeping: one allocation (jg_nr_create)
     hipFree(h->d_dst);
     hipFree(h->d_vm0); hipFree(h->d_va0);
+    hipFree(h->d_lt); hipFree(h->d_flags_all); hipFree(h->d_skip); hipFree(h->d_shift);
+    h->qt.destroy();
     if (h->h_counter) hipHostFree(h->h_counter);
     if (h->stream) hipStreamDestroy(h->stream);
     delete h;
@@ -1921,6 +2009,7 @@ int jg_nr_solve(jg_nr* h) {
 int jg_nr_set_refine(jg_nr* h, int mode) {
     if (!h || mode < 0 || mode > 1) return fail(1, "jg_nr_set_refine: bad argument");
     if (h->fast) return fail(1, "jg_nr_set_refine: fast Newton-Raphson solves with constant matrices");
+    if (mode && h->lt_on) return fail(1, "jg_nr_set_refine: scenarios have bus types of their own (jg_nr_set_bus_type / jg_nr_reactive_limit); the refinement residual reads the create-time types");
     if (int rc = set_device(h)) return rc;
     NR_HIP(hipStreamSynchronize(h->stream));
     if (mode && !h->d_R) {
@@ -2275,7 +2364,8 @@ int jg_nr_run(jg_nr* h, int64_t max_iter, double tol, int32_t* iters, int32_t* s
         if (int rc = run_start(h, max_iter)) return rc;                        // acPowerFlow.jl:1406: mismatch!, verdict (+ a compensated first iteration)
         if (int rc = run_loop(h, max_iter, 0)) return rc;
     }
-    return run_finish(h, iters, status);
+    if (int rc = run_finish(h, iters, status)) return rc;
+    return mark_dead(h, status);
 }
 
 int jg_nr_run_defer(jg_nr* h, int64_t max_iter, double tol, int64_t defer_at, int32_t* n_left) {
@@ -2293,11 +2383,13 @@ int jg_nr_run_defer(jg_nr* h, int64_t max_iter, double tol, int64_t defer_at, in
 int jg_nr_finish(jg_nr* h, int32_t* iters, int32_t* status) {
     if (!h || !h->paused) return fail(1, "jg_nr_finish: the handle is not paused (jg_nr_run_defer)");
     if (int rc = set_device(h)) return rc;
-    return run_finish(h, iters, status);
+    if (int rc = run_finish(h, iters, status)) return rc;
+    return mark_dead(h, status);
 }
 
 int jg_nr_move_lanes(jg_nr* dst, int64_t dst_lane0, jg_nr* src, int32_t* home, int32_t* count) {
     if (!dst || !src || dst == src || !home || !count || dst_lane0 < 0) return fail(1, "jg_nr_move_lanes: bad argument");
+    if (src->lt_on || dst->lt_on) return fail(1, "jg_nr_move_lanes: scenarios with bus types of their own (jg_nr_set_bus_type / jg_nr_reactive_limit) do not move between handles");
     if (!src->paused) return fail(1, "jg_nr_move_lanes: the source is not paused (jg_nr_run_defer)");
     if (dst->device != src->device || dst->n != src->n || dst->nnz != src->nnz || dst->mp != src->mp || dst->fast || src->fast)
         return fail(1, "jg_nr_move_lanes: the two handles must hold the same grid on the same device");
@@ -2376,6 +2468,7 @@ int jg_nr_pack_rows_device(jg_nr* h, double* dst_dev, int64_t lane0, int64_t cou
 
 int jg_nr_get_mismatch(jg_nr* h, double* mism) {
     if (!h || !mism) return fail(1, "jg_nr_get_mismatch: bad argument");
+    if (h->lt_on) return fail(1, "jg_nr_get_mismatch: scenarios have bus types of their own; the reference layout depends on the types");
     if (int rc = set_device(h)) return rc;
     if (h->f_stale) { launch_assemble(h, jg::GroupSel{}, false); NR_HIP(hipGetLastError()); h->f_stale = false; }
     NR_HIP(hipStreamSynchronize(h->stream));
@@ -2394,6 +2487,7 @@ int jg_nr_get_mismatch(jg_nr* h, double* mism) {
 
 int jg_nr_get_increment(jg_nr* h, double* incr) {
     if (!h || !incr) return fail(1, "jg_nr_get_increment: bad argument");
+    if (h->lt_on) return fail(1, "jg_nr_get_increment: scenarios have bus types of their own; the reference layout depends on the types");
     if (int rc = set_device(h)) return rc;
     NR_HIP(hipStreamSynchronize(h->stream));
     std::vector<double> t((size_t)h->n * 2 * h->batch);
@@ -2411,6 +2505,7 @@ int jg_nr_get_increment(jg_nr* h, double* incr) {
 
 int jg_nr_get_jacobian(jg_nr* h, double* nzval) {
     if (!h || !nzval) return fail(1, "jg_nr_get_jacobian: bad argument");
+    if (h->lt_on) return fail(1, "jg_nr_get_jacobian: scenarios have bus types of their own; the reference layout depends on the types");
     if (h->fast) return fail(1, "jg_nr_get_jacobian: this handle runs fast Newton-Raphson: the factor storage holds the factorised B', B'', assembling the full Jacobian there would destroy them");
     if (int rc = set_device(h)) return rc;
     if (!h->jac_valid) { launch_assemble(h); h->jac_valid = true; }      // Jacobian at the current state
@@ -2424,6 +2519,7 @@ int jg_nr_get_jacobian(jg_nr* h, double* nzval) {
 
 int jg_nr_get_maps(jg_nr* h, int64_t* pq, int64_t* pvpq, int64_t* pcount, int64_t* jcolptr, int64_t* jrowval) {
     if (!h) return fail(1, "jg_nr_get_maps: bad argument");
+    if (h->lt_on) return fail(1, "jg_nr_get_maps: scenarios have bus types of their own; the reference layout depends on the types");
     if (pq) std::memcpy(pq, h->pq.data(), h->pq.size() * 8);
     if (pvpq) std::memcpy(pvpq, h->pvpq.data(), h->pvpq.size() * 8);
     if (pcount) std::memcpy(pcount, h->pcount.data(), h->pcount.size() * 8);
@@ -2494,6 +2590,7 @@ static int fast_half(jg_nr* h, int pass) {
 
 int jg_nr_fast_setup(jg_nr* h, const double* bp, const double* bq) {
     if (!h || !bp || !bq) return fail(1, "jg_nr_fast_setup: bad argument");
+    if (h->lt_on) return fail(1, "jg_nr_fast_setup: scenarios have bus types of their own (jg_nr_set_bus_type); fast Newton-Raphson keeps the create-time types");
     if (int rc = set_device(h)) return rc;
     NR_HIP(hipStreamSynchronize(h->stream));
     // block (r, c) of the shared matrix = diag(B'[r,c], B''[r,c]); the caller pads slack / PV rows and columns with identity
@@ -2784,6 +2881,131 @@ int jg_nr_screen_rows_device(jg_nr* h, double* rec_dev, int64_t lane0, int64_t c
     hipLaunchKernelGGL(k_screen_rows, dim3((unsigned)((count * 10 + 255) / 256)), dim3(256), 0, h->stream, h->d_screc, h->d_itmp, rec_dev, (int)lane0, (int)count);
     NR_HIP(hipGetLastError());
     NR_HIP(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+
+// ---- bus types per scenario and reactiveLimit! on a batch (jg_qlim.hip) -------------------------------------------------------------------
+int jg_nr_set_bus_type(jg_nr* h, int64_t scenario0, int64_t count, const int8_t* type) {
+    if (!h || scenario0 < 0 || count < 0 || scenario0 + count > (int64_t)h->batch) return fail(1, "jg_nr_set_bus_type: bad argument");
+    if (h->fast) return fail(1, "jg_nr_set_bus_type: a fast Newton-Raphson handle keeps its create-time types");
+    if (h->batch < 2) return fail(1, "jg_nr_set_bus_type: a handle of one scenario keeps its create-time types (the single-instance path)");
+    if (h->refine) return fail(1, "jg_nr_set_bus_type: iterative refinement (jg_nr_set_refine) reads the create-time types");
+    if (h->paused) return fail(1, "jg_nr_set_bus_type: the handle is paused (jg_nr_run_defer)");
+    const int n = h->n;
+    if (type)
+        for (int64_t s = 0; s < count; ++s) {
+            int slacks = 0;
+            for (int i = 0; i < n; ++i) {
+                const int8_t t = type[s * n + i];
+                if (t < 1 || t > 3) return fail(1, "jg_nr_set_bus_type: a bus type is 1 (PQ), 2 (PV) or 3 (slack)");
+                slacks += t == 3;
+            }
+            if (slacks != 1) return fail(1, "jg_nr_set_bus_type: scenario " + std::to_string(scenario0 + s) + " does not have exactly one slack bus");
+        }
+    if (int rc = set_device(h)) return rc;
+    NR_HIP(hipStreamSynchronize(h->stream));
+    if (int rc = ensure_lane_types(h)) return rc;
+    if (count == 0) return 0;
+    const int rows = lt_rows(h);
+    std::vector<unsigned long long> w((size_t)rows * count);
+    for (int64_t s = 0; s < count; ++s) {
+        const int8_t* t = type ? type + s * n : h->type.data();
+        pack_types(t, n, w.data() + s, rows, (size_t)count);
+        h->lt_set[scenario0 + s] = type && std::memcmp(t, h->type.data(), (size_t)n) != 0;
+        h->dead[scenario0 + s] = 0;
+    }
+    NR_HIP(hipMemcpy2DAsync(h->d_lt + scenario0, (size_t)h->ld * 8, w.data(), (size_t)count * 8, (size_t)count * 8, (size_t)rows, hipMemcpyHostToDevice, h->stream));
+    NR_HIP(hipStreamSynchronize(h->stream));
+    h->start_is_base = false;                                    // the next run refactorises (the base's factor has the create-time types)
+    h->jac_valid = false;
+    set_lane_types_on(h);
+    return 0;
+}
+
+int jg_nr_get_bus_type(jg_nr* h, int8_t* type, int64_t* slack) {
+    if (!h) return fail(1, "jg_nr_get_bus_type: bad argument");
+    if (int rc = set_device(h)) return rc;
+    const int n = h->n, rows = lt_rows(h);
+    std::vector<unsigned long long> w;
+    if (h->d_lt) {
+        w.resize((size_t)rows * h->ld);
+        NR_HIP(jg::sync_copy(w.data(), h->d_lt, w.size() * 8, hipMemcpyDeviceToHost, h->stream));
+    }
+    for (int b = 0; b < h->batch; ++b) {
+        int64_t sl = 0;
+        for (int i = 0; i < n; ++i) {
+            const int t = h->d_lt ? (int)((w[(size_t)(i >> 5) * h->ld + b] >> ((i & 31) * 2)) & 3) : h->type[i];
+            if (type) type[(size_t)b * n + i] = (int8_t)t;
+            if (t == 3 && sl == 0) sl = i + 1;
+        }
+        if (slack) slack[b] = sl;
+    }
+    return 0;
+}
+
+int jg_nr_set_generators(jg_nr* h, int64_t ng, const int64_t* bus, const int8_t* status, const double* pg, const double* qmin, const double* qmax,
+                         const double* vg, const double* bus_vm, const double* bus_va, const double* pd, const double* qd, double base_mva) {
+    if (!h || ng < 0 || (ng > 0 && (!bus || !status || !pg || !qmin || !qmax || !vg)) || !bus_vm || !bus_va || !pd || !qd || !(base_mva > 0.0))
+        return fail(1, "jg_nr_set_generators: bad argument");
+    if (h->fast) return fail(1, "jg_nr_set_generators: reactive limits are not available for fast Newton-Raphson");
+    if (int rc = set_device(h)) return rc;
+    NR_HIP(hipStreamSynchronize(h->stream));
+    std::string msg;
+    if (int rc = jg::qlim_setup(h->qt, h->n, h->ld, (int)ng, bus, status, pg, qmin, qmax, vg, bus_vm, bus_va, pd, qd, base_mva, h->stream, msg)) return fail(rc, msg);
+    return 0;
+}
+
+int jg_nr_reactive_limit(jg_nr* h, int flags, int8_t* violate, int32_t* count) {
+    if (!h || flags < 0 || flags > 1) return fail(1, "jg_nr_reactive_limit: bad argument (flags: 0 or 1 = restart the scenarios with a violation)");
+    if (h->fast) return fail(1, "jg_nr_reactive_limit: reactive limits are not available for fast Newton-Raphson");
+    if (h->batch < 2) return fail(1, "jg_nr_reactive_limit: a handle of one scenario (the single-instance path keeps its create-time types)");
+    if (h->refine) return fail(1, "jg_nr_reactive_limit: iterative refinement (jg_nr_set_refine) reads the create-time types");
+    if (h->paused) return fail(1, "jg_nr_reactive_limit: the handle is paused (jg_nr_run_defer)");
+    if (!h->qt.ready()) return fail(1, "jg_nr_reactive_limit: no generator table (jg_nr_set_generators)");
+    if (int rc = set_device(h)) return rc;
+    NR_HIP(hipStreamSynchronize(h->stream));
+    if (int rc = ensure_lane_types(h)) return rc;
+    if (!h->d_skip) NR_HIP(hipMalloc((void**)&h->d_skip, (size_t)h->ld * 4));
+    std::vector<int> skip(h->ld, 0);
+    for (int b = 0; b < h->batch; ++b) skip[b] = h->dead[b];
+    NR_HIP(hipMemcpyAsync(h->d_skip, skip.data(), skip.size() * 4, hipMemcpyHostToDevice, h->stream));
+    // P_i, Q_i of every lane at its current state (the mismatch pass of its own types) into the factor storage, which holds nothing live between runs
+    launch_assemble(h, jg::GroupSel{}, false, h->eng.X);
+    h->jac_valid = false;
+    h->f_stale = true;                                           // injections, types and (restart) state change below: method.mismatch is re-assembled on demand
+    jg::qlim_launch(h->qt, h->eng.X, h->d_lt, h->d_p, h->d_q, h->d_vm, h->d_va, h->d_skip, h->batch, h->ld, (flags & 1) != 0, h->stream);
+    NR_HIP(hipGetLastError());
+    std::vector<int> cnt(h->ld), dead(h->ld);
+    NR_HIP(jg::sync_copy(cnt.data(), h->qt.cnt, (size_t)h->ld * 4, hipMemcpyDeviceToHost, h->stream));
+    NR_HIP(jg::sync_copy(dead.data(), h->qt.dead, (size_t)h->ld * 4, hipMemcpyDeviceToHost, h->stream));
+    if (violate) {
+        const int ng = h->qt.ng;
+        std::vector<signed char> v((size_t)std::max(ng, 1) * h->ld);
+        NR_HIP(jg::sync_copy(v.data(), h->qt.VO, v.size(), hipMemcpyDeviceToHost, h->stream));
+        for (int b = 0; b < h->batch; ++b)
+            for (int k = 0; k < ng; ++k) violate[(size_t)b * ng + k] = v[(size_t)k * h->ld + b];
+    }
+    for (int b = 0; b < h->batch; ++b) {
+        if (count) count[b] = cnt[b];
+        if (dead[b]) h->dead[b] = 1;
+        else if (cnt[b] > 0) h->lt_set[b] = 1;
+    }
+    h->start_is_base = false;
+    h->inj_checked = false;
+    set_lane_types_on(h);
+    return 0;
+}
+
+int jg_nr_adjust_angle(jg_nr* h, int64_t bus, double angle) {
+    if (!h || bus < 1 || bus > h->n) return fail(1, "jg_nr_adjust_angle: bad argument (bus: 1-based index)");
+    if (int rc = set_device(h)) return rc;
+    if (!h->d_shift) NR_HIP(hipMalloc((void**)&h->d_shift, (size_t)h->ld * 8));
+    jg::adjust_angle_launch(h->d_shift, h->d_va, h->n, h->ld, h->batch, (int)bus - 1, angle, h->stream);
+    NR_HIP(hipGetLastError());
+    NR_HIP(hipStreamSynchronize(h->stream));
+    h->jac_valid = false;
+    h->start_is_base = false;
     return 0;
 }
 

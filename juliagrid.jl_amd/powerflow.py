@@ -70,6 +70,7 @@ class AcPowerFlow:
         self.batch = int(batch)
         self._device, self._max_patch = int(device), int(max_patch)
         self._injection = None                                           # per-scenario injections set by the caller (kept for a rebuild)
+        self._lane_types = False                                         # some scenario may have bus types of its own (setBusType_ / reactiveLimit_)
         self._h = None
         self._create()
         self.voltage = NS(magnitude=None, angle=None)
@@ -739,6 +740,12 @@ def power_(an: AcPowerFlow):
     the Ybus row walk (injections) and the branch formulas run on the device, the O(n) bus / generator bookkeeping
     (shunt :884-889, supply :53-61, generators :84-166) on the host.  Arrays are [batch, ...] (1-D for batch 1)."""
     system, bus, gen = an.system, an.system.bus, an.system.generator
+    if an.batch > 1 and getattr(an, "_lane_types", False):
+        typ_lanes, _ = busType(an)
+        if np.any(typ_lanes != bus.layout.type[None, :]):
+            raise ValueError("power_: scenarios of this analysis have bus types of their own (setBusType_ / reactiveLimit_); the supply and generator "
+                             "powers follow the system's types -- return them with setBusType_(an, None) first")
+        an._lane_types = False
     L = _lib.lib()
     if not an._branches_on_device:
         _upload_branches(an)
@@ -868,7 +875,7 @@ def reactiveLimit_(an: AcPowerFlow):
     hands over to the first generator bus.  Mutates `an.system` like the reference; returns the violate vector.
     The caller then builds a new analysis (`newtonRaphson(system)`) and solves again."""
     if an.batch != 1:
-        raise ValueError("reactiveLimit_ works on a single-scenario analysis")
+        return _reactive_limit_batch(an)
     system, bus, gen = an.system, an.system.bus, an.system.generator
     power_(an)
     gp, gq = an.power.generator.active, an.power.generator.reactive
@@ -918,3 +925,89 @@ def adjustAngle_(an: AcPowerFlow, slack: int):
     carries the angle the PowerSystem container holds for it."""
     shift = an.system.bus.voltage.angle[int(slack) - 1] - np.atleast_2d(an.voltage.angle)[:, int(slack) - 1]
     an.voltage.angle = an._shape(np.atleast_2d(an.voltage.angle) + shift[:, None])
+
+
+# ---- bus types per scenario and reactiveLimit! on a batch (jgrid.h: jg_nr_set_bus_type, jg_nr_reactive_limit) --------------------------------
+def _upload_generators(an: AcPowerFlow):
+    """The generator table, demand and initial point of the system as they are now (jg_nr_set_generators); sent again only when they changed."""
+    system, bus, gen = an.system, an.system.bus, an.system.generator
+    arrays = (np.ascontiguousarray(gen.layout.bus, dtype=np.int64), np.ascontiguousarray(gen.layout.status, dtype=np.int8),
+              np.ascontiguousarray(gen.output.active, dtype=np.float64), np.ascontiguousarray(gen.capability.minReactive, dtype=np.float64),
+              np.ascontiguousarray(gen.capability.maxReactive, dtype=np.float64), np.ascontiguousarray(gen.voltage.magnitude, dtype=np.float64),
+              np.ascontiguousarray(bus.voltage.magnitude, dtype=np.float64), np.ascontiguousarray(bus.voltage.angle, dtype=np.float64),
+              np.ascontiguousarray(bus.demand.active, dtype=np.float64), np.ascontiguousarray(bus.demand.reactive, dtype=np.float64))
+    base_mva = float(system.base.power) * 1e-6
+    key = (base_mva,) + tuple(x.tobytes() for x in arrays)
+    if getattr(an, "_qlim_key", None) == key:
+        return
+    _lib.check(_lib.lib().jg_nr_set_generators(an._h, gen.number, *arrays, base_mva))
+    an._qlim_key = key
+
+
+def _reactive_limit_batch(an: AcPowerFlow, fetch: bool = True):
+    """reactiveLimit! for every scenario of a batch, on the device: each scenario's generator outputs at its own state, its violating PV / slack buses
+    turned PQ with Q at the limit, its slack handed over in the reference's loop order -- kept in the handle as per-scenario bus types and injections
+    (`an.system` is not touched).  The scenarios with a violation start again from the system's initial point under their new types (what the
+    reference's user gets from newtonRaphson(system)); the others keep their converged state.  Returns violate [batch, ng]; a scenario left without a
+    slack reports status 5 from the next powerFlow_ on."""
+    if getattr(an.method, "fast", False):
+        raise ValueError("reactiveLimit_: fast Newton-Raphson keeps its bus types (use newtonRaphson)")
+    _upload_generators(an)
+    violate = np.zeros((an.batch, an.system.generator.number), dtype=np.int8)
+    count = np.zeros(an.batch, dtype=np.int32)
+    _lib.check(_lib.lib().jg_nr_reactive_limit(an._h, 1, violate.ctypes.data, count.ctypes.data))
+    an.method.limitCount = count
+    an._lane_types = an._lane_types or bool(np.any(count > 0))
+    if fetch:
+        an._pull_voltage()
+    return violate.astype(np.int64)
+
+
+def powerFlowLimits_(an: AcPowerFlow, rounds: int, iteration: int = 20, tolerance: float = 1e-8, fetch: bool = True):
+    """powerFlow! followed by up to `rounds` rounds of reactiveLimit! + powerFlow! on every scenario of a batch (test/powerFlow/limits.jl: solve,
+    reactiveLimit!, newtonRaphson(system), solve again); a round in which no scenario violates ends the loop.  method.iteration is the sum over
+    the solves per scenario, status that of the last solve (5: no slack bus left)."""
+    powerFlow_(an, iteration=iteration, tolerance=tolerance, fetch=False)
+    total = np.array(an.method.iteration, dtype=np.int64)
+    for _ in range(int(rounds)):
+        _reactive_limit_batch(an, fetch=False)
+        if not np.any(an.method.limitCount > 0):
+            break
+        powerFlow_(an, iteration=iteration, tolerance=tolerance, fetch=False)
+        total += an.method.iteration
+    an.method.iteration = total.astype(np.int32)
+    if fetch:
+        an._pull_voltage()
+
+
+def setBusType_(an: AcPowerFlow, type=None, scenarios=None):
+    """Bus types of scenarios of a batched analysis (1 PQ, 2 PV, 3 slack; exactly one slack each): `type` [n] for all of `scenarios` or
+    [len(scenarios), n]; None: the types the analysis was built with.  scenarios: 0-based indices (default: all)."""
+    sc = np.arange(an.batch) if scenarios is None else np.atleast_1d(np.asarray(scenarios, dtype=np.int64))
+    if sc.size and (sc.min() < 0 or sc.max() >= an.batch):
+        raise IndexError("setBusType_: scenario out of range")
+    tp = None
+    if type is not None:
+        tp = np.asarray(type, dtype=np.int8)
+        tp = np.ascontiguousarray(np.broadcast_to(tp, (sc.size, an.system.bus.number)) if tp.ndim == 1 else tp)
+        if tp.shape != (sc.size, an.system.bus.number):
+            raise ValueError("setBusType_: type must be [n] or [len(scenarios), n]")
+    L = _lib.lib()
+    if tp is not None:
+        an._lane_types = True
+    k = 0
+    while k < sc.size:                                           # consecutive scenarios in one call
+        e = k + 1
+        while e < sc.size and sc[e] == sc[e - 1] + 1:
+            e += 1
+        ptr = None if tp is None else np.ascontiguousarray(tp[k:e]).ctypes.data
+        _lib.check(L.jg_nr_set_bus_type(an._h, int(sc[k]), e - k, ptr))
+        k = e
+
+
+def busType(an: AcPowerFlow):
+    """(type [batch, n], slack [batch] 1-based) of every scenario of the analysis."""
+    t = np.zeros((an.batch, an.system.bus.number), dtype=np.int8)
+    sl = np.zeros(an.batch, dtype=np.int64)
+    _lib.check(_lib.lib().jg_nr_get_bus_type(an._h, t, sl))
+    return t, sl
