@@ -1187,9 +1187,128 @@ function timeKernel(analysis::HipStateEstimation, kernel::Int, reps::Int = 10)
     return ms[]
 end
 
+# ---- DC power flow and the batched DC N-1 screen (jgrid.h: jg_dc_*; csrc/jg_dc.hip) ------------------------------------------------------
+# dcPowerFlow / solve! / power!(::DcPowerFlow) (src/powerFlow/dcPowerFlow.jl:42-134, src/postprocessing/dcAnalysis.jl:27-75) for `batch` scenarios of one
+# grid on ONE factor of the base nodal matrix: an outage of a scenario (updateBranch!(analysis; label, status = 0)) is a rank-1 correction on that
+# factor, never a refactorisation.  The C handle is an Int64 token.
+"""
+    DcPowerFlowBatch(system; batch = 1, device = 0)
+
+Factorises system.model.dc.nodalMatrix (slack row and column removed, dcPowerFlow.jl:63-80) once on the device and uploads the branch table.
+`solve!(b)` then gives `b.angle` [bus, batch] and `b.status` (0, or 3 where the outaged branch is a bridge: its angles are NaN).
+"""
+mutable struct DcPowerFlowBatch
+    token::Int64
+    system::PowerSystem
+    batch::Int64
+    angle::Matrix{Float64}
+    status::Vector{Int32}
+    rhs::Vector{Float64}                              # the base right-hand side the library holds (empty: none yet)
+    injections::Vector{Tuple{Int64, Matrix{Float64}}}   # (lane0, [bus, count] right-hand sides) in the order they were set: a later one wins where lanes overlap
+end
+function DcPowerFlowBatch(system::PowerSystem; batch::Int64 = 1, device::Int64 = 0)
+    if isempty(system.model.dc.nodalMatrix)
+        dcModel!(system)
+    end
+    B = system.model.dc.nodalMatrix
+    slack = system.bus.layout.slack
+    token = Ref{Int64}(0)
+    check(ccall((:jg_dc_create, lib), Cint, (Ref{Int64}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Int64, Float64, Int64, Cint),
+        token, system.bus.number, B.colptr, B.rowval, B.nzval, slack, system.bus.voltage.angle[slack], batch, device))
+    b = DcPowerFlowBatch(token[], system, batch, zeros(system.bus.number, batch), zeros(Int32, batch), Float64[], Tuple{Int64, Matrix{Float64}}[])
+    finalizer(x -> (x.token != 0 && ccall((:jg_dc_destroy, lib), Cvoid, (Int64,), x.token); x.token = 0), b)
+    br = system.branch
+    check(ccall((:jg_dc_set_branches, lib), Cint, (Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}),
+        b.token, br.number, br.layout.from, br.layout.to, system.model.dc.admittance, br.parameter.shiftAngle))
+    return b
+end
+"{n, batch, ld, branches, factor entries, factorisation levels, forward levels, backward levels, launches of a sweep pair, padded sweep terms}"
+function dims(b::DcPowerFlowBatch)
+    d = zeros(Int64, 10)
+    check(ccall((:jg_dc_dims, lib), Cint, (Int64, Ptr{Int64}), b.token, d))
+    return d
+end
+"scenario `lane0 + s` (0-based lanes) loses branch `branches[s]` (index, 0 = no outage)"
+setOutages!(b::DcPowerFlowBatch, branches::Vector{Int64}; lane0::Int64 = 0) =
+    check(ccall((:jg_dc_set_outages, lib), Cint, (Int64, Int64, Int64, Ptr{Int64}), b.token, lane0, length(branches), branches))
+baseRhs(b::DcPowerFlowBatch) = b.system.bus.supply.active .- b.system.bus.demand.active .- b.system.bus.shunt.conductance .- b.system.model.dc.shiftPower
+# jg_dc_set_rhs drops the per-scenario injections the library holds (jgrid.h), so the base right-hand side goes up only when it CHANGED and the
+# injections kept in b.injections follow it again (what dcpowerflow.py: solve_ / _upload_injections do)
+function uploadRhs!(b::DcPowerFlowBatch)
+    rhs = baseRhs(b)
+    if rhs != b.rhs
+        check(ccall((:jg_dc_set_rhs, lib), Cint, (Int64, Ptr{Float64}), b.token, rhs))
+        b.rhs = rhs
+        for (lane0, own) in b.injections
+            check(ccall((:jg_dc_set_injections, lib), Cint, (Int64, Int64, Int64, Ptr{Float64}), b.token, lane0, size(own, 2), own))
+        end
+    end
+    return nothing
+end
+"""
+    setInjections!(b, rhs; lane0 = 0)
+
+Lanes lane0 .. lane0 + size(rhs, 2) - 1 (0-based) get right-hand sides of their own: a [bus, count] matrix of supply - demand - shunt conductance -
+shiftPower per scenario.  They hold for every later `solve!` of the batch, also after the system's own right-hand side changed.
+"""
+function setInjections!(b::DcPowerFlowBatch, rhs::Matrix{Float64}; lane0::Int64 = 0)
+    push!(b.injections, (lane0, copy(rhs)))
+    uploadRhs!(b)                                     # the base first (the library asks for it), with every kept injection if it changed
+    check(ccall((:jg_dc_set_injections, lib), Cint, (Int64, Int64, Int64, Ptr{Float64}), b.token, lane0, size(rhs, 2), rhs))
+    return nothing
+end
+"solve!(analysis) for every scenario (dcPowerFlow.jl:63-101)"
+function JuliaGrid.solve!(b::DcPowerFlowBatch)
+    uploadRhs!(b)
+    check(ccall((:jg_dc_solve, lib), Cint, (Int64,), b.token))
+    check(ccall((:jg_dc_get_angle, lib), Cint, (Int64, Ptr{Float64}, Ptr{Int32}), b.token, b.angle, b.status))
+    return nothing
+end
+"active power at the from-bus end of every branch, [branch, batch] (dcAnalysis.jl:41-48); to = -from; 0 on a lane's outaged branch"
+function fromPower(b::DcPowerFlowBatch)
+    from = Matrix{Float64}(undef, b.system.branch.number, b.batch)
+    check(ccall((:jg_dc_get_flows, lib), Cint, (Int64, Ptr{Float64}), b.token, from))
+    return from
+end
+"""
+    screenSummary(b::DcPowerFlowBatch; rating = nothing, record = nothing) -> Matrix [5, batch]
+
+Per scenario: worst |from| / rating and its branch (0: none rated), largest |from| and its branch, status.  `record`: a DEVICE pointer for
+`5 * batch` doubles instead (the operand of `allgatherDevice`).
+"""
+function screenSummary(b::DcPowerFlowBatch; rating::Union{Nothing, Vector{Float64}} = nothing, record::Union{Nothing, Ptr{Float64}} = nothing)
+    if rating === nothing
+        check(ccall((:jg_dc_set_rating, lib), Cint, (Int64, Ptr{Float64}), b.token, C_NULL))
+    else
+        check(ccall((:jg_dc_set_rating, lib), Cint, (Int64, Ptr{Float64}), b.token, rating))
+    end
+    if record !== nothing
+        check(ccall((:jg_dc_screen_device, lib), Cint, (Int64, Ptr{Float64}), b.token, record))
+        return nothing
+    end
+    rec = Matrix{Float64}(undef, 5, b.batch)
+    check(ccall((:jg_dc_screen, lib), Cint, (Int64, Ptr{Float64}), b.token, rec))
+    return rec
+end
+"angle | status per scenario, `(bus + 1) * batch` doubles, into DEVICE memory of the caller (the operand of `allgatherDevice`)"
+packResults!(b::DcPowerFlowBatch, dst::Ptr{Float64}) = check(ccall((:jg_dc_pack_results_device, lib), Cint, (Int64, Ptr{Float64}), b.token, dst))
+"(device address of the batch-minor angles, their leading dimension, device address of the Int32 status)"
+function angleDevice(b::DcPowerFlowBatch)
+    info = zeros(Int64, 3)
+    check(ccall((:jg_dc_angle_device, lib), Cint, (Int64, Ptr{Int64}), b.token, info))
+    return info
+end
+"milliseconds of `reps` runs (HIP events): 0 the whole chain of a batch, 1 the sweep pair, 2 the combine, 3 flows + summary"
+function timeKernel(b::DcPowerFlowBatch, kernel::Int, reps::Int = 20)
+    ms = zeros(Float64, reps)
+    check(ccall((:jg_dc_time_kernel, lib), Cint, (Int64, Cint, Cint, Ptr{Float64}), b.token, kernel, reps, ms))
+    return ms
+end
+
 export HIP, HIPOrthogonal, NewtonRaphsonBatch, BaseCase, baseInfo, baseInverseOnPattern, attach!, startFromBase!, firstIteration!, firstIterationCounts, setOutages!, shareDevice!, branchQuantities, screenSummary, powerFlowDefer!, moveLanes!, finish!, resume!, jacobian!,
        largestNormalizedResidual, normalizedResiduals, commUniqueId, Comm, shard, contingencyAnalysis, clearPlanCache,
        deviceCount, dims, setRefinement!, deviceMaps, setOutage!, snapshotVoltage!, restoreVoltage!, iterations, voltageDevice!, packResults!, packRows!,
-       allgatherDevice, commRank, commWorld, timeKernel, setBusType!, busType, GaussNewtonBatch, setRealisations!, monteCarloEstimation, fastPatch!, setReadings!, drawNoise!, measurementDevice
+       allgatherDevice, commRank, commWorld, timeKernel, setBusType!, busType, GaussNewtonBatch, setRealisations!, monteCarloEstimation, fastPatch!, setReadings!, drawNoise!, measurementDevice,
+       DcPowerFlowBatch, setInjections!, fromPower, angleDevice
 
 end # module

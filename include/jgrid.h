@@ -450,6 +450,71 @@ int jg_nr_allgather_results(jg_nr* h, jg_comm* c, double* dst_dev);
 int jg_gn_allgather_results(jg_gn* h, jg_comm* c, double* dst_dev);
 
 /* ---------------------------------------------------------------------------------------------
+ * DC power flow and the batched DC N-1 screen (csrc/jg_dc.hip)
+ * ------------------------------------------------------------------------------------------- */
+
+/*
+ * The DC handle is an int64 TOKEN (0 = none), not a pointer to an opaque struct: it crosses every binding as a plain integer.
+ *
+ * dcPowerFlow(system)  -- src/powerFlow/dcPowerFlow.jl:42-61 with the factorisation of the first solve! (:63-101): the slack row and column leave
+ * system.model.dc.nodalMatrix (dcModel!, src/powerSystem/model.jl:161-209), the slack diagonal becomes 1, and the matrix is factorised ONCE on the
+ * device (scalar LU on the elimination order and dependency levels of the bus graph, no pivoting); every later solve reuses that factor.
+ *   n               number of buses
+ *   colptr,rowval   pattern of dc.nodalMatrix (1-based CSC, rows sorted: SparseMatrixCSC), structurally symmetric with a full diagonal
+ *   nzval           its values, stored zeros of out-of-service branches included
+ *   slack           bus.layout.slack (1-based);  slack_angle = bus.voltage.angle[slack], added to every angle (dcPowerFlow.jl:94-99)
+ *   batch           scenarios resident on the device (>= 1; kept batch-minor with a leading dimension of batch rounded up to 64)
+ * Return code 3: zero / non-finite pivot.
+ * jg_dc_dims: {n, batch, ld, branches, factor entries, factorisation levels, forward levels, backward levels, launches of a sweep pair, padded sweep terms}.
+ */
+int jg_dc_create(int64_t* h, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, int64_t slack,
+                 double slack_angle, int64_t batch, int device);
+void jg_dc_destroy(int64_t h);
+int jg_dc_dims(int64_t h, int64_t* dims10);
+/*
+ * The right-hand side of solve! (dcPowerFlow.jl:82-92): b = supply.active - demand.active - shunt.conductance - shiftPower, [n] (the slack's
+ * entry is ignored).  jg_dc_set_rhs is the base case of every lane and drops earlier per-scenario injections.
+ * jg_dc_set_injections: lanes lane0 .. lane0 + count - 1 get right-hand sides of their own, rhs [count][n] (the user loop updateBus!(analysis; active) /
+ * updateGenerator!(analysis; active) -> solve!, src/powerSystem/bus.jl:300-311, generator.jl:382-395, over Monte-Carlo draws).  Only the 64-lane groups
+ * that hold such a lane pay a second sweep pair.
+ */
+int jg_dc_set_rhs(int64_t h, const double* rhs);
+int jg_dc_set_injections(int64_t h, int64_t lane0, int64_t count, const double* rhs);
+/*
+ * The branch table, once per handle: from / to (1-based bus indices, branch.layout.from / to), dc.admittance (0 for a branch out of service in the base,
+ * model.jl:176-183), parameter.shiftAngle.  Needed by outages, flows and the screen.  jg_dc_set_rating: the [branches] ratings the screen divides |from| by
+ * (per unit of active power; <= 0: the branch is not rated; NULL: none is).
+ */
+int jg_dc_set_branches(int64_t h, int64_t nbr, const int64_t* from, const int64_t* to, const double* admittance, const double* shift_angle);
+int jg_dc_set_rating(int64_t h, const double* rating);
+/*
+ * updateBranch!(analysis; label, status = 0) per scenario (src/powerSystem/branch.jl:453-459 with dcNodalUpdate! / dcShiftUpdate! / dcAdmittanceUpdate!,
+ * model.jl:212-262): lane lane0 + s loses branch branch[s] (1-based, 0 = no outage).  The matrix is NOT rebuilt: the lane's solution is the base
+ * solution plus a rank-1 correction on the shared factor (csrc/jg_dc.hpp).
+ */
+int jg_dc_set_outages(int64_t h, int64_t lane0, int64_t count, const int64_t* branch);
+/*
+ * solve!(analysis) for every lane (dcPowerFlow.jl:63-101): the base solution if the right-hand side changed, one sweep pair for the lanes' outages,
+ * the rank-1 combine.  status per scenario: 0 solved, 3 the outaged branch is a bridge (the outage islands the grid; its angles are NaN).
+ *   jg_dc_get_angle     theta [batch][n] = analysis.voltage.angle, status [batch] (either may be NULL)
+ *   jg_dc_angle_device  info[0] = device address of the angles, batch-minor [n][info[1]], info[2] = device address of the int32 status [info[1]]
+ *   jg_dc_get_flows     power!(analysis) branch part (src/postprocessing/dcAnalysis.jl:41-48): from [batch][branches], to = -from; the outaged branch of a lane carries 0
+ *   jg_dc_screen        rec [batch][5]: worst |from| / rating and its branch (1-based, 0 = none rated), largest |from| and its branch, status; ties go to
+ *                       the lowest branch index.  jg_dc_screen_device: the same record into device memory of the caller (an operand of jg_comm_allgather_device)
+ *   jg_dc_pack_results_device   angle | status, [batch][n + 1] doubles, into device memory of the caller (likewise)
+ *   jg_dc_time_kernel   milliseconds (HIP events on the handle's stream) of `reps` runs of: 0 the whole chain of a batch (sweeps, combine, flows + summary),
+ *                       1 the sweep pair, 2 the combine, 3 flows + summary; ms [reps]
+ */
+int jg_dc_solve(int64_t h);
+int jg_dc_get_angle(int64_t h, double* theta, int32_t* status);
+int jg_dc_angle_device(int64_t h, int64_t* info3);
+int jg_dc_get_flows(int64_t h, double* from);
+int jg_dc_screen(int64_t h, double* rec);
+int jg_dc_screen_device(int64_t h, double* rec_dev);
+int jg_dc_pack_results_device(int64_t h, double* dst_dev);
+int jg_dc_time_kernel(int64_t h, int kernel, int reps, double* ms);
+
+/* ---------------------------------------------------------------------------------------------
  * Symbolic analysis only (no device needed): the static schedule that replaces the symbolic half
  * of `lu`/`klu` (src/backend/utility.jl:470-476, 486-492).  Used by the CPU test-suite to replay
  * and race-check the schedule.  pattern: 0-based int32 block CSR, structurally symmetric, full

@@ -3,7 +3,8 @@
 Host-side mirror of the JuliaGrid interface for the hot path only; all numerics run
 in libjgrid_hip.so (hand-written HIP for gfx950) through the C ABI of include/jgrid.h.
 """
-from .system import PowerSystem, CscMatrix, powerSystem, acModel_          # noqa: F401
+from .system import PowerSystem, CscMatrix, powerSystem, acModel_, dcModel_          # noqa: F401
+from .dcpowerflow import DcPowerFlow, dcPowerFlow          # noqa: F401
 from .system import addBranch_ as addBranchSystem_, dropZeros_ as dropZerosSystem_   # noqa: F401
 from .system import (updateBranch_ as updateBranchSystem_, updateBus_ as updateBusSystem_,   # noqa: F401
                      updateGenerator_ as updateGeneratorSystem_)
@@ -19,7 +20,7 @@ from .stateestimation import (WlsMethod, Normal, LU, KLU, QR, LDLt, LL, Orthogon
                               updateVoltmeter_, updateAmmeter_, updateWattmeter_, updateVarmeter_, updatePmu_)
 from .montecarlo import MonteCarloPipeline, gatherEstimates, gatherEstimatesDevice, unpackEstimates   # noqa: F401
 from .synthetic import pegaseShaped, case9241synth                          # noqa: F401
-from . import powerflow, stateestimation   # noqa: F401
+from . import powerflow, stateestimation, dcpowerflow   # noqa: F401
 from . import _lib                                                           # noqa: F401
 
 __all__ = [
@@ -31,5 +32,5 @@ __all__ = [
     "outagePatch", "fastOutagePatch", "initializeACPowerFlow", "bridges", "outageList", "shard", "deviceBatching", "recommendedLanes", "contingencyAnalysis", "gatherResults", "gatherResultsDevice", "unpackResults",
     "WlsMethod", "Normal", "LU", "KLU", "QR", "LDLt", "LL", "Orthogonal", "PetersWilkinson",
     "addBranch_", "dropZeros_", "addBranchSystem_", "dropZerosSystem_", "pegaseShaped", "case9241synth", "ContingencyPipeline", "MonteCarloPipeline", "gatherEstimates", "gatherEstimatesDevice", "unpackEstimates", "setOutages_", "power_", "current_", "screenSummary_", "reactiveLimit_", "adjustAngle_",
-    "BaseCase", "startFromBase_", "setFirstIteration_", "firstIterationCounts", "setBusType_", "busType", "powerFlowLimits_",
+    "dcModel_", "DcPowerFlow", "dcPowerFlow", "BaseCase", "startFromBase_", "setFirstIteration_", "firstIterationCounts", "setBusType_", "busType", "powerFlowLimits_",
 ]

@@ -137,6 +137,22 @@ def lib():
         "jg_nr_start_from_base": [VP],
         "jg_nr_set_first_iteration": [VP, C.c_int],
         "jg_nr_first_iteration_counts": [VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
+        # DC power flow: the handle is an int64 token
+        "jg_dc_create": [C.POINTER(C.c_int64), C.c_int64, I64P, I64P, F64P, C.c_int64, C.c_double, C.c_int64, C.c_int],
+        "jg_dc_dims": [C.c_int64, I64P],
+        "jg_dc_set_rhs": [C.c_int64, F64P],
+        "jg_dc_set_injections": [C.c_int64, C.c_int64, C.c_int64, F64P],
+        "jg_dc_set_branches": [C.c_int64, C.c_int64, I64P, I64P, F64P, F64P],
+        "jg_dc_set_rating": [C.c_int64, VP],
+        "jg_dc_set_outages": [C.c_int64, C.c_int64, C.c_int64, I64P],
+        "jg_dc_solve": [C.c_int64],
+        "jg_dc_get_angle": [C.c_int64, F64P, I32P],
+        "jg_dc_angle_device": [C.c_int64, I64P],
+        "jg_dc_get_flows": [C.c_int64, F64P],
+        "jg_dc_screen": [C.c_int64, F64P],
+        "jg_dc_screen_device": [C.c_int64, VP],
+        "jg_dc_pack_results_device": [C.c_int64, VP],
+        "jg_dc_time_kernel": [C.c_int64, C.c_int, C.c_int, F64P],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -148,6 +164,8 @@ def lib():
     L.jg_gn_destroy.restype = None
     L.jg_nr_base_destroy.argtypes = [VP]
     L.jg_nr_base_destroy.restype = None
+    L.jg_dc_destroy.argtypes = [C.c_int64]
+    L.jg_dc_destroy.restype = None
     L.jg_plan_cache_clear.argtypes = []
     L.jg_plan_cache_clear.restype = None
     L.jg_comm_destroy.argtypes = [VP]

@@ -110,12 +110,21 @@ def deviceBatching(share: int, steps: int, lanes: int = 512) -> int:
 
 
 def contingencyAnalysis(system: PowerSystem, labels, device: int = 0, method: str = "nr", reactiveLimit: int = 0, start=None,
-                        iteration: int = 20, tolerance: float = 1e-8) -> AcPowerFlow:
+                        iteration: int = 20, tolerance: float = 1e-8, rating=None) -> "AcPowerFlow | DcPowerFlow":
     """Batched analysis with scenario s = outage of branch labels[s] (None / 0 = base case).  method: "nr" Newton-Raphson, "bx" / "xb" fast
     Newton-Raphson (constant matrices with per-scenario edits, ONE factorisation for the batch: jg_nr_fast_patch_batch).
     reactiveLimit = k > 0 (Newton-Raphson, two or more scenarios): the analysis is also SOLVED -- from `start` (V, theta) when given -- with up to k rounds
-    of reactiveLimit! + powerFlow! per scenario (powerflow.powerFlowLimits_); method.iteration sums the solves of each scenario (test/powerFlow/limits.jl)."""
+    of reactiveLimit! + powerFlow! per scenario (powerflow.powerFlowLimits_); method.iteration sums the solves of each scenario (test/powerFlow/limits.jl).
+    method "dc": the DC model instead -- a SOLVED DcPowerFlow comes back (voltage.angle [batch, n], status [batch] with 3 on bridges, and, when `rating`
+    (per branch, per unit of active power) is given, screen [batch, 5]: dcpowerflow.screenSummary_)."""
     labels = list(labels)
+    if method == "dc" and (reactiveLimit or start is not None or iteration != 20 or tolerance != 1e-8):
+        raise ValueError("contingencyAnalysis: reactiveLimit, start, iteration and tolerance have no meaning for method='dc' (nothing is iterated)")
+    if method != "dc" and rating is not None:
+        raise ValueError("contingencyAnalysis: rating belongs to method='dc'; an AC screen takes it in screenSummary_(analysis, rating=...)")
+    if method == "dc":                                          # the pre-filter of a screen: solved on return, one factor for the whole batch (dcpowerflow.py)
+        from .dcpowerflow import dcContingencyAnalysis
+        return dcContingencyAnalysis(system, labels, device=device, rating=rating)
     if reactiveLimit and (method != "nr" or len(labels) < 2):
         raise ValueError("contingencyAnalysis: reactiveLimit needs method='nr' and two or more scenarios")
     if method in ("bx", "xb"):
@@ -124,7 +133,7 @@ def contingencyAnalysis(system: PowerSystem, labels, device: int = 0, method: st
     elif method == "nr":
         an = newtonRaphson(system, batch=len(labels), device=device, max_patch=4)
     else:
-        raise ValueError("method: nr | bx | xb")
+        raise ValueError("method: nr | bx | xb | dc")
     setOutages_(an, [int(lab) if lab else 0 for lab in labels])
     if reactiveLimit:
         from .powerflow import powerFlowLimits_

@@ -1,0 +1,707 @@
+// jg_dc.hip -- DC power flow and the batched DC N-1 screen on one shared scalar factor (jg_dc.hpp has the algebra and the reference lines it stands for).
+//
+// What runs: the elimination order, fill pattern, update terms and dependency levels come from jg_symbolic (the bus graph, no top tasks); the
+// factorisation of the ONE base matrix is a launch per dependency level with a thread per entry (once per base case); the sweeps give a wavefront one
+// row x 64 scenarios, read the premultiplied factor values and the column indices through the scalar cache (they are the same for every scenario)
+// and move 8 bytes per (row, scenario) through the vector pipe.  Every store is a vector store.
+#include "jg_dc.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+
+#include "../../include/jgrid.h"
+#include "jg_engine.hpp"
+
+namespace jg {
+
+namespace {
+
+typedef const double __attribute__((address_space(4)))* CDbl;      // wave-uniform values: scalar loads
+typedef const int __attribute__((address_space(4)))* CInt;
+typedef int I4 __attribute__((ext_vector_type(4)));
+typedef double D4 __attribute__((ext_vector_type(4)));
+typedef const I4 __attribute__((address_space(4)))* CI4;
+typedef const D4 __attribute__((address_space(4)))* CD4;
+#ifndef JG_DC_CHAIN_SPLIT
+#define JG_DC_CHAIN_SPLIT 1             // probe builds: -DJG_DC_CHAIN_SPLIT=0 gives every row of a chain level to ONE wave (the A/B of DESIGN.md 3.7)
+#endif
+static_assert(DC_T == 4, "a step of a sweep row is one 16-byte index load and one 32-byte value load");
+
+// ---- factorisation of the base matrix: A = Lh D^-1 U on the static pivot order, scalars ---------------------------------------------------
+__global__ void k_dc_init(const int* e_src, const double* A, double* X, int n_entries) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < n_entries) X[e] = e_src[e] >= 0 ? A[e_src[e]] : 0.0;
+}
+// one dependency level: entry e -= sum Lh(i,k) U(k,j) / D(k) over its update terms (all final at lower levels)
+__global__ void k_dc_fact_level(const int* f_ent, const int* t_ptr, const int* t_a, const int* t_d, const int* t_b, double* X, int i0, int i1) {
+    const int i = i0 + blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= i1) return;
+    const int e = f_ent[i];
+    double s = X[e];
+    for (int t = t_ptr[e]; t < t_ptr[e + 1]; ++t) s -= X[t_a[t]] * X[t_b[t]] / X[t_d[t]];
+    X[e] = s;
+}
+__global__ void k_dc_dinv(const int* diag, const double* X, double* dinv, int* bad, int n) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const double d = X[diag[k]];
+    if (d == 0.0 || !isfinite(d)) atomicOr(bad, 1);
+    dinv[k] = 1.0 / d;
+}
+// the sweeps' values in list order: Lh(k,c) / D(c) below the diagonal, U(k,c) / D(k) above it; 0 for the padding of a list
+__global__ void k_dc_compact(const int* ent, const int* dpiv, const double* X, const double* dinv, double* val, int terms, int n_entries) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= terms) return;
+    const int e = ent[p];
+    val[p] = e < n_entries ? X[e] * dinv[dpiv[p]] : 0.0;
+}
+
+// ---- sweeps on the shared factor, scenarios as lanes --------------------------------------------------------------------------------------
+struct DcSweepArgs {
+    const int* rows; const int* lev; const int* ptr; const int* col; const double* val;
+    const int* perm; const double* dinv;
+    const double* rhs;                  // MODE 0: [n][ld], bus order
+    const int* of; const int* ot;       // MODE 1: the lanes' outage buses (-1: none / the slack): the right-hand side e_from - e_to is formed here
+    double* W;                          // [n + 1][ld], pivot order; row n stays zero
+    double* out;                        // MODE 2: [n][ld], bus order
+    const int* groups;                  // nullable: the lane groups this launch works on
+    int ld, l0, l1;
+};
+
+// share `sub` of `wpi` of row k: MODE 0 / 1 forward (y_k = r_k - sum M(k,c) y_c), MODE 2 backward (x_k = y_k / D_k - sum M(k,c) x_c)
+template <int MODE>
+__device__ __forceinline__ double dc_row(const DcSweepArgs& a, int k, int sub, int wpi, size_t bl) {
+    const size_t ld = (size_t)a.ld;
+    double acc = 0.0;
+    if (sub == 0) {
+        if (MODE == 2) acc = a.W[(size_t)k * ld + bl] * ((CDbl)a.dinv)[k];
+        else {
+            const int bus = ((CInt)a.perm)[k];
+            if (MODE == 0) acc = a.rhs[(size_t)bus * ld + bl];
+            else acc = (a.of[bl] == bus ? 1.0 : 0.0) - (a.ot[bl] == bus ? 1.0 : 0.0);
+        }
+    }
+    const int p0 = ((CInt)a.ptr)[k], p1 = ((CInt)a.ptr)[k + 1];
+    for (int p = p0 + DC_T * sub; p < p1; p += DC_T * wpi) {
+        const I4 c = *(CI4)(a.col + p);
+        const D4 v = *(CD4)(a.val + p);
+        const double w0 = a.W[(size_t)c[0] * ld + bl], w1 = a.W[(size_t)c[1] * ld + bl];
+        const double w2 = a.W[(size_t)c[2] * ld + bl], w3 = a.W[(size_t)c[3] * ld + bl];
+        acc = fma(-v[0], w0, acc); acc = fma(-v[1], w1, acc); acc = fma(-v[2], w2, acc); acc = fma(-v[3], w3, acc);
+    }
+    return acc;
+}
+template <int MODE>
+__device__ __forceinline__ void dc_store(const DcSweepArgs& a, int k, size_t bl, double acc) {
+    a.W[(size_t)k * a.ld + bl] = acc;
+    if (MODE == 2) a.out[(size_t)((CInt)a.perm)[k] * a.ld + bl] = acc;
+}
+
+// one wide level: a wave = one row
+template <int MODE>
+__global__ __launch_bounds__(256) void k_dc_sweep(DcSweepArgs a) {
+    const int wave = uniform(threadIdx.y);
+    const int r0 = ((CInt)a.lev)[a.l0], r1 = ((CInt)a.lev)[a.l0 + 1];
+    const int item = r0 + blockIdx.x * 4 + wave;
+    if (item >= r1) return;
+    const int grp = a.groups ? ((CInt)a.groups)[blockIdx.y] : (int)blockIdx.y;
+    const size_t bl = (size_t)grp * 64 + threadIdx.x;
+    const int k = ((CInt)a.rows)[item];
+    dc_store<MODE>(a, k, bl, dc_row<MODE>(a, k, 0, 1, bl));
+}
+// a run of narrow levels (at most DC_CHAIN_WAVES rows each): ONE workgroup per lane group walks them, a workgroup barrier between levels; the waves
+// left over by a level of few rows share its rows' lists (partial sums meet in LDS, fixed order)
+template <int MODE>
+__global__ __launch_bounds__(64 * DC_CHAIN_WAVES) void k_dc_chain(DcSweepArgs a) {
+    __shared__ double red[DC_CHAIN_WAVES * 64];
+    const int wave = uniform(threadIdx.y), lane = threadIdx.x;
+    const int grp = a.groups ? ((CInt)a.groups)[blockIdx.y] : (int)blockIdx.y;
+    const size_t bl = (size_t)grp * 64 + lane;
+    for (int l = a.l0; l < a.l1; ++l) {
+        const int r0 = ((CInt)a.lev)[l], cnt = ((CInt)a.lev)[l + 1] - r0;
+        int wpi = JG_DC_CHAIN_SPLIT ? DC_CHAIN_WAVES : 1;
+        while (cnt * wpi > DC_CHAIN_WAVES) wpi >>= 1;               // cnt <= DC_CHAIN_WAVES: ends at wpi >= 1
+        const int row = wave / wpi, sub = wave & (wpi - 1);
+        const bool have = row < cnt;
+        int k = 0; double acc = 0.0;
+        if (have) {
+            k = ((CInt)a.rows)[r0 + row];
+            acc = dc_row<MODE>(a, k, sub, wpi, bl);
+            if (sub != 0) red[wave * 64 + lane] = acc;
+        }
+        if (wpi > 1) __syncthreads();
+        if (have && sub == 0) {
+            for (int w = 1; w < wpi; ++w) acc += red[(wave + w) * 64 + lane];
+            dc_store<MODE>(a, k, bl, acc);
+        }
+        __syncthreads();
+    }
+}
+
+// ---- the rank-1 combine ------------------------------------------------------------------------------------------------------------------
+struct DcCombineArgs {
+    const double* Z; const double* XS; const double* th0;      // z_s [n][ld]; B^-1 rhs_s [n][ld] of the groups with ginj; theta_0 [n][64], lane 0
+    const int* ginj;                                            // nullable [ld / 64]
+    const int* of; const int* ot; const int* obr; const double* oy; const double* osh;
+    double* TH; int* status;
+    double slack_angle; int n, ld, slack;
+};
+constexpr int DC_COMBINE_ROWS = 8;
+__global__ __launch_bounds__(256) void k_dc_combine(DcCombineArgs a) {
+    const int wave = uniform(threadIdx.y);
+    const int grp = blockIdx.y;
+    const size_t ld = (size_t)a.ld, bl = (size_t)grp * 64 + threadIdx.x;
+    const bool own = a.ginj && ((CInt)a.ginj)[grp] != 0;
+    const int fi = a.of[bl], ti = a.ot[bl];
+    const bool has = a.obr[bl] >= 0;
+    const double yk = a.oy[bl], sh = a.osh[bl];
+    auto x0 = [&](int bus) { return own ? a.XS[(size_t)bus * ld + bl] : a.th0[(size_t)bus * 64]; };
+    const double az = (fi >= 0 ? a.Z[(size_t)fi * ld + bl] : 0.0) - (ti >= 0 ? a.Z[(size_t)ti * ld + bl] : 0.0);
+    const double ax = ((fi >= 0 ? x0(fi) : 0.0) - (ti >= 0 ? x0(ti) : 0.0)) - sh * az;
+    const double den = 1.0 - yk * az;
+    const bool sing = has && fabs(den) < DC_SINGULAR;
+    const double c = (has && !sing) ? yk * ax / den - sh : 0.0;      // theta = x0 - sh z + z y (a'x) / den
+    if (blockIdx.x == 0 && wave == 0) a.status[bl] = sing ? 3 : 0;
+    const int b0 = (blockIdx.x * 4 + wave) * DC_COMBINE_ROWS;
+    for (int bus = b0; bus < min(b0 + DC_COMBINE_ROWS, a.n); ++bus) {
+        double th = x0(bus) + c * a.Z[(size_t)bus * ld + bl] + a.slack_angle;
+        if (bus == a.slack) th = a.slack_angle;
+        if (sing) th = __longlong_as_double(0x7ff8000000000000LL);
+        a.TH[(size_t)bus * ld + bl] = th;
+    }
+}
+
+// ---- branch flows and the screen summary ---------------------------------------------------------------------------------------------------
+struct DcFlowArgs {
+    const double* TH; const int* bf; const int* bt; const double* by; const double* bs; const double* rating;    // rating nullable
+    const int* obr;
+    double* flows;                      // nullable [nbr][ld]
+    double* part;                       // [chunks][4][ld]: worst loading, its branch, largest |from|, its branch
+    int nbr, ld;
+};
+constexpr int DC_FLOW_BRANCHES = 32;    // per wave
+__global__ __launch_bounds__(256) void k_dc_flows(DcFlowArgs a) {
+    const int wave = uniform(threadIdx.y);
+    const int chunk = blockIdx.x * 4 + wave;
+    const int k0 = chunk * DC_FLOW_BRANCHES;
+    if (k0 >= a.nbr) return;
+    const size_t ld = (size_t)a.ld, bl = (size_t)blockIdx.y * 64 + threadIdx.x;
+    const int out = a.obr[bl];
+    double wl = 0.0, wf = 0.0, il = 0.0, jf = 0.0;
+    for (int k = k0; k < min(k0 + DC_FLOW_BRANCHES, a.nbr); ++k) {
+        const int f = ((CInt)a.bf)[k], t = ((CInt)a.bt)[k];
+        const double y = ((CDbl)a.by)[k], s = ((CDbl)a.bs)[k];
+        double p = y * (a.TH[(size_t)f * ld + bl] - a.TH[(size_t)t * ld + bl] - s);
+        if (k == out) p = 0.0;
+        if (a.flows) a.flows[(size_t)k * ld + bl] = p;
+        const double m = fabs(p);
+        if (m > wf) { wf = m; jf = (double)(k + 1); }
+        if (a.rating) {
+            const double r = ((CDbl)a.rating)[k];
+            if (r > 0.0 && m / r > wl) { wl = m / r; il = (double)(k + 1); }
+        }
+    }
+    double* q = a.part + (size_t)chunk * 4 * ld + bl;
+    q[0] = wl; q[ld] = il; q[2 * ld] = wf; q[3 * ld] = jf;
+}
+// chunks in ascending order, strict comparison: ties go to the lowest branch index (as k_screen_final)
+__global__ __launch_bounds__(64) void k_dc_screen_final(const double* part, const int* status, double* screen, int chunks, int ld, int batch) {
+    const size_t bl = (size_t)blockIdx.x * 64 + threadIdx.x;
+    double wl = 0.0, wf = 0.0, il = 0.0, jf = 0.0;
+    for (int c = 0; c < chunks; ++c) {
+        const double* q = part + (size_t)c * 4 * ld + bl;
+        const double l = q[0], i = q[ld], f = q[2 * (size_t)ld], j = q[3 * (size_t)ld];
+        if (l > wl) { wl = l; il = i; }
+        if (f > wf) { wf = f; jf = j; }
+    }
+    if (bl < (size_t)batch) {
+        double* r = screen + bl * 5;
+        r[0] = wl; r[1] = il; r[2] = wf; r[3] = jf; r[4] = (double)status[bl];
+    }
+}
+// angle | status, scenario-major [batch][n + 1]: the record a gather carries
+__global__ __launch_bounds__(256) void k_dc_pack(const double* TH, const int* status, double* dst, int n, int ld, int batch) {
+    const size_t bl = (size_t)blockIdx.y * 64 + threadIdx.x;
+    if (bl >= (size_t)batch) return;
+    const int bus = blockIdx.x * 4 + threadIdx.y;
+    if (bus < n) dst[bl * (n + 1) + bus] = TH[(size_t)bus * ld + bl];
+    else if (bus == n) dst[bl * (n + 1) + n] = (double)status[bl];
+}
+__global__ void k_dc_fill_rhs(const double* rhs0, double* RHS, int n, int ld) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < (size_t)n * ld) RHS[i] = rhs0[(i / ld) * 64];
+}
+
+#define DC_HIP(expr)                                                                      \
+    do {                                                                                  \
+        hipError_t err__ = (expr);                                                        \
+        if (err__ != hipSuccess) {                                                        \
+            h->error = std::string(#expr) + ": " + hipGetErrorString(err__);              \
+            return 2;                                                                     \
+        }                                                                                 \
+    } while (0)
+
+template <typename T>
+int dev_alloc(DcHandle* h, T** p, size_t count, const T* src = nullptr, bool zero = false) {
+    void* q = nullptr;
+    DC_HIP(hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T)));
+    h->allocs.push_back(q);
+    *p = (T*)q;
+    if (src && count) DC_HIP(sync_copy(q, src, count * sizeof(T), hipMemcpyHostToDevice, h->stream));
+    else if (zero && count) DC_HIP(sync_fill(q, 0, count * sizeof(T), h->stream));
+    return 0;
+}
+// frees what only jg_dc_create needed (factorisation tables, the unfactorised values)
+template <typename T>
+void dev_release(DcHandle* h, T*& p) {
+    if (!p) return;
+    h->allocs.erase(std::remove(h->allocs.begin(), h->allocs.end(), (void*)p), h->allocs.end());
+    hipFree((void*)p);
+    p = nullptr;
+}
+#define DC_TRY(expr) do { const int rc__ = (expr); if (rc__) return rc__; } while (0)
+
+// term lists of one triangle, rows grouped by level, lists padded to DC_T
+int build_sweep(DcHandle* h, DcSweepTables& T, const std::vector<int>& level, const std::vector<int>& lptr, const std::vector<int>& lent,
+                const std::vector<int>& lcol, bool upper) {
+    const int n = h->n;
+    int nlev = 0;
+    for (int k = 0; k < n; ++k) nlev = std::max(nlev, level[k]);
+    T.h_lev.assign(nlev + 1, 0);
+    for (int k = 0; k < n; ++k) T.h_lev[level[k]]++;                 // level is 1-based
+    for (int l = 0; l < nlev; ++l) T.h_lev[l + 1] += T.h_lev[l];
+    std::vector<int> rows(n), fill(T.h_lev.begin(), T.h_lev.end() - 1);
+    for (int k = 0; k < n; ++k) rows[fill[level[k] - 1]++] = k;
+    std::vector<int> ptr(n + 1, 0);
+    for (int k = 0; k < n; ++k) ptr[k + 1] = ptr[k] + (lptr[k + 1] - lptr[k] + DC_T - 1) / DC_T * DC_T;
+    T.terms = ptr[n];
+    std::vector<int> col(ptr[n], n), ent(ptr[n], h->n_entries), dpiv(ptr[n], 0);
+    for (int k = 0; k < n; ++k)
+        for (int p = lptr[k], q = ptr[k]; p < lptr[k + 1]; ++p, ++q) { col[q] = lcol[p]; ent[q] = lent[p]; dpiv[q] = upper ? k : lcol[p]; }
+    int* d_dpiv = nullptr; int* d_ent = nullptr;
+    DC_TRY(dev_alloc(h, &T.rows, (size_t)n, rows.data()));
+    DC_TRY(dev_alloc(h, &T.lev, T.h_lev.size(), T.h_lev.data()));
+    DC_TRY(dev_alloc(h, &T.ptr, (size_t)n + 1, ptr.data()));
+    DC_TRY(dev_alloc(h, &T.col, col.size(), col.data()));
+    DC_TRY(dev_alloc(h, &d_ent, ent.size(), ent.data()));
+    DC_TRY(dev_alloc(h, &d_dpiv, dpiv.size(), dpiv.data()));
+    DC_TRY(dev_alloc(h, &T.val, col.size(), (const double*)nullptr, true));
+    if (T.terms) hipLaunchKernelGGL(k_dc_compact, dim3((unsigned)((T.terms + 255) / 256)), dim3(256), 0, h->stream, d_ent, d_dpiv, h->X, h->dinv, T.val, (int)T.terms, h->n_entries);
+    DC_HIP(hipGetLastError());
+    DC_HIP(hipStreamSynchronize(h->stream));
+    dev_release(h, d_ent); dev_release(h, d_dpiv);
+    T.launches.clear();
+    for (int l = 0; l < nlev;) {
+        const bool narrow = T.h_lev[l + 1] - T.h_lev[l] <= DC_CHAIN_WAVES;
+        int e = l + 1;
+        if (narrow) while (e < nlev && T.h_lev[e + 1] - T.h_lev[e] <= DC_CHAIN_WAVES) ++e;
+        T.launches.push_back({l, e, narrow ? 1 : 0});
+        l = e;
+    }
+    return 0;
+}
+
+template <int MODE>
+void launch_sweep(DcHandle* h, const DcSweepTables& T, DcSweepArgs a, int groups) {
+    a.rows = T.rows; a.lev = T.lev; a.ptr = T.ptr; a.col = T.col; a.val = T.val; a.perm = h->perm; a.dinv = h->dinv;
+    for (const auto& L : T.launches) {
+        a.l0 = L.l0; a.l1 = L.l1;
+        if (L.chain) hipLaunchKernelGGL((k_dc_chain<MODE>), dim3(1, groups), dim3(64, DC_CHAIN_WAVES), 0, h->stream, a);
+        else {
+            const int cnt = T.h_lev[L.l0 + 1] - T.h_lev[L.l0];
+            hipLaunchKernelGGL((k_dc_sweep<MODE>), dim3((cnt + 3) / 4, groups), dim3(64, 4), 0, h->stream, a);
+        }
+    }
+}
+
+// x = B^-1 r for `groups` lane groups: MODE_F 0 (r = rhs) or 1 (r = e_from - e_to of the lanes' outages)
+template <int MODE_F>
+void sweep_pair(DcHandle* h, const double* rhs, double* W, double* out, int ld, int groups, const int* glist) {
+    DcSweepArgs a{};
+    a.rhs = rhs; a.of = h->o_from; a.ot = h->o_to; a.W = W; a.out = out; a.groups = glist; a.ld = ld;
+    launch_sweep<MODE_F>(h, h->fwd, a, groups);
+    launch_sweep<2>(h, h->bwd, a, groups);
+}
+
+void launch_combine(DcHandle* h) {
+    DcCombineArgs c{};
+    c.Z = h->Z; c.XS = h->XS; c.th0 = h->th0; c.ginj = h->n_glist ? h->ginj : nullptr;
+    c.of = h->o_from; c.ot = h->o_to; c.obr = h->o_br; c.oy = h->o_y; c.osh = h->o_sh;
+    c.TH = h->TH; c.status = h->status; c.slack_angle = h->slack_angle; c.n = h->n; c.ld = h->ld; c.slack = h->slack;
+    const int per = 4 * DC_COMBINE_ROWS;
+    hipLaunchKernelGGL(k_dc_combine, dim3((h->n + per - 1) / per, h->ld / 64), dim3(64, 4), 0, h->stream, c);
+}
+
+int launch_flows(DcHandle* h, bool store) {
+    if (!h->nbr) { h->error = "jg_dc_set_branches has not been called"; return 1; }
+    if (store && !h->flows) DC_TRY(dev_alloc(h, &h->flows, (size_t)h->nbr * h->ld, (const double*)nullptr, true));
+    DcFlowArgs f{};
+    f.TH = h->TH; f.bf = h->b_from; f.bt = h->b_to; f.by = h->b_y; f.bs = h->b_shift; f.rating = h->b_rating; f.obr = h->o_br;
+    f.flows = store ? h->flows : nullptr; f.part = h->part; f.nbr = h->nbr; f.ld = h->ld;
+    hipLaunchKernelGGL(k_dc_flows, dim3((h->n_chunks + 3) / 4, h->ld / 64), dim3(64, 4), 0, h->stream, f);
+    hipLaunchKernelGGL(k_dc_screen_final, dim3(h->ld / 64), dim3(64), 0, h->stream, h->part, h->status, h->screen, h->n_chunks, h->ld, h->batch);
+    DC_HIP(hipGetLastError());
+    return 0;
+}
+
+int base_solve(DcHandle* h) {
+    if (h->h_rhs.empty()) { h->error = "jg_dc_set_rhs has not been called"; return 1; }
+    DC_HIP(hipMemcpy2DAsync(h->rhs0, 64 * sizeof(double), h->h_rhs.data(), sizeof(double), sizeof(double), (size_t)h->n, hipMemcpyHostToDevice, h->stream));
+    sweep_pair<0>(h, h->rhs0, h->W0, h->th0, 64, 1, nullptr);
+    DC_HIP(hipGetLastError());
+    h->base_dirty = false;
+    return 0;
+}
+
+// the launch chain of a batch: sweeps for z, (sweeps for the groups with injections of their own,) combine.  One straight line on the handle's stream.
+int solve_chain(DcHandle* h) {
+    sweep_pair<1>(h, nullptr, h->W, h->Z, h->ld, h->ld / 64, nullptr);
+    if (h->n_glist) sweep_pair<0>(h, h->RHS, h->W, h->XS, h->ld, h->n_glist, h->glist);
+    launch_combine(h);
+    DC_HIP(hipGetLastError());
+    return 0;
+}
+
+int dc_create(DcHandle* h, int64_t n64, const int64_t* colptr, const int64_t* rowval, const double* nzval, int64_t slack1, double slack_angle, int64_t batch, int device) {
+    const int n = (int)n64;
+    h->n = n; h->batch = (int)batch; h->ld = (int)((batch + 63) / 64 * 64); h->device = device; h->slack = (int)slack1 - 1; h->slack_angle = slack_angle;
+    if (colptr[0] != 1) { h->error = "colptr is not 1-based"; return 1; }
+    const int nnz = (int)(colptr[n] - 1);
+    // the pattern is structurally symmetric with sorted rows (SparseMatrixCSC): the row-CSR pattern is the same pair of arrays; values are transposed entry by entry
+    std::vector<int> rp(n + 1), ci(nnz);
+    for (int j = 0; j <= n; ++j) rp[j] = (int)(colptr[j] - 1);
+    for (int j = 0; j < n; ++j) {
+        if (rp[j + 1] < rp[j]) { h->error = "colptr is not monotone"; return 1; }
+        for (int p = rp[j]; p < rp[j + 1]; ++p) {
+            ci[p] = (int)(rowval[p] - 1);
+            if (ci[p] < 0 || ci[p] >= n || (p > rp[j] && ci[p] <= ci[p - 1])) { h->error = "rowval: rows of a column must be sorted, unique and in 1..n"; return 1; }
+        }
+    }
+    std::vector<double> A(nnz);
+    for (int r = 0; r < n; ++r)
+        for (int q = rp[r]; q < rp[r + 1]; ++q) {
+            const int c = ci[q];                                           // entry (r, c) of the row form = pointer of row r in column c
+            const int* lo = ci.data() + rp[c]; const int* hi = ci.data() + rp[c + 1];
+            const int* it = std::lower_bound(lo, hi, r);
+            if (it == hi || *it != r) { h->error = "the nodal matrix pattern is not structurally symmetric"; return 1; }
+            double v = nzval[it - ci.data()];
+            if (r == h->slack || c == h->slack) v = (r == c) ? 1.0 : 0.0;   // the slack row and column leave the system (dcPowerFlow.jl:63-80): an identity row here
+            A[q] = v;
+        }
+    BlockSymbolic S;
+    // policy bits 8-15 = 255: no pivot goes to a top task (jg_symbolic.hpp), every pivot is a level item.  The JG_TOP_LEVEL test knob can override that
+    // byte; the top tasks it would add are further replay tables -- the generic lists read here (t_ptr / t_a / t_d / t_b, e_level, l_* / u_*, bwd_level)
+    // are complete before build_top runs and neither it nor build_tables changes them, so the DC factor is the same with the knob set.
+    constexpr long long DC_POLICY_NO_TOP = (long long)255 << 8;
+    if (analyze(n, rp.data(), ci.data(), DC_POLICY_NO_TOP, S) != 0) { h->error = "symbolic analysis failed (pattern must contain the diagonal)"; return 1; }
+    h->n_entries = S.n_entries;
+    DC_HIP(hipSetDevice(device));
+    DC_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    // factorisation tables
+    int nlev = 0;
+    for (int e = 0; e < S.n_entries; ++e) nlev = std::max(nlev, S.e_level[e]);
+    h->n_fact_levels = nlev;
+    h->f_lev.assign(nlev + 2, 0);
+    for (int e = 0; e < S.n_entries; ++e) h->f_lev[S.e_level[e] + 1]++;
+    for (int l = 0; l <= nlev; ++l) h->f_lev[l + 1] += h->f_lev[l];
+    std::vector<int> f_ent(S.n_entries), fill(h->f_lev.begin(), h->f_lev.end() - 1);
+    for (int e = 0; e < S.n_entries; ++e) f_ent[fill[S.e_level[e]]++] = e;
+    DC_TRY(dev_alloc(h, &h->perm, (size_t)n, S.perm.data()));
+    DC_TRY(dev_alloc(h, &h->f_ent, f_ent.size(), f_ent.data()));
+    DC_TRY(dev_alloc(h, &h->t_ptr, S.t_ptr.size(), S.t_ptr.data()));
+    DC_TRY(dev_alloc(h, &h->t_a, S.t_a.size(), S.t_a.data()));
+    DC_TRY(dev_alloc(h, &h->t_d, S.t_d.size(), S.t_d.data()));
+    DC_TRY(dev_alloc(h, &h->t_b, S.t_b.size(), S.t_b.data()));
+    DC_TRY(dev_alloc(h, &h->e_src, S.e_src.size(), S.e_src.data()));
+    DC_TRY(dev_alloc(h, &h->diag, (size_t)n, S.diag.data()));
+    DC_TRY(dev_alloc(h, &h->A, (size_t)nnz, A.data()));
+    DC_TRY(dev_alloc(h, &h->X, (size_t)S.n_entries + 1, (const double*)nullptr, true));
+    DC_TRY(dev_alloc(h, &h->dinv, (size_t)n, (const double*)nullptr, true));
+    DC_TRY(dev_alloc(h, &h->bad, (size_t)1, (const int*)nullptr, true));
+    // numeric factorisation, once: a launch per dependency level
+    hipLaunchKernelGGL(k_dc_init, dim3((S.n_entries + 255) / 256), dim3(256), 0, h->stream, h->e_src, h->A, h->X, S.n_entries);
+    for (int l = 0; l <= nlev; ++l) {
+        const int i0 = h->f_lev[l], i1 = h->f_lev[l + 1];
+        if (i1 > i0) hipLaunchKernelGGL(k_dc_fact_level, dim3((i1 - i0 + 255) / 256), dim3(256), 0, h->stream, h->f_ent, h->t_ptr, h->t_a, h->t_d, h->t_b, h->X, i0, i1);
+    }
+    hipLaunchKernelGGL(k_dc_dinv, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->diag, h->X, h->dinv, h->bad, n);
+    DC_HIP(hipGetLastError());
+    std::vector<int> flev(n, 1);
+    for (int r = 0; r < n; ++r)
+        for (int p = S.l_ptr[r]; p < S.l_ptr[r + 1]; ++p) flev[r] = std::max(flev[r], flev[S.l_col[p]] + 1);
+    DC_TRY(build_sweep(h, h->fwd, flev, S.l_ptr, S.l_ent, S.l_col, false));
+    DC_TRY(build_sweep(h, h->bwd, S.bwd_level, S.u_ptr, S.u_ent, S.u_col, true));
+    int bad = 0;
+    DC_HIP(sync_copy(&bad, h->bad, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    dev_release(h, h->f_ent); dev_release(h, h->t_ptr); dev_release(h, h->t_a); dev_release(h, h->t_d); dev_release(h, h->t_b);
+    dev_release(h, h->e_src); dev_release(h, h->diag); dev_release(h, h->A); dev_release(h, h->X); dev_release(h, h->bad);
+    if (bad) { h->error = "zero or non-finite pivot in the DC nodal matrix (an island without the slack bus?)"; return 3; }
+    const size_t ld = (size_t)h->ld;
+    DC_TRY(dev_alloc(h, &h->rhs0, (size_t)n * 64, (const double*)nullptr, true));
+    DC_TRY(dev_alloc(h, &h->W0, ((size_t)n + 1) * 64, (const double*)nullptr, true));
+    DC_TRY(dev_alloc(h, &h->th0, (size_t)n * 64, (const double*)nullptr, true));
+    DC_TRY(dev_alloc(h, &h->W, ((size_t)n + 1) * ld, (const double*)nullptr, true));
+    DC_TRY(dev_alloc(h, &h->Z, (size_t)n * ld, (const double*)nullptr, true));
+    DC_TRY(dev_alloc(h, &h->TH, (size_t)n * ld, (const double*)nullptr, true));
+    DC_TRY(dev_alloc(h, &h->o_from, ld, (const int*)nullptr, false));
+    DC_TRY(dev_alloc(h, &h->o_to, ld, (const int*)nullptr, false));
+    DC_TRY(dev_alloc(h, &h->o_br, ld, (const int*)nullptr, false));
+    DC_HIP(sync_fill(h->o_from, 0xff, ld * sizeof(int), h->stream));       // -1: no outage
+    DC_HIP(sync_fill(h->o_to, 0xff, ld * sizeof(int), h->stream));
+    DC_HIP(sync_fill(h->o_br, 0xff, ld * sizeof(int), h->stream));
+    DC_TRY(dev_alloc(h, &h->o_y, ld, (const double*)nullptr, true));
+    DC_TRY(dev_alloc(h, &h->o_sh, ld, (const double*)nullptr, true));
+    DC_TRY(dev_alloc(h, &h->status, ld, (const int*)nullptr, true));
+    DC_TRY(dev_alloc(h, &h->screen, ld * 5, (const double*)nullptr, true));
+    DC_TRY(dev_alloc(h, &h->ginj, ld / 64, (const int*)nullptr, true));
+    DC_TRY(dev_alloc(h, &h->glist, ld / 64, (const int*)nullptr, true));
+    h->h_ginj.assign(ld / 64, 0);
+    return 0;
+}
+
+void dc_destroy(DcHandle* h) {
+    hipSetDevice(h->device);
+    if (h->stream) hipStreamSynchronize(h->stream);
+    for (void* p : h->allocs) hipFree(p);
+    if (h->stream) hipStreamDestroy(h->stream);
+    delete h;
+}
+
+}  // namespace
+}  // namespace jg
+
+using jg::DcHandle;
+
+namespace {
+int faild(int code, const std::string& msg) { jg::set_last_error(msg); return code; }
+DcHandle* H(int64_t h) { return reinterpret_cast<DcHandle*>(static_cast<intptr_t>(h)); }
+#define DC_ENTER(h)                                                                     \
+    DcHandle* d = H(h);                                                                 \
+    if (!d) return faild(1, "null DC handle");                                          \
+    if (hipSetDevice(d->device) != hipSuccess) return faild(2, "hipSetDevice failed")
+#define DC_RET(expr) do { const int rc__ = (expr); if (rc__) return faild(rc__, d->error); } while (0)
+#define DC_API_HIP(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) return faild(2, std::string(#expr) + ": " + hipGetErrorString(e__)); } while (0)
+}  // namespace
+
+extern "C" {
+
+int jg_dc_create(int64_t* out, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, int64_t slack, double slack_angle,
+                 int64_t batch, int device) {
+    if (!out || !colptr || !rowval || !nzval || n < 1 || n > (1 << 24) || slack < 1 || slack > n || batch < 1 || batch > (1 << 20)) return faild(1, "jg_dc_create: bad argument");
+    DcHandle* h = new DcHandle();
+    const int rc = jg::dc_create(h, n, colptr, rowval, nzval, slack, slack_angle, batch, device);
+    if (rc) { const std::string msg = h->error; jg::dc_destroy(h); *out = 0; return faild(rc, msg); }
+    *out = (int64_t)reinterpret_cast<intptr_t>(h);
+    return 0;
+}
+
+void jg_dc_destroy(int64_t h) {
+    if (H(h)) jg::dc_destroy(H(h));
+}
+
+int jg_dc_dims(int64_t h, int64_t* dims) {
+    DC_ENTER(h);
+    if (!dims) return faild(1, "jg_dc_dims: null pointer");
+    dims[0] = d->n; dims[1] = d->batch; dims[2] = d->ld; dims[3] = d->nbr; dims[4] = d->n_entries; dims[5] = d->n_fact_levels;
+    dims[6] = (int64_t)d->fwd.h_lev.size() - 1; dims[7] = (int64_t)d->bwd.h_lev.size() - 1;
+    dims[8] = (int64_t)(d->fwd.launches.size() + d->bwd.launches.size()); dims[9] = d->fwd.terms + d->bwd.terms;
+    return 0;
+}
+
+int jg_dc_set_rhs(int64_t h, const double* rhs) {
+    DC_ENTER(h);
+    if (!rhs) return faild(1, "jg_dc_set_rhs: null pointer");
+    d->h_rhs.assign(rhs, rhs + d->n);
+    d->h_rhs[d->slack] = 0.0;
+    d->base_dirty = true; d->solved = false;
+    std::fill(d->h_ginj.begin(), d->h_ginj.end(), 0); d->n_glist = 0;
+    return 0;
+}
+
+int jg_dc_set_injections(int64_t h, int64_t lane0, int64_t count, const double* rhs) {
+    DC_ENTER(h);
+    if (lane0 < 0 || count < 0 || lane0 + count > d->batch || (count && !rhs)) return faild(1, "jg_dc_set_injections: lanes out of range");
+    if (d->h_rhs.empty()) return faild(1, "jg_dc_set_injections: jg_dc_set_rhs first");
+    if (!count) return 0;
+    const size_t n = (size_t)d->n, ld = (size_t)d->ld;
+    if (!d->RHS) {
+        DC_RET(jg::dev_alloc(d, &d->RHS, n * ld, (const double*)nullptr, true));
+        DC_RET(jg::dev_alloc(d, &d->XS, n * ld, (const double*)nullptr, true));
+    }
+    bool any = false;
+    for (int g : d->h_ginj) any = any || g;
+    if (!any) {                                                            // every lane starts from the base right-hand side
+        if (d->base_dirty) DC_RET(jg::base_solve(d));
+        hipLaunchKernelGGL(jg::k_dc_fill_rhs, dim3((unsigned)((n * ld + 255) / 256)), dim3(256), 0, d->stream, d->rhs0, d->RHS, d->n, d->ld);
+    }
+    std::vector<double> t(n * (size_t)count);
+    for (size_t s = 0; s < (size_t)count; ++s)
+        for (size_t i = 0; i < n; ++i) t[i * count + s] = (int)i == d->slack ? 0.0 : rhs[s * n + i];
+    DC_API_HIP(hipMemcpy2DAsync(d->RHS + lane0, ld * sizeof(double), t.data(), (size_t)count * sizeof(double), (size_t)count * sizeof(double), n, hipMemcpyHostToDevice, d->stream));
+    DC_API_HIP(hipStreamSynchronize(d->stream));
+    for (int64_t s = lane0; s < lane0 + count; ++s) d->h_ginj[s / 64] = 1;
+    std::vector<int> list;
+    for (size_t g = 0; g < d->h_ginj.size(); ++g) if (d->h_ginj[g]) list.push_back((int)g);
+    d->n_glist = (int)list.size();
+    DC_API_HIP(jg::sync_copy(d->ginj, d->h_ginj.data(), d->h_ginj.size() * sizeof(int), hipMemcpyHostToDevice, d->stream));
+    DC_API_HIP(jg::sync_copy(d->glist, list.data(), list.size() * sizeof(int), hipMemcpyHostToDevice, d->stream));
+    d->solved = false;
+    return 0;
+}
+
+int jg_dc_set_branches(int64_t h, int64_t nbr, const int64_t* from, const int64_t* to, const double* admittance, const double* shift) {
+    DC_ENTER(h);
+    if (nbr < 1 || !from || !to || !admittance || !shift) return faild(1, "jg_dc_set_branches: bad argument");
+    if (d->nbr) return faild(1, "jg_dc_set_branches: the branch table is already set");
+    std::vector<int> f(nbr), t(nbr);
+    for (int64_t k = 0; k < nbr; ++k) {
+        if (from[k] < 1 || from[k] > d->n || to[k] < 1 || to[k] > d->n) return faild(1, "jg_dc_set_branches: bus index out of range");
+        f[k] = (int)from[k] - 1; t[k] = (int)to[k] - 1;
+    }
+    d->h_from = f; d->h_to = t; d->h_y.assign(admittance, admittance + nbr); d->h_shift.assign(shift, shift + nbr);
+    d->n_chunks = (int)((nbr + jg::DC_FLOW_BRANCHES - 1) / jg::DC_FLOW_BRANCHES);
+    DC_RET(jg::dev_alloc(d, &d->b_from, (size_t)nbr, f.data()));
+    DC_RET(jg::dev_alloc(d, &d->b_to, (size_t)nbr, t.data()));
+    DC_RET(jg::dev_alloc(d, &d->b_y, (size_t)nbr, admittance));
+    DC_RET(jg::dev_alloc(d, &d->b_shift, (size_t)nbr, shift));
+    DC_RET(jg::dev_alloc(d, &d->part, (size_t)d->n_chunks * 4 * d->ld, (const double*)nullptr, true));
+    d->nbr = (int)nbr;
+    return 0;
+}
+
+int jg_dc_set_rating(int64_t h, const double* rating) {
+    DC_ENTER(h);
+    if (!d->nbr) return faild(1, "jg_dc_set_rating: jg_dc_set_branches first");
+    if (!rating) { d->b_rating = nullptr; return 0; }                     // (the buffer stays with the handle)
+    if (!d->rating_buf) DC_RET(jg::dev_alloc(d, &d->rating_buf, (size_t)d->nbr, (const double*)nullptr, true));
+    DC_API_HIP(jg::sync_copy(d->rating_buf, rating, (size_t)d->nbr * sizeof(double), hipMemcpyHostToDevice, d->stream));
+    d->b_rating = d->rating_buf;
+    return 0;
+}
+
+int jg_dc_set_outages(int64_t h, int64_t lane0, int64_t count, const int64_t* branch) {
+    DC_ENTER(h);
+    if (lane0 < 0 || count < 0 || lane0 + count > d->batch || (count && !branch)) return faild(1, "jg_dc_set_outages: lanes out of range");
+    if (!d->nbr) return faild(1, "jg_dc_set_outages: jg_dc_set_branches first");
+    if (!count) return 0;
+    std::vector<int> of(count), ot(count), ob(count);
+    std::vector<double> oy(count), os(count);
+    for (int64_t s = 0; s < count; ++s) {
+        const int64_t k = branch[s] - 1;
+        if (k < -1 || k >= d->nbr) return faild(1, "jg_dc_set_outages: branch index out of range");
+        if (k < 0) { of[s] = ot[s] = ob[s] = -1; oy[s] = os[s] = 0.0; continue; }
+        of[s] = d->h_from[k] == d->slack ? -1 : d->h_from[k];           // the slack's component of a = e_from - e_to is dropped
+        ot[s] = d->h_to[k] == d->slack ? -1 : d->h_to[k];
+        ob[s] = (int)k; oy[s] = d->h_y[k]; os[s] = d->h_shift[k] * d->h_y[k];
+    }
+    DC_API_HIP(hipMemcpyAsync(d->o_from + lane0, of.data(), count * sizeof(int), hipMemcpyHostToDevice, d->stream));
+    DC_API_HIP(hipMemcpyAsync(d->o_to + lane0, ot.data(), count * sizeof(int), hipMemcpyHostToDevice, d->stream));
+    DC_API_HIP(hipMemcpyAsync(d->o_br + lane0, ob.data(), count * sizeof(int), hipMemcpyHostToDevice, d->stream));
+    DC_API_HIP(hipMemcpyAsync(d->o_y + lane0, oy.data(), count * sizeof(double), hipMemcpyHostToDevice, d->stream));
+    DC_API_HIP(hipMemcpyAsync(d->o_sh + lane0, os.data(), count * sizeof(double), hipMemcpyHostToDevice, d->stream));
+    DC_API_HIP(hipStreamSynchronize(d->stream));                         // the host vectors go out of scope
+    d->solved = false;
+    return 0;
+}
+
+int jg_dc_solve(int64_t h) {
+    DC_ENTER(h);
+    if (d->base_dirty) DC_RET(jg::base_solve(d));
+    DC_RET(jg::solve_chain(d));
+    DC_API_HIP(hipStreamSynchronize(d->stream));
+    d->solved = true;
+    return 0;
+}
+
+int jg_dc_get_angle(int64_t h, double* theta, int32_t* status) {
+    DC_ENTER(h);
+    if (!d->solved) return faild(4, "jg_dc_get_angle: jg_dc_solve first");
+    const size_t n = (size_t)d->n, ld = (size_t)d->ld;
+    if (theta) {
+        std::vector<double> t(n * ld);
+        DC_API_HIP(jg::sync_copy(t.data(), d->TH, n * ld * sizeof(double), hipMemcpyDeviceToHost, d->stream));
+        for (size_t s = 0; s < (size_t)d->batch; ++s)
+            for (size_t i = 0; i < n; ++i) theta[s * n + i] = t[i * ld + s];
+    }
+    if (status) DC_API_HIP(jg::sync_copy(status, d->status, (size_t)d->batch * sizeof(int32_t), hipMemcpyDeviceToHost, d->stream));
+    return 0;
+}
+
+int jg_dc_angle_device(int64_t h, int64_t* info) {
+    DC_ENTER(h);
+    if (!info) return faild(1, "jg_dc_angle_device: null pointer");
+    info[0] = (int64_t)reinterpret_cast<intptr_t>(d->TH); info[1] = d->ld; info[2] = (int64_t)reinterpret_cast<intptr_t>(d->status);
+    return 0;
+}
+
+int jg_dc_get_flows(int64_t h, double* from) {
+    DC_ENTER(h);
+    if (!d->solved) return faild(4, "jg_dc_get_flows: jg_dc_solve first");
+    if (!from) return faild(1, "jg_dc_get_flows: null pointer");
+    DC_RET(jg::launch_flows(d, true));
+    const size_t nb = (size_t)d->nbr, ld = (size_t)d->ld;
+    std::vector<double> t(nb * ld);
+    DC_API_HIP(jg::sync_copy(t.data(), d->flows, nb * ld * sizeof(double), hipMemcpyDeviceToHost, d->stream));
+    for (size_t s = 0; s < (size_t)d->batch; ++s)
+        for (size_t k = 0; k < nb; ++k) from[s * nb + k] = t[k * ld + s];
+    return 0;
+}
+
+int jg_dc_screen(int64_t h, double* rec) {
+    DC_ENTER(h);
+    if (!d->solved) return faild(4, "jg_dc_screen: jg_dc_solve first");
+    if (!rec) return faild(1, "jg_dc_screen: null pointer");
+    DC_RET(jg::launch_flows(d, false));
+    DC_API_HIP(jg::sync_copy(rec, d->screen, (size_t)d->batch * 5 * sizeof(double), hipMemcpyDeviceToHost, d->stream));
+    return 0;
+}
+
+int jg_dc_screen_device(int64_t h, double* rec_dev) {
+    DC_ENTER(h);
+    if (!d->solved) return faild(4, "jg_dc_screen_device: jg_dc_solve first");
+    if (!rec_dev) return faild(1, "jg_dc_screen_device: null pointer");
+    DC_RET(jg::launch_flows(d, false));
+    DC_API_HIP(hipMemcpyAsync(rec_dev, d->screen, (size_t)d->batch * 5 * sizeof(double), hipMemcpyDeviceToDevice, d->stream));
+    DC_API_HIP(hipStreamSynchronize(d->stream));
+    return 0;
+}
+
+int jg_dc_pack_results_device(int64_t h, double* dst_dev) {
+    DC_ENTER(h);
+    if (!d->solved) return faild(4, "jg_dc_pack_results_device: jg_dc_solve first");
+    if (!dst_dev) return faild(1, "jg_dc_pack_results_device: null pointer");
+    hipLaunchKernelGGL(jg::k_dc_pack, dim3((d->n + 1 + 3) / 4, d->ld / 64), dim3(64, 4), 0, d->stream, d->TH, d->status, dst_dev, d->n, d->ld, d->batch);
+    DC_API_HIP(hipGetLastError());
+    DC_API_HIP(hipStreamSynchronize(d->stream));
+    return 0;
+}
+
+int jg_dc_time_kernel(int64_t h, int kernel, int reps, double* ms) {
+    DC_ENTER(h);
+    if (!ms || reps < 1 || kernel < 0 || kernel > 3) return faild(1, "jg_dc_time_kernel: bad argument");
+    if (!d->solved) return faild(4, "jg_dc_time_kernel: jg_dc_solve first");
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    int rc = 0;
+    std::string msg;
+    auto hip = [&](hipError_t e, const char* what) { if (e != hipSuccess && !rc) { rc = 2; msg = std::string(what) + ": " + hipGetErrorString(e); } return e == hipSuccess; };
+    if (hip(hipEventCreate(&e0), "hipEventCreate") && hip(hipEventCreate(&e1), "hipEventCreate"))
+        for (int r = 0; r < reps && !rc; ++r) {
+            if (!hip(hipEventRecord(e0, d->stream), "hipEventRecord")) break;
+            if (kernel == 0) { rc = jg::solve_chain(d); if (!rc) rc = jg::launch_flows(d, false); }
+            else if (kernel == 1) jg::sweep_pair<1>(d, nullptr, d->W, d->Z, d->ld, d->ld / 64, nullptr);
+            else if (kernel == 2) jg::launch_combine(d);
+            else rc = jg::launch_flows(d, false);
+            if (rc) { msg = d->error; break; }
+            float t = 0.f;
+            if (!hip(hipEventRecord(e1, d->stream), "hipEventRecord") || !hip(hipEventSynchronize(e1), "hipEventSynchronize") ||
+                !hip(hipEventElapsedTime(&t, e0, e1), "hipEventElapsedTime")) break;
+            ms[r] = (double)t;
+        }
+    if (e0) (void)hipEventDestroy(e0);                                  // on every path
+    if (e1) (void)hipEventDestroy(e1);
+    return rc ? faild(rc, msg) : 0;
+}
+
+}  // extern "C"

@@ -1,0 +1,76 @@
+// jg_dc.hpp -- DC power flow and the batched DC N-1 screen on ONE shared scalar factor.
+//
+// Reference counterpart: dcPowerFlow / solve! (src/powerFlow/dcPowerFlow.jl:42-134: the slack row and column leave the nodal matrix
+// B of dcModel! (src/powerSystem/model.jl:161-262), theta = B^-1 (supply - demand - shunt conductance - shiftPower)), and the user loop
+// updateBranch!(analysis; label, status = 0) -> solve! that a planning tool runs over every branch before it spends an AC solve on the few that matter.
+// An outage of branch k = (i, j) with admittance y_k moves the matrix by a rank-1 term and the right-hand side along the same vector:
+//     B_s = B - y_k a a',   rhs_s = rhs - shiftAngle_k y_k a,   a = e_i - e_j  (the slack's component dropped)
+// so the whole batch needs ONE factor, formed once per base case and never redone (nothing is iterated):
+//     z_s     = B^-1 a                                   one sweep pair per scenario on the shared factor
+//     x_s     = theta_0 - shiftAngle_k y_k z_s           theta_0 = B^-1 rhs, once per base; a lane with injections of its own: x_s = B^-1 rhs_s - ...
+//     theta_s = x_s + z_s y_k (a' x_s) / (1 - y_k a' z_s)
+// 1 - y_k a' z_s = 0: the branch is a bridge, the scenario gets status 3 (the code of islanding outages) and its angles are NaN.
+//
+// It is the scalar counterpart of jg_comp.hip: the factor VALUES are wave-uniform (scalar loads of a few hundred KB), a wavefront is one row x 64
+// scenarios, the only vector traffic is the right-hand sides (8 bytes per row and scenario), batch-minor with ld = batch rounded up to 64.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <vector>
+
+#include "jg_symbolic.hpp"
+
+namespace jg {
+
+constexpr int DC_T = 4;            // terms per step of a sweep row: the rows' lists are padded to it (pad = factor value 0 x the zero row n of the scratch)
+constexpr int DC_CHAIN_WAVES = 16; // a level of at most this many rows is "narrow": runs of narrow levels are ONE launch (workgroup barriers between levels)
+constexpr double DC_SINGULAR = 1e-9;   // |1 - y_k a' z_s| below it: bridge.  The two sides of the difference are O(1) and carry the rounding of one sweep pair
+                                       // (1e-13 on the 10k-bus grid); the smallest denominator of a non-bridge there is 3e-3.
+
+struct DcSweepTables {             // one triangle of the factor, rows grouped by dependency level
+    int* rows = nullptr;           // [n] pivots, level-major
+    int* lev = nullptr;            // [levels + 1] offsets into rows
+    int* ptr = nullptr;            // [n + 1] offsets of the padded term lists (multiples of DC_T)
+    int* col = nullptr;            // [terms] pivot of the operand row (n = the zero row)
+    double* val = nullptr;         // [terms] premultiplied factor value, in list order (k_dc_compact)
+    std::vector<int> h_lev;
+    long long terms = 0;
+    struct Launch { int l0, l1, chain; };     // levels [l0, l1): a chain launch, or one wide level
+    std::vector<Launch> launches;
+};
+
+struct DcHandle {
+    int n = 0, nbr = 0, batch = 0, ld = 0, device = 0, slack = 0, n_entries = 0, n_fact_levels = 0;
+    double slack_angle = 0.0;
+    hipStream_t stream = nullptr;
+    std::string error;
+    // factor (the factorisation tables, A, X and bad live only inside jg_dc_create)
+    int* perm = nullptr;                                    // [n] pivot -> bus
+    int* f_ent = nullptr; std::vector<int> f_lev;           // entries by factorisation level
+    int* t_ptr = nullptr; int* t_a = nullptr; int* t_d = nullptr; int* t_b = nullptr;
+    int* e_src = nullptr; int* diag = nullptr;
+    double* A = nullptr;                                    // [nnz] row-CSR values, slack row / column as identity
+    double* X = nullptr;                                    // [n_entries] factor, A = Lh D^-1 U
+    double* dinv = nullptr;                                 // [n]
+    int* bad = nullptr;                                     // zero / non-finite pivot flag
+    DcSweepTables fwd, bwd;
+    // base solve (one lane group, lane 0 carries the base case)
+    double* rhs0 = nullptr; double* W0 = nullptr; double* th0 = nullptr;      // [n][64], [n + 1][64], [n][64]
+    std::vector<double> h_rhs; bool base_dirty = true;
+    // batch
+    double* W = nullptr; double* Z = nullptr; double* TH = nullptr;           // [n + 1][ld], [n][ld], [n][ld]
+    double* RHS = nullptr; double* XS = nullptr;                              // per-scenario injections (allocated on first use)
+    int* ginj = nullptr; int* glist = nullptr; std::vector<int> h_ginj; int n_glist = 0;   // lane groups with injections of their own
+    int* o_from = nullptr; int* o_to = nullptr; int* o_br = nullptr; double* o_y = nullptr; double* o_sh = nullptr;   // [ld] the lanes' outages
+    int* status = nullptr;                                                     // [ld]
+    // branches
+    std::vector<int> h_from, h_to; std::vector<double> h_y, h_shift;
+    int* b_from = nullptr; int* b_to = nullptr; double* b_y = nullptr; double* b_shift = nullptr; double* b_rating = nullptr; double* rating_buf = nullptr;
+    double* flows = nullptr; double* part = nullptr; double* screen = nullptr;  // [nbr][ld], [chunks][4][ld], [ld][5]
+    int n_chunks = 0;
+    bool solved = false;
+    std::vector<void*> allocs;                                                 // everything the handle owns on the device
+};
+
+}  // namespace jg

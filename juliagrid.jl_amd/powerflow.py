@@ -23,6 +23,7 @@ from types import SimpleNamespace as NS
 import numpy as np
 
 from . import _lib
+from . import dcpowerflow as _dc
 from .system import (CscMatrix, PowerSystem, acModel_, updateBranch_ as _update_branch_system,
                      updateBus_ as _update_bus_system, updateGenerator_ as _update_generator_system)
 
@@ -297,9 +298,15 @@ def _push_voltage(an: AcPowerFlow, vm, va):
         an.voltage.magnitude, an.voltage.angle = an._shape(vm.reshape(an.batch, n).copy()), an._shape(va.reshape(an.batch, n).copy())
 
 
-def setInjection_(an: AcPowerFlow, active=None, reactive=None):
+def setInjection_(an: AcPowerFlow, active=None, reactive=None, scenario0: int = 0):
     """Net injections supply - demand per scenario ([n] broadcast or [batch, n]);
     default = the system's own bus.supply - bus.demand (acPowerFlow.jl:676-680)."""
+    if isinstance(an, _dc.DcPowerFlow):
+        if reactive is not None:
+            raise ValueError("setInjection_: a DcPowerFlow has no reactive injections")
+        return _dc.setInjection_(an, active, scenario0)                # (scenario0: the DC analysis only -- lanes scenario0 .. get injections of their own)
+    if scenario0:
+        raise ValueError("setInjection_: scenario0 belongs to a DcPowerFlow; an AC analysis takes [n] or [batch, n]")
     bus = an.system.bus
     p = bus.supply.active - bus.demand.active if active is None else active
     q = bus.supply.reactive - bus.demand.reactive if reactive is None else reactive
@@ -508,7 +515,9 @@ def _check_signature(an: AcPowerFlow):
 
 
 def solve_(an: AcPowerFlow):
-    """solve!(analysis): Jacobian fill + refactorization + solve + state update on the device."""
+    """solve!(analysis): Jacobian fill + refactorization + solve + state update on the device (a DcPowerFlow: dcpowerflow.solve_)."""
+    if isinstance(an, _dc.DcPowerFlow):
+        return _dc.solve_(an)
     _check_signature(an)
     fn = _lib.lib().jg_nr_fast_solve if getattr(an.method, "fast", False) else _lib.lib().jg_nr_solve
     _lib.check(fn(an._h))
@@ -516,10 +525,13 @@ def solve_(an: AcPowerFlow):
     an._pull_voltage()
 
 
-def powerFlow_(an: AcPowerFlow, iteration: int = 20, tolerance: float = 1e-8, fetch: bool = True):
-    """powerFlow!(analysis; iteration, tolerance). Sets analysis.method.iteration (array if batch > 1)
+def powerFlow_(an: AcPowerFlow, iteration: int = 20, tolerance: float = 1e-8, fetch: bool = True, power: bool = False):
+    """powerFlow!(analysis; iteration, tolerance, power). Sets analysis.method.iteration (array if batch > 1)
     and analysis.status (0 converged, 1 iteration limit, 3 numeric failure).  fetch=False leaves the
-    voltages in HBM (batched loops read them later through analysis._pull_voltage / voltage_device)."""
+    voltages in HBM (batched loops read them later through analysis._pull_voltage / voltage_device).
+    power=True: power!(analysis) follows.  A DcPowerFlow is solved directly (dcpowerflow.powerFlow_)."""
+    if isinstance(an, _dc.DcPowerFlow):
+        return _dc.powerFlow_(an, power=power)
     _check_signature(an)
     it = np.zeros(an.batch, dtype=np.int32)
     st = np.zeros(an.batch, dtype=np.int32)
@@ -529,6 +541,8 @@ def powerFlow_(an: AcPowerFlow, iteration: int = 20, tolerance: float = 1e-8, fe
     an.status = int(st[0]) if an.batch == 1 else st
     if fetch:
         an._pull_voltage()
+    if power:
+        power_(an)
 
 
 def setInitialPoint_(an: AcPowerFlow, source=None):
@@ -679,6 +693,8 @@ def setOutage_(an: AcPowerFlow, scenario: int, label: int | None):
 def setOutages_(an: AcPowerFlow, labels, scenario0: int = 0):
     """setOutage_ for consecutive scenarios in ONE upload: scenario scenario0 + s = base grid with branch labels[s] out
     of service (0 / None = base grid)."""
+    if isinstance(an, _dc.DcPowerFlow):
+        return _dc.setOutages_(an, labels, scenario0)
     lab = np.array([int(x) if x else 0 for x in labels], dtype=np.int64)
     labels = [int(x) for x in lab]
     tptr, tdy = outagePatchTable(an.system)
@@ -738,7 +754,10 @@ def _ns2(an, buf, names=("active", "reactive")):
 def power_(an: AcPowerFlow):
     """power!(analysis::AcPowerFlow) (src/postprocessing/acAnalysis.jl:30-169) at the current state of EVERY scenario:
     the Ybus row walk (injections) and the branch formulas run on the device, the O(n) bus / generator bookkeeping
-    (shunt :884-889, supply :53-61, generators :84-166) on the host.  Arrays are [batch, ...] (1-D for batch 1)."""
+    (shunt :884-889, supply :53-61, generators :84-166) on the host.  Arrays are [batch, ...] (1-D for batch 1).
+    A DcPowerFlow: power!(analysis::DcPowerFlow), dcpowerflow.power_."""
+    if isinstance(an, _dc.DcPowerFlow):
+        return _dc.power_(an)
     system, bus, gen = an.system, an.system.bus, an.system.generator
     if an.batch > 1 and getattr(an, "_lane_types", False):
         typ_lanes, _ = busType(an)

@@ -79,6 +79,7 @@ class PowerSystem:
         self.model = NS(
             ac=NS(nodalMatrix=None, nodalMatrixTranspose=None, nodalFromFrom=None, nodalFromTo=None,
                   nodalToTo=None, nodalToFrom=None, admittance=None),
+            dc=NS(nodalMatrix=None, admittance=None, shiftPower=None),
             revision=NS(topology=0, type=0, slack=0, acModel=0, acPattern=0),
         )
 
@@ -260,6 +261,50 @@ def acModel_(system: PowerSystem) -> None:
     # and value p of the transpose is Y[col, row] of pointer p.
     ac.nodalMatrixTranspose = CscMatrix(n, colptr.copy(), rowval.copy(), _transpose_values(ac.nodalMatrix))
     ac.admittance, ac.nodalFromFrom, ac.nodalFromTo, ac.nodalToTo, ac.nodalToFrom = y, yff, yft, ytt, ytf
+
+
+def dcModel_(system: PowerSystem) -> None:
+    """dcModel!(system): branch admittances 1 / (turnsRatio * reactance), shiftPower and the nodal matrix B.
+
+    Reference: src/powerSystem/model.jl:161-209 with the CSC builder of src/backend/sparse.jl:2-101 -- a column holds its diagonal entry first,
+    then the branch stamps in branch order, stably sorted by row, duplicates summed in that order; an out-of-service branch stores zeros.
+    """
+    n, nb = system.bus.number, system.branch.number
+    lay, par = system.branch.layout, system.branch.parameter
+    f = lay.from_ - 1
+    t = lay.to - 1
+    on = lay.status == 1
+    with np.errstate(divide="ignore", invalid="ignore"):
+        y = np.where(on, 1.0 / (par.turnsRatio * par.reactance), 0.0)
+    shift = np.where(on, par.shiftAngle * y, 0.0)
+    shiftPower = np.zeros(n)
+    idx = np.empty(2 * nb, dtype=np.int64)
+    idx[0::2], idx[1::2] = f, t
+    val = np.empty(2 * nb)
+    val[0::2], val[1::2] = -shift, shift
+    np.add.at(shiftPower, idx, val)                                   # sequential, branch order (model.jl:176-184)
+    diag = np.zeros(n)
+    val[0::2], val[1::2] = y, y
+    np.add.at(diag, idx, val)                                         # model.jl:197-201
+    rows = np.empty(2 * nb, dtype=np.int64)
+    cols = np.empty(2 * nb, dtype=np.int64)
+    rows[0::2], cols[0::2] = f, t                                     # addEntry!(builder, from, to, -y), then (to, from)
+    rows[1::2], cols[1::2] = t, f
+    rows = np.concatenate([np.arange(n), rows])
+    cols = np.concatenate([np.arange(n), cols])
+    vals = np.concatenate([diag, np.repeat(-y, 2)])
+    order = np.lexsort((np.arange(rows.size), rows, cols))           # stable by (col, row, insertion)
+    rows, cols, vals = rows[order], cols[order], vals[order]
+    first = np.ones(rows.size, dtype=bool)
+    first[1:] = (rows[1:] != rows[:-1]) | (cols[1:] != cols[:-1])
+    group = np.cumsum(first) - 1
+    nzval = np.zeros(int(group[-1]) + 1)
+    np.add.at(nzval, group, vals)
+    colptr = np.zeros(n + 1, dtype=np.int64)
+    np.add.at(colptr, cols[first] + 1, 1)
+    dc = system.model.dc
+    dc.nodalMatrix = CscMatrix(n, np.cumsum(colptr) + 1, rows[first] + 1, nzval)
+    dc.admittance, dc.shiftPower = y, shiftPower
 
 
 def _transpose_perm(A: CscMatrix) -> np.ndarray:
