@@ -1305,10 +1305,186 @@ function timeKernel(b::DcPowerFlowBatch, kernel::Int, reps::Int = 20)
     return ms
 end
 
+# ---- DC state estimation with batched bad-data removal (jgrid.h: jg_dcse_*; csrc/jg_dcse.hip) ------------------------------------------------
+# dcStateEstimation / solve! / power! / residualTest! / chiTest (src/stateEstimation/dcStateEstimation.jl:42-151, 342-434, badData.jl:48-117, 963-977) for
+# `batch` realisations of one measurement set on ONE factor of the gain matrix.  The C handle is an Int64 token.
+"""
+    DcStateEstimationBatch
+
+What `dcStateEstimation(monitoring, HIP; batch)` returns: `se` is the reference's WLS model (coefficient, mean, precision, index, built by the reference's
+own `dcStateEstimationWls`), `readings` [row, batch] the lanes' means, `angle` [bus, batch], `status` and `objective` per lane after `solve!`.
+"""
+mutable struct DcStateEstimationBatch
+    token::Int64
+    system::PowerSystem
+    monitoring::Measurement
+    se::Any
+    correct::Int64
+    batch::Int64
+    readings::Matrix{Float64}
+    angle::Matrix{Float64}
+    status::Vector{Int32}
+    objective::Vector{Float64}
+    from::Matrix{Float64}
+    rowStatus::Vector{Int32}
+    stale::Bool
+end
+"rows of se.coefficient as 0-based row pointers, 1-based ascending columns and values with every status taken as 1"
+function dcseRows(system::PowerSystem, monitoring::Measurement, coefficient)
+    dc = system.model.dc
+    Ht = sparse(transpose(coefficient))
+    rowptr = Ht.colptr .- 1
+    col = copy(Ht.rowval)
+    val = copy(Ht.nzval)
+    watt = monitoring.wattmeter
+    for i = 1:watt.number                                 # out-of-service rows hold stored zeros: their values with status 1 come from the model
+        k = watt.layout.index[i]
+        for p in Ht.colptr[i]:(Ht.colptr[i + 1] - 1)
+            if watt.layout.bus[i]
+                val[p] = dc.nodalMatrix[col[p], k]
+            else
+                a = watt.layout.from[i] ? dc.admittance[k] : -dc.admittance[k]
+                val[p] = col[p] == system.branch.layout.from[k] ? a : -a
+            end
+        end
+    end
+    for p in Ht.colptr[watt.number + 1]:(Ht.colptr[end] - 1)
+        val[p] = 1.0
+    end
+    return rowptr, col, val
+end
+function dcseRowStatus(monitoring::Measurement, index, number::Int64)
+    status = ones(Int32, number)
+    status[1:monitoring.wattmeter.number] .= monitoring.wattmeter.active.status
+    for (i, row) in index
+        status[row] = monitoring.pmu.angle.status[i]
+    end
+    return status
+end
+function JuliaGrid.dcStateEstimation(monitoring::Measurement, ::Type{T}; batch::Int64 = 1, device::Int64 = 0) where T <: Union{HIP, HIPOrthogonal}
+    system = monitoring.system
+    coefficient, mean, precision, power, index, number, inservice = JuliaGrid.dcStateEstimationWls(system, monitoring)
+    se = (coefficient = coefficient, mean = mean, precision = precision, index = index, number = number, inservice = inservice)
+    rowptr, col, val = dcseRows(system, monitoring, coefficient)
+    status = dcseRowStatus(monitoring, index, number)
+    slack = system.bus.layout.slack
+    token = Ref{Int64}(0)
+    check(ccall((:jg_dcse_create, lib), Cint, (Ref{Int64}, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Int64, Float64, Int64, Cint),
+        token, system.bus.number, number, rowptr, col, val, precision.nzval, status, slack, system.bus.voltage.angle[slack], batch, device))
+    b = DcStateEstimationBatch(token[], system, monitoring, se, T === HIPOrthogonal ? 1 : 0, batch, repeat(mean, 1, batch), zeros(system.bus.number, batch),
+        zeros(Int32, batch), zeros(batch), zeros(system.branch.number, batch), status, true)
+    finalizer(x -> (x.token != 0 && ccall((:jg_dcse_destroy, lib), Cvoid, (Int64,), x.token); x.token = 0), b)
+    br = system.branch
+    check(ccall((:jg_dcse_set_branches, lib), Cint, (Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}),
+        b.token, br.number, br.layout.from, br.layout.to, system.model.dc.admittance, br.parameter.shiftAngle))
+    return b
+end
+"{n, m, batch, ld, entries of G, factor entries, factorisation levels, forward levels, backward levels, sweep launches, sweep terms, refactorisations, Omega runs, largest |S|}"
+function dims(b::DcStateEstimationBatch)
+    d = zeros(Int64, 14)
+    check(ccall((:jg_dcse_dims, lib), Cint, (Int64, Ptr{Int64}), b.token, d))
+    return d
+end
+"the means of lanes lane0 .. (0-based), a [row, count] matrix in the order of se.mean"
+function setReadings!(b::DcStateEstimationBatch, z::Matrix{Float64}; lane0::Int64 = 0)
+    b.readings[:, (lane0 + 1):(lane0 + size(z, 2))] .= z
+    check(ccall((:jg_dcse_set_readings, lib), Cint, (Int64, Int64, Int64, Ptr{Float64}), b.token, lane0, size(z, 2), z))
+    return nothing
+end
+"solve!(analysis) for every lane (dcStateEstimation.jl:342-434); lanes with removed rows are compensated on the shared factor"
+function JuliaGrid.solve!(b::DcStateEstimationBatch)
+    if b.stale
+        check(ccall((:jg_dcse_set_readings, lib), Cint, (Int64, Int64, Int64, Ptr{Float64}), b.token, 0, b.batch, b.readings))
+        b.stale = false
+    end
+    check(ccall((:jg_dcse_solve, lib), Cint, (Int64, Cint), b.token, b.correct))
+    check(ccall((:jg_dcse_get_angle, lib), Cint, (Int64, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}), b.token, b.angle, b.status, b.objective))
+    return nothing
+end
+"power!(analysis) branch part (dcAnalysis.jl:353-374): from [branch, batch]; to = -from"
+function JuliaGrid.power!(b::DcStateEstimationBatch)
+    check(ccall((:jg_dcse_get_flows, lib), Cint, (Int64, Ptr{Float64}), b.token, b.from))
+    return nothing
+end
+"""
+    residualTest!(b::DcStateEstimationBatch; threshold = 3.0) -> (detect, maxNormalizedResidual, index)
+
+Per lane (badData.jl:48-117).  A lane of a batch whose maximum exceeds the threshold drops that row by compensation; a handle of batch 1 follows the
+reference: the row's status becomes 0 and the gain is re-assembled and refactorised.
+"""
+function JuliaGrid.residualTest!(b::DcStateEstimationBatch; threshold::Float64 = 3.0)
+    mx = zeros(b.batch)
+    idx = zeros(Int32, b.batch)
+    check(ccall((:jg_dcse_residual_test, lib), Cint, (Int64, Float64, Cint, Ptr{Float64}, Ptr{Int32}), b.token, threshold, b.batch == 1 ? 0 : 1, mx, idx))
+    if b.batch == 1 && mx[1] > threshold && idx[1] > 0
+        b.rowStatus[idx[1]] = 0
+        b.readings[idx[1], 1] = 0.0
+        b.stale = true
+        check(ccall((:jg_dcse_set_weights, lib), Cint, (Int64, Ptr{Float64}, Ptr{Int32}), b.token, b.se.precision.nzval, b.rowStatus))
+    end
+    return (detect = mx .> threshold, maxNormalizedResidual = mx, index = idx)
+end
+"every normalised residual of the current estimate, [row, batch]"
+function normalizedResiduals(b::DcStateEstimationBatch)
+    r = Matrix{Float64}(undef, b.se.number, b.batch)
+    check(ccall((:jg_dcse_get_normalized_residual, lib), Cint, (Int64, Ptr{Float64}), b.token, r))
+    return r
+end
+"lane s drops row rows[s] of se.mean (0: none) by compensation, whatever its residual"
+removeRows!(b::DcStateEstimationBatch, rows::Vector{Int32}) = check(ccall((:jg_dcse_remove_rows, lib), Cint, (Int64, Ptr{Int32}), b.token, rows))
+"(rows [largest |S|, batch] (0: none), count [batch]) of the measurements the lanes have removed"
+function removedRows(b::DcStateEstimationBatch)
+    rows = zeros(Int32, dims(b)[14], b.batch)
+    count = zeros(Int32, b.batch)
+    check(ccall((:jg_dcse_get_removed, lib), Cint, (Int64, Ptr{Int32}, Ptr{Int32}), b.token, rows, count))
+    return rows, count
+end
+"chiTest(analysis; confidence) per lane (badData.jl:963-977): (detect, threshold, objective)"
+function chiTest(b::DcStateEstimationBatch; confidence::Float64 = 0.95)
+    _, gone = removedRows(b)
+    df = sum(b.rowStatus) .- gone .- b.system.bus.number .+ 1
+    chi = [JuliaGrid.quantile(JuliaGrid.Chisq(d), confidence) for d in df]
+    return (detect = b.objective .>= chi, threshold = chi, objective = b.objective)
+end
+"the analysis follows a changed status or variance: re-assembly and ONE numeric refactorisation (powermeter.jl:704-757, pmu.jl:877-899)"
+function refreshWeights!(b::DcStateEstimationBatch)
+    b.rowStatus = dcseRowStatus(b.monitoring, b.se.index, b.se.number)
+    precision = 1.0 ./ vcat(b.monitoring.wattmeter.active.variance, [b.monitoring.pmu.angle.variance[i] for (i, row) in b.se.index])
+    check(ccall((:jg_dcse_set_weights, lib), Cint, (Int64, Ptr{Float64}, Ptr{Int32}), b.token, precision, b.rowStatus))
+    return nothing
+end
+"updateWattmeter!(analysis; label, active, variance, status): a reading moves the row's mean in every lane; a status or variance refactorises once"
+function JuliaGrid.updateWattmeter!(b::DcStateEstimationBatch; label, active = nothing, variance = nothing, status = nothing)
+    updateWattmeter!(b.monitoring; label = label, (k => v for (k, v) in pairs((active = active, variance = variance, status = status)) if v !== nothing)...)
+    refreshRow!(b)
+    (variance !== nothing || status !== nothing) && refreshWeights!(b)
+    return nothing
+end
+"updatePmu!(analysis; label, angle, varianceAngle, statusAngle)"
+function JuliaGrid.updatePmu!(b::DcStateEstimationBatch; label, angle = nothing, varianceAngle = nothing, statusAngle = nothing)
+    updatePmu!(b.monitoring; label = label, (k => v for (k, v) in pairs((angle = angle, varianceAngle = varianceAngle, statusAngle = statusAngle)) if v !== nothing)...)
+    refreshRow!(b)
+    (varianceAngle !== nothing || statusAngle !== nothing) && refreshWeights!(b)
+    return nothing
+end
+"se.mean follows the Measurement container; every lane restarts from it"
+function refreshRow!(b::DcStateEstimationBatch)
+    mean = JuliaGrid.dcStateEstimationWls(b.system, b.monitoring)[2]
+    b.readings .= mean
+    b.stale = true
+    return nothing
+end
+"milliseconds of `reps` runs (HIP events): 0 the chain of a batch, 1 right-hand side, 2 sweep pair, 3 residual pass, 4 normalised pass, 5 Omega diagonal + pass"
+function timeKernel(b::DcStateEstimationBatch, kernel::Int, reps::Int = 20)
+    ms = zeros(Float64, reps)
+    check(ccall((:jg_dcse_time_kernel, lib), Cint, (Int64, Cint, Cint, Ptr{Float64}), b.token, kernel, reps, ms))
+    return ms
+end
+
 export HIP, HIPOrthogonal, NewtonRaphsonBatch, BaseCase, baseInfo, baseInverseOnPattern, attach!, startFromBase!, firstIteration!, firstIterationCounts, setOutages!, shareDevice!, branchQuantities, screenSummary, powerFlowDefer!, moveLanes!, finish!, resume!, jacobian!,
        largestNormalizedResidual, normalizedResiduals, commUniqueId, Comm, shard, contingencyAnalysis, clearPlanCache,
        deviceCount, dims, setRefinement!, deviceMaps, setOutage!, snapshotVoltage!, restoreVoltage!, iterations, voltageDevice!, packResults!, packRows!,
        allgatherDevice, commRank, commWorld, timeKernel, setBusType!, busType, GaussNewtonBatch, setRealisations!, monteCarloEstimation, fastPatch!, setReadings!, drawNoise!, measurementDevice,
-       DcPowerFlowBatch, setInjections!, fromPower, angleDevice
+       DcPowerFlowBatch, setInjections!, fromPower, angleDevice, DcStateEstimationBatch, removedRows, removeRows!
 
 end # module

@@ -515,6 +515,66 @@ int jg_dc_pack_results_device(int64_t h, double* dst_dev);
 int jg_dc_time_kernel(int64_t h, int kernel, int reps, double* ms);
 
 /* ---------------------------------------------------------------------------------------------
+ * DC state estimation with batched bad-data removal (csrc/jg_dcse.hip)
+ * ------------------------------------------------------------------------------------------- */
+
+/*
+ * The handle is an int64 TOKEN (0 = none), like the DC power flow's.
+ *
+ * dcStateEstimation(monitoring)  -- src/stateEstimation/dcStateEstimation.jl:42-151 with the factorisation of the first solve! (:342-371): the slack's
+ * column leaves the coefficient matrix H, G = H' W H with G[slack, slack] = 1 is assembled on the device from H's values x status x precision and
+ * factorised ONCE (scalar LU on the elimination order and dependency levels of G's pattern, no pivoting: G is positive definite for an observable set).
+ *   n, m            buses, rows of se.coefficient (wattmeters in stored order, then PMUs at buses)
+ *   rowptr,col,val  H by rows: rowptr 0-based [m + 1], col 1-based and ascending inside a row, val with every status taken as 1 (the stored zeros of an
+ *                   out-of-service row keep their pattern: a status change needs no new symbolic analysis)
+ *   precision       1 / variance per row, out-of-service rows included;  status 0 / 1 per row
+ *   slack           bus.layout.slack (1-based);  slack_angle = bus.voltage.angle[slack] (addSlackAngle!, src/backend/utility.jl:610-622)
+ *   batch           realisations resident on the device (lanes, batch-minor with a leading dimension of batch rounded up to 64)
+ * Return code 3: zero / non-finite pivot -- the set does not make the grid observable.
+ * jg_dcse_dims: {n, m, batch, ld, entries of G, factor entries, factorisation levels, forward levels, backward levels, launches of a sweep pair, padded
+ * sweep terms, numeric refactorisations since create, runs of the Omega diagonal, largest number of removed rows per lane}.
+ * jg_dcse_set_weights: updateWattmeter! / updatePmu! of a status or a variance (src/measurement/powermeter.jl:704-757, pmu.jl:877-899, signature[:run]):
+ * re-assembles G and refactorises numerically; the lanes' removed rows are forgotten.  A changed READING is jg_dcse_set_readings alone.
+ */
+int jg_dcse_create(int64_t* h, int64_t n, int64_t m, const int64_t* rowptr, const int64_t* col, const double* val, const double* precision,
+                   const int32_t* status, int64_t slack, double slack_angle, int64_t batch, int device);
+void jg_dcse_destroy(int64_t h);
+int jg_dcse_dims(int64_t h, int64_t* dims14);
+int jg_dcse_set_weights(int64_t h, const double* precision, const int32_t* status);
+/*
+ * se.mean of lanes lane0 .. lane0 + count - 1, z [count][m] in row order (meanPi / meanPij / meanθi already applied, src/backend/equations.jl:121, 178,
+ * 461; rows out of service are ignored).
+ * jg_dcse_solve: solve!(analysis) for every lane (:342-371): b = H' W z, one sweep pair on the shared factor, one residual pass (objective).  correct = 1
+ * (the Orthogonal / PetersWilkinson tags, :373-434): one more step theta += G^-1 H' W (z - H theta) on the same factor.  A lane with removed rows gets
+ * theta' = x - U Omega_SS^-1 r_S (csrc/jg_dcse.hpp) instead of a refactorisation.
+ *   jg_dcse_get_angle   theta [batch][n] = analysis.voltage.angle, status [batch] (0; 1: a removed row was critical -- without it the grid is unobservable;
+ *                       2: more than the largest number of removed rows; both with NaN angles), objective [batch] = sum w r^2 of chiTest
+ *                       (src/stateEstimation/badData.jl:963-977); each may be NULL
+ * jg_dcse_residual_test: residualTest!(analysis; threshold) (badData.jl:48-117) for every lane: the largest normalised residual
+ * |r_i| / sqrt(|1 / w_i - h_i G^-1 h_i'|) and its row (1-based, first on ties, 0: every residual is 0; rows out of service or with r == 0 are skipped).
+ * The Omega diagonal is formed once per factor and shared by all lanes.  remove = 1: a lane whose maximum exceeds the threshold drops that row -- one
+ * more sweep pair for its column of U; the next jg_dcse_solve compensates.  remove = 0 (a handle of batch 1 follows the reference: the caller sets the
+ * status to 0 and calls jg_dcse_set_weights).
+ *   jg_dcse_remove_rows               lane s drops row rows[s] (1-based, 0: none) whatever its residual: the caller knows the meter is bad
+ *   jg_dcse_get_normalized_residual   every normalised residual of the current estimate, [batch][m]
+ *   jg_dcse_get_removed               rows [batch][largest number] (1-based, 0: none), count [batch]
+ *   jg_dcse_set_branches / jg_dcse_get_flows   power!(analysis) branch part (src/postprocessing/dcAnalysis.jl:106-131 with allPowerBranch): the arguments
+ *                                     of jg_dc_set_branches; from [batch][branches], to = -from
+ *   jg_dcse_time_kernel   milliseconds (HIP events) of `reps` runs of: 0 the chain of a batch, 1 the right-hand side, 2 the sweep pair, 3 the residual
+ *                         pass, 4 the normalised residual pass, 5 the Omega diagonal + that pass; ms [reps]
+ */
+int jg_dcse_set_readings(int64_t h, int64_t lane0, int64_t count, const double* z);
+int jg_dcse_solve(int64_t h, int correct);
+int jg_dcse_get_angle(int64_t h, double* theta, int32_t* status, double* objective);
+int jg_dcse_residual_test(int64_t h, double threshold, int remove, double* maximum, int32_t* index);
+int jg_dcse_remove_rows(int64_t h, const int32_t* rows);
+int jg_dcse_get_normalized_residual(int64_t h, double* r);
+int jg_dcse_get_removed(int64_t h, int32_t* rows, int32_t* count);
+int jg_dcse_set_branches(int64_t h, int64_t nbr, const int64_t* from, const int64_t* to, const double* admittance, const double* shift_angle);
+int jg_dcse_get_flows(int64_t h, double* from);
+int jg_dcse_time_kernel(int64_t h, int kernel, int reps, double* ms);
+
+/* ---------------------------------------------------------------------------------------------
  * Symbolic analysis only (no device needed): the static schedule that replaces the symbolic half
  * of `lu`/`klu` (src/backend/utility.jl:470-476, 486-492).  Used by the CPU test-suite to replay
  * and race-check the schedule.  pattern: 0-based int32 block CSR, structurally symmetric, full

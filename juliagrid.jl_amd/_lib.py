@@ -153,6 +153,19 @@ def lib():
         "jg_dc_screen_device": [C.c_int64, VP],
         "jg_dc_pack_results_device": [C.c_int64, VP],
         "jg_dc_time_kernel": [C.c_int64, C.c_int, C.c_int, F64P],
+        "jg_dcse_create": [C.POINTER(C.c_int64), C.c_int64, C.c_int64, I64P, I64P, F64P, F64P, I32P, C.c_int64, C.c_double, C.c_int64, C.c_int],
+        "jg_dcse_dims": [C.c_int64, I64P],
+        "jg_dcse_set_weights": [C.c_int64, F64P, I32P],
+        "jg_dcse_set_readings": [C.c_int64, C.c_int64, C.c_int64, F64P],
+        "jg_dcse_solve": [C.c_int64, C.c_int],
+        "jg_dcse_get_angle": [C.c_int64, VP, VP, VP],
+        "jg_dcse_residual_test": [C.c_int64, C.c_double, C.c_int, F64P, I32P],
+        "jg_dcse_remove_rows": [C.c_int64, I32P],
+        "jg_dcse_get_normalized_residual": [C.c_int64, F64P],
+        "jg_dcse_get_removed": [C.c_int64, I32P, I32P],
+        "jg_dcse_set_branches": [C.c_int64, C.c_int64, I64P, I64P, F64P, F64P],
+        "jg_dcse_get_flows": [C.c_int64, F64P],
+        "jg_dcse_time_kernel": [C.c_int64, C.c_int, C.c_int, F64P],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -166,6 +179,8 @@ def lib():
     L.jg_nr_base_destroy.restype = None
     L.jg_dc_destroy.argtypes = [C.c_int64]
     L.jg_dc_destroy.restype = None
+    L.jg_dcse_destroy.argtypes = [C.c_int64]
+    L.jg_dcse_destroy.restype = None
     L.jg_plan_cache_clear.argtypes = []
     L.jg_plan_cache_clear.restype = None
     L.jg_comm_destroy.argtypes = [VP]

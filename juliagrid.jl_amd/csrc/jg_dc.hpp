@@ -34,6 +34,8 @@ struct DcSweepTables {             // one triangle of the factor, rows grouped b
     int* ptr = nullptr;            // [n + 1] offsets of the padded term lists (multiples of DC_T)
     int* col = nullptr;            // [terms] pivot of the operand row (n = the zero row)
     double* val = nullptr;         // [terms] premultiplied factor value, in list order (k_dc_compact)
+    int* ent = nullptr;            // [terms] factor entry of a term and the pivot whose diagonal divides it: kept only by a handle that refactorises
+    int* dpiv = nullptr;
     std::vector<int> h_lev;
     long long terms = 0;
     struct Launch { int l0, l1, chain; };     // levels [l0, l1): a chain launch, or one wide level

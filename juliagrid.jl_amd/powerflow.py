@@ -755,7 +755,10 @@ def power_(an: AcPowerFlow):
     """power!(analysis::AcPowerFlow) (src/postprocessing/acAnalysis.jl:30-169) at the current state of EVERY scenario:
     the Ybus row walk (injections) and the branch formulas run on the device, the O(n) bus / generator bookkeeping
     (shunt :884-889, supply :53-61, generators :84-166) on the host.  Arrays are [batch, ...] (1-D for batch 1).
-    A DcPowerFlow: power!(analysis::DcPowerFlow), dcpowerflow.power_."""
+    A DcPowerFlow: power!(analysis::DcPowerFlow), dcpowerflow.power_; a DcStateEstimation: dcstateestimation.power_."""
+    from . import dcstateestimation as _dcse                        # (imports the method tags of stateestimation, which imports this module)
+    if isinstance(an, _dcse.DcStateEstimation):
+        return _dcse.power_(an)
     if isinstance(an, _dc.DcPowerFlow):
         return _dc.power_(an)
     system, bus, gen = an.system, an.system.bus, an.system.generator

@@ -379,6 +379,15 @@ class PmuStateEstimation(AcStateEstimation):
         return self.jacobian
 
 
+def _dcse():
+    from . import dcstateestimation                                 # (it imports the method tags below)
+    return dcstateestimation
+
+
+def _is_dc(an):
+    return type(an).__name__ == "DcStateEstimation" and isinstance(an, _dcse().DcStateEstimation)
+
+
 class WlsMethod:
     """Factorisation tags of the reference (src/definition/analysis.jl:36-99).  The Normal tags all run the gain matrix through
     the block engine (the L/U factors are parity-unpinned); Orthogonal and PetersWilkinson -- the reference's two
@@ -464,6 +473,8 @@ def drawNoise_(an: AcStateEstimation, seed: int, scale: float = 1.0, first: int 
     reading (measurement/utility.jl:70-73) from a counter-based generator, then the acWLS value rules -- without a byte over PCIe; the same (seed, realisation)
     gives the same numbers on any rank, in any batch, at any lane.  The host mirrors (method.mean, the precision) are marked stale and pulled from the device by
     whoever reads them next (residualTest_, objective, precision, chiTest); rows a residual test removed stay removed in the new realisations."""
+    if _is_dc(an):
+        raise ValueError("drawNoise_: not available for a DcStateEstimation; draw on the host with setNoise_")
     if isinstance(an, PmuStateEstimation):
         raise TypeError("drawNoise_: Gauss-Newton analyses (the linear PMU model keeps its own rows)")
     if not getattr(an, "_readings_on_device", False):
@@ -497,6 +508,8 @@ def setNoise_(an: AcStateEstimation, rng, scale: float = 1.0):
     (what `noise = true` does in add*!, measurement/utility.jl:70-73), then the acWLS value rules are
     re-applied per scenario (squared currents and rectangular PMUs make mean AND precision depend on z).
     Host path (numpy generator, [batch, m] arrays over PCIe); drawNoise_ does the same on the device from an integer seed."""
+    if _is_dc(an):
+        return _dcse().setNoise_(an, rng, scale)
     z1, v1, s1, z2, v2, s2 = an._z
     B = an.batch
     n1 = z1[None, :] + scale * np.sqrt(v1)[None, :] * rng.standard_normal((B, z1.size))
@@ -515,6 +528,8 @@ def increment_(an: AcStateEstimation):
 def solve_(an: AcStateEstimation):
     """solve!(analysis): theta += increment[1:n], V += increment[n+1:2n]; iteration += 1.
     For a PmuStateEstimation: the whole linear WLS solve."""
+    if _is_dc(an):
+        return _dcse().solve_(an)
     if isinstance(an, PmuStateEstimation):
         return _solve_pmu(an)
     _lib.check(_lib.lib().jg_gn_solve(an._h))
@@ -522,8 +537,16 @@ def solve_(an: AcStateEstimation):
     an._pull_voltage()
 
 
-def stateEstimation_(an: AcStateEstimation, iteration: int = 40, tolerance: float = 1e-8, fetch: bool = True):
-    """stateEstimation!(analysis; iteration, tolerance)."""
+def stateEstimation_(an: AcStateEstimation, iteration: int = None, tolerance: float = None, fetch: bool = None, power: bool = False):
+    """stateEstimation!(analysis; iteration, tolerance) (defaults 40, 1e-8).  A DcStateEstimation takes `power` alone: nothing is iterated there."""
+    if _is_dc(an):
+        for name, value in (("iteration", iteration), ("tolerance", tolerance), ("fetch", fetch)):
+            if value is not None:
+                raise ValueError(f"stateEstimation_: `{name}` means nothing for a DcStateEstimation")
+        return _dcse().stateEstimation_(an, power=power)
+    if power:
+        raise ValueError("stateEstimation_: `power` belongs to a DcStateEstimation")
+    iteration, tolerance, fetch = 40 if iteration is None else iteration, 1e-8 if tolerance is None else tolerance, True if fetch is None else fetch
     if isinstance(an, PmuStateEstimation):
         return _solve_pmu(an, fetch)
     it = np.zeros(an.batch, dtype=np.int32)
@@ -546,7 +569,7 @@ def _device_of_row(an, row0):
     return d, int(an._dev_row[d])
 
 
-def residualTest_(an: AcStateEstimation, threshold: float = 3.0):
+def residualTest_(an: AcStateEstimation, threshold: float = 3.0, labels: bool = False):
     """residualTest!(analysis; threshold) (badData.jl:119-311), for every scenario of the batch.
 
     The device recomputes residual, Jacobian, gain and its factor at the current state, forms the selected inverse of
@@ -557,6 +580,8 @@ def residualTest_(an: AcStateEstimation, threshold: float = 3.0):
     device's status in the Measurement container, like the reference.
     Returns a namespace (detect, maxNormalizedResidual, label, index), fields are arrays for batch > 1; index is the
     1-based row of se.mean (0: every residual is zero)."""
+    if _is_dc(an):
+        return _dcse().residualTest_(an, threshold, labels)
     mx = np.zeros(an.batch)
     idx = np.zeros(an.batch, dtype=np.int32)
     _lib.check(_lib.lib().jg_gn_residual_test(an._h, mx, idx))
@@ -617,6 +642,8 @@ def residualTest_(an: AcStateEstimation, threshold: float = 3.0):
 
 def normalizedResidual(an: AcStateEstimation):
     """All normalised residuals of the last residualTest_ call [batch, m] (the reference keeps only the largest)."""
+    if _is_dc(an):
+        return _dcse().normalizedResidual(an)
     r = np.zeros((an.batch, an.dims["m"]))
     _lib.check(_lib.lib().jg_gn_get_normalized_residual(an._h, r))
     return an._shape(r)
@@ -625,6 +652,8 @@ def normalizedResidual(an: AcStateEstimation):
 def chiTest(an: AcStateEstimation, confidence: float = 0.95):
     """chiTest(analysis; confidence) (badData.jl:948-995): objective r' W r at the current state against the
     chi-square quantile with df = rows in service - state variables.  Returns (detect, threshold, objective)."""
+    if _is_dc(an):
+        return _dcse().chiTest(an, confidence)
     from scipy.stats import chi2
     _lib.check(_lib.lib().jg_gn_evaluate(an._h))
     n = an.system.bus.number
@@ -662,7 +691,7 @@ def _refresh(an: AcStateEstimation):
 def _update(target, family, label, channels, layout=None):
     """channels: {gauss field: (mean, variance, status)}; label = 1-based device number inside its family;
     layout: {layout flag: new value or None}."""
-    mon = target.monitoring if isinstance(target, AcStateEstimation) else target
+    mon = target.monitoring if isinstance(target, AcStateEstimation) or _is_dc(target) else target
     meter = getattr(mon, family)
     i = int(label) - 1
     if not 0 <= i < meter.number:
@@ -680,7 +709,11 @@ def _update(target, family, label, channels, layout=None):
             if status not in (0, 1):
                 raise ValueError("status must be 0 or 1")
             g.status[i] = int(status)
-    if isinstance(target, AcStateEstimation):
+    if _is_dc(target):
+        if family not in ("wattmeter", "pmu"):
+            raise ValueError(f"a DcStateEstimation holds no {family}")
+        target._refresh_row(family, i)
+    elif isinstance(target, AcStateEstimation):
         _refresh(target)
 
 
