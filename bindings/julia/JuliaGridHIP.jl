@@ -1304,6 +1304,54 @@ function timeKernel(b::DcPowerFlowBatch, kernel::Int, reps::Int = 20)
     check(ccall((:jg_dc_time_kernel, lib), Cint, (Int64, Cint, Cint, Ptr{Float64}), b.token, kernel, reps, ms))
     return ms
 end
+"scenario `lane0 + s` (0-based lanes) loses branches `first[s]` AND `second[s]` (indices; `second[s] = 0`: a single outage)"
+setOutagePairs!(b::DcPowerFlowBatch, first::Vector{Int64}, second::Vector{Int64}; lane0::Int64 = 0) =
+    check(ccall((:jg_dc_set_outage_pairs, lib), Cint, (Int64, Int64, Int64, Ptr{Int64}, Ptr{Int64}), b.token, lane0, length(first), first, second))
+"""
+    pairScreenBuild!(b, candidates; monitored = nothing, budget = 0) -> info [8]
+
+The DC N-2 screen (jgrid.h: jg_dc_pair_*): one sweep pair per candidate branch (indices, in service, ascending) fills the outage sensitivities of the
+monitored branches (default: every branch in service).  `budget`: bytes they may take (0: 0.8 of the free device memory); an error names the sizes.
+"""
+function pairScreenBuild!(b::DcPowerFlowBatch, candidates::Vector{Int64}; monitored::Union{Nothing, Vector{Int64}} = nothing, budget::Int64 = 0)
+    uploadRhs!(b)
+    info = zeros(Float64, 8)
+    if monitored === nothing
+        check(ccall((:jg_dc_pair_build, lib), Cint, (Int64, Int64, Ptr{Int64}, Int64, Ptr{Int64}, Int64, Ptr{Float64}),
+            b.token, length(candidates), candidates, 0, C_NULL, budget, info))
+    else
+        check(ccall((:jg_dc_pair_build, lib), Cint, (Int64, Int64, Ptr{Int64}, Int64, Ptr{Int64}, Int64, Ptr{Float64}),
+            b.token, length(candidates), candidates, length(monitored), monitored, budget, info))
+    end
+    return info
+end
+"""
+    pairScreen(b, k0, k1, candidates; rating, threshold = 1.0, capacity = 2^20, islandCapacity = 2^16) -> (records [5, m], islanding [2, i], totals [6], worst)
+
+All pairs (k, l > k) whose first branch is candidate position k0 .. k1 - 1 (0-based): the records of the pairs above `threshold` sorted by (k, l) (branch k,
+branch l, worst branch, worst |from| / rating, overloaded branches), the islanding pairs, the totals (pairs, violating, islanding, records kept, islanding
+pairs kept, overflow flags) and the worst loading per candidate.
+"""
+function pairScreen(b::DcPowerFlowBatch, k0::Int64, k1::Int64, candidates::Vector{Int64}; rating::Vector{Float64}, threshold::Float64 = 1.0,
+                    capacity::Int64 = 2^20, islandCapacity::Int64 = 2^16)
+    check(ccall((:jg_dc_set_rating, lib), Cint, (Int64, Ptr{Float64}), b.token, rating))
+    records = Matrix{Float64}(undef, 5, capacity)
+    islanding = Matrix{Int64}(undef, 2, islandCapacity)
+    totals = zeros(Int64, 6)
+    worst = zeros(Float64, length(candidates))
+    check(ccall((:jg_dc_pair_screen, lib), Cint, (Int64, Int64, Int64, Float64, Int64, Ptr{Float64}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64},
+                                                  Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}),
+        b.token, k0, k1, threshold, capacity, records, islandCapacity, islanding, totals, worst, C_NULL, C_NULL, C_NULL, C_NULL))
+    return records[:, 1:totals[4]], islanding[:, 1:totals[5]], totals, worst
+end
+"milliseconds of `reps` runs on candidate rows k0 .. k1 - 1 (HIP events): 0 the pair screen kernel, 1 its row / column summaries"
+function pairTimeKernel(b::DcPowerFlowBatch, kernel::Int, k0::Int64, k1::Int64, reps::Int = 20)
+    ms = zeros(Float64, reps)
+    check(ccall((:jg_dc_pair_time_kernel, lib), Cint, (Int64, Cint, Int64, Int64, Cint, Ptr{Float64}), b.token, kernel, k0, k1, reps, ms))
+    return ms
+end
+"frees the sensitivities a pair screen keeps on the device"
+pairScreenRelease!(b::DcPowerFlowBatch) = check(ccall((:jg_dc_pair_release, lib), Cint, (Int64,), b.token))
 
 # ---- DC state estimation with batched bad-data removal (jgrid.h: jg_dcse_*; csrc/jg_dcse.hip) ------------------------------------------------
 # dcStateEstimation / solve! / power! / residualTest! / chiTest (src/stateEstimation/dcStateEstimation.jl:42-151, 342-434, badData.jl:48-117, 963-977) for
@@ -1485,6 +1533,6 @@ export HIP, HIPOrthogonal, NewtonRaphsonBatch, BaseCase, baseInfo, baseInverseOn
        largestNormalizedResidual, normalizedResiduals, commUniqueId, Comm, shard, contingencyAnalysis, clearPlanCache,
        deviceCount, dims, setRefinement!, deviceMaps, setOutage!, snapshotVoltage!, restoreVoltage!, iterations, voltageDevice!, packResults!, packRows!,
        allgatherDevice, commRank, commWorld, timeKernel, setBusType!, busType, GaussNewtonBatch, setRealisations!, monteCarloEstimation, fastPatch!, setReadings!, drawNoise!, measurementDevice,
-       DcPowerFlowBatch, setInjections!, fromPower, angleDevice, DcStateEstimationBatch, removedRows, removeRows!
+       DcPowerFlowBatch, setInjections!, setOutagePairs!, pairScreenBuild!, pairScreen, pairTimeKernel, pairScreenRelease!, fromPower, angleDevice, DcStateEstimationBatch, removedRows, removeRows!
 
 end # module

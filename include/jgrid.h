@@ -513,6 +513,43 @@ int jg_dc_screen(int64_t h, double* rec);
 int jg_dc_screen_device(int64_t h, double* rec_dev);
 int jg_dc_pack_results_device(int64_t h, double* dst_dev);
 int jg_dc_time_kernel(int64_t h, int kernel, int reps, double* ms);
+/*
+ * Two outages per lane: updateBranch!(analysis; label = a, status = 0), updateBranch!(analysis; label = b, status = 0), solve!.  Lane lane0 + s loses
+ * branch_a[s] and branch_b[s] (1-based; branch_b[s] = 0: a single outage, both 0: none; the two must differ).  jg_dc_solve then runs a second sweep pair
+ * for the 64-lane groups that hold a second outage, and only for those, and combines through the 2 x 2 system of csrc/jg_dc_pair.hpp (injections of
+ * the lane's own included).  Flows and the screen put 0 on both branches; a pair that islands a part of the grid gets status 3 and NaN angles, also
+ * when neither branch alone is a bridge.  A handle on which no second outage was ever set allocates nothing for this and takes the one-outage path.
+ * jg_dc_set_outages over such lanes clears their second outage.
+ */
+int jg_dc_set_outage_pairs(int64_t h, int64_t lane0, int64_t count, const int64_t* branch_a, const int64_t* branch_b);
+/*
+ * The DC N-2 screen over ALL pairs k < l of a candidate list, from the one factor and the kept outage sensitivities (csrc/jg_dc_pair.hpp): the user loop
+ * updateBranch!(k), updateBranch!(l), solve!, power! over all pairs.  Needs jg_dc_set_branches and jg_dc_set_rhs; the lanes of the handle are not touched.
+ *   jg_dc_pair_build    candidates [nk] (1-based branches, in service, strictly ascending, nk >= 2); monitored [nm] (1-based; NULL: every branch in
+ *                       service).  One sweep pair per candidate (512 at a time) fills Phi[m,k] = y_m a_m' B^-1 a_k on the rows monitored u candidates,
+ *                       [rows][nk rounded up to 64] doubles.  budget_bytes: what Phi and the build's scratch may take (<= 0: 0.8 of the free device
+ *                       memory, asked from hipMemGetInfo); return code 5 and a message that names the sizes when they do not fit -- nothing is
+ *                       allocated then and the handle stays as it was.  info [8]: rows, leading dimension, bytes of Phi, free bytes, budget, and
+ *                       the milliseconds (HIP events) of the build: total, sweep pairs, Phi kernel.  A second build replaces the first.
+ *   jg_dc_pair_screen   the pairs (k, l > k) of the candidate POSITIONS k in [k0, k1) (0-based; the row block bounds the memory of a call, 16 bytes per
+ *                       pair, and is the unit a caller shards by) against the ratings of jg_dc_set_rating (not rated or not monitored: loading 0).
+ *                       records [capacity][5]: the pairs whose worst loading exceeds threshold, sorted by (k, l): branch k, branch l (1-based), worst
+ *                       branch, worst |from| / rating, number of monitored branches above threshold; ties of the worst branch go to the lowest index.
+ *                       islanding [island_capacity][2]: the pairs whose 2 x 2 system is singular (|det| < 1e-9: status 3), sorted likewise.
+ *                       totals [6]: pairs screened, violating, islanding, records written, islanding pairs written, flags (1: the record list
+ *                       overflowed, 2: the islanding list did) -- the counts are exact also then, and the entries kept are the FIRST by (k, l).
+ *                       worst [nk] (nullable, in/out): max-merged with the worst loading over the pairs of each candidate, as k or as l.
+ *                       dense_* (each nullable) [k1 - k0][nk]: worst loading (NaN: islanding), its branch, the count, the determinant; 0 where l <= k.
+ *   jg_dc_pair_time_kernel   milliseconds of `reps` runs on rows [k0, k1) (a block jg_dc_pair_screen has held): 0 the screen kernel, 1 the row / column
+ *                       summaries behind it
+ *   jg_dc_pair_release  frees what the screen holds on the device
+ */
+int jg_dc_pair_build(int64_t h, int64_t nk, const int64_t* candidates, int64_t nm, const int64_t* monitored, int64_t budget_bytes, double* info8);
+int jg_dc_pair_screen(int64_t h, int64_t k0, int64_t k1, double threshold, int64_t capacity, double* records, int64_t island_capacity,
+                      int64_t* islanding, int64_t* totals6, double* worst, double* dense_load, int32_t* dense_branch, int32_t* dense_count,
+                      double* dense_det);
+int jg_dc_pair_time_kernel(int64_t h, int kernel, int64_t k0, int64_t k1, int reps, double* ms);
+int jg_dc_pair_release(int64_t h);
 
 /* ---------------------------------------------------------------------------------------------
  * DC state estimation with batched bad-data removal (csrc/jg_dcse.hip)

@@ -115,13 +115,15 @@ def contingencyAnalysis(system: PowerSystem, labels, device: int = 0, method: st
     Newton-Raphson (constant matrices with per-scenario edits, ONE factorisation for the batch: jg_nr_fast_patch_batch).
     reactiveLimit = k > 0 (Newton-Raphson, two or more scenarios): the analysis is also SOLVED -- from `start` (V, theta) when given -- with up to k rounds
     of reactiveLimit! + powerFlow! per scenario (powerflow.powerFlowLimits_); method.iteration sums the solves of each scenario (test/powerFlow/limits.jl).
-    method "dc": the DC model instead -- a SOLVED DcPowerFlow comes back (voltage.angle [batch, n], status [batch] with 3 on bridges, and, when `rating`
+    method "dc" (the only one that takes a tuple (k, l) as a label: a scenario with TWO outages): the DC model instead -- a SOLVED DcPowerFlow comes back (voltage.angle [batch, n], status [batch] with 3 on bridges, and, when `rating`
     (per branch, per unit of active power) is given, screen [batch, 5]: dcpowerflow.screenSummary_)."""
     labels = list(labels)
     if method == "dc" and (reactiveLimit or start is not None or iteration != 20 or tolerance != 1e-8):
         raise ValueError("contingencyAnalysis: reactiveLimit, start, iteration and tolerance have no meaning for method='dc' (nothing is iterated)")
     if method != "dc" and rating is not None:
         raise ValueError("contingencyAnalysis: rating belongs to method='dc'; an AC screen takes it in screenSummary_(analysis, rating=...)")
+    if method != "dc" and any(isinstance(lab, (tuple, list)) for lab in labels):
+        raise ValueError("contingencyAnalysis: a tuple (k, l) of two outages is a DC scenario (method='dc'); nr / bx / xb take one branch per scenario")
     if method == "dc":                                          # the pre-filter of a screen: solved on return, one factor for the whole batch (dcpowerflow.py)
         from .dcpowerflow import dcContingencyAnalysis
         return dcContingencyAnalysis(system, labels, device=device, rating=rating)

@@ -3,6 +3,7 @@
 // The scalar factorisation of the ONE base matrix (once per base case), the level-scheduled sweeps with scenarios as lanes and the branch-flow kernel
 // are in jg_dc_sweep.hpp, shared with jg_dcse.hip; here: the rank-1 combine, the screen summary and the C ABI.
 #include "jg_dc.hpp"
+#include "jg_dc_pair.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -52,6 +53,45 @@ __global__ __launch_bounds__(256) void k_dc_combine(DcCombineArgs a) {
     }
 }
 
+// ---- the rank-2 combine of the lanes with a second outage (jg_dc_set_outage_pairs) ------------------------------------------------------------
+// theta = x0 + z1 c1 + z2 c2 with (I - Y A' Z) c = f0 on the lane's two branches, f0_k = y_k a_k' x0 - shiftAngle_k y_k (jg_dc_pair.hpp: the same 2 x 2
+// system as the N-2 screen's).  Runs behind k_dc_combine on the lane groups that hold such a lane and writes ONLY those lanes.
+struct DcCombine2Args {
+    const double* Z; const double* Z2; const double* XS; const double* th0;
+    const int* ginj; const int* groups;
+    const int* of; const int* ot; const double* oy; const double* osh;
+    const int* of2; const int* ot2; const int* obr2; const double* oy2; const double* osh2;
+    double* TH; int* status;
+    double slack_angle; int n, ld, slack;
+};
+__global__ __launch_bounds__(256) void k_dc_combine2(DcCombine2Args a) {
+    const int wave = uniform(threadIdx.y);
+    const int grp = ((CInt)a.groups)[blockIdx.y];
+    const size_t ld = (size_t)a.ld, bl = (size_t)grp * 64 + threadIdx.x;
+    if (a.obr2[bl] < 0) return;
+    const bool own = a.ginj && ((CInt)a.ginj)[grp] != 0;
+    auto x0 = [&](int bus) { return own ? a.XS[(size_t)bus * ld + bl] : a.th0[(size_t)bus * 64]; };
+    auto dot = [&](int fi, int ti, auto&& v) { return (fi >= 0 ? v(fi) : 0.0) - (ti >= 0 ? v(ti) : 0.0); };
+    auto z1 = [&](int bus) { return a.Z[(size_t)bus * ld + bl]; };
+    auto z2 = [&](int bus) { return a.Z2[(size_t)bus * ld + bl]; };
+    const int f1 = a.of[bl], t1 = a.ot[bl], f2 = a.of2[bl], t2 = a.ot2[bl];
+    const double y1 = a.oy[bl], y2 = a.oy2[bl];
+    const double a11 = 1.0 - y1 * dot(f1, t1, z1), a12 = -y1 * dot(f1, t1, z2);
+    const double a21 = -y2 * dot(f2, t2, z1), a22 = 1.0 - y2 * dot(f2, t2, z2);
+    const double g1 = y1 * dot(f1, t1, x0) - a.osh[bl], g2 = y2 * dot(f2, t2, x0) - a.osh2[bl];
+    const double det = a11 * a22 - a12 * a21;
+    const bool sing = fabs(det) < DC_SINGULAR;
+    const double c1 = sing ? 0.0 : (a22 * g1 - a12 * g2) / det, c2 = sing ? 0.0 : (a11 * g2 - a21 * g1) / det;
+    if (blockIdx.x == 0 && wave == 0) a.status[bl] = sing ? 3 : 0;
+    const int b0 = (blockIdx.x * 4 + wave) * DC_COMBINE_ROWS;
+    for (int bus = b0; bus < min(b0 + DC_COMBINE_ROWS, a.n); ++bus) {
+        double th = x0(bus) + c1 * z1(bus) + c2 * z2(bus) + a.slack_angle;
+        if (bus == a.slack) th = a.slack_angle;
+        if (sing) th = __longlong_as_double(0x7ff8000000000000LL);
+        a.TH[(size_t)bus * ld + bl] = th;
+    }
+}
+
 // chunks in ascending order, strict comparison: ties go to the lowest branch index (as k_screen_final)
 __global__ __launch_bounds__(64) void k_dc_screen_final(const double* part, const int* status, double* screen, int chunks, int ld, int batch) {
     const size_t bl = (size_t)blockIdx.x * 64 + threadIdx.x;
@@ -94,13 +134,20 @@ void launch_combine(DcHandle* h) {
     c.TH = h->TH; c.status = h->status; c.slack_angle = h->slack_angle; c.n = h->n; c.ld = h->ld; c.slack = h->slack;
     const int per = 4 * DC_COMBINE_ROWS;
     hipLaunchKernelGGL(k_dc_combine, dim3((h->n + per - 1) / per, h->ld / 64), dim3(64, 4), 0, h->stream, c);
+    if (!h->n_glist2) return;
+    DcCombine2Args q{};
+    q.Z = h->Z; q.Z2 = h->Z2; q.XS = h->XS; q.th0 = h->th0; q.ginj = c.ginj; q.groups = h->glist2;
+    q.of = h->o_from; q.ot = h->o_to; q.oy = h->o_y; q.osh = h->o_sh;
+    q.of2 = h->o2_from; q.ot2 = h->o2_to; q.obr2 = h->o2_br; q.oy2 = h->o2_y; q.osh2 = h->o2_sh;
+    q.TH = h->TH; q.status = h->status; q.slack_angle = h->slack_angle; q.n = h->n; q.ld = h->ld; q.slack = h->slack;
+    hipLaunchKernelGGL(k_dc_combine2, dim3((h->n + per - 1) / per, h->n_glist2), dim3(64, 4), 0, h->stream, q);
 }
 
 int launch_flows(DcHandle* h, bool store) {
     if (!h->nbr) { h->error = "jg_dc_set_branches has not been called"; return 1; }
     if (store && !h->flows) DC_TRY(dev_alloc(h, &h->flows, (size_t)h->nbr * h->ld, (const double*)nullptr, true));
     DcFlowArgs f{};
-    f.TH = h->TH; f.bf = h->b_from; f.bt = h->b_to; f.by = h->b_y; f.bs = h->b_shift; f.rating = h->b_rating; f.obr = h->o_br;
+    f.TH = h->TH; f.bf = h->b_from; f.bt = h->b_to; f.by = h->b_y; f.bs = h->b_shift; f.rating = h->b_rating; f.obr = h->o_br; f.obr2 = h->o2_br;
     f.flows = store ? h->flows : nullptr; f.part = h->part; f.nbr = h->nbr; f.ld = h->ld;
     hipLaunchKernelGGL(k_dc_flows, dim3((h->n_chunks + 3) / 4, h->ld / 64), dim3(64, 4), 0, h->stream, f);
     hipLaunchKernelGGL(k_dc_screen_final, dim3(h->ld / 64), dim3(64), 0, h->stream, h->part, h->status, h->screen, h->n_chunks, h->ld, h->batch);
@@ -121,6 +168,7 @@ int base_solve(DcHandle* h) {
 int solve_chain(DcHandle* h) {
     sweep_pair<1>(h, nullptr, h->W, h->Z, h->ld, h->ld / 64, nullptr);
     if (h->n_glist) sweep_pair<0>(h, h->RHS, h->W, h->XS, h->ld, h->n_glist, h->glist);
+    if (h->n_glist2) sweep_pair_on<1>(h, (const double*)nullptr, h->o2_from, h->o2_to, h->W, h->Z2, h->ld, h->n_glist2, h->glist2);   // a second sweep pair, for the groups with a second outage only
     launch_combine(h);
     DC_HIP(hipGetLastError());
     return 0;
@@ -200,6 +248,7 @@ int dc_create(DcHandle* h, int64_t n64, const int64_t* colptr, const int64_t* ro
 void dc_destroy(DcHandle* h) {
     hipSetDevice(h->device);
     if (h->stream) hipStreamSynchronize(h->stream);
+    dc_pair_free(h);
     for (void* p : h->allocs) hipFree(p);
     if (h->stream) hipStreamDestroy(h->stream);
     delete h;
@@ -317,29 +366,76 @@ int jg_dc_set_rating(int64_t h, const double* rating) {
     return 0;
 }
 
-int jg_dc_set_outages(int64_t h, int64_t lane0, int64_t count, const int64_t* branch) {
-    DC_ENTER(h);
-    if (lane0 < 0 || count < 0 || lane0 + count > d->batch || (count && !branch)) return faild(1, "jg_dc_set_outages: lanes out of range");
-    if (!d->nbr) return faild(1, "jg_dc_set_outages: jg_dc_set_branches first");
+// lanes lane0 .. : outage of branch[s] and, where branch2 is given and not 0, of branch2[s] as well
+static int dc_set_lane_outages(DcHandle* d, const char* who, int64_t lane0, int64_t count, const int64_t* branch, const int64_t* branch2) {
+    const std::string me = who;
+    if (lane0 < 0 || count < 0 || lane0 + count > d->batch || (count && !branch)) return faild(1, me + ": lanes out of range");
+    if (!d->nbr) return faild(1, me + ": jg_dc_set_branches first");
     if (!count) return 0;
-    std::vector<int> of(count), ot(count), ob(count);
-    std::vector<double> oy(count), os(count);
+    std::vector<int> of(count), ot(count), ob(count), of2(count, -1), ot2(count, -1), ob2(count, -1);
+    std::vector<double> oy(count), os(count), oy2(count, 0.0), os2(count, 0.0);
+    bool second = false;
     for (int64_t s = 0; s < count; ++s) {
-        const int64_t k = branch[s] - 1;
-        if (k < -1 || k >= d->nbr) return faild(1, "jg_dc_set_outages: branch index out of range");
+        int64_t k = branch[s] - 1, k2 = branch2 ? branch2[s] - 1 : -1;
+        if (k < -1 || k >= d->nbr || k2 < -1 || k2 >= d->nbr) return faild(1, me + ": branch index out of range");
+        if (k >= 0 && k == k2) return faild(1, me + ": the two outages of a lane must be different branches");
+        if (k < 0) { k = k2; k2 = -1; }
         if (k < 0) { of[s] = ot[s] = ob[s] = -1; oy[s] = os[s] = 0.0; continue; }
         of[s] = d->h_from[k] == d->slack ? -1 : d->h_from[k];           // the slack's component of a = e_from - e_to is dropped
         ot[s] = d->h_to[k] == d->slack ? -1 : d->h_to[k];
         ob[s] = (int)k; oy[s] = d->h_y[k]; os[s] = d->h_shift[k] * d->h_y[k];
+        if (k2 < 0) continue;
+        second = true;
+        of2[s] = d->h_from[k2] == d->slack ? -1 : d->h_from[k2];
+        ot2[s] = d->h_to[k2] == d->slack ? -1 : d->h_to[k2];
+        ob2[s] = (int)k2; oy2[s] = d->h_y[k2]; os2[s] = d->h_shift[k2] * d->h_y[k2];
+    }
+    if (second && !d->o2_br) {                                           // the first second outage of the handle
+        const size_t ld = (size_t)d->ld;
+        DC_RET(jg::dev_alloc(d, &d->o2_from, ld, (const int*)nullptr, false));
+        DC_RET(jg::dev_alloc(d, &d->o2_to, ld, (const int*)nullptr, false));
+        DC_RET(jg::dev_alloc(d, &d->o2_br, ld, (const int*)nullptr, false));
+        DC_API_HIP(jg::sync_fill(d->o2_from, 0xff, ld * sizeof(int), d->stream));
+        DC_API_HIP(jg::sync_fill(d->o2_to, 0xff, ld * sizeof(int), d->stream));
+        DC_API_HIP(jg::sync_fill(d->o2_br, 0xff, ld * sizeof(int), d->stream));
+        DC_RET(jg::dev_alloc(d, &d->o2_y, ld, (const double*)nullptr, true));
+        DC_RET(jg::dev_alloc(d, &d->o2_sh, ld, (const double*)nullptr, true));
+        DC_RET(jg::dev_alloc(d, &d->Z2, (size_t)d->n * ld, (const double*)nullptr, true));
+        DC_RET(jg::dev_alloc(d, &d->glist2, ld / 64, (const int*)nullptr, true));
+        d->h_o2.assign(ld, -1);
     }
     DC_API_HIP(hipMemcpyAsync(d->o_from + lane0, of.data(), count * sizeof(int), hipMemcpyHostToDevice, d->stream));
     DC_API_HIP(hipMemcpyAsync(d->o_to + lane0, ot.data(), count * sizeof(int), hipMemcpyHostToDevice, d->stream));
     DC_API_HIP(hipMemcpyAsync(d->o_br + lane0, ob.data(), count * sizeof(int), hipMemcpyHostToDevice, d->stream));
     DC_API_HIP(hipMemcpyAsync(d->o_y + lane0, oy.data(), count * sizeof(double), hipMemcpyHostToDevice, d->stream));
     DC_API_HIP(hipMemcpyAsync(d->o_sh + lane0, os.data(), count * sizeof(double), hipMemcpyHostToDevice, d->stream));
+    std::vector<int> list;
+    if (d->o2_br) {                                                      // (also a plain jg_dc_set_outages over lanes that held a pair)
+        DC_API_HIP(hipMemcpyAsync(d->o2_from + lane0, of2.data(), count * sizeof(int), hipMemcpyHostToDevice, d->stream));
+        DC_API_HIP(hipMemcpyAsync(d->o2_to + lane0, ot2.data(), count * sizeof(int), hipMemcpyHostToDevice, d->stream));
+        DC_API_HIP(hipMemcpyAsync(d->o2_br + lane0, ob2.data(), count * sizeof(int), hipMemcpyHostToDevice, d->stream));
+        DC_API_HIP(hipMemcpyAsync(d->o2_y + lane0, oy2.data(), count * sizeof(double), hipMemcpyHostToDevice, d->stream));
+        DC_API_HIP(hipMemcpyAsync(d->o2_sh + lane0, os2.data(), count * sizeof(double), hipMemcpyHostToDevice, d->stream));
+        std::copy(ob2.begin(), ob2.end(), d->h_o2.begin() + lane0);
+        for (int g = 0; g < d->ld / 64; ++g)
+            if (std::any_of(d->h_o2.begin() + g * 64, d->h_o2.begin() + (g + 1) * 64, [](int b) { return b >= 0; })) list.push_back(g);
+        d->n_glist2 = (int)list.size();
+        if (!list.empty()) DC_API_HIP(hipMemcpyAsync(d->glist2, list.data(), list.size() * sizeof(int), hipMemcpyHostToDevice, d->stream));
+    }
     DC_API_HIP(hipStreamSynchronize(d->stream));                         // the host vectors go out of scope
     d->solved = false;
     return 0;
+}
+
+int jg_dc_set_outages(int64_t h, int64_t lane0, int64_t count, const int64_t* branch) {
+    DC_ENTER(h);
+    return dc_set_lane_outages(d, "jg_dc_set_outages", lane0, count, branch, nullptr);
+}
+
+int jg_dc_set_outage_pairs(int64_t h, int64_t lane0, int64_t count, const int64_t* branch_a, const int64_t* branch_b) {
+    DC_ENTER(h);
+    if (count && !branch_b) return faild(1, "jg_dc_set_outage_pairs: null pointer");
+    return dc_set_lane_outages(d, "jg_dc_set_outage_pairs", lane0, count, branch_a, branch_b);
 }
 
 int jg_dc_solve(int64_t h) {

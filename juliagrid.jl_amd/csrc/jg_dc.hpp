@@ -42,6 +42,8 @@ struct DcSweepTables {             // one triangle of the factor, rows grouped b
     std::vector<Launch> launches;
 };
 
+struct DcPairState;
+
 struct DcHandle {
     int n = 0, nbr = 0, batch = 0, ld = 0, device = 0, slack = 0, n_entries = 0, n_fact_levels = 0;
     double slack_angle = 0.0;
@@ -66,6 +68,11 @@ struct DcHandle {
     int* ginj = nullptr; int* glist = nullptr; std::vector<int> h_ginj; int n_glist = 0;   // lane groups with injections of their own
     int* o_from = nullptr; int* o_to = nullptr; int* o_br = nullptr; double* o_y = nullptr; double* o_sh = nullptr;   // [ld] the lanes' outages
     int* status = nullptr;                                                     // [ld]
+    // lanes with a SECOND outage (jg_dc_set_outage_pairs): allocated by the first call that names one, a handle without such a lane holds none of it
+    int* o2_from = nullptr; int* o2_to = nullptr; int* o2_br = nullptr; double* o2_y = nullptr; double* o2_sh = nullptr;   // [ld]
+    double* Z2 = nullptr;                                                      // [n][ld] z of the second outage, for the groups of glist2
+    int* glist2 = nullptr; std::vector<int> h_o2; int n_glist2 = 0;            // lane groups that hold a second outage
+    DcPairState* pair = nullptr;                                               // the N-2 screen's kept sensitivities (jg_dc_pair.hpp)
     // branches
     std::vector<int> h_from, h_to; std::vector<double> h_y, h_shift;
     int* b_from = nullptr; int* b_to = nullptr; double* b_y = nullptr; double* b_shift = nullptr; double* b_rating = nullptr; double* rating_buf = nullptr;

@@ -135,6 +135,7 @@ __global__ __launch_bounds__(64 * DC_CHAIN_WAVES) void k_dc_chain(DcSweepArgs a)
 struct DcFlowArgs {
     const double* TH; const int* bf; const int* bt; const double* by; const double* bs; const double* rating;    // rating nullable
     const int* obr;
+    const int* obr2;                    // nullable: the lanes' second outaged branch (-1: none)
     double* flows;                      // nullable [nbr][ld]
     double* part;                       // [chunks][4][ld]: worst loading, its branch, largest |from|, its branch
     int nbr, ld;
@@ -146,13 +147,13 @@ __global__ __launch_bounds__(256) void k_dc_flows(DcFlowArgs a) {
     const int k0 = chunk * DC_FLOW_BRANCHES;
     if (k0 >= a.nbr) return;
     const size_t ld = (size_t)a.ld, bl = (size_t)blockIdx.y * 64 + threadIdx.x;
-    const int out = a.obr[bl];
+    const int out = a.obr[bl], out2 = a.obr2 ? a.obr2[bl] : -1;
     double wl = 0.0, wf = 0.0, il = 0.0, jf = 0.0;
     for (int k = k0; k < min(k0 + DC_FLOW_BRANCHES, a.nbr); ++k) {
         const int f = ((CInt)a.bf)[k], t = ((CInt)a.bt)[k];
         const double y = ((CDbl)a.by)[k], s = ((CDbl)a.bs)[k];
         double p = y * (a.TH[(size_t)f * ld + bl] - a.TH[(size_t)t * ld + bl] - s);
-        if (k == out) p = 0.0;
+        if (k == out || k == out2) p = 0.0;
         if (a.flows) a.flows[(size_t)k * ld + bl] = p;
         const double m = fabs(p);
         if (m > wf) { wf = m; jf = (double)(k + 1); }

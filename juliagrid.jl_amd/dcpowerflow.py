@@ -3,7 +3,9 @@
   dcPowerFlow(system)          src/powerFlow/dcPowerFlow.jl:42-61
   solve!(analysis)             src/powerFlow/dcPowerFlow.jl:63-101
   power!(analysis)             src/postprocessing/dcAnalysis.jl:27-75 and its branch part (:41-48 of allPowerBranch)
-  updateBranch!(analysis; label, status = 0) -> solve!   per scenario: setOutages_ (one shared factor, a rank-1 correction per lane: csrc/jg_dc.hpp)
+  updateBranch!(analysis; label, status = 0) -> solve!   per scenario: setOutages_ (one shared factor, a rank-1 correction per lane: csrc/jg_dc.hpp;
+                                                         a tuple (k, l) is a lane with two outages: a 2 x 2 correction)
+  the same loop over ALL pairs of a candidate list          dcPairScreen (the DC N-2 screen: csrc/jg_dc_pair.hpp)
 
 All numerics run in libjgrid_hip.so (csrc/jg_dc.hip); the O(n) bus / generator bookkeeping of power! runs here.  A batched analysis keeps
 `batch` scenarios of ONE grid on the device; arrays are [batch, ...] (1-D for batch 1), as in the AC analysis.
@@ -40,6 +42,7 @@ class DcPowerFlow:
         self.method = NS(dcmodel=True)
         self.status = 0 if self.batch == 1 else np.zeros(self.batch, dtype=np.int32)
         self._outage_labels = np.zeros(self.batch, dtype=np.int64)
+        self._outage_labels2 = np.zeros(self.batch, dtype=np.int64)
         self._injection = None                                          # [batch, n] net injections of the scenarios that have their own, NaN rows elsewhere
         self._rhs = None
 
@@ -124,14 +127,35 @@ def powerFlow_(an: DcPowerFlow, power: bool = False):
         power_(an)
 
 
+def outagePairs(labels, branches: int):
+    """labels of a scenario list as two int64 arrays (first, second outage; 0 = none): an entry is None / 0, a branch label, or a tuple (k, l) of two
+    different labels ((k, 0): k alone).  Checked on the host: IndexError for a label outside 1 .. branches, ValueError for k == l or a tuple of another length."""
+    a = np.zeros(len(labels), dtype=np.int64)
+    b = np.zeros(len(labels), dtype=np.int64)
+    for s, x in enumerate(labels):
+        if isinstance(x, (tuple, list)):
+            if len(x) != 2:
+                raise ValueError("an outage pair is a tuple (k, l) of two branch labels")
+            a[s], b[s] = (int(x[0]) if x[0] else 0), (int(x[1]) if x[1] else 0)
+            if a[s] and a[s] == b[s]:
+                raise ValueError(f"outage pair ({a[s]}, {b[s]}): the two branches must differ")
+        else:
+            a[s] = int(x) if x else 0
+    if a.size and (min(a.min(), b.min()) < 0 or max(a.max(), b.max()) > branches):
+        raise IndexError("branch label out of range")
+    return a, b
+
+
 def setOutages_(an: DcPowerFlow, labels, scenario0: int = 0):
-    """scenario scenario0 + s = base grid with branch labels[s] out of service (0 / None = base grid): the reference's
+    """scenario scenario0 + s = base grid with branch labels[s] out of service (0 / None = base grid; a tuple (k, l): BOTH branches): the reference's
     updateBranch!(analysis; label, status = 0) per scenario, without touching the factor."""
-    lab = np.array([int(x) if x else 0 for x in labels], dtype=np.int64)
-    if lab.size and (lab.min() < 0 or lab.max() > an.system.branch.number):
-        raise IndexError("setOutages_: branch label out of range")
-    _lib.check(_lib.lib().jg_dc_set_outages(an._h, int(scenario0), int(lab.size), lab))
+    lab, lab2 = outagePairs(list(labels), an.system.branch.number)
+    if lab2.any():
+        _lib.check(_lib.lib().jg_dc_set_outage_pairs(an._h, int(scenario0), int(lab.size), lab, lab2))
+    else:
+        _lib.check(_lib.lib().jg_dc_set_outages(an._h, int(scenario0), int(lab.size), lab))
     an._outage_labels[scenario0:scenario0 + lab.size] = lab
+    an._outage_labels2[scenario0:scenario0 + lab.size] = lab2
 
 
 def _upload_injections(an: DcPowerFlow):
@@ -201,11 +225,135 @@ def screenSummary_(an: DcPowerFlow, rating=None) -> np.ndarray:
 
 
 def dcContingencyAnalysis(system: PowerSystem, labels, device: int = 0, rating=None) -> DcPowerFlow:
-    """Solved batched DC analysis, scenario s = outage of branch labels[s] (0 / None: base case): analysis.voltage.angle [batch, n],
+    """Solved batched DC analysis, scenario s = outage of branch labels[s] (0 / None: base case; a tuple (k, l): both branches): analysis.voltage.angle [batch, n],
     analysis.status [batch] (3: bridge), and analysis.screen [batch, 5] (screenSummary_) when `rating` is given."""
     labels = list(labels)
+    outagePairs(labels, system.branch.number)                           # refused on the host, before the device is touched
     an = dcPowerFlow(system, batch=len(labels), device=device)
     setOutages_(an, labels)
     solve_(an)
     an.screen = screenSummary_(an, rating) if rating is not None else None
     return an
+
+
+class DcPairScreen:
+    """What dcPairScreen returns.
+      candidates  [K] branch labels (1-based, ascending); monitored rows are those of the call
+      records     [m, 5] the pairs whose worst loading exceeds the threshold, sorted by (k, l): label k, label l, worst branch, worst |from| / rating,
+                  number of monitored branches above the threshold
+      islanding   [i, 2] int64 labels of the pairs that island a part of the grid (status 3)
+      totals      dict(pairs, violating, islanding): exact also when a list overflowed
+      overflow / islandingOverflow   a list was cut at its capacity: it holds the FIRST entries by (k, l)
+      worst       [K] the worst loading over all screened pairs of each candidate (ranking)
+      loading, branch, count, determinant   with dense=True: [K, K], the upper triangle mirrored (NaN loading on islanding pairs, diagonal 0); with
+                  rows=(k0, k1): the block [k1 - k0, K] as screened, 0 where l <= k
+      info        dict(rows, ld, phiBytes, freeBytes, budgetBytes, buildMs, sweepMs, phiMs)"""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def pairCandidates(system: PowerSystem) -> np.ndarray:
+    """default candidates of the N-2 screen: labels of the in-service branches that are not bridges (and not self-loops), ascending"""
+    from .contingency import bridges
+    lay = system.branch.layout
+    return (np.flatnonzero((lay.status == 1) & ~bridges(system) & (lay.from_ != lay.to)) + 1).astype(np.int64)
+
+
+def _pair_lists(system: PowerSystem, candidates, monitored, rating):
+    """candidate and monitored labels of a pair screen, checked on the host before anything touches the device"""
+    nb, status = system.branch.number, system.branch.layout.status
+    rating = np.ascontiguousarray(rating, dtype=np.float64)
+    if rating.shape != (nb,):
+        raise ValueError("rating: one value per branch")
+    cand = pairCandidates(system) if candidates is None else np.asarray(list(candidates), dtype=np.int64)
+    if cand.size and (cand.min() < 1 or cand.max() > nb):
+        raise IndexError("dcPairScreen: candidate branch label out of range")
+    if np.unique(cand).size != cand.size:
+        raise ValueError("dcPairScreen: a candidate is named twice (a pair needs two different branches)")
+    if cand.size < 2:
+        raise ValueError("dcPairScreen: two or more candidates are needed")
+    off = cand[status[cand - 1] != 1]
+    if off.size:
+        raise ValueError(f"dcPairScreen: candidate branch {int(off[0])} is out of service")
+    if monitored is None:
+        mon = (np.flatnonzero((status == 1) & (rating > 0)) + 1).astype(np.int64)
+    else:
+        mon = np.unique(np.asarray(list(monitored), dtype=np.int64))
+        if mon.size and (mon.min() < 1 or mon.max() > nb):
+            raise IndexError("dcPairScreen: monitored branch label out of range")
+    return np.sort(cand), mon, rating
+
+
+PAIR_BLOCK_BYTES = 256 << 20                                           # default bound of the dense result of one device call (16 bytes per pair)
+
+
+def dcPairScreen(analysis_or_system, candidates=None, monitored=None, rating=None, threshold: float = 1.0, rows=None, capacity: int = 1 << 20,
+                 dense: bool = False, islandCapacity: int = 1 << 16, block=None, budget=None, device: int = 0) -> DcPairScreen:
+    """The DC N-2 screen: every pair k < l of `candidates` (labels; default pairCandidates(system)) out of service together, the worst |from| / rating over
+    `monitored` (default: every in-service branch with a rating > 0) per pair -- the loop updateBranch!(k), updateBranch!(l), solve!, power! over all
+    pairs, from ONE factor and one sweep pair per candidate (csrc/jg_dc_pair.hpp).
+      rows       (k0, k1): only the pairs whose FIRST branch is candidate position k0 .. k1 - 1 (what one rank of a sharded screen takes: shard())
+      block      candidate rows per device call (bounds the memory of a call; default: 256 MiB of dense result); the result does not depend on it
+      capacity / islandCapacity   most records / islanding pairs kept (the first by (k, l); the totals stay exact)
+      budget     bytes the kept sensitivities may take (default: 0.8 of the free device memory); JGridError code 5 with the sizes when they do not fit"""
+    own = isinstance(analysis_or_system, PowerSystem)
+    system = analysis_or_system if own else analysis_or_system.system
+    if rating is None:
+        raise ValueError("dcPairScreen: rating (per branch, per unit of active power) is needed")
+    if not threshold >= 0:
+        raise ValueError("dcPairScreen: threshold >= 0")
+    if own and system.model.dc.nodalMatrix is None:
+        dcModel_(system)
+    cand, mon, rating = _pair_lists(system, candidates, monitored, rating)
+    nk = int(cand.size)
+    k0, k1 = (0, nk - 1) if rows is None else (int(rows[0]), min(int(rows[1]), nk - 1))     # (the last candidate is the first branch of no pair)
+    if k0 < 0 or k1 < k0:
+        raise ValueError("dcPairScreen: rows = (k0, k1) with 0 <= k0 <= k1 <= candidates")
+    ld = (nk + 63) // 64 * 64
+    step = max(1, PAIR_BLOCK_BYTES // (ld * (24 if dense else 16))) if block is None else int(block)
+    if step < 1:
+        raise ValueError("dcPairScreen: block >= 1")
+    an = dcPowerFlow(system, device=device) if own else analysis_or_system
+    L = _lib.lib()
+    try:
+        if an._rhs is None:
+            an._rhs = np.ascontiguousarray(_base_rhs(system), dtype=np.float64)
+            _lib.check(L.jg_dc_set_rhs(an._h, an._rhs))
+        _set_rating(an, rating)
+        info = np.zeros(8)
+        _lib.check(L.jg_dc_pair_build(an._h, nk, cand, int(mon.size), mon.ctypes.data_as(_lib.VP), int(budget or 0), info))
+        ptr = lambda a: None if a is None else a.ctypes.data_as(_lib.VP)
+        rec = np.zeros((max(int(capacity), 0), 5))
+        isl = np.zeros((max(int(islandCapacity), 0), 2), dtype=np.int64)
+        worst = np.zeros(nk)
+        tot = np.zeros(3, dtype=np.int64)
+        nrec = nisl = 0
+        full = {name: np.zeros((k1 - k0, nk), dtype=dt) for name, dt in (("loading", np.float64), ("branch", np.int32), ("count", np.int32), ("determinant", np.float64))} if dense else None
+        for b0 in range(k0, k1, step):
+            b1 = min(b0 + step, k1)
+            t6 = np.zeros(6, dtype=np.int64)
+            part = {name: np.zeros((b1 - b0, nk), dtype=a.dtype) for name, a in full.items()} if dense else {}
+            r, i = rec[nrec:], isl[nisl:]
+            _lib.check(L.jg_dc_pair_screen(an._h, b0, b1, float(threshold), r.shape[0], ptr(r) if r.shape[0] else None, i.shape[0], ptr(i) if i.shape[0] else None,
+                                           t6, ptr(worst), ptr(part.get("loading")), ptr(part.get("branch")), ptr(part.get("count")), ptr(part.get("determinant"))))
+            tot += t6[:3]
+            nrec += int(t6[3])
+            nisl += int(t6[4])
+            for name, a in part.items():
+                full[name][b0 - k0:b1 - k0] = a
+        res = DcPairScreen(candidates=cand, monitored=mon, records=rec[:nrec].copy(), islanding=isl[:nisl].copy(), worst=worst, threshold=float(threshold),
+                           totals=dict(pairs=int(tot[0]), violating=int(tot[1]), islanding=int(tot[2])), overflow=bool(tot[1] > nrec),
+                           islandingOverflow=bool(tot[2] > nisl), rows=(k0, k1),
+                           info=dict(zip(("rows", "ld", "phiBytes", "freeBytes", "budgetBytes", "buildMs", "sweepMs", "phiMs"), (float(x) for x in info))))
+        for name, a in (full or {}).items():
+            if rows is None:                                            # the upper triangle, mirrored ([nk - 1, nk] rows came back: the last candidate has none)
+                a = np.vstack([a, np.zeros((1, nk), dtype=a.dtype)])
+                a = (a + a.T).astype(a.dtype)
+            setattr(res, name, a)
+        return res
+    finally:
+        if own:
+            an.close()
+        else:
+            _lib.check(L.jg_dc_pair_release(an._h))
