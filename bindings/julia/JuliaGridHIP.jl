@@ -1308,6 +1308,28 @@ end
 setOutagePairs!(b::DcPowerFlowBatch, first::Vector{Int64}, second::Vector{Int64}; lane0::Int64 = 0) =
     check(ccall((:jg_dc_set_outage_pairs, lib), Cint, (Int64, Int64, Int64, Ptr{Int64}, Ptr{Int64}), b.token, lane0, length(first), first, second))
 """
+    setIslandMode!(b, mode)
+
+`mode = 1`: lanes set AFTERWARDS by `setOutages!` whose branch is a bridge are solved on the side of the bridge that holds the slack (status 4, NaN angles on
+the buses that leave, flows 0 on the branches that touch them) instead of being skipped with status 3; `mode = 0` is the default (jgrid.h: jg_dc_set_island_mode).
+"""
+setIslandMode!(b::DcPowerFlowBatch, mode::Integer) = check(ccall((:jg_dc_set_island_mode, lib), Cint, (Int64, Cint), b.token, mode))
+"what the lanes of a solved batch shed, `[4, batch]`: buses, the right-hand side summed over them, the bridge's end `m` on the slack's side, the flow that left `m`"
+function islands(b::DcPowerFlowBatch)
+    rec = zeros(Float64, 4, dims(b)[2])
+    check(ccall((:jg_dc_get_islands, lib), Cint, (Int64, Ptr{Float64}), b.token, rec))
+    return rec
+end
+"host only: `(preorder, lo, hi, side)` -- the buses that leave with branch `k` are those with `lo[k] <= preorder <= hi[k]` (`lo > hi`: no bridge; jgrid.h: jg_dc_island_table)"
+function islandTable(system::PowerSystem)
+    br = system.branch
+    pre = zeros(Int32, system.bus.number)
+    lo = zeros(Int32, br.number); hi = zeros(Int32, br.number); side = zeros(Int32, br.number)
+    check(ccall((:jg_dc_island_table, lib), Cint, (Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Int64, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}),
+                system.bus.number, br.number, br.layout.from, br.layout.to, Float64.(br.layout.status .== 1), system.bus.layout.slack, pre, lo, hi, side))
+    return pre, lo, hi, side
+end
+"""
     pairScreenBuild!(b, candidates; monitored = nothing, budget = 0) -> info [8]
 
 The DC N-2 screen (jgrid.h: jg_dc_pair_*): one sweep pair per candidate branch (indices, in service, ascending) fills the outage sensitivities of the
@@ -1533,6 +1555,6 @@ export HIP, HIPOrthogonal, NewtonRaphsonBatch, BaseCase, baseInfo, baseInverseOn
        largestNormalizedResidual, normalizedResiduals, commUniqueId, Comm, shard, contingencyAnalysis, clearPlanCache,
        deviceCount, dims, setRefinement!, deviceMaps, setOutage!, snapshotVoltage!, restoreVoltage!, iterations, voltageDevice!, packResults!, packRows!,
        allgatherDevice, commRank, commWorld, timeKernel, setBusType!, busType, GaussNewtonBatch, setRealisations!, monteCarloEstimation, fastPatch!, setReadings!, drawNoise!, measurementDevice,
-       DcPowerFlowBatch, setInjections!, setOutagePairs!, pairScreenBuild!, pairScreen, pairTimeKernel, pairScreenRelease!, fromPower, angleDevice, DcStateEstimationBatch, removedRows, removeRows!
+       DcPowerFlowBatch, setInjections!, setOutagePairs!, pairScreenBuild!, pairScreen, pairTimeKernel, pairScreenRelease!, setIslandMode!, islands, islandTable, fromPower, angleDevice, DcStateEstimationBatch, removedRows, removeRows!
 
 end # module

@@ -495,7 +495,8 @@ int jg_dc_set_rating(int64_t h, const double* rating);
 int jg_dc_set_outages(int64_t h, int64_t lane0, int64_t count, const int64_t* branch);
 /*
  * solve!(analysis) for every lane (dcPowerFlow.jl:63-101): the base solution if the right-hand side changed, one sweep pair for the lanes' outages,
- * the rank-1 combine.  status per scenario: 0 solved, 3 the outaged branch is a bridge (the outage islands the grid; its angles are NaN).
+ * the rank-1 combine.  status per scenario: 0 solved, 3 the outaged branch is a bridge (the outage islands the grid; its angles are NaN);
+ * 4 only in island mode 1 (below): solved on the slack's island, the rest shed).
  *   jg_dc_get_angle     theta [batch][n] = analysis.voltage.angle, status [batch] (either may be NULL)
  *   jg_dc_angle_device  info[0] = device address of the angles, batch-minor [n][info[1]], info[2] = device address of the int32 status [info[1]]
  *   jg_dc_get_flows     power!(analysis) branch part (src/postprocessing/dcAnalysis.jl:41-48): from [batch][branches], to = -from; the outaged branch of a lane carries 0
@@ -522,6 +523,25 @@ int jg_dc_time_kernel(int64_t h, int kernel, int reps, double* ms);
  * jg_dc_set_outages over such lanes clears their second outage.
  */
 int jg_dc_set_outage_pairs(int64_t h, int64_t lane0, int64_t count, const int64_t* branch_a, const int64_t* branch_b);
+/*
+ * Bridge outages solved on the slack's island (an extension of the batch interface: the reference's solve! meets a singular matrix there).
+ *   jg_dc_set_island_mode   mode 0 (default): a lane whose outage is a bridge gets status 3 and NaN angles.  mode 1: lanes set AFTERWARDS by
+ *                       jg_dc_set_outages (or by jg_dc_set_outage_pairs with one branch) whose branch is a bridge are solved on the side of the bridge
+ *                       that holds the slack: status 4, the angles of the buses that leave are NaN, flows are 0 on the outaged branch and on every
+ *                       branch with an end among those buses, and the screen record covers the branches that stay.  The same sweep pair as any lane
+ *                       (right-hand side e_m, m the bridge's end on the slack's side) and a combine without a denominator (csrc/jg_dc.hpp).  Lanes with
+ *                       TWO outages and jg_dc_pair_screen keep status 3 for whatever islands.  Every other lane is bitwise what it is in mode 0.
+ *                       Needs jg_dc_set_branches.
+ *   jg_dc_get_islands   rec [batch][4] after jg_dc_solve: buses shed, the lane's right-hand side summed over them, m (1-based), g = the flow that left m
+ *                       over the bridge before the outage; zeros on lanes that shed nothing.
+ *   jg_dc_island_table  host only (no device is touched): the table behind it for a branch list (from / to 1-based, admittance 0 = out of service).
+ *                       preorder [n]: DFS number of every bus from the slack (-1: not reached); per branch lo, hi: the buses that leave with it are those
+ *                       with lo <= preorder <= hi (lo > hi: not a bridge), side: +1 / -1 the from / to end stays on the slack's side (0: not a bridge).
+ */
+int jg_dc_set_island_mode(int64_t h, int mode);
+int jg_dc_get_islands(int64_t h, double* rec);
+int jg_dc_island_table(int64_t n, int64_t nbr, const int64_t* from, const int64_t* to, const double* admittance, int64_t slack,
+                       int32_t* preorder, int32_t* lo, int32_t* hi, int32_t* side);
 /*
  * The DC N-2 screen over ALL pairs k < l of a candidate list, from the one factor and the kept outage sensitivities (csrc/jg_dc_pair.hpp): the user loop
  * updateBranch!(k), updateBranch!(l), solve!, power! over all pairs.  Needs jg_dc_set_branches and jg_dc_set_rhs; the lanes of the handle are not touched.

@@ -154,6 +154,9 @@ def lib():
         "jg_dc_pack_results_device": [C.c_int64, VP],
         "jg_dc_time_kernel": [C.c_int64, C.c_int, C.c_int, F64P],
         "jg_dc_set_outage_pairs": [C.c_int64, C.c_int64, C.c_int64, I64P, I64P],
+        "jg_dc_set_island_mode": [C.c_int64, C.c_int],
+        "jg_dc_get_islands": [C.c_int64, F64P],
+        "jg_dc_island_table": [C.c_int64, C.c_int64, I64P, I64P, F64P, C.c_int64, I32P, I32P, I32P, I32P],
         "jg_dc_pair_build": [C.c_int64, C.c_int64, I64P, C.c_int64, VP, C.c_int64, F64P],
         "jg_dc_pair_screen": [C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_int64, VP, C.c_int64, VP, I64P, VP, VP, VP, VP, VP],
         "jg_dc_pair_time_kernel": [C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int, F64P],

@@ -61,10 +61,30 @@ def bridges(system: PowerSystem) -> np.ndarray:
     return is_bridge
 
 
-def outageList(system: PowerSystem, count: int, seed: int = 512) -> np.ndarray:
+def islandTable(system: PowerSystem):
+    """Who leaves with each bridge, from ONE DFS of the in-service bus graph rooted at the slack (jg_dc_island_table, host code of the library: the table
+    a DC handle builds for islands="shed").  The subtree below a bridge is a contiguous interval of preorder numbers and never holds the slack:
+      preorder [n]   DFS number of every bus (-1: the slack does not reach it)
+      lo, hi [nb]    the buses that leave with branch k are those with lo[k] <= preorder <= hi[k]; lo > hi: k is not a bridge (a doubled branch never is)
+      side [nb]      +1 / -1: the from / to end of the bridge stays on the slack's side; 0: not a bridge
+      m [nb]         that end (1-based bus, 0: not a bridge)
+      order [n]      the buses by preorder number (reached buses only): order[lo[k]:hi[k] + 1] are the buses that leave"""
+    from types import SimpleNamespace as NS
+    n, nb, lay = system.bus.number, system.branch.number, system.branch.layout
+    pre = np.zeros(n, dtype=np.int32)
+    lo, hi, side = (np.zeros(nb, dtype=np.int32) for _ in range(3))
+    _lib.check(_lib.lib().jg_dc_island_table(n, nb, np.ascontiguousarray(lay.from_, dtype=np.int64), np.ascontiguousarray(lay.to, dtype=np.int64),
+                                             np.ascontiguousarray(lay.status == 1, dtype=np.float64), int(system.bus.layout.slack), pre, lo, hi, side))
+    m = np.where(side > 0, lay.from_, np.where(side < 0, lay.to, 0)).astype(np.int64)
+    reached = np.flatnonzero(pre >= 0)
+    order = reached[np.argsort(pre[reached])]
+    return NS(preorder=pre, lo=lo, hi=hi, side=side, m=m, order=order)
+
+
+def outageList(system: PowerSystem, count: int, seed: int = 512, keepBridges: bool = False) -> np.ndarray:
     """`count` branch labels (1-based) drawn by a seeded shuffle of the non-bridge in-service branches
-    (BASELINE config 5); wraps around if the grid has fewer candidates."""
-    ok = np.flatnonzero((system.branch.layout.status == 1) & ~bridges(system)
+    (BASELINE config 5); wraps around if the grid has fewer candidates.  keepBridges: the bridges stay in the draw (a DC screen with islands="shed")."""
+    ok = np.flatnonzero((system.branch.layout.status == 1) & (keepBridges | ~bridges(system))
                         & (system.branch.layout.from_ != system.branch.layout.to))
     rng = np.random.default_rng(seed)
     rng.shuffle(ok)
@@ -110,14 +130,19 @@ def deviceBatching(share: int, steps: int, lanes: int = 512) -> int:
 
 
 def contingencyAnalysis(system: PowerSystem, labels, device: int = 0, method: str = "nr", reactiveLimit: int = 0, start=None,
-                        iteration: int = 20, tolerance: float = 1e-8, rating=None) -> "AcPowerFlow | DcPowerFlow":
+                        iteration: int = 20, tolerance: float = 1e-8, rating=None, islands: str = "skip") -> "AcPowerFlow | DcPowerFlow":
     """Batched analysis with scenario s = outage of branch labels[s] (None / 0 = base case).  method: "nr" Newton-Raphson, "bx" / "xb" fast
     Newton-Raphson (constant matrices with per-scenario edits, ONE factorisation for the batch: jg_nr_fast_patch_batch).
     reactiveLimit = k > 0 (Newton-Raphson, two or more scenarios): the analysis is also SOLVED -- from `start` (V, theta) when given -- with up to k rounds
     of reactiveLimit! + powerFlow! per scenario (powerflow.powerFlowLimits_); method.iteration sums the solves of each scenario (test/powerFlow/limits.jl).
     method "dc" (the only one that takes a tuple (k, l) as a label: a scenario with TWO outages): the DC model instead -- a SOLVED DcPowerFlow comes back (voltage.angle [batch, n], status [batch] with 3 on bridges, and, when `rating`
-    (per branch, per unit of active power) is given, screen [batch, 5]: dcpowerflow.screenSummary_)."""
+    (per branch, per unit of active power) is given, screen [batch, 5]: dcpowerflow.screenSummary_).  islands="shed" (method "dc" only): a bridge outage is
+    solved on the slack's island instead of being skipped (status 4, analysis.island: dcpowerflow.setOutages_)."""
     labels = list(labels)
+    if islands not in ("skip", "shed"):
+        raise ValueError("contingencyAnalysis: islands is 'skip' or 'shed'")
+    if method != "dc" and islands != "skip":
+        raise ValueError("contingencyAnalysis: islands='shed' belongs to method='dc'")
     if method == "dc" and (reactiveLimit or start is not None or iteration != 20 or tolerance != 1e-8):
         raise ValueError("contingencyAnalysis: reactiveLimit, start, iteration and tolerance have no meaning for method='dc' (nothing is iterated)")
     if method != "dc" and rating is not None:
@@ -126,7 +151,7 @@ def contingencyAnalysis(system: PowerSystem, labels, device: int = 0, method: st
         raise ValueError("contingencyAnalysis: a tuple (k, l) of two outages is a DC scenario (method='dc'); nr / bx / xb take one branch per scenario")
     if method == "dc":                                          # the pre-filter of a screen: solved on return, one factor for the whole batch (dcpowerflow.py)
         from .dcpowerflow import dcContingencyAnalysis
-        return dcContingencyAnalysis(system, labels, device=device, rating=rating)
+        return dcContingencyAnalysis(system, labels, device=device, rating=rating, islands=islands)
     if reactiveLimit and (method != "nr" or len(labels) < 2):
         raise ValueError("contingencyAnalysis: reactiveLimit needs method='nr' and two or more scenarios")
     if method in ("bx", "xb"):

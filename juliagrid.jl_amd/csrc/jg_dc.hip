@@ -27,8 +27,16 @@ struct DcCombineArgs {
     const int* of; const int* ot; const int* obr; const double* oy; const double* osh;
     double* TH; int* status;
     double slack_angle; int n, ld, slack;
+    // ISL (island mode 1 and a lane that needs it): preorder [n]; isl [ld] = (S end of the bridge or -1, lo, hi, side); rhs0 [n][64] / RHS [n][ld] the
+    // right-hand sides the shed record sums; ipart [chunks][2][ld]; ig [ld]
+    const int* preorder; const I4* isl; const double* rhs0; const double* RHS; double* ipart; double* ig;
 };
 constexpr int DC_COMBINE_ROWS = 8;
+// ISL: a lane whose outage is a bridge, set in island mode 1, has o_from = m (the bridge's end on the slack's side; -1: m is the slack) and o_to = -1, so
+// Z holds z = B^-1 e_m.  theta = x0 + g z outside the preorder interval lo .. hi of the side S that leaves, NaN inside, status 4; g = the flow on the
+// bridge that left m.  Each wave also leaves the buses of S among its rows and their right-hand side in ipart (k_dc_island_final adds them up in
+// order).  The other lanes take the expressions of ISL = false unchanged.
+template <bool ISL>
 __global__ __launch_bounds__(256) void k_dc_combine(DcCombineArgs a) {
     const int wave = uniform(threadIdx.y);
     const int grp = blockIdx.y;
@@ -42,15 +50,51 @@ __global__ __launch_bounds__(256) void k_dc_combine(DcCombineArgs a) {
     const double ax = ((fi >= 0 ? x0(fi) : 0.0) - (ti >= 0 ? x0(ti) : 0.0)) - sh * az;
     const double den = 1.0 - yk * az;
     const bool sing = has && fabs(den) < DC_SINGULAR;
-    const double c = (has && !sing) ? yk * ax / den - sh : 0.0;      // theta = x0 - sh z + z y (a'x) / den
-    if (blockIdx.x == 0 && wave == 0) a.status[bl] = sing ? 3 : 0;
+    double c = (has && !sing) ? yk * ax / den - sh : 0.0;            // theta = x0 - sh z + z y (a'x) / den
+    bool dead = sing, island = false;
+    int lo = 1, hi = 0;
+    if (ISL) {
+        const I4 q = a.isl[bl];
+        island = q[0] >= 0;
+        if (island) {
+            lo = q[1]; hi = q[2];
+            const double xm = fi >= 0 ? x0(fi) : 0.0, xs = x0(q[0]);
+            c = q[3] > 0 ? yk * (xm - xs) - sh : -(yk * (xs - xm) - sh);      // +- y_k (x_f - x_t - shiftAngle_k), + when m is the from end
+            dead = false;
+        }
+        if (blockIdx.x == 0 && wave == 0) a.ig[bl] = island ? c : 0.0;
+    }
+    if (blockIdx.x == 0 && wave == 0) a.status[bl] = island ? 4 : (sing ? 3 : 0);
     const int b0 = (blockIdx.x * 4 + wave) * DC_COMBINE_ROWS;
+    double shed_n = 0.0, shed_p = 0.0;
     for (int bus = b0; bus < min(b0 + DC_COMBINE_ROWS, a.n); ++bus) {
         double th = x0(bus) + c * a.Z[(size_t)bus * ld + bl] + a.slack_angle;
         if (bus == a.slack) th = a.slack_angle;
-        if (sing) th = __longlong_as_double(0x7ff8000000000000LL);
+        if (dead) th = __longlong_as_double(0x7ff8000000000000LL);
+        if (ISL) {
+            const int pre = ((CInt)a.preorder)[bus];
+            if (pre >= lo && pre <= hi) {
+                th = __longlong_as_double(0x7ff8000000000000LL);
+                shed_n += 1.0;
+                shed_p += own ? a.RHS[(size_t)bus * ld + bl] : a.rhs0[(size_t)bus * 64];
+            }
+        }
         a.TH[(size_t)bus * ld + bl] = th;
     }
+    if (ISL) {
+        double* q = a.ipart + (size_t)(blockIdx.x * 4 + wave) * 2 * ld + bl;
+        q[0] = shed_n; q[ld] = shed_p;
+    }
+}
+// the shed record of every lane: the chunks of k_dc_combine<true> in ascending order
+__global__ __launch_bounds__(64) void k_dc_island_final(const double* ipart, double* irec, int chunks, int ld) {
+    const size_t bl = (size_t)blockIdx.x * 64 + threadIdx.x;
+    double cnt = 0.0, net = 0.0;
+    for (int c = 0; c < chunks; ++c) {
+        const double* q = ipart + (size_t)c * 2 * ld + bl;
+        cnt += q[0]; net += q[ld];
+    }
+    irec[bl] = cnt; irec[(size_t)ld + bl] = net;                         // (row 2 of irec, g, is k_dc_combine's)
 }
 
 // ---- the rank-2 combine of the lanes with a second outage (jg_dc_set_outage_pairs) ------------------------------------------------------------
@@ -133,7 +177,11 @@ void launch_combine(DcHandle* h) {
     c.of = h->o_from; c.ot = h->o_to; c.obr = h->o_br; c.oy = h->o_y; c.osh = h->o_sh;
     c.TH = h->TH; c.status = h->status; c.slack_angle = h->slack_angle; c.n = h->n; c.ld = h->ld; c.slack = h->slack;
     const int per = 4 * DC_COMBINE_ROWS;
-    hipLaunchKernelGGL(k_dc_combine, dim3((h->n + per - 1) / per, h->ld / 64), dim3(64, 4), 0, h->stream, c);
+    if (h->n_isl) {                                                      // a batch without an island lane runs the kernel it always ran
+        c.preorder = h->preorder; c.isl = (const I4*)h->isl; c.rhs0 = h->rhs0; c.RHS = h->RHS; c.ipart = h->ipart; c.ig = h->irec + 2 * (size_t)h->ld;
+        hipLaunchKernelGGL(k_dc_combine<true>, dim3((h->n + per - 1) / per, h->ld / 64), dim3(64, 4), 0, h->stream, c);
+    } else
+        hipLaunchKernelGGL(k_dc_combine<false>, dim3((h->n + per - 1) / per, h->ld / 64), dim3(64, 4), 0, h->stream, c);
     if (!h->n_glist2) return;
     DcCombine2Args q{};
     q.Z = h->Z; q.Z2 = h->Z2; q.XS = h->XS; q.th0 = h->th0; q.ginj = c.ginj; q.groups = h->glist2;
@@ -149,7 +197,11 @@ int launch_flows(DcHandle* h, bool store) {
     DcFlowArgs f{};
     f.TH = h->TH; f.bf = h->b_from; f.bt = h->b_to; f.by = h->b_y; f.bs = h->b_shift; f.rating = h->b_rating; f.obr = h->o_br; f.obr2 = h->o2_br;
     f.flows = store ? h->flows : nullptr; f.part = h->part; f.nbr = h->nbr; f.ld = h->ld;
-    hipLaunchKernelGGL(k_dc_flows, dim3((h->n_chunks + 3) / 4, h->ld / 64), dim3(64, 4), 0, h->stream, f);
+    if (h->n_isl) {
+        f.preorder = h->preorder; f.isl = (const I4*)h->isl;
+        hipLaunchKernelGGL(k_dc_flows<true>, dim3((h->n_chunks + 3) / 4, h->ld / 64), dim3(64, 4), 0, h->stream, f);
+    } else
+        hipLaunchKernelGGL(k_dc_flows<false>, dim3((h->n_chunks + 3) / 4, h->ld / 64), dim3(64, 4), 0, h->stream, f);
     hipLaunchKernelGGL(k_dc_screen_final, dim3(h->ld / 64), dim3(64), 0, h->stream, h->part, h->status, h->screen, h->n_chunks, h->ld, h->batch);
     DC_HIP(hipGetLastError());
     return 0;
@@ -374,6 +426,8 @@ static int dc_set_lane_outages(DcHandle* d, const char* who, int64_t lane0, int6
     if (!count) return 0;
     std::vector<int> of(count), ot(count), ob(count), of2(count, -1), ot2(count, -1), ob2(count, -1);
     std::vector<double> oy(count), os(count), oy2(count, 0.0), os2(count, 0.0);
+    std::vector<int> isl(d->isl ? 4 * (size_t)count : 0), isl_m(count, 0);      // (a handle that never saw island mode 1 keeps no such table)
+    for (size_t s = 0; s < isl.size(); s += 4) { isl[s] = -1; isl[s + 1] = 1; isl[s + 2] = 0; isl[s + 3] = 0; }
     bool second = false;
     for (int64_t s = 0; s < count; ++s) {
         int64_t k = branch[s] - 1, k2 = branch2 ? branch2[s] - 1 : -1;
@@ -384,6 +438,12 @@ static int dc_set_lane_outages(DcHandle* d, const char* who, int64_t lane0, int6
         of[s] = d->h_from[k] == d->slack ? -1 : d->h_from[k];           // the slack's component of a = e_from - e_to is dropped
         ot[s] = d->h_to[k] == d->slack ? -1 : d->h_to[k];
         ob[s] = (int)k; oy[s] = d->h_y[k]; os[s] = d->h_shift[k] * d->h_y[k];
+        if (d->island_mode == 1 && k2 < 0 && d->h_bside[k] != 0) {       // a bridge, alone in its lane: the right-hand side of the sweep is e_m
+            const int m = d->h_bside[k] > 0 ? d->h_from[k] : d->h_to[k];
+            of[s] = m == d->slack ? -1 : m; ot[s] = -1;
+            isl[4 * s] = d->h_bside[k] > 0 ? d->h_to[k] : d->h_from[k]; isl[4 * s + 1] = d->h_blo[k]; isl[4 * s + 2] = d->h_bhi[k]; isl[4 * s + 3] = d->h_bside[k];
+            isl_m[s] = m + 1;
+        }
         if (k2 < 0) continue;
         second = true;
         of2[s] = d->h_from[k2] == d->slack ? -1 : d->h_from[k2];
@@ -409,6 +469,11 @@ static int dc_set_lane_outages(DcHandle* d, const char* who, int64_t lane0, int6
     DC_API_HIP(hipMemcpyAsync(d->o_br + lane0, ob.data(), count * sizeof(int), hipMemcpyHostToDevice, d->stream));
     DC_API_HIP(hipMemcpyAsync(d->o_y + lane0, oy.data(), count * sizeof(double), hipMemcpyHostToDevice, d->stream));
     DC_API_HIP(hipMemcpyAsync(d->o_sh + lane0, os.data(), count * sizeof(double), hipMemcpyHostToDevice, d->stream));
+    if (d->isl) {
+        DC_API_HIP(hipMemcpyAsync(d->isl + 4 * lane0, isl.data(), isl.size() * sizeof(int), hipMemcpyHostToDevice, d->stream));
+        std::copy(isl_m.begin(), isl_m.end(), d->h_isl_m.begin() + lane0);
+        d->n_isl = (int)std::count_if(d->h_isl_m.begin(), d->h_isl_m.end(), [](int m) { return m != 0; });
+    }
     std::vector<int> list;
     if (d->o2_br) {                                                      // (also a plain jg_dc_set_outages over lanes that held a pair)
         DC_API_HIP(hipMemcpyAsync(d->o2_from + lane0, of2.data(), count * sizeof(int), hipMemcpyHostToDevice, d->stream));
@@ -424,6 +489,44 @@ static int dc_set_lane_outages(DcHandle* d, const char* who, int64_t lane0, int6
     }
     DC_API_HIP(hipStreamSynchronize(d->stream));                         // the host vectors go out of scope
     d->solved = false;
+    return 0;
+}
+
+int jg_dc_set_island_mode(int64_t h, int mode) {
+    DC_ENTER(h);
+    if (mode != 0 && mode != 1) return faild(1, "jg_dc_set_island_mode: mode is 0 (a bridge outage is skipped: status 3) or 1 (solved on the slack's island: status 4)");
+    if (mode == 1 && !d->nbr) return faild(1, "jg_dc_set_island_mode: jg_dc_set_branches first");
+    if (mode == 1 && !d->isl) {                                          // the table of the handle's grid and the lanes' records, once
+        const size_t n = (size_t)d->n, nb = (size_t)d->nbr, ld = (size_t)d->ld;
+        d->h_pre.resize(n); d->h_blo.resize(nb); d->h_bhi.resize(nb); d->h_bside.resize(nb);
+        jg::dc_island_table(d->n, d->nbr, d->h_from.data(), d->h_to.data(), d->h_y.data(), d->slack, d->h_pre.data(), d->h_blo.data(), d->h_bhi.data(), d->h_bside.data());
+        DC_RET(jg::dev_alloc(d, &d->preorder, n, d->h_pre.data()));
+        const int chunks = (d->n + 4 * jg::DC_COMBINE_ROWS - 1) / (4 * jg::DC_COMBINE_ROWS) * 4;
+        DC_RET(jg::dev_alloc(d, &d->ipart, (size_t)chunks * 2 * ld, (const double*)nullptr, true));
+        DC_RET(jg::dev_alloc(d, &d->irec, 3 * ld, (const double*)nullptr, true));
+        std::vector<int> none(4 * ld);
+        for (size_t s = 0; s < ld; ++s) { none[4 * s] = -1; none[4 * s + 1] = 1; none[4 * s + 2] = 0; none[4 * s + 3] = 0; }
+        DC_RET(jg::dev_alloc(d, &d->isl, 4 * ld, none.data()));
+        d->h_isl_m.assign(ld, 0);
+    }
+    d->island_mode = mode;
+    return 0;
+}
+
+int jg_dc_get_islands(int64_t h, double* rec) {
+    DC_ENTER(h);
+    if (!d->solved) return faild(4, "jg_dc_get_islands: jg_dc_solve first");
+    if (!rec) return faild(1, "jg_dc_get_islands: null pointer");
+    std::fill(rec, rec + (size_t)d->batch * 4, 0.0);
+    if (!d->n_isl) return 0;
+    const size_t ld = (size_t)d->ld;
+    const int chunks = (d->n + 4 * jg::DC_COMBINE_ROWS - 1) / (4 * jg::DC_COMBINE_ROWS) * 4;
+    hipLaunchKernelGGL(jg::k_dc_island_final, dim3(d->ld / 64), dim3(64), 0, d->stream, d->ipart, d->irec, chunks, d->ld);
+    DC_API_HIP(hipGetLastError());
+    std::vector<double> t(3 * ld);
+    DC_API_HIP(jg::sync_copy(t.data(), d->irec, 3 * ld * sizeof(double), hipMemcpyDeviceToHost, d->stream));
+    for (size_t s = 0; s < (size_t)d->batch; ++s)
+        if (d->h_isl_m[s]) { rec[4 * s] = t[s]; rec[4 * s + 1] = t[ld + s]; rec[4 * s + 2] = (double)d->h_isl_m[s]; rec[4 * s + 3] = t[2 * ld + s]; }
     return 0;
 }
 

@@ -11,6 +11,12 @@
 //     theta_s = x_s + z_s y_k (a' x_s) / (1 - y_k a' z_s)
 // 1 - y_k a' z_s = 0: the branch is a bridge, the scenario gets status 3 (the code of islanding outages) and its angles are NaN.
 //
+// Island mode 1 ("shed") solves such a lane on the side M of the bridge that holds the slack instead.  With m the bridge's end in M, S the other side:
+// every injection in S reaches M through m, so zeroing S's net injection leaves no flow on k and removing k then changes nothing in M:
+//     theta_M = x_M + g z_M,   z = B^-1 e_m (slack component dropped),   g = the flow on k that LEAVES m before the outage
+// the same sweep pair with ONE unit entry in the right-hand side, a combine without a denominator; status 4, NaN on S.  S is an interval of DFS preorder
+// numbers (dc_island_table below), so a lane carries (lo, hi) and no bus list.
+//
 // It is the scalar counterpart of jg_comp.hip: the factor VALUES are wave-uniform (scalar loads of a few hundred KB), a wavefront is one row x 64
 // scenarios, the only vector traffic is the right-hand sides (8 bytes per row and scenario), batch-minor with ld = batch rounded up to 64.
 #pragma once
@@ -73,6 +79,14 @@ struct DcHandle {
     double* Z2 = nullptr;                                                      // [n][ld] z of the second outage, for the groups of glist2
     int* glist2 = nullptr; std::vector<int> h_o2; int n_glist2 = 0;            // lane groups that hold a second outage
     DcPairState* pair = nullptr;                                               // the N-2 screen's kept sensitivities (jg_dc_pair.hpp)
+    // bridge outages solved on the slack's island (jg_dc_set_island_mode 1): allocated by the first such call, a handle without it holds none of it
+    int island_mode = 0, n_isl = 0;                                            // n_isl: lanes whose ONE outage is a bridge, set while the mode was 1
+    std::vector<int> h_pre, h_blo, h_bhi, h_bside;                             // dc_island_table of the handle's branch table
+    std::vector<int> h_isl_m;                                                  // [ld] m of an island lane (1-based), 0: not an island lane
+    int* preorder = nullptr;                                                   // [n]
+    int* isl = nullptr;                                                        // [ld][4] per lane: S end of the bridge (-1: not an island lane), lo, hi, side
+    double* ipart = nullptr;                                                   // [island chunks][2][ld]: buses and right-hand side shed, per chunk of buses
+    double* irec = nullptr;                                                    // [3][ld]: buses shed, right-hand side shed, g
     // branches
     std::vector<int> h_from, h_to; std::vector<double> h_y, h_shift;
     int* b_from = nullptr; int* b_to = nullptr; double* b_y = nullptr; double* b_shift = nullptr; double* b_rating = nullptr; double* rating_buf = nullptr;
@@ -81,5 +95,12 @@ struct DcHandle {
     bool solved = false;
     std::vector<void*> allocs;                                                 // everything the handle owns on the device
 };
+
+// Who leaves with a bridge: ONE DFS of the in-service bus graph (admittance != 0, self-loops aside) from the slack numbers the buses in preorder; the
+// subtree below a tree edge is a contiguous interval of those numbers, and a tree edge (p, u) is a bridge iff no edge other than itself leaves u's subtree
+// (low-link; the parent EDGE is skipped by its index, so one of two parallel branches is never a bridge).  Rooted at the slack, the subtree is the side S
+// WITHOUT the slack.  Per branch: lo..hi the interval of S (lo > hi: not a bridge), side +1 / -1: the end m on the slack's side is the from / to end
+// (0: not a bridge).  preorder is -1 on buses the slack does not reach.  Host only; 0-based buses.
+void dc_island_table(int n, int nbr, const int* from, const int* to, const double* admittance, int slack, int* preorder, int* lo, int* hi, int* side);
 
 }  // namespace jg

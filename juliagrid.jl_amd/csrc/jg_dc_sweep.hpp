@@ -139,8 +139,11 @@ struct DcFlowArgs {
     double* flows;                      // nullable [nbr][ld]
     double* part;                       // [chunks][4][ld]: worst loading, its branch, largest |from|, its branch
     int nbr, ld;
+    const int* preorder; const I4* isl; // ISL: DFS preorder number per bus; per lane (S end, lo, hi, side) of a bridge outage solved on the slack's island
 };
 constexpr int DC_FLOW_BRANCHES = 32;    // per wave
+// ISL: a lane whose outage sheds the buses with preorder numbers lo .. hi (their angles are NaN) carries 0 on every branch with an end among them
+template <bool ISL>
 __global__ __launch_bounds__(256) void k_dc_flows(DcFlowArgs a) {
     const int wave = uniform(threadIdx.y);
     const int chunk = blockIdx.x * 4 + wave;
@@ -148,12 +151,18 @@ __global__ __launch_bounds__(256) void k_dc_flows(DcFlowArgs a) {
     if (k0 >= a.nbr) return;
     const size_t ld = (size_t)a.ld, bl = (size_t)blockIdx.y * 64 + threadIdx.x;
     const int out = a.obr[bl], out2 = a.obr2 ? a.obr2[bl] : -1;
+    int lo = 1, hi = 0;
+    if (ISL) { const I4 q = a.isl[bl]; lo = q[1]; hi = q[2]; }
     double wl = 0.0, wf = 0.0, il = 0.0, jf = 0.0;
     for (int k = k0; k < min(k0 + DC_FLOW_BRANCHES, a.nbr); ++k) {
         const int f = ((CInt)a.bf)[k], t = ((CInt)a.bt)[k];
         const double y = ((CDbl)a.by)[k], s = ((CDbl)a.bs)[k];
         double p = y * (a.TH[(size_t)f * ld + bl] - a.TH[(size_t)t * ld + bl] - s);
         if (k == out || k == out2) p = 0.0;
+        if (ISL) {
+            const int pf = ((CInt)a.preorder)[f], pt = ((CInt)a.preorder)[t];
+            if ((pf >= lo && pf <= hi) || (pt >= lo && pt <= hi)) p = 0.0;
+        }
         if (a.flows) a.flows[(size_t)k * ld + bl] = p;
         const double m = fabs(p);
         if (m > wf) { wf = m; jf = (double)(k + 1); }

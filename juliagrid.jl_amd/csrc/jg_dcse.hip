@@ -694,7 +694,7 @@ int jg_dcse_get_flows(int64_t h, double* from) {
     jg::DcFlowArgs f{};
     f.TH = d->cur; f.bf = d->b_from; f.bt = d->b_to; f.by = d->b_y; f.bs = d->b_shift; f.rating = nullptr; f.obr = d->o_none;
     f.flows = d->flows; f.part = d->fpart; f.nbr = d->nbr; f.ld = d->ld;
-    hipLaunchKernelGGL(jg::k_dc_flows, dim3((d->n_fchunks + 3) / 4, d->ld / 64), dim3(64, 4), 0, d->stream, f);
+    hipLaunchKernelGGL(jg::k_dc_flows<false>, dim3((d->n_fchunks + 3) / 4, d->ld / 64), dim3(64, 4), 0, d->stream, f);
     SE_HIP(hipGetLastError());
     SE_RET(fetch_lanes(d, d->flows, (size_t)d->nbr, from, 0.0));
     return 0;

@@ -4,7 +4,8 @@
   solve!(analysis)             src/powerFlow/dcPowerFlow.jl:63-101
   power!(analysis)             src/postprocessing/dcAnalysis.jl:27-75 and its branch part (:41-48 of allPowerBranch)
   updateBranch!(analysis; label, status = 0) -> solve!   per scenario: setOutages_ (one shared factor, a rank-1 correction per lane: csrc/jg_dc.hpp;
-                                                         a tuple (k, l) is a lane with two outages: a 2 x 2 correction)
+                                                         a tuple (k, l) is a lane with two outages: a 2 x 2 correction; islands="shed": a bridge
+                                                         outage is solved on the slack's island, which the reference cannot do)
   the same loop over ALL pairs of a candidate list          dcPairScreen (the DC N-2 screen: csrc/jg_dc_pair.hpp)
 
 All numerics run in libjgrid_hip.so (csrc/jg_dc.hip); the O(n) bus / generator bookkeeping of power! runs here.  A batched analysis keeps
@@ -45,6 +46,9 @@ class DcPowerFlow:
         self._outage_labels2 = np.zeros(self.batch, dtype=np.int64)
         self._injection = None                                          # [batch, n] net injections of the scenarios that have their own, NaN rows elsewhere
         self._rhs = None
+        self._island_mode = 0                                           # what jg_dc_set_island_mode was last told
+        self._island_table = None                                       # contingency.islandTable(system), once, when islands="shed" is first asked for
+        self.island = None
 
     def _shape(self, a):
         return a[0] if self.batch == 1 else a
@@ -105,7 +109,8 @@ def _set_rating(an: DcPowerFlow, rating):
 
 
 def solve_(an: DcPowerFlow):
-    """solve!(analysis::DcPowerFlow) for every scenario; analysis.status: 0, or 3 where the outaged branch is a bridge (angles NaN)."""
+    """solve!(analysis::DcPowerFlow) for every scenario; analysis.status: 0, or 3 where the outaged branch is a bridge (angles NaN); 4 on a bridge lane
+    set with islands="shed" (solved on the slack's island, NaN on the buses that leave; analysis.island holds what was shed)."""
     rhs = np.ascontiguousarray(_base_rhs(an.system), dtype=np.float64)
     if an._rhs is None or not np.array_equal(rhs, an._rhs):
         _lib.check(_lib.lib().jg_dc_set_rhs(an._h, rhs))
@@ -118,6 +123,50 @@ def solve_(an: DcPowerFlow):
     _lib.check(_lib.lib().jg_dc_get_angle(an._h, th.reshape(-1), st))
     an.voltage.angle = an._shape(th)
     an.status = int(st[0]) if an.batch == 1 else st
+    an.island = _island_record(an) if an._island_table is not None else None
+
+
+ISLAND_MODES = {"skip": 0, "shed": 1}
+
+
+def _island_mode(islands) -> int:
+    if islands not in ISLAND_MODES:
+        raise ValueError("islands is 'skip' (a bridge outage gets status 3) or 'shed' (it is solved on the slack's island: status 4)")
+    return ISLAND_MODES[islands]
+
+
+def _island_record(an: DcPowerFlow):
+    """analysis.island of a solved batch, [batch] each: buses shed (0: the lane shed nothing), injection = the lane's right-hand side summed over them
+    (supply - demand - shunt conductance - shiftPower, of the lane's own injections where it has them), m = the bridge's end on the slack's side
+    (1-based), flow = what left m over the bridge before the outage -- all from the device -- and demand / supply shed, prefix sums over the preorder
+    of the system's own values (NaN on a shedding lane with injections of its own, which carry no such split)."""
+    rec = np.zeros((an.batch, 4))
+    _lib.check(_lib.lib().jg_dc_get_islands(an._h, rec.reshape(-1)))
+    tb, bus = an._island_table, an.system.bus
+    lab = an._outage_labels - 1
+    isl = rec[:, 2] > 0
+    lo = np.where(isl, tb.lo[lab], 0)
+    hi = np.where(isl, tb.hi[lab], -1)
+    own = np.zeros(an.batch, dtype=bool) if an._injection is None else ~np.isnan(an._injection[:, 0])
+    out = {}
+    for name, v in (("demand", bus.demand.active), ("supply", bus.supply.active)):
+        cs = np.r_[0.0, np.cumsum(v[tb.order], dtype=np.longdouble)]   # (extended precision where the platform has it: the difference of two long sums)
+        out[name] = np.where(isl & own, np.nan, (cs[hi + 1] - cs[lo]).astype(np.float64))
+    return NS(buses=an._shape(rec[:, 0].astype(np.int64)), injection=an._shape(rec[:, 1].copy()), m=an._shape(rec[:, 2].astype(np.int64)),
+              flow=an._shape(rec[:, 3].copy()), demand=an._shape(out["demand"]), supply=an._shape(out["supply"]))
+
+
+def _shed_mask(an: DcPowerFlow):
+    """[batch, n] True on the buses a lane shed, or None when no lane shed any"""
+    if an.island is None or not np.any(np.atleast_1d(an.island.buses)):
+        return None
+    tb = an._island_table
+    lab = an._outage_labels - 1
+    isl = np.atleast_1d(an.island.buses) > 0
+    lo = np.where(isl, tb.lo[lab], 1)
+    hi = np.where(isl, tb.hi[lab], 0)
+    pre = tb.preorder[None, :]
+    return (pre >= lo[:, None]) & (pre <= hi[:, None])
 
 
 def powerFlow_(an: DcPowerFlow, power: bool = False):
@@ -146,10 +195,19 @@ def outagePairs(labels, branches: int):
     return a, b
 
 
-def setOutages_(an: DcPowerFlow, labels, scenario0: int = 0):
+def setOutages_(an: DcPowerFlow, labels, scenario0: int = 0, islands: str = "skip"):
     """scenario scenario0 + s = base grid with branch labels[s] out of service (0 / None = base grid; a tuple (k, l): BOTH branches): the reference's
-    updateBranch!(analysis; label, status = 0) per scenario, without touching the factor."""
+    updateBranch!(analysis; label, status = 0) per scenario, without touching the factor.  islands="shed": a lane of THIS call whose one outage is a
+    bridge is solved on the side of the bridge that holds the slack (status 4, NaN angles on the buses that leave, analysis.island after solve_) instead
+    of being skipped with status 3; lanes with two outages keep status 3 for whatever islands."""
+    mode = _island_mode(islands)                                        # refused on the host, before the device is touched
     lab, lab2 = outagePairs(list(labels), an.system.branch.number)
+    if mode != an._island_mode:
+        if mode and an._island_table is None:
+            from .contingency import islandTable
+            an._island_table = islandTable(an.system)
+        _lib.check(_lib.lib().jg_dc_set_island_mode(an._h, mode))
+        an._island_mode = mode
     if lab2.any():
         _lib.check(_lib.lib().jg_dc_set_outage_pairs(an._h, int(scenario0), int(lab.size), lab, lab2))
     else:
@@ -210,6 +268,11 @@ def power_(an: DcPowerFlow):
     lst = bus.supply.generator.get(slack + 1, [])
     if lst and gen.layout.status[lst[0] - 1] == 1:                      # dcAnalysis.jl:59-72
         gp[:, lst[0] - 1] = inj[:, slack] + bus.demand.active[slack] - sum(gen.output.active[j - 1] for j in lst[1:])
+    shed = _shed_mask(an)
+    if shed is not None:                                                # what a lane shed is not solved for: NaN on its buses and on their generators
+        inj[shed] = np.nan
+        sup[shed] = np.nan
+        gp[shed[:, gen.layout.bus - 1] & on[None, :]] = np.nan
     pw = an.power
     pw.injection, pw.supply, pw.generator = NS(active=an._shape(inj)), NS(active=an._shape(sup)), NS(active=an._shape(gp))
     pw.from_, pw.to = NS(active=an._shape(fr)), NS(active=an._shape(-fr))
@@ -224,13 +287,14 @@ def screenSummary_(an: DcPowerFlow, rating=None) -> np.ndarray:
     return rec
 
 
-def dcContingencyAnalysis(system: PowerSystem, labels, device: int = 0, rating=None) -> DcPowerFlow:
+def dcContingencyAnalysis(system: PowerSystem, labels, device: int = 0, rating=None, islands: str = "skip") -> DcPowerFlow:
     """Solved batched DC analysis, scenario s = outage of branch labels[s] (0 / None: base case; a tuple (k, l): both branches): analysis.voltage.angle [batch, n],
-    analysis.status [batch] (3: bridge), and analysis.screen [batch, 5] (screenSummary_) when `rating` is given."""
+    analysis.status [batch] (3: bridge), and analysis.screen [batch, 5] (screenSummary_) when `rating` is given.  islands="shed": setOutages_."""
     labels = list(labels)
     outagePairs(labels, system.branch.number)                           # refused on the host, before the device is touched
+    _island_mode(islands)
     an = dcPowerFlow(system, batch=len(labels), device=device)
-    setOutages_(an, labels)
+    setOutages_(an, labels, islands=islands)
     solve_(an)
     an.screen = screenSummary_(an, rating) if rating is not None else None
     return an

@@ -690,11 +690,13 @@ def setOutage_(an: AcPowerFlow, scenario: int, label: int | None):
     an._outage_labels[int(scenario)] = int(label)
 
 
-def setOutages_(an: AcPowerFlow, labels, scenario0: int = 0):
+def setOutages_(an: AcPowerFlow, labels, scenario0: int = 0, islands: str = "skip"):
     """setOutage_ for consecutive scenarios in ONE upload: scenario scenario0 + s = base grid with branch labels[s] out
-    of service (0 / None = base grid)."""
+    of service (0 / None = base grid).  islands: a DcPowerFlow only (dcpowerflow.setOutages_)."""
     if isinstance(an, _dc.DcPowerFlow):
-        return _dc.setOutages_(an, labels, scenario0)
+        return _dc.setOutages_(an, labels, scenario0, islands=islands)
+    if islands != "skip":
+        raise ValueError("setOutages_: islands belongs to a DcPowerFlow")
     lab = np.array([int(x) if x else 0 for x in labels], dtype=np.int64)
     labels = [int(x) for x in lab]
     tptr, tdy = outagePatchTable(an.system)
