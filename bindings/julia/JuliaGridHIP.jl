@@ -1374,6 +1374,54 @@ function pairTimeKernel(b::DcPowerFlowBatch, kernel::Int, k0::Int64, k1::Int64, 
 end
 "frees the sensitivities a pair screen keeps on the device"
 pairScreenRelease!(b::DcPowerFlowBatch) = check(ccall((:jg_dc_pair_release, lib), Cint, (Int64,), b.token))
+"""
+    seriesScreenBuild!(b, candidates, rhs; monitored = nothing, budget = 0) -> info [12]
+
+The DC N-1 screen over a series of injection profiles (jgrid.h: jg_dc_series_*): `rhs` is `[buses, T]`, one right-hand side per profile as
+`setInjections!` takes them (net injection - shunt conductance - shiftPower).  One sweep pair per candidate branch (indices, in service, ascending; one is
+allowed) and one per profile; `budget`: bytes the sensitivities and the profiles' base flows may take (0: 0.8 of the free device memory).
+"""
+function seriesScreenBuild!(b::DcPowerFlowBatch, candidates::Vector{Int64}, rhs::Matrix{Float64}; monitored::Union{Nothing, Vector{Int64}} = nothing, budget::Int64 = 0)
+    size(rhs, 1) == dims(b)[1] || throw(DimensionMismatch("[buses, profiles] right-hand sides"))
+    uploadRhs!(b)
+    info = zeros(Float64, 12)
+    if monitored === nothing
+        check(ccall((:jg_dc_series_build, lib), Cint, (Int64, Int64, Ptr{Int64}, Int64, Ptr{Int64}, Int64, Ptr{Float64}, Int64, Ptr{Float64}),
+            b.token, length(candidates), candidates, 0, C_NULL, size(rhs, 2), rhs, budget, info))
+    else
+        check(ccall((:jg_dc_series_build, lib), Cint, (Int64, Int64, Ptr{Int64}, Int64, Ptr{Int64}, Int64, Ptr{Float64}, Int64, Ptr{Float64}),
+            b.token, length(candidates), candidates, length(monitored), monitored, size(rhs, 2), rhs, budget, info))
+    end
+    return info
+end
+"""
+    seriesScreen(b, k0, k1, candidates, profiles; rating, threshold = 1.0, capacity = 2^20) -> (records [5, m], islanding, totals [5], worst, worstProfile, violatingProfile, base [3, T])
+
+All cases (k, t) of the candidate positions k0 .. k1 - 1 (0-based) and every profile: the records of the cases above `threshold` sorted by (k, t) (branch k,
+profile t (0-based), worst branch, worst |from| / rating, overloaded branches), the bridge candidates of the block, the totals (cases, violating, bridges,
+records kept, overflow flag), the worst loading per candidate and per profile, the violating candidates per profile and the profiles' base case.
+"""
+function seriesScreen(b::DcPowerFlowBatch, k0::Int64, k1::Int64, candidates::Vector{Int64}, profiles::Int64; rating::Vector{Float64}, threshold::Float64 = 1.0,
+                      capacity::Int64 = 2^20)
+    check(ccall((:jg_dc_set_rating, lib), Cint, (Int64, Ptr{Float64}), b.token, rating))
+    records = Matrix{Float64}(undef, 5, capacity)
+    islanding = zeros(Int64, max(k1 - k0, 1))
+    totals = zeros(Int64, 5)
+    worst = zeros(Float64, length(candidates))
+    worstProfile = zeros(Float64, profiles); violatingProfile = zeros(Int64, profiles); base = zeros(Float64, 3, profiles)
+    check(ccall((:jg_dc_series_screen, lib), Cint, (Int64, Int64, Int64, Float64, Int64, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64},
+                                                    Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}),
+        b.token, k0, k1, threshold, capacity, records, islanding, totals, worst, worstProfile, violatingProfile, base, C_NULL, C_NULL, C_NULL))
+    return records[:, 1:totals[4]], islanding[1:totals[3]], totals, worst, worstProfile, violatingProfile, base
+end
+"milliseconds of `reps` runs on candidate rows k0 .. k1 - 1 (HIP events): 0 the series screen kernel, 1 its row / column summaries"
+function seriesTimeKernel(b::DcPowerFlowBatch, kernel::Int, k0::Int64, k1::Int64, reps::Int = 20)
+    ms = zeros(Float64, reps)
+    check(ccall((:jg_dc_series_time_kernel, lib), Cint, (Int64, Cint, Int64, Int64, Cint, Ptr{Float64}), b.token, kernel, k0, k1, reps, ms))
+    return ms
+end
+"frees the sensitivities and base flows a series screen keeps on the device"
+seriesScreenRelease!(b::DcPowerFlowBatch) = check(ccall((:jg_dc_series_release, lib), Cint, (Int64,), b.token))
 
 # ---- DC state estimation with batched bad-data removal (jgrid.h: jg_dcse_*; csrc/jg_dcse.hip) ------------------------------------------------
 # dcStateEstimation / solve! / power! / residualTest! / chiTest (src/stateEstimation/dcStateEstimation.jl:42-151, 342-434, badData.jl:48-117, 963-977) for
@@ -1555,6 +1603,6 @@ export HIP, HIPOrthogonal, NewtonRaphsonBatch, BaseCase, baseInfo, baseInverseOn
        largestNormalizedResidual, normalizedResiduals, commUniqueId, Comm, shard, contingencyAnalysis, clearPlanCache,
        deviceCount, dims, setRefinement!, deviceMaps, setOutage!, snapshotVoltage!, restoreVoltage!, iterations, voltageDevice!, packResults!, packRows!,
        allgatherDevice, commRank, commWorld, timeKernel, setBusType!, busType, GaussNewtonBatch, setRealisations!, monteCarloEstimation, fastPatch!, setReadings!, drawNoise!, measurementDevice,
-       DcPowerFlowBatch, setInjections!, setOutagePairs!, pairScreenBuild!, pairScreen, pairTimeKernel, pairScreenRelease!, setIslandMode!, islands, islandTable, fromPower, angleDevice, DcStateEstimationBatch, removedRows, removeRows!
+       DcPowerFlowBatch, setInjections!, setOutagePairs!, pairScreenBuild!, pairScreen, pairTimeKernel, pairScreenRelease!, seriesScreenBuild!, seriesScreen, seriesTimeKernel, seriesScreenRelease!, setIslandMode!, islands, islandTable, fromPower, angleDevice, DcStateEstimationBatch, removedRows, removeRows!
 
 end # module

@@ -570,6 +570,42 @@ int jg_dc_pair_screen(int64_t h, int64_t k0, int64_t k1, double threshold, int64
                       double* dense_det);
 int jg_dc_pair_time_kernel(int64_t h, int kernel, int64_t k0, int64_t k1, int reps, double* ms);
 int jg_dc_pair_release(int64_t h);
+/*
+ * The DC N-1 screen over a SERIES of injection profiles (csrc/jg_dc_series.hpp): the user loop updateBus!(...; active) / updateGenerator!(...; active) per
+ * profile t around updateBranch!(k, status = 0), solve!, power!, updateBranch!(k, status = 1) per branch k.  No sweep per case: with Phi of
+ * jg_dc_pair_build and the profiles' base flows F0[m,t], f_m(k,t) = F0[m,t] + Phi[m,k] F0[k,t] / (1 - Phi[k,k]).  Needs jg_dc_set_branches and
+ * jg_dc_set_rhs; neither the lanes of the handle nor what jg_dc_pair_build keeps are touched.
+ *   jg_dc_series_build  candidates [nk] and monitored [nm] as jg_dc_pair_build takes them, but nk >= 1; rhs [profiles][n]: the right-hand sides as
+ *                       jg_dc_set_injections takes them (net injection - shunt conductance - shiftPower).  Phi by the build of jg_dc_pair_build, then
+ *                       one sweep pair per profile (512 at a time, scratch of the build's own) fills F0 [rows][profiles rounded up to 64] doubles.
+ *                       budget_bytes as jg_dc_pair_build, for Phi + F0 + the scratch of both: return code 5 with the sizes in the message and nothing
+ *                       allocated when they do not fit (a caller with more profiles than fit splits them: the result of a profile does not depend on
+ *                       the others).  info [12]: the eight of jg_dc_pair_build, bytes of F0, and the milliseconds of its build: total, sweep pairs,
+ *                       F0 kernel.  A second build replaces the first.
+ *   jg_dc_series_screen the cases (k, t) of the candidate POSITIONS k in [k0, k1) (0-based; the row block bounds the memory of a call, 16 bytes per
+ *                       case) x all profiles against the ratings of jg_dc_set_rating (not rated or not monitored: loading 0).
+ *                       records [capacity][5]: the cases whose worst loading exceeds threshold, sorted by (k, t): branch k (1-based), profile t
+ *                       (0-based), worst branch, worst |from| / rating, number of monitored branches above threshold; ties of the worst branch go to
+ *                       the lowest index.  islanding [k1 - k0] (nullable): the candidates of the block that are bridges (|1 - Phi[k,k]| < 1e-9:
+ *                       status 3 and a NaN loading in every profile; never in the records), 1-based.
+ *                       totals [5]: cases screened, violating, bridge candidates, records written, 1 when the record list overflowed -- the counts
+ *                       are exact also then, and the records kept are the FIRST by (k, t).
+ *                       worst [nk] (nullable): positions k0 .. k1 - 1 get the worst loading over the profiles (0 on a bridge).  worst_profile
+ *                       [profiles] (nullable, in/out): max-merged with the worst loading over the block's candidates (bridges aside);
+ *                       violating_profile [profiles] (nullable, in/out): the block's candidates whose outage violates are added.
+ *                       base [profiles][3] (nullable): the profiles' base case -- worst loading, its branch, branches above threshold.
+ *                       dense_* (each nullable) [k1 - k0][profiles]: worst loading (NaN: bridge), its branch, the count.
+ *   jg_dc_series_time_kernel   milliseconds of `reps` runs on rows [k0, k1) (a block jg_dc_series_screen has held): 0 the screen kernel, 1 the row /
+ *                       column summaries behind it
+ *   jg_dc_series_release  frees what the screen holds on the device
+ */
+int jg_dc_series_build(int64_t h, int64_t nk, const int64_t* candidates, int64_t nm, const int64_t* monitored, int64_t profiles, const double* rhs,
+                       int64_t budget_bytes, double* info12);
+int jg_dc_series_screen(int64_t h, int64_t k0, int64_t k1, double threshold, int64_t capacity, double* records, int64_t* islanding, int64_t* totals5,
+                        double* worst, double* worst_profile, int64_t* violating_profile, double* base, double* dense_load, int32_t* dense_branch,
+                        int32_t* dense_count);
+int jg_dc_series_time_kernel(int64_t h, int kernel, int64_t k0, int64_t k1, int reps, double* ms);
+int jg_dc_series_release(int64_t h);
 
 /* ---------------------------------------------------------------------------------------------
  * DC state estimation with batched bad-data removal (csrc/jg_dcse.hip)

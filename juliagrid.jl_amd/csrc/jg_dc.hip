@@ -4,6 +4,7 @@
 // are in jg_dc_sweep.hpp, shared with jg_dcse.hip; here: the rank-1 combine, the screen summary and the C ABI.
 #include "jg_dc.hpp"
 #include "jg_dc_pair.hpp"
+#include "jg_dc_series.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -301,6 +302,7 @@ void dc_destroy(DcHandle* h) {
     hipSetDevice(h->device);
     if (h->stream) hipStreamSynchronize(h->stream);
     dc_pair_free(h);
+    dc_series_free(h);
     for (void* p : h->allocs) hipFree(p);
     if (h->stream) hipStreamDestroy(h->stream);
     delete h;

@@ -49,6 +49,7 @@ struct DcSweepTables {             // one triangle of the factor, rows grouped b
 };
 
 struct DcPairState;
+struct DcSeriesState;
 
 struct DcHandle {
     int n = 0, nbr = 0, batch = 0, ld = 0, device = 0, slack = 0, n_entries = 0, n_fact_levels = 0;
@@ -79,6 +80,7 @@ struct DcHandle {
     double* Z2 = nullptr;                                                      // [n][ld] z of the second outage, for the groups of glist2
     int* glist2 = nullptr; std::vector<int> h_o2; int n_glist2 = 0;            // lane groups that hold a second outage
     DcPairState* pair = nullptr;                                               // the N-2 screen's kept sensitivities (jg_dc_pair.hpp)
+    DcSeriesState* series = nullptr;                                           // the N-1 screen over a series of injection profiles (jg_dc_series.hpp)
     // bridge outages solved on the slack's island (jg_dc_set_island_mode 1): allocated by the first such call, a handle without it holds none of it
     int island_mode = 0, n_isl = 0;                                            // n_isl: lanes whose ONE outage is a bridge, set while the mode was 1
     std::vector<int> h_pre, h_blo, h_bhi, h_bside;                             // dc_island_table of the handle's branch table

@@ -215,8 +215,8 @@ int pair_base_solve(DcHandle* h) {
     return 0;
 }
 
-void pair_release(DcHandle* h) {
-    DcPairState* p = h->pair;
+void state_release(DcHandle* h, DcPairState*& slot) {
+    DcPairState* p = slot;
     if (!p) return;
     hipStreamSynchronize(h->stream);
     dev_release(h, p->Phi); dev_release(h, p->row_branch); dev_release(h, p->row_pos); dev_release(h, p->row_mon); dev_release(h, p->row_f0);
@@ -225,8 +225,9 @@ void pair_release(DcHandle* h) {
     dev_release(h, p->r_viol); dev_release(h, p->r_isl); dev_release(h, p->r_max); dev_release(h, p->r_off); dev_release(h, p->r_ioff);
     dev_release(h, p->c_max); dev_release(h, p->rec); dev_release(h, p->isl);
     delete p;
-    h->pair = nullptr;
+    slot = nullptr;
 }
+void pair_release(DcHandle* h) { state_release(h, h->pair); }
 
 std::string bytes_text(size_t b) {
     char t[64];
@@ -234,8 +235,11 @@ std::string bytes_text(size_t b) {
     return t;
 }
 
-int pair_build(DcHandle* h, const std::vector<int>& cand, const std::vector<int>& mon, int64_t budget, double* info) {
-    pair_release(h);
+// the build of Phi into `slot` (the pair screen's h->pair, or the state the series screen keeps): `extra` bytes the caller will ask for beside Phi are
+// part of the memory question, `extra_text` names them in the refusal
+int state_build(DcHandle* h, DcPairState*& slot, const char* who, const std::vector<int>& cand, const std::vector<int>& mon, int64_t budget, size_t extra,
+                const std::string& extra_text, double* info) {
+    state_release(h, slot);
     if (h->base_dirty) DC_TRY(pair_base_solve(h));
     const int nk = (int)cand.size(), ldk = (nk + 63) / 64 * 64, n = h->n;
     std::vector<int> rows, pos, flag, crow(ldk, 0), clab(ldk, 0);
@@ -258,13 +262,13 @@ int pair_build(DcHandle* h, const std::vector<int>& cand, const std::vector<int>
     DC_HIP(hipMemGetInfo(&free_b, &total_b));
     const size_t allowed = budget > 0 ? (size_t)budget : (size_t)(DC_PAIR_BUDGET * (double)free_b);
     info[0] = nr; info[1] = ldk; info[2] = (double)phi_bytes; info[3] = (double)free_b; info[4] = (double)allowed; info[5] = info[6] = info[7] = 0.0;
-    if (phi_bytes + scratch > allowed || phi_bytes + scratch > free_b) {
-        h->error = "jg_dc_pair_build: Phi needs " + bytes_text(phi_bytes) + " (" + std::to_string(nr) + " rows x " + std::to_string(ldk) + " candidates x 8) and " +
-                   bytes_text(scratch) + " of scratch; the budget is " + bytes_text(allowed) + ", " + bytes_text(free_b) + " are free: fewer candidates or monitored branches, or a larger budget";
+    if (phi_bytes + scratch + extra > allowed || phi_bytes + scratch + extra > free_b) {
+        h->error = std::string(who) + ": Phi needs " + bytes_text(phi_bytes) + " (" + std::to_string(nr) + " rows x " + std::to_string(ldk) + " candidates x 8) and " +
+                   bytes_text(scratch) + " of scratch" + extra_text + "; the budget is " + bytes_text(allowed) + ", " + bytes_text(free_b) + " are free: fewer candidates or monitored branches, or a larger budget";
         return 5;
     }
     DcPairState* p = new DcPairState();
-    h->pair = p;
+    slot = p;
     p->nk = nk; p->ldk = ldk; p->rows = nr; p->h_cand = cand;
     DC_TRY(dev_alloc(h, &p->Phi, (size_t)nr * ldk, (const double*)nullptr, true));
     DC_TRY(dev_alloc(h, &p->row_branch, (size_t)nr, rows.data()));
@@ -323,7 +327,7 @@ int pair_build(DcHandle* h, const std::vector<int>& cand, const std::vector<int>
     }
     for (auto& e : ev) if (e) (void)hipEventDestroy(e);
     dev_release(h, of); dev_release(h, ot); dev_release(h, W); dev_release(h, Z);
-    if (rc) { const std::string msg = h->error; pair_release(h); h->error = msg; return rc; }
+    if (rc) { const std::string msg = h->error; state_release(h, slot); h->error = msg; return rc; }
     p->build_ms[0] = sweep_ms + phi_ms; p->build_ms[1] = sweep_ms; p->build_ms[2] = phi_ms;
     info[5] = p->build_ms[0]; info[6] = sweep_ms; info[7] = phi_ms;
     return 0;
@@ -407,7 +411,7 @@ int pair_screen(DcHandle* h, int k0, int k1, double thr, long long rec_cap, long
     DcPairState* p = h->pair;
     const int rb = k1 - k0, nk = p->nk, ldk = p->ldk;
     DC_TRY(pair_block(h, rb, o.d_det != nullptr, rec_cap, isl_cap));
-    hipLaunchKernelGGL(k_pair_rinv, dim3((p->rows + 255) / 256), dim3(256), 0, h->stream, h->b_rating, p->row_branch, p->row_mon, p->row_rinv, p->rows);
+    dc_pair_state_rinv(h, p);
     launch_screen(h, screen_args(h, k0, k1, thr, o.d_det != nullptr));
     PairListArgs la = list_args(h, k0, k1, thr, rec_cap, isl_cap);
     launch_stats(h, la);
@@ -449,6 +453,37 @@ int pair_screen(DcHandle* h, int k0, int k1, double thr, long long rec_cap, long
 }  // namespace
 
 void dc_pair_free(DcHandle* h) { pair_release(h); }
+void dc_pair_state_free(DcHandle* h, DcPairState*& slot) { state_release(h, slot); }
+int dc_pair_state_build(DcHandle* h, DcPairState*& slot, const char* who, const std::vector<int>& cand, const std::vector<int>& mon, int64_t budget,
+                        size_t extra, const std::string& extra_text, double* info) {
+    return state_build(h, slot, who, cand, mon, budget, extra, extra_text, info);
+}
+void dc_pair_state_rinv(DcHandle* h, DcPairState* p) {
+    hipLaunchKernelGGL(k_pair_rinv, dim3((p->rows + 255) / 256), dim3(256), 0, h->stream, h->b_rating, p->row_branch, p->row_mon, p->row_rinv, p->rows);
+}
+std::string dc_pair_bytes_text(size_t b) { return bytes_text(b); }
+
+int dc_pair_lists(DcHandle* d, const std::string& who, int64_t nk, const int64_t* candidates, int64_t nm, const int64_t* monitored, std::vector<int>& cand,
+                  std::vector<int>& mon) {
+    cand.assign(nk, 0); mon.clear();
+    for (int64_t j = 0; j < nk; ++j) {
+        const int64_t m = candidates[j] - 1;
+        if (m < 0 || m >= d->nbr) { d->error = who + ": candidate branch out of range"; return 1; }
+        if (j && m <= cand[j - 1]) { d->error = who + ": the candidates must ascend strictly (no branch twice)"; return 1; }
+        if (d->h_y[m] == 0.0) { d->error = who + ": candidate branch " + std::to_string(m + 1) + " is out of service"; return 1; }
+        cand[j] = (int)m;
+    }
+    if (monitored) {
+        for (int64_t j = 0; j < nm; ++j) {
+            const int64_t m = monitored[j] - 1;
+            if (m < 0 || m >= d->nbr) { d->error = who + ": monitored branch out of range"; return 1; }
+            mon.push_back((int)m);
+        }
+    } else {
+        for (int m = 0; m < d->nbr; ++m) if (d->h_y[m] != 0.0) mon.push_back(m);      // every branch in service
+    }
+    return 0;
+}
 
 }  // namespace jg
 
@@ -471,24 +506,9 @@ int jg_dc_pair_build(int64_t h, int64_t nk, const int64_t* candidates, int64_t n
     if (!d->nbr) return failp(1, "jg_dc_pair_build: jg_dc_set_branches first");
     if (d->h_rhs.empty()) return failp(1, "jg_dc_pair_build: jg_dc_set_rhs first");
     if (nk < 2 || !candidates || !info || nm < 0 || (nm && !monitored)) return failp(1, "jg_dc_pair_build: two or more candidates, and info, are needed");
-    std::vector<int> cand(nk), mon;
-    for (int64_t j = 0; j < nk; ++j) {
-        const int64_t m = candidates[j] - 1;
-        if (m < 0 || m >= d->nbr) return failp(1, "jg_dc_pair_build: candidate branch out of range");
-        if (j && m <= cand[j - 1]) return failp(1, "jg_dc_pair_build: the candidates must ascend strictly (no branch twice)");
-        if (d->h_y[m] == 0.0) return failp(1, "jg_dc_pair_build: candidate branch " + std::to_string(m + 1) + " is out of service");
-        cand[j] = (int)m;
-    }
-    if (monitored) {
-        for (int64_t j = 0; j < nm; ++j) {
-            const int64_t m = monitored[j] - 1;
-            if (m < 0 || m >= d->nbr) return failp(1, "jg_dc_pair_build: monitored branch out of range");
-            mon.push_back((int)m);
-        }
-    } else {
-        for (int m = 0; m < d->nbr; ++m) if (d->h_y[m] != 0.0) mon.push_back(m);      // every branch in service
-    }
-    PAIR_RET(jg::pair_build(d, cand, mon, budget_bytes, info));
+    std::vector<int> cand, mon;
+    PAIR_RET(jg::dc_pair_lists(d, "jg_dc_pair_build", nk, candidates, nm, monitored, cand, mon));
+    PAIR_RET(jg::dc_pair_state_build(d, d->pair, "jg_dc_pair_build", cand, mon, budget_bytes, 0, "", info));
     return 0;
 }
 

@@ -15,6 +15,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
+#include <string>
 #include <vector>
 
 namespace jg {
@@ -53,5 +55,18 @@ struct DcPairState {
 
 struct DcHandle;
 void dc_pair_free(DcHandle* h);              // releases what the pair screen holds, on the device and on the host (jg_dc_destroy, jg_dc_pair_release)
+
+// The build of Phi is shared with the series screen (jg_dc_series.hpp), which keeps a state of its own beside h->pair:
+//   dc_pair_lists        the candidate / monitored lists of a build call (1-based in, 0-based out) with the checks of jg_dc_pair_build; 1 and h->error
+//   dc_pair_state_build  replaces `slot` by a fresh build.  `extra` bytes the caller keeps beside Phi count in the memory question (code 5, nothing
+//                        allocated, `extra_text` names them in the message); info [8] as jg_dc_pair_build
+//   dc_pair_state_rinv   row_rinv from the handle's rating (a launch on the handle's stream)
+int dc_pair_lists(DcHandle* h, const std::string& who, int64_t nk, const int64_t* candidates, int64_t nm, const int64_t* monitored, std::vector<int>& cand,
+                  std::vector<int>& mon);
+int dc_pair_state_build(DcHandle* h, DcPairState*& slot, const char* who, const std::vector<int>& cand, const std::vector<int>& mon, int64_t budget,
+                        size_t extra, const std::string& extra_text, double* info);
+void dc_pair_state_free(DcHandle* h, DcPairState*& slot);
+void dc_pair_state_rinv(DcHandle* h, DcPairState* p);
+std::string dc_pair_bytes_text(size_t b);
 
 }  // namespace jg

@@ -7,6 +7,7 @@
                                                          a tuple (k, l) is a lane with two outages: a 2 x 2 correction; islands="shed": a bridge
                                                          outage is solved on the slack's island, which the reference cannot do)
   the same loop over ALL pairs of a candidate list          dcPairScreen (the DC N-2 screen: csrc/jg_dc_pair.hpp)
+  the N-1 loop inside a loop over injection profiles        dcSeriesScreen (csrc/jg_dc_series.hpp)
 
 All numerics run in libjgrid_hip.so (csrc/jg_dc.hip); the O(n) bus / generator bookkeeping of power! runs here.  A batched analysis keeps
 `batch` scenarios of ONE grid on the device; arrays are [batch, ...] (1-D for batch 1), as in the AC analysis.
@@ -324,7 +325,7 @@ def pairCandidates(system: PowerSystem) -> np.ndarray:
     return (np.flatnonzero((lay.status == 1) & ~bridges(system) & (lay.from_ != lay.to)) + 1).astype(np.int64)
 
 
-def _pair_lists(system: PowerSystem, candidates, monitored, rating):
+def _pair_lists(system: PowerSystem, candidates, monitored, rating, who: str = "dcPairScreen", least: int = 2):
     """candidate and monitored labels of a pair screen, checked on the host before anything touches the device"""
     nb, status = system.branch.number, system.branch.layout.status
     rating = np.ascontiguousarray(rating, dtype=np.float64)
@@ -332,20 +333,20 @@ def _pair_lists(system: PowerSystem, candidates, monitored, rating):
         raise ValueError("rating: one value per branch")
     cand = pairCandidates(system) if candidates is None else np.asarray(list(candidates), dtype=np.int64)
     if cand.size and (cand.min() < 1 or cand.max() > nb):
-        raise IndexError("dcPairScreen: candidate branch label out of range")
+        raise IndexError(f"{who}: candidate branch label out of range")
     if np.unique(cand).size != cand.size:
-        raise ValueError("dcPairScreen: a candidate is named twice (a pair needs two different branches)")
-    if cand.size < 2:
-        raise ValueError("dcPairScreen: two or more candidates are needed")
+        raise ValueError(f"{who}: a candidate is named twice" + (" (a pair needs two different branches)" if least == 2 else ""))
+    if cand.size < least:
+        raise ValueError(f"{who}: two or more candidates are needed" if least == 2 else f"{who}: one or more candidates are needed")
     off = cand[status[cand - 1] != 1]
     if off.size:
-        raise ValueError(f"dcPairScreen: candidate branch {int(off[0])} is out of service")
+        raise ValueError(f"{who}: candidate branch {int(off[0])} is out of service")
     if monitored is None:
         mon = (np.flatnonzero((status == 1) & (rating > 0)) + 1).astype(np.int64)
     else:
         mon = np.unique(np.asarray(list(monitored), dtype=np.int64))
         if mon.size and (mon.min() < 1 or mon.max() > nb):
-            raise IndexError("dcPairScreen: monitored branch label out of range")
+            raise IndexError(f"{who}: monitored branch label out of range")
     return np.sort(cand), mon, rating
 
 
@@ -421,3 +422,100 @@ def dcPairScreen(analysis_or_system, candidates=None, monitored=None, rating=Non
             an.close()
         else:
             _lib.check(L.jg_dc_pair_release(an._h))
+
+
+class DcSeriesScreen:
+    """What dcSeriesScreen returns.
+      candidates  [K] branch labels (1-based, ascending); monitored the labels of the call; profiles = T; threshold; rows = (k0, k1)
+      records     [r, 5] the cases (k, t) whose worst loading exceeds the threshold, sorted by (k, t): label k, profile index t (0-based row of
+                  `injections`), worst branch label, worst |from| / rating, number of monitored branches above the threshold
+      overflow    the record list was cut at its capacity: it holds the FIRST entries by (k, t)
+      islanding   labels of the screened candidates that are bridges (status 3): NaN loading in every profile, never in `records`
+      totals      dict(cases = rows screened x T, violating, islanding = bridge candidates): exact also when the list overflowed
+      worst       [K] the worst loading over all profiles of each screened candidate (0 on a bridge and outside `rows`)
+      worstProfile / violatingProfile   [T] per profile over the screened candidates: the worst loading (bridges aside) and the number of candidates
+                  whose outage violates (int64)
+      base        [T, 3] the base case of every profile, no outage: worst loading, its branch label, number of branches above the threshold
+      loading, branch, count   with dense=True: [k1 - k0, T]
+      info        dict(rows, ld, phiBytes, freeBytes, budgetBytes, buildMs, sweepMs, phiMs, f0Bytes, f0BuildMs, f0SweepMs, f0KernelMs)"""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+SERIES_BLOCK_BYTES = 256 << 20                                         # default bound of the dense result of one device call (16 bytes per case)
+
+
+def dcSeriesScreen(analysis_or_system, injections, candidates=None, monitored=None, rating=None, threshold: float = 1.0, rows=None,
+                   capacity: int = 1 << 20, dense: bool = False, block=None, budget=None, device: int = 0) -> DcSeriesScreen:
+    """The DC N-1 screen at every one of a series of injection profiles: branch k of `candidates` (labels; default pairCandidates(system); one is
+    allowed) out of service under profile t of `injections` ([T, buses] net active injection per bus, supply - demand, the meaning of setInjection_;
+    shunts and phase shifters stay the system's), the worst |from| / rating over `monitored` per case -- the loop updateBus! / updateGenerator! per
+    profile around updateBranch!(k, status = 0), solve!, power! per branch, from ONE factor, one sweep pair per candidate and one per profile
+    (csrc/jg_dc_series.hpp).  `monitored`, `rating`, `rows`, `block`, `budget` and `capacity` mean what they mean for dcPairScreen; the budget covers
+    the sensitivities and the profiles' base flows, and a caller with more profiles than fit splits them (a profile's results do not depend on the others)."""
+    own = isinstance(analysis_or_system, PowerSystem)
+    system = analysis_or_system if own else analysis_or_system.system
+    if rating is None:
+        raise ValueError("dcSeriesScreen: rating (per branch, per unit of active power) is needed")
+    if not threshold >= 0:
+        raise ValueError("dcSeriesScreen: threshold >= 0")
+    inj = np.asarray(injections, dtype=np.float64)
+    if inj.ndim != 2 or inj.shape[0] < 1 or inj.shape[1] != system.bus.number:
+        raise ValueError("dcSeriesScreen: injections must be [T, buses] with T >= 1")
+    if not np.isfinite(inj).all():
+        raise ValueError("dcSeriesScreen: injections must be finite")
+    if own and system.model.dc.nodalMatrix is None:
+        dcModel_(system)
+    cand, mon, rating = _pair_lists(system, candidates, monitored, rating, who="dcSeriesScreen", least=1)
+    nk, T = int(cand.size), int(inj.shape[0])
+    k0, k1 = (0, nk) if rows is None else (int(rows[0]), min(int(rows[1]), nk))
+    if k0 < 0 or k1 < k0:
+        raise ValueError("dcSeriesScreen: rows = (k0, k1) with 0 <= k0 <= k1 <= candidates")
+    ldt = (T + 63) // 64 * 64
+    step = max(1, SERIES_BLOCK_BYTES // (ldt * 16)) if block is None else int(block)
+    if step < 1:
+        raise ValueError("dcSeriesScreen: block >= 1")
+    an = dcPowerFlow(system, device=device) if own else analysis_or_system
+    L = _lib.lib()
+    try:
+        if an._rhs is None:
+            an._rhs = np.ascontiguousarray(_base_rhs(system), dtype=np.float64)
+            _lib.check(L.jg_dc_set_rhs(an._h, an._rhs))
+        _set_rating(an, rating)
+        rhs = np.ascontiguousarray(inj - system.bus.shunt.conductance[None, :] - system.model.dc.shiftPower[None, :])
+        info = np.zeros(12)
+        _lib.check(L.jg_dc_series_build(an._h, nk, cand, int(mon.size), mon.ctypes.data_as(_lib.VP), T, rhs.reshape(-1), int(budget or 0), info))
+        del rhs
+        ptr = lambda a: None if a is None else a.ctypes.data_as(_lib.VP)
+        rec = np.zeros((max(int(capacity), 0), 5))
+        worst, worstProfile, violatingProfile, base = np.zeros(nk), np.zeros(T), np.zeros(T, dtype=np.int64), np.zeros((T, 3))
+        tot = np.zeros(3, dtype=np.int64)
+        nrec, bridges = 0, []
+        full = {name: np.zeros((k1 - k0, T), dtype=dt) for name, dt in (("loading", np.float64), ("branch", np.int32), ("count", np.int32))} if dense else {}
+        for b0 in range(k0, k1, step):
+            b1 = min(b0 + step, k1)
+            t5 = np.zeros(5, dtype=np.int64)
+            isl = np.zeros(b1 - b0, dtype=np.int64)
+            part = {name: a[b0 - k0:b1 - k0] for name, a in full.items()}                     # (row slices of a C-contiguous array are contiguous)
+            r = rec[nrec:]
+            _lib.check(L.jg_dc_series_screen(an._h, b0, b1, float(threshold), r.shape[0], ptr(r) if r.shape[0] else None, ptr(isl), t5, ptr(worst),
+                                             ptr(worstProfile), ptr(violatingProfile), ptr(base) if b0 == k0 else None,
+                                             ptr(part.get("loading")), ptr(part.get("branch")), ptr(part.get("count"))))
+            tot += t5[:3]
+            nrec += int(t5[3])
+            bridges.append(isl[:int(t5[2])])
+        res = DcSeriesScreen(candidates=cand, monitored=mon, profiles=T, threshold=float(threshold), rows=(k0, k1), records=rec[:nrec].copy(),
+                             overflow=bool(tot[1] > nrec), islanding=np.concatenate(bridges) if bridges else np.zeros(0, dtype=np.int64),
+                             totals=dict(cases=int(tot[0]), violating=int(tot[1]), islanding=int(tot[2])), worst=worst, worstProfile=worstProfile,
+                             violatingProfile=violatingProfile, base=base,
+                             info=dict(zip(("rows", "ld", "phiBytes", "freeBytes", "budgetBytes", "buildMs", "sweepMs", "phiMs", "f0Bytes", "f0BuildMs",
+                                            "f0SweepMs", "f0KernelMs"), (float(x) for x in info))))
+        for name, a in full.items():
+            setattr(res, name, a)
+        return res
+    finally:
+        if own:
+            an.close()
+        else:
+            _lib.check(L.jg_dc_series_release(an._h))
