@@ -1,8 +1,9 @@
 // jg_dc.hip -- DC power flow and the batched DC N-1 screen on one shared scalar factor (jg_dc.hpp has the algebra and the reference lines it stands for).
 //
 // The scalar factorisation of the ONE base matrix (once per base case), the level-scheduled sweeps with scenarios as lanes and the branch-flow kernel
-// are in jg_dc_sweep.hpp, shared with jg_dcse.hip; here: the rank-1 combine, the screen summary and the C ABI.
+// are jg_dc_sweep.hip's (declared in jg_dc_sweep.hpp), shared with jg_dcse.hip; here: the rank-1 combine, the screen summary and the C ABI.
 #include "jg_dc.hpp"
+#include "jg_dc_abi.hpp"
 #include "jg_dc_pair.hpp"
 #include "jg_dc_series.hpp"
 
@@ -17,9 +18,6 @@
 namespace jg {
 
 namespace {
-
-#include "jg_dc_sweep.hpp"
-
 
 // ---- the rank-1 combine ------------------------------------------------------------------------------------------------------------------
 struct DcCombineArgs {
@@ -165,12 +163,8 @@ __global__ void k_dc_fill_rhs(const double* rhs0, double* RHS, int n, int ld) {
     if (i < (size_t)n * ld) RHS[i] = rhs0[(i / ld) * 64];
 }
 
-
-// x = B^-1 r for `groups` lane groups: MODE_F 0 (r = rhs) or 1 (r = e_from - e_to of the lanes' outages)
-template <int MODE_F>
-void sweep_pair(DcHandle* h, const double* rhs, double* W, double* out, int ld, int groups, const int* glist) {
-    sweep_pair_on<MODE_F>(h, rhs, h->o_from, h->o_to, W, out, ld, groups, glist);
-}
+// z = B^-1 (e_from - e_to) of every lane's outage
+void sweep_outages(DcHandle* h) { sweep_pair(h->fac, h->stream, 1, nullptr, h->o_from, h->o_to, h->W, h->Z, h->ld, h->ld / 64, nullptr); }
 
 void launch_combine(DcHandle* h) {
     DcCombineArgs c{};
@@ -198,30 +192,18 @@ int launch_flows(DcHandle* h, bool store) {
     DcFlowArgs f{};
     f.TH = h->TH; f.bf = h->b_from; f.bt = h->b_to; f.by = h->b_y; f.bs = h->b_shift; f.rating = h->b_rating; f.obr = h->o_br; f.obr2 = h->o2_br;
     f.flows = store ? h->flows : nullptr; f.part = h->part; f.nbr = h->nbr; f.ld = h->ld;
-    if (h->n_isl) {
-        f.preorder = h->preorder; f.isl = (const I4*)h->isl;
-        hipLaunchKernelGGL(k_dc_flows<true>, dim3((h->n_chunks + 3) / 4, h->ld / 64), dim3(64, 4), 0, h->stream, f);
-    } else
-        hipLaunchKernelGGL(k_dc_flows<false>, dim3((h->n_chunks + 3) / 4, h->ld / 64), dim3(64, 4), 0, h->stream, f);
+    if (h->n_isl) { f.preorder = h->preorder; f.isl = (const I4*)h->isl; }
+    launch_dc_flows(f, h->n_isl != 0, dim3((h->n_chunks + 3) / 4, h->ld / 64), h->stream);
     hipLaunchKernelGGL(k_dc_screen_final, dim3(h->ld / 64), dim3(64), 0, h->stream, h->part, h->status, h->screen, h->n_chunks, h->ld, h->batch);
     DC_HIP(hipGetLastError());
     return 0;
 }
 
-int base_solve(DcHandle* h) {
-    if (h->h_rhs.empty()) { h->error = "jg_dc_set_rhs has not been called"; return 1; }
-    DC_HIP(hipMemcpy2DAsync(h->rhs0, 64 * sizeof(double), h->h_rhs.data(), sizeof(double), sizeof(double), (size_t)h->n, hipMemcpyHostToDevice, h->stream));
-    sweep_pair<0>(h, h->rhs0, h->W0, h->th0, 64, 1, nullptr);
-    DC_HIP(hipGetLastError());
-    h->base_dirty = false;
-    return 0;
-}
-
 // the launch chain of a batch: sweeps for z, (sweeps for the groups with injections of their own,) combine.  One straight line on the handle's stream.
 int solve_chain(DcHandle* h) {
-    sweep_pair<1>(h, nullptr, h->W, h->Z, h->ld, h->ld / 64, nullptr);
-    if (h->n_glist) sweep_pair<0>(h, h->RHS, h->W, h->XS, h->ld, h->n_glist, h->glist);
-    if (h->n_glist2) sweep_pair_on<1>(h, (const double*)nullptr, h->o2_from, h->o2_to, h->W, h->Z2, h->ld, h->n_glist2, h->glist2);   // a second sweep pair, for the groups with a second outage only
+    sweep_outages(h);
+    if (h->n_glist) sweep_pair(h->fac, h->stream, 0, h->RHS, nullptr, nullptr, h->W, h->XS, h->ld, h->n_glist, h->glist);
+    if (h->n_glist2) sweep_pair(h->fac, h->stream, 1, nullptr, h->o2_from, h->o2_to, h->W, h->Z2, h->ld, h->n_glist2, h->glist2);   // a second sweep pair, for the groups with a second outage only
     launch_combine(h);
     DC_HIP(hipGetLastError());
     return 0;
@@ -254,26 +236,23 @@ int dc_create(DcHandle* h, int64_t n64, const int64_t* colptr, const int64_t* ro
             A[q] = v;
         }
     BlockSymbolic S;
-    // policy bits 8-15 = 255: no pivot goes to a top task (jg_symbolic.hpp), every pivot is a level item.  The JG_TOP_LEVEL test knob can override that
-    // byte; the top tasks it would add are further replay tables -- the generic lists read here (t_ptr / t_a / t_d / t_b, e_level, l_* / u_*, bwd_level)
-    // are complete before build_top runs and neither it nor build_tables changes them, so the DC factor is the same with the knob set.
-    constexpr long long DC_POLICY_NO_TOP = (long long)255 << 8;
     if (analyze(n, rp.data(), ci.data(), DC_POLICY_NO_TOP, S) != 0) { h->error = "symbolic analysis failed (pattern must contain the diagonal)"; return 1; }
     DC_HIP(hipSetDevice(device));
     DC_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    DC_TRY(factor_tables(h, S));
-    DC_TRY(dev_alloc(h, &h->A, (size_t)nnz, A.data()));
-    DC_TRY(dev_alloc(h, &h->X, (size_t)S.n_entries + 1, (const double*)nullptr, true));
-    DC_TRY(dev_alloc(h, &h->dinv, (size_t)n, (const double*)nullptr, true));
-    DC_TRY(dev_alloc(h, &h->bad, (size_t)1, (const int*)nullptr, true));
-    factor_numeric(h);                                                      // once
+    DcFactor& F = h->fac;
+    DC_TRY(factor_tables(h, F, n, S));
+    DC_TRY(dev_alloc(h, &F.A, (size_t)nnz, A.data()));                       // slack row / column as identity
+    DC_TRY(dev_alloc(h, &F.X, (size_t)S.n_entries + 1, (const double*)nullptr, true));
+    DC_TRY(dev_alloc(h, &F.dinv, (size_t)n, (const double*)nullptr, true));
+    DC_TRY(dev_alloc(h, &F.bad, (size_t)1, (const int*)nullptr, true));
+    factor_numeric(F, h->stream);                                           // once
     DC_HIP(hipGetLastError());
-    DC_TRY(build_sweep(h, h->fwd, forward_levels(n, S), S.l_ptr, S.l_ent, S.l_col, false));
-    DC_TRY(build_sweep(h, h->bwd, S.bwd_level, S.u_ptr, S.u_ent, S.u_col, true));
+    DC_TRY(build_sweep(h, F, F.fwd, forward_levels(n, S), S.l_ptr, S.l_ent, S.l_col, false));
+    DC_TRY(build_sweep(h, F, F.bwd, S.bwd_level, S.u_ptr, S.u_ent, S.u_col, true));
     int bad = 0;
-    DC_HIP(sync_copy(&bad, h->bad, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    dev_release(h, h->f_ent); dev_release(h, h->t_ptr); dev_release(h, h->t_a); dev_release(h, h->t_d); dev_release(h, h->t_b);
-    dev_release(h, h->e_src); dev_release(h, h->diag); dev_release(h, h->A); dev_release(h, h->X); dev_release(h, h->bad);
+    DC_HIP(sync_copy(&bad, F.bad, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    dev_release(h, F.f_ent); dev_release(h, F.t_ptr); dev_release(h, F.t_a); dev_release(h, F.t_d); dev_release(h, F.t_b);
+    dev_release(h, F.e_src); dev_release(h, F.diag); dev_release(h, F.A); dev_release(h, F.X); dev_release(h, F.bad);
     if (bad) { h->error = "zero or non-finite pivot in the DC nodal matrix (an island without the slack bus?)"; return 3; }
     const size_t ld = (size_t)h->ld;
     DC_TRY(dev_alloc(h, &h->rhs0, (size_t)n * 64, (const double*)nullptr, true));
@@ -309,49 +288,50 @@ void dc_destroy(DcHandle* h) {
 }
 
 }  // namespace
+
+int dc_base_solve(DcHandle* h) {
+    if (h->h_rhs.empty()) { h->error = "jg_dc_set_rhs has not been called"; return 1; }
+    DC_HIP(hipMemcpy2DAsync(h->rhs0, 64 * sizeof(double), h->h_rhs.data(), sizeof(double), sizeof(double), (size_t)h->n, hipMemcpyHostToDevice, h->stream));
+    sweep_pair(h->fac, h->stream, 0, h->rhs0, nullptr, nullptr, h->W0, h->th0, 64, 1, nullptr);
+    DC_HIP(hipGetLastError());
+    h->base_dirty = false;
+    return 0;
+}
+
 }  // namespace jg
 
 using jg::DcHandle;
 
-namespace {
-int faild(int code, const std::string& msg) { jg::set_last_error(msg); return code; }
-DcHandle* H(int64_t h) { return reinterpret_cast<DcHandle*>(static_cast<intptr_t>(h)); }
-#define DC_ENTER(h)                                                                     \
-    DcHandle* d = H(h);                                                                 \
-    if (!d) return faild(1, "null DC handle");                                          \
-    if (hipSetDevice(d->device) != hipSuccess) return faild(2, "hipSetDevice failed")
-#define DC_RET(expr) do { const int rc__ = (expr); if (rc__) return faild(rc__, d->error); } while (0)
-#define DC_API_HIP(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) return faild(2, std::string(#expr) + ": " + hipGetErrorString(e__)); } while (0)
-}  // namespace
+using jg::api_fail;
 
 extern "C" {
 
 int jg_dc_create(int64_t* out, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* nzval, int64_t slack, double slack_angle,
                  int64_t batch, int device) {
-    if (!out || !colptr || !rowval || !nzval || n < 1 || n > (1 << 24) || slack < 1 || slack > n || batch < 1 || batch > (1 << 20)) return faild(1, "jg_dc_create: bad argument");
+    if (!out || !colptr || !rowval || !nzval || n < 1 || n > (1 << 24) || slack < 1 || slack > n || batch < 1 || batch > (1 << 20)) return api_fail(1, "jg_dc_create: bad argument");
     DcHandle* h = new DcHandle();
     const int rc = jg::dc_create(h, n, colptr, rowval, nzval, slack, slack_angle, batch, device);
-    if (rc) { const std::string msg = h->error; jg::dc_destroy(h); *out = 0; return faild(rc, msg); }
+    if (rc) { const std::string msg = h->error; jg::dc_destroy(h); *out = 0; return api_fail(rc, msg); }
     *out = (int64_t)reinterpret_cast<intptr_t>(h);
     return 0;
 }
 
 void jg_dc_destroy(int64_t h) {
-    if (H(h)) jg::dc_destroy(H(h));
+    if (h) jg::dc_destroy(reinterpret_cast<DcHandle*>(static_cast<intptr_t>(h)));
 }
 
 int jg_dc_dims(int64_t h, int64_t* dims) {
     DC_ENTER(h);
-    if (!dims) return faild(1, "jg_dc_dims: null pointer");
-    dims[0] = d->n; dims[1] = d->batch; dims[2] = d->ld; dims[3] = d->nbr; dims[4] = d->n_entries; dims[5] = d->n_fact_levels;
-    dims[6] = (int64_t)d->fwd.h_lev.size() - 1; dims[7] = (int64_t)d->bwd.h_lev.size() - 1;
-    dims[8] = (int64_t)(d->fwd.launches.size() + d->bwd.launches.size()); dims[9] = d->fwd.terms + d->bwd.terms;
+    if (!dims) return api_fail(1, "jg_dc_dims: null pointer");
+    dims[0] = d->n; dims[1] = d->batch; dims[2] = d->ld; dims[3] = d->nbr; dims[4] = d->fac.n_entries; dims[5] = d->fac.n_fact_levels;
+    dims[6] = (int64_t)d->fac.fwd.h_lev.size() - 1; dims[7] = (int64_t)d->fac.bwd.h_lev.size() - 1;
+    dims[8] = (int64_t)(d->fac.fwd.launches.size() + d->fac.bwd.launches.size()); dims[9] = d->fac.fwd.terms + d->fac.bwd.terms;
     return 0;
 }
 
 int jg_dc_set_rhs(int64_t h, const double* rhs) {
     DC_ENTER(h);
-    if (!rhs) return faild(1, "jg_dc_set_rhs: null pointer");
+    if (!rhs) return api_fail(1, "jg_dc_set_rhs: null pointer");
     d->h_rhs.assign(rhs, rhs + d->n);
     d->h_rhs[d->slack] = 0.0;
     d->base_dirty = true; d->solved = false;
@@ -361,8 +341,8 @@ int jg_dc_set_rhs(int64_t h, const double* rhs) {
 
 int jg_dc_set_injections(int64_t h, int64_t lane0, int64_t count, const double* rhs) {
     DC_ENTER(h);
-    if (lane0 < 0 || count < 0 || lane0 + count > d->batch || (count && !rhs)) return faild(1, "jg_dc_set_injections: lanes out of range");
-    if (d->h_rhs.empty()) return faild(1, "jg_dc_set_injections: jg_dc_set_rhs first");
+    if (lane0 < 0 || count < 0 || lane0 + count > d->batch || (count && !rhs)) return api_fail(1, "jg_dc_set_injections: lanes out of range");
+    if (d->h_rhs.empty()) return api_fail(1, "jg_dc_set_injections: jg_dc_set_rhs first");
     if (!count) return 0;
     const size_t n = (size_t)d->n, ld = (size_t)d->ld;
     if (!d->RHS) {
@@ -372,7 +352,7 @@ int jg_dc_set_injections(int64_t h, int64_t lane0, int64_t count, const double* 
     bool any = false;
     for (int g : d->h_ginj) any = any || g;
     if (!any) {                                                            // every lane starts from the base right-hand side
-        if (d->base_dirty) DC_RET(jg::base_solve(d));
+        if (d->base_dirty) DC_RET(jg::dc_base_solve(d));
         hipLaunchKernelGGL(jg::k_dc_fill_rhs, dim3((unsigned)((n * ld + 255) / 256)), dim3(256), 0, d->stream, d->rhs0, d->RHS, d->n, d->ld);
     }
     std::vector<double> t(n * (size_t)count);
@@ -392,11 +372,11 @@ int jg_dc_set_injections(int64_t h, int64_t lane0, int64_t count, const double* 
 
 int jg_dc_set_branches(int64_t h, int64_t nbr, const int64_t* from, const int64_t* to, const double* admittance, const double* shift) {
     DC_ENTER(h);
-    if (nbr < 1 || !from || !to || !admittance || !shift) return faild(1, "jg_dc_set_branches: bad argument");
-    if (d->nbr) return faild(1, "jg_dc_set_branches: the branch table is already set");
+    if (nbr < 1 || !from || !to || !admittance || !shift) return api_fail(1, "jg_dc_set_branches: bad argument");
+    if (d->nbr) return api_fail(1, "jg_dc_set_branches: the branch table is already set");
     std::vector<int> f(nbr), t(nbr);
     for (int64_t k = 0; k < nbr; ++k) {
-        if (from[k] < 1 || from[k] > d->n || to[k] < 1 || to[k] > d->n) return faild(1, "jg_dc_set_branches: bus index out of range");
+        if (from[k] < 1 || from[k] > d->n || to[k] < 1 || to[k] > d->n) return api_fail(1, "jg_dc_set_branches: bus index out of range");
         f[k] = (int)from[k] - 1; t[k] = (int)to[k] - 1;
     }
     d->h_from = f; d->h_to = t; d->h_y.assign(admittance, admittance + nbr); d->h_shift.assign(shift, shift + nbr);
@@ -412,7 +392,7 @@ int jg_dc_set_branches(int64_t h, int64_t nbr, const int64_t* from, const int64_
 
 int jg_dc_set_rating(int64_t h, const double* rating) {
     DC_ENTER(h);
-    if (!d->nbr) return faild(1, "jg_dc_set_rating: jg_dc_set_branches first");
+    if (!d->nbr) return api_fail(1, "jg_dc_set_rating: jg_dc_set_branches first");
     if (!rating) { d->b_rating = nullptr; return 0; }                     // (the buffer stays with the handle)
     if (!d->rating_buf) DC_RET(jg::dev_alloc(d, &d->rating_buf, (size_t)d->nbr, (const double*)nullptr, true));
     DC_API_HIP(jg::sync_copy(d->rating_buf, rating, (size_t)d->nbr * sizeof(double), hipMemcpyHostToDevice, d->stream));
@@ -423,8 +403,8 @@ int jg_dc_set_rating(int64_t h, const double* rating) {
 // lanes lane0 .. : outage of branch[s] and, where branch2 is given and not 0, of branch2[s] as well
 static int dc_set_lane_outages(DcHandle* d, const char* who, int64_t lane0, int64_t count, const int64_t* branch, const int64_t* branch2) {
     const std::string me = who;
-    if (lane0 < 0 || count < 0 || lane0 + count > d->batch || (count && !branch)) return faild(1, me + ": lanes out of range");
-    if (!d->nbr) return faild(1, me + ": jg_dc_set_branches first");
+    if (lane0 < 0 || count < 0 || lane0 + count > d->batch || (count && !branch)) return api_fail(1, me + ": lanes out of range");
+    if (!d->nbr) return api_fail(1, me + ": jg_dc_set_branches first");
     if (!count) return 0;
     std::vector<int> of(count), ot(count), ob(count), of2(count, -1), ot2(count, -1), ob2(count, -1);
     std::vector<double> oy(count), os(count), oy2(count, 0.0), os2(count, 0.0);
@@ -433,8 +413,8 @@ static int dc_set_lane_outages(DcHandle* d, const char* who, int64_t lane0, int6
     bool second = false;
     for (int64_t s = 0; s < count; ++s) {
         int64_t k = branch[s] - 1, k2 = branch2 ? branch2[s] - 1 : -1;
-        if (k < -1 || k >= d->nbr || k2 < -1 || k2 >= d->nbr) return faild(1, me + ": branch index out of range");
-        if (k >= 0 && k == k2) return faild(1, me + ": the two outages of a lane must be different branches");
+        if (k < -1 || k >= d->nbr || k2 < -1 || k2 >= d->nbr) return api_fail(1, me + ": branch index out of range");
+        if (k >= 0 && k == k2) return api_fail(1, me + ": the two outages of a lane must be different branches");
         if (k < 0) { k = k2; k2 = -1; }
         if (k < 0) { of[s] = ot[s] = ob[s] = -1; oy[s] = os[s] = 0.0; continue; }
         of[s] = d->h_from[k] == d->slack ? -1 : d->h_from[k];           // the slack's component of a = e_from - e_to is dropped
@@ -496,8 +476,8 @@ static int dc_set_lane_outages(DcHandle* d, const char* who, int64_t lane0, int6
 
 int jg_dc_set_island_mode(int64_t h, int mode) {
     DC_ENTER(h);
-    if (mode != 0 && mode != 1) return faild(1, "jg_dc_set_island_mode: mode is 0 (a bridge outage is skipped: status 3) or 1 (solved on the slack's island: status 4)");
-    if (mode == 1 && !d->nbr) return faild(1, "jg_dc_set_island_mode: jg_dc_set_branches first");
+    if (mode != 0 && mode != 1) return api_fail(1, "jg_dc_set_island_mode: mode is 0 (a bridge outage is skipped: status 3) or 1 (solved on the slack's island: status 4)");
+    if (mode == 1 && !d->nbr) return api_fail(1, "jg_dc_set_island_mode: jg_dc_set_branches first");
     if (mode == 1 && !d->isl) {                                          // the table of the handle's grid and the lanes' records, once
         const size_t n = (size_t)d->n, nb = (size_t)d->nbr, ld = (size_t)d->ld;
         d->h_pre.resize(n); d->h_blo.resize(nb); d->h_bhi.resize(nb); d->h_bside.resize(nb);
@@ -517,8 +497,8 @@ int jg_dc_set_island_mode(int64_t h, int mode) {
 
 int jg_dc_get_islands(int64_t h, double* rec) {
     DC_ENTER(h);
-    if (!d->solved) return faild(4, "jg_dc_get_islands: jg_dc_solve first");
-    if (!rec) return faild(1, "jg_dc_get_islands: null pointer");
+    if (!d->solved) return api_fail(4, "jg_dc_get_islands: jg_dc_solve first");
+    if (!rec) return api_fail(1, "jg_dc_get_islands: null pointer");
     std::fill(rec, rec + (size_t)d->batch * 4, 0.0);
     if (!d->n_isl) return 0;
     const size_t ld = (size_t)d->ld;
@@ -539,13 +519,13 @@ int jg_dc_set_outages(int64_t h, int64_t lane0, int64_t count, const int64_t* br
 
 int jg_dc_set_outage_pairs(int64_t h, int64_t lane0, int64_t count, const int64_t* branch_a, const int64_t* branch_b) {
     DC_ENTER(h);
-    if (count && !branch_b) return faild(1, "jg_dc_set_outage_pairs: null pointer");
+    if (count && !branch_b) return api_fail(1, "jg_dc_set_outage_pairs: null pointer");
     return dc_set_lane_outages(d, "jg_dc_set_outage_pairs", lane0, count, branch_a, branch_b);
 }
 
 int jg_dc_solve(int64_t h) {
     DC_ENTER(h);
-    if (d->base_dirty) DC_RET(jg::base_solve(d));
+    if (d->base_dirty) DC_RET(jg::dc_base_solve(d));
     DC_RET(jg::solve_chain(d));
     DC_API_HIP(hipStreamSynchronize(d->stream));
     d->solved = true;
@@ -554,7 +534,7 @@ int jg_dc_solve(int64_t h) {
 
 int jg_dc_get_angle(int64_t h, double* theta, int32_t* status) {
     DC_ENTER(h);
-    if (!d->solved) return faild(4, "jg_dc_get_angle: jg_dc_solve first");
+    if (!d->solved) return api_fail(4, "jg_dc_get_angle: jg_dc_solve first");
     const size_t n = (size_t)d->n, ld = (size_t)d->ld;
     if (theta) {
         std::vector<double> t(n * ld);
@@ -568,15 +548,15 @@ int jg_dc_get_angle(int64_t h, double* theta, int32_t* status) {
 
 int jg_dc_angle_device(int64_t h, int64_t* info) {
     DC_ENTER(h);
-    if (!info) return faild(1, "jg_dc_angle_device: null pointer");
+    if (!info) return api_fail(1, "jg_dc_angle_device: null pointer");
     info[0] = (int64_t)reinterpret_cast<intptr_t>(d->TH); info[1] = d->ld; info[2] = (int64_t)reinterpret_cast<intptr_t>(d->status);
     return 0;
 }
 
 int jg_dc_get_flows(int64_t h, double* from) {
     DC_ENTER(h);
-    if (!d->solved) return faild(4, "jg_dc_get_flows: jg_dc_solve first");
-    if (!from) return faild(1, "jg_dc_get_flows: null pointer");
+    if (!d->solved) return api_fail(4, "jg_dc_get_flows: jg_dc_solve first");
+    if (!from) return api_fail(1, "jg_dc_get_flows: null pointer");
     DC_RET(jg::launch_flows(d, true));
     const size_t nb = (size_t)d->nbr, ld = (size_t)d->ld;
     std::vector<double> t(nb * ld);
@@ -588,8 +568,8 @@ int jg_dc_get_flows(int64_t h, double* from) {
 
 int jg_dc_screen(int64_t h, double* rec) {
     DC_ENTER(h);
-    if (!d->solved) return faild(4, "jg_dc_screen: jg_dc_solve first");
-    if (!rec) return faild(1, "jg_dc_screen: null pointer");
+    if (!d->solved) return api_fail(4, "jg_dc_screen: jg_dc_solve first");
+    if (!rec) return api_fail(1, "jg_dc_screen: null pointer");
     DC_RET(jg::launch_flows(d, false));
     DC_API_HIP(jg::sync_copy(rec, d->screen, (size_t)d->batch * 5 * sizeof(double), hipMemcpyDeviceToHost, d->stream));
     return 0;
@@ -597,8 +577,8 @@ int jg_dc_screen(int64_t h, double* rec) {
 
 int jg_dc_screen_device(int64_t h, double* rec_dev) {
     DC_ENTER(h);
-    if (!d->solved) return faild(4, "jg_dc_screen_device: jg_dc_solve first");
-    if (!rec_dev) return faild(1, "jg_dc_screen_device: null pointer");
+    if (!d->solved) return api_fail(4, "jg_dc_screen_device: jg_dc_solve first");
+    if (!rec_dev) return api_fail(1, "jg_dc_screen_device: null pointer");
     DC_RET(jg::launch_flows(d, false));
     DC_API_HIP(hipMemcpyAsync(rec_dev, d->screen, (size_t)d->batch * 5 * sizeof(double), hipMemcpyDeviceToDevice, d->stream));
     DC_API_HIP(hipStreamSynchronize(d->stream));
@@ -607,8 +587,8 @@ int jg_dc_screen_device(int64_t h, double* rec_dev) {
 
 int jg_dc_pack_results_device(int64_t h, double* dst_dev) {
     DC_ENTER(h);
-    if (!d->solved) return faild(4, "jg_dc_pack_results_device: jg_dc_solve first");
-    if (!dst_dev) return faild(1, "jg_dc_pack_results_device: null pointer");
+    if (!d->solved) return api_fail(4, "jg_dc_pack_results_device: jg_dc_solve first");
+    if (!dst_dev) return api_fail(1, "jg_dc_pack_results_device: null pointer");
     hipLaunchKernelGGL(jg::k_dc_pack, dim3((d->n + 1 + 3) / 4, d->ld / 64), dim3(64, 4), 0, d->stream, d->TH, d->status, dst_dev, d->n, d->ld, d->batch);
     DC_API_HIP(hipGetLastError());
     DC_API_HIP(hipStreamSynchronize(d->stream));
@@ -617,28 +597,18 @@ int jg_dc_pack_results_device(int64_t h, double* dst_dev) {
 
 int jg_dc_time_kernel(int64_t h, int kernel, int reps, double* ms) {
     DC_ENTER(h);
-    if (!ms || reps < 1 || kernel < 0 || kernel > 3) return faild(1, "jg_dc_time_kernel: bad argument");
-    if (!d->solved) return faild(4, "jg_dc_time_kernel: jg_dc_solve first");
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int rc = 0;
-    std::string msg;
-    auto hip = [&](hipError_t e, const char* what) { if (e != hipSuccess && !rc) { rc = 2; msg = std::string(what) + ": " + hipGetErrorString(e); } return e == hipSuccess; };
-    if (hip(hipEventCreate(&e0), "hipEventCreate") && hip(hipEventCreate(&e1), "hipEventCreate"))
-        for (int r = 0; r < reps && !rc; ++r) {
-            if (!hip(hipEventRecord(e0, d->stream), "hipEventRecord")) break;
-            if (kernel == 0) { rc = jg::solve_chain(d); if (!rc) rc = jg::launch_flows(d, false); }
-            else if (kernel == 1) jg::sweep_pair<1>(d, nullptr, d->W, d->Z, d->ld, d->ld / 64, nullptr);
-            else if (kernel == 2) jg::launch_combine(d);
-            else rc = jg::launch_flows(d, false);
-            if (rc) { msg = d->error; break; }
-            float t = 0.f;
-            if (!hip(hipEventRecord(e1, d->stream), "hipEventRecord") || !hip(hipEventSynchronize(e1), "hipEventSynchronize") ||
-                !hip(hipEventElapsedTime(&t, e0, e1), "hipEventElapsedTime")) break;
-            ms[r] = (double)t;
+    if (!ms || reps < 1 || kernel < 0 || kernel > 3) return api_fail(1, "jg_dc_time_kernel: bad argument");
+    if (!d->solved) return api_fail(4, "jg_dc_time_kernel: jg_dc_solve first");
+    DC_RET(jg::time_events(d->stream, reps, ms, d->error, [&]() -> int {
+        if (kernel == 1) jg::sweep_outages(d);
+        else if (kernel == 2) jg::launch_combine(d);
+        else {
+            if (kernel == 0) { const int rc = jg::solve_chain(d); if (rc) return rc; }
+            return jg::launch_flows(d, false);
         }
-    if (e0) (void)hipEventDestroy(e0);                                  // on every path
-    if (e1) (void)hipEventDestroy(e1);
-    return rc ? faild(rc, msg) : 0;
+        return 0;
+    }));
+    return 0;
 }
 
 }  // extern "C"

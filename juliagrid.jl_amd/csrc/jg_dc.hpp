@@ -25,47 +25,20 @@
 #include <string>
 #include <vector>
 
-#include "jg_symbolic.hpp"
+#include "jg_dc_sweep.hpp"
 
 namespace jg {
 
-constexpr int DC_T = 4;            // terms per step of a sweep row: the rows' lists are padded to it (pad = factor value 0 x the zero row n of the scratch)
-constexpr int DC_CHAIN_WAVES = 16; // a level of at most this many rows is "narrow": runs of narrow levels are ONE launch (workgroup barriers between levels)
 constexpr double DC_SINGULAR = 1e-9;   // |1 - y_k a' z_s| below it: bridge.  The two sides of the difference are O(1) and carry the rounding of one sweep pair
                                        // (1e-13 on the 10k-bus grid); the smallest denominator of a non-bridge there is 3e-3.
-
-struct DcSweepTables {             // one triangle of the factor, rows grouped by dependency level
-    int* rows = nullptr;           // [n] pivots, level-major
-    int* lev = nullptr;            // [levels + 1] offsets into rows
-    int* ptr = nullptr;            // [n + 1] offsets of the padded term lists (multiples of DC_T)
-    int* col = nullptr;            // [terms] pivot of the operand row (n = the zero row)
-    double* val = nullptr;         // [terms] premultiplied factor value, in list order (k_dc_compact)
-    int* ent = nullptr;            // [terms] factor entry of a term and the pivot whose diagonal divides it: kept only by a handle that refactorises
-    int* dpiv = nullptr;
-    std::vector<int> h_lev;
-    long long terms = 0;
-    struct Launch { int l0, l1, chain; };     // levels [l0, l1): a chain launch, or one wide level
-    std::vector<Launch> launches;
-};
 
 struct DcPairState;
 struct DcSeriesState;
 
-struct DcHandle {
-    int n = 0, nbr = 0, batch = 0, ld = 0, device = 0, slack = 0, n_entries = 0, n_fact_levels = 0;
+struct DcHandle : DcDevice {
+    int n = 0, nbr = 0, batch = 0, ld = 0, slack = 0;
     double slack_angle = 0.0;
-    hipStream_t stream = nullptr;
-    std::string error;
-    // factor (the factorisation tables, A, X and bad live only inside jg_dc_create)
-    int* perm = nullptr;                                    // [n] pivot -> bus
-    int* f_ent = nullptr; std::vector<int> f_lev;           // entries by factorisation level
-    int* t_ptr = nullptr; int* t_a = nullptr; int* t_d = nullptr; int* t_b = nullptr;
-    int* e_src = nullptr; int* diag = nullptr;
-    double* A = nullptr;                                    // [nnz] row-CSR values, slack row / column as identity
-    double* X = nullptr;                                    // [n_entries] factor, A = Lh D^-1 U
-    double* dinv = nullptr;                                 // [n]
-    int* bad = nullptr;                                     // zero / non-finite pivot flag
-    DcSweepTables fwd, bwd;
+    DcFactor fac;                                           // of the nodal matrix (the factorisation tables, A, X and bad live only inside jg_dc_create)
     // base solve (one lane group, lane 0 carries the base case)
     double* rhs0 = nullptr; double* W0 = nullptr; double* th0 = nullptr;      // [n][64], [n + 1][64], [n][64]
     std::vector<double> h_rhs; bool base_dirty = true;
@@ -95,8 +68,9 @@ struct DcHandle {
     double* flows = nullptr; double* part = nullptr; double* screen = nullptr;  // [nbr][ld], [chunks][4][ld], [ld][5]
     int n_chunks = 0;
     bool solved = false;
-    std::vector<void*> allocs;                                                 // everything the handle owns on the device
 };
+
+int dc_base_solve(DcHandle* h);    // theta_0 = B^-1 rhs on lane 0 of the base buffers (jg_dc.hip; the pair and series builds start from it)
 
 // Who leaves with a bridge: ONE DFS of the in-service bus graph (admittance != 0, self-loops aside) from the slack numbers the buses in preorder; the
 // subtree below a tree edge is a contiguous interval of those numbers, and a tree edge (p, u) is a bridge iff no edge other than itself leaves u's subtree

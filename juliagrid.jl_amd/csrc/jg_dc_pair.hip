@@ -1,6 +1,6 @@
 // jg_dc_pair.hip -- the DC N-2 screen over all pairs of a candidate list (jg_dc_pair.hpp has the algebra and the reference loop it stands for).
 //
-// Build: the sweep pair of jg_dc_sweep.hpp over the candidates, DC_PAIR_LANES at a time, and k_pair_phi after each batch (the flow kernel's shape: a wave
+// Build: the sweep pair of jg_dc_sweep.hip over the candidates, DC_PAIR_LANES at a time, and k_pair_phi after each batch (the flow kernel's shape: a wave
 // is 8 rows x 64 candidates, y_m (z[from_m] - z[to_m]), coalesced stores).  Screen of a row block [k0, k1): k_pair_screen solves the 2 x 2 systems and
 // walks the rows of Phi once (a wave = DC_PAIR_TILE candidates k in registers x 64 consecutive l; Phi[m, k..], f0_m, 1 / rating_m through scalar loads,
 // Phi[m, l..l+63] one coalesced vector load reused for every k of the tile; nothing is written per m); the records come out of the block's dense result by
@@ -17,17 +17,11 @@
 
 #include "../../include/jgrid.h"
 #include "jg_dc.hpp"
-#include "jg_engine.hpp"
+#include "jg_dc_abi.hpp"
 
 namespace jg {
 
 namespace {
-
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wunused-function"                   // only the sweeps of the shared header are used here: the factor is the handle's
-#pragma clang diagnostic ignored "-Wunneeded-internal-declaration"
-#include "jg_dc_sweep.hpp"
-#pragma clang diagnostic pop
 
 constexpr int PAIR_PHI_ROWS = 8;        // rows of Phi per wave of k_pair_phi
 
@@ -206,15 +200,6 @@ __global__ void k_pair_colmax(const double* load, double* c_max, int ldk, int nk
     c_max[l] = mx;
 }
 
-int pair_base_solve(DcHandle* h) {
-    if (h->h_rhs.empty()) { h->error = "jg_dc_set_rhs has not been called"; return 1; }
-    DC_HIP(hipMemcpy2DAsync(h->rhs0, 64 * sizeof(double), h->h_rhs.data(), sizeof(double), sizeof(double), (size_t)h->n, hipMemcpyHostToDevice, h->stream));
-    sweep_pair_on<0>(h, h->rhs0, (const int*)nullptr, (const int*)nullptr, h->W0, h->th0, 64, 1, nullptr);
-    DC_HIP(hipGetLastError());
-    h->base_dirty = false;
-    return 0;
-}
-
 void state_release(DcHandle* h, DcPairState*& slot) {
     DcPairState* p = slot;
     if (!p) return;
@@ -240,7 +225,7 @@ std::string bytes_text(size_t b) {
 int state_build(DcHandle* h, DcPairState*& slot, const char* who, const std::vector<int>& cand, const std::vector<int>& mon, int64_t budget, size_t extra,
                 const std::string& extra_text, double* info) {
     state_release(h, slot);
-    if (h->base_dirty) DC_TRY(pair_base_solve(h));
+    if (h->base_dirty) DC_TRY(dc_base_solve(h));
     const int nk = (int)cand.size(), ldk = (nk + 63) / 64 * 64, n = h->n;
     std::vector<int> rows, pos, flag, crow(ldk, 0), clab(ldk, 0);
     {
@@ -308,7 +293,7 @@ int state_build(DcHandle* h, DcPairState*& slot, const char* who, const std::vec
             !hip(sync_copy(ot, ht.data(), ldb * sizeof(int), hipMemcpyHostToDevice, h->stream), "upload")) break;
         const int groups = (std::min(ldb, ldk - c0) + 63) / 64;
         hip(hipEventRecord(ev[0], h->stream), "hipEventRecord");
-        sweep_pair_on<1>(h, (const double*)nullptr, of, ot, W, Z, ldb, groups, (const int*)nullptr);
+        sweep_pair(h->fac, h->stream, 1, nullptr, of, ot, W, Z, ldb, groups, nullptr);
         hip(hipEventRecord(ev[1], h->stream), "hipEventRecord");
         PairPhiArgs a{Z, p->row_branch, h->b_from, h->b_to, h->b_y, p->Phi, nr, ldb, ldk, c0};
         hipLaunchKernelGGL(k_pair_phi, dim3((nr + 4 * PAIR_PHI_ROWS - 1) / (4 * PAIR_PHI_ROWS), groups), dim3(64, 4), 0, h->stream, a);
@@ -489,70 +474,51 @@ int dc_pair_lists(DcHandle* d, const std::string& who, int64_t nk, const int64_t
 
 using jg::DcHandle;
 
-namespace {
-int failp(int code, const std::string& msg) { jg::set_last_error(msg); return code; }
-DcHandle* HP(int64_t h) { return reinterpret_cast<DcHandle*>(static_cast<intptr_t>(h)); }
-#define PAIR_ENTER(h)                                                                   \
-    DcHandle* d = HP(h);                                                                \
-    if (!d) return failp(1, "null DC handle");                                          \
-    if (hipSetDevice(d->device) != hipSuccess) return failp(2, "hipSetDevice failed")
-#define PAIR_RET(expr) do { const int rc__ = (expr); if (rc__) return failp(rc__, d->error); } while (0)
-}  // namespace
+using jg::api_fail;
 
 extern "C" {
 
 int jg_dc_pair_build(int64_t h, int64_t nk, const int64_t* candidates, int64_t nm, const int64_t* monitored, int64_t budget_bytes, double* info) {
-    PAIR_ENTER(h);
-    if (!d->nbr) return failp(1, "jg_dc_pair_build: jg_dc_set_branches first");
-    if (d->h_rhs.empty()) return failp(1, "jg_dc_pair_build: jg_dc_set_rhs first");
-    if (nk < 2 || !candidates || !info || nm < 0 || (nm && !monitored)) return failp(1, "jg_dc_pair_build: two or more candidates, and info, are needed");
+    DC_ENTER(h);
+    if (!d->nbr) return api_fail(1, "jg_dc_pair_build: jg_dc_set_branches first");
+    if (d->h_rhs.empty()) return api_fail(1, "jg_dc_pair_build: jg_dc_set_rhs first");
+    if (nk < 2 || !candidates || !info || nm < 0 || (nm && !monitored)) return api_fail(1, "jg_dc_pair_build: two or more candidates, and info, are needed");
     std::vector<int> cand, mon;
-    PAIR_RET(jg::dc_pair_lists(d, "jg_dc_pair_build", nk, candidates, nm, monitored, cand, mon));
-    PAIR_RET(jg::dc_pair_state_build(d, d->pair, "jg_dc_pair_build", cand, mon, budget_bytes, 0, "", info));
+    DC_RET(jg::dc_pair_lists(d, "jg_dc_pair_build", nk, candidates, nm, monitored, cand, mon));
+    DC_RET(jg::dc_pair_state_build(d, d->pair, "jg_dc_pair_build", cand, mon, budget_bytes, 0, "", info));
     return 0;
 }
 
 int jg_dc_pair_screen(int64_t h, int64_t k0, int64_t k1, double threshold, int64_t capacity, double* records, int64_t island_capacity, int64_t* islanding,
                       int64_t* totals, double* worst, double* dense_load, int32_t* dense_branch, int32_t* dense_count, double* dense_det) {
-    PAIR_ENTER(h);
-    if (!d->pair) return failp(4, "jg_dc_pair_screen: jg_dc_pair_build first");
-    if (!d->b_rating) return failp(1, "jg_dc_pair_screen: jg_dc_set_rating first (the loadings are |from| / rating)");
-    if (k0 < 0 || k1 <= k0 || k1 > d->pair->nk) return failp(1, "jg_dc_pair_screen: rows [k0, k1) out of range");
+    DC_ENTER(h);
+    if (!d->pair) return api_fail(4, "jg_dc_pair_screen: jg_dc_pair_build first");
+    if (!d->b_rating) return api_fail(1, "jg_dc_pair_screen: jg_dc_set_rating first (the loadings are |from| / rating)");
+    if (k0 < 0 || k1 <= k0 || k1 > d->pair->nk) return api_fail(1, "jg_dc_pair_screen: rows [k0, k1) out of range");
     if (!(threshold >= 0.0) || capacity < 0 || island_capacity < 0 || (capacity && !records) || (island_capacity && !islanding) || !totals)
-        return failp(1, "jg_dc_pair_screen: bad argument");
+        return api_fail(1, "jg_dc_pair_screen: bad argument");
     jg::PairOut o{records, islanding, totals, worst, dense_load, dense_branch, dense_count, dense_det};
-    PAIR_RET(jg::pair_screen(d, (int)k0, (int)k1, threshold, capacity, island_capacity, o));
+    DC_RET(jg::pair_screen(d, (int)k0, (int)k1, threshold, capacity, island_capacity, o));
     return 0;
 }
 
 int jg_dc_pair_time_kernel(int64_t h, int kernel, int64_t k0, int64_t k1, int reps, double* ms) {
-    PAIR_ENTER(h);
-    if (!d->pair) return failp(4, "jg_dc_pair_time_kernel: jg_dc_pair_build first");
-    if (!ms || reps < 1 || kernel < 0 || kernel > 1 || k0 < 0 || k1 <= k0 || k1 > d->pair->nk) return failp(1, "jg_dc_pair_time_kernel: bad argument");
-    if (k1 - k0 > d->pair->blk_rows) return failp(4, "jg_dc_pair_time_kernel: jg_dc_pair_screen with a block of at least these rows first");
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int rc = 0;
-    std::string msg;
-    auto hip = [&](hipError_t e, const char* what) { if (e != hipSuccess && !rc) { rc = 2; msg = std::string(what) + ": " + hipGetErrorString(e); } return e == hipSuccess; };
+    DC_ENTER(h);
+    if (!d->pair) return api_fail(4, "jg_dc_pair_time_kernel: jg_dc_pair_build first");
+    if (!ms || reps < 1 || kernel < 0 || kernel > 1 || k0 < 0 || k1 <= k0 || k1 > d->pair->nk) return api_fail(1, "jg_dc_pair_time_kernel: bad argument");
+    if (k1 - k0 > d->pair->blk_rows) return api_fail(4, "jg_dc_pair_time_kernel: jg_dc_pair_screen with a block of at least these rows first");
     const jg::PairScreenArgs sa = jg::screen_args(d, (int)k0, (int)k1, 1.0, false);
     const jg::PairListArgs la = jg::list_args(d, (int)k0, (int)k1, 1.0, 0, 0);
-    if (hip(hipEventCreate(&e0), "hipEventCreate") && hip(hipEventCreate(&e1), "hipEventCreate"))
-        for (int r = 0; r < reps && !rc; ++r) {
-            if (!hip(hipEventRecord(e0, d->stream), "hipEventRecord")) break;
-            if (kernel == 0) jg::launch_screen(d, sa);
-            else jg::launch_stats(d, la);
-            float t = 0.f;
-            if (!hip(hipGetLastError(), "launch") || !hip(hipEventRecord(e1, d->stream), "hipEventRecord") || !hip(hipEventSynchronize(e1), "hipEventSynchronize") ||
-                !hip(hipEventElapsedTime(&t, e0, e1), "hipEventElapsedTime")) break;
-            ms[r] = (double)t;
-        }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    return rc ? failp(rc, msg) : 0;
+    DC_RET(jg::time_events(d->stream, reps, ms, d->error, [&]() -> int {
+        if (kernel == 0) jg::launch_screen(d, sa);
+        else jg::launch_stats(d, la);
+        return 0;
+    }));
+    return 0;
 }
 
 int jg_dc_pair_release(int64_t h) {
-    PAIR_ENTER(h);
+    DC_ENTER(h);
     jg::dc_pair_free(d);
     return 0;
 }

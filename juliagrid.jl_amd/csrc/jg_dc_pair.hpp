@@ -11,7 +11,7 @@
 // neither branch alone is a bridge): status 3, the worst loading is NaN.
 //
 // What is kept: Phi on the rows R = monitored u candidates (ascending branch index), columns = candidates, [rows][ldk] doubles with ldk = candidates
-// rounded up to 64 -- the sweep pair of jg_dc_sweep.hpp runs once per candidate (a lane batch at a time), never per pair.
+// rounded up to 64 -- the sweep pair of jg_dc_sweep.hip runs once per candidate (a lane batch at a time), never per pair.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,6 +1,6 @@
 // jg_dc_series.hip -- the DC N-1 screen over a series of injection profiles (jg_dc_series.hpp has the algebra and the reference loop it stands for).
 //
-// Build: Phi by the build the pair screen shares (jg_dc_pair.hip), into a state of the series' own; then the sweep pair of jg_dc_sweep.hpp over the
+// Build: Phi by the build the pair screen shares (jg_dc_pair.hip), into a state of the series' own; then the sweep pair of jg_dc_sweep.hip over the
 // profiles' right-hand sides, DC_PAIR_LANES at a time on scratch of the build's own, and k_series_f0 after each batch (k_pair_phi's shape: a wave is 8 rows
 // x 64 profiles, y_m ((theta[from_m] + slack angle) - (theta[to_m] + slack angle) - shiftAngle_m), coalesced stores).  Screen of a row block [k0, k1):
 // k_series_screen walks the rows once (a wave = DC_SERIES_TILE candidates k in registers x 64 consecutive profiles; Phi[m, k..], 1 / rating_m and the
@@ -18,17 +18,11 @@
 
 #include "../../include/jgrid.h"
 #include "jg_dc.hpp"
-#include "jg_engine.hpp"
+#include "jg_dc_abi.hpp"
 
 namespace jg {
 
 namespace {
-
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wunused-function"                   // only the sweeps of the shared header are used here: the factor is the handle's
-#pragma clang diagnostic ignored "-Wunneeded-internal-declaration"
-#include "jg_dc_sweep.hpp"
-#pragma clang diagnostic pop
 
 constexpr int SERIES_F0_ROWS = 8;       // rows of F0 per wave of k_series_f0
 
@@ -249,7 +243,7 @@ int series_build(DcHandle* h, const std::vector<int>& cand, const std::vector<in
             if (!hip(hipMemcpy2DAsync(R, (size_t)ldb * sizeof(double), tb.data(), (size_t)w * sizeof(double), (size_t)w * sizeof(double), (size_t)n, hipMemcpyHostToDevice, h->stream), "upload") ||
                 !hip(hipStreamSynchronize(h->stream), "hipStreamSynchronize")) break;
             hip(hipEventRecord(ev[0], h->stream), "hipEventRecord");
-            sweep_pair_on<0>(h, R, (const int*)nullptr, (const int*)nullptr, W, TH, ldb, groups, (const int*)nullptr);
+            sweep_pair(h->fac, h->stream, 0, R, nullptr, nullptr, W, TH, ldb, groups, nullptr);
             hip(hipEventRecord(ev[1], h->stream), "hipEventRecord");
             SeriesF0Args a{TH, p->row_branch, h->b_from, h->b_to, h->b_y, h->b_shift, h->slack_angle, s->F0, nr, ldb, ldt, c0, T};
             hipLaunchKernelGGL(k_series_f0, dim3((nr + 4 * SERIES_F0_ROWS - 1) / (4 * SERIES_F0_ROWS), groups), dim3(64, 4), 0, h->stream, a);
@@ -395,72 +389,53 @@ void dc_series_free(DcHandle* h) { series_release(h); }
 
 using jg::DcHandle;
 
-namespace {
-int fails(int code, const std::string& msg) { jg::set_last_error(msg); return code; }
-DcHandle* HS(int64_t h) { return reinterpret_cast<DcHandle*>(static_cast<intptr_t>(h)); }
-#define SERIES_ENTER(h)                                                                 \
-    DcHandle* d = HS(h);                                                                \
-    if (!d) return fails(1, "null DC handle");                                          \
-    if (hipSetDevice(d->device) != hipSuccess) return fails(2, "hipSetDevice failed")
-#define SERIES_RET(expr) do { const int rc__ = (expr); if (rc__) return fails(rc__, d->error); } while (0)
-}  // namespace
+using jg::api_fail;
 
 extern "C" {
 
 int jg_dc_series_build(int64_t h, int64_t nk, const int64_t* candidates, int64_t nm, const int64_t* monitored, int64_t profiles, const double* rhs,
                        int64_t budget_bytes, double* info) {
-    SERIES_ENTER(h);
-    if (!d->nbr) return fails(1, "jg_dc_series_build: jg_dc_set_branches first");
-    if (d->h_rhs.empty()) return fails(1, "jg_dc_series_build: jg_dc_set_rhs first");
-    if (nk < 1 || !candidates || !info || nm < 0 || (nm && !monitored)) return fails(1, "jg_dc_series_build: one or more candidates, and info, are needed");
-    if (profiles < 1 || profiles > (1 << 24) || !rhs) return fails(1, "jg_dc_series_build: one or more profiles are needed");
+    DC_ENTER(h);
+    if (!d->nbr) return api_fail(1, "jg_dc_series_build: jg_dc_set_branches first");
+    if (d->h_rhs.empty()) return api_fail(1, "jg_dc_series_build: jg_dc_set_rhs first");
+    if (nk < 1 || !candidates || !info || nm < 0 || (nm && !monitored)) return api_fail(1, "jg_dc_series_build: one or more candidates, and info, are needed");
+    if (profiles < 1 || profiles > (1 << 24) || !rhs) return api_fail(1, "jg_dc_series_build: one or more profiles are needed");
     std::vector<int> cand, mon;
-    SERIES_RET(jg::dc_pair_lists(d, "jg_dc_series_build", nk, candidates, nm, monitored, cand, mon));
-    SERIES_RET(jg::series_build(d, cand, mon, (int)profiles, rhs, budget_bytes, info));
+    DC_RET(jg::dc_pair_lists(d, "jg_dc_series_build", nk, candidates, nm, monitored, cand, mon));
+    DC_RET(jg::series_build(d, cand, mon, (int)profiles, rhs, budget_bytes, info));
     return 0;
 }
 
 int jg_dc_series_screen(int64_t h, int64_t k0, int64_t k1, double threshold, int64_t capacity, double* records, int64_t* islanding, int64_t* totals,
                         double* worst, double* worst_profile, int64_t* violating_profile, double* base, double* dense_load, int32_t* dense_branch,
                         int32_t* dense_count) {
-    SERIES_ENTER(h);
-    if (!d->series) return fails(4, "jg_dc_series_screen: jg_dc_series_build first");
-    if (!d->b_rating) return fails(1, "jg_dc_series_screen: jg_dc_set_rating first (the loadings are |from| / rating)");
-    if (k0 < 0 || k1 <= k0 || k1 > d->series->phi->nk) return fails(1, "jg_dc_series_screen: rows [k0, k1) out of range");
-    if (!(threshold >= 0.0) || capacity < 0 || (capacity && !records) || !totals) return fails(1, "jg_dc_series_screen: bad argument");
+    DC_ENTER(h);
+    if (!d->series) return api_fail(4, "jg_dc_series_screen: jg_dc_series_build first");
+    if (!d->b_rating) return api_fail(1, "jg_dc_series_screen: jg_dc_set_rating first (the loadings are |from| / rating)");
+    if (k0 < 0 || k1 <= k0 || k1 > d->series->phi->nk) return api_fail(1, "jg_dc_series_screen: rows [k0, k1) out of range");
+    if (!(threshold >= 0.0) || capacity < 0 || (capacity && !records) || !totals) return api_fail(1, "jg_dc_series_screen: bad argument");
     jg::SeriesOut o{records, islanding, totals, worst, worst_profile, violating_profile, base, dense_load, dense_branch, dense_count};
-    SERIES_RET(jg::series_screen(d, (int)k0, (int)k1, threshold, capacity, o));
+    DC_RET(jg::series_screen(d, (int)k0, (int)k1, threshold, capacity, o));
     return 0;
 }
 
 int jg_dc_series_time_kernel(int64_t h, int kernel, int64_t k0, int64_t k1, int reps, double* ms) {
-    SERIES_ENTER(h);
-    if (!d->series) return fails(4, "jg_dc_series_time_kernel: jg_dc_series_build first");
-    if (!ms || reps < 1 || kernel < 0 || kernel > 1 || k0 < 0 || k1 <= k0 || k1 > d->series->phi->nk) return fails(1, "jg_dc_series_time_kernel: bad argument");
-    if (k1 - k0 > d->series->blk_rows) return fails(4, "jg_dc_series_time_kernel: jg_dc_series_screen with a block of at least these rows first");
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int rc = 0;
-    std::string msg;
-    auto hip = [&](hipError_t e, const char* what) { if (e != hipSuccess && !rc) { rc = 2; msg = std::string(what) + ": " + hipGetErrorString(e); } return e == hipSuccess; };
+    DC_ENTER(h);
+    if (!d->series) return api_fail(4, "jg_dc_series_time_kernel: jg_dc_series_build first");
+    if (!ms || reps < 1 || kernel < 0 || kernel > 1 || k0 < 0 || k1 <= k0 || k1 > d->series->phi->nk) return api_fail(1, "jg_dc_series_time_kernel: bad argument");
+    if (k1 - k0 > d->series->blk_rows) return api_fail(4, "jg_dc_series_time_kernel: jg_dc_series_screen with a block of at least these rows first");
     const jg::SeriesScreenArgs sa = jg::screen_args(d, (int)k0, (int)k1, 1.0);
     const jg::SeriesListArgs la = jg::list_args(d, (int)k0, (int)k1, 1.0, 0);
-    if (hip(hipEventCreate(&e0), "hipEventCreate") && hip(hipEventCreate(&e1), "hipEventCreate"))
-        for (int r = 0; r < reps && !rc; ++r) {
-            if (!hip(hipEventRecord(e0, d->stream), "hipEventRecord")) break;
-            if (kernel == 0) jg::launch_screen(d, sa);
-            else jg::launch_stats(d, la);
-            float t = 0.f;
-            if (!hip(hipGetLastError(), "launch") || !hip(hipEventRecord(e1, d->stream), "hipEventRecord") || !hip(hipEventSynchronize(e1), "hipEventSynchronize") ||
-                !hip(hipEventElapsedTime(&t, e0, e1), "hipEventElapsedTime")) break;
-            ms[r] = (double)t;
-        }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    return rc ? fails(rc, msg) : 0;
+    DC_RET(jg::time_events(d->stream, reps, ms, d->error, [&]() -> int {
+        if (kernel == 0) jg::launch_screen(d, sa);
+        else jg::launch_stats(d, la);
+        return 0;
+    }));
+    return 0;
 }
 
 int jg_dc_series_release(int64_t h) {
-    SERIES_ENTER(h);
+    DC_ENTER(h);
     jg::dc_series_free(d);
     return 0;
 }

@@ -1,5 +1,5 @@
 // jg_dcse.hip -- DC state estimation with batched bad-data removal on one shared scalar factor of the gain matrix (jg_dcse.hpp has the algebra and the
-// reference lines it stands for).  The factorisation and the sweeps are jg_dc_sweep.hpp's, on the pattern of G = H' W H; here: the gain assembly, the
+// reference lines it stands for).  The factorisation and the sweeps are jg_dc_sweep.hip's, on the pattern of G = H' W H; here: the gain assembly, the
 // right-hand side H' W z, the residual pass (objective, normalised residuals, their arg-max), the Omega diagonal, the removal by compensation, the C ABI.
 // Coefficient values, weights and indices are wave-uniform and go through scalar loads; every store is a vector store.
 //
@@ -7,6 +7,7 @@
 // coefficient WITHOUT its slack column by voltage.angle = theta + a (badData.jl:66-73), chiTest the full coefficient (:971).  So row i of the test
 // subtracts roff_t[i] = a sum_{j != slack} H_ij and the objective roff_c[i] = a sum_j H_ij on top of r_i.  Both are 0 for a = 0.
 #include "jg_dcse.hpp"
+#include "jg_dc_abi.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -19,8 +20,6 @@
 namespace jg {
 
 namespace {
-
-#include "jg_dc_sweep.hpp"
 
 constexpr int K = DCSE_MAX_REMOVED;
 
@@ -221,7 +220,7 @@ void launch_rhs(DcseHandle* h, const double* Z) {
     DcseRhsArgs a{h->c_ptr, h->c_row, h->c_val, h->ws, Z, h->B, h->n, h->ld};
     hipLaunchKernelGGL(k_dcse_rhs, dim3((h->n + 3) / 4, h->ld / 64), dim3(64, 4), 0, h->stream, a);
 }
-void sweep(DcseHandle* h, double* out) { sweep_pair_on<0>(h, h->B, nullptr, nullptr, h->W, out, h->ld, h->ld / 64, nullptr); }
+void sweep(DcseHandle* h, double* out) { sweep_pair(h->fac, h->stream, 0, h->B, nullptr, nullptr, h->W, out, h->ld, h->ld / 64, nullptr); }
 
 template <bool NORM, bool REM>
 void launch_residual(DcseHandle* h, const double* TH, double* R, double* NRM) {
@@ -278,15 +277,15 @@ int assemble_and_factor(DcseHandle* h) {
     DC_HIP(sync_copy(h->wi, wi.data(), m * sizeof(double), hipMemcpyHostToDevice, h->stream));
     DC_HIP(sync_copy(h->roff_t, rt.data(), m * sizeof(double), hipMemcpyHostToDevice, h->stream));
     DC_HIP(sync_copy(h->roff_c, rc.data(), m * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    DC_HIP(sync_fill(h->bad, 0, sizeof(int), h->stream));
-    hipLaunchKernelGGL(k_dcse_gain, dim3((h->nnz_gain + 255) / 256), dim3(256), 0, h->stream, h->g_ptr, h->g_row, h->g_prod, h->g_add, h->ws, h->A, h->nnz_gain);
-    factor_numeric(h);
+    DC_HIP(sync_fill(h->fac.bad, 0, sizeof(int), h->stream));
+    hipLaunchKernelGGL(k_dcse_gain, dim3((h->nnz_gain + 255) / 256), dim3(256), 0, h->stream, h->g_ptr, h->g_row, h->g_prod, h->g_add, h->ws, h->fac.A, h->nnz_gain);
+    factor_numeric(h->fac, h->stream);
     DC_HIP(hipGetLastError());
     return 0;
 }
 int check_pivots(DcseHandle* h) {
     int bad = 0;
-    DC_HIP(sync_copy(&bad, h->bad, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    DC_HIP(sync_copy(&bad, h->fac.bad, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     if (bad) { h->error = "zero or non-finite pivot in the gain matrix: the measurement set does not make the grid observable"; return 3; }
     return 0;
 }
@@ -381,17 +380,17 @@ int dcse_create(DcseHandle* h, int64_t n64, int64_t m64, const int64_t* rowptr, 
     DC_TRY(dev_alloc(h, &h->r_ptr, h->h_rptr.size(), h->h_rptr.data()));
     DC_TRY(dev_alloc(h, &h->r_col, h->h_rcol.size(), h->h_rcol.data()));
     DC_TRY(dev_alloc(h, &h->r_val, h->h_rval.size(), h->h_rval.data()));
-    // symbolic analysis of G's pattern, no top tasks (the policy of jg_dc.hip); G is symmetric positive definite when the set is observable, so the
+    // symbolic analysis of G's pattern, no top tasks (DC_POLICY_NO_TOP); G is symmetric positive definite when the set is observable, so the
     // scalar factor without pivoting is safe
     BlockSymbolic S;
-    constexpr long long DC_POLICY_NO_TOP = (long long)255 << 8;
     if (analyze(n, rp.data(), ci.data(), DC_POLICY_NO_TOP, S) != 0) { h->error = "symbolic analysis of the gain pattern failed"; return 1; }
-    DC_TRY(factor_tables(h, S));
+    DcFactor& F = h->fac;
+    DC_TRY(factor_tables(h, F, n, S));
     const size_t M = (size_t)m, ld = (size_t)h->ld, N = (size_t)n;
-    DC_TRY(dev_alloc(h, &h->A, (size_t)nnzg, (const double*)nullptr, true));
-    DC_TRY(dev_alloc(h, &h->X, (size_t)S.n_entries + 1, (const double*)nullptr, true));
-    DC_TRY(dev_alloc(h, &h->dinv, N, (const double*)nullptr, true));
-    DC_TRY(dev_alloc(h, &h->bad, (size_t)1, (const int*)nullptr, true));
+    DC_TRY(dev_alloc(h, &F.A, (size_t)nnzg, (const double*)nullptr, true));
+    DC_TRY(dev_alloc(h, &F.X, (size_t)S.n_entries + 1, (const double*)nullptr, true));
+    DC_TRY(dev_alloc(h, &F.dinv, N, (const double*)nullptr, true));
+    DC_TRY(dev_alloc(h, &F.bad, (size_t)1, (const int*)nullptr, true));
     DC_TRY(dev_alloc(h, &h->st, M, (const int*)nullptr, true));
     DC_TRY(dev_alloc(h, &h->ws, M, (const double*)nullptr, true));
     DC_TRY(dev_alloc(h, &h->wi, M, (const double*)nullptr, true));
@@ -399,8 +398,8 @@ int dcse_create(DcseHandle* h, int64_t n64, int64_t m64, const int64_t* rowptr, 
     DC_TRY(dev_alloc(h, &h->roff_c, M, (const double*)nullptr, true));
     DC_TRY(dev_alloc(h, &h->omega, M, (const double*)nullptr, true));
     DC_TRY(assemble_and_factor(h));
-    DC_TRY(build_sweep(h, h->fwd, forward_levels(n, S), S.l_ptr, S.l_ent, S.l_col, false, true));
-    DC_TRY(build_sweep(h, h->bwd, S.bwd_level, S.u_ptr, S.u_ent, S.u_col, true, true));
+    DC_TRY(build_sweep(h, F, F.fwd, forward_levels(n, S), S.l_ptr, S.l_ent, S.l_col, false, true));
+    DC_TRY(build_sweep(h, F, F.bwd, S.bwd_level, S.u_ptr, S.u_ent, S.u_col, true, true));
     DC_TRY(check_pivots(h));
     h->n_chunks = (m + DCSE_ROWS - 1) / DCSE_ROWS;
     DC_TRY(dev_alloc(h, &h->Z, M * ld, (const double*)nullptr, true));
@@ -439,7 +438,7 @@ int compute_omega(DcseHandle* h) {
         if (e == hipSuccess) e = hipMemsetAsync(Bo, 0, N * ldo * sizeof(double), h->stream);
         if (e != hipSuccess) { h->error = std::string("Omega diagonal: ") + hipGetErrorString(e); rc = 2; break; }
         hipLaunchKernelGGL(k_dcse_row_rhs, dim3(ldo / 256), dim3(256), 0, h->stream, h->newrow, h->r_ptr, h->r_col, h->r_val, h->st, Bo, ldo, h->slack);
-        sweep_pair_on<0>(h, Bo, nullptr, nullptr, Wo, Uo, ldo, ldo / 64, nullptr);
+        sweep_pair(h->fac, h->stream, 0, Bo, nullptr, nullptr, Wo, Uo, ldo, ldo / 64, nullptr);
         hipLaunchKernelGGL(k_dcse_omega, dim3(ldo / 256), dim3(256), 0, h->stream, h->newrow, h->r_ptr, h->r_col, h->r_val, h->st, h->wi, Uo, h->omega, ldo, h->slack);
     }
     hipError_t e = hipStreamSynchronize(h->stream);
@@ -478,7 +477,7 @@ int remove_rows(DcseHandle* h, const std::vector<int>& rows) {
     DC_HIP(hipMemsetAsync(h->B, 0, N * ld * sizeof(double), h->stream));
     const int tb = (int)((ld + 255) / 256);
     hipLaunchKernelGGL(k_dcse_row_rhs, dim3(tb), dim3(256), 0, h->stream, h->newrow, h->r_ptr, h->r_col, h->r_val, h->st, h->B, h->ld, h->slack);
-    sweep_pair_on<0>(h, h->B, nullptr, nullptr, h->W, h->TMP, h->ld, (int)groups.size(), h->glist);
+    sweep_pair(h->fac, h->stream, 0, h->B, nullptr, nullptr, h->W, h->TMP, h->ld, (int)groups.size(), h->glist);
     hipLaunchKernelGGL(k_dcse_keep_column, dim3((unsigned)((N * ld + 255) / 256)), dim3(256), 0, h->stream, h->newrow, h->cnt, h->TMP, h->U, h->n, h->ld);
     hipLaunchKernelGGL(k_dcse_extend, dim3(tb), dim3(256), 0, h->stream, h->newrow, h->rem, h->cnt, h->lstat, h->U, h->LD, h->wi, h->r_ptr, h->r_col, h->r_val,
                        h->n, h->ld, h->slack);
@@ -504,16 +503,9 @@ void dcse_destroy(DcseHandle* h) {
 
 using jg::DcseHandle;
 
-namespace {
-int faile(int code, const std::string& msg) { jg::set_last_error(msg); return code; }
-DcseHandle* HS(int64_t h) { return reinterpret_cast<DcseHandle*>(static_cast<intptr_t>(h)); }
-#define SE_ENTER(h)                                                                     \
-    DcseHandle* d = HS(h);                                                              \
-    if (!d) return faile(1, "null DC state estimation handle");                         \
-    if (hipSetDevice(d->device) != hipSuccess) return faile(2, "hipSetDevice failed")
-#define SE_RET(expr) do { const int rc__ = (expr); if (rc__) return faile(rc__, d->error); } while (0)
-#define SE_HIP(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) return faile(2, std::string(#expr) + ": " + hipGetErrorString(e__)); } while (0)
+using jg::api_fail;
 
+namespace {
 // [rows][ld] on the device -> [batch][rows] on the host
 int fetch_lanes(DcseHandle* d, const double* dev, size_t rows, double* out, double add) {
     const size_t ld = (size_t)d->ld;
@@ -531,79 +523,79 @@ int jg_dcse_create(int64_t* out, int64_t n, int64_t m, const int64_t* rowptr, co
                    const int32_t* status, int64_t slack, double slack_angle, int64_t batch, int device) {
     if (!out || !rowptr || !col || !val || !precision || !status || n < 1 || n > (1 << 24) || m < 1 || m > (1 << 26) || slack < 1 || slack > n || batch < 1 ||
         batch > (1 << 20))
-        return faile(1, "jg_dcse_create: bad argument");
+        return api_fail(1, "jg_dcse_create: bad argument");
     DcseHandle* h = new DcseHandle();
     const int rc = jg::dcse_create(h, n, m, rowptr, col, val, precision, status, slack, slack_angle, batch, device);
-    if (rc) { const std::string msg = h->error; jg::dcse_destroy(h); *out = 0; return faile(rc, msg); }
+    if (rc) { const std::string msg = h->error; jg::dcse_destroy(h); *out = 0; return api_fail(rc, msg); }
     *out = (int64_t)reinterpret_cast<intptr_t>(h);
     return 0;
 }
 
 void jg_dcse_destroy(int64_t h) {
-    if (HS(h)) jg::dcse_destroy(HS(h));
+    if (h) jg::dcse_destroy(reinterpret_cast<DcseHandle*>(static_cast<intptr_t>(h)));
 }
 
 int jg_dcse_dims(int64_t h, int64_t* dims) {
     SE_ENTER(h);
-    if (!dims) return faile(1, "jg_dcse_dims: null pointer");
-    dims[0] = d->n; dims[1] = d->m; dims[2] = d->batch; dims[3] = d->ld; dims[4] = d->nnz_gain; dims[5] = d->n_entries; dims[6] = d->n_fact_levels;
-    dims[7] = (int64_t)d->fwd.h_lev.size() - 1; dims[8] = (int64_t)d->bwd.h_lev.size() - 1;
-    dims[9] = (int64_t)(d->fwd.launches.size() + d->bwd.launches.size()); dims[10] = d->fwd.terms + d->bwd.terms;
+    if (!dims) return api_fail(1, "jg_dcse_dims: null pointer");
+    dims[0] = d->n; dims[1] = d->m; dims[2] = d->batch; dims[3] = d->ld; dims[4] = d->nnz_gain; dims[5] = d->fac.n_entries; dims[6] = d->fac.n_fact_levels;
+    dims[7] = (int64_t)d->fac.fwd.h_lev.size() - 1; dims[8] = (int64_t)d->fac.bwd.h_lev.size() - 1;
+    dims[9] = (int64_t)(d->fac.fwd.launches.size() + d->fac.bwd.launches.size()); dims[10] = d->fac.fwd.terms + d->fac.bwd.terms;
     dims[11] = d->refactorisations; dims[12] = d->omega_runs; dims[13] = jg::DCSE_MAX_REMOVED;
     return 0;
 }
 
 int jg_dcse_set_weights(int64_t h, const double* precision, const int32_t* status) {
     SE_ENTER(h);
-    if (!precision || !status) return faile(1, "jg_dcse_set_weights: null pointer");
+    if (!precision || !status) return api_fail(1, "jg_dcse_set_weights: null pointer");
     for (int i = 0; i < d->m; ++i)
-        if (!(precision[i] > 0.0) || !std::isfinite(precision[i]) || (status[i] != 0 && status[i] != 1)) return faile(1, "jg_dcse_set_weights: precision must be positive, status 0 or 1");
+        if (!(precision[i] > 0.0) || !std::isfinite(precision[i]) || (status[i] != 0 && status[i] != 1)) return api_fail(1, "jg_dcse_set_weights: precision must be positive, status 0 or 1");
     d->h_prec.assign(precision, precision + d->m);
     for (int i = 0; i < d->m; ++i) d->h_st[i] = status[i];
     d->solved = false; d->omega_valid = false;
-    SE_RET(jg::assemble_and_factor(d));
-    jg::compact_sweep(d, d->fwd);
-    jg::compact_sweep(d, d->bwd);
-    SE_HIP(hipGetLastError());
+    DC_RET(jg::assemble_and_factor(d));
+    jg::compact_sweep(d->fac, d->fac.fwd, d->stream);
+    jg::compact_sweep(d->fac, d->fac.bwd, d->stream);
+    DC_API_HIP(hipGetLastError());
     d->refactorisations++;
-    SE_RET(jg::reset_removed(d));
-    SE_RET(jg::check_pivots(d));
+    DC_RET(jg::reset_removed(d));
+    DC_RET(jg::check_pivots(d));
     return 0;
 }
 
 int jg_dcse_set_readings(int64_t h, int64_t lane0, int64_t count, const double* z) {
     SE_ENTER(h);
-    if (lane0 < 0 || count < 1 || lane0 + count > d->batch || !z) return faile(1, "jg_dcse_set_readings: lanes out of range");
+    if (lane0 < 0 || count < 1 || lane0 + count > d->batch || !z) return api_fail(1, "jg_dcse_set_readings: lanes out of range");
     const size_t m = (size_t)d->m, ld = (size_t)d->ld;
     std::vector<double> t(m * (size_t)count);
     for (size_t s = 0; s < (size_t)count; ++s)
         for (size_t i = 0; i < m; ++i) t[i * count + s] = z[s * m + i];
-    SE_HIP(hipMemcpy2DAsync(d->Z + lane0, ld * sizeof(double), t.data(), (size_t)count * sizeof(double), (size_t)count * sizeof(double), m, hipMemcpyHostToDevice, d->stream));
-    SE_HIP(hipStreamSynchronize(d->stream));
+    DC_API_HIP(hipMemcpy2DAsync(d->Z + lane0, ld * sizeof(double), t.data(), (size_t)count * sizeof(double), (size_t)count * sizeof(double), m, hipMemcpyHostToDevice, d->stream));
+    DC_API_HIP(hipStreamSynchronize(d->stream));
     d->have_z = true; d->solved = false;
     return 0;
 }
 
 int jg_dcse_solve(int64_t h, int correct) {
     SE_ENTER(h);
-    if (!d->have_z) return faile(4, "jg_dcse_solve: jg_dcse_set_readings first");
-    SE_RET(jg::solve_chain(d, correct));
-    SE_HIP(hipStreamSynchronize(d->stream));
+    if (!d->have_z) return api_fail(4, "jg_dcse_solve: jg_dcse_set_readings first");
+    DC_RET(jg::solve_chain(d, correct));
+    DC_API_HIP(hipStreamSynchronize(d->stream));
     d->solved = true;
     return 0;
 }
 
 int jg_dcse_get_angle(int64_t h, double* theta, int32_t* status, double* objective) {
     SE_ENTER(h);
-    if (!d->solved) return faile(4, "jg_dcse_get_angle: jg_dcse_solve first");
+    if (!d->solved) return api_fail(4, "jg_dcse_get_angle: jg_dcse_solve first");
     if (theta) {
-        SE_RET(fetch_lanes(d, d->cur, (size_t)d->n, theta, d->slack_angle));
+        DC_RET(fetch_lanes(d, d->cur, (size_t)d->n, theta, d->slack_angle));
         for (size_t s = 0; s < (size_t)d->batch; ++s)
             if (!d->h_stat[s]) theta[s * d->n + d->slack] = d->slack_angle;
     }
     if (status) for (int s = 0; s < d->batch; ++s) status[s] = d->h_stat[s];
     if (objective) {
-        SE_RET(fetch_lanes(d, d->res, 1, objective, 0.0));
+        DC_RET(fetch_lanes(d, d->res, 1, objective, 0.0));
         for (int s = 0; s < d->batch; ++s) if (d->h_stat[s]) objective[s] = std::nan("");
     }
     return 0;
@@ -611,12 +603,12 @@ int jg_dcse_get_angle(int64_t h, double* theta, int32_t* status, double* objecti
 
 int jg_dcse_residual_test(int64_t h, double threshold, int remove, double* maximum, int32_t* index) {
     SE_ENTER(h);
-    if (!d->solved) return faile(4, "jg_dcse_residual_test: jg_dcse_solve first");
-    if (!maximum || !index) return faile(1, "jg_dcse_residual_test: null pointer");
-    SE_RET(jg::run_test_pass(d, nullptr));
+    if (!d->solved) return api_fail(4, "jg_dcse_residual_test: jg_dcse_solve first");
+    if (!maximum || !index) return api_fail(1, "jg_dcse_residual_test: null pointer");
+    DC_RET(jg::run_test_pass(d, nullptr));
     const size_t ld = (size_t)d->ld;
     std::vector<double> res(3 * ld);
-    SE_HIP(jg::sync_copy(res.data(), d->res, 3 * ld * sizeof(double), hipMemcpyDeviceToHost, d->stream));
+    DC_API_HIP(jg::sync_copy(res.data(), d->res, 3 * ld * sizeof(double), hipMemcpyDeviceToHost, d->stream));
     std::vector<int> rows(ld, -1);
     bool any = false;
     for (int s = 0; s < d->batch; ++s) {
@@ -624,39 +616,39 @@ int jg_dcse_residual_test(int64_t h, double threshold, int remove, double* maxim
         index[s] = d->h_stat[s] ? 0 : (int32_t)res[2 * ld + s];
         if (remove && !d->h_stat[s] && index[s] > 0 && maximum[s] > threshold) { rows[s] = index[s] - 1; any = true; }
     }
-    if (any) SE_RET(jg::remove_rows(d, rows));
+    if (any) DC_RET(jg::remove_rows(d, rows));
     return 0;
 }
 
 int jg_dcse_remove_rows(int64_t h, const int32_t* rows) {
     SE_ENTER(h);
-    if (!rows) return faile(1, "jg_dcse_remove_rows: null pointer");
+    if (!rows) return api_fail(1, "jg_dcse_remove_rows: null pointer");
     std::vector<int> r(d->ld, -1);
     for (int s = 0; s < d->batch; ++s) {
-        if (rows[s] < 0 || rows[s] > d->m) return faile(1, "jg_dcse_remove_rows: row out of range");
+        if (rows[s] < 0 || rows[s] > d->m) return api_fail(1, "jg_dcse_remove_rows: row out of range");
         if (rows[s] == 0 || d->h_stat[s]) continue;
         for (int q = 0; q < d->h_cnt[s]; ++q)
-            if (d->h_rem[(size_t)q * d->ld + s] == rows[s] - 1) return faile(1, "jg_dcse_remove_rows: the lane has removed that row already");
-        if (!d->h_st[rows[s] - 1]) return faile(1, "jg_dcse_remove_rows: the row is out of service");
+            if (d->h_rem[(size_t)q * d->ld + s] == rows[s] - 1) return api_fail(1, "jg_dcse_remove_rows: the lane has removed that row already");
+        if (!d->h_st[rows[s] - 1]) return api_fail(1, "jg_dcse_remove_rows: the row is out of service");
         r[s] = rows[s] - 1;
     }
-    SE_RET(jg::remove_rows(d, r));
+    DC_RET(jg::remove_rows(d, r));
     return 0;
 }
 
 int jg_dcse_get_normalized_residual(int64_t h, double* r) {
     SE_ENTER(h);
-    if (!d->solved) return faile(4, "jg_dcse_get_normalized_residual: jg_dcse_solve first");
-    if (!r) return faile(1, "jg_dcse_get_normalized_residual: null pointer");
-    if (!d->NRM) SE_RET(jg::dev_alloc(d, &d->NRM, (size_t)d->m * d->ld, (const double*)nullptr, true));
-    SE_RET(jg::run_test_pass(d, d->NRM));
-    SE_RET(fetch_lanes(d, d->NRM, (size_t)d->m, r, 0.0));
+    if (!d->solved) return api_fail(4, "jg_dcse_get_normalized_residual: jg_dcse_solve first");
+    if (!r) return api_fail(1, "jg_dcse_get_normalized_residual: null pointer");
+    if (!d->NRM) DC_RET(jg::dev_alloc(d, &d->NRM, (size_t)d->m * d->ld, (const double*)nullptr, true));
+    DC_RET(jg::run_test_pass(d, d->NRM));
+    DC_RET(fetch_lanes(d, d->NRM, (size_t)d->m, r, 0.0));
     return 0;
 }
 
 int jg_dcse_get_removed(int64_t h, int32_t* rows, int32_t* count) {
     SE_ENTER(h);
-    if (!rows || !count) return faile(1, "jg_dcse_get_removed: null pointer");
+    if (!rows || !count) return api_fail(1, "jg_dcse_get_removed: null pointer");
     for (int s = 0; s < d->batch; ++s) {
         count[s] = d->h_cnt[s];
         for (int q = 0; q < jg::DCSE_MAX_REMOVED; ++q) rows[s * jg::DCSE_MAX_REMOVED + q] = q < d->h_cnt[s] ? d->h_rem[(size_t)q * d->ld + s] + 1 : 0;
@@ -666,71 +658,58 @@ int jg_dcse_get_removed(int64_t h, int32_t* rows, int32_t* count) {
 
 int jg_dcse_set_branches(int64_t h, int64_t nbr, const int64_t* from, const int64_t* to, const double* admittance, const double* shift) {
     SE_ENTER(h);
-    if (nbr < 1 || !from || !to || !admittance || !shift) return faile(1, "jg_dcse_set_branches: bad argument");
-    if (d->nbr) return faile(1, "jg_dcse_set_branches: the branch table is already set");
+    if (nbr < 1 || !from || !to || !admittance || !shift) return api_fail(1, "jg_dcse_set_branches: bad argument");
+    if (d->nbr) return api_fail(1, "jg_dcse_set_branches: the branch table is already set");
     std::vector<int> f(nbr), t(nbr);
     for (int64_t k = 0; k < nbr; ++k) {
-        if (from[k] < 1 || from[k] > d->n || to[k] < 1 || to[k] > d->n) return faile(1, "jg_dcse_set_branches: bus index out of range");
+        if (from[k] < 1 || from[k] > d->n || to[k] < 1 || to[k] > d->n) return api_fail(1, "jg_dcse_set_branches: bus index out of range");
         f[k] = (int)from[k] - 1; t[k] = (int)to[k] - 1;
     }
     d->n_fchunks = (int)((nbr + jg::DC_FLOW_BRANCHES - 1) / jg::DC_FLOW_BRANCHES);
-    SE_RET(jg::dev_alloc(d, &d->b_from, (size_t)nbr, f.data()));
-    SE_RET(jg::dev_alloc(d, &d->b_to, (size_t)nbr, t.data()));
-    SE_RET(jg::dev_alloc(d, &d->b_y, (size_t)nbr, admittance));
-    SE_RET(jg::dev_alloc(d, &d->b_shift, (size_t)nbr, shift));
-    SE_RET(jg::dev_alloc(d, &d->fpart, (size_t)d->n_fchunks * 4 * d->ld, (const double*)nullptr, true));
-    SE_RET(jg::dev_alloc(d, &d->flows, (size_t)nbr * d->ld, (const double*)nullptr, true));
-    SE_RET(jg::dev_alloc(d, &d->o_none, (size_t)d->ld, (const int*)nullptr, false));
-    SE_HIP(jg::sync_fill(d->o_none, 0xff, (size_t)d->ld * sizeof(int), d->stream));       // -1: no lane has an outage
+    DC_RET(jg::dev_alloc(d, &d->b_from, (size_t)nbr, f.data()));
+    DC_RET(jg::dev_alloc(d, &d->b_to, (size_t)nbr, t.data()));
+    DC_RET(jg::dev_alloc(d, &d->b_y, (size_t)nbr, admittance));
+    DC_RET(jg::dev_alloc(d, &d->b_shift, (size_t)nbr, shift));
+    DC_RET(jg::dev_alloc(d, &d->fpart, (size_t)d->n_fchunks * 4 * d->ld, (const double*)nullptr, true));
+    DC_RET(jg::dev_alloc(d, &d->flows, (size_t)nbr * d->ld, (const double*)nullptr, true));
+    DC_RET(jg::dev_alloc(d, &d->o_none, (size_t)d->ld, (const int*)nullptr, false));
+    DC_API_HIP(jg::sync_fill(d->o_none, 0xff, (size_t)d->ld * sizeof(int), d->stream));       // -1: no lane has an outage
     d->nbr = (int)nbr;
     return 0;
 }
 
 int jg_dcse_get_flows(int64_t h, double* from) {
     SE_ENTER(h);
-    if (!d->solved) return faile(4, "jg_dcse_get_flows: jg_dcse_solve first");
-    if (!d->nbr) return faile(1, "jg_dcse_get_flows: jg_dcse_set_branches first");
-    if (!from) return faile(1, "jg_dcse_get_flows: null pointer");
+    if (!d->solved) return api_fail(4, "jg_dcse_get_flows: jg_dcse_solve first");
+    if (!d->nbr) return api_fail(1, "jg_dcse_get_flows: jg_dcse_set_branches first");
+    if (!from) return api_fail(1, "jg_dcse_get_flows: null pointer");
     jg::DcFlowArgs f{};
     f.TH = d->cur; f.bf = d->b_from; f.bt = d->b_to; f.by = d->b_y; f.bs = d->b_shift; f.rating = nullptr; f.obr = d->o_none;
     f.flows = d->flows; f.part = d->fpart; f.nbr = d->nbr; f.ld = d->ld;
-    hipLaunchKernelGGL(jg::k_dc_flows<false>, dim3((d->n_fchunks + 3) / 4, d->ld / 64), dim3(64, 4), 0, d->stream, f);
-    SE_HIP(hipGetLastError());
-    SE_RET(fetch_lanes(d, d->flows, (size_t)d->nbr, from, 0.0));
+    jg::launch_dc_flows(f, false, dim3((d->n_fchunks + 3) / 4, d->ld / 64), d->stream);
+    DC_API_HIP(hipGetLastError());
+    DC_RET(fetch_lanes(d, d->flows, (size_t)d->nbr, from, 0.0));
     return 0;
 }
 
 int jg_dcse_time_kernel(int64_t h, int kernel, int reps, double* ms) {
     SE_ENTER(h);
-    if (!ms || reps < 1 || kernel < 0 || kernel > 5) return faile(1, "jg_dcse_time_kernel: bad argument");
-    if (!d->solved) return faile(4, "jg_dcse_time_kernel: jg_dcse_solve first");
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int rc = 0;
-    std::string msg;
-    auto hip = [&](hipError_t e, const char* what) { if (e != hipSuccess && !rc) { rc = 2; msg = std::string(what) + ": " + hipGetErrorString(e); } return e == hipSuccess; };
-    if (hip(hipEventCreate(&e0), "hipEventCreate") && hip(hipEventCreate(&e1), "hipEventCreate"))
-        for (int r = 0; r < reps && !rc; ++r) {
-            if (kernel == 5) d->omega_valid = false;
-            if (!hip(hipEventRecord(e0, d->stream), "hipEventRecord")) break;
-            if (kernel == 0) rc = jg::solve_chain(d, 0);
-            else if (kernel == 1) jg::launch_rhs(d, d->Z);
-            else if (kernel == 2) jg::sweep(d, d->X0);
-            else if (kernel == 3) jg::launch_residual<false, false>(d, d->X0, d->R, nullptr);
-            else rc = jg::run_test_pass(d, nullptr);                       // 4: the normalised pass; 5: the Omega diagonal before it
-            if (rc) { msg = d->error; break; }
-            float t = 0.f;
-            if (!hip(hipEventRecord(e1, d->stream), "hipEventRecord") || !hip(hipEventSynchronize(e1), "hipEventSynchronize") ||
-                !hip(hipEventElapsedTime(&t, e0, e1), "hipEventElapsedTime")) break;
-            ms[r] = (double)t;
-        }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
+    if (!ms || reps < 1 || kernel < 0 || kernel > 5) return api_fail(1, "jg_dcse_time_kernel: bad argument");
+    if (!d->solved) return api_fail(4, "jg_dcse_time_kernel: jg_dcse_solve first");
+    int rc = jg::time_events(d->stream, reps, ms, d->error, [&]() -> int {
+        if (kernel == 5) d->omega_valid = false;
+        if (kernel == 0) return jg::solve_chain(d, 0);
+        if (kernel == 1) jg::launch_rhs(d, d->Z);
+        else if (kernel == 2) jg::sweep(d, d->X0);
+        else if (kernel == 3) jg::launch_residual<false, false>(d, d->X0, d->R, nullptr);
+        else return jg::run_test_pass(d, nullptr);                          // 4: the normalised pass; 5: the Omega diagonal before it
+        return 0;
+    });
     if (!rc && kernel != 0) {                                               // leave the handle as a solve left it
         rc = jg::solve_chain(d, 0);
-        if (rc) msg = d->error;
-        else if (hipStreamSynchronize(d->stream) != hipSuccess) { rc = 2; msg = "hipStreamSynchronize failed"; }
+        if (!rc && hipStreamSynchronize(d->stream) != hipSuccess) { rc = 2; d->error = "hipStreamSynchronize failed"; }
     }
-    return rc ? faile(rc, msg) : 0;
+    return rc ? api_fail(rc, d->error) : 0;
 }
 
 }  // extern "C"

@@ -32,17 +32,11 @@ constexpr int DCSE_OMEGA_LD = 512;      // lanes (= rows of H) per sweep pair of
 // + to wattmeters at 1e-2 and bus PMUs at 1e-5: three decades of room on either side.
 constexpr double DCSE_SINGULAR = 1e-6;
 
-struct DcseHandle {
-    int n = 0, m = 0, batch = 0, ld = 0, device = 0, slack = 0, n_entries = 0, n_fact_levels = 0, nnz_gain = 0, nbr = 0;
+struct DcseHandle : DcDevice {
+    int n = 0, m = 0, batch = 0, ld = 0, slack = 0, nnz_gain = 0, nbr = 0;
     double slack_angle = 0.0;
     long long refactorisations = 0, omega_runs = 0;
-    hipStream_t stream = nullptr;
-    std::string error;
-    // the shared scalar factor of G (jg_dc_sweep.hpp); the tables stay for numeric refactorisations
-    int* perm = nullptr; int* f_ent = nullptr; std::vector<int> f_lev;
-    int* t_ptr = nullptr; int* t_a = nullptr; int* t_d = nullptr; int* t_b = nullptr; int* e_src = nullptr; int* diag = nullptr;
-    double* A = nullptr; double* X = nullptr; double* dinv = nullptr; int* bad = nullptr;
-    DcSweepTables fwd, bwd;
+    DcFactor fac;                                                       // of G (jg_dc_sweep.hpp); the tables stay for numeric refactorisations
     // H by rows (values with status 1), H' by state columns (the slack's list is empty), the terms of every entry of G
     std::vector<int> h_rptr, h_rcol; std::vector<double> h_rval, h_prec; std::vector<int> h_st;
     int* r_ptr = nullptr; int* r_col = nullptr; double* r_val = nullptr;
@@ -67,7 +61,6 @@ struct DcseHandle {
     int* b_from = nullptr; int* b_to = nullptr; double* b_y = nullptr; double* b_shift = nullptr; int* o_none = nullptr;
     double* flows = nullptr; double* fpart = nullptr; int n_fchunks = 0;
     bool solved = false, have_z = false;
-    std::vector<void*> allocs;
 };
 
 }  // namespace jg

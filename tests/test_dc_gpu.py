@@ -356,3 +356,69 @@ def test_one_solve_through_the_plain_c_abi(jg):
     assert st[0] == 0 and R.worst(np.array(th[:]), rth) <= TOL and R.worst(np.array(fr[:]), rfr) <= TOL
     L.jg_dc_destroy(h)
     assert L.jg_dc_solve(C.c_int64(0)) == 1                         # a null token is a bad argument, not a crash
+
+
+def test_a_dc_and_a_dcse_handle_take_turns_in_one_process(jg):
+    """The factorisation and sweep kernels and their launchers are ONE compiled unit (csrc/jg_dc_sweep.hip) that both kinds of handle call.  A DC handle
+    (batch 70: ld 128, the second lane group partial) and a DC state-estimation handle (batch 3) take turns call by call -- DC rhs and outages, DCSE
+    readings, DC solve, DCSE solve, DC screen, DCSE residual test with one removal, DC solve again (and the DCSE solve that applies the removal) -- and
+    every angle, status, screen record and estimate is bit for bit that of equal handles run alone, one after the other.  It fails if the unit keeps any
+    state of its own: a static table, a cached argument block, a shared stream."""
+    from test_dcse_host import bad_data_set, monitoring_of
+    D, E = jg.dcpowerflow, jg.dcstateestimation
+    t = load_case("case14")
+    s = jg.powerSystem(t)
+    labels = np.resize(np.flatnonzero(s.branch.layout.status == 1) + 1, 70)      # every branch in turn, the bridge 7-8 among them (status 3)
+    labels[::9] = 0
+    rating = 0.5 + np.random.default_rng(5).random(s.branch.number)
+    mon = monitoring_of(jg, t, bad_data_set(t)[1])
+
+    def run(taking_turns):
+        dc, se = jg.dcPowerFlow(s, batch=70), jg.dcStateEstimation(mon, batch=3)
+        assert dc.dims()["ld"] == 128 and se.dims()["ld"] == 64
+        z = se.readings.copy()
+        z[2] *= 1.0 + 1e-4 * np.sin(np.arange(z.shape[1]))         # lane 0 exact, lane 2 slightly off: neither reaches the threshold
+        z[1, 1] += 50.0                                            # lane 1: one gross error
+        out = {}
+
+        def dc_set():
+            D.setOutages_(dc, labels)
+            dc._rhs = np.ascontiguousarray(D._base_rhs(s), dtype=np.float64)
+            jg._lib.check(jg._lib.lib().jg_dc_set_rhs(dc._h, dc._rhs))
+
+        def se_set():
+            E.setReadings_(se, z)
+            E._sync(se)
+
+        def dc_solve(key):
+            D.solve_(dc)
+            out[key], out[key + " status"] = dc.voltage.angle.copy(), np.array(dc.status)
+
+        def se_solve(key):
+            E.solve_(se)
+            out[key], out[key + " status"], out[key + " objective"] = se.voltage.angle.copy(), np.array(se.status), np.array(se.objective)
+
+        def dc_screen():
+            out["screen"] = D.screenSummary_(dc, rating)
+
+        def se_test():
+            r = E.residualTest_(se, threshold=3.0)
+            out["maximum"], out["index"] = r.maxNormalizedResidual.copy(), r.index.copy()
+            out["removed"] = np.array([len(rows) for rows in E.removed(se).rows])
+
+        dc_steps = [dc_set, lambda: dc_solve("angle"), dc_screen, lambda: dc_solve("angle again")]
+        se_steps = [se_set, lambda: se_solve("estimate"), se_test, lambda: se_solve("reduced estimate")]
+        steps = [f for pair in zip(dc_steps, se_steps) for f in pair] if taking_turns else dc_steps + se_steps
+        for f in steps:
+            f()
+        dc.close()
+        se.close()
+        return out
+
+    a, b = run(True), run(False)
+    assert sorted(a) == sorted(b) and len(a) == 14
+    for key in a:
+        assert np.array_equal(a[key], b[key], equal_nan=True), key
+    assert np.array_equal(a["removed"], [0, 1, 0]) and np.all(a["estimate status"] == 0) and np.all(a["reduced estimate status"] == 0)
+    assert set(np.unique(a["angle status"])) == {0, 3} and np.array_equal(a["angle"], a["angle again"], equal_nan=True)
+    assert not np.array_equal(a["estimate"][1], a["reduced estimate"][1]) and np.all(np.isfinite(a["screen"][a["angle status"] == 0]))
