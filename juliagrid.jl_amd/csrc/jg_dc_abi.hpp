@@ -1,5 +1,5 @@
 // jg_dc_abi.hpp -- internal: the prologue every extern "C" entry point of the DC files shares (handle cast, null check, hipSetDevice, return through
-// set_last_error, HIP-call check) and the HIP-event timing loop of their *_time_kernel exports.  Codes: 1 bad argument / null handle, 2 HIP error, 4 a call
+// jg::api_fail, HIP-call check -- both from jg_engine.hpp) and the HIP-event timing loop of their *_time_kernel exports.  Codes: 1 bad argument / null handle, 2 HIP error, 4 a call
 // out of order, 5 memory budget.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -10,8 +10,6 @@
 #include "jg_engine.hpp"
 
 namespace jg {
-
-inline int api_fail(int code, const std::string& msg) { set_last_error(msg); return code; }
 
 // `reps` timings of what `enqueue` puts on `stream` (it returns a status; not 0: its text is in `error` already), one pair of HIP events around each.  The
 // first error wins and goes to `error`; the events are destroyed on every path.
@@ -43,4 +41,4 @@ int time_events(hipStream_t stream, int reps, double* ms, std::string& error, F&
 #define DC_ENTER(h) DC_API_ENTER(jg::DcHandle, "null DC handle", h)
 #define SE_ENTER(h) DC_API_ENTER(jg::DcseHandle, "null DC state estimation handle", h)
 #define DC_RET(expr) do { const int rc__ = (expr); if (rc__) return jg::api_fail(rc__, d->error); } while (0)
-#define DC_API_HIP(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) return jg::api_fail(2, std::string(#expr) + ": " + hipGetErrorString(e__)); } while (0)
+#define DC_API_HIP JG_API_HIP

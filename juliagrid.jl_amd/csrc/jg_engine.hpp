@@ -290,6 +290,11 @@ struct Engine {
         }                                                                                 \
     } while (0)
 
+// The error path of every extern "C" entry point: the text goes behind jg_last_error(), the code back to the caller.  JG_API_HIP: a HIP call in a function
+// that returns such a code (2 = HIP error).
+inline int api_fail(int code, const std::string& msg) { set_last_error(msg); return code; }
+#define JG_API_HIP(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) return jg::api_fail(2, std::string(#expr) + ": " + hipGetErrorString(e__)); } while (0)
+
 // Blocking copies / fills on the HANDLE's stream, never on the legacy stream: handles are driven from several host
 // threads (ContingencyPipeline), and a legacy-stream operation issued while another thread captures its graphs fails
 // ("would make the legacy stream depend on a capturing blocking stream").

@@ -26,24 +26,17 @@
 #include <map>
 #include <set>
 #include <string>
-#include <thread>
-#include <chrono>
 #include <vector>
 
 #include "../../include/jgrid.h"
 #include "jg_engine.hpp"
+#include "jg_lanes.hpp"
 
 namespace {
 
-int failg(int code, const std::string& msg) { jg::set_last_error(msg); return code; }
-
-#define GN_HIP(expr)                                                                    \
-    do {                                                                                \
-        hipError_t err__ = (expr);                                                      \
-        if (err__ != hipSuccess) return failg(2, std::string(#expr) + ": " + hipGetErrorString(err__)); \
-    } while (0)
-
-__device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+int failg(int code, const std::string& msg) { return jg::api_fail(code, msg); }
+#define GN_HIP JG_API_HIP
+using jg::uniform;
 
 struct RowDesc { int type; int idx; int slot0; int nslots; };      // idx: bus or branch (0-based)
 struct BranchP { double g, b, gs, bs, tinv, shift; int from, to; double pad; };   // 64 bytes
@@ -529,22 +522,7 @@ __global__ __launch_bounds__(64) void k_gn_obj_final(const double* part, int chu
     }
     obj[b] = acc;
 }
-// [n][ld] rows -> the scenario-major record (the transpose kernel of the power-flow record, jg_nr.hip: k_pack_bus): z = 0 magnitudes, 1 angles
-__global__ __launch_bounds__(512) void k_gn_pack_bus(const double* vm, const double* va, double* dst, int n, int ld, int batch, long long stride) {
-    __shared__ double tile[64][65];
-    const double* src = blockIdx.z ? va : vm;
-    const int off = blockIdx.z ? n : 0;
-    const int i0 = blockIdx.x * 64, b0 = blockIdx.y * 64;
-    for (int r = threadIdx.y; r < 64; r += blockDim.y) {
-        const int i = i0 + r, b = b0 + threadIdx.x;
-        tile[r][threadIdx.x] = (i < n && b < ld) ? src[(size_t)i * ld + b] : 0.0;
-    }
-    __syncthreads();
-    for (int r = threadIdx.y; r < 64; r += blockDim.y) {
-        const int b = b0 + r, i = i0 + threadIdx.x;
-        if (b < batch && i < n) dst[(size_t)b * stride + off + i] = tile[threadIdx.x][r];
-    }
-}
+// the columns of the scenario-major result record behind V | theta (jg::Lanes::collect2)
 __global__ void k_gn_pack_tail(const int* iters, const int* status, const double* obj, double* dst, int batch, long long stride, int off) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b < batch) { double* q = dst + (size_t)b * stride + off; q[0] = (double)iters[b]; q[1] = (double)status[b]; q[2] = obj[b]; }
@@ -678,8 +656,8 @@ __global__ void k_gn_add_iter(int* iters, int n) {
 
 }  // namespace
 
-struct jg_gn {
-    int n = 0, nnzY = 0, nb = 0, m = 0, batch = 0, ld = 0, device = 0, slack0 = 0, nslots = 0, ncorr = 0, nchunk = 0;
+struct jg_gn : jg::Lanes {             // Lanes: stream, batch, ld, the staging buffer of put_rows / get_rows, the pinned verdict word and the wait for it
+    int n = 0, nnzY = 0, nb = 0, m = 0, device = 0, slack0 = 0, nslots = 0, ncorr = 0, nchunk = 0;
     int64_t nnzH = 0;
     std::vector<int64_t> hcolptr, hrowval;      // reference CSC pattern of H (1-based)
     std::vector<int64_t> hmap;                  // CSC nz -> slot*2 + comp
@@ -707,12 +685,8 @@ struct jg_gn {
     NoiseDev* d_noise = nullptr; int n_noise = 0; int* d_noise_bad = nullptr;   // raw readings per device (jg_gn_set_readings)
     double* d_obj = nullptr; double* d_objpart = nullptr; int* d_corr = nullptr; int obj_chunks = 0;   // objective per scenario (first use: jg_gn_get_objective / jg_gn_pack_results_device)
     bool ran = false;                                   // d_iters / d_status hold the verdicts of a stateEstimation! run
-    double wait_us = 0.0;                               // running mean of the host's waits for an iteration's verdict (jg_gn_run: polls while this is short)
-    double* d_stage = nullptr; size_t stage_bytes = 0;  // rows on their way up or down (put_rows / get_rows)
     jg::Engine eng;
-    hipStream_t stream = nullptr;
     hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
-    int* h_counter = nullptr;
 };
 
 namespace {
@@ -763,77 +737,6 @@ void launch_check(jg_gn* h, int mode) {
 
 void launch_update(jg_gn* h, const int* active) {
     hipLaunchKernelGGL(k_gn_update, dim3(h->nchunk, h->ld / 64), dim3(64, 4), 0, h->stream, h->d_inc, h->d_vm, h->d_va, active, h->n, h->ld);
-}
-
-// host [batch][rows] (stride = rows) or ONE [rows] for every scenario (stride 0) -> device [rows][ld]; lanes beyond the batch repeat the last scenario.
-// The rows go up as the host holds them and a kernel spreads them over the lanes (round 5: the host-side transposition that used to happen here wrote
-// 96 723 x 512 doubles with a stride of 4 KB and uploaded 396 MB even for one shared column -- 0.95 of the 1.4 s a Gauss-Newton handle of config 4 took to build).
-__global__ __launch_bounds__(512) void k_gn_spread_rows(const double* src, double* dst, int rows, int ld, int batch, int src_rows) {
-    __shared__ double tile[64][65];
-    const int i0 = blockIdx.x * 64, b0 = blockIdx.y * 64;
-    for (int r = threadIdx.y; r < 64; r += blockDim.y) {
-        const int b = min(min(b0 + r, batch - 1), src_rows - 1), i = i0 + threadIdx.x;
-        tile[r][threadIdx.x] = i < rows ? src[(size_t)b * rows + i] : 0.0;
-    }
-    __syncthreads();
-    for (int r = threadIdx.y; r < 64; r += blockDim.y) {
-        const int i = i0 + r, b = b0 + threadIdx.x;
-        if (i < rows && b < ld) dst[(size_t)i * ld + b] = tile[threadIdx.x][r];
-    }
-}
-// device [rows][ld] -> device [batch][rows] (what the host receives)
-__global__ __launch_bounds__(512) void k_gn_collect_rows(const double* src, double* dst, int rows, int ld, int batch) {
-    __shared__ double tile[64][65];
-    const int i0 = blockIdx.x * 64, b0 = blockIdx.y * 64;
-    for (int r = threadIdx.y; r < 64; r += blockDim.y) {
-        const int i = i0 + r, b = b0 + threadIdx.x;
-        tile[r][threadIdx.x] = (i < rows && b < ld) ? src[(size_t)i * ld + b] : 0.0;
-    }
-    __syncthreads();
-    for (int r = threadIdx.y; r < 64; r += blockDim.y) {
-        const int b = b0 + r, i = i0 + threadIdx.x;
-        if (b < batch && i < rows) dst[(size_t)b * rows + i] = tile[threadIdx.x][r];
-    }
-}
-
-// the staging area of a handle for rows on their way up or down: grows, is never freed before the handle (a hipFree per call would synchronise the device -- while
-// another host thread of a pipeline may be capturing its hipGraph)
-int stage_room(jg_gn* h, size_t bytes) {
-    if (bytes <= h->stage_bytes) return 0;
-    GN_HIP(hipStreamSynchronize(h->stream));
-    hipFree(h->d_stage); h->d_stage = nullptr; h->stage_bytes = 0;
-    GN_HIP(hipMalloc((void**)&h->d_stage, bytes));
-    h->stage_bytes = bytes;
-    return 0;
-}
-
-int put_rows(jg_gn* h, double* dst, const double* src, int64_t stride, int rows) {
-    if (stride != 0 && stride != rows) {                         // a caller's own row pitch: the general (slow) way
-        std::vector<double> t((size_t)rows * h->ld, 0.0);
-        for (int b = 0; b < h->ld; ++b) {
-            const double* s = src + (size_t)(b < h->batch ? b : h->batch - 1) * (size_t)stride;
-            for (int i = 0; i < rows; ++i) t[(size_t)i * h->ld + b] = s[i];
-        }
-        GN_HIP(jg::sync_copy(dst, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        return 0;
-    }
-    const int src_rows = stride == 0 ? 1 : h->batch;
-    const size_t bytes = (size_t)src_rows * rows * sizeof(double);
-    if (int rc = stage_room(h, bytes)) return rc;
-    GN_HIP(jg::sync_copy(h->d_stage, src, bytes, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_gn_spread_rows, dim3((rows + 63) / 64, h->ld / 64), dim3(64, 8), 0, h->stream, (const double*)h->d_stage, dst, rows, h->ld, h->batch, src_rows);
-    GN_HIP(hipGetLastError());
-    GN_HIP(hipStreamSynchronize(h->stream));
-    return 0;
-}
-
-int get_rows(jg_gn* h, const double* src, double* dst, size_t rows) {
-    const size_t bytes = (size_t)h->batch * rows * sizeof(double);
-    if (int rc = stage_room(h, bytes)) return rc;
-    hipLaunchKernelGGL(k_gn_collect_rows, dim3((unsigned)((rows + 63) / 64), h->ld / 64), dim3(64, 8), 0, h->stream, src, h->d_stage, (int)rows, h->ld, h->batch);
-    GN_HIP(hipGetLastError());
-    GN_HIP(jg::sync_copy(dst, h->d_stage, bytes, hipMemcpyDeviceToHost, h->stream));
-    return 0;
 }
 
 }  // namespace
@@ -1154,10 +1057,10 @@ int jg_gn_set_measurement(jg_gn* h, const double* mean, const double* wdiag, con
     if (!h || !mean || !wdiag || (h->ncorr > 0 && !woff)) return failg(1, "jg_gn_set_measurement: bad argument");
     if (int rc = set_device(h)) return rc;
     GN_HIP(hipStreamSynchronize(h->stream));
-    if (int rc = put_rows(h, h->d_mean, mean, batch_stride_m, h->m)) return rc;
-    if (int rc = put_rows(h, h->d_w, wdiag, batch_stride_m, h->m)) return rc;
+    if (int rc = h->put_rows(h->d_mean, mean, batch_stride_m, h->m)) return rc;
+    if (int rc = h->put_rows(h->d_w, wdiag, batch_stride_m, h->m)) return rc;
     if (h->ncorr > 0)
-        if (int rc = put_rows(h, h->d_w + (size_t)h->m * h->ld, woff, batch_stride_corr, h->ncorr)) return rc;
+        if (int rc = h->put_rows(h->d_w + (size_t)h->m * h->ld, woff, batch_stride_corr, h->ncorr)) return rc;
     return 0;
 }
 
@@ -1206,9 +1109,9 @@ int jg_gn_get_measurement(jg_gn* h, double* mean, double* wdiag, double* woff) {
     if (!h || !mean || !wdiag) return failg(1, "jg_gn_get_measurement: bad argument");
     if (int rc = set_device(h)) return rc;
     GN_HIP(hipStreamSynchronize(h->stream));
-    if (int rc = get_rows(h, h->d_mean, mean, h->m)) return rc;
-    if (int rc = get_rows(h, h->d_w, wdiag, h->m)) return rc;
-    if (woff && h->ncorr > 0) return get_rows(h, h->d_w + (size_t)h->m * h->ld, woff, h->ncorr);
+    if (int rc = h->get_rows(h->d_mean, mean, h->m)) return rc;
+    if (int rc = h->get_rows(h->d_w, wdiag, h->m)) return rc;
+    if (woff && h->ncorr > 0) return h->get_rows(h->d_w + (size_t)h->m * h->ld, woff, h->ncorr);
     return 0;
 }
 
@@ -1216,36 +1119,28 @@ int jg_gn_set_voltage(jg_gn* h, const double* vm, const double* va, int64_t stri
     if (!h || !vm || !va) return failg(1, "jg_gn_set_voltage: bad argument");
     if (int rc = set_device(h)) return rc;
     GN_HIP(hipStreamSynchronize(h->stream));
-    if (int rc = put_rows(h, h->d_vm, vm, stride, h->n)) return rc;
-    return put_rows(h, h->d_va, va, stride, h->n);
+    if (int rc = h->put_rows(h->d_vm, vm, stride, h->n)) return rc;
+    return h->put_rows(h->d_va, va, stride, h->n);
 }
 
 int jg_gn_snapshot_voltage(jg_gn* h) {
     if (!h) return failg(1, "jg_gn_snapshot_voltage: bad argument");
     if (int rc = set_device(h)) return rc;
-    const size_t bytes = (size_t)h->n * h->ld * 8;
-    if (!h->d_vm0) { GN_HIP(hipMalloc((void**)&h->d_vm0, bytes)); GN_HIP(hipMalloc((void**)&h->d_va0, bytes)); }
-    GN_HIP(hipMemcpyAsync(h->d_vm0, h->d_vm, bytes, hipMemcpyDeviceToDevice, h->stream));
-    GN_HIP(hipMemcpyAsync(h->d_va0, h->d_va, bytes, hipMemcpyDeviceToDevice, h->stream));
-    GN_HIP(hipStreamSynchronize(h->stream));
-    return 0;
+    return h->snapshot(h->d_vm, h->d_va, &h->d_vm0, &h->d_va0, h->n);
 }
 
 int jg_gn_restore_voltage(jg_gn* h) {
     if (!h || !h->d_vm0) return failg(1, "jg_gn_restore_voltage: no snapshot");
     if (int rc = set_device(h)) return rc;
-    const size_t bytes = (size_t)h->n * h->ld * 8;
-    GN_HIP(hipMemcpyAsync(h->d_vm, h->d_vm0, bytes, hipMemcpyDeviceToDevice, h->stream));
-    GN_HIP(hipMemcpyAsync(h->d_va, h->d_va0, bytes, hipMemcpyDeviceToDevice, h->stream));
-    return 0;
+    return h->restore(h->d_vm, h->d_va, h->d_vm0, h->d_va0, h->n);
 }
 
 int jg_gn_get_voltage(jg_gn* h, double* vm, double* va) {
     if (!h || !vm || !va) return failg(1, "jg_gn_get_voltage: bad argument");
     if (int rc = set_device(h)) return rc;
     GN_HIP(hipStreamSynchronize(h->stream));
-    if (int rc = get_rows(h, h->d_vm, vm, h->n)) return rc;
-    return get_rows(h, h->d_va, va, h->n);
+    if (int rc = h->get_rows(h->d_vm, vm, h->n)) return rc;
+    return h->get_rows(h->d_va, va, h->n);
 }
 
 int jg_gn_increment(jg_gn* h, double* maxinc) {
@@ -1298,31 +1193,10 @@ int jg_gn_run(jg_gn* h, int64_t max_iter, double tol, int32_t* iters, int32_t* s
     GN_HIP(hipMemsetAsync(h->d_iters, 0, (size_t)h->ld * 4, h->stream));          // acStateEstimation.jl:1298
     GN_HIP(hipMemsetAsync(h->eng.status, 0, (size_t)h->ld * 4, h->stream));
     GN_HIP(hipMemsetAsync(h->d_group, 0xff, (size_t)(h->ld / 64) * sizeof(int), h->stream));
-    // (round 5, as jg_nr_run: while the handle's iterations are SHORT the host arms the pinned word and polls it instead of paying a stream synchronise per
-    // iteration; a long iteration -- config 4 at 512 lanes: 4.4 ms -- blocks as before, see wait_verdict in jg_nr.hip.  JG_POLL=0 switches polling off)
-    static const bool poll = jg::knob("POLL", 1) != 0;
     for (int64_t it = 0; it <= max_iter; ++it) {                                   // :1303
-        const bool spin = poll && h->wait_us <= 800.0;
-        if (spin) *(volatile int*)h->h_counter = -1;
+        h->arm();                                                                  // the verdict lands in the pinned word: polled while the iterations are short (jg_lanes.hpp)
         GN_HIP(hipGraphLaunch(h->exec, h->stream));
-        const auto t0 = std::chrono::steady_clock::now();
-        auto elapsed = [&] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); };
-        bool block = !spin;
-        if (spin) {
-            volatile int* w = (volatile int*)h->h_counter;
-            for (long spins = 0; *w == -1; ++spins) {
-                if ((spins & 63) == 63) {
-                    const double us = elapsed();
-                    if (us > 2.0e6) { block = true; break; }
-                    if (us > 1600.0) std::this_thread::yield();
-                }
-#if defined(__x86_64__)
-                __builtin_ia32_pause();
-#endif
-            }
-        }
-        if (block) GN_HIP(hipStreamSynchronize(h->stream));
-        h->wait_us = 0.5 * h->wait_us + 0.5 * elapsed();
+        GN_HIP(h->wait());
         if (*h->h_counter == 0) break;
     }
     GN_HIP(hipStreamSynchronize(h->stream));
@@ -1351,7 +1225,7 @@ int launch_objective(jg_gn* h) {
 int launch_pack(jg_gn* h, double* dst) {
     if (int rc = launch_objective(h)) return rc;
     const long long stride = 2LL * h->n + 3;
-    hipLaunchKernelGGL(k_gn_pack_bus, dim3((h->n + 63) / 64, (h->ld + 63) / 64, 2), dim3(64, 8), 0, h->stream, h->d_vm, h->d_va, dst, h->n, h->ld, h->batch, stride);
+    h->collect2(h->d_vm, h->d_va, dst, h->n, stride);
     hipLaunchKernelGGL(k_gn_pack_tail, dim3((h->batch + 255) / 256), dim3(256), 0, h->stream, h->d_iters, h->d_status, h->d_obj, dst, h->batch, stride, 2 * h->n);
     GN_HIP(hipGetLastError());
     return 0;
@@ -1411,19 +1285,19 @@ int jg_gn_get_residual(jg_gn* h, double* res) {
     if (!h || !res) return failg(1, "jg_gn_get_residual: bad argument");
     if (int rc = set_device(h)) return rc;
     GN_HIP(hipStreamSynchronize(h->stream));
-    return get_rows(h, h->d_res, res, h->m);
+    return h->get_rows(h->d_res, res, h->m);
 }
 
 int jg_gn_get_increment(jg_gn* h, double* inc) {
     if (!h || !inc) return failg(1, "jg_gn_get_increment: bad argument");
     if (int rc = set_device(h)) return rc;
     GN_HIP(hipStreamSynchronize(h->stream));
-    std::vector<double> t((size_t)h->n * 2 * h->ld);                               // device [n][ld][2]
-    GN_HIP(jg::sync_copy(t.data(), h->d_inc, t.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    std::vector<double> t((size_t)h->batch * h->n * 2);                            // [batch][n][2]
+    if (int rc = h->get_rows2(h->d_inc, t.data(), h->n)) return rc;
     for (int b = 0; b < h->batch; ++b)                                             // [theta_1..n, V_1..n] like se.increment
         for (int i = 0; i < h->n; ++i) {
-            inc[(size_t)b * 2 * h->n + i] = t[((size_t)i * h->ld + b) * 2];
-            inc[(size_t)b * 2 * h->n + h->n + i] = t[((size_t)i * h->ld + b) * 2 + 1];
+            inc[(size_t)b * 2 * h->n + i] = t[((size_t)b * h->n + i) * 2];
+            inc[(size_t)b * 2 * h->n + h->n + i] = t[((size_t)b * h->n + i) * 2 + 1];
         }
     return 0;
 }
@@ -1524,7 +1398,7 @@ int jg_gn_get_normalized_residual(jg_gn* h, double* nres) {
     if (!h || !nres) return failg(1, "jg_gn_get_normalized_residual: bad argument");
     if (!h->d_nres) return failg(1, "jg_gn_get_normalized_residual: call jg_gn_residual_test first");
     if (int rc = set_device(h)) return rc;
-    return get_rows(h, h->d_nres, nres, h->m);
+    return h->get_rows(h->d_nres, nres, h->m);
 }
 
 int jg_gn_time_kernel(jg_gn* h, int kernel, int reps, double* mean_ms) {

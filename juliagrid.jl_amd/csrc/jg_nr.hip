@@ -31,19 +31,16 @@
 #include "../../include/jgrid.h"
 #include "jg_engine.hpp"
 #include "jg_comp.hpp"
+#include "jg_lanes.hpp"
 #include "jg_qlim.hpp"
 
 namespace {
 
 thread_local std::string g_error;
 
-int fail(int code, const std::string& msg) { g_error = msg; return code; }
-
-#define NR_HIP(expr)                                                                   \
-    do {                                                                               \
-        hipError_t err__ = (expr);                                                     \
-        if (err__ != hipSuccess) return fail(2, std::string(#expr) + ": " + hipGetErrorString(err__)); \
-    } while (0)
+int fail(int code, const std::string& msg) { return jg::api_fail(code, msg); }
+#define NR_HIP JG_API_HIP
+using jg::uniform;
 
 constexpr int ASM_ROWS = 16;   // bus rows per workgroup
 constexpr int ASM_WAVES = 4;
@@ -68,7 +65,6 @@ struct AsmArgs {
 // The type of bus i in the lane whose word of row i / 32 is w (2 bits per bus: 1 PQ, 2 PV, 3 slack)
 __device__ __forceinline__ int lane_type(unsigned long long w, int i) { return (int)((w >> ((i & 31) * 2)) & 3ull); }
 
-__device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ void store_vec_nt(double* base, size_t item, size_t b, size_t ld, double v0, double v1) {
     typedef double d2 __attribute__((ext_vector_type(2)));
     __builtin_nontemporal_store(d2{v0, v1}, (d2*)(base + (item * ld + b) * 2));
@@ -815,7 +811,8 @@ __global__ __launch_bounds__(1024) void k_lanes_permute(LaneSet s, const int* de
     }
 }
 
-// [n][ld] batch-minor -> [batch][n] scenario-major, tiled through LDS so both sides stay coalesced
+// [n][ld] batch-minor -> [batch][n] scenario-major, tiled through LDS so both sides stay coalesced.  What jg::Lanes::collect does on 64 x 64 tiles; kept for
+// jg_nr_get_voltage_device until the two have been timed against each other on that call (10k-bus grid, 512 lanes).
 __global__ void k_to_scenario_major(const double* src, double* dst, int n, int ld, int batch) {
     __shared__ double tile[32][33];
     const int i0 = blockIdx.x * 32, b0 = blockIdx.y * 32;
@@ -830,24 +827,8 @@ __global__ void k_to_scenario_major(const double* src, double* dst, int n, int l
     }
 }
 
-// [n][ld] batch-minor -> column block `off` of a scenario-major result record [batch][stride] (the packed result of a batch:
-// V | theta | iterations | status per scenario, one buffer for the one gather of a sharded run)
-// (64 x 64 tiles: a wave reads and writes 512 contiguous bytes; both arrays of a record in one launch, blockIdx.z)
-__global__ __launch_bounds__(512) void k_pack_bus(const double* vm, const double* va, double* dst, int n, int ld, int batch, long long stride) {
-    __shared__ double tile[64][65];
-    const double* src = blockIdx.z ? va : vm;
-    const int off = blockIdx.z ? n : 0;
-    const int i0 = blockIdx.x * 64, b0 = blockIdx.y * 64;
-    for (int r = threadIdx.y; r < 64; r += blockDim.y) {
-        const int i = i0 + r, b = b0 + threadIdx.x;
-        tile[r][threadIdx.x] = (i < n && b < ld) ? src[(size_t)i * ld + b] : 0.0;
-    }
-    __syncthreads();
-    for (int r = threadIdx.y; r < 64; r += blockDim.y) {
-        const int b = b0 + r, i = i0 + threadIdx.x;
-        if (b < batch && i < n) dst[(size_t)b * stride + off + i] = tile[threadIdx.x][r];
-    }
-}
+// The packed result of a batch is a scenario-major record [batch][stride]: V | theta | iterations | status per scenario, one buffer for the one gather of a
+// sharded run.  V | theta: jg::Lanes::collect2; the two columns behind them:
 __global__ void k_pack_tail(const int* iters, const int* status, double* dst, int batch, long long stride, int off) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b < batch) { dst[(size_t)b * stride + off] = (double)iters[b]; dst[(size_t)b * stride + off + 1] = (double)status[b]; }
@@ -917,8 +898,8 @@ namespace jg {
 void set_last_error(const std::string& msg) { g_error = msg; }
 }
 
-struct jg_nr {
-    int n = 0, nnz = 0, batch = 0, ld = 0, mp = 0, device = 0, nchunk = 0;
+struct jg_nr : jg::Lanes {             // Lanes: stream, batch, ld, the staging buffer of put_rows / get_rows, the pinned verdict word and the wait for it
+    int n = 0, nnz = 0, mp = 0, device = 0, nchunk = 0;
     int64_t dimJ = 0, nnzJ = 0, slack = 0;
     std::vector<int64_t> colptr, rowval, pq, pvpq, pcount, jcolptr, jrowval;
     std::vector<int8_t> type;
@@ -931,7 +912,6 @@ struct jg_nr {
     double* d_vm = nullptr; double* d_va = nullptr; double* d_p = nullptr; double* d_q = nullptr;
     int* d_ppos = nullptr; double* d_pdg = nullptr; double* d_pdb = nullptr;
     int* d_dst = nullptr; double* d_F = nullptr; double* d_inc = nullptr; double* d_part = nullptr;
-    double* d_stage = nullptr; size_t stage_bytes = 0;           // host rows on their way to a [n][ld] array (put_bus_array)
     double* d_normp = nullptr; double* d_normq = nullptr; double* d_params = nullptr;
     double* d_vm0 = nullptr; double* d_va0 = nullptr;   // snapshot of the start point
     int* d_active = nullptr; int* d_iters = nullptr; int* d_status = nullptr; int* d_counter = nullptr; int* d_group = nullptr;
@@ -950,7 +930,6 @@ struct jg_nr {
     double* d_post = nullptr; size_t post_bytes = 0;  // staging for branch / bus quantities, grown on demand
     double* d_rating = nullptr; double* d_screen = nullptr; double* d_screc = nullptr;   // contingency screen: ratings [nb], partial maxima, the record [batch][10]
     jg::Engine eng;
-    hipStream_t stream = nullptr;
     hipGraph_t graphA = nullptr, graphB = nullptr, graphBm = nullptr, graphJ = nullptr;
     hipGraphExec_t execA = nullptr, execB = nullptr, execBm = nullptr, execJ = nullptr;   // Bm / J: an iteration whose verdict assembles NO Jacobian / the Jacobian alone (run_loop)
     hipGraph_t graphM = nullptr; hipGraphExec_t execM = nullptr; int m_iters = 0;          // ONE scenario: a whole solve of m_iters iterations as one graph (run_whole)
@@ -963,10 +942,8 @@ struct jg_nr {
     int* d_move = nullptr;           // straggler hand-off: map[64] | home[64] | count[1] | source lane[64] (device), home/count mirrored in h_move (pinned)
     int* h_move = nullptr;
     double host_launch_us = 0.0, host_wait_us = 0.0; long long host_iters = 0;   // JG_HOST_TIMING=1: what the host spent in hipGraphLaunch / waiting per iteration of run_loop
-    double wait_us = 0.0;            // how long the host waited for the last verdicts (running mean; wait_verdict: polls the pinned word while this is short)
     bool res_pinned = false;         // this run's verdicts write iterations | status behind the pinned verdict word (one lane group; run_finish)
-    int* h_counter = nullptr;        // pinned (129 ints: the verdict word, then iterations [64] | status [64] of a handle of one lane group)
-    int* h_counter_dev = nullptr;    // its device alias
+    int* h_counter_dev = nullptr;    // device alias of h_counter (pinned, 129 ints: the verdict word, then iterations [64] | status [64] of a handle of one lane group)
     // ---- first iteration on a shared factor (jg_comp.hpp; jg_nr_attach_base) ----
     std::vector<int> csr_row, csr_col;                // Ybus row-CSR position -> (row, column)
     jg_nr_base* base = nullptr;                       // the base case this handle's scenarios start from (nullptr: none attached)
@@ -1170,50 +1147,6 @@ void launch_check(jg_nr* h, int mode, const int* group = nullptr) {
     CheckArgs c{h->d_part, h->nchunk, h->ld, h->batch, h->d_params, h->d_normp, h->d_normq, h->d_active,
                 h->d_iters, h->d_status, h->eng.status, h->d_counter, group, mode};
     hipLaunchKernelGGL(k_check, dim3(h->ld / 64), dim3(64, 16), 0, h->stream, c);
-}
-
-// host [batch][n] (or one [n] broadcast) -> device [n][ld]
-// [rows][n] (scenario-major, as the host hands it over; rows = 1: one row for every scenario) -> dst [n][ld]; lanes beyond the batch
-// repeat the last scenario.  64 x 64 tiles through LDS: contiguous reads along the bus index, contiguous writes along the lanes.
-__global__ __launch_bounds__(512) void k_spread_bus(const double* src, double* dst, int n, int ld, int batch, int rows) {
-    __shared__ double tile[64][65];
-    const int i0 = blockIdx.x * 64, b0 = blockIdx.y * 64;
-    for (int r = threadIdx.y; r < 64; r += blockDim.y) {
-        const int b = min(min(b0 + r, batch - 1), rows - 1), i = i0 + threadIdx.x;
-        tile[r][threadIdx.x] = i < n ? src[(size_t)b * n + i] : 0.0;
-    }
-    __syncthreads();
-    for (int r = threadIdx.y; r < 64; r += blockDim.y) {
-        const int i = i0 + r, b = b0 + threadIdx.x;
-        if (i < n && b < ld) dst[(size_t)i * ld + b] = tile[threadIdx.x][r];
-    }
-}
-
-// host [batch][n] (stride n) or [n] (stride 0: every scenario the same) -> device [n][ld].  The rows go up as they are (80 KB for one row
-// of a 10 000-bus grid; the host-side transposition to [n][ld] that used to happen here moved 5 MB per array even for one scenario) and
-// a kernel spreads them over the lanes.
-int put_bus_array(jg_nr* h, double* dst, const double* src, int64_t stride) {
-    const int rows = stride == 0 ? 1 : h->batch;
-    if (stride != 0 && stride != h->n) {                         // a caller's own row pitch: the general (slow) way
-        std::vector<double> t((size_t)h->n * h->ld, 0.0);
-        for (int b = 0; b < h->ld; ++b) {
-            const double* s = src + (size_t)(b < h->batch ? b : h->batch - 1) * (size_t)stride;   // pad with last scenario
-            for (int i = 0; i < h->n; ++i) t[(size_t)i * h->ld + b] = s[i];
-        }
-        NR_HIP(jg::sync_copy(dst, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        return 0;
-    }
-    const size_t need = (size_t)rows * h->n * sizeof(double);
-    if (need > h->stage_bytes) {
-        hipFree(h->d_stage); h->d_stage = nullptr; h->stage_bytes = 0;
-        NR_HIP(hipMalloc((void**)&h->d_stage, need));
-        h->stage_bytes = need;
-    }
-    NR_HIP(hipMemcpyAsync(h->d_stage, src, need, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_spread_bus, dim3((h->n + 63) / 64, h->ld / 64), dim3(64, 8), 0, h->stream, (const double*)h->d_stage, dst, h->n, h->ld, h->batch, rows);
-    NR_HIP(hipGetLastError());
-    NR_HIP(hipStreamSynchronize(h->stream));
-    return 0;
 }
 
 // pack the active scenarios into the leading lanes (restore = 1: send every lane back home)
@@ -1764,8 +1697,8 @@ int jg_nr_set_injection(jg_nr* h, const double* p, const double* q, int64_t stri
     if (!h || !p || !q || stride < 0) return fail(1, "jg_nr_set_injection: bad argument");
     if (int rc = set_device(h)) return rc;
     NR_HIP(hipStreamSynchronize(h->stream));
-    if (int rc = put_bus_array(h, h->d_p, p, stride)) return rc;
-    if (int rc = put_bus_array(h, h->d_q, q, stride)) return rc;
+    if (int rc = h->put_rows(h->d_p, p, stride, h->n)) return rc;
+    if (int rc = h->put_rows(h->d_q, q, stride, h->n)) return rc;
     h->jac_valid = false;
     h->inj_checked = false;                                      // compared with the base's again before the next compensated start
     return 0;
@@ -1775,48 +1708,10 @@ int jg_nr_set_voltage(jg_nr* h, const double* vm, const double* va, int64_t stri
     if (!h || !vm || !va || stride < 0) return fail(1, "jg_nr_set_voltage: bad argument");
     if (int rc = set_device(h)) return rc;
     NR_HIP(hipStreamSynchronize(h->stream));
-    if (int rc = put_bus_array(h, h->d_vm, vm, stride)) return rc;
-    if (int rc = put_bus_array(h, h->d_va, va, stride)) return rc;
+    if (int rc = h->put_rows(h->d_vm, vm, stride, h->n)) return rc;
+    if (int rc = h->put_rows(h->d_va, va, stride, h->n)) return rc;
     h->jac_valid = false;
     h->start_is_base = false;
-    return 0;
-}
-
-// device [n][ld] -> device [batch][n] (64 x 64 tiles: contiguous on both sides)
-__global__ __launch_bounds__(512) void k_gather_bus(const double* src, double* dst, int n, int ld, int batch) {
-    __shared__ double tile[64][65];
-    const int i0 = blockIdx.x * 64, b0 = blockIdx.y * 64;
-    for (int r = threadIdx.y; r < 64; r += blockDim.y) {
-        const int i = i0 + r, b = b0 + threadIdx.x;
-        tile[r][threadIdx.x] = (i < n && b < ld) ? src[(size_t)i * ld + b] : 0.0;
-    }
-    __syncthreads();
-    for (int r = threadIdx.y; r < 64; r += blockDim.y) {
-        const int b = b0 + r, i = i0 + threadIdx.x;
-        if (b < batch && i < n) dst[(size_t)b * n + i] = tile[threadIdx.x][r];
-    }
-}
-
-static int get_bus_array(jg_nr* h, const double* src, double* dst, int comps) {
-    // device [n][ld][comps] -> host [batch][n*comps]
-    if (comps == 1) {                                            // transposed on the device, then ONE copy of exactly the rows asked for
-        const size_t need = (size_t)h->batch * h->n * sizeof(double);
-        if (need > h->stage_bytes) {
-            hipFree(h->d_stage); h->d_stage = nullptr; h->stage_bytes = 0;
-            NR_HIP(hipMalloc((void**)&h->d_stage, need));
-            h->stage_bytes = need;
-        }
-        hipLaunchKernelGGL(k_gather_bus, dim3((h->n + 63) / 64, h->ld / 64), dim3(64, 8), 0, h->stream, src, h->d_stage, h->n, h->ld, h->batch);
-        NR_HIP(hipGetLastError());
-        NR_HIP(jg::sync_copy(dst, h->d_stage, need, hipMemcpyDeviceToHost, h->stream));
-        return 0;
-    }
-    const size_t rows = (size_t)h->n * comps;
-    std::vector<double> t(rows * h->ld);
-    NR_HIP(jg::sync_copy(t.data(), src, t.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    for (int b = 0; b < h->batch; ++b)
-        for (size_t i = 0; i < (size_t)h->n; ++i)
-            for (int c = 0; c < comps; ++c) dst[(size_t)b * rows + i * comps + c] = t[(i * h->ld + b) * comps + c];
     return 0;
 }
 
@@ -1824,30 +1719,22 @@ int jg_nr_get_voltage(jg_nr* h, double* vm, double* va) {
     if (!h || !vm || !va) return fail(1, "jg_nr_get_voltage: bad argument");
     if (int rc = set_device(h)) return rc;
     NR_HIP(hipStreamSynchronize(h->stream));
-    if (int rc = get_bus_array(h, h->d_vm, vm, 1)) return rc;
-    return get_bus_array(h, h->d_va, va, 1);
+    if (int rc = h->get_rows(h->d_vm, vm, h->n)) return rc;
+    return h->get_rows(h->d_va, va, h->n);
 }
 
 int jg_nr_snapshot_voltage(jg_nr* h) {
     if (!h) return fail(1, "jg_nr_snapshot_voltage: bad argument");
     if (int rc = set_device(h)) return rc;
-    const size_t bytes = (size_t)h->n * h->ld * 8;
-    if (!h->d_vm0) { NR_HIP(hipMalloc((void**)&h->d_vm0, bytes)); NR_HIP(hipMalloc((void**)&h->d_va0, bytes)); }
-    NR_HIP(hipMemcpyAsync(h->d_vm0, h->d_vm, bytes, hipMemcpyDeviceToDevice, h->stream));
-    NR_HIP(hipMemcpyAsync(h->d_va0, h->d_va, bytes, hipMemcpyDeviceToDevice, h->stream));
-    NR_HIP(hipStreamSynchronize(h->stream));
-    return 0;
+    return h->snapshot(h->d_vm, h->d_va, &h->d_vm0, &h->d_va0, h->n);
 }
 
 int jg_nr_restore_voltage(jg_nr* h) {
     if (!h || !h->d_vm0) return fail(1, "jg_nr_restore_voltage: no snapshot");
     if (int rc = set_device(h)) return rc;
-    const size_t bytes = (size_t)h->n * h->ld * 8;
-    NR_HIP(hipMemcpyAsync(h->d_vm, h->d_vm0, bytes, hipMemcpyDeviceToDevice, h->stream));
-    NR_HIP(hipMemcpyAsync(h->d_va, h->d_va0, bytes, hipMemcpyDeviceToDevice, h->stream));
     h->jac_valid = false;
     h->start_is_base = false;
-    return 0;
+    return h->restore(h->d_vm, h->d_va, h->d_vm0, h->d_va0, h->n);
 }
 
 int jg_nr_get_voltage_device(jg_nr* h, double* vm_dev, double* va_dev) {
@@ -1865,8 +1752,7 @@ int jg_nr_pack_results_device(jg_nr* h, double* dst_dev) {
     if (!h || !dst_dev) return fail(1, "jg_nr_pack_results_device: bad argument");
     if (int rc = set_device(h)) return rc;
     const long long stride = 2LL * h->n + 2;
-    dim3 grid((h->n + 63) / 64, (h->ld + 63) / 64, 2), block(64, 8);
-    hipLaunchKernelGGL(k_pack_bus, grid, block, 0, h->stream, h->d_vm, h->d_va, dst_dev, h->n, h->ld, h->batch, stride);
+    h->collect2(h->d_vm, h->d_va, dst_dev, h->n, stride);
     hipLaunchKernelGGL(k_pack_tail, dim3((h->batch + 255) / 256), dim3(256), 0, h->stream, h->d_iters, h->d_status, dst_dev, h->batch, stride, 2 * h->n);
     NR_HIP(hipGetLastError());
     NR_HIP(hipStreamSynchronize(h->stream));
@@ -1880,8 +1766,7 @@ int jg_nr_allgather_results(jg_nr* h, jg_comm* c, double* dst_dev) {
     const long long stride = 2LL * h->n + 2;
     const size_t count = (size_t)h->batch * stride;
     double* mine = dst_dev + (size_t)jg::comm_rank(c) * count;   // in-place all-gather: this rank's record sits in its own block
-    dim3 grid((h->n + 63) / 64, (h->ld + 63) / 64, 2), block(64, 8);
-    hipLaunchKernelGGL(k_pack_bus, grid, block, 0, h->stream, h->d_vm, h->d_va, mine, h->n, h->ld, h->batch, stride);
+    h->collect2(h->d_vm, h->d_va, mine, h->n, stride);
     hipLaunchKernelGGL(k_pack_tail, dim3((h->batch + 255) / 256), dim3(256), 0, h->stream, h->d_iters, h->d_status, mine, h->batch, stride, 2 * h->n);
     NR_HIP(hipGetLastError());
     if (int rc = jg::comm_allgather(c, mine, dst_dev, count, h->stream)) return rc;
@@ -2056,40 +1941,6 @@ int run_setup(jg_nr* h, int64_t max_iter, double tol, int lanes, bool keep_iters
     return 0;
 }
 
-// The host learns the verdict of an iteration from ONE pinned word the verdict kernel stores into (k_compact: host_count).  Waiting for it with
-// hipStreamSynchronize costs a wake-up of ~20 us per iteration -- a tenth of a single instance's iteration; round 5: the host ARMS the word (-1) before
-// the launch and polls it (bounded spin, then yields; hipStreamSynchronize after 2 s as the safety net).  The next graph is then launched while the tail of
-// the previous one (the predicated re-assembly of a compaction) still runs -- stream order keeps them apart.  JG_POLL=0: the synchronise of round 4.
-constexpr double POLL_BELOW_US = 800.0;   // a handle whose waits average more than this blocks in hipStreamSynchronize instead
-static bool poll_enabled() { static const bool on = jg::knob("POLL", 1) != 0; return on; }
-static void arm_verdict(jg_nr* h) { if (poll_enabled()) *(volatile int*)h->h_counter = -1; }
-static hipError_t wait_verdict(jg_nr* h, bool whole = false) {    // whole: the wait is a whole solve of one scenario (run_whole): polled whatever its length, and not counted into wait_us
-    const auto t0 = std::chrono::steady_clock::now();
-    auto elapsed = [&] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); };
-    // Polling pays where an iteration is SHORT (a single instance of the 10k-bus grid: 366 us per iteration; 1.595 ms per solve spinning against 1.656 with the
-    // synchronise).  Where it is long -- a 512-lane batch: 1.6 ms, three of them in flight on a thread each -- the blocking wait is the right one: measured on one
-    // box, interleaved (profiles/r05_poll_ab.txt), the pipeline loses 7 - 10 % to three spinning / napping host threads (254 - 264k against 282 - 287k NR it/s at
-    // the driver's K = 20).  The handle remembers how long its last waits took and picks by that.
-    if (!poll_enabled() || (!whole && h->wait_us > POLL_BELOW_US)) {
-        const hipError_t e = hipStreamSynchronize(h->stream);
-        h->wait_us = 0.5 * h->wait_us + 0.5 * elapsed();
-        return e;
-    }
-    volatile int* w = (volatile int*)h->h_counter;
-    for (long spins = 0; *w == -1; ++spins) {
-        if ((spins & 63) == 63) {
-            const double us = elapsed();
-            if (us > 2.0e6) return hipStreamSynchronize(h->stream);          // something is wrong (or very slow): the blocking wait reports it
-            if (us > 2.0 * POLL_BELOW_US) std::this_thread::yield();          // longer than anything this branch is meant for (the first wait of a big batch): give the core away between looks
-        }
-#if defined(__x86_64__)
-        __builtin_ia32_pause();
-#endif
-    }
-    if (!whole) h->wait_us = 0.5 * h->wait_us + 0.5 * elapsed();
-    return hipSuccess;
-}
-
 // The iteration loop: one graph per iteration until no scenario is active (the iteration limit itself is kept on the device,
 // k_check) -- or, defer_at > 0, until at most defer_at (<= 64) scenarios are: they stay in their lanes, listed for the hand-off (k_compact: hold).
 int run_loop(jg_nr* h, int64_t max_iter, int defer_at) {
@@ -2104,11 +1955,11 @@ int run_loop(jg_nr* h, int64_t max_iter, int defer_at) {
         const double tc = now_us();
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (trace) { hipEventCreate(&e0); hipEventCreate(&e1); hipEventRecord(e0, h->stream); }
-        if (!trace) arm_verdict(h);
+        if (!trace) h->arm();
         NR_HIP(hipGraphLaunch(guess_last ? h->execBm : h->execB, h->stream));  // solve!, then mismatch! and the verdict on the new state
         const double tl = now_us();
         if (trace) hipEventRecord(e1, h->stream);
-        NR_HIP(trace ? hipStreamSynchronize(h->stream) : wait_verdict(h));
+        NR_HIP(trace ? hipStreamSynchronize(h->stream) : h->wait());
         h->host_launch_us += tl - tc; h->host_wait_us += now_us() - tl; h->host_iters += 1;     // JG_HOST_TIMING: printed when the handle goes
         if (guess_last) {
             const bool stops = *h->h_counter == 0 || (defer_at > 0 && *h->h_counter <= defer_at) || it + 1 > max_iter;
@@ -2134,9 +1985,9 @@ int run_start(jg_nr* h, int64_t max_iter) {
     if (int rc = comp_ready(h, comp)) return rc;
     h->start_is_base = false;                                                  // whatever follows moves the state
     h->iter_graphs = 0;
-    arm_verdict(h);
+    h->arm();
     NR_HIP(hipGraphLaunch(comp ? h->execA2 : h->execA, h->stream));
-    NR_HIP(wait_verdict(h));
+    NR_HIP(h->wait());
     if (!comp) { h->first_full += 1; return 0; }
     h->first_comp += 1;
     if (max_iter < 1 || *h->h_counter == 0) {                                  // nothing to iterate: the Jacobian getters find no assembly in place
@@ -2145,9 +1996,9 @@ int run_start(jg_nr* h, int64_t max_iter) {
     }
     const bool trace = jg::knob_set("TRACE");
     const double t0 = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
-    arm_verdict(h);
+    h->arm();
     NR_HIP(hipGraphLaunch(h->execC, h->stream));
-    NR_HIP(wait_verdict(h));
+    NR_HIP(h->wait());
     h->iter_graphs = 1;
     if (trace) fprintf(stderr, "[jg_nr_run] iteration 1 on the shared base factor: %.1f us, %d scenarios still active\n",
                        std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count() - t0, *h->h_counter);
@@ -2165,9 +2016,9 @@ int run_whole(jg_nr* h, int64_t max_iter) {
     if (int rc = build_whole_graph(h, k)) return rc;
     h->start_is_base = false;
     h->first_full += 1;
-    arm_verdict(h);
+    h->arm();
     NR_HIP(hipGraphLaunch(h->execM, h->stream));
-    NR_HIP(wait_verdict(h, true));
+    NR_HIP(h->wait(true));
     h->iter_graphs = k;
     if (*h->h_counter != 0) {                                    // more iterations than the last run took: the Jacobian of the new state, then the loop
         h->last_guess_miss += 1;
@@ -2466,17 +2317,13 @@ int jg_nr_pack_rows_device(jg_nr* h, double* dst_dev, int64_t lane0, int64_t cou
     return 0;
 }
 
-int jg_nr_get_mismatch(jg_nr* h, double* mism) {
-    if (!h || !mism) return fail(1, "jg_nr_get_mismatch: bad argument");
-    if (h->lt_on) return fail(1, "jg_nr_get_mismatch: scenarios have bus types of their own; the reference layout depends on the types");
-    if (int rc = set_device(h)) return rc;
-    if (h->f_stale) { launch_assemble(h, jg::GroupSel{}, false); NR_HIP(hipGetLastError()); h->f_stale = false; }
-    NR_HIP(hipStreamSynchronize(h->stream));
+// device [n][ld][2] (per bus: the theta / P and the V / Q component) -> host [batch][dimJ] in the reference's order: the pvpq rows, then the pq rows
+static int get_scattered(jg_nr* h, const double* src, double* out) {
     std::vector<double> t((size_t)h->n * 2 * h->batch);
-    if (int rc = get_bus_array(h, h->d_F, t.data(), 2)) return rc;
+    if (int rc = h->get_rows2(src, t.data(), h->n)) return rc;
     for (int b = 0; b < h->batch; ++b) {
         const double* s = t.data() + (size_t)b * h->n * 2;
-        double* d = mism + (size_t)b * h->dimJ;
+        double* d = out + (size_t)b * h->dimJ;
         for (int i = 0; i < h->n; ++i) {
             if (h->pvpq[i]) d[h->pvpq[i] - 1] = s[2 * i];
             if (h->pq[i]) d[h->pq[i] - 1] = s[2 * i + 1];
@@ -2485,22 +2332,21 @@ int jg_nr_get_mismatch(jg_nr* h, double* mism) {
     return 0;
 }
 
+int jg_nr_get_mismatch(jg_nr* h, double* mism) {
+    if (!h || !mism) return fail(1, "jg_nr_get_mismatch: bad argument");
+    if (h->lt_on) return fail(1, "jg_nr_get_mismatch: scenarios have bus types of their own; the reference layout depends on the types");
+    if (int rc = set_device(h)) return rc;
+    if (h->f_stale) { launch_assemble(h, jg::GroupSel{}, false); NR_HIP(hipGetLastError()); h->f_stale = false; }
+    NR_HIP(hipStreamSynchronize(h->stream));
+    return get_scattered(h, h->d_F, mism);
+}
+
 int jg_nr_get_increment(jg_nr* h, double* incr) {
     if (!h || !incr) return fail(1, "jg_nr_get_increment: bad argument");
     if (h->lt_on) return fail(1, "jg_nr_get_increment: scenarios have bus types of their own; the reference layout depends on the types");
     if (int rc = set_device(h)) return rc;
     NR_HIP(hipStreamSynchronize(h->stream));
-    std::vector<double> t((size_t)h->n * 2 * h->batch);
-    if (int rc = get_bus_array(h, h->d_inc, t.data(), 2)) return rc;
-    for (int b = 0; b < h->batch; ++b) {
-        const double* s = t.data() + (size_t)b * h->n * 2;
-        double* d = incr + (size_t)b * h->dimJ;
-        for (int i = 0; i < h->n; ++i) {
-            if (h->pvpq[i]) d[h->pvpq[i] - 1] = s[2 * i];
-            if (h->pq[i]) d[h->pq[i] - 1] = s[2 * i + 1];
-        }
-    }
-    return 0;
+    return get_scattered(h, h->d_inc, incr);
 }
 
 int jg_nr_get_jacobian(jg_nr* h, double* nzval) {
@@ -2669,8 +2515,8 @@ int jg_nr_fast_get_increment(jg_nr* h, double* incr) {
     if (int rc = set_device(h)) return rc;
     NR_HIP(hipStreamSynchronize(h->stream));
     std::vector<double> t0((size_t)h->n * 2 * h->batch), t1((size_t)h->n * 2 * h->batch);
-    if (int rc = get_bus_array(h, h->d_inc2[0], t0.data(), 2)) return rc;
-    if (int rc = get_bus_array(h, h->d_inc2[1], t1.data(), 2)) return rc;
+    if (int rc = h->get_rows2(h->d_inc2[0], t0.data(), h->n)) return rc;
+    if (int rc = h->get_rows2(h->d_inc2[1], t1.data(), h->n)) return rc;
     for (int b = 0; b < h->batch; ++b) {                          // [active.increment (pvpq order) | reactive.increment (pq order)]
         double* d = incr + (size_t)b * h->dimJ;
         for (int i = 0; i < h->n; ++i) {
@@ -2775,15 +2621,6 @@ static int post_staging(jg_nr* h, size_t bytes) {
     return 0;
 }
 
-// device [rows][ld][2] -> host [batch][rows][2]
-static int get_pairs(jg_nr* h, const double* src, double* dst, size_t rows) {
-    std::vector<double> t(rows * h->ld * 2);
-    NR_HIP(jg::sync_copy(t.data(), src, t.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    for (int b = 0; b < h->batch; ++b)
-        for (size_t r = 0; r < rows; ++r) { dst[((size_t)b * rows + r) * 2] = t[(r * h->ld + b) * 2]; dst[((size_t)b * rows + r) * 2 + 1] = t[(r * h->ld + b) * 2 + 1]; }
-    return 0;
-}
-
 int jg_nr_branch_quantities(jg_nr* h, double* from_pq, double* to_pq, double* series_pq, double* charging_pq,
                             double* from_i, double* to_i, double* series_i) {
     if (!h) return fail(1, "jg_nr_branch_quantities: bad argument");
@@ -2804,7 +2641,7 @@ int jg_nr_branch_quantities(jg_nr* h, double* from_pq, double* to_pq, double* se
     NR_HIP(hipGetLastError());
     NR_HIP(hipStreamSynchronize(h->stream));
     for (int k = 0; k < 7; ++k)
-        if (host[k]) if (int rc = get_pairs(h, dev[k], host[k], (size_t)h->nb)) return rc;
+        if (host[k]) if (int rc = h->get_rows2(dev[k], host[k], (size_t)h->nb)) return rc;
     return 0;
 }
 
@@ -2816,7 +2653,7 @@ int jg_nr_bus_injection(jg_nr* h, double* inj_pq) {
     NR_HIP(hipGetLastError());
     NR_HIP(hipStreamSynchronize(h->stream));
     h->jac_valid = false;
-    return get_pairs(h, h->d_post, inj_pq, (size_t)h->n);
+    return h->get_rows2(h->d_post, inj_pq, (size_t)h->n);
 }
 
 int jg_nr_set_screen(jg_nr* h, const double* rating) {
