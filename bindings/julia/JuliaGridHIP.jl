@@ -1422,6 +1422,59 @@ function seriesTimeKernel(b::DcPowerFlowBatch, kernel::Int, k0::Int64, k1::Int64
 end
 "frees the sensitivities and base flows a series screen keeps on the device"
 seriesScreenRelease!(b::DcPowerFlowBatch) = check(ccall((:jg_dc_series_release, lib), Cint, (Int64,), b.token))
+"""
+    transferScreenBuild!(b, candidates, directions; baseRhs = nothing, monitored = nothing, budget = 0) -> info [12]
+
+The DC transfer-capability screen (jgrid.h: jg_dc_transfer_*): `directions` is `[buses, T]`, the net active injection per unit of transfer of every
+direction (the slack takes what a direction does not balance).  `baseRhs`: the right-hand side of a base profile as `uploadRhs!` sets it (default: the
+system's own).  One sweep pair per candidate branch (indices, in service, ascending; one is allowed) and one per direction; `budget`: bytes the outage and
+the transfer sensitivities may take (0: 0.8 of the free device memory).
+"""
+function transferScreenBuild!(b::DcPowerFlowBatch, candidates::Vector{Int64}, directions::Matrix{Float64}; baseRhs::Union{Nothing, Vector{Float64}} = nothing,
+                              monitored::Union{Nothing, Vector{Int64}} = nothing, budget::Int64 = 0)
+    size(directions, 1) == dims(b)[1] || throw(DimensionMismatch("[buses, transfers] directions"))
+    baseRhs === nothing || length(baseRhs) == dims(b)[1] || throw(DimensionMismatch("[buses] base right-hand side"))
+    uploadRhs!(b)
+    info = zeros(Float64, 12)
+    mon = monitored === nothing ? Int64[] : monitored
+    check(ccall((:jg_dc_transfer_build, lib), Cint, (Int64, Int64, Ptr{Int64}, Int64, Ptr{Int64}, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}),
+        b.token, length(candidates), candidates, length(mon), monitored === nothing ? C_NULL : mon, size(directions, 2), directions,
+        baseRhs === nothing ? C_NULL : baseRhs, budget, info))
+    return info
+end
+"""
+    transferScreen(b, k0, k1, candidates, transfers; rating, cutoff = 1e-6, amount = nothing, capacity = 2^20)
+        -> (records [5, m], islanding, totals [5], worst, capability, limitingOutage, limitingBranch, base [3, T])
+
+All cases (k, t) of the candidate positions k0 .. k1 - 1 (0-based) and every transfer: the capability per transfer over the block's outages with the outage
+and the branch that give it (merge with `base[1, :]`, the base case, for the answer), the least capability per candidate, the bridge candidates of the
+block, and with `amount` (one value per transfer) the records of the cases below it sorted by (k, t) (branch k, transfer t (0-based), limiting branch,
+capability, flow sensitivity of the limiting branch) with the totals (cases, below their amount, bridges, records kept, overflow flag).
+"""
+function transferScreen(b::DcPowerFlowBatch, k0::Int64, k1::Int64, candidates::Vector{Int64}, transfers::Int64; rating::Vector{Float64}, cutoff::Float64 = 1e-6,
+                        amount::Union{Nothing, Vector{Float64}} = nothing, capacity::Int64 = 2^20)
+    check(ccall((:jg_dc_set_rating, lib), Cint, (Int64, Ptr{Float64}), b.token, rating))
+    amount === nothing || length(amount) == transfers || throw(DimensionMismatch("one amount per transfer"))
+    capacity = amount === nothing ? 0 : capacity
+    records = Matrix{Float64}(undef, 5, max(capacity, 1))
+    islanding = zeros(Int64, max(k1 - k0, 1))
+    totals = zeros(Int64, 5)
+    worst = fill(Inf, length(candidates))
+    capability = fill(Inf, transfers); limitingOutage = zeros(Int64, transfers); limitingBranch = zeros(Int64, transfers); base = zeros(Float64, 3, transfers)
+    check(ccall((:jg_dc_transfer_screen, lib), Cint, (Int64, Int64, Int64, Float64, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64},
+                                                      Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+        b.token, k0, k1, cutoff, amount === nothing ? C_NULL : amount, capacity, records, islanding, totals, worst, capability, limitingOutage, limitingBranch,
+        base, C_NULL, C_NULL))
+    return records[:, 1:totals[4]], islanding[1:totals[3]], totals, worst, capability, limitingOutage, limitingBranch, base
+end
+"milliseconds of `reps` runs on candidate rows k0 .. k1 - 1 (HIP events): 0 the transfer screen kernel, 1 its row / column summaries"
+function transferTimeKernel(b::DcPowerFlowBatch, kernel::Int, k0::Int64, k1::Int64, reps::Int = 20)
+    ms = zeros(Float64, reps)
+    check(ccall((:jg_dc_transfer_time_kernel, lib), Cint, (Int64, Cint, Int64, Int64, Cint, Ptr{Float64}), b.token, kernel, k0, k1, reps, ms))
+    return ms
+end
+"frees the sensitivities a transfer screen keeps on the device"
+transferScreenRelease!(b::DcPowerFlowBatch) = check(ccall((:jg_dc_transfer_release, lib), Cint, (Int64,), b.token))
 
 # ---- DC state estimation with batched bad-data removal (jgrid.h: jg_dcse_*; csrc/jg_dcse.hip) ------------------------------------------------
 # dcStateEstimation / solve! / power! / residualTest! / chiTest (src/stateEstimation/dcStateEstimation.jl:42-151, 342-434, badData.jl:48-117, 963-977) for

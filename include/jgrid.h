@@ -606,6 +606,46 @@ int jg_dc_series_screen(int64_t h, int64_t k0, int64_t k1, double threshold, int
                         int32_t* dense_count);
 int jg_dc_series_time_kernel(int64_t h, int kernel, int64_t k0, int64_t k1, int reps, double* ms);
 int jg_dc_series_release(int64_t h);
+/*
+ * The DC transfer-capability screen over transfers x N-1 outages (csrc/jg_dc_transfer.hpp): the user loop that raises the injections along a direction
+ * with updateBus! / updateGenerator! around updateBranch!(k, status = 0), solve!, power! per branch until a monitored branch reaches its rating.  No
+ * sweep per case: with Phi of jg_dc_pair_build, the base flows F0[m] and the flow sensitivities G[m,t] of the directions, the post-outage flow at
+ * P0 + lambda d_t is f + lambda g with f = F0[m] + Phi[m,k] F0[k] / (1 - Phi[k,k]), g = G[m,t] + Phi[m,k] G[k,t] / (1 - Phi[k,k]), and the capability
+ * TC(k,t) is the least (sign(g) rating_m - f) / g over the monitored, rated branches m != k with |g| > cutoff (negative: that branch is beyond the rating
+ * at zero transfer; +inf: no such branch).  Needs jg_dc_set_branches and jg_dc_set_rhs; neither the lanes of the handle nor what jg_dc_pair_build and
+ * jg_dc_series_build keep are touched.
+ *   jg_dc_transfer_build  candidates [nk] and monitored [nm] as jg_dc_series_build takes them (nk >= 1); directions [transfers][n]: net active injection
+ *                       per unit of transfer (no shunt, no shiftPower term; the slack's entry is ignored: the slack takes what a direction does not
+ *                       balance).  base_rhs [n] (nullable): the right-hand side of a base profile as jg_dc_set_rhs takes it; NULL: the handle's own.
+ *                       Phi by the build of jg_dc_pair_build, then one sweep pair per direction (512 at a time, scratch of the build's own) fills
+ *                       G [rows][transfers rounded up to 64] doubles.  budget_bytes as jg_dc_pair_build, for Phi + G + the scratch of both: return code 5
+ *                       with the sizes in the message and nothing allocated when they do not fit.  info [12]: the eight of jg_dc_pair_build, bytes of
+ *                       G, and the milliseconds of its build: total, sweep pairs, G kernel.  A second build replaces the first.
+ *   jg_dc_transfer_screen the cases (k, t) of the candidate POSITIONS k in [k0, k1) (0-based; the row block bounds the memory of a call, 12 bytes per
+ *                       case) x all transfers against the ratings of jg_dc_set_rating; cutoff > 0 in per unit of flow per per unit of transfer.
+ *                       amount [transfers] (nullable: no records): records [capacity][5] are the cases with TC(k,t) < amount[t], sorted by (k, t):
+ *                       branch k (1-based), transfer t (0-based), limiting branch, TC, g of the limiting branch; ties of the limiting branch go to the
+ *                       lowest index.  islanding [k1 - k0] (nullable): the candidates of the block that are bridges (|1 - Phi[k,k]| < 1e-9: status 3
+ *                       and a NaN capability for every transfer; never in a record or a minimum), 1-based.
+ *                       totals [5]: cases screened, cases below their amount, bridge candidates, records written, 1 when the record list overflowed --
+ *                       the counts are exact also then, and the records kept are the FIRST by (k, t).
+ *                       worst [nk] (nullable): positions k0 .. k1 - 1 get the least TC over the transfers (NaN on a bridge).  capability,
+ *                       limiting_outage, limiting_branch [transfers] (nullable together, in/out): min-merged with the least TC over the block's
+ *                       candidates (bridges aside), the candidate (1-based branch) and the branch that give it; ties go to the lowest candidate, so
+ *                       the result of a caller that starts from +inf does not depend on the blocks.  base [transfers][3] (nullable): the base case of
+ *                       every transfer, no outage -- TC, limiting branch (0: none), monitored branches above their rating at zero transfer.
+ *                       dense_* (each nullable) [k1 - k0][transfers]: TC (NaN: bridge), the limiting branch (0: none).
+ *   jg_dc_transfer_time_kernel   milliseconds of `reps` runs on rows [k0, k1) (a block jg_dc_transfer_screen has held): 0 the screen kernel, 1 the row /
+ *                       column summaries behind it
+ *   jg_dc_transfer_release  frees what the screen holds on the device
+ */
+int jg_dc_transfer_build(int64_t h, int64_t nk, const int64_t* candidates, int64_t nm, const int64_t* monitored, int64_t transfers,
+                         const double* directions, const double* base_rhs, int64_t budget_bytes, double* info12);
+int jg_dc_transfer_screen(int64_t h, int64_t k0, int64_t k1, double cutoff, const double* amount, int64_t capacity, double* records, int64_t* islanding,
+                          int64_t* totals5, double* worst, double* capability, int64_t* limiting_outage, int64_t* limiting_branch, double* base,
+                          double* dense_capability, int32_t* dense_branch);
+int jg_dc_transfer_time_kernel(int64_t h, int kernel, int64_t k0, int64_t k1, int reps, double* ms);
+int jg_dc_transfer_release(int64_t h);
 
 /* ---------------------------------------------------------------------------------------------
  * DC state estimation with batched bad-data removal (csrc/jg_dcse.hip)

@@ -6,6 +6,7 @@
 #include "jg_dc_abi.hpp"
 #include "jg_dc_pair.hpp"
 #include "jg_dc_series.hpp"
+#include "jg_dc_transfer.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -282,6 +283,7 @@ void dc_destroy(DcHandle* h) {
     if (h->stream) hipStreamSynchronize(h->stream);
     dc_pair_free(h);
     dc_series_free(h);
+    dc_transfer_free(h);
     for (void* p : h->allocs) hipFree(p);
     if (h->stream) hipStreamDestroy(h->stream);
     delete h;

@@ -34,6 +34,7 @@ constexpr double DC_SINGULAR = 1e-9;   // |1 - y_k a' z_s| below it: bridge.  Th
 
 struct DcPairState;
 struct DcSeriesState;
+struct DcTransferState;
 
 struct DcHandle : DcDevice {
     int n = 0, nbr = 0, batch = 0, ld = 0, slack = 0;
@@ -54,6 +55,7 @@ struct DcHandle : DcDevice {
     int* glist2 = nullptr; std::vector<int> h_o2; int n_glist2 = 0;            // lane groups that hold a second outage
     DcPairState* pair = nullptr;                                               // the N-2 screen's kept sensitivities (jg_dc_pair.hpp)
     DcSeriesState* series = nullptr;                                           // the N-1 screen over a series of injection profiles (jg_dc_series.hpp)
+    DcTransferState* transfer = nullptr;                                       // the transfer-capability screen over transfers x N-1 outages (jg_dc_transfer.hpp)
     // bridge outages solved on the slack's island (jg_dc_set_island_mode 1): allocated by the first such call, a handle without it holds none of it
     int island_mode = 0, n_isl = 0;                                            // n_isl: lanes whose ONE outage is a bridge, set while the mode was 1
     std::vector<int> h_pre, h_blo, h_bhi, h_bside;                             // dc_island_table of the handle's branch table

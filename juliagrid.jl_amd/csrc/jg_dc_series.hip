@@ -27,9 +27,11 @@ namespace {
 constexpr int SERIES_F0_ROWS = 8;       // rows of F0 per wave of k_series_f0
 
 // F0[r, col0 + lane] = y_m ((theta[from_m] + slack angle) - (theta[to_m] + slack angle) - shiftAngle_m) for the profiles of one lane batch, formed as
-// k_dc_flows forms a flow; columns behind the last profile stay 0
+// k_dc_flows forms a flow; columns behind the last profile stay 0.  SHIFT false: y_m (theta[from_m] - theta[to_m]), what the flow gains per unit of the
+// right-hand side (the transfer screen's G), formed as k_pair_phi forms Phi
 struct SeriesF0Args { const double* TH; const int* rbranch; const int* bf; const int* bt; const double* by; const double* bs; double slack_angle;
                       double* F0; int rows, ldb, ldt, col0, T; };
+template <bool SHIFT>
 __global__ __launch_bounds__(256) void k_series_f0(SeriesF0Args a) {
     const int wave = uniform(threadIdx.y);
     const int r0 = (blockIdx.x * 4 + wave) * SERIES_F0_ROWS;
@@ -40,7 +42,8 @@ __global__ __launch_bounds__(256) void k_series_f0(SeriesF0Args a) {
         const int m = ((CInt)a.rbranch)[r];
         const int f = ((CInt)a.bf)[m], t = ((CInt)a.bt)[m];
         const double y = ((CDbl)a.by)[m], s = ((CDbl)a.bs)[m];
-        a.F0[(size_t)r * a.ldt + col] = y * ((a.TH[(size_t)f * ldb + bl] + a.slack_angle) - (a.TH[(size_t)t * ldb + bl] + a.slack_angle) - s);
+        if constexpr (SHIFT) a.F0[(size_t)r * a.ldt + col] = y * ((a.TH[(size_t)f * ldb + bl] + a.slack_angle) - (a.TH[(size_t)t * ldb + bl] + a.slack_angle) - s);
+        else a.F0[(size_t)r * a.ldt + col] = y * (a.TH[(size_t)f * ldb + bl] - a.TH[(size_t)t * ldb + bl]);
     }
 }
 
@@ -197,38 +200,17 @@ void series_release(DcHandle* h) {
     h->series = nullptr;
 }
 
-// rhs [T][n]: the lane right-hand sides as jg_dc_set_injections takes them
-int series_build(DcHandle* h, const std::vector<int>& cand, const std::vector<int>& mon, int T, const double* rhs, int64_t budget, double* info) {
-    series_release(h);
-    const int n = h->n, nk = (int)cand.size();
-    const int ldt = (T + 63) / 64 * 64, ldb = std::min(ldt, DC_PAIR_LANES);
-    int nr = 0;
-    {
-        std::vector<char> in(h->nbr, 0);
-        for (int m : mon) in[m] = 1;
-        for (int m : cand) in[m] = 1;
-        for (char c : in) nr += c;
-    }
-    const size_t f0_bytes = (size_t)nr * ldt * sizeof(double), scratch = ((size_t)3 * n + 1) * ldb * sizeof(double);
-    for (int j = 8; j < 12; ++j) info[j] = 0.0;
-    info[8] = (double)f0_bytes;
-    DcSeriesState* s = new DcSeriesState();
-    h->series = s;
-    s->T = T; s->ldt = ldt;
-    const std::string extra = "; F0 needs " + dc_pair_bytes_text(f0_bytes) + " (" + std::to_string(nr) + " rows x " + std::to_string(ldt) + " profiles x 8) and " +
-                              dc_pair_bytes_text(scratch) + " of scratch";
-    int rc = dc_pair_state_build(h, s->phi, "jg_dc_series_build", cand, mon, budget, f0_bytes + scratch, extra, info);
-    if (rc) { const std::string msg = h->error; series_release(h); h->error = msg; return rc; }
-    DcPairState* p = s->phi;
+// the lane-batch loop of a build (dc_series_row_flows of jg_dc_series.hpp): F0 of the series screen with the shift angle, G of the transfer screen without
+int row_flows(DcHandle* h, const DcPairState* p, int T, const double* rhs, bool shift, double* F, int ldt, double* ms) {
+    const int n = h->n, nr = p->rows, ldb = std::min(ldt, DC_PAIR_LANES);
+    int rc = 0;
     double* R = nullptr; double* W = nullptr; double* TH = nullptr;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     auto hip = [&](hipError_t e, const char* what) { if (e != hipSuccess && !rc) { rc = 2; h->error = std::string(what) + ": " + hipGetErrorString(e); } return e == hipSuccess; };
     auto alloc = [&](int r) { if (r && !rc) rc = r; return r == 0; };
     double sweep_ms = 0.0, f0_ms = 0.0;
-    if (alloc(dev_alloc(h, &s->F0, (size_t)nr * ldt, (const double*)nullptr, true)) && alloc(dev_alloc(h, &s->c_max, (size_t)ldt, (const double*)nullptr, true)) &&
-        alloc(dev_alloc(h, &s->c_viol, (size_t)ldt, (const int*)nullptr, true)) && alloc(dev_alloc(h, &s->base, (size_t)ldt * 3, (const double*)nullptr, true)) &&
-        // scratch of the build: one lane batch of right-hand sides and of the sweeps (row n of W stays zero)
-        alloc(dev_alloc(h, &R, (size_t)n * ldb, (const double*)nullptr, true)) && alloc(dev_alloc(h, &W, ((size_t)n + 1) * ldb, (const double*)nullptr, true)) &&
+    // scratch: one lane batch of right-hand sides and of the sweeps (row n of W stays zero)
+    if (alloc(dev_alloc(h, &R, (size_t)n * ldb, (const double*)nullptr, true)) && alloc(dev_alloc(h, &W, ((size_t)n + 1) * ldb, (const double*)nullptr, true)) &&
         alloc(dev_alloc(h, &TH, (size_t)n * ldb, (const double*)nullptr, true))) {
         for (auto& e : ev) hip(hipEventCreate(&e), "hipEventCreate");
         std::vector<double> tb;
@@ -245,8 +227,10 @@ int series_build(DcHandle* h, const std::vector<int>& cand, const std::vector<in
             hip(hipEventRecord(ev[0], h->stream), "hipEventRecord");
             sweep_pair(h->fac, h->stream, 0, R, nullptr, nullptr, W, TH, ldb, groups, nullptr);
             hip(hipEventRecord(ev[1], h->stream), "hipEventRecord");
-            SeriesF0Args a{TH, p->row_branch, h->b_from, h->b_to, h->b_y, h->b_shift, h->slack_angle, s->F0, nr, ldb, ldt, c0, T};
-            hipLaunchKernelGGL(k_series_f0, dim3((nr + 4 * SERIES_F0_ROWS - 1) / (4 * SERIES_F0_ROWS), groups), dim3(64, 4), 0, h->stream, a);
+            SeriesF0Args a{TH, p->row_branch, h->b_from, h->b_to, h->b_y, h->b_shift, h->slack_angle, F, nr, ldb, ldt, c0, T};
+            const dim3 grid((nr + 4 * SERIES_F0_ROWS - 1) / (4 * SERIES_F0_ROWS), groups);
+            if (shift) hipLaunchKernelGGL(k_series_f0<true>, grid, dim3(64, 4), 0, h->stream, a);
+            else hipLaunchKernelGGL(k_series_f0<false>, grid, dim3(64, 4), 0, h->stream, a);
             hip(hipEventRecord(ev[2], h->stream), "hipEventRecord");
             hip(hipGetLastError(), "launch");
             if (!hip(hipEventSynchronize(ev[2]), "hipEventSynchronize")) break;
@@ -255,19 +239,50 @@ int series_build(DcHandle* h, const std::vector<int>& cand, const std::vector<in
             hip(hipEventElapsedTime(&t2, ev[1], ev[2]), "hipEventElapsedTime");
             sweep_ms += t1; f0_ms += t2;
         }
-        if (!rc) {
-            std::vector<double> diag(p->ldk);
-            if (hip(sync_copy(diag.data(), p->cand_diag, diag.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream), "download")) {
-                s->h_bridge.assign(nk, 0);
-                for (int k = 0; k < nk; ++k) s->h_bridge[k] = std::fabs(1.0 - diag[k]) < DC_SINGULAR;
-            }
-        }
     }
     for (auto& e : ev) if (e) (void)hipEventDestroy(e);
     dev_release(h, R); dev_release(h, W); dev_release(h, TH);
+    ms[0] += sweep_ms; ms[1] += f0_ms;
+    return rc;
+}
+int bridges(DcHandle* h, const DcPairState* p, std::vector<char>& bridge) {
+    std::vector<double> diag(p->ldk);
+    DC_HIP(sync_copy(diag.data(), p->cand_diag, diag.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    bridge.assign(p->nk, 0);
+    for (int k = 0; k < p->nk; ++k) bridge[k] = std::fabs(1.0 - diag[k]) < DC_SINGULAR;
+    return 0;
+}
+
+// rhs [T][n]: the lane right-hand sides as jg_dc_set_injections takes them
+int series_build(DcHandle* h, const std::vector<int>& cand, const std::vector<int>& mon, int T, const double* rhs, int64_t budget, double* info) {
+    series_release(h);
+    const int ldt = (T + 63) / 64 * 64;
+    int nr = 0;
+    {
+        std::vector<char> in(h->nbr, 0);
+        for (int m : mon) in[m] = 1;
+        for (int m : cand) in[m] = 1;
+        for (char c : in) nr += c;
+    }
+    const size_t f0_bytes = (size_t)nr * ldt * sizeof(double), scratch = dc_series_flows_scratch(h, ldt);
+    for (int j = 8; j < 12; ++j) info[j] = 0.0;
+    info[8] = (double)f0_bytes;
+    DcSeriesState* s = new DcSeriesState();
+    h->series = s;
+    s->T = T; s->ldt = ldt;
+    const std::string extra = "; F0 needs " + dc_pair_bytes_text(f0_bytes) + " (" + std::to_string(nr) + " rows x " + std::to_string(ldt) + " profiles x 8) and " +
+                              dc_pair_bytes_text(scratch) + " of scratch";
+    int rc = dc_pair_state_build(h, s->phi, "jg_dc_series_build", cand, mon, budget, f0_bytes + scratch, extra, info);
     if (rc) { const std::string msg = h->error; series_release(h); h->error = msg; return rc; }
-    s->build_ms[0] = sweep_ms + f0_ms; s->build_ms[1] = sweep_ms; s->build_ms[2] = f0_ms;
-    info[9] = s->build_ms[0]; info[10] = sweep_ms; info[11] = f0_ms;
+    DcPairState* p = s->phi;
+    auto step = [&](int r) { if (r && !rc) rc = r; return r == 0; };
+    double ms[2] = {0.0, 0.0};
+    step(dev_alloc(h, &s->F0, (size_t)nr * ldt, (const double*)nullptr, true)) && step(dev_alloc(h, &s->c_max, (size_t)ldt, (const double*)nullptr, true)) &&
+        step(dev_alloc(h, &s->c_viol, (size_t)ldt, (const int*)nullptr, true)) && step(dev_alloc(h, &s->base, (size_t)ldt * 3, (const double*)nullptr, true)) &&
+        step(row_flows(h, p, T, rhs, true, s->F0, ldt, ms)) && step(bridges(h, p, s->h_bridge));
+    if (rc) { const std::string msg = h->error; series_release(h); h->error = msg; return rc; }
+    s->build_ms[0] = ms[0] + ms[1]; s->build_ms[1] = ms[0]; s->build_ms[2] = ms[1];
+    info[9] = s->build_ms[0]; info[10] = ms[0]; info[11] = ms[1];
     return 0;
 }
 
@@ -384,6 +399,11 @@ int series_screen(DcHandle* h, int k0, int k1, double thr, long long rec_cap, co
 }  // namespace
 
 void dc_series_free(DcHandle* h) { series_release(h); }
+size_t dc_series_flows_scratch(const DcHandle* h, int ldt) { return ((size_t)3 * h->n + 1) * std::min(ldt, DC_PAIR_LANES) * sizeof(double); }
+int dc_series_row_flows(DcHandle* h, const DcPairState* p, int T, const double* rhs, bool shift, double* F, int ldt, double* ms) {
+    return row_flows(h, p, T, rhs, shift, F, ldt, ms);
+}
+int dc_series_bridges(DcHandle* h, const DcPairState* p, std::vector<char>& bridge) { return bridges(h, p, bridge); }
 
 }  // namespace jg
 

@@ -44,4 +44,14 @@ struct DcSeriesState {
 
 void dc_series_free(DcHandle* h);            // releases what the series screen holds (jg_dc_destroy, jg_dc_series_release)
 
+// The lane-batch loop of the build is shared with the transfer screen (jg_dc_transfer.hpp):
+//   dc_series_row_flows     F [rows of p][ldt] from `T` right-hand sides rhs [T][n] (the slack's entry is taken as 0): uploads DC_PAIR_LANES of them at a
+//                           time, runs the sweep pair and turns the angles into row flows y_m (a_m' theta - shiftAngle_m); shift false: y_m a_m' theta,
+//                           the sensitivity of the flow to the right-hand side.  Scratch of its own (dc_series_flows_scratch bytes), released on return;
+//                           ms [2] gets the milliseconds of the sweep pairs and of the flow kernel added (HIP events).  Not 0: the text is in h->error
+//   dc_series_bridges       bridge [nk] 1: |1 - Phi[k,k]| < DC_SINGULAR
+size_t dc_series_flows_scratch(const DcHandle* h, int ldt);
+int dc_series_row_flows(DcHandle* h, const DcPairState* p, int T, const double* rhs, bool shift, double* F, int ldt, double* ms);
+int dc_series_bridges(DcHandle* h, const DcPairState* p, std::vector<char>& bridge);
+
 }  // namespace jg

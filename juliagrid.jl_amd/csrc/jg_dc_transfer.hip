@@ -1,0 +1,433 @@
+// jg_dc_transfer.hip -- the DC transfer-capability screen over transfers x N-1 outages (jg_dc_transfer.hpp has the algebra and the reference loop it
+// stands for).
+//
+// Build: Phi by the build the pair screen shares (jg_dc_pair.hip), into a state of the screen's own; then the sweep pair of jg_dc_sweep.hip over the
+// directions, DC_PAIR_LANES at a time, through the lane-batch loop the series build shares (dc_series_row_flows, without the shift angle); the base flows
+// are the pair state's, or one more such batch of one lane for a base profile.  Screen of a row block [k0, k1): k_transfer_screen walks the rows once (lanes
+// = 64 consecutive candidates k of a chunk, a wave keeps DC_TRANSFER_TILE transfers in registers, the waves of a workgroup share the chunk so its Phi rows
+// meet in the vector L1; 1 / rating_m, F0[m], the row's candidate position and G[m, t..t+3] through scalar loads, Phi[m, k..k+63] one coalesced vector load
+// reused for every transfer of the tile; nothing is written per m).  The summaries come out of the block's dense result without atomics: per candidate and
+// per transfer minima, the records by count (k_transfer_rows<false>) / prefix sum over the rows (host) / ordered scatter (k_transfer_rows<true>: ballot
+// ranks), so the list is sorted by (k, t) and a list that overflows keeps the first.  Every store is a vector store.
+#include "jg_dc_transfer.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <limits>
+#include <type_traits>
+
+#include "../../include/jgrid.h"
+#include "jg_dc.hpp"
+#include "jg_dc_abi.hpp"
+#include "jg_dc_series.hpp"
+
+namespace jg {
+
+namespace {
+
+// sign(g) x: the sign bit of g flips x
+__device__ __forceinline__ double flip_by(double x, double g) {
+    return __longlong_as_double(__double_as_longlong(x) ^ (__double_as_longlong(g) & (long long)0x8000000000000000ull));
+}
+// One row against the running minimum (bn / bd, br) of a case, in loading space: fl = f rinv (signed), g the sensitivity, ri = rinv (0: not monitored or not
+// rated).  limit = (1 - sign(g) fl) / (|g| ri); an ineligible row is (1, 0) = +inf and never wins; strict comparison, rows ascending.
+__device__ __forceinline__ void transfer_row(double fl, double g, double ri, bool eligible, double cutoff, int r, double& bn, double& bd, int& br) {
+    const double ag = fabs(g);
+    const bool el = eligible && ag > cutoff;
+    const double num = el ? 1.0 - flip_by(fl, g) : 1.0;
+    const double den = el ? ag * ri : 0.0;
+    if (num * bd < bn * den) { bn = num; bd = den; br = r; }
+}
+__device__ __forceinline__ double transfer_limit(double bn, double bd) { return bd > 0.0 ? bn / bd : __longlong_as_double(0x7ff0000000000000LL); }
+
+// ---- the screen kernel -------------------------------------------------------------------------------------------------------------------
+struct TransferScreenArgs {
+    const double* Phi; const double* G; const double* f0; const double* rinv; const int* pos;
+    const int* crow; const double* cdiag;
+    double* tc; int* row;                                       // [k1 - k0][ldt]
+    double cutoff; int rows, ldk, ldt, T, k0, k1, kbase;        // kbase: k0 rounded down to a multiple of 64 (a chunk's row of Phi is one aligned 512-byte load)
+};
+__global__ __launch_bounds__(64 * DC_PAIR_WAVES) void k_transfer_screen(TransferScreenArgs a) {
+    constexpr int K = DC_TRANSFER_TILE;
+    const int wave = uniform(threadIdx.y);
+    const int t0 = (blockIdx.y * DC_PAIR_WAVES + wave) * K;     // < ldt: G is [rows][ldt], 0 behind T
+    if (t0 >= a.T) return;
+    const int c0 = a.kbase + blockIdx.x * 64;
+    const int k = c0 + threadIdx.x;                             // < ldk: the per-candidate arrays are [ldk], 0 behind nk; so are the columns of Phi
+    const size_t ldk = (size_t)a.ldk, ldt = (size_t)a.ldt;
+    const double dk = 1.0 - a.cdiag[k];
+    const int rk = a.crow[k];
+    const bool sing = fabs(dk) < DC_SINGULAR;
+    const double cf = sing ? 0.0 : a.f0[rk] / dk;
+    double cg[K], bn[K], bd[K];
+    int br[K];
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+        cg[i] = sing ? 0.0 : a.G[(size_t)rk * ldt + t0 + i] / dk;
+        bn[i] = 1.0; bd[i] = 0.0; br[i] = -1;
+    }
+    const double cutoff = a.cutoff;
+    const double* pcol = a.Phi + k;
+    auto row = [&](int r, int pk, auto hit_c) {
+        constexpr bool HIT = decltype(hit_c)::value;
+        const double ri = ((CDbl)a.rinv)[r], fr = ((CDbl)a.f0)[r];
+        const D4 g4 = *(CD4)(a.G + (size_t)r * ldt + t0);
+        const double ph = pcol[(size_t)r * ldk];
+        const double fl = fma(ph, cf, fr) * ri;
+        const bool other = !(HIT && pk == k);                   // the outaged branch limits nothing
+#pragma unroll
+        for (int i = 0; i < K; ++i) transfer_row(fl, fma(ph, cg[i], g4[i]), ri, other, cutoff, r, bn[i], bd[i], br[i]);
+    };
+    for (int r = 0; r < a.rows; ++r) {
+        const int pk = ((CInt)a.pos)[r];
+        // only a row whose branch is one of this chunk's own candidates (at most 64 of the rows) needs the test per lane
+        if ((unsigned)(pk - c0) < 64u) row(r, pk, std::true_type{});
+        else row(r, pk, std::false_type{});
+    }
+    if (k < a.k0 || k >= a.k1) return;
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+        const int t = t0 + i;
+        if (t >= a.T) continue;
+        const size_t o = (size_t)(k - a.k0) * ldt + t;
+        a.tc[o] = sing ? nan : transfer_limit(bn[i], bd[i]);
+        a.row[o] = sing ? -1 : br[i];
+    }
+}
+
+// ---- summaries out of the block's dense result: count, (prefix sum on the host), ordered scatter ---------------------------------------------
+struct TransferListArgs {
+    const double* tc; const int* row; const double* amount; const int* clabel; const int* rbranch;
+    const double* Phi; const double* G; const int* crow; const double* cdiag;      // scatter: g of the limiting branch, formed as the screen kernel forms it
+    int* r_rec; double* r_min;                                   // per row of the block
+    const long long* r_off;                                      // scatter: the row's first record
+    double* rec; long long rec_cap;
+    int ldk, ldt, T, k0, k1;
+};
+template <bool SCATTER>
+__global__ __launch_bounds__(256) void k_transfer_rows(TransferListArgs a) {
+    const int wave = uniform(threadIdx.y), lane = threadIdx.x;
+    const int i = blockIdx.x * 4 + wave;
+    const int k = a.k0 + i;
+    if (k >= a.k1) return;
+    const size_t ldt = (size_t)a.ldt, ldk = (size_t)a.ldk;
+    int nv = 0;
+    double mn = __longlong_as_double(0x7ff0000000000000LL);
+    long long vb = SCATTER ? a.r_off[i] : 0;
+    const int klab = ((CInt)a.clabel)[k];
+    for (int t0 = 0; t0 < a.T; t0 += 64) {
+        const int t = t0 + lane;
+        const bool valid = t < a.T;
+        const double v = valid ? a.tc[(size_t)i * ldt + t] : 0.0;
+        const bool below = valid && v < a.amount[t];             // (a NaN, the capability of a bridge candidate, compares false)
+        const unsigned long long mv = __ballot(below);
+        if (SCATTER) {
+            if (below) {
+                const long long at = vb + __popcll(mv & ((1ull << lane) - 1ull));
+                const int r = a.row[(size_t)i * ldt + t];
+                if (at < a.rec_cap && r >= 0) {
+                    const int rk = a.crow[k];
+                    const double g = fma(a.Phi[(size_t)r * ldk + k], a.G[(size_t)rk * ldt + t] / (1.0 - a.cdiag[k]), a.G[(size_t)r * ldt + t]);
+                    double* q = a.rec + at * 5;
+                    q[0] = (double)klab; q[1] = (double)t; q[2] = (double)(a.rbranch[r] + 1); q[3] = v; q[4] = g;
+                }
+            }
+            vb += __popcll(mv);
+        } else {
+            nv += __popcll(mv);
+            if (valid && v < mn) mn = v;
+        }
+    }
+    if (!SCATTER) {
+        for (int s = 32; s; s >>= 1) mn = fmin(mn, __shfl_xor(mn, s, 64));
+        if (lane == 0) { a.r_rec[i] = nv; a.r_min[i] = mn; }
+    }
+}
+// per transfer over the block's candidates, rows ascending and strict: the least capability (bridges aside), the block row that gives it (-1: none), its limiting row
+__global__ void k_transfer_cols(const double* tc, const int* row, double* c_min, int* c_at, int* c_row, int ldt, int T, int rb) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= ldt) return;
+    double mn = __longlong_as_double(0x7ff0000000000000LL);
+    int at = -1;
+    if (t < T)
+        for (int i = 0; i < rb; ++i) {
+            const double v = tc[(size_t)i * ldt + t];
+            if (v < mn) { mn = v; at = i; }
+        }
+    c_min[t] = mn; c_at[t] = at; c_row[t] = at < 0 ? -1 : row[(size_t)at * ldt + t];
+}
+// the base case of every transfer (no outage): the capability, its limiting row (-1: none), monitored branches above their rating at zero transfer
+__global__ void k_transfer_base(const double* G, const double* f0, const double* rinv, double* base, double cutoff, int rows, int ldt, int T) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= T) return;
+    double bn = 1.0, bd = 0.0;
+    int br = -1, cnt = 0;
+    for (int r = 0; r < rows; ++r) {
+        const double ri = ((CDbl)rinv)[r];
+        const double fl = ((CDbl)f0)[r] * ri;
+        transfer_row(fl, G[(size_t)r * ldt + t], ri, true, cutoff, r, bn, bd, br);
+        cnt += fabs(fl) > 1.0 ? 1 : 0;
+    }
+    double* q = base + (size_t)t * 3;
+    q[0] = transfer_limit(bn, bd); q[1] = (double)br; q[2] = (double)cnt;
+}
+// the base flows of a base profile: lane 0 of its one lane batch
+__global__ void k_transfer_pick(const double* F, double* f0, int rows, int ld) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < rows) f0[r] = F[(size_t)r * ld];
+}
+
+void transfer_release(DcHandle* h) {
+    DcTransferState* s = h->transfer;
+    if (!s) return;
+    hipStreamSynchronize(h->stream);
+    dc_pair_state_free(h, s->phi);
+    dev_release(h, s->G); dev_release(h, s->f0); dev_release(h, s->b_tc); dev_release(h, s->b_row);
+    dev_release(h, s->r_rec); dev_release(h, s->r_min); dev_release(h, s->r_off); dev_release(h, s->c_min); dev_release(h, s->c_at); dev_release(h, s->c_row);
+    dev_release(h, s->amount); dev_release(h, s->base); dev_release(h, s->rec);
+    delete s;
+    h->transfer = nullptr;
+}
+
+// dirs [T][n]: net injection per unit of transfer; base_rhs [n] nullable: the right-hand side of a base profile as jg_dc_set_rhs takes it
+int transfer_build(DcHandle* h, const std::vector<int>& cand, const std::vector<int>& mon, int T, const double* dirs, const double* base_rhs, int64_t budget,
+                   double* info) {
+    transfer_release(h);
+    const int ldt = (T + 63) / 64 * 64;
+    std::vector<int> label;
+    {
+        std::vector<char> in(h->nbr, 0);
+        for (int m : mon) in[m] = 1;
+        for (int m : cand) in[m] = 1;
+        for (int m = 0; m < h->nbr; ++m) if (in[m]) label.push_back(m + 1);
+    }
+    const int nr = (int)label.size();
+    const size_t g_bytes = (size_t)nr * ldt * sizeof(double);
+    const size_t scratch = dc_series_flows_scratch(h, ldt) + (base_rhs ? (size_t)nr * 64 * sizeof(double) : 0);
+    for (int j = 8; j < 12; ++j) info[j] = 0.0;
+    info[8] = (double)g_bytes;
+    DcTransferState* s = new DcTransferState();
+    h->transfer = s;
+    s->T = T; s->ldt = ldt; s->h_row_label = label;
+    const std::string extra = "; G needs " + dc_pair_bytes_text(g_bytes) + " (" + std::to_string(nr) + " rows x " + std::to_string(ldt) + " transfers x 8) and " +
+                              dc_pair_bytes_text(scratch) + " of scratch";
+    int rc = dc_pair_state_build(h, s->phi, "jg_dc_transfer_build", cand, mon, budget, g_bytes + scratch, extra, info);
+    if (rc) { const std::string msg = h->error; transfer_release(h); h->error = msg; return rc; }
+    DcPairState* p = s->phi;
+    auto step = [&](int r) { if (r && !rc) rc = r; return rc == 0; };
+    auto hip = [&](hipError_t e, const char* what) { if (e != hipSuccess && !rc) { rc = 2; h->error = std::string(what) + ": " + hipGetErrorString(e); } return rc == 0; };
+    double ms[2] = {0.0, 0.0};
+    if (step(dev_alloc(h, &s->G, (size_t)nr * ldt, (const double*)nullptr, true)) && step(dev_alloc(h, &s->f0, (size_t)nr, (const double*)nullptr, true)) &&
+        step(dev_alloc(h, &s->c_min, (size_t)ldt, (const double*)nullptr, true)) && step(dev_alloc(h, &s->c_at, (size_t)ldt, (const int*)nullptr, true)) &&
+        step(dev_alloc(h, &s->c_row, (size_t)ldt, (const int*)nullptr, true)) && step(dev_alloc(h, &s->amount, (size_t)ldt, (const double*)nullptr, true)) &&
+        step(dev_alloc(h, &s->base, (size_t)ldt * 3, (const double*)nullptr, true))) {
+        if (base_rhs) {
+            double* Fb = nullptr;                                // [nr][64]: one lane batch of one lane
+            double unused[2] = {0.0, 0.0};
+            if (step(dev_alloc(h, &Fb, (size_t)nr * 64, (const double*)nullptr, true)) && step(dc_series_row_flows(h, p, 1, base_rhs, true, Fb, 64, unused))) {
+                hipLaunchKernelGGL(k_transfer_pick, dim3((nr + 255) / 256), dim3(256), 0, h->stream, Fb, s->f0, nr, 64);
+                hip(hipGetLastError(), "launch") && hip(hipStreamSynchronize(h->stream), "hipStreamSynchronize");
+            }
+            dev_release(h, Fb);
+        } else {
+            hip(sync_copy(s->f0, p->row_f0, (size_t)nr * sizeof(double), hipMemcpyDeviceToDevice, h->stream), "copy of the base flows");
+        }
+        if (!rc) step(dc_series_row_flows(h, p, T, dirs, false, s->G, ldt, ms));
+        if (!rc) step(dc_series_bridges(h, p, s->h_bridge));
+    }
+    if (rc) { const std::string msg = h->error; transfer_release(h); h->error = msg; return rc; }
+    s->build_ms[0] = ms[0] + ms[1]; s->build_ms[1] = ms[0]; s->build_ms[2] = ms[1];
+    info[9] = s->build_ms[0]; info[10] = ms[0]; info[11] = ms[1];
+    return 0;
+}
+
+// the block's buffers for `rb` rows; grown, never shrunk
+int transfer_block(DcHandle* h, int rb, long long rec_cap) {
+    DcTransferState* s = h->transfer;
+    if (rb > s->blk_rows) {
+        const size_t cells = (size_t)rb * s->ldt, need = cells * 12;
+        dev_release(h, s->b_tc); dev_release(h, s->b_row); dev_release(h, s->r_rec); dev_release(h, s->r_min); dev_release(h, s->r_off);
+        s->blk_rows = 0;
+        size_t free_b = 0, total_b = 0;
+        DC_HIP(hipMemGetInfo(&free_b, &total_b));
+        if (need > free_b) {
+            h->error = "jg_dc_transfer_screen: a block of " + std::to_string(rb) + " rows needs " + dc_pair_bytes_text(need) + ", " + dc_pair_bytes_text(free_b) +
+                       " are free: screen fewer rows per call";
+            return 5;
+        }
+        DC_TRY(dev_alloc(h, &s->b_tc, cells, (const double*)nullptr, true));
+        DC_TRY(dev_alloc(h, &s->b_row, cells, (const int*)nullptr, true));
+        DC_TRY(dev_alloc(h, &s->r_rec, (size_t)rb, (const int*)nullptr, true));
+        DC_TRY(dev_alloc(h, &s->r_min, (size_t)rb, (const double*)nullptr, true));
+        DC_TRY(dev_alloc(h, &s->r_off, (size_t)rb, (const long long*)nullptr, true));
+        s->blk_rows = rb;
+    }
+    if (rec_cap > s->rec_cap) { dev_release(h, s->rec); s->rec_cap = 0; DC_TRY(dev_alloc(h, &s->rec, (size_t)rec_cap * 5, (const double*)nullptr, true)); s->rec_cap = rec_cap; }
+    return 0;
+}
+
+TransferScreenArgs screen_args(DcHandle* h, int k0, int k1, double cutoff) {
+    DcTransferState* s = h->transfer;
+    DcPairState* p = s->phi;
+    TransferScreenArgs a{};
+    a.Phi = p->Phi; a.G = s->G; a.f0 = s->f0; a.rinv = p->row_rinv; a.pos = p->row_pos; a.crow = p->cand_row; a.cdiag = p->cand_diag;
+    a.tc = s->b_tc; a.row = s->b_row;
+    a.cutoff = cutoff; a.rows = p->rows; a.ldk = p->ldk; a.ldt = s->ldt; a.T = s->T; a.k0 = k0; a.k1 = k1; a.kbase = k0 / 64 * 64;
+    return a;
+}
+void launch_screen(DcHandle* h, const TransferScreenArgs& a) {
+    const int tiles = (a.T + DC_TRANSFER_TILE - 1) / DC_TRANSFER_TILE;
+    hipLaunchKernelGGL(k_transfer_screen, dim3((a.k1 - a.kbase + 63) / 64, (tiles + DC_PAIR_WAVES - 1) / DC_PAIR_WAVES), dim3(64, DC_PAIR_WAVES), 0, h->stream, a);
+}
+TransferListArgs list_args(DcHandle* h, int k0, int k1, long long rec_cap) {
+    DcTransferState* s = h->transfer;
+    DcPairState* p = s->phi;
+    TransferListArgs a{};
+    a.tc = s->b_tc; a.row = s->b_row; a.amount = s->amount; a.clabel = p->cand_label; a.rbranch = p->row_branch;
+    a.Phi = p->Phi; a.G = s->G; a.crow = p->cand_row; a.cdiag = p->cand_diag;
+    a.r_rec = s->r_rec; a.r_min = s->r_min; a.r_off = s->r_off; a.rec = s->rec; a.rec_cap = rec_cap;
+    a.ldk = p->ldk; a.ldt = s->ldt; a.T = s->T; a.k0 = k0; a.k1 = k1;
+    return a;
+}
+void launch_stats(DcHandle* h, const TransferListArgs& a) {
+    DcTransferState* s = h->transfer;
+    hipLaunchKernelGGL((k_transfer_rows<false>), dim3((a.k1 - a.k0 + 3) / 4), dim3(64, 4), 0, h->stream, a);
+    hipLaunchKernelGGL(k_transfer_cols, dim3((s->ldt + 255) / 256), dim3(256), 0, h->stream, s->b_tc, s->b_row, s->c_min, s->c_at, s->c_row, s->ldt, s->T, a.k1 - a.k0);
+}
+
+struct TransferOut {
+    const double* amount; double* records; int64_t* islanding; int64_t* totals; double* worst;
+    double* capability; int64_t* cap_outage; int64_t* cap_branch; double* base;
+    double* d_tc; int32_t* d_branch;
+};
+int transfer_screen(DcHandle* h, int k0, int k1, double cutoff, long long rec_cap, const TransferOut& o) {
+    DcTransferState* s = h->transfer;
+    DcPairState* p = s->phi;
+    const int rb = k1 - k0, T = s->T, ldt = s->ldt;
+    const double inf = std::numeric_limits<double>::infinity();
+    DC_TRY(transfer_block(h, rb, rec_cap));
+    {
+        std::vector<double> am(ldt, -inf);                       // no amount: nothing lies below it, no records
+        if (o.amount) std::copy(o.amount, o.amount + T, am.begin());
+        DC_HIP(sync_copy(s->amount, am.data(), (size_t)ldt * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    }
+    dc_pair_state_rinv(h, p);
+    launch_screen(h, screen_args(h, k0, k1, cutoff));
+    TransferListArgs la = list_args(h, k0, k1, rec_cap);
+    launch_stats(h, la);
+    if (o.base) hipLaunchKernelGGL(k_transfer_base, dim3((T + 63) / 64), dim3(64), 0, h->stream, s->G, s->f0, p->row_rinv, s->base, cutoff, p->rows, ldt, T);
+    DC_HIP(hipGetLastError());
+    std::vector<int> nv(rb), cat(ldt), crow(ldt);
+    std::vector<double> rmin(rb), cmin(ldt), base(o.base ? (size_t)T * 3 : 0);
+    DC_HIP(hipMemcpyAsync(nv.data(), s->r_rec, rb * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    DC_HIP(hipMemcpyAsync(rmin.data(), s->r_min, rb * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    DC_HIP(hipMemcpyAsync(cat.data(), s->c_at, ldt * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    DC_HIP(hipMemcpyAsync(crow.data(), s->c_row, ldt * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (o.base) DC_HIP(hipMemcpyAsync(base.data(), s->base, (size_t)T * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    DC_HIP(sync_copy(cmin.data(), s->c_min, ldt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    std::vector<long long> off(rb);
+    long long below = 0, isl = 0;
+    for (int i = 0; i < rb; ++i) {
+        off[i] = below; below += nv[i];
+        if (s->h_bridge[k0 + i]) { if (o.islanding) o.islanding[isl] = p->h_cand[k0 + i] + 1; ++isl; }
+    }
+    const long long nrec = std::min(below, rec_cap);
+    if (nrec) {
+        DC_HIP(hipMemcpyAsync(s->r_off, off.data(), rb * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+        hipLaunchKernelGGL((k_transfer_rows<true>), dim3((rb + 3) / 4), dim3(64, 4), 0, h->stream, la);
+        DC_HIP(hipGetLastError());
+        DC_HIP(hipMemcpyAsync(o.records, s->rec, (size_t)nrec * 5 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        DC_HIP(hipStreamSynchronize(h->stream));                // (off goes out of scope behind it)
+    }
+    o.totals[0] = (long long)rb * T; o.totals[1] = below; o.totals[2] = isl; o.totals[3] = nrec; o.totals[4] = below > rec_cap ? 1 : 0;
+    if (o.worst) for (int i = 0; i < rb; ++i) o.worst[k0 + i] = s->h_bridge[k0 + i] ? std::numeric_limits<double>::quiet_NaN() : rmin[i];
+    if (o.capability && o.cap_outage && o.cap_branch)
+        for (int t = 0; t < T; ++t)
+            if (cmin[t] < o.capability[t]) {                    // strict, blocks ascending: the first candidate that gives the least value, whatever the block size
+                o.capability[t] = cmin[t]; o.cap_outage[t] = p->h_cand[k0 + cat[t]] + 1; o.cap_branch[t] = crow[t] < 0 ? 0 : s->h_row_label[crow[t]];
+            }
+    if (o.base)
+        for (int t = 0; t < T; ++t) {
+            const int r = (int)base[(size_t)t * 3 + 1];
+            o.base[(size_t)t * 3] = base[(size_t)t * 3]; o.base[(size_t)t * 3 + 1] = r < 0 ? 0.0 : (double)s->h_row_label[r]; o.base[(size_t)t * 3 + 2] = base[(size_t)t * 3 + 2];
+        }
+    if (o.d_tc) {
+        std::vector<double> v((size_t)rb * ldt);
+        DC_HIP(sync_copy(v.data(), s->b_tc, v.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        for (int i = 0; i < rb; ++i) std::copy(v.begin() + (size_t)i * ldt, v.begin() + (size_t)i * ldt + T, o.d_tc + (size_t)i * T);
+    }
+    if (o.d_branch) {
+        std::vector<int> v((size_t)rb * ldt);
+        DC_HIP(sync_copy(v.data(), s->b_row, v.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        for (int i = 0; i < rb; ++i)
+            for (int t = 0; t < T; ++t) { const int r = v[(size_t)i * ldt + t]; o.d_branch[(size_t)i * T + t] = r < 0 ? 0 : s->h_row_label[r]; }
+    }
+    return 0;
+}
+
+}  // namespace
+
+void dc_transfer_free(DcHandle* h) { transfer_release(h); }
+
+}  // namespace jg
+
+using jg::DcHandle;
+
+using jg::api_fail;
+
+extern "C" {
+
+int jg_dc_transfer_build(int64_t h, int64_t nk, const int64_t* candidates, int64_t nm, const int64_t* monitored, int64_t transfers, const double* directions,
+                         const double* base_rhs, int64_t budget_bytes, double* info) {
+    DC_ENTER(h);
+    if (!d->nbr) return api_fail(1, "jg_dc_transfer_build: jg_dc_set_branches first");
+    if (d->h_rhs.empty()) return api_fail(1, "jg_dc_transfer_build: jg_dc_set_rhs first");
+    if (nk < 1 || !candidates || !info || nm < 0 || (nm && !monitored)) return api_fail(1, "jg_dc_transfer_build: one or more candidates, and info, are needed");
+    if (transfers < 1 || transfers > (1 << 24) || !directions) return api_fail(1, "jg_dc_transfer_build: one or more transfer directions are needed");
+    std::vector<int> cand, mon;
+    DC_RET(jg::dc_pair_lists(d, "jg_dc_transfer_build", nk, candidates, nm, monitored, cand, mon));
+    DC_RET(jg::transfer_build(d, cand, mon, (int)transfers, directions, base_rhs, budget_bytes, info));
+    return 0;
+}
+
+int jg_dc_transfer_screen(int64_t h, int64_t k0, int64_t k1, double cutoff, const double* amount, int64_t capacity, double* records, int64_t* islanding,
+                          int64_t* totals, double* worst, double* capability, int64_t* limiting_outage, int64_t* limiting_branch, double* base,
+                          double* dense_capability, int32_t* dense_branch) {
+    DC_ENTER(h);
+    if (!d->transfer) return api_fail(4, "jg_dc_transfer_screen: jg_dc_transfer_build first");
+    if (!d->b_rating) return api_fail(1, "jg_dc_transfer_screen: jg_dc_set_rating first (a branch limits at |from| = rating)");
+    if (k0 < 0 || k1 <= k0 || k1 > d->transfer->phi->nk) return api_fail(1, "jg_dc_transfer_screen: rows [k0, k1) out of range");
+    if (!(cutoff > 0.0) || capacity < 0 || (capacity && !records) || !totals) return api_fail(1, "jg_dc_transfer_screen: bad argument");
+    if ((capability || limiting_outage || limiting_branch) && !(capability && limiting_outage && limiting_branch))
+        return api_fail(1, "jg_dc_transfer_screen: capability, limiting_outage and limiting_branch go together");
+    jg::TransferOut o{amount, records, islanding, totals, worst, capability, limiting_outage, limiting_branch, base, dense_capability, dense_branch};
+    DC_RET(jg::transfer_screen(d, (int)k0, (int)k1, cutoff, amount ? capacity : 0, o));
+    return 0;
+}
+
+int jg_dc_transfer_time_kernel(int64_t h, int kernel, int64_t k0, int64_t k1, int reps, double* ms) {
+    DC_ENTER(h);
+    if (!d->transfer) return api_fail(4, "jg_dc_transfer_time_kernel: jg_dc_transfer_build first");
+    if (!ms || reps < 1 || kernel < 0 || kernel > 1 || k0 < 0 || k1 <= k0 || k1 > d->transfer->phi->nk) return api_fail(1, "jg_dc_transfer_time_kernel: bad argument");
+    if (k1 - k0 > d->transfer->blk_rows) return api_fail(4, "jg_dc_transfer_time_kernel: jg_dc_transfer_screen with a block of at least these rows first");
+    const jg::TransferScreenArgs sa = jg::screen_args(d, (int)k0, (int)k1, 1e-6);
+    const jg::TransferListArgs la = jg::list_args(d, (int)k0, (int)k1, 0);
+    DC_RET(jg::time_events(d->stream, reps, ms, d->error, [&]() -> int {
+        if (kernel == 0) jg::launch_screen(d, sa);
+        else jg::launch_stats(d, la);
+        return 0;
+    }));
+    return 0;
+}
+
+int jg_dc_transfer_release(int64_t h) {
+    DC_ENTER(h);
+    jg::dc_transfer_free(d);
+    return 0;
+}
+
+}  // extern "C"

@@ -8,6 +8,7 @@
                                                          outage is solved on the slack's island, which the reference cannot do)
   the same loop over ALL pairs of a candidate list          dcPairScreen (the DC N-2 screen: csrc/jg_dc_pair.hpp)
   the N-1 loop inside a loop over injection profiles        dcSeriesScreen (csrc/jg_dc_series.hpp)
+  the N-1 loop while the injections move along a direction  dcTransferScreen (the transfer capability: csrc/jg_dc_transfer.hpp)
 
 All numerics run in libjgrid_hip.so (csrc/jg_dc.hip); the O(n) bus / generator bookkeeping of power! runs here.  A batched analysis keeps
 `batch` scenarios of ONE grid on the device; arrays are [batch, ...] (1-D for batch 1), as in the AC analysis.
@@ -519,3 +520,137 @@ def dcSeriesScreen(analysis_or_system, injections, candidates=None, monitored=No
             an.close()
         else:
             _lib.check(L.jg_dc_series_release(an._h))
+
+
+class DcTransferScreen:
+    """What dcTransferScreen returns.
+      candidates  [K] branch labels (1-based, ascending); monitored the labels of the call; transfers = T; cutoff; rows = (k0, k1)
+      capability  [T] the least transfer capability over the base case and the screened outages (+inf: nothing limits the transfer; negative: a
+                  branch is beyond its rating at zero transfer), limitingOutage [T] the branch label whose outage gives it (0: the base case) and
+                  limitingBranch [T] the branch that reaches its rating (0: none); ties go to the base case, then to the lowest candidate
+      base        [T, 3] the base case of every transfer, no outage: capability, limiting branch label, monitored branches above their rating at zero transfer
+      worst       [K] the least capability over all transfers of each screened candidate (NaN on a bridge, +inf outside `rows`)
+      records     [r, 5] the cases (k, t) whose capability lies below amount[t], sorted by (k, t): label k, transfer index t (0-based row of
+                  `transfers`), limiting branch label, capability, flow sensitivity g of the limiting branch; empty without `amount`
+      overflow    the record list was cut at its capacity: it holds the FIRST entries by (k, t)
+      islanding   labels of the screened candidates that are bridges (status 3): NaN capability for every transfer, never in `records` or a minimum
+      totals      dict(cases = rows screened x T, limited = cases below their amount, islanding = bridge candidates): exact also when the list overflowed
+      capabilityCases, branch   with dense=True: [k1 - k0, T]
+      info        dict(rows, ld, phiBytes, freeBytes, budgetBytes, buildMs, sweepMs, phiMs, gBytes, gBuildMs, gSweepMs, gKernelMs)"""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+TRANSFER_BLOCK_BYTES = 256 << 20                                       # default bound of the dense result of one device call (12 bytes per case)
+
+
+def transferDirection(system: PowerSystem, source, sink, sourceShare=None, sinkShare=None) -> np.ndarray:
+    """A transfer direction [buses] for dcTransferScreen: +1 spread over the buses `source` (labels) and -1 over the buses `sink`, by the shares given
+    (normalised to sum 1 on each side; equal by default).  A bus may stand on both sides."""
+    d = np.zeros(system.bus.number)
+    for name, labels, share, sign in (("source", source, sourceShare, 1.0), ("sink", sink, sinkShare, -1.0)):
+        labels = [int(x) for x in np.atleast_1d(np.asarray(labels)).ravel()]
+        if not labels:
+            raise ValueError(f"transferDirection: {name} names no bus")
+        missing = [x for x in labels if x not in system.bus.label]
+        if missing:
+            raise KeyError(f"The bus label {missing[0]} that has been specified does not exist.")
+        w = np.ones(len(labels)) if share is None else np.asarray(share, dtype=np.float64).ravel()
+        if w.shape != (len(labels),) or not np.isfinite(w).all() or (w < 0).any() or not w.sum() > 0:
+            raise ValueError(f"transferDirection: {name}Share needs one finite value >= 0 per bus and a positive sum")
+        np.add.at(d, [system.bus.label[x] - 1 for x in labels], sign * w / w.sum())
+    return d
+
+
+def dcTransferScreen(analysis_or_system, transfers, candidates=None, monitored=None, rating=None, amount=None, cutoff: float = 1e-6, injection=None,
+                     rows=None, capacity: int = 1 << 20, dense: bool = False, block=None, budget=None, device: int = 0) -> DcTransferScreen:
+    """The DC transfer-capability screen: how far the injections can move along direction t of `transfers` ([T, buses] net active injection per unit of
+    transfer, the meaning of setInjection_; transferDirection builds one; the slack takes what a direction does not balance) before the first monitored
+    branch reaches its rating, in the base case and with branch k of `candidates` (labels; default pairCandidates(system)) out of service -- the loop
+    that raises updateBus! / updateGenerator! along a direction around updateBranch!(k, status = 0), solve!, power! per branch, from ONE factor, one
+    sweep pair per candidate and one per direction (csrc/jg_dc_transfer.hpp).  A branch limits only where its flow moves by more than `cutoff` per unit
+    of transfer.  `injection` ([buses], default: the system's own) is the base operating point; `amount` (a value or [T]) asks for the records of the
+    cases that cannot carry that much.  `monitored`, `rating`, `rows`, `block`, `budget` and `capacity` mean what they mean for dcSeriesScreen."""
+    own = isinstance(analysis_or_system, PowerSystem)
+    system = analysis_or_system if own else analysis_or_system.system
+    who = "dcTransferScreen"
+    if rating is None:
+        raise ValueError(f"{who}: rating (per branch, per unit of active power) is needed")
+    if not cutoff > 0:
+        raise ValueError(f"{who}: cutoff > 0")
+    d = np.asarray(transfers, dtype=np.float64)
+    if d.ndim != 2 or d.shape[0] < 1 or d.shape[1] != system.bus.number:
+        raise ValueError(f"{who}: transfers must be [T, buses] with T >= 1")
+    if not np.isfinite(d).all():
+        raise ValueError(f"{who}: transfers must be finite")
+    zero = np.flatnonzero(~d.any(axis=1))
+    if zero.size:
+        raise ValueError(f"{who}: transfer {int(zero[0])} is all zero: it moves nothing")
+    T = int(d.shape[0])
+    if amount is not None:
+        amount = np.ascontiguousarray(np.broadcast_to(np.asarray(amount, dtype=np.float64), (T,)) if np.ndim(amount) == 0 else np.asarray(amount, dtype=np.float64))
+        if amount.shape != (T,) or np.isnan(amount).any():
+            raise ValueError(f"{who}: amount is one value, or one per transfer, and no NaN")
+    if injection is not None:
+        injection = np.asarray(injection, dtype=np.float64)
+        if injection.shape != (system.bus.number,) or not np.isfinite(injection).all():
+            raise ValueError(f"{who}: injection must be [buses] and finite")
+    if own and system.model.dc.nodalMatrix is None:
+        dcModel_(system)
+    cand, mon, rating = _pair_lists(system, candidates, monitored, rating, who=who, least=1)
+    nk = int(cand.size)
+    k0, k1 = (0, nk) if rows is None else (int(rows[0]), min(int(rows[1]), nk))
+    if k0 < 0 or k1 < k0:
+        raise ValueError(f"{who}: rows = (k0, k1) with 0 <= k0 <= k1 <= candidates")
+    ldt = (T + 63) // 64 * 64
+    step = max(1, TRANSFER_BLOCK_BYTES // (ldt * 12)) if block is None else int(block)
+    if step < 1:
+        raise ValueError(f"{who}: block >= 1")
+    an = dcPowerFlow(system, device=device) if own else analysis_or_system
+    L = _lib.lib()
+    try:
+        if an._rhs is None:
+            an._rhs = np.ascontiguousarray(_base_rhs(system), dtype=np.float64)
+            _lib.check(L.jg_dc_set_rhs(an._h, an._rhs))
+        _set_rating(an, rating)
+        ptr = lambda a: None if a is None else a.ctypes.data_as(_lib.VP)
+        base_rhs = None if injection is None else np.ascontiguousarray(injection - system.bus.shunt.conductance - system.model.dc.shiftPower)
+        info = np.zeros(12)
+        _lib.check(L.jg_dc_transfer_build(an._h, nk, cand, int(mon.size), mon.ctypes.data_as(_lib.VP), T, np.ascontiguousarray(d).reshape(-1), ptr(base_rhs),
+                                          int(budget or 0), info))
+        rec = np.zeros((max(int(capacity), 0) if amount is not None else 0, 5))
+        worst, base = np.full(nk, np.inf), np.zeros((T, 3))
+        cap, capOutage, capBranch = np.full(T, np.inf), np.zeros(T, dtype=np.int64), np.zeros(T, dtype=np.int64)
+        tot = np.zeros(3, dtype=np.int64)
+        nrec, bridges = 0, []
+        full = {name: np.zeros((k1 - k0, T), dtype=dt) for name, dt in (("capabilityCases", np.float64), ("branch", np.int32))} if dense else {}
+        for b0 in range(k0, k1, step):
+            b1 = min(b0 + step, k1)
+            t5 = np.zeros(5, dtype=np.int64)
+            isl = np.zeros(b1 - b0, dtype=np.int64)
+            part = {name: a[b0 - k0:b1 - k0] for name, a in full.items()}                     # (row slices of a C-contiguous array are contiguous)
+            r = rec[nrec:]
+            _lib.check(L.jg_dc_transfer_screen(an._h, b0, b1, float(cutoff), ptr(amount), r.shape[0], ptr(r) if r.shape[0] else None, ptr(isl), t5, ptr(worst),
+                                               ptr(cap), ptr(capOutage), ptr(capBranch), ptr(base) if b0 == k0 else None,
+                                               ptr(part.get("capabilityCases")), ptr(part.get("branch"))))
+            tot += t5[:3]
+            nrec += int(t5[3])
+            bridges.append(isl[:int(t5[2])])
+        first = base[:, 0] <= cap                                       # ties go to the base case
+        res = DcTransferScreen(candidates=cand, monitored=mon, transfers=T, cutoff=float(cutoff), rows=(k0, k1),
+                               capability=np.where(first, base[:, 0], cap), limitingOutage=np.where(first, 0, capOutage),
+                               limitingBranch=np.where(first, base[:, 1].astype(np.int64), capBranch), base=base, worst=worst, records=rec[:nrec].copy(),
+                               overflow=bool(tot[1] > nrec),
+                               islanding=np.concatenate(bridges) if bridges else np.zeros(0, dtype=np.int64),
+                               totals=dict(cases=int(tot[0]), limited=int(tot[1]), islanding=int(tot[2])),
+                               info=dict(zip(("rows", "ld", "phiBytes", "freeBytes", "budgetBytes", "buildMs", "sweepMs", "phiMs", "gBytes", "gBuildMs",
+                                              "gSweepMs", "gKernelMs"), (float(x) for x in info))))
+        for name, a in full.items():
+            setattr(res, name, a)
+        return res
+    finally:
+        if own:
+            an.close()
+        else:
+            _lib.check(L.jg_dc_transfer_release(an._h))
