@@ -1422,6 +1422,24 @@ function seriesTimeKernel(b::DcPowerFlowBatch, kernel::Int, k0::Int64, k1::Int64
 end
 "frees the sensitivities and base flows a series screen keeps on the device"
 seriesScreenRelease!(b::DcPowerFlowBatch) = check(ccall((:jg_dc_series_release, lib), Cint, (Int64,), b.token))
+"island mode of the NEXT `seriesScreenBuild!`: 0 a bridge candidate is skipped (status 3), 1 it is screened on the slack's island (jgrid.h)"
+seriesScreenIslandMode!(b::DcPowerFlowBatch, mode::Int) = check(ccall((:jg_dc_series_set_island_mode, lib), Cint, (Int64, Cint), b.token, mode))
+"""
+    seriesScreenShed(b, k0, k1, profiles) -> (branches, buses, m, side, flow [T, bridges])
+
+The bridge candidates among the positions k0 .. k1 - 1 (0-based) of a series screen built in island mode 1: the branch, the number of buses that leave, the
+bridge's end on the slack's side, which end that is (+1 from, -1 to), and the flow that left that end over the bridge before the outage, per profile.
+"""
+function seriesScreenShed(b::DcPowerFlowBatch, k0::Int64, k1::Int64, profiles::Int64)
+    count = zeros(Int64, 1)
+    branches = zeros(Int64, max(k1 - k0, 1)); buses = zeros(Int64, max(k1 - k0, 1)); m = zeros(Int64, max(k1 - k0, 1)); side = zeros(Int64, max(k1 - k0, 1))
+    check(ccall((:jg_dc_series_get_shed_table, lib), Cint, (Int64, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}),
+        b.token, k0, k1, count, branches, buses, m, side))
+    c = count[1]
+    flow = zeros(Float64, profiles, max(c, 1))
+    c > 0 && check(ccall((:jg_dc_series_get_shed, lib), Cint, (Int64, Int64, Int64, Ptr{Float64}), b.token, k0, k1, flow))
+    return branches[1:c], buses[1:c], m[1:c], side[1:c], flow[:, 1:c]
+end
 """
     transferScreenBuild!(b, candidates, directions; baseRhs = nothing, monitored = nothing, budget = 0) -> info [12]
 
@@ -1475,6 +1493,24 @@ function transferTimeKernel(b::DcPowerFlowBatch, kernel::Int, k0::Int64, k1::Int
 end
 "frees the sensitivities a transfer screen keeps on the device"
 transferScreenRelease!(b::DcPowerFlowBatch) = check(ccall((:jg_dc_transfer_release, lib), Cint, (Int64,), b.token))
+"island mode of the NEXT `transferScreenBuild!`: 0 a bridge candidate is skipped (status 3), 1 it is screened on the slack's island (jgrid.h)"
+transferScreenIslandMode!(b::DcPowerFlowBatch, mode::Int) = check(ccall((:jg_dc_transfer_set_island_mode, lib), Cint, (Int64, Cint), b.token, mode))
+"""
+    transferScreenShed(b, k0, k1, transfers) -> (branches, buses, m, side, flow [bridges], transfer [T, bridges])
+
+The bridge candidates among the positions k0 .. k1 - 1 (0-based) of a transfer screen built in island mode 1, as `seriesScreenShed`: the flow that left the
+bridge's end on the slack's side at zero transfer, and per unit of each transfer (not 0: the direction is partly shed with the bridge).
+"""
+function transferScreenShed(b::DcPowerFlowBatch, k0::Int64, k1::Int64, transfers::Int64)
+    count = zeros(Int64, 1)
+    branches = zeros(Int64, max(k1 - k0, 1)); buses = zeros(Int64, max(k1 - k0, 1)); m = zeros(Int64, max(k1 - k0, 1)); side = zeros(Int64, max(k1 - k0, 1))
+    check(ccall((:jg_dc_transfer_get_shed_table, lib), Cint, (Int64, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}),
+        b.token, k0, k1, count, branches, buses, m, side))
+    c = count[1]
+    flow = zeros(Float64, max(c, 1)); per = zeros(Float64, transfers, max(c, 1))
+    c > 0 && check(ccall((:jg_dc_transfer_get_shed, lib), Cint, (Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}), b.token, k0, k1, flow, per))
+    return branches[1:c], buses[1:c], m[1:c], side[1:c], flow[1:c], per[:, 1:c]
+end
 
 # ---- DC state estimation with batched bad-data removal (jgrid.h: jg_dcse_*; csrc/jg_dcse.hip) ------------------------------------------------
 # dcStateEstimation / solve! / power! / residualTest! / chiTest (src/stateEstimation/dcStateEstimation.jl:42-151, 342-434, badData.jl:48-117, 963-977) for
@@ -1656,6 +1692,6 @@ export HIP, HIPOrthogonal, NewtonRaphsonBatch, BaseCase, baseInfo, baseInverseOn
        largestNormalizedResidual, normalizedResiduals, commUniqueId, Comm, shard, contingencyAnalysis, clearPlanCache,
        deviceCount, dims, setRefinement!, deviceMaps, setOutage!, snapshotVoltage!, restoreVoltage!, iterations, voltageDevice!, packResults!, packRows!,
        allgatherDevice, commRank, commWorld, timeKernel, setBusType!, busType, GaussNewtonBatch, setRealisations!, monteCarloEstimation, fastPatch!, setReadings!, drawNoise!, measurementDevice,
-       DcPowerFlowBatch, setInjections!, setOutagePairs!, pairScreenBuild!, pairScreen, pairTimeKernel, pairScreenRelease!, seriesScreenBuild!, seriesScreen, seriesTimeKernel, seriesScreenRelease!, setIslandMode!, islands, islandTable, fromPower, angleDevice, DcStateEstimationBatch, removedRows, removeRows!
+       DcPowerFlowBatch, setInjections!, setOutagePairs!, pairScreenBuild!, pairScreen, pairTimeKernel, pairScreenRelease!, seriesScreenIslandMode!, seriesScreenShed, transferScreenIslandMode!, transferScreenShed, seriesScreenBuild!, seriesScreen, seriesTimeKernel, seriesScreenRelease!, setIslandMode!, islands, islandTable, fromPower, angleDevice, DcStateEstimationBatch, removedRows, removeRows!
 
 end # module

@@ -598,6 +598,17 @@ int jg_dc_pair_release(int64_t h);
  *   jg_dc_series_time_kernel   milliseconds of `reps` runs on rows [k0, k1) (a block jg_dc_series_screen has held): 0 the screen kernel, 1 the row /
  *                       column summaries behind it
  *   jg_dc_series_release  frees what the screen holds on the device
+ * Bridge candidates screened on the slack's island (csrc/jg_dc_series.hpp, "shed mode"):
+ *   jg_dc_series_set_island_mode   the island mode of the NEXT jg_dc_series_build, which takes it and sets it back to 0.  0: a bridge candidate is
+ *                       skipped (status 3, as above).  1: a candidate the graph calls a bridge (the table of jg_dc_island_table on the handle's branches)
+ *                       is solved as jg_dc_set_island_mode 1 solves a lane: the buses behind it leave, a branch with an end among them carries 0, the
+ *                       worst loading, its branch and the count cover the branches that stay, and the case enters the records, worst, worst_profile
+ *                       and violating_profile like any other; it is not in `islanding`, which keeps the non-bridges with |1 - Phi[k,k]| < 1e-9.
+ *   jg_dc_series_get_shed_table    the bridge candidates among the POSITIONS [k0, k1) of a build in mode 1 (none after a build in mode 0): *count, and
+ *                       per bridge (each [k1 - k0], nullable) the branch (1-based), the buses that leave, the bridge's end m on the slack's side
+ *                       (1-based bus), side +1 / -1: m is the from / to end.
+ *   jg_dc_series_get_shed          flow [count][profiles]: what left m over the bridge before the outage, per bridge of [k0, k1) in the order of the
+ *                       table and per profile, gathered on the device.  The right-hand side summed over what leaves is its negative.
  */
 int jg_dc_series_build(int64_t h, int64_t nk, const int64_t* candidates, int64_t nm, const int64_t* monitored, int64_t profiles, const double* rhs,
                        int64_t budget_bytes, double* info12);
@@ -606,6 +617,9 @@ int jg_dc_series_screen(int64_t h, int64_t k0, int64_t k1, double threshold, int
                         int32_t* dense_count);
 int jg_dc_series_time_kernel(int64_t h, int kernel, int64_t k0, int64_t k1, int reps, double* ms);
 int jg_dc_series_release(int64_t h);
+int jg_dc_series_set_island_mode(int64_t h, int mode);
+int jg_dc_series_get_shed_table(int64_t h, int64_t k0, int64_t k1, int64_t* count, int64_t* branches, int64_t* buses, int64_t* m, int64_t* side);
+int jg_dc_series_get_shed(int64_t h, int64_t k0, int64_t k1, double* flow);
 /*
  * The DC transfer-capability screen over transfers x N-1 outages (csrc/jg_dc_transfer.hpp): the user loop that raises the injections along a direction
  * with updateBus! / updateGenerator! around updateBranch!(k, status = 0), solve!, power! per branch until a monitored branch reaches its rating.  No
@@ -638,6 +652,13 @@ int jg_dc_series_release(int64_t h);
  *   jg_dc_transfer_time_kernel   milliseconds of `reps` runs on rows [k0, k1) (a block jg_dc_transfer_screen has held): 0 the screen kernel, 1 the row /
  *                       column summaries behind it
  *   jg_dc_transfer_release  frees what the screen holds on the device
+ * Bridge candidates screened on the slack's island, as for the series screen:
+ *   jg_dc_transfer_set_island_mode the island mode of the NEXT jg_dc_transfer_build (0 / 1 as jg_dc_series_set_island_mode).  In mode 1 a branch that
+ *                       leaves with a bridge candidate limits nothing; the case has a real TC and limiting branch (+inf and 0 when nothing eligible
+ *                       stays) and enters the records and the minima like any other.
+ *   jg_dc_transfer_get_shed_table  as jg_dc_series_get_shed_table.
+ *   jg_dc_transfer_get_shed        flow [count]: what left m over the bridge at zero transfer; transfer [count][transfers]: per unit of each transfer
+ *                       (not 0: the direction has a source or sink behind the bridge and is partly shed with it).
  */
 int jg_dc_transfer_build(int64_t h, int64_t nk, const int64_t* candidates, int64_t nm, const int64_t* monitored, int64_t transfers,
                          const double* directions, const double* base_rhs, int64_t budget_bytes, double* info12);
@@ -646,6 +667,9 @@ int jg_dc_transfer_screen(int64_t h, int64_t k0, int64_t k1, double cutoff, cons
                           double* dense_capability, int32_t* dense_branch);
 int jg_dc_transfer_time_kernel(int64_t h, int kernel, int64_t k0, int64_t k1, int reps, double* ms);
 int jg_dc_transfer_release(int64_t h);
+int jg_dc_transfer_set_island_mode(int64_t h, int mode);
+int jg_dc_transfer_get_shed_table(int64_t h, int64_t k0, int64_t k1, int64_t* count, int64_t* branches, int64_t* buses, int64_t* m, int64_t* side);
+int jg_dc_transfer_get_shed(int64_t h, int64_t k0, int64_t k1, double* flow, double* transfer);
 
 /* ---------------------------------------------------------------------------------------------
  * DC state estimation with batched bad-data removal (csrc/jg_dcse.hip)

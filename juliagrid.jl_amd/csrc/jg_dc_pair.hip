@@ -208,7 +208,7 @@ void state_release(DcHandle* h, DcPairState*& slot) {
     dev_release(h, p->row_rinv); dev_release(h, p->cand_row); dev_release(h, p->cand_label); dev_release(h, p->cand_diag); dev_release(h, p->cand_f0);
     dev_release(h, p->b_load); dev_release(h, p->b_branch); dev_release(h, p->b_count); dev_release(h, p->b_det);
     dev_release(h, p->r_viol); dev_release(h, p->r_isl); dev_release(h, p->r_max); dev_release(h, p->r_off); dev_release(h, p->r_ioff);
-    dev_release(h, p->c_max); dev_release(h, p->rec); dev_release(h, p->isl);
+    dev_release(h, p->c_max); dev_release(h, p->rec); dev_release(h, p->isl); dev_release(h, p->cand_isl); dev_release(h, p->row_pre);
     delete p;
     slot = nullptr;
 }
@@ -223,7 +223,7 @@ std::string bytes_text(size_t b) {
 // the build of Phi into `slot` (the pair screen's h->pair, or the state the series screen keeps): `extra` bytes the caller will ask for beside Phi are
 // part of the memory question, `extra_text` names them in the refusal
 int state_build(DcHandle* h, DcPairState*& slot, const char* who, const std::vector<int>& cand, const std::vector<int>& mon, int64_t budget, size_t extra,
-                const std::string& extra_text, double* info) {
+                const std::string& extra_text, double* info, bool shed) {
     state_release(h, slot);
     if (h->base_dirty) DC_TRY(dc_base_solve(h));
     const int nk = (int)cand.size(), ldk = (nk + 63) / 64 * 64, n = h->n;
@@ -242,7 +242,8 @@ int state_build(DcHandle* h, DcPairState*& slot, const char* who, const std::vec
     const int nr = (int)rows.size();
     const int ldb = std::min(ldk, DC_PAIR_LANES);
     const size_t phi_bytes = (size_t)nr * ldk * sizeof(double);
-    const size_t scratch = ((size_t)2 * n + 1) * ldb * sizeof(double) + (size_t)2 * ldb * sizeof(int);
+    const size_t scratch = ((size_t)2 * n + 1) * ldb * sizeof(double) + (size_t)2 * ldb * sizeof(int) +
+                           (shed ? ((size_t)4 * ldk + nr) * sizeof(int) : 0);       // (shed mode: the candidates' intervals and the rows' preorder numbers)
     size_t free_b = 0, total_b = 0;
     DC_HIP(hipMemGetInfo(&free_b, &total_b));
     const size_t allowed = budget > 0 ? (size_t)budget : (size_t)(DC_PAIR_BUDGET * (double)free_b);
@@ -266,6 +267,23 @@ int state_build(DcHandle* h, DcPairState*& slot, const char* who, const std::vec
     DC_TRY(dev_alloc(h, &p->cand_diag, (size_t)ldk, (const double*)nullptr, true));
     DC_TRY(dev_alloc(h, &p->cand_f0, (size_t)ldk, (const double*)nullptr, true));
     DC_TRY(dev_alloc(h, &p->c_max, (size_t)ldk, (const double*)nullptr, true));
+    if (shed) {
+        if (h->h_pre.empty()) {                                  // the table of the handle's grid, once (jg_dc_set_island_mode makes the same)
+            h->h_pre.resize(n); h->h_blo.resize(h->nbr); h->h_bhi.resize(h->nbr); h->h_bside.resize(h->nbr);
+            dc_island_table(n, h->nbr, h->h_from.data(), h->h_to.data(), h->h_y.data(), h->slack, h->h_pre.data(), h->h_blo.data(), h->h_bhi.data(), h->h_bside.data());
+        }
+        p->shed = true;
+        p->h_side.assign(nk, 0); p->h_lo.assign(nk, 1); p->h_hi.assign(nk, 0);
+        std::vector<int> cisl((size_t)4 * ldk, 0), rpre(nr);
+        for (int j = 0; j < ldk; ++j) cisl[4 * j + 1] = 1;
+        for (int j = 0; j < nk; ++j)
+            if (h->h_bside[cand[j]] != 0) {
+                p->h_side[j] = cisl[4 * j] = h->h_bside[cand[j]]; p->h_lo[j] = cisl[4 * j + 1] = h->h_blo[cand[j]]; p->h_hi[j] = cisl[4 * j + 2] = h->h_bhi[cand[j]];
+            }
+        for (int r = 0; r < nr; ++r) rpre[r] = h->h_pre[h->h_from[rows[r]]];
+        DC_TRY(dev_alloc(h, &p->cand_isl, (size_t)4 * ldk, cisl.data()));
+        DC_TRY(dev_alloc(h, &p->row_pre, (size_t)nr, rpre.data()));
+    }
     // scratch of the build: the lanes' outage buses and one lane batch of the sweeps
     int* of = nullptr; int* ot = nullptr; double* W = nullptr; double* Z = nullptr;
     DC_TRY(dev_alloc(h, &of, (size_t)ldb, (const int*)nullptr, false));
@@ -287,6 +305,10 @@ int state_build(DcHandle* h, DcPairState*& slot, const char* who, const std::vec
                 const int m = cand[q];
                 hf[j] = h->h_from[m] == h->slack ? -1 : h->h_from[m];     // the slack's component of a = e_from - e_to is dropped
                 ht[j] = h->h_to[m] == h->slack ? -1 : h->h_to[m];
+                if (shed && p->h_side[q] != 0) {                 // a bridge: e_m of its end on the slack's side (all zero where that is the slack)
+                    if (p->h_side[q] < 0) hf[j] = ht[j];
+                    ht[j] = -1;
+                }
             }
         }
         if (!hip(sync_copy(of, hf.data(), ldb * sizeof(int), hipMemcpyHostToDevice, h->stream), "upload") ||
@@ -440,8 +462,8 @@ int pair_screen(DcHandle* h, int k0, int k1, double thr, long long rec_cap, long
 void dc_pair_free(DcHandle* h) { pair_release(h); }
 void dc_pair_state_free(DcHandle* h, DcPairState*& slot) { state_release(h, slot); }
 int dc_pair_state_build(DcHandle* h, DcPairState*& slot, const char* who, const std::vector<int>& cand, const std::vector<int>& mon, int64_t budget,
-                        size_t extra, const std::string& extra_text, double* info) {
-    return state_build(h, slot, who, cand, mon, budget, extra, extra_text, info);
+                        size_t extra, const std::string& extra_text, double* info, bool shed) {
+    return state_build(h, slot, who, cand, mon, budget, extra, extra_text, info, shed);
 }
 void dc_pair_state_rinv(DcHandle* h, DcPairState* p) {
     hipLaunchKernelGGL(k_pair_rinv, dim3((p->rows + 255) / 256), dim3(256), 0, h->stream, h->b_rating, p->row_branch, p->row_mon, p->row_rinv, p->rows);

@@ -43,6 +43,11 @@ struct DcPairState {
     int* cand_label = nullptr;               // [ldk] 1-based branch label of a candidate
     double* cand_diag = nullptr;             // [ldk] Phi[k,k]
     double* cand_f0 = nullptr;               // [ldk]
+    // shed mode of the series / transfer build (jg_dc_series.hpp): a bridge candidate's column holds Z[:,k] = y_l a_l' B^-1 e_m instead of Phi[:,k]
+    bool shed = false;
+    std::vector<int> h_side, h_lo, h_hi;     // [nk] dc_island_table of the candidates: side 0: not a bridge; lo .. hi the preorder interval of what leaves
+    int* cand_isl = nullptr;                 // [ldk][4] side, lo, hi, 0 ((0, 1, 0, 0): not a bridge, the interval is empty)
+    int* row_pre = nullptr;                  // [rows] preorder number of the from end of the row's branch
     // the row block of a screen call (grown on demand)
     int blk_rows = 0;
     double* b_load = nullptr; int* b_branch = nullptr; int* b_count = nullptr; double* b_det = nullptr;     // [blk_rows][ldk]; b_det only on request
@@ -59,12 +64,13 @@ void dc_pair_free(DcHandle* h);              // releases what the pair screen ho
 // The build of Phi is shared with the series screen (jg_dc_series.hpp), which keeps a state of its own beside h->pair:
 //   dc_pair_lists        the candidate / monitored lists of a build call (1-based in, 0-based out) with the checks of jg_dc_pair_build; 1 and h->error
 //   dc_pair_state_build  replaces `slot` by a fresh build.  `extra` bytes the caller keeps beside Phi count in the memory question (code 5, nothing
-//                        allocated, `extra_text` names them in the message); info [8] as jg_dc_pair_build
+//                        allocated, `extra_text` names them in the message); info [8] as jg_dc_pair_build.  `shed`: the candidates the handle's island
+//                        table (dc_island_table, the graph) calls bridges get the sweep pair on e_m and the tables above
 //   dc_pair_state_rinv   row_rinv from the handle's rating (a launch on the handle's stream)
 int dc_pair_lists(DcHandle* h, const std::string& who, int64_t nk, const int64_t* candidates, int64_t nm, const int64_t* monitored, std::vector<int>& cand,
                   std::vector<int>& mon);
 int dc_pair_state_build(DcHandle* h, DcPairState*& slot, const char* who, const std::vector<int>& cand, const std::vector<int>& mon, int64_t budget,
-                        size_t extra, const std::string& extra_text, double* info);
+                        size_t extra, const std::string& extra_text, double* info, bool shed = false);
 void dc_pair_state_free(DcHandle* h, DcPairState*& slot);
 void dc_pair_state_rinv(DcHandle* h, DcPairState* p);
 std::string dc_pair_bytes_text(size_t b);

@@ -53,7 +53,11 @@ struct SeriesScreenArgs {
     const int* crow; const double* cdiag;
     double* load; int* branch; int* count;                      // [k1 - k0][ldt]
     double thr; int rows, ldk, ldt, T, k0, k1, kbase;           // kbase: k0 rounded down to a multiple of the tile (the scalar loads of a tile are 32-byte aligned)
+    const int* cisl; const int* rpre;                            // SHED: the candidates' (side, lo, hi, 0) and the rows' preorder[from]
 };
+// SHED (a screen built in shed mode): a bridge candidate's column of Phi holds Z[:,k], its coefficient is s_k F0[k,t] without a denominator, and a row whose
+// from end lies in its preorder interval left with it and carries 0.  The interval and the row's number are wave-uniform: scalar loads, scalar compares.
+template <bool SHED>
 __global__ __launch_bounds__(64 * DC_PAIR_WAVES) void k_series_screen(SeriesScreenArgs a) {
     constexpr int K = DC_SERIES_TILE;
     const int wave = uniform(threadIdx.y);
@@ -65,6 +69,7 @@ __global__ __launch_bounds__(64 * DC_PAIR_WAVES) void k_series_screen(SeriesScre
     double c[K], wl[K];
     int il[K], cnt[K];
     bool sing[K];
+    int lo[K], hi[K];
 #pragma unroll
     for (int i = 0; i < K; ++i) {
         const int k = kt + i;                                    // < ldk: the per-candidate arrays are [ldk], 0 behind nk
@@ -73,6 +78,12 @@ __global__ __launch_bounds__(64 * DC_PAIR_WAVES) void k_series_screen(SeriesScre
         sing[i] = fabs(dk) < DC_SINGULAR;
         c[i] = sing[i] ? 0.0 : fcol[(size_t)rk * ldt] / dk;
         wl[i] = 0.0; il[i] = -1; cnt[i] = 0;
+        lo[i] = 1; hi[i] = 0;
+        if constexpr (SHED) {
+            const I4 q = ((CI4)a.cisl)[k];
+            lo[i] = q[1]; hi[i] = q[2];
+            if (q[0] != 0) { sing[i] = false; c[i] = (q[0] > 0 ? 1.0 : -1.0) * fcol[(size_t)rk * ldt]; }     // what left m over the bridge before the outage
+        }
     }
     const double thr = a.thr;
     auto row = [&](int r, int pk, auto hit_c) {
@@ -87,10 +98,13 @@ __global__ __launch_bounds__(64 * DC_PAIR_WAVES) void k_series_screen(SeriesScre
             pt[4] = q1[0]; pt[5] = q1[1]; pt[6] = q1[2]; pt[7] = q1[3];
         }
         const double f = fcol[(size_t)r * ldt];
+        int pr = 0;
+        if constexpr (SHED) pr = ((CInt)a.rpre)[r];
 #pragma unroll
         for (int i = 0; i < K; ++i) {
             double v = fma(pt[i], c[i], f);
             if (HIT && pk == kt + i) v = 0.0;                    // the outaged branch carries nothing
+            if (SHED && pr >= lo[i] && pr <= hi[i]) v = 0.0;     // nor does a branch that left with the bridge
             const double ld = fabs(v) * ri;
             if (ld > wl[i]) { wl[i] = ld; il[i] = r; }           // rows ascend by branch index, strict comparison: ties go to the lowest branch (k_dc_flows)
             cnt[i] += ld > thr ? 1 : 0;
@@ -188,6 +202,16 @@ __global__ void k_series_base(const double* F0, const double* rinv, const int* r
     q[0] = wl; q[1] = il < 0 ? 0.0 : (double)(rbranch[il] + 1); q[2] = (double)cnt;
 }
 
+// what left m over the bridge before the outage, for the bridge candidates `list` of a block: out[j][t] = s_k F[row of k][t]
+__global__ void k_shed_gather(const double* F, const int* crow, const int* cisl, const int* list, double* out, int nb, int ldt, int T) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= T) return;
+    for (int j = blockIdx.y; j < nb; j += gridDim.y) {
+        const int k = list[j];
+        out[(size_t)j * T + t] = (cisl[4 * k] > 0 ? 1.0 : -1.0) * F[(size_t)crow[k] * ldt + t];
+    }
+}
+
 void series_release(DcHandle* h) {
     DcSeriesState* s = h->series;
     if (!s) return;
@@ -249,13 +273,15 @@ int bridges(DcHandle* h, const DcPairState* p, std::vector<char>& bridge) {
     std::vector<double> diag(p->ldk);
     DC_HIP(sync_copy(diag.data(), p->cand_diag, diag.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     bridge.assign(p->nk, 0);
-    for (int k = 0; k < p->nk; ++k) bridge[k] = std::fabs(1.0 - diag[k]) < DC_SINGULAR;
+    for (int k = 0; k < p->nk; ++k) bridge[k] = !(p->shed && p->h_side[k] != 0) && std::fabs(1.0 - diag[k]) < DC_SINGULAR;
     return 0;
 }
 
 // rhs [T][n]: the lane right-hand sides as jg_dc_set_injections takes them
 int series_build(DcHandle* h, const std::vector<int>& cand, const std::vector<int>& mon, int T, const double* rhs, int64_t budget, double* info) {
     series_release(h);
+    const bool shed = h->series_shed == 1;
+    h->series_shed = 0;
     const int ldt = (T + 63) / 64 * 64;
     int nr = 0;
     {
@@ -272,7 +298,7 @@ int series_build(DcHandle* h, const std::vector<int>& cand, const std::vector<in
     s->T = T; s->ldt = ldt;
     const std::string extra = "; F0 needs " + dc_pair_bytes_text(f0_bytes) + " (" + std::to_string(nr) + " rows x " + std::to_string(ldt) + " profiles x 8) and " +
                               dc_pair_bytes_text(scratch) + " of scratch";
-    int rc = dc_pair_state_build(h, s->phi, "jg_dc_series_build", cand, mon, budget, f0_bytes + scratch, extra, info);
+    int rc = dc_pair_state_build(h, s->phi, "jg_dc_series_build", cand, mon, budget, f0_bytes + scratch, extra, info, shed);
     if (rc) { const std::string msg = h->error; series_release(h); h->error = msg; return rc; }
     DcPairState* p = s->phi;
     auto step = [&](int r) { if (r && !rc) rc = r; return r == 0; };
@@ -320,11 +346,14 @@ SeriesScreenArgs screen_args(DcHandle* h, int k0, int k1, double thr) {
     a.Phi = p->Phi; a.F0 = s->F0; a.rinv = p->row_rinv; a.pos = p->row_pos; a.rbranch = p->row_branch; a.crow = p->cand_row; a.cdiag = p->cand_diag;
     a.load = s->b_load; a.branch = s->b_branch; a.count = s->b_count;
     a.thr = thr; a.rows = p->rows; a.ldk = p->ldk; a.ldt = s->ldt; a.T = s->T; a.k0 = k0; a.k1 = k1; a.kbase = k0 / DC_SERIES_TILE * DC_SERIES_TILE;
+    a.cisl = p->shed ? p->cand_isl : nullptr; a.rpre = p->shed ? p->row_pre : nullptr;
     return a;
 }
 void launch_screen(DcHandle* h, const SeriesScreenArgs& a) {
     const int tiles = (a.k1 - a.kbase + DC_SERIES_TILE - 1) / DC_SERIES_TILE;
-    hipLaunchKernelGGL(k_series_screen, dim3(a.ldt / 64, (tiles + DC_PAIR_WAVES - 1) / DC_PAIR_WAVES), dim3(64, DC_PAIR_WAVES), 0, h->stream, a);
+    const dim3 grid(a.ldt / 64, (tiles + DC_PAIR_WAVES - 1) / DC_PAIR_WAVES), block(64, DC_PAIR_WAVES);
+    if (a.cisl) hipLaunchKernelGGL(k_series_screen<true>, grid, block, 0, h->stream, a);
+    else hipLaunchKernelGGL(k_series_screen<false>, grid, block, 0, h->stream, a);
 }
 SeriesListArgs list_args(DcHandle* h, int k0, int k1, double thr, long long rec_cap) {
     DcSeriesState* s = h->series;
@@ -404,6 +433,38 @@ int dc_series_row_flows(DcHandle* h, const DcPairState* p, int T, const double* 
     return row_flows(h, p, T, rhs, shift, F, ldt, ms);
 }
 int dc_series_bridges(DcHandle* h, const DcPairState* p, std::vector<char>& bridge) { return bridges(h, p, bridge); }
+int dc_series_shed_table(const DcHandle* h, const DcPairState* p, int k0, int k1, int64_t* labels, int64_t* buses, int64_t* m, int64_t* side) {
+    int nb = 0;
+    if (!p->shed) return 0;
+    for (int k = k0; k < k1; ++k) {
+        if (p->h_side[k] == 0) continue;
+        const int br = p->h_cand[k];
+        if (labels) labels[nb] = br + 1;
+        if (buses) buses[nb] = p->h_hi[k] - p->h_lo[k] + 1;
+        if (m) m[nb] = (p->h_side[k] > 0 ? h->h_from[br] : h->h_to[br]) + 1;
+        if (side) side[nb] = p->h_side[k];
+        ++nb;
+    }
+    return nb;
+}
+int dc_series_shed_gather(DcHandle* h, const DcPairState* p, int k0, int k1, const double* F, int ldt, int T, double* out) {
+    std::vector<int> list;
+    if (p->shed)
+        for (int k = k0; k < k1; ++k) if (p->h_side[k] != 0) list.push_back(k);
+    const int nb = (int)list.size();
+    if (!nb) return 0;
+    int* d_list = nullptr; double* d_out = nullptr;
+    int rc = dev_alloc(h, &d_list, (size_t)nb, list.data());
+    if (!rc) rc = dev_alloc(h, &d_out, (size_t)nb * T, (const double*)nullptr, false);
+    if (!rc) {
+        hipLaunchKernelGGL(k_shed_gather, dim3((T + 255) / 256, std::min(nb, 4096)), dim3(256), 0, h->stream, F, p->cand_row, p->cand_isl, d_list, d_out, nb, ldt, T);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = sync_copy(out, d_out, (size_t)nb * T * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+        if (e != hipSuccess) { h->error = std::string("shed gather: ") + hipGetErrorString(e); rc = 2; }
+    }
+    dev_release(h, d_list); dev_release(h, d_out);
+    return rc;
+}
 
 }  // namespace jg
 
@@ -451,6 +512,30 @@ int jg_dc_series_time_kernel(int64_t h, int kernel, int64_t k0, int64_t k1, int 
         else jg::launch_stats(d, la);
         return 0;
     }));
+    return 0;
+}
+
+int jg_dc_series_set_island_mode(int64_t h, int mode) {
+    DC_ENTER(h);
+    if (mode != 0 && mode != 1) return api_fail(1, "jg_dc_series_set_island_mode: mode is 0 (a bridge candidate is skipped: status 3) or 1 (screened on the slack's island)");
+    if (mode == 1 && !d->nbr) return api_fail(1, "jg_dc_series_set_island_mode: jg_dc_set_branches first");
+    d->series_shed = mode;
+    return 0;
+}
+
+int jg_dc_series_get_shed_table(int64_t h, int64_t k0, int64_t k1, int64_t* count, int64_t* labels, int64_t* buses, int64_t* m, int64_t* side) {
+    DC_ENTER(h);
+    if (!d->series) return api_fail(4, "jg_dc_series_get_shed_table: jg_dc_series_build first");
+    if (!count || k0 < 0 || k1 < k0 || k1 > d->series->phi->nk) return api_fail(1, "jg_dc_series_get_shed_table: bad argument");
+    *count = jg::dc_series_shed_table(d, d->series->phi, (int)k0, (int)k1, labels, buses, m, side);
+    return 0;
+}
+
+int jg_dc_series_get_shed(int64_t h, int64_t k0, int64_t k1, double* flow) {
+    DC_ENTER(h);
+    if (!d->series) return api_fail(4, "jg_dc_series_get_shed: jg_dc_series_build first");
+    if (!flow || k0 < 0 || k1 < k0 || k1 > d->series->phi->nk) return api_fail(1, "jg_dc_series_get_shed: bad argument");
+    DC_RET(jg::dc_series_shed_gather(d, d->series->phi, (int)k0, (int)k1, d->series->F0, d->series->ldt, d->series->T, flow));
     return 0;
 }
 

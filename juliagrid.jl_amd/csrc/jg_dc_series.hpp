@@ -10,11 +10,20 @@
 //     f_m(k,t) = F0[m,t] + Phi[m,k] c_kt        (m != k),   f_k(k,t) = 0
 // so a case (k, t) costs no sweep: one FMA and one compare per monitored branch.  The sweeps run once per candidate (Phi) and once per profile (F0).
 //
+// Shed mode (jg_dc_series_set_island_mode 1 before the build): a candidate the handle's island table (dc_island_table: the graph, not |d_k|) calls a
+// bridge is solved on the side M that holds the slack, as the lanes of jg_dc.hpp are.  With m its end in M, S the preorder interval [lo_k, hi_k] that leaves:
+//     z_k      = B^-1 e_m (slack component dropped; m = slack: 0)         Z[l,k] = y_l a_l' z_k stands in the candidate's column of Phi
+//     g_kt     = s_k F0[k,t]                s_k = +1 / -1: m is the from / to end -- what left m over the bridge before the outage
+//     f_l(k,t) = F0[l,t] + Z[l,k] g_kt      for l with both ends in M;   0 for l = k and every branch with an end in S
+// k is the only branch between S and M, so a row other than k left exactly when lo_k <= preorder[from_l] <= hi_k.  A non-bridge with |d_k| < DC_SINGULAR
+// keeps status 3 and NaN.
+//
 // What is kept: Phi [rows][ldk] exactly as the pair build makes it (a DcPairState of the series' own: the pair screen's h->pair is not touched), and
 // F0 [rows][ldt] doubles on the same rows, ldt = profiles rounded up to 64, 0 behind the last profile.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
 #include <vector>
 
 #include "jg_dc_pair.hpp"
@@ -50,7 +59,12 @@ void dc_series_free(DcHandle* h);            // releases what the series screen 
 //                           the sensitivity of the flow to the right-hand side.  Scratch of its own (dc_series_flows_scratch bytes), released on return;
 //                           ms [2] gets the milliseconds of the sweep pairs and of the flow kernel added (HIP events).  Not 0: the text is in h->error
 //   dc_series_bridges       bridge [nk] 1: |1 - Phi[k,k]| < DC_SINGULAR
+//   dc_series_shed_table    the bridge candidates (shed mode) among the positions [k0, k1): their number, and per bridge the label, the buses that leave,
+//                           m (1-based) and the side; null outputs are skipped
+//   dc_series_shed_gather   out [bridges in [k0, k1)][T] on the host = s_k F[row of k][t], from the device (k_shed_gather: one thread per value)
 size_t dc_series_flows_scratch(const DcHandle* h, int ldt);
+int dc_series_shed_table(const DcHandle* h, const DcPairState* p, int k0, int k1, int64_t* labels, int64_t* buses, int64_t* m, int64_t* side);
+int dc_series_shed_gather(DcHandle* h, const DcPairState* p, int k0, int k1, const double* F, int ldt, int T, double* out);
 int dc_series_row_flows(DcHandle* h, const DcPairState* p, int T, const double* rhs, bool shift, double* F, int ldt, double* ms);
 int dc_series_bridges(DcHandle* h, const DcPairState* p, std::vector<char>& bridge);
 

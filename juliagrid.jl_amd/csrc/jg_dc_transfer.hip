@@ -49,7 +49,11 @@ struct TransferScreenArgs {
     const int* crow; const double* cdiag;
     double* tc; int* row;                                       // [k1 - k0][ldt]
     double cutoff; int rows, ldk, ldt, T, k0, k1, kbase;        // kbase: k0 rounded down to a multiple of 64 (a chunk's row of Phi is one aligned 512-byte load)
+    const int* cisl; const int* rpre;                            // SHED: the candidates' (side, lo, hi, 0) and the rows' preorder[from]
 };
+// SHED (a screen built in shed mode): a bridge candidate's column of Phi holds Z[:,k], its coefficients are s_k F0[k] and s_k G[k,t] without a denominator,
+// and a row whose from end lies in its preorder interval left with it: ineligible, (1, 0).  The row's number is a scalar load, the interval sits in the lane.
+template <bool SHED>
 __global__ __launch_bounds__(64 * DC_PAIR_WAVES) void k_transfer_screen(TransferScreenArgs a) {
     constexpr int K = DC_TRANSFER_TILE;
     const int wave = uniform(threadIdx.y);
@@ -60,14 +64,26 @@ __global__ __launch_bounds__(64 * DC_PAIR_WAVES) void k_transfer_screen(Transfer
     const size_t ldk = (size_t)a.ldk, ldt = (size_t)a.ldt;
     const double dk = 1.0 - a.cdiag[k];
     const int rk = a.crow[k];
-    const bool sing = fabs(dk) < DC_SINGULAR;
-    const double cf = sing ? 0.0 : a.f0[rk] / dk;
+    bool sing = fabs(dk) < DC_SINGULAR;
+    double cf = sing ? 0.0 : a.f0[rk] / dk;
     double cg[K], bn[K], bd[K];
     int br[K];
 #pragma unroll
     for (int i = 0; i < K; ++i) {
         cg[i] = sing ? 0.0 : a.G[(size_t)rk * ldt + t0 + i] / dk;
         bn[i] = 1.0; bd[i] = 0.0; br[i] = -1;
+    }
+    int lo = 1, hi = 0;
+    if constexpr (SHED) {
+        const I4 q = ((const I4*)a.cisl)[k];
+        lo = q[1]; hi = q[2];
+        if (q[0] != 0) {                                         // what left m over the bridge: at zero transfer, and per unit of each transfer
+            const double sk = q[0] > 0 ? 1.0 : -1.0;
+            sing = false;
+            cf = sk * a.f0[rk];
+#pragma unroll
+            for (int i = 0; i < K; ++i) cg[i] = sk * a.G[(size_t)rk * ldt + t0 + i];
+        }
     }
     const double cutoff = a.cutoff;
     const double* pcol = a.Phi + k;
@@ -77,7 +93,11 @@ __global__ __launch_bounds__(64 * DC_PAIR_WAVES) void k_transfer_screen(Transfer
         const D4 g4 = *(CD4)(a.G + (size_t)r * ldt + t0);
         const double ph = pcol[(size_t)r * ldk];
         const double fl = fma(ph, cf, fr) * ri;
-        const bool other = !(HIT && pk == k);                   // the outaged branch limits nothing
+        bool other = !(HIT && pk == k);                         // the outaged branch limits nothing
+        if constexpr (SHED) {
+            const int pr = ((CInt)a.rpre)[r];
+            other = other && !(pr >= lo && pr <= hi);            // nor does a branch that left with the bridge
+        }
 #pragma unroll
         for (int i = 0; i < K; ++i) transfer_row(fl, fma(ph, cg[i], g4[i]), ri, other, cutoff, r, bn[i], bd[i], br[i]);
     };
@@ -103,6 +123,7 @@ __global__ __launch_bounds__(64 * DC_PAIR_WAVES) void k_transfer_screen(Transfer
 struct TransferListArgs {
     const double* tc; const int* row; const double* amount; const int* clabel; const int* rbranch;
     const double* Phi; const double* G; const int* crow; const double* cdiag;      // scatter: g of the limiting branch, formed as the screen kernel forms it
+    const int* cisl;                                             // shed mode (else null): the candidates' (side, lo, hi, 0)
     int* r_rec; double* r_min;                                   // per row of the block
     const long long* r_off;                                      // scatter: the row's first record
     double* rec; long long rec_cap;
@@ -131,7 +152,9 @@ __global__ __launch_bounds__(256) void k_transfer_rows(TransferListArgs a) {
                 const int r = a.row[(size_t)i * ldt + t];
                 if (at < a.rec_cap && r >= 0) {
                     const int rk = a.crow[k];
-                    const double g = fma(a.Phi[(size_t)r * ldk + k], a.G[(size_t)rk * ldt + t] / (1.0 - a.cdiag[k]), a.G[(size_t)r * ldt + t]);
+                    const int sd = a.cisl ? a.cisl[4 * k] : 0;
+                    const double cgk = sd ? (sd > 0 ? 1.0 : -1.0) * a.G[(size_t)rk * ldt + t] : a.G[(size_t)rk * ldt + t] / (1.0 - a.cdiag[k]);
+                    const double g = fma(a.Phi[(size_t)r * ldk + k], cgk, a.G[(size_t)r * ldt + t]);
                     double* q = a.rec + at * 5;
                     q[0] = (double)klab; q[1] = (double)t; q[2] = (double)(a.rbranch[r] + 1); q[3] = v; q[4] = g;
                 }
@@ -197,6 +220,8 @@ void transfer_release(DcHandle* h) {
 int transfer_build(DcHandle* h, const std::vector<int>& cand, const std::vector<int>& mon, int T, const double* dirs, const double* base_rhs, int64_t budget,
                    double* info) {
     transfer_release(h);
+    const bool shed = h->transfer_shed == 1;
+    h->transfer_shed = 0;
     const int ldt = (T + 63) / 64 * 64;
     std::vector<int> label;
     {
@@ -215,7 +240,7 @@ int transfer_build(DcHandle* h, const std::vector<int>& cand, const std::vector<
     s->T = T; s->ldt = ldt; s->h_row_label = label;
     const std::string extra = "; G needs " + dc_pair_bytes_text(g_bytes) + " (" + std::to_string(nr) + " rows x " + std::to_string(ldt) + " transfers x 8) and " +
                               dc_pair_bytes_text(scratch) + " of scratch";
-    int rc = dc_pair_state_build(h, s->phi, "jg_dc_transfer_build", cand, mon, budget, g_bytes + scratch, extra, info);
+    int rc = dc_pair_state_build(h, s->phi, "jg_dc_transfer_build", cand, mon, budget, g_bytes + scratch, extra, info, shed);
     if (rc) { const std::string msg = h->error; transfer_release(h); h->error = msg; return rc; }
     DcPairState* p = s->phi;
     auto step = [&](int r) { if (r && !rc) rc = r; return rc == 0; };
@@ -277,18 +302,21 @@ TransferScreenArgs screen_args(DcHandle* h, int k0, int k1, double cutoff) {
     a.Phi = p->Phi; a.G = s->G; a.f0 = s->f0; a.rinv = p->row_rinv; a.pos = p->row_pos; a.crow = p->cand_row; a.cdiag = p->cand_diag;
     a.tc = s->b_tc; a.row = s->b_row;
     a.cutoff = cutoff; a.rows = p->rows; a.ldk = p->ldk; a.ldt = s->ldt; a.T = s->T; a.k0 = k0; a.k1 = k1; a.kbase = k0 / 64 * 64;
+    a.cisl = p->shed ? p->cand_isl : nullptr; a.rpre = p->shed ? p->row_pre : nullptr;
     return a;
 }
 void launch_screen(DcHandle* h, const TransferScreenArgs& a) {
     const int tiles = (a.T + DC_TRANSFER_TILE - 1) / DC_TRANSFER_TILE;
-    hipLaunchKernelGGL(k_transfer_screen, dim3((a.k1 - a.kbase + 63) / 64, (tiles + DC_PAIR_WAVES - 1) / DC_PAIR_WAVES), dim3(64, DC_PAIR_WAVES), 0, h->stream, a);
+    const dim3 grid((a.k1 - a.kbase + 63) / 64, (tiles + DC_PAIR_WAVES - 1) / DC_PAIR_WAVES), block(64, DC_PAIR_WAVES);
+    if (a.cisl) hipLaunchKernelGGL(k_transfer_screen<true>, grid, block, 0, h->stream, a);
+    else hipLaunchKernelGGL(k_transfer_screen<false>, grid, block, 0, h->stream, a);
 }
 TransferListArgs list_args(DcHandle* h, int k0, int k1, long long rec_cap) {
     DcTransferState* s = h->transfer;
     DcPairState* p = s->phi;
     TransferListArgs a{};
     a.tc = s->b_tc; a.row = s->b_row; a.amount = s->amount; a.clabel = p->cand_label; a.rbranch = p->row_branch;
-    a.Phi = p->Phi; a.G = s->G; a.crow = p->cand_row; a.cdiag = p->cand_diag;
+    a.Phi = p->Phi; a.G = s->G; a.crow = p->cand_row; a.cdiag = p->cand_diag; a.cisl = p->shed ? p->cand_isl : nullptr;
     a.r_rec = s->r_rec; a.r_min = s->r_min; a.r_off = s->r_off; a.rec = s->rec; a.rec_cap = rec_cap;
     a.ldk = p->ldk; a.ldt = s->ldt; a.T = s->T; a.k0 = k0; a.k1 = k1;
     return a;
@@ -421,6 +449,32 @@ int jg_dc_transfer_time_kernel(int64_t h, int kernel, int64_t k0, int64_t k1, in
         else jg::launch_stats(d, la);
         return 0;
     }));
+    return 0;
+}
+
+int jg_dc_transfer_set_island_mode(int64_t h, int mode) {
+    DC_ENTER(h);
+    if (mode != 0 && mode != 1) return api_fail(1, "jg_dc_transfer_set_island_mode: mode is 0 (a bridge candidate is skipped: status 3) or 1 (screened on the slack's island)");
+    if (mode == 1 && !d->nbr) return api_fail(1, "jg_dc_transfer_set_island_mode: jg_dc_set_branches first");
+    d->transfer_shed = mode;
+    return 0;
+}
+
+int jg_dc_transfer_get_shed_table(int64_t h, int64_t k0, int64_t k1, int64_t* count, int64_t* labels, int64_t* buses, int64_t* m, int64_t* side) {
+    DC_ENTER(h);
+    if (!d->transfer) return api_fail(4, "jg_dc_transfer_get_shed_table: jg_dc_transfer_build first");
+    if (!count || k0 < 0 || k1 < k0 || k1 > d->transfer->phi->nk) return api_fail(1, "jg_dc_transfer_get_shed_table: bad argument");
+    *count = jg::dc_series_shed_table(d, d->transfer->phi, (int)k0, (int)k1, labels, buses, m, side);
+    return 0;
+}
+
+int jg_dc_transfer_get_shed(int64_t h, int64_t k0, int64_t k1, double* flow, double* transfer) {
+    DC_ENTER(h);
+    jg::DcTransferState* s = d->transfer;
+    if (!s) return api_fail(4, "jg_dc_transfer_get_shed: jg_dc_transfer_build first");
+    if (!flow || !transfer || k0 < 0 || k1 < k0 || k1 > s->phi->nk) return api_fail(1, "jg_dc_transfer_get_shed: bad argument");
+    DC_RET(jg::dc_series_shed_gather(d, s->phi, (int)k0, (int)k1, s->f0, 1, 1, flow));
+    DC_RET(jg::dc_series_shed_gather(d, s->phi, (int)k0, (int)k1, s->G, s->ldt, s->T, transfer));
     return 0;
 }
 

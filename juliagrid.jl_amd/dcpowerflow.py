@@ -326,13 +326,19 @@ def pairCandidates(system: PowerSystem) -> np.ndarray:
     return (np.flatnonzero((lay.status == 1) & ~bridges(system) & (lay.from_ != lay.to)) + 1).astype(np.int64)
 
 
-def _pair_lists(system: PowerSystem, candidates, monitored, rating, who: str = "dcPairScreen", least: int = 2):
+def shedCandidates(system: PowerSystem) -> np.ndarray:
+    """default candidates of a screen with islands="shed": labels of the in-service branches that are not self-loops, bridges included, ascending"""
+    lay = system.branch.layout
+    return (np.flatnonzero((lay.status == 1) & (lay.from_ != lay.to)) + 1).astype(np.int64)
+
+
+def _pair_lists(system: PowerSystem, candidates, monitored, rating, who: str = "dcPairScreen", least: int = 2, shed: bool = False):
     """candidate and monitored labels of a pair screen, checked on the host before anything touches the device"""
     nb, status = system.branch.number, system.branch.layout.status
     rating = np.ascontiguousarray(rating, dtype=np.float64)
     if rating.shape != (nb,):
         raise ValueError("rating: one value per branch")
-    cand = pairCandidates(system) if candidates is None else np.asarray(list(candidates), dtype=np.int64)
+    cand = (shedCandidates(system) if shed else pairCandidates(system)) if candidates is None else np.asarray(list(candidates), dtype=np.int64)
     if cand.size and (cand.min() < 1 or cand.max() > nb):
         raise IndexError(f"{who}: candidate branch label out of range")
     if np.unique(cand).size != cand.size:
@@ -434,6 +440,11 @@ class DcSeriesScreen:
       islanding   labels of the screened candidates that are bridges (status 3): NaN loading in every profile, never in `records`
       totals      dict(cases = rows screened x T, violating, islanding = bridge candidates): exact also when the list overflowed
       worst       [K] the worst loading over all profiles of each screened candidate (0 on a bridge and outside `rows`)
+      shed, shedBuses, shedM, shedFlow, shedDemand, unserved   with islands="shed" (else None): the screened bridge candidates, which are then solved on
+                  the slack's island and are cases like any other (no longer in `islanding`, which keeps what is still status 3): their labels
+                  ascending, the number of buses that leave [S] int64, the bridge's end on the slack's side [S] (1-based bus), the flow that left that
+                  end over the bridge before the outage [S, T] (from the device; the right-hand side summed over what leaves is -shedFlow, the meaning
+                  of analysis.island.flow / .injection -- on a phase-shifting bridge less the bridge's own shiftPower entry at its end that leaves), and with `demand`: the demand summed over what leaves [S, T] and its sum over the profiles [S]
       worstProfile / violatingProfile   [T] per profile over the screened candidates: the worst loading (bridges aside) and the number of candidates
                   whose outage violates (int64)
       base        [T, 3] the base case of every profile, no outage: worst loading, its branch label, number of branches above the threshold
@@ -447,16 +458,48 @@ class DcSeriesScreen:
 SERIES_BLOCK_BYTES = 256 << 20                                         # default bound of the dense result of one device call (16 bytes per case)
 
 
+def _shed_block(L, an, which: str, b0: int, b1: int):
+    """(labels, buses, m) of the bridge candidates among the positions [b0, b1) of a screen built in shed mode"""
+    n = np.zeros(1, dtype=np.int64)
+    lab, buses, m, side = (np.zeros(b1 - b0, dtype=np.int64) for _ in range(4))
+    _lib.check(getattr(L, f"jg_dc_{which}_get_shed_table")(an._h, b0, b1, n, lab, buses, m, side))
+    c = int(n[0])
+    return lab[:c], buses[:c], m[:c]
+
+
+def _shed_demand(system: PowerSystem, labels: np.ndarray, demand: np.ndarray) -> np.ndarray:
+    """[len(labels), T] the demand summed over the buses that leave with each bridge: prefix sums over the preorder per profile, a chunk of profiles at
+    a time (32 MiB of prefix sums, in extended precision where the platform has it: the difference of two long sums)"""
+    from .contingency import islandTable
+    tb = islandTable(system)
+    lo, hi = tb.lo[labels - 1].astype(np.int64), tb.hi[labels - 1].astype(np.int64)
+    T, n = demand.shape[0], tb.order.size
+    out = np.zeros((labels.size, T))
+    step = max(1, (32 << 20) // (np.dtype(np.longdouble).itemsize * (n + 1)))
+    for t0 in range(0, T, step):
+        cs = np.zeros((min(step, T - t0), n + 1), dtype=np.longdouble)
+        np.cumsum(demand[t0:t0 + step][:, tb.order], axis=1, dtype=np.longdouble, out=cs[:, 1:])
+        out[:, t0:t0 + step] = (cs[:, hi + 1] - cs[:, lo]).T.astype(np.float64)
+    return out
+
+
 def dcSeriesScreen(analysis_or_system, injections, candidates=None, monitored=None, rating=None, threshold: float = 1.0, rows=None,
-                   capacity: int = 1 << 20, dense: bool = False, block=None, budget=None, device: int = 0) -> DcSeriesScreen:
+                   capacity: int = 1 << 20, dense: bool = False, block=None, budget=None, device: int = 0, islands: str = "skip",
+                   demand=None) -> DcSeriesScreen:
     """The DC N-1 screen at every one of a series of injection profiles: branch k of `candidates` (labels; default pairCandidates(system); one is
     allowed) out of service under profile t of `injections` ([T, buses] net active injection per bus, supply - demand, the meaning of setInjection_;
     shunts and phase shifters stay the system's), the worst |from| / rating over `monitored` per case -- the loop updateBus! / updateGenerator! per
     profile around updateBranch!(k, status = 0), solve!, power! per branch, from ONE factor, one sweep pair per candidate and one per profile
     (csrc/jg_dc_series.hpp).  `monitored`, `rating`, `rows`, `block`, `budget` and `capacity` mean what they mean for dcPairScreen; the budget covers
-    the sensitivities and the profiles' base flows, and a caller with more profiles than fit splits them (a profile's results do not depend on the others)."""
+    the sensitivities and the profiles' base flows, and a caller with more profiles than fit splits them (a profile's results do not depend on the others).
+      islands    "skip": a bridge candidate gets status 3 (`islanding`, NaN loadings).  "shed": it is screened on the slack's island as setOutages_(...,
+                 islands="shed") solves a lane: the buses behind it leave with their injections, the worst loading, its branch and the count cover the
+                 branches that stay, and the case enters the records and every summary like any other; the default candidates are then
+                 shedCandidates(system), and the result names what was shed (DcSeriesScreen).  A non-bridge whose |1 - Phi[k,k]| vanishes keeps status 3
+      demand     [T, buses] with islands="shed": the demand of every profile, for shedDemand / unserved (host prefix sums)"""
     own = isinstance(analysis_or_system, PowerSystem)
     system = analysis_or_system if own else analysis_or_system.system
+    mode = _island_mode(islands)                                        # refused on the host, before the device is touched
     if rating is None:
         raise ValueError("dcSeriesScreen: rating (per branch, per unit of active power) is needed")
     if not threshold >= 0:
@@ -466,9 +509,15 @@ def dcSeriesScreen(analysis_or_system, injections, candidates=None, monitored=No
         raise ValueError("dcSeriesScreen: injections must be [T, buses] with T >= 1")
     if not np.isfinite(inj).all():
         raise ValueError("dcSeriesScreen: injections must be finite")
+    if demand is not None:
+        if not mode:
+            raise ValueError("dcSeriesScreen: demand goes with islands='shed'")
+        demand = np.asarray(demand, dtype=np.float64)
+        if demand.shape != inj.shape or not np.isfinite(demand).all():
+            raise ValueError("dcSeriesScreen: demand must be [T, buses] like injections, and finite")
     if own and system.model.dc.nodalMatrix is None:
         dcModel_(system)
-    cand, mon, rating = _pair_lists(system, candidates, monitored, rating, who="dcSeriesScreen", least=1)
+    cand, mon, rating = _pair_lists(system, candidates, monitored, rating, who="dcSeriesScreen", least=1, shed=bool(mode))
     nk, T = int(cand.size), int(inj.shape[0])
     k0, k1 = (0, nk) if rows is None else (int(rows[0]), min(int(rows[1]), nk))
     if k0 < 0 or k1 < k0:
@@ -486,13 +535,14 @@ def dcSeriesScreen(analysis_or_system, injections, candidates=None, monitored=No
         _set_rating(an, rating)
         rhs = np.ascontiguousarray(inj - system.bus.shunt.conductance[None, :] - system.model.dc.shiftPower[None, :])
         info = np.zeros(12)
+        _lib.check(L.jg_dc_series_set_island_mode(an._h, mode))
         _lib.check(L.jg_dc_series_build(an._h, nk, cand, int(mon.size), mon.ctypes.data_as(_lib.VP), T, rhs.reshape(-1), int(budget or 0), info))
         del rhs
         ptr = lambda a: None if a is None else a.ctypes.data_as(_lib.VP)
         rec = np.zeros((max(int(capacity), 0), 5))
         worst, worstProfile, violatingProfile, base = np.zeros(nk), np.zeros(T), np.zeros(T, dtype=np.int64), np.zeros((T, 3))
         tot = np.zeros(3, dtype=np.int64)
-        nrec, bridges = 0, []
+        nrec, bridges, shed = 0, [], []
         full = {name: np.zeros((k1 - k0, T), dtype=dt) for name, dt in (("loading", np.float64), ("branch", np.int32), ("count", np.int32))} if dense else {}
         for b0 in range(k0, k1, step):
             b1 = min(b0 + step, k1)
@@ -506,6 +556,12 @@ def dcSeriesScreen(analysis_or_system, injections, candidates=None, monitored=No
             tot += t5[:3]
             nrec += int(t5[3])
             bridges.append(isl[:int(t5[2])])
+            if mode:
+                lab, buses, m = _shed_block(L, an, "series", b0, b1)
+                flow = np.zeros((lab.size, T))
+                if lab.size:
+                    _lib.check(L.jg_dc_series_get_shed(an._h, b0, b1, flow.reshape(-1)))
+                shed.append((lab, buses, m, flow))
         res = DcSeriesScreen(candidates=cand, monitored=mon, profiles=T, threshold=float(threshold), rows=(k0, k1), records=rec[:nrec].copy(),
                              overflow=bool(tot[1] > nrec), islanding=np.concatenate(bridges) if bridges else np.zeros(0, dtype=np.int64),
                              totals=dict(cases=int(tot[0]), violating=int(tot[1]), islanding=int(tot[2])), worst=worst, worstProfile=worstProfile,
@@ -514,6 +570,13 @@ def dcSeriesScreen(analysis_or_system, injections, candidates=None, monitored=No
                                             "f0SweepMs", "f0KernelMs"), (float(x) for x in info))))
         for name, a in full.items():
             setattr(res, name, a)
+        res.shed = res.shedBuses = res.shedM = res.shedFlow = res.shedDemand = res.unserved = None
+        if mode:
+            res.shed, res.shedBuses, res.shedM = (np.concatenate([x[j] for x in shed]) if shed else np.zeros(0, dtype=np.int64) for j in range(3))
+            res.shedFlow = np.concatenate([x[3] for x in shed]) if shed else np.zeros((0, T))
+            if demand is not None:
+                res.shedDemand = _shed_demand(system, res.shed, demand)
+                res.unserved = res.shedDemand.sum(axis=1)
         return res
     finally:
         if own:
@@ -536,6 +599,11 @@ class DcTransferScreen:
       islanding   labels of the screened candidates that are bridges (status 3): NaN capability for every transfer, never in `records` or a minimum
       totals      dict(cases = rows screened x T, limited = cases below their amount, islanding = bridge candidates): exact also when the list overflowed
       capabilityCases, branch   with dense=True: [k1 - k0, T]
+      shed, shedBuses, shedM, shedFlow, shedTransfer   with islands="shed" (else None): the screened bridge candidates, which are then screened on the
+                  slack's island and are cases like any other (no longer in `islanding`): their labels ascending, the number of buses that leave [S]
+                  int64, the bridge's end on the slack's side [S] (1-based bus), the flow that left that end over the bridge at zero transfer [S] and
+                  per unit of each transfer [S, T] (both from the device).  shedTransfer[k, t] != 0: direction t has a source or sink behind bridge k and
+                  is partly shed with it; the capability of that case belongs to what remains of the direction
       info        dict(rows, ld, phiBytes, freeBytes, budgetBytes, buildMs, sweepMs, phiMs, gBytes, gBuildMs, gSweepMs, gKernelMs)"""
 
     def __init__(self, **kw):
@@ -564,17 +632,22 @@ def transferDirection(system: PowerSystem, source, sink, sourceShare=None, sinkS
 
 
 def dcTransferScreen(analysis_or_system, transfers, candidates=None, monitored=None, rating=None, amount=None, cutoff: float = 1e-6, injection=None,
-                     rows=None, capacity: int = 1 << 20, dense: bool = False, block=None, budget=None, device: int = 0) -> DcTransferScreen:
+                     rows=None, capacity: int = 1 << 20, dense: bool = False, block=None, budget=None, device: int = 0,
+                     islands: str = "skip") -> DcTransferScreen:
     """The DC transfer-capability screen: how far the injections can move along direction t of `transfers` ([T, buses] net active injection per unit of
     transfer, the meaning of setInjection_; transferDirection builds one; the slack takes what a direction does not balance) before the first monitored
     branch reaches its rating, in the base case and with branch k of `candidates` (labels; default pairCandidates(system)) out of service -- the loop
     that raises updateBus! / updateGenerator! along a direction around updateBranch!(k, status = 0), solve!, power! per branch, from ONE factor, one
     sweep pair per candidate and one per direction (csrc/jg_dc_transfer.hpp).  A branch limits only where its flow moves by more than `cutoff` per unit
     of transfer.  `injection` ([buses], default: the system's own) is the base operating point; `amount` (a value or [T]) asks for the records of the
-    cases that cannot carry that much.  `monitored`, `rating`, `rows`, `block`, `budget` and `capacity` mean what they mean for dcSeriesScreen."""
+    cases that cannot carry that much.  `monitored`, `rating`, `rows`, `block`, `budget` and `capacity` mean what they mean for dcSeriesScreen, and so
+    does islands="shed": a bridge candidate is screened on the slack's island (a branch that leaves with it limits nothing; +inf and branch 0 when
+    nothing eligible stays), the default candidates are shedCandidates(system).  The part of a direction that lies behind the bridge is shed with it
+    (shedTransfer), and the capability of such a case is that of what remains of the direction."""
     own = isinstance(analysis_or_system, PowerSystem)
     system = analysis_or_system if own else analysis_or_system.system
     who = "dcTransferScreen"
+    mode = _island_mode(islands)                                        # refused on the host, before the device is touched
     if rating is None:
         raise ValueError(f"{who}: rating (per branch, per unit of active power) is needed")
     if not cutoff > 0:
@@ -598,7 +671,7 @@ def dcTransferScreen(analysis_or_system, transfers, candidates=None, monitored=N
             raise ValueError(f"{who}: injection must be [buses] and finite")
     if own and system.model.dc.nodalMatrix is None:
         dcModel_(system)
-    cand, mon, rating = _pair_lists(system, candidates, monitored, rating, who=who, least=1)
+    cand, mon, rating = _pair_lists(system, candidates, monitored, rating, who=who, least=1, shed=bool(mode))
     nk = int(cand.size)
     k0, k1 = (0, nk) if rows is None else (int(rows[0]), min(int(rows[1]), nk))
     if k0 < 0 or k1 < k0:
@@ -617,13 +690,14 @@ def dcTransferScreen(analysis_or_system, transfers, candidates=None, monitored=N
         ptr = lambda a: None if a is None else a.ctypes.data_as(_lib.VP)
         base_rhs = None if injection is None else np.ascontiguousarray(injection - system.bus.shunt.conductance - system.model.dc.shiftPower)
         info = np.zeros(12)
+        _lib.check(L.jg_dc_transfer_set_island_mode(an._h, mode))
         _lib.check(L.jg_dc_transfer_build(an._h, nk, cand, int(mon.size), mon.ctypes.data_as(_lib.VP), T, np.ascontiguousarray(d).reshape(-1), ptr(base_rhs),
                                           int(budget or 0), info))
         rec = np.zeros((max(int(capacity), 0) if amount is not None else 0, 5))
         worst, base = np.full(nk, np.inf), np.zeros((T, 3))
         cap, capOutage, capBranch = np.full(T, np.inf), np.zeros(T, dtype=np.int64), np.zeros(T, dtype=np.int64)
         tot = np.zeros(3, dtype=np.int64)
-        nrec, bridges = 0, []
+        nrec, bridges, shed = 0, [], []
         full = {name: np.zeros((k1 - k0, T), dtype=dt) for name, dt in (("capabilityCases", np.float64), ("branch", np.int32))} if dense else {}
         for b0 in range(k0, k1, step):
             b1 = min(b0 + step, k1)
@@ -637,6 +711,12 @@ def dcTransferScreen(analysis_or_system, transfers, candidates=None, monitored=N
             tot += t5[:3]
             nrec += int(t5[3])
             bridges.append(isl[:int(t5[2])])
+            if mode:
+                lab, buses, m = _shed_block(L, an, "transfer", b0, b1)
+                flow, per = np.zeros(lab.size), np.zeros((lab.size, T))
+                if lab.size:
+                    _lib.check(L.jg_dc_transfer_get_shed(an._h, b0, b1, flow, per.reshape(-1)))
+                shed.append((lab, buses, m, flow, per))
         first = base[:, 0] <= cap                                       # ties go to the base case
         res = DcTransferScreen(candidates=cand, monitored=mon, transfers=T, cutoff=float(cutoff), rows=(k0, k1),
                                capability=np.where(first, base[:, 0], cap), limitingOutage=np.where(first, 0, capOutage),
@@ -648,6 +728,11 @@ def dcTransferScreen(analysis_or_system, transfers, candidates=None, monitored=N
                                               "gSweepMs", "gKernelMs"), (float(x) for x in info))))
         for name, a in full.items():
             setattr(res, name, a)
+        res.shed = res.shedBuses = res.shedM = res.shedFlow = res.shedTransfer = None
+        if mode:
+            res.shed, res.shedBuses, res.shedM = (np.concatenate([x[j] for x in shed]) if shed else np.zeros(0, dtype=np.int64) for j in range(3))
+            res.shedFlow = np.concatenate([x[3] for x in shed]) if shed else np.zeros(0)
+            res.shedTransfer = np.concatenate([x[4] for x in shed]) if shed else np.zeros((0, T))
         return res
     finally:
         if own:
