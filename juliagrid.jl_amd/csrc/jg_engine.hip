@@ -842,6 +842,8 @@ struct TopArgs {
     int ld, lanes, task_begin, ntasks, lpg;   // lpg: scenarios per 64-lane group that get a workgroup (64, or the real count of a single small group)
     const int* wgmap; int wg_begin, nwg;      // grouped launches (k_fact_grp): workgroup x of a group -> task << 8 | scenario block
     double* jc; int jc_first;                 // ONE scenario (Engine::single_bwd): Jordan rows leave COMPACT -- block j at jc + 4 (j - jc_first), 32 contiguous bytes -- for k_bwd1_top
+    int sweep_only;                           // Jordan tasks: 1 = only the Jordan sweep reads this factor (Engine::sweep_only) -- the off-diagonal entries of the tasks' pivot
+                                              // columns and in-task triangles (jg_symbolic.hpp: top_dead) are not stored.  Wave-uniform: a kernel argument.
 };
 
 // Where scenario b keeps 16-byte unit q of a task's update block: the block is interleaved over the 2^lg scenarios that share a workgroup
@@ -1772,7 +1774,7 @@ __global__ __launch_bounds__(PW ? TOP_THREADS : 256) __attribute__((amdgpu_waves
                     } else store_blk(a.X, (size_t)(jb + i * e + (j - m)), b, ld, v.v00, v.v01, v.v10, v.v11);
                 }
                 else if (cd <= -2) store_vec(a.W, (size_t)(-(cd + 2)), b, ld, v.v00, v.v10);
-                else if (cd >= 0 && (!((cd >> 28) & 4) || (!PW && i == j && i < m))) store_blk(a.X, (size_t)(cd & 0x0fffffff), b, ld, v.v00, v.v01, v.v10, v.v11);
+                else if (cd >= 0 && ((!((cd >> 28) & 4) && !(JORDAN && a.sweep_only)) || (!PW && i == j && i < m))) store_blk(a.X, (size_t)(cd & 0x0fffffff), b, ld, v.v00, v.v01, v.v10, v.v11);
                 else if (i >= m && i < f && j >= m && j < fprime) {                              // update matrix | vector: scenario-major stack
                     double2* p = out + ((((size_t)(i - m) * (e + 1) + (j - m)) * 2) << lgo);
                     p[0] = double2{v.v00, v.v01}; p[(size_t)1 << lgo] = double2{v.v10, v.v11};
@@ -2291,7 +2293,8 @@ int Engine::factor(hipStream_t st, const double* A, const double* rhs, const Gro
     if (!plan->S.top_launch.empty() && probe_part != 1) {
         const long long s0 = std::max<long long>(plan->S.top_stack_cls[0], 2);
         TopArgs t{top_task, top_data, X, W, top_stack, status, sel, s0, {0, s0 * ld, (s0 + plan->S.top_stack_cls[1]) * ld}, {s0, plan->S.top_stack_cls[1], plan->S.top_stack_cls[2]},
-                  top_prof, ld, a.lanes, 0, 0, 64, top_wgmap, 0, 0, single_bwd && jordan ? jc : nullptr, plan->S.n_entries};
+                  top_prof, ld, a.lanes, 0, 0, 64, top_wgmap, 0, 0, single_bwd && jordan ? jc : nullptr, plan->S.n_entries,
+                  sweep_only && jordan && plan->S.jordan && plan->S.top_dead_ok && !single_bwd ? 1 : 0};
         if (ld == 64 && t.lanes < 64) t.lpg = t.lanes;
         for (const TopLaunch& L : plan->S.top_launch) {
             t.task_begin = L.task_begin; t.ntasks = L.ntasks;

@@ -251,6 +251,9 @@ struct Engine {
     int probe_part = 0;            // TIMING PROBE (JG_PROBE_FACT_PART at create: 1 = factor() launches the bottom levels only, 2 = the top only; wrong numbers) -- tools/r05_overlap_probe.py
     double* jc = nullptr;          // single_bwd: the Jordan rows of the top tasks, compact ([n_jordan][4] doubles: k_fact_top writes, k_bwd1_top reads)
     bool single_bwd = false;       // ONE scenario on a Jordan plan: backsolve() runs the row-per-lane sweep (k_bwd1_top / k_bwd1_bottom, jg_symbolic.hpp: SingleTables)
+    bool sweep_only = false;       // the owner reads this factor through backsolve() over Jordan rows ONLY (no forward(), no selected inverse, no plain sweep, no reader of X): the top
+                                   // tasks then keep the entries nothing of that path reads to themselves (plan->S.top_dead; same bits everywhere else).  Ignored unless `jordan` is on
+                                   // and the plan grants it; read by factor() at launch time, like `jordan`.
     bool shared = false;           // hint (jg_nr_set_shared): other batches are in flight on this GPU -- the top launches take the 4-wave variant (same bits)
     Rec* top_task = nullptr; int* top_data = nullptr;          // multifrontal top (jg_symbolic.hpp): task headers, task data
     int* top_wgmap = nullptr;                                  // workgroup map of the grouped launches

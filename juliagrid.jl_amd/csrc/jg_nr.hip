@@ -1640,6 +1640,9 @@ int jg_nr_create(jg_nr** out, int64_t n, const int64_t* colptr, const int64_t* r
     if (eng_thread.joinable()) eng_thread.join();
     if (timing) fprintf(stderr, "[jg nr create] engine joined at                        %6.1f ms\n", tnow() - tc0);
     if (eng_rc) { std::string m = h->eng.error; jg_nr_destroy(h); return fail(eng_rc, m); }
+    // Every reader of this handle's factor other than the Jordan sweep -- forward() of a refined or fast step, the compact factor of jg_nr_base_create -- switches
+    // Engine::jordan off for its factorisation, and with it this flag: the iteration graphs then leave the top tasks' dead entries unstored (JG_SWEEP_ONLY=0: stored)
+    h->eng.sweep_only = jg::knob("SWEEP_ONLY", 1) != 0;
     if (jg::upload(&h->d_dst, h->eng.plan->S.src_entry, err, h->stream)) { jg_nr_destroy(h); return fail(2, err); }
     if (h->eng.plan->S.prefactor) {                            // the row table of the assemblies that also finish the plan's level 0
         std::vector<int> rt(type, type + n);

@@ -39,6 +39,8 @@ void jg_plan_destroy(jg_plan* p) { delete p; }
 //        bottom items, [workgroups][levels + 1] ranges of them, first record of the partial items, {ok, workgroups, levels, items per workgroup}
 //        90 - 97 the backward sweep of a single instance (jg_symbolic.hpp: SingleTables): {ok, top rows, top levels, bottom rows, bottom workgroups, bottom levels, rows per
 //        workgroup, terms-as-lanes form granted, most terms / rows of a level}, t_row (x4), t_ptr (x2), t_term, t_level, b_wg (x2), b_row (x6), b_term (x2), 98 - 100 t_jb (x2), t_cslot, t_toff
+//        101 per entry: 1 = stored by a top task and read by nothing of the factorisation and the Jordan sweep (jg_symbolic.hpp: top_dead), 102 {one flag may skip them all,
+//        16-byte units per scenario and factorisation it keeps from being stored, ... of those the tasks store without it}
 // out == NULL returns the length.
 int64_t jg_plan_export(jg_plan* p, int which, int32_t* out, int64_t cap) {
     if (!p) return -1;
@@ -90,6 +92,8 @@ int64_t jg_plan_export(jg_plan* p, int which, int32_t* out, int64_t cap) {
             }
             v = &tmp; break;
         }
+        case 101: tmp.assign(S.top_dead.begin(), S.top_dead.end()); v = &tmp; break;
+        case 102: tmp = {S.top_dead_ok, (int)(S.top_dead_blocks & 0x7fffffff), (int)(S.top_store_blocks & 0x7fffffff)}; v = &tmp; break;
         case 75: tmp.assign(S.pre_pivot.begin(), S.pre_pivot.end()); v = &tmp; break;
         case 76: tmp.assign((const int*)S.pre_seg.data(), (const int*)S.pre_seg.data() + S.pre_seg.size() * 8); v = &tmp; break;
         case 77: tmp.assign((const int*)S.pre_rec.data(), (const int*)S.pre_rec.data() + S.pre_rec.size() * 16); v = &tmp; break;

@@ -20,7 +20,7 @@ namespace jg {
 
 int knob(const char* name, int unset) {
     static const char* const known[] = {"TRACE", "PLAN_CACHE", "POLL", "PLAN_THREADS", "PLAN_TIMING", "HOST_TIMING",
-                                        "TOP_PW", "TOP_FUSE", "TOP_SYM", "JORDAN", "CHAIN_SMALL", "NO_PREFACTOR", "LANES_INPLACE", "TOP_LEVEL", "ROW_TASKS", "ORDER_CHECK", "TOP_PROFILE", "SINGLE"};
+                                        "TOP_PW", "TOP_FUSE", "TOP_SYM", "JORDAN", "CHAIN_SMALL", "NO_PREFACTOR", "LANES_INPLACE", "TOP_LEVEL", "ROW_TASKS", "ORDER_CHECK", "TOP_PROFILE", "SINGLE", "SWEEP_ONLY"};
     bool ok = false;
     for (const char* k : known) ok = ok || std::strcmp(k, name) == 0;
     if (!ok) return unset;
@@ -1547,8 +1547,86 @@ int analyze(int n, const int* rowptr, const int* col, long long policy64, BlockS
     }
     if (S.n_entries + S.n_jordan >= (1 << 24)) S.fact_tasks = 0;   // a task term packs (entry | slot << 24)
     build_tables(S);
+    mark_sweep_dead(S);
     lap("replay tables");
     return 0;
+}
+
+// Which task-owned entries does nothing read once their task has run (jg_symbolic.hpp: top_dead)?  Candidates: what a slot of a Jordan task stores into the
+// factor entries -- every entry of its map outside the pivot rows' external columns (those leave as Jordan rows) that is neither a diagonal block nor a
+// transposed copy.  Readers: every operand of the factorisation records (level items, the producer's level 0) and everything the Jordan sweep names
+// (diagonal blocks, row terms, the blocks of its chain tasks).  An entry with a reader is no candidate any more; the flag is granted only if none was struck.
+void mark_sweep_dead(BlockSymbolic& S) {
+    S.top_dead.assign((size_t)S.n_entries, 0);
+    S.top_dead_ok = 0; S.top_dead_blocks = 0; S.top_store_blocks = 0;
+    if (!S.jordan || S.symmetric || S.top_task.empty()) return;       // (symmetric plans: k_fact_top_sym, which has no such flag)
+    std::vector<int> seen((size_t)S.n_entries, 0);
+    long long half = 0;
+    for (const Rec& h : S.top_task) {
+        const int m = h.w[0], e = h.w[1], f = m + e, fprime = h.w[11];
+        const int* emap = S.top_data.data() + h.w[3];
+        for (int r = 0; r < f; ++r)
+            for (int c = 0; c < f; ++c) {
+                const int cd = emap[(size_t)r * fprime + c];
+                if (r < m && c >= m) continue;                       // Jordan row slot
+                if (cd < 0 || ((cd >> 28) & 4)) continue;
+                S.top_dead[cd & 0x0fffffff] = 1; seen[cd & 0x0fffffff]++;
+            }
+        half += 2LL * m /* diagonal blocks */ + 2LL * m * e /* Jordan rows */ + m /* y' */ + 2LL * e * (e + 1) /* update matrix | vector */;
+    }
+    long long cand = 0;
+    bool struck = false;
+    for (int en = 0; en < S.n_entries; ++en) if (S.top_dead[en]) { ++cand; if (seen[en] != 1) struck = true; }
+    auto read = [&](int en) { if (en >= 0 && en < S.n_entries && S.top_dead[en]) { S.top_dead[en] = 0; struck = true; } };
+    auto scan_fact = [&](const std::vector<Rec>& recs) {
+        for (const Rec& r : recs) {
+            if (r.w[0] < 0) continue;
+            for (int t = 0; t < r.w[3] && t < FACT_T; ++t) {
+                read(r.w[4 + 3 * t] & 0x3fffffff); read(r.w[5 + 3 * t]);
+                if (r.w[0] != 3) read(r.w[6 + 3 * t]);               // (a rhs row's third operand is a row of y)
+            }
+        }
+    };
+    auto scan_tasks = [&](const std::vector<Rec>& recs) {           // factorisation TASKS (jg_symbolic.hpp): staging entries of every record, then the item's terms
+        for (const Rec& r : recs) {
+            for (int u = 0; u < ((r.w[3] >> 8) & 0xff) && u < TASK_STAGE; ++u) { read(r.w[10 + 3 * u] & 0xffffff); read(r.w[11 + 3 * u]); }
+            const int kind = r.w[0] & TK_KIND, nt = r.w[3] & 0xff;
+            if (kind == 7) continue;
+            for (int t = 0; t < nt; ++t) {
+                if (r.w[0] & TK_DIRECT) {
+                    if (t >= TASK_DIRECT_T) break;
+                    read(r.w[4 + 3 * t] & 0x3fffffff); read(r.w[5 + 3 * t]);
+                    if (kind != 3) read(r.w[6 + 3 * t]);
+                } else if (t < TASK_T && kind != 3) read(r.w[4 + t] & 0xffffff);   // (a rhs row's memory operand is a row of y)
+            }
+        }
+    };
+    if (S.fact_tasks) scan_tasks(S.fact_rec); else scan_fact(S.fact_rec);
+    scan_fact(S.pre_rec);
+    for (const Segment& sg : S.bwdj_seg) {
+        if (sg.wpi <= 0) {                                           // chain tasks: {rows, external columns, U(row, ext), U(row, row')}
+            for (int x = 0; x < sg.nchunks; ++x) {
+                const Rec& r = S.bwdj_rec[(size_t)sg.rec_base + x];
+                const int nb = r.w[0], nE = r.w[1];
+                const int* d = S.bwd_chain.data() + r.w[2];
+                for (int p = 0; p < nb; ++p) read(d[3 * p + 2]);
+                const int* u = d + 3 * nb + nE;
+                for (int q = 0; q < nb * nE + nb * nb; ++q) read(u[q]);
+            }
+            continue;
+        }
+        const size_t nrec = (size_t)sg.nchunks * 16 * sg.rpw;
+        for (size_t x = 0; x < nrec; ++x) {
+            const Rec& r = S.bwdj_rec[(size_t)sg.rec_base + x];
+            if (r.w[0] < 0) continue;
+            read(r.w[2]);
+            for (int t = 0; t < r.w[3] && t < BWD_T; ++t) read(r.w[4 + 2 * t]);
+        }
+    }
+    S.top_dead_ok = struck ? 0 : 1;
+    for (int en = 0; en < S.n_entries; ++en) if (S.top_dead[en]) S.top_dead_blocks++;
+    S.top_store_blocks = half + 2 * cand;
+    S.top_dead_blocks *= 2;                                          // both counts in half blocks (16 bytes per scenario)
 }
 
 }  // namespace jg

@@ -21,7 +21,7 @@ namespace jg {
 // handles), JG_POLL=0 (the host always blocks in the stream synchronise), JG_PLAN_THREADS (host threads of the table builder), JG_PLAN_TIMING, JG_HOST_TIMING
 // (timings on stderr).  The rest are TEST HOOKS that force a code path the library also takes by itself, so that the suites can hold the variants against each
 // other (tests/test_top_variants_gpu.py, tests/test_plan_cpu.py): JG_TOP_PW, JG_TOP_FUSE, JG_TOP_SYM, JG_JORDAN, JG_CHAIN_SMALL, JG_NO_PREFACTOR, JG_LANES_INPLACE,
-// JG_TOP_LEVEL, JG_ROW_TASKS, JG_ORDER_CHECK, JG_TOP_PROFILE, JG_SINGLE.  Nothing else is read: the switches of retired experiments left with their kernels
+// JG_TOP_LEVEL, JG_ROW_TASKS, JG_ORDER_CHECK, JG_TOP_PROFILE, JG_SINGLE, JG_SWEEP_ONLY.  Nothing else is read: the switches of retired experiments left with their kernels
 // (tools/experiments/*.patch).
 int knob(const char* name, int unset);      // integer value of the environment variable JG_<name>; `unset` when it is not set (or not in the lists above)
 inline bool knob_set(const char* name) { return knob(name, -2147483647) != -2147483647; }
@@ -205,6 +205,15 @@ struct BlockSymbolic {
     long long top_stack = 0;            // doubles per scenario on the update stacks
     long long top_stack_cls[3] = {0, 0, 0};   // ... of the blocks interleaved over 1 / 4 / 16 scenarios (a task's w4 is an offset inside its class)
     long long top_terms = 0;            // update terms executed inside tasks
+    // SWEEP-ONLY consumers (Engine::sweep_only, Jordan plans; mark_sweep_dead).  A task stores the final value of every entry it owns, but with Jordan rows
+    // the factorisation and the sweep read only the diagonal blocks, the Jordan rows and y' of a task pivot afterwards: the Lh column blocks and the in-task
+    // triangle are for the forward elimination alone, the plain sweep and the selected inverse.  top_dead[e] = 1: entry e is stored by a task and read by no
+    // record of the factorisation and of the Jordan sweep (checked against the tables, not assumed); top_dead_ok: every off-diagonal entry the tasks store is
+    // such an entry, so ONE wave-uniform flag of k_fact_top may skip them all.
+    std::vector<char> top_dead;         // [n_entries]
+    int top_dead_ok = 0;
+    long long top_dead_blocks = 0;      // blocks per scenario and factorisation the flag keeps from being stored ...
+    long long top_store_blocks = 0;     // ... of the blocks the tasks store without it (entries, Jordan rows, update matrices; a 2-vector counts half: the sum is in HALF blocks)
 };
 
 // ---- shared-factor solve (compensation, jg_comp.hip): tables of x = A^-1 r for MANY right-hand sides on ONE numeric factor ----------
@@ -294,6 +303,7 @@ void build_single_tables(const BlockSymbolic& S, SingleTables& out);
 int analyze(int n, const int* rowptr, const int* col, long long policy, BlockSymbolic& out);
 // Replay tables of the selected inverse of a SYMMETRIC matrix on the factor pattern (see jg_symbolic.cpp); idempotent.
 void build_selected_inverse(BlockSymbolic& S);
+void mark_sweep_dead(BlockSymbolic& S);        // top_dead, top_dead_ok and the two counts (called by analyze)
 // entry id of block (r, c) in pivot numbering, -1 if outside the factor pattern
 int entry_of(const BlockSymbolic& S, int r, int c);
 
