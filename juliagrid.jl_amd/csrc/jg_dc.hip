@@ -300,6 +300,12 @@ int dc_base_solve(DcHandle* h) {
     return 0;
 }
 
+void dc_handle_island_table(DcHandle* h) {
+    if (!h->h_pre.empty()) return;
+    h->h_pre.resize(h->n); h->h_blo.resize(h->nbr); h->h_bhi.resize(h->nbr); h->h_bside.resize(h->nbr);
+    dc_island_table(h->n, h->nbr, h->h_from.data(), h->h_to.data(), h->h_y.data(), h->slack, h->h_pre.data(), h->h_blo.data(), h->h_bhi.data(), h->h_bside.data());
+}
+
 }  // namespace jg
 
 using jg::DcHandle;
@@ -481,9 +487,8 @@ int jg_dc_set_island_mode(int64_t h, int mode) {
     if (mode != 0 && mode != 1) return api_fail(1, "jg_dc_set_island_mode: mode is 0 (a bridge outage is skipped: status 3) or 1 (solved on the slack's island: status 4)");
     if (mode == 1 && !d->nbr) return api_fail(1, "jg_dc_set_island_mode: jg_dc_set_branches first");
     if (mode == 1 && !d->isl) {                                          // the table of the handle's grid and the lanes' records, once
-        const size_t n = (size_t)d->n, nb = (size_t)d->nbr, ld = (size_t)d->ld;
-        d->h_pre.resize(n); d->h_blo.resize(nb); d->h_bhi.resize(nb); d->h_bside.resize(nb);
-        jg::dc_island_table(d->n, d->nbr, d->h_from.data(), d->h_to.data(), d->h_y.data(), d->slack, d->h_pre.data(), d->h_blo.data(), d->h_bhi.data(), d->h_bside.data());
+        const size_t n = (size_t)d->n, ld = (size_t)d->ld;
+        jg::dc_handle_island_table(d);
         DC_RET(jg::dev_alloc(d, &d->preorder, n, d->h_pre.data()));
         const int chunks = (d->n + 4 * jg::DC_COMBINE_ROWS - 1) / (4 * jg::DC_COMBINE_ROWS) * 4;
         DC_RET(jg::dev_alloc(d, &d->ipart, (size_t)chunks * 2 * ld, (const double*)nullptr, true));

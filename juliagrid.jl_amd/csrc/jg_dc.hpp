@@ -53,10 +53,12 @@ struct DcHandle : DcDevice {
     int* o2_from = nullptr; int* o2_to = nullptr; int* o2_br = nullptr; double* o2_y = nullptr; double* o2_sh = nullptr;   // [ld]
     double* Z2 = nullptr;                                                      // [n][ld] z of the second outage, for the groups of glist2
     int* glist2 = nullptr; std::vector<int> h_o2; int n_glist2 = 0;            // lane groups that hold a second outage
-    DcPairState* pair = nullptr;                                               // the N-2 screen's kept sensitivities (jg_dc_pair.hpp)
+    DcPairState* pair = nullptr;                                               // the N-2 screen over all pairs of a candidate list (jg_dc_pair.hpp)
     DcSeriesState* series = nullptr;                                           // the N-1 screen over a series of injection profiles (jg_dc_series.hpp)
     DcTransferState* transfer = nullptr;                                       // the transfer-capability screen over transfers x N-1 outages (jg_dc_transfer.hpp)
-    int series_shed = 0, transfer_shed = 0;                                    // island mode of the NEXT series / transfer build (the build takes it and sets it back to 0)
+    // island mode of the NEXT series / transfer build (the build takes it and sets it back to 0).  A sticky flag beside the build call is awkward -- the mode
+    // belongs among the build's arguments -- but jg_dc_*_set_island_mode is part of the C ABI, so the flags stay
+    int series_shed = 0, transfer_shed = 0;
     // bridge outages solved on the slack's island (jg_dc_set_island_mode 1): allocated by the first such call, a handle without it holds none of it
     int island_mode = 0, n_isl = 0;                                            // n_isl: lanes whose ONE outage is a bridge, set while the mode was 1
     std::vector<int> h_pre, h_blo, h_bhi, h_bside;                             // dc_island_table of the handle's branch table
@@ -73,7 +75,7 @@ struct DcHandle : DcDevice {
     bool solved = false;
 };
 
-int dc_base_solve(DcHandle* h);    // theta_0 = B^-1 rhs on lane 0 of the base buffers (jg_dc.hip; the pair and series builds start from it)
+int dc_base_solve(DcHandle* h);    // theta_0 = B^-1 rhs on lane 0 of the base buffers (jg_dc.hip; the build of Phi starts from it)
 
 // Who leaves with a bridge: ONE DFS of the in-service bus graph (admittance != 0, self-loops aside) from the slack numbers the buses in preorder; the
 // subtree below a tree edge is a contiguous interval of those numbers, and a tree edge (p, u) is a bridge iff no edge other than itself leaves u's subtree
@@ -81,5 +83,7 @@ int dc_base_solve(DcHandle* h);    // theta_0 = B^-1 rhs on lane 0 of the base b
 // WITHOUT the slack.  Per branch: lo..hi the interval of S (lo > hi: not a bridge), side +1 / -1: the end m on the slack's side is the from / to end
 // (0: not a bridge).  preorder is -1 on buses the slack does not reach.  Host only; 0-based buses.
 void dc_island_table(int n, int nbr, const int* from, const int* to, const double* admittance, int slack, int* preorder, int* lo, int* hi, int* side);
+// h_pre / h_blo / h_bhi / h_bside of the handle's branch table, made once (jg_dc.hip; jg_dc_set_island_mode and the shed build of jg_dc_phi.hip ask for it)
+void dc_handle_island_table(DcHandle* h);
 
 }  // namespace jg

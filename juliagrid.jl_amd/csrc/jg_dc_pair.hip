@@ -1,7 +1,6 @@
 // jg_dc_pair.hip -- the DC N-2 screen over all pairs of a candidate list (jg_dc_pair.hpp has the algebra and the reference loop it stands for).
 //
-// Build: the sweep pair of jg_dc_sweep.hip over the candidates, DC_PAIR_LANES at a time, and k_pair_phi after each batch (the flow kernel's shape: a wave
-// is 8 rows x 64 candidates, y_m (z[from_m] - z[to_m]), coalesced stores).  Screen of a row block [k0, k1): k_pair_screen solves the 2 x 2 systems and
+// Build: Phi by dc_phi_build (jg_dc_phi.hip).  Screen of a row block [k0, k1): k_pair_screen solves the 2 x 2 systems and
 // walks the rows of Phi once (a wave = DC_PAIR_TILE candidates k in registers x 64 consecutive l; Phi[m, k..], f0_m, 1 / rating_m through scalar loads,
 // Phi[m, l..l+63] one coalesced vector load reused for every k of the tile; nothing is written per m); the records come out of the block's dense result by
 // count (k_pair_rows<false>) / prefix sum over the rows (host, a few thousand integers) / ordered scatter (k_pair_rows<true>: ballot ranks, no atomics),
@@ -11,55 +10,13 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
-#include <cstdio>
-#include <cstring>
 #include <type_traits>
 
 #include "../../include/jgrid.h"
-#include "jg_dc.hpp"
-#include "jg_dc_abi.hpp"
 
 namespace jg {
 
 namespace {
-
-constexpr int PAIR_PHI_ROWS = 8;        // rows of Phi per wave of k_pair_phi
-
-// base-case flows on the rows of Phi, formed as k_dc_flows forms them (the slack angle added to both ends first)
-__global__ void k_pair_f0(const double* th0, const int* rbranch, const int* bf, const int* bt, const double* by, const double* bs, double slack_angle,
-                          double* f0, int rows) {
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= rows) return;
-    const int m = rbranch[r];
-    f0[r] = by[m] * ((th0[(size_t)bf[m] * 64] + slack_angle) - (th0[(size_t)bt[m] * 64] + slack_angle) - bs[m]);
-}
-// Phi[r, col0 + lane] = y_m (z[from_m] - z[to_m]) for the candidates of one lane batch
-struct PairPhiArgs { const double* Z; const int* rbranch; const int* bf; const int* bt; const double* by; double* Phi; int rows, ldb, ldk, col0; };
-__global__ __launch_bounds__(256) void k_pair_phi(PairPhiArgs a) {
-    const int wave = uniform(threadIdx.y);
-    const int r0 = (blockIdx.x * 4 + wave) * PAIR_PHI_ROWS;
-    const size_t ldb = (size_t)a.ldb, bl = (size_t)blockIdx.y * 64 + threadIdx.x;
-    const size_t col = (size_t)a.col0 + bl;
-    if (col >= (size_t)a.ldk) return;
-    for (int r = r0; r < min(r0 + PAIR_PHI_ROWS, a.rows); ++r) {
-        const int m = ((CInt)a.rbranch)[r];
-        const int f = ((CInt)a.bf)[m], t = ((CInt)a.bt)[m];
-        const double y = ((CDbl)a.by)[m];
-        a.Phi[(size_t)r * a.ldk + col] = y * (a.Z[(size_t)f * ldb + bl] - a.Z[(size_t)t * ldb + bl]);
-    }
-}
-__global__ void k_pair_cand(const double* Phi, const double* f0, const int* crow, double* cdiag, double* cf0, int nk, int ldk) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= ldk) return;
-    cdiag[j] = j < nk ? Phi[(size_t)crow[j] * ldk + j] : 0.0;
-    cf0[j] = j < nk ? f0[crow[j]] : 0.0;
-}
-__global__ void k_pair_rinv(const double* rating, const int* rbranch, const int* mon, double* rinv, int rows) {
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= rows) return;
-    const double q = rating[rbranch[r]];
-    rinv[r] = (mon[r] && q > 0.0) ? 1.0 / q : 0.0;
-}
 
 // ---- the screen kernel -------------------------------------------------------------------------------------------------------------------
 struct PairScreenArgs {
@@ -200,185 +157,36 @@ __global__ void k_pair_colmax(const double* load, double* c_max, int ldk, int nk
     c_max[l] = mx;
 }
 
-void state_release(DcHandle* h, DcPairState*& slot) {
-    DcPairState* p = slot;
-    if (!p) return;
-    hipStreamSynchronize(h->stream);
-    dev_release(h, p->Phi); dev_release(h, p->row_branch); dev_release(h, p->row_pos); dev_release(h, p->row_mon); dev_release(h, p->row_f0);
-    dev_release(h, p->row_rinv); dev_release(h, p->cand_row); dev_release(h, p->cand_label); dev_release(h, p->cand_diag); dev_release(h, p->cand_f0);
-    dev_release(h, p->b_load); dev_release(h, p->b_branch); dev_release(h, p->b_count); dev_release(h, p->b_det);
-    dev_release(h, p->r_viol); dev_release(h, p->r_isl); dev_release(h, p->r_max); dev_release(h, p->r_off); dev_release(h, p->r_ioff);
-    dev_release(h, p->c_max); dev_release(h, p->rec); dev_release(h, p->isl); dev_release(h, p->cand_isl); dev_release(h, p->row_pre);
-    delete p;
-    slot = nullptr;
-}
-void pair_release(DcHandle* h) { state_release(h, h->pair); }
-
-std::string bytes_text(size_t b) {
-    char t[64];
-    snprintf(t, sizeof t, "%zu bytes (%.2f GiB)", b, (double)b / (1024.0 * 1024.0 * 1024.0));
-    return t;
+int pair_build(DcHandle* h, const std::vector<int>& cand, const std::vector<int>& mon, int64_t budget, double* info) {
+    dc_state_release(h, h->pair);
+    DcPairState* p = h->pair = new DcPairState();
+    int rc = dc_phi_build(h, &p->phi, "jg_dc_pair_build", cand, mon, budget, 0, "", info);
+    if (!rc) rc = dev_alloc(h, p->mem, &p->c_max, (size_t)p->phi.ldk, (const double*)nullptr, true);
+    return rc ? dc_build_failed(h, h->pair, rc) : 0;
 }
 
-// the build of Phi into `slot` (the pair screen's h->pair, or the state the series screen keeps): `extra` bytes the caller will ask for beside Phi are
-// part of the memory question, `extra_text` names them in the refusal
-int state_build(DcHandle* h, DcPairState*& slot, const char* who, const std::vector<int>& cand, const std::vector<int>& mon, int64_t budget, size_t extra,
-                const std::string& extra_text, double* info, bool shed) {
-    state_release(h, slot);
-    if (h->base_dirty) DC_TRY(dc_base_solve(h));
-    const int nk = (int)cand.size(), ldk = (nk + 63) / 64 * 64, n = h->n;
-    std::vector<int> rows, pos, flag, crow(ldk, 0), clab(ldk, 0);
-    {
-        std::vector<char> is_mon(h->nbr, 0);
-        std::vector<int> cpos(h->nbr, -1);
-        for (int m : mon) is_mon[m] = 1;
-        for (int j = 0; j < nk; ++j) cpos[cand[j]] = j;
-        for (int m = 0; m < h->nbr; ++m)
-            if (is_mon[m] || cpos[m] >= 0) {
-                if (cpos[m] >= 0) { crow[cpos[m]] = (int)rows.size(); clab[cpos[m]] = m + 1; }
-                rows.push_back(m); pos.push_back(cpos[m]); flag.push_back(is_mon[m]);
-            }
-    }
-    const int nr = (int)rows.size();
-    const int ldb = std::min(ldk, DC_PAIR_LANES);
-    const size_t phi_bytes = (size_t)nr * ldk * sizeof(double);
-    const size_t scratch = ((size_t)2 * n + 1) * ldb * sizeof(double) + (size_t)2 * ldb * sizeof(int) +
-                           (shed ? ((size_t)4 * ldk + nr) * sizeof(int) : 0);       // (shed mode: the candidates' intervals and the rows' preorder numbers)
-    size_t free_b = 0, total_b = 0;
-    DC_HIP(hipMemGetInfo(&free_b, &total_b));
-    const size_t allowed = budget > 0 ? (size_t)budget : (size_t)(DC_PAIR_BUDGET * (double)free_b);
-    info[0] = nr; info[1] = ldk; info[2] = (double)phi_bytes; info[3] = (double)free_b; info[4] = (double)allowed; info[5] = info[6] = info[7] = 0.0;
-    if (phi_bytes + scratch + extra > allowed || phi_bytes + scratch + extra > free_b) {
-        h->error = std::string(who) + ": Phi needs " + bytes_text(phi_bytes) + " (" + std::to_string(nr) + " rows x " + std::to_string(ldk) + " candidates x 8) and " +
-                   bytes_text(scratch) + " of scratch" + extra_text + "; the budget is " + bytes_text(allowed) + ", " + bytes_text(free_b) + " are free: fewer candidates or monitored branches, or a larger budget";
-        return 5;
-    }
-    DcPairState* p = new DcPairState();
-    slot = p;
-    p->nk = nk; p->ldk = ldk; p->rows = nr; p->h_cand = cand;
-    DC_TRY(dev_alloc(h, &p->Phi, (size_t)nr * ldk, (const double*)nullptr, true));
-    DC_TRY(dev_alloc(h, &p->row_branch, (size_t)nr, rows.data()));
-    DC_TRY(dev_alloc(h, &p->row_pos, (size_t)nr, pos.data()));
-    DC_TRY(dev_alloc(h, &p->row_mon, (size_t)nr, flag.data()));
-    DC_TRY(dev_alloc(h, &p->row_f0, (size_t)nr, (const double*)nullptr, true));
-    DC_TRY(dev_alloc(h, &p->row_rinv, (size_t)nr, (const double*)nullptr, true));
-    DC_TRY(dev_alloc(h, &p->cand_row, (size_t)ldk, crow.data()));
-    DC_TRY(dev_alloc(h, &p->cand_label, (size_t)ldk, clab.data()));
-    DC_TRY(dev_alloc(h, &p->cand_diag, (size_t)ldk, (const double*)nullptr, true));
-    DC_TRY(dev_alloc(h, &p->cand_f0, (size_t)ldk, (const double*)nullptr, true));
-    DC_TRY(dev_alloc(h, &p->c_max, (size_t)ldk, (const double*)nullptr, true));
-    if (shed) {
-        if (h->h_pre.empty()) {                                  // the table of the handle's grid, once (jg_dc_set_island_mode makes the same)
-            h->h_pre.resize(n); h->h_blo.resize(h->nbr); h->h_bhi.resize(h->nbr); h->h_bside.resize(h->nbr);
-            dc_island_table(n, h->nbr, h->h_from.data(), h->h_to.data(), h->h_y.data(), h->slack, h->h_pre.data(), h->h_blo.data(), h->h_bhi.data(), h->h_bside.data());
-        }
-        p->shed = true;
-        p->h_side.assign(nk, 0); p->h_lo.assign(nk, 1); p->h_hi.assign(nk, 0);
-        std::vector<int> cisl((size_t)4 * ldk, 0), rpre(nr);
-        for (int j = 0; j < ldk; ++j) cisl[4 * j + 1] = 1;
-        for (int j = 0; j < nk; ++j)
-            if (h->h_bside[cand[j]] != 0) {
-                p->h_side[j] = cisl[4 * j] = h->h_bside[cand[j]]; p->h_lo[j] = cisl[4 * j + 1] = h->h_blo[cand[j]]; p->h_hi[j] = cisl[4 * j + 2] = h->h_bhi[cand[j]];
-            }
-        for (int r = 0; r < nr; ++r) rpre[r] = h->h_pre[h->h_from[rows[r]]];
-        DC_TRY(dev_alloc(h, &p->cand_isl, (size_t)4 * ldk, cisl.data()));
-        DC_TRY(dev_alloc(h, &p->row_pre, (size_t)nr, rpre.data()));
-    }
-    // scratch of the build: the lanes' outage buses and one lane batch of the sweeps
-    int* of = nullptr; int* ot = nullptr; double* W = nullptr; double* Z = nullptr;
-    DC_TRY(dev_alloc(h, &of, (size_t)ldb, (const int*)nullptr, false));
-    DC_TRY(dev_alloc(h, &ot, (size_t)ldb, (const int*)nullptr, false));
-    DC_TRY(dev_alloc(h, &W, ((size_t)n + 1) * ldb, (const double*)nullptr, true));
-    DC_TRY(dev_alloc(h, &Z, (size_t)n * ldb, (const double*)nullptr, true));
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    int rc = 0;
-    auto hip = [&](hipError_t e, const char* what) { if (e != hipSuccess && !rc) { rc = 2; h->error = std::string(what) + ": " + hipGetErrorString(e); } return e == hipSuccess; };
-    for (auto& e : ev) hip(hipEventCreate(&e), "hipEventCreate");
-    hipLaunchKernelGGL(k_pair_f0, dim3((nr + 255) / 256), dim3(256), 0, h->stream, h->th0, p->row_branch, h->b_from, h->b_to, h->b_y, h->b_shift, h->slack_angle, p->row_f0, nr);
-    double sweep_ms = 0.0, phi_ms = 0.0;
-    std::vector<int> hf(ldb), ht(ldb);
-    for (int c0 = 0; c0 < ldk && !rc; c0 += ldb) {
-        for (int j = 0; j < ldb; ++j) {
-            const int q = c0 + j;
-            hf[j] = ht[j] = -1;
-            if (q < nk) {
-                const int m = cand[q];
-                hf[j] = h->h_from[m] == h->slack ? -1 : h->h_from[m];     // the slack's component of a = e_from - e_to is dropped
-                ht[j] = h->h_to[m] == h->slack ? -1 : h->h_to[m];
-                if (shed && p->h_side[q] != 0) {                 // a bridge: e_m of its end on the slack's side (all zero where that is the slack)
-                    if (p->h_side[q] < 0) hf[j] = ht[j];
-                    ht[j] = -1;
-                }
-            }
-        }
-        if (!hip(sync_copy(of, hf.data(), ldb * sizeof(int), hipMemcpyHostToDevice, h->stream), "upload") ||
-            !hip(sync_copy(ot, ht.data(), ldb * sizeof(int), hipMemcpyHostToDevice, h->stream), "upload")) break;
-        const int groups = (std::min(ldb, ldk - c0) + 63) / 64;
-        hip(hipEventRecord(ev[0], h->stream), "hipEventRecord");
-        sweep_pair(h->fac, h->stream, 1, nullptr, of, ot, W, Z, ldb, groups, nullptr);
-        hip(hipEventRecord(ev[1], h->stream), "hipEventRecord");
-        PairPhiArgs a{Z, p->row_branch, h->b_from, h->b_to, h->b_y, p->Phi, nr, ldb, ldk, c0};
-        hipLaunchKernelGGL(k_pair_phi, dim3((nr + 4 * PAIR_PHI_ROWS - 1) / (4 * PAIR_PHI_ROWS), groups), dim3(64, 4), 0, h->stream, a);
-        hip(hipEventRecord(ev[2], h->stream), "hipEventRecord");
-        hip(hipGetLastError(), "launch");
-        if (!hip(hipEventSynchronize(ev[2]), "hipEventSynchronize")) break;
-        float t1 = 0.f, t2 = 0.f;
-        hip(hipEventElapsedTime(&t1, ev[0], ev[1]), "hipEventElapsedTime");
-        hip(hipEventElapsedTime(&t2, ev[1], ev[2]), "hipEventElapsedTime");
-        sweep_ms += t1; phi_ms += t2;
-    }
-    if (!rc) {
-        hipLaunchKernelGGL(k_pair_cand, dim3((ldk + 255) / 256), dim3(256), 0, h->stream, p->Phi, p->row_f0, p->cand_row, p->cand_diag, p->cand_f0, nk, ldk);
-        hip(hipGetLastError(), "launch");
-        hip(hipStreamSynchronize(h->stream), "hipStreamSynchronize");
-    }
-    for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-    dev_release(h, of); dev_release(h, ot); dev_release(h, W); dev_release(h, Z);
-    if (rc) { const std::string msg = h->error; state_release(h, slot); h->error = msg; return rc; }
-    p->build_ms[0] = sweep_ms + phi_ms; p->build_ms[1] = sweep_ms; p->build_ms[2] = phi_ms;
-    info[5] = p->build_ms[0]; info[6] = sweep_ms; info[7] = phi_ms;
-    return 0;
-}
-
-// the block's buffers for `rb` rows (and the determinants, on request); grown, never shrunk
+// the block's buffers for `rb` rows (and the determinants, on request: kept once allocated); grown, never shrunk
 int pair_block(DcHandle* h, int rb, bool want_det, long long rec_cap, long long isl_cap) {
     DcPairState* p = h->pair;
     if (rb > p->blk_rows || (want_det && !p->b_det)) {
         const int rows = std::max(rb, p->blk_rows);
         const bool det = want_det || p->b_det != nullptr;
-        const size_t cells = (size_t)rows * p->ldk, need = cells * (det ? 24 : 16);
-        dev_release(h, p->b_load); dev_release(h, p->b_branch); dev_release(h, p->b_count); dev_release(h, p->b_det);
-        dev_release(h, p->r_viol); dev_release(h, p->r_isl); dev_release(h, p->r_max); dev_release(h, p->r_off); dev_release(h, p->r_ioff);
-        p->blk_rows = 0;
-        size_t free_b = 0, total_b = 0;
-        DC_HIP(hipMemGetInfo(&free_b, &total_b));
-        if (need > free_b) {
-            h->error = "jg_dc_pair_screen: a block of " + std::to_string(rows) + " rows needs " + bytes_text(need) + ", " + bytes_text(free_b) + " are free: screen fewer rows per call";
-            return 5;
-        }
-        DC_TRY(dev_alloc(h, &p->b_load, cells, (const double*)nullptr, true));
-        DC_TRY(dev_alloc(h, &p->b_branch, cells, (const int*)nullptr, true));
-        DC_TRY(dev_alloc(h, &p->b_count, cells, (const int*)nullptr, true));
-        if (det) DC_TRY(dev_alloc(h, &p->b_det, cells, (const double*)nullptr, true));
-        DC_TRY(dev_alloc(h, &p->r_viol, (size_t)rows, (const int*)nullptr, true));
-        DC_TRY(dev_alloc(h, &p->r_isl, (size_t)rows, (const int*)nullptr, true));
-        DC_TRY(dev_alloc(h, &p->r_max, (size_t)rows, (const double*)nullptr, true));
-        DC_TRY(dev_alloc(h, &p->r_off, (size_t)rows, (const long long*)nullptr, true));
-        DC_TRY(dev_alloc(h, &p->r_ioff, (size_t)rows, (const long long*)nullptr, true));
-        p->blk_rows = rows;
+        const size_t cells = (size_t)rows * p->phi.ldk, r = (size_t)rows;
+        DC_TRY(dc_block_grow(h, p->mem, "jg_dc_pair_screen", rows, p->blk_rows, cells * (det ? 24 : 16), dc_blk(p->b_load, cells), dc_blk(p->b_branch, cells),
+                             dc_blk(p->b_count, cells), dc_blk(p->b_det, det ? cells : 0), dc_blk(p->r_viol, r), dc_blk(p->r_isl, r), dc_blk(p->r_max, r),
+                             dc_blk(p->r_off, r), dc_blk(p->r_ioff, r)));
     }
-    if (rec_cap > p->rec_cap) { dev_release(h, p->rec); p->rec_cap = 0; DC_TRY(dev_alloc(h, &p->rec, (size_t)rec_cap * 5, (const double*)nullptr, true)); p->rec_cap = rec_cap; }
-    if (isl_cap > p->isl_cap) { dev_release(h, p->isl); p->isl_cap = 0; DC_TRY(dev_alloc(h, &p->isl, (size_t)isl_cap * 2, (const long long*)nullptr, true)); p->isl_cap = isl_cap; }
-    return 0;
+    DC_TRY(dc_list_grow(h, p->mem, p->rec, p->rec_cap, rec_cap, 5));
+    return dc_list_grow(h, p->mem, p->isl, p->isl_cap, isl_cap, 2);
 }
 
 PairScreenArgs screen_args(DcHandle* h, int k0, int k1, double thr, bool det) {
     DcPairState* p = h->pair;
     PairScreenArgs a{};
-    a.Phi = p->Phi; a.f0 = p->row_f0; a.rinv = p->row_rinv; a.pos = p->row_pos; a.rbranch = p->row_branch;
-    a.crow = p->cand_row; a.cdiag = p->cand_diag; a.cf0 = p->cand_f0;
+    a.Phi = p->phi.Phi; a.f0 = p->phi.row_f0; a.rinv = p->phi.row_rinv; a.pos = p->phi.row_pos; a.rbranch = p->phi.row_branch;
+    a.crow = p->phi.cand_row; a.cdiag = p->phi.cand_diag; a.cf0 = p->phi.cand_f0;
     a.load = p->b_load; a.branch = p->b_branch; a.count = p->b_count; a.det = det ? p->b_det : nullptr;
-    a.thr = thr; a.rows = p->rows; a.ldk = p->ldk; a.nk = p->nk; a.k0 = k0; a.k1 = k1; a.kbase = k0 / DC_PAIR_TILE * DC_PAIR_TILE;
+    a.thr = thr; a.rows = p->phi.rows; a.ldk = p->phi.ldk; a.nk = p->phi.nk; a.k0 = k0; a.k1 = k1; a.kbase = k0 / DC_PAIR_TILE * DC_PAIR_TILE;
     return a;
 }
 void launch_screen(DcHandle* h, const PairScreenArgs& a) {
@@ -388,37 +196,27 @@ void launch_screen(DcHandle* h, const PairScreenArgs& a) {
 PairListArgs list_args(DcHandle* h, int k0, int k1, double thr, long long rec_cap, long long isl_cap) {
     DcPairState* p = h->pair;
     PairListArgs a{};
-    a.load = p->b_load; a.branch = p->b_branch; a.count = p->b_count; a.clabel = p->cand_label;
+    a.load = p->b_load; a.branch = p->b_branch; a.count = p->b_count; a.clabel = p->phi.cand_label;
     a.r_viol = p->r_viol; a.r_isl = p->r_isl; a.r_max = p->r_max; a.r_off = p->r_off; a.r_ioff = p->r_ioff;
     a.rec = p->rec; a.rec_cap = rec_cap; a.isl = p->isl; a.isl_cap = isl_cap;
-    a.thr = thr; a.ldk = p->ldk; a.nk = p->nk; a.k0 = k0; a.k1 = k1;
+    a.thr = thr; a.ldk = p->phi.ldk; a.nk = p->phi.nk; a.k0 = k0; a.k1 = k1;
     return a;
 }
 void launch_stats(DcHandle* h, const PairListArgs& a) {
     DcPairState* p = h->pair;
     hipLaunchKernelGGL((k_pair_rows<false>), dim3((a.k1 - a.k0 + 3) / 4), dim3(64, 4), 0, h->stream, a);
-    hipLaunchKernelGGL(k_pair_colmax, dim3((p->ldk + 255) / 256), dim3(256), 0, h->stream, p->b_load, p->c_max, p->ldk, p->nk, a.k0, a.k1);
+    hipLaunchKernelGGL(k_pair_colmax, dim3((a.ldk + 255) / 256), dim3(256), 0, h->stream, p->b_load, p->c_max, a.ldk, a.nk, a.k0, a.k1);
 }
 
 struct PairOut {
     double* records; int64_t* islanding; int64_t* totals; double* worst;
     double* d_load; int32_t* d_branch; int32_t* d_count; double* d_det;
 };
-// the block's dense result of one quantity on the host: [k1 - k0][nk], 0 where l <= k
-template <typename V, typename D>
-int pair_dense(DcHandle* h, D* dst, const V* src, int k0, int rb) {
-    const int nk = h->pair->nk, ldk = h->pair->ldk;
-    std::vector<V> t((size_t)rb * ldk);
-    DC_HIP(sync_copy(t.data(), src, t.size() * sizeof(V), hipMemcpyDeviceToHost, h->stream));
-    for (int i = 0; i < rb; ++i)
-        for (int l = 0; l < nk; ++l) dst[(size_t)i * nk + l] = l > k0 + i ? (D)t[(size_t)i * ldk + l] : D(0);
-    return 0;
-}
 int pair_screen(DcHandle* h, int k0, int k1, double thr, long long rec_cap, long long isl_cap, const PairOut& o) {
     DcPairState* p = h->pair;
-    const int rb = k1 - k0, nk = p->nk, ldk = p->ldk;
+    const int rb = k1 - k0, nk = p->phi.nk, ldk = p->phi.ldk;
     DC_TRY(pair_block(h, rb, o.d_det != nullptr, rec_cap, isl_cap));
-    dc_pair_state_rinv(h, p);
+    dc_phi_rinv(h, &p->phi);
     launch_screen(h, screen_args(h, k0, k1, thr, o.d_det != nullptr));
     PairListArgs la = list_args(h, k0, k1, thr, rec_cap, isl_cap);
     launch_stats(h, la);
@@ -429,9 +227,10 @@ int pair_screen(DcHandle* h, int k0, int k1, double thr, long long rec_cap, long
     DC_HIP(hipMemcpyAsync(ni.data(), p->r_isl, rb * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     DC_HIP(hipMemcpyAsync(rmax.data(), p->r_max, rb * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     DC_HIP(sync_copy(cmax.data(), p->c_max, ldk * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    std::vector<long long> off(rb), ioff(rb);
-    long long viol = 0, isl = 0, pairs = 0;
-    for (int i = 0; i < rb; ++i) { off[i] = viol; ioff[i] = isl; viol += nv[i]; isl += ni[i]; pairs += nk - 1 - (k0 + i); }
+    std::vector<long long> off, ioff;
+    const long long viol = dc_prefix(nv, off), isl = dc_prefix(ni, ioff);
+    long long pairs = 0;
+    for (int i = 0; i < rb; ++i) pairs += nk - 1 - (k0 + i);
     const long long nrec = std::min(viol, rec_cap), nisl = std::min(isl, isl_cap);
     if (nrec || nisl) {
         DC_HIP(hipMemcpyAsync(p->r_off, off.data(), rb * sizeof(long long), hipMemcpyHostToDevice, h->stream));
@@ -450,47 +249,17 @@ int pair_screen(DcHandle* h, int k0, int k1, double thr, long long rec_cap, long
             if (j >= k0 && j < k1) w = std::max(w, rmax[j - k0]);
             o.worst[j] = std::max(o.worst[j], w);
         }
-    if (o.d_load) DC_TRY(pair_dense(h, o.d_load, (const double*)p->b_load, k0, rb));
-    if (o.d_branch) DC_TRY(pair_dense(h, o.d_branch, (const int*)p->b_branch, k0, rb));
-    if (o.d_count) DC_TRY(pair_dense(h, o.d_count, (const int*)p->b_count, k0, rb));
-    if (o.d_det) DC_TRY(pair_dense(h, o.d_det, (const double*)p->b_det, k0, rb));
+    auto upper = [k0](int i, int l, auto v) { return l > k0 + i ? v : decltype(v)(0); };       // the block's dense results are [k1 - k0][nk], 0 where l <= k
+    if (o.d_load) DC_TRY(dc_dense(h, o.d_load, (const double*)p->b_load, rb, ldk, nk, upper));
+    if (o.d_branch) DC_TRY(dc_dense(h, o.d_branch, (const int*)p->b_branch, rb, ldk, nk, upper));
+    if (o.d_count) DC_TRY(dc_dense(h, o.d_count, (const int*)p->b_count, rb, ldk, nk, upper));
+    if (o.d_det) DC_TRY(dc_dense(h, o.d_det, (const double*)p->b_det, rb, ldk, nk, upper));
     return 0;
 }
 
 }  // namespace
 
-void dc_pair_free(DcHandle* h) { pair_release(h); }
-void dc_pair_state_free(DcHandle* h, DcPairState*& slot) { state_release(h, slot); }
-int dc_pair_state_build(DcHandle* h, DcPairState*& slot, const char* who, const std::vector<int>& cand, const std::vector<int>& mon, int64_t budget,
-                        size_t extra, const std::string& extra_text, double* info, bool shed) {
-    return state_build(h, slot, who, cand, mon, budget, extra, extra_text, info, shed);
-}
-void dc_pair_state_rinv(DcHandle* h, DcPairState* p) {
-    hipLaunchKernelGGL(k_pair_rinv, dim3((p->rows + 255) / 256), dim3(256), 0, h->stream, h->b_rating, p->row_branch, p->row_mon, p->row_rinv, p->rows);
-}
-std::string dc_pair_bytes_text(size_t b) { return bytes_text(b); }
-
-int dc_pair_lists(DcHandle* d, const std::string& who, int64_t nk, const int64_t* candidates, int64_t nm, const int64_t* monitored, std::vector<int>& cand,
-                  std::vector<int>& mon) {
-    cand.assign(nk, 0); mon.clear();
-    for (int64_t j = 0; j < nk; ++j) {
-        const int64_t m = candidates[j] - 1;
-        if (m < 0 || m >= d->nbr) { d->error = who + ": candidate branch out of range"; return 1; }
-        if (j && m <= cand[j - 1]) { d->error = who + ": the candidates must ascend strictly (no branch twice)"; return 1; }
-        if (d->h_y[m] == 0.0) { d->error = who + ": candidate branch " + std::to_string(m + 1) + " is out of service"; return 1; }
-        cand[j] = (int)m;
-    }
-    if (monitored) {
-        for (int64_t j = 0; j < nm; ++j) {
-            const int64_t m = monitored[j] - 1;
-            if (m < 0 || m >= d->nbr) { d->error = who + ": monitored branch out of range"; return 1; }
-            mon.push_back((int)m);
-        }
-    } else {
-        for (int m = 0; m < d->nbr; ++m) if (d->h_y[m] != 0.0) mon.push_back(m);      // every branch in service
-    }
-    return 0;
-}
+void dc_pair_free(DcHandle* h) { dc_state_release(h, h->pair); }
 
 }  // namespace jg
 
@@ -506,8 +275,8 @@ int jg_dc_pair_build(int64_t h, int64_t nk, const int64_t* candidates, int64_t n
     if (d->h_rhs.empty()) return api_fail(1, "jg_dc_pair_build: jg_dc_set_rhs first");
     if (nk < 2 || !candidates || !info || nm < 0 || (nm && !monitored)) return api_fail(1, "jg_dc_pair_build: two or more candidates, and info, are needed");
     std::vector<int> cand, mon;
-    DC_RET(jg::dc_pair_lists(d, "jg_dc_pair_build", nk, candidates, nm, monitored, cand, mon));
-    DC_RET(jg::dc_pair_state_build(d, d->pair, "jg_dc_pair_build", cand, mon, budget_bytes, 0, "", info));
+    DC_RET(jg::dc_phi_lists(d, "jg_dc_pair_build", nk, candidates, nm, monitored, cand, mon));
+    DC_RET(jg::pair_build(d, cand, mon, budget_bytes, info));
     return 0;
 }
 
@@ -516,7 +285,7 @@ int jg_dc_pair_screen(int64_t h, int64_t k0, int64_t k1, double threshold, int64
     DC_ENTER(h);
     if (!d->pair) return api_fail(4, "jg_dc_pair_screen: jg_dc_pair_build first");
     if (!d->b_rating) return api_fail(1, "jg_dc_pair_screen: jg_dc_set_rating first (the loadings are |from| / rating)");
-    if (k0 < 0 || k1 <= k0 || k1 > d->pair->nk) return api_fail(1, "jg_dc_pair_screen: rows [k0, k1) out of range");
+    if (k0 < 0 || k1 <= k0 || k1 > d->pair->phi.nk) return api_fail(1, "jg_dc_pair_screen: rows [k0, k1) out of range");
     if (!(threshold >= 0.0) || capacity < 0 || island_capacity < 0 || (capacity && !records) || (island_capacity && !islanding) || !totals)
         return api_fail(1, "jg_dc_pair_screen: bad argument");
     jg::PairOut o{records, islanding, totals, worst, dense_load, dense_branch, dense_count, dense_det};
@@ -526,17 +295,14 @@ int jg_dc_pair_screen(int64_t h, int64_t k0, int64_t k1, double threshold, int64
 
 int jg_dc_pair_time_kernel(int64_t h, int kernel, int64_t k0, int64_t k1, int reps, double* ms) {
     DC_ENTER(h);
-    if (!d->pair) return api_fail(4, "jg_dc_pair_time_kernel: jg_dc_pair_build first");
-    if (!ms || reps < 1 || kernel < 0 || kernel > 1 || k0 < 0 || k1 <= k0 || k1 > d->pair->nk) return api_fail(1, "jg_dc_pair_time_kernel: bad argument");
-    if (k1 - k0 > d->pair->blk_rows) return api_fail(4, "jg_dc_pair_time_kernel: jg_dc_pair_screen with a block of at least these rows first");
-    const jg::PairScreenArgs sa = jg::screen_args(d, (int)k0, (int)k1, 1.0, false);
-    const jg::PairListArgs la = jg::list_args(d, (int)k0, (int)k1, 1.0, 0, 0);
-    DC_RET(jg::time_events(d->stream, reps, ms, d->error, [&]() -> int {
-        if (kernel == 0) jg::launch_screen(d, sa);
-        else jg::launch_stats(d, la);
-        return 0;
-    }));
-    return 0;
+    jg::DcPairState* p = d->pair;
+    return jg::dc_phi_time_kernel(d, "pair", p ? &p->phi : nullptr, p ? p->blk_rows : 0, kernel, k0, k1, reps, ms,
+                                  [&] {
+        return [d, sa = jg::screen_args(d, (int)k0, (int)k1, 1.0, false), la = jg::list_args(d, (int)k0, (int)k1, 1.0, 0, 0)](int which) {
+            if (which == 0) jg::launch_screen(d, sa);
+            else jg::launch_stats(d, la);
+        };
+    });
 }
 
 int jg_dc_pair_release(int64_t h) {

@@ -1,8 +1,7 @@
 // jg_dc_series.hip -- the DC N-1 screen over a series of injection profiles (jg_dc_series.hpp has the algebra and the reference loop it stands for).
 //
-// Build: Phi by the build the pair screen shares (jg_dc_pair.hip), into a state of the series' own; then the sweep pair of jg_dc_sweep.hip over the
-// profiles' right-hand sides, DC_PAIR_LANES at a time on scratch of the build's own, and k_series_f0 after each batch (k_pair_phi's shape: a wave is 8 rows
-// x 64 profiles, y_m ((theta[from_m] + slack angle) - (theta[to_m] + slack angle) - shiftAngle_m), coalesced stores).  Screen of a row block [k0, k1):
+// Build: Phi by the build the three screens share (dc_phi_build, jg_dc_phi.hip), into a state of the series' own; then F0, the row flows of the profiles'
+// right-hand sides (dc_phi_row_flows: the sweep pair of jg_dc_sweep.hip, DC_PAIR_LANES profiles at a time).  Screen of a row block [k0, k1):
 // k_series_screen walks the rows once (a wave = DC_SERIES_TILE candidates k in registers x 64 consecutive profiles; Phi[m, k..], 1 / rating_m and the
 // row's candidate position through scalar loads, F0[m, t..t+63] one coalesced vector load reused for every k of the tile; nothing is written per m); the
 // records come out of the block's dense result by count (k_series_rows<false>) / prefix sum over the rows (host) / ordered scatter
@@ -12,40 +11,13 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
-#include <cstdio>
-#include <cstring>
 #include <type_traits>
 
 #include "../../include/jgrid.h"
-#include "jg_dc.hpp"
-#include "jg_dc_abi.hpp"
 
 namespace jg {
 
 namespace {
-
-constexpr int SERIES_F0_ROWS = 8;       // rows of F0 per wave of k_series_f0
-
-// F0[r, col0 + lane] = y_m ((theta[from_m] + slack angle) - (theta[to_m] + slack angle) - shiftAngle_m) for the profiles of one lane batch, formed as
-// k_dc_flows forms a flow; columns behind the last profile stay 0.  SHIFT false: y_m (theta[from_m] - theta[to_m]), what the flow gains per unit of the
-// right-hand side (the transfer screen's G), formed as k_pair_phi forms Phi
-struct SeriesF0Args { const double* TH; const int* rbranch; const int* bf; const int* bt; const double* by; const double* bs; double slack_angle;
-                      double* F0; int rows, ldb, ldt, col0, T; };
-template <bool SHIFT>
-__global__ __launch_bounds__(256) void k_series_f0(SeriesF0Args a) {
-    const int wave = uniform(threadIdx.y);
-    const int r0 = (blockIdx.x * 4 + wave) * SERIES_F0_ROWS;
-    const size_t ldb = (size_t)a.ldb, bl = (size_t)blockIdx.y * 64 + threadIdx.x;
-    const size_t col = (size_t)a.col0 + bl;
-    if (col >= (size_t)a.T) return;
-    for (int r = r0; r < min(r0 + SERIES_F0_ROWS, a.rows); ++r) {
-        const int m = ((CInt)a.rbranch)[r];
-        const int f = ((CInt)a.bf)[m], t = ((CInt)a.bt)[m];
-        const double y = ((CDbl)a.by)[m], s = ((CDbl)a.bs)[m];
-        if constexpr (SHIFT) a.F0[(size_t)r * a.ldt + col] = y * ((a.TH[(size_t)f * ldb + bl] + a.slack_angle) - (a.TH[(size_t)t * ldb + bl] + a.slack_angle) - s);
-        else a.F0[(size_t)r * a.ldt + col] = y * (a.TH[(size_t)f * ldb + bl] - a.TH[(size_t)t * ldb + bl]);
-    }
-}
 
 // ---- the screen kernel -------------------------------------------------------------------------------------------------------------------
 struct SeriesScreenArgs {
@@ -202,84 +174,9 @@ __global__ void k_series_base(const double* F0, const double* rinv, const int* r
     q[0] = wl; q[1] = il < 0 ? 0.0 : (double)(rbranch[il] + 1); q[2] = (double)cnt;
 }
 
-// what left m over the bridge before the outage, for the bridge candidates `list` of a block: out[j][t] = s_k F[row of k][t]
-__global__ void k_shed_gather(const double* F, const int* crow, const int* cisl, const int* list, double* out, int nb, int ldt, int T) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= T) return;
-    for (int j = blockIdx.y; j < nb; j += gridDim.y) {
-        const int k = list[j];
-        out[(size_t)j * T + t] = (cisl[4 * k] > 0 ? 1.0 : -1.0) * F[(size_t)crow[k] * ldt + t];
-    }
-}
-
-void series_release(DcHandle* h) {
-    DcSeriesState* s = h->series;
-    if (!s) return;
-    hipStreamSynchronize(h->stream);
-    dc_pair_state_free(h, s->phi);
-    dev_release(h, s->F0); dev_release(h, s->b_load); dev_release(h, s->b_branch); dev_release(h, s->b_count);
-    dev_release(h, s->r_viol); dev_release(h, s->r_max); dev_release(h, s->r_off); dev_release(h, s->c_max); dev_release(h, s->c_viol);
-    dev_release(h, s->base); dev_release(h, s->rec);
-    delete s;
-    h->series = nullptr;
-}
-
-// the lane-batch loop of a build (dc_series_row_flows of jg_dc_series.hpp): F0 of the series screen with the shift angle, G of the transfer screen without
-int row_flows(DcHandle* h, const DcPairState* p, int T, const double* rhs, bool shift, double* F, int ldt, double* ms) {
-    const int n = h->n, nr = p->rows, ldb = std::min(ldt, DC_PAIR_LANES);
-    int rc = 0;
-    double* R = nullptr; double* W = nullptr; double* TH = nullptr;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    auto hip = [&](hipError_t e, const char* what) { if (e != hipSuccess && !rc) { rc = 2; h->error = std::string(what) + ": " + hipGetErrorString(e); } return e == hipSuccess; };
-    auto alloc = [&](int r) { if (r && !rc) rc = r; return r == 0; };
-    double sweep_ms = 0.0, f0_ms = 0.0;
-    // scratch: one lane batch of right-hand sides and of the sweeps (row n of W stays zero)
-    if (alloc(dev_alloc(h, &R, (size_t)n * ldb, (const double*)nullptr, true)) && alloc(dev_alloc(h, &W, ((size_t)n + 1) * ldb, (const double*)nullptr, true)) &&
-        alloc(dev_alloc(h, &TH, (size_t)n * ldb, (const double*)nullptr, true))) {
-        for (auto& e : ev) hip(hipEventCreate(&e), "hipEventCreate");
-        std::vector<double> tb;
-        for (int c0 = 0; c0 < T && !rc; c0 += ldb) {
-            const int cnt = std::min(ldb, T - c0), groups = (cnt + 63) / 64, w = groups * 64;
-            tb.assign((size_t)n * w, 0.0);                      // bus-major, lanes behind the last profile carry a zero right-hand side
-            for (int q = 0; q < cnt; ++q) {
-                const double* src = rhs + (size_t)(c0 + q) * n;
-                for (int i = 0; i < n; ++i) tb[(size_t)i * w + q] = src[i];
-            }
-            for (int q = 0; q < cnt; ++q) tb[(size_t)h->slack * w + q] = 0.0;
-            if (!hip(hipMemcpy2DAsync(R, (size_t)ldb * sizeof(double), tb.data(), (size_t)w * sizeof(double), (size_t)w * sizeof(double), (size_t)n, hipMemcpyHostToDevice, h->stream), "upload") ||
-                !hip(hipStreamSynchronize(h->stream), "hipStreamSynchronize")) break;
-            hip(hipEventRecord(ev[0], h->stream), "hipEventRecord");
-            sweep_pair(h->fac, h->stream, 0, R, nullptr, nullptr, W, TH, ldb, groups, nullptr);
-            hip(hipEventRecord(ev[1], h->stream), "hipEventRecord");
-            SeriesF0Args a{TH, p->row_branch, h->b_from, h->b_to, h->b_y, h->b_shift, h->slack_angle, F, nr, ldb, ldt, c0, T};
-            const dim3 grid((nr + 4 * SERIES_F0_ROWS - 1) / (4 * SERIES_F0_ROWS), groups);
-            if (shift) hipLaunchKernelGGL(k_series_f0<true>, grid, dim3(64, 4), 0, h->stream, a);
-            else hipLaunchKernelGGL(k_series_f0<false>, grid, dim3(64, 4), 0, h->stream, a);
-            hip(hipEventRecord(ev[2], h->stream), "hipEventRecord");
-            hip(hipGetLastError(), "launch");
-            if (!hip(hipEventSynchronize(ev[2]), "hipEventSynchronize")) break;
-            float t1 = 0.f, t2 = 0.f;
-            hip(hipEventElapsedTime(&t1, ev[0], ev[1]), "hipEventElapsedTime");
-            hip(hipEventElapsedTime(&t2, ev[1], ev[2]), "hipEventElapsedTime");
-            sweep_ms += t1; f0_ms += t2;
-        }
-    }
-    for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-    dev_release(h, R); dev_release(h, W); dev_release(h, TH);
-    ms[0] += sweep_ms; ms[1] += f0_ms;
-    return rc;
-}
-int bridges(DcHandle* h, const DcPairState* p, std::vector<char>& bridge) {
-    std::vector<double> diag(p->ldk);
-    DC_HIP(sync_copy(diag.data(), p->cand_diag, diag.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    bridge.assign(p->nk, 0);
-    for (int k = 0; k < p->nk; ++k) bridge[k] = !(p->shed && p->h_side[k] != 0) && std::fabs(1.0 - diag[k]) < DC_SINGULAR;
-    return 0;
-}
-
 // rhs [T][n]: the lane right-hand sides as jg_dc_set_injections takes them
 int series_build(DcHandle* h, const std::vector<int>& cand, const std::vector<int>& mon, int T, const double* rhs, int64_t budget, double* info) {
-    series_release(h);
+    dc_state_release(h, h->series);
     const bool shed = h->series_shed == 1;
     h->series_shed = 0;
     const int ldt = (T + 63) / 64 * 64;
@@ -290,23 +187,21 @@ int series_build(DcHandle* h, const std::vector<int>& cand, const std::vector<in
         for (int m : cand) in[m] = 1;
         for (char c : in) nr += c;
     }
-    const size_t f0_bytes = (size_t)nr * ldt * sizeof(double), scratch = dc_series_flows_scratch(h, ldt);
+    const size_t f0_bytes = (size_t)nr * ldt * sizeof(double), scratch = dc_phi_flows_scratch(h, ldt);
     for (int j = 8; j < 12; ++j) info[j] = 0.0;
     info[8] = (double)f0_bytes;
-    DcSeriesState* s = new DcSeriesState();
-    h->series = s;
+    DcSeriesState* s = h->series = new DcSeriesState();
     s->T = T; s->ldt = ldt;
-    const std::string extra = "; F0 needs " + dc_pair_bytes_text(f0_bytes) + " (" + std::to_string(nr) + " rows x " + std::to_string(ldt) + " profiles x 8) and " +
-                              dc_pair_bytes_text(scratch) + " of scratch";
-    int rc = dc_pair_state_build(h, s->phi, "jg_dc_series_build", cand, mon, budget, f0_bytes + scratch, extra, info, shed);
-    if (rc) { const std::string msg = h->error; series_release(h); h->error = msg; return rc; }
-    DcPairState* p = s->phi;
-    auto step = [&](int r) { if (r && !rc) rc = r; return r == 0; };
+    const std::string extra = "; F0 needs " + dc_bytes_text(f0_bytes) + " (" + std::to_string(nr) + " rows x " + std::to_string(ldt) + " profiles x 8) and " +
+                              dc_bytes_text(scratch) + " of scratch";
+    int rc = 0;
+    auto step = [&](int r) { if (r && !rc) rc = r; return rc == 0; };
     double ms[2] = {0.0, 0.0};
-    step(dev_alloc(h, &s->F0, (size_t)nr * ldt, (const double*)nullptr, true)) && step(dev_alloc(h, &s->c_max, (size_t)ldt, (const double*)nullptr, true)) &&
-        step(dev_alloc(h, &s->c_viol, (size_t)ldt, (const int*)nullptr, true)) && step(dev_alloc(h, &s->base, (size_t)ldt * 3, (const double*)nullptr, true)) &&
-        step(row_flows(h, p, T, rhs, true, s->F0, ldt, ms)) && step(bridges(h, p, s->h_bridge));
-    if (rc) { const std::string msg = h->error; series_release(h); h->error = msg; return rc; }
+    step(dc_phi_build(h, &s->phi, "jg_dc_series_build", cand, mon, budget, f0_bytes + scratch, extra, info, shed)) &&
+        step(dev_alloc(h, s->mem, &s->F0, (size_t)nr * ldt, (const double*)nullptr, true)) && step(dev_alloc(h, s->mem, &s->c_max, (size_t)ldt, (const double*)nullptr, true)) &&
+        step(dev_alloc(h, s->mem, &s->c_viol, (size_t)ldt, (const int*)nullptr, true)) && step(dev_alloc(h, s->mem, &s->base, (size_t)ldt * 3, (const double*)nullptr, true)) &&
+        step(dc_phi_row_flows(h, &s->phi, T, rhs, true, s->F0, ldt, ms)) && step(dc_phi_bridges(h, &s->phi, s->h_bridge));
+    if (rc) return dc_build_failed(h, h->series, rc);
     s->build_ms[0] = ms[0] + ms[1]; s->build_ms[1] = ms[0]; s->build_ms[2] = ms[1];
     info[9] = s->build_ms[0]; info[10] = ms[0]; info[11] = ms[1];
     return 0;
@@ -316,32 +211,16 @@ int series_build(DcHandle* h, const std::vector<int>& cand, const std::vector<in
 int series_block(DcHandle* h, int rb, long long rec_cap) {
     DcSeriesState* s = h->series;
     if (rb > s->blk_rows) {
-        const size_t cells = (size_t)rb * s->ldt, need = cells * 16;
-        dev_release(h, s->b_load); dev_release(h, s->b_branch); dev_release(h, s->b_count);
-        dev_release(h, s->r_viol); dev_release(h, s->r_max); dev_release(h, s->r_off);
-        s->blk_rows = 0;
-        size_t free_b = 0, total_b = 0;
-        DC_HIP(hipMemGetInfo(&free_b, &total_b));
-        if (need > free_b) {
-            h->error = "jg_dc_series_screen: a block of " + std::to_string(rb) + " rows needs " + dc_pair_bytes_text(need) + ", " + dc_pair_bytes_text(free_b) +
-                       " are free: screen fewer rows per call";
-            return 5;
-        }
-        DC_TRY(dev_alloc(h, &s->b_load, cells, (const double*)nullptr, true));
-        DC_TRY(dev_alloc(h, &s->b_branch, cells, (const int*)nullptr, true));
-        DC_TRY(dev_alloc(h, &s->b_count, cells, (const int*)nullptr, true));
-        DC_TRY(dev_alloc(h, &s->r_viol, (size_t)rb, (const int*)nullptr, true));
-        DC_TRY(dev_alloc(h, &s->r_max, (size_t)rb, (const double*)nullptr, true));
-        DC_TRY(dev_alloc(h, &s->r_off, (size_t)rb, (const long long*)nullptr, true));
-        s->blk_rows = rb;
+        const size_t cells = (size_t)rb * s->ldt, r = (size_t)rb;
+        DC_TRY(dc_block_grow(h, s->mem, "jg_dc_series_screen", rb, s->blk_rows, cells * 16, dc_blk(s->b_load, cells), dc_blk(s->b_branch, cells), dc_blk(s->b_count, cells),
+                             dc_blk(s->r_viol, r), dc_blk(s->r_max, r), dc_blk(s->r_off, r)));
     }
-    if (rec_cap > s->rec_cap) { dev_release(h, s->rec); s->rec_cap = 0; DC_TRY(dev_alloc(h, &s->rec, (size_t)rec_cap * 5, (const double*)nullptr, true)); s->rec_cap = rec_cap; }
-    return 0;
+    return dc_list_grow(h, s->mem, s->rec, s->rec_cap, rec_cap, 5);
 }
 
 SeriesScreenArgs screen_args(DcHandle* h, int k0, int k1, double thr) {
     DcSeriesState* s = h->series;
-    DcPairState* p = s->phi;
+    const DcPhi* p = &s->phi;
     SeriesScreenArgs a{};
     a.Phi = p->Phi; a.F0 = s->F0; a.rinv = p->row_rinv; a.pos = p->row_pos; a.rbranch = p->row_branch; a.crow = p->cand_row; a.cdiag = p->cand_diag;
     a.load = s->b_load; a.branch = s->b_branch; a.count = s->b_count;
@@ -358,7 +237,7 @@ void launch_screen(DcHandle* h, const SeriesScreenArgs& a) {
 SeriesListArgs list_args(DcHandle* h, int k0, int k1, double thr, long long rec_cap) {
     DcSeriesState* s = h->series;
     SeriesListArgs a{};
-    a.load = s->b_load; a.branch = s->b_branch; a.count = s->b_count; a.clabel = s->phi->cand_label;
+    a.load = s->b_load; a.branch = s->b_branch; a.count = s->b_count; a.clabel = s->phi.cand_label;
     a.r_viol = s->r_viol; a.r_max = s->r_max; a.r_off = s->r_off; a.rec = s->rec; a.rec_cap = rec_cap;
     a.thr = thr; a.ldt = s->ldt; a.T = s->T; a.k0 = k0; a.k1 = k1;
     return a;
@@ -373,22 +252,12 @@ struct SeriesOut {
     double* records; int64_t* islanding; int64_t* totals; double* worst; double* worst_profile; int64_t* viol_profile; double* base;
     double* d_load; int32_t* d_branch; int32_t* d_count;
 };
-// the block's dense result of one quantity on the host: [k1 - k0][T]
-template <typename V, typename D>
-int series_dense(DcHandle* h, D* dst, const V* src, int rb) {
-    const int T = h->series->T, ldt = h->series->ldt;
-    std::vector<V> t((size_t)rb * ldt);
-    DC_HIP(sync_copy(t.data(), src, t.size() * sizeof(V), hipMemcpyDeviceToHost, h->stream));
-    for (int i = 0; i < rb; ++i)
-        for (int q = 0; q < T; ++q) dst[(size_t)i * T + q] = (D)t[(size_t)i * ldt + q];
-    return 0;
-}
 int series_screen(DcHandle* h, int k0, int k1, double thr, long long rec_cap, const SeriesOut& o) {
     DcSeriesState* s = h->series;
-    DcPairState* p = s->phi;
+    DcPhi* p = &s->phi;
     const int rb = k1 - k0, T = s->T, ldt = s->ldt;
     DC_TRY(series_block(h, rb, rec_cap));
-    dc_pair_state_rinv(h, p);
+    dc_phi_rinv(h, p);
     launch_screen(h, screen_args(h, k0, k1, thr));
     SeriesListArgs la = list_args(h, k0, k1, thr, rec_cap);
     launch_stats(h, la);
@@ -401,12 +270,11 @@ int series_screen(DcHandle* h, int k0, int k1, double thr, long long rec_cap, co
     DC_HIP(hipMemcpyAsync(cviol.data(), s->c_viol, ldt * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     if (o.base) DC_HIP(hipMemcpyAsync(o.base, s->base, (size_t)T * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     DC_HIP(sync_copy(cmax.data(), s->c_max, ldt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    std::vector<long long> off(rb);
-    long long viol = 0, isl = 0;
-    for (int i = 0; i < rb; ++i) {
-        off[i] = viol; viol += nv[i];
+    std::vector<long long> off;
+    const long long viol = dc_prefix(nv, off);
+    long long isl = 0;
+    for (int i = 0; i < rb; ++i)
         if (s->h_bridge[k0 + i]) { if (o.islanding) o.islanding[isl] = p->h_cand[k0 + i] + 1; ++isl; }
-    }
     const long long nrec = std::min(viol, rec_cap);
     if (nrec) {
         DC_HIP(hipMemcpyAsync(s->r_off, off.data(), rb * sizeof(long long), hipMemcpyHostToDevice, h->stream));
@@ -419,52 +287,16 @@ int series_screen(DcHandle* h, int k0, int k1, double thr, long long rec_cap, co
     if (o.worst) for (int i = 0; i < rb; ++i) o.worst[k0 + i] = rmax[i];
     if (o.worst_profile) for (int t = 0; t < T; ++t) o.worst_profile[t] = std::max(o.worst_profile[t], cmax[t]);
     if (o.viol_profile) for (int t = 0; t < T; ++t) o.viol_profile[t] += cviol[t];
-    if (o.d_load) DC_TRY(series_dense(h, o.d_load, (const double*)s->b_load, rb));
-    if (o.d_branch) DC_TRY(series_dense(h, o.d_branch, (const int*)s->b_branch, rb));
-    if (o.d_count) DC_TRY(series_dense(h, o.d_count, (const int*)s->b_count, rb));
+    auto same = [](int, int, auto v) { return v; };
+    if (o.d_load) DC_TRY(dc_dense(h, o.d_load, (const double*)s->b_load, rb, ldt, T, same));
+    if (o.d_branch) DC_TRY(dc_dense(h, o.d_branch, (const int*)s->b_branch, rb, ldt, T, same));
+    if (o.d_count) DC_TRY(dc_dense(h, o.d_count, (const int*)s->b_count, rb, ldt, T, same));
     return 0;
 }
 
 }  // namespace
 
-void dc_series_free(DcHandle* h) { series_release(h); }
-size_t dc_series_flows_scratch(const DcHandle* h, int ldt) { return ((size_t)3 * h->n + 1) * std::min(ldt, DC_PAIR_LANES) * sizeof(double); }
-int dc_series_row_flows(DcHandle* h, const DcPairState* p, int T, const double* rhs, bool shift, double* F, int ldt, double* ms) {
-    return row_flows(h, p, T, rhs, shift, F, ldt, ms);
-}
-int dc_series_bridges(DcHandle* h, const DcPairState* p, std::vector<char>& bridge) { return bridges(h, p, bridge); }
-int dc_series_shed_table(const DcHandle* h, const DcPairState* p, int k0, int k1, int64_t* labels, int64_t* buses, int64_t* m, int64_t* side) {
-    int nb = 0;
-    if (!p->shed) return 0;
-    for (int k = k0; k < k1; ++k) {
-        if (p->h_side[k] == 0) continue;
-        const int br = p->h_cand[k];
-        if (labels) labels[nb] = br + 1;
-        if (buses) buses[nb] = p->h_hi[k] - p->h_lo[k] + 1;
-        if (m) m[nb] = (p->h_side[k] > 0 ? h->h_from[br] : h->h_to[br]) + 1;
-        if (side) side[nb] = p->h_side[k];
-        ++nb;
-    }
-    return nb;
-}
-int dc_series_shed_gather(DcHandle* h, const DcPairState* p, int k0, int k1, const double* F, int ldt, int T, double* out) {
-    std::vector<int> list;
-    if (p->shed)
-        for (int k = k0; k < k1; ++k) if (p->h_side[k] != 0) list.push_back(k);
-    const int nb = (int)list.size();
-    if (!nb) return 0;
-    int* d_list = nullptr; double* d_out = nullptr;
-    int rc = dev_alloc(h, &d_list, (size_t)nb, list.data());
-    if (!rc) rc = dev_alloc(h, &d_out, (size_t)nb * T, (const double*)nullptr, false);
-    if (!rc) {
-        hipLaunchKernelGGL(k_shed_gather, dim3((T + 255) / 256, std::min(nb, 4096)), dim3(256), 0, h->stream, F, p->cand_row, p->cand_isl, d_list, d_out, nb, ldt, T);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = sync_copy(out, d_out, (size_t)nb * T * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-        if (e != hipSuccess) { h->error = std::string("shed gather: ") + hipGetErrorString(e); rc = 2; }
-    }
-    dev_release(h, d_list); dev_release(h, d_out);
-    return rc;
-}
+void dc_series_free(DcHandle* h) { dc_state_release(h, h->series); }
 
 }  // namespace jg
 
@@ -482,7 +314,7 @@ int jg_dc_series_build(int64_t h, int64_t nk, const int64_t* candidates, int64_t
     if (nk < 1 || !candidates || !info || nm < 0 || (nm && !monitored)) return api_fail(1, "jg_dc_series_build: one or more candidates, and info, are needed");
     if (profiles < 1 || profiles > (1 << 24) || !rhs) return api_fail(1, "jg_dc_series_build: one or more profiles are needed");
     std::vector<int> cand, mon;
-    DC_RET(jg::dc_pair_lists(d, "jg_dc_series_build", nk, candidates, nm, monitored, cand, mon));
+    DC_RET(jg::dc_phi_lists(d, "jg_dc_series_build", nk, candidates, nm, monitored, cand, mon));
     DC_RET(jg::series_build(d, cand, mon, (int)profiles, rhs, budget_bytes, info));
     return 0;
 }
@@ -493,7 +325,7 @@ int jg_dc_series_screen(int64_t h, int64_t k0, int64_t k1, double threshold, int
     DC_ENTER(h);
     if (!d->series) return api_fail(4, "jg_dc_series_screen: jg_dc_series_build first");
     if (!d->b_rating) return api_fail(1, "jg_dc_series_screen: jg_dc_set_rating first (the loadings are |from| / rating)");
-    if (k0 < 0 || k1 <= k0 || k1 > d->series->phi->nk) return api_fail(1, "jg_dc_series_screen: rows [k0, k1) out of range");
+    if (k0 < 0 || k1 <= k0 || k1 > d->series->phi.nk) return api_fail(1, "jg_dc_series_screen: rows [k0, k1) out of range");
     if (!(threshold >= 0.0) || capacity < 0 || (capacity && !records) || !totals) return api_fail(1, "jg_dc_series_screen: bad argument");
     jg::SeriesOut o{records, islanding, totals, worst, worst_profile, violating_profile, base, dense_load, dense_branch, dense_count};
     DC_RET(jg::series_screen(d, (int)k0, (int)k1, threshold, capacity, o));
@@ -502,40 +334,31 @@ int jg_dc_series_screen(int64_t h, int64_t k0, int64_t k1, double threshold, int
 
 int jg_dc_series_time_kernel(int64_t h, int kernel, int64_t k0, int64_t k1, int reps, double* ms) {
     DC_ENTER(h);
-    if (!d->series) return api_fail(4, "jg_dc_series_time_kernel: jg_dc_series_build first");
-    if (!ms || reps < 1 || kernel < 0 || kernel > 1 || k0 < 0 || k1 <= k0 || k1 > d->series->phi->nk) return api_fail(1, "jg_dc_series_time_kernel: bad argument");
-    if (k1 - k0 > d->series->blk_rows) return api_fail(4, "jg_dc_series_time_kernel: jg_dc_series_screen with a block of at least these rows first");
-    const jg::SeriesScreenArgs sa = jg::screen_args(d, (int)k0, (int)k1, 1.0);
-    const jg::SeriesListArgs la = jg::list_args(d, (int)k0, (int)k1, 1.0, 0);
-    DC_RET(jg::time_events(d->stream, reps, ms, d->error, [&]() -> int {
-        if (kernel == 0) jg::launch_screen(d, sa);
-        else jg::launch_stats(d, la);
-        return 0;
-    }));
-    return 0;
+    jg::DcSeriesState* s = d->series;
+    return jg::dc_phi_time_kernel(d, "series", s ? &s->phi : nullptr, s ? s->blk_rows : 0, kernel, k0, k1, reps, ms,
+                                  [&] {
+        return [d, sa = jg::screen_args(d, (int)k0, (int)k1, 1.0), la = jg::list_args(d, (int)k0, (int)k1, 1.0, 0)](int which) {
+            if (which == 0) jg::launch_screen(d, sa);
+            else jg::launch_stats(d, la);
+        };
+    });
 }
 
 int jg_dc_series_set_island_mode(int64_t h, int mode) {
     DC_ENTER(h);
-    if (mode != 0 && mode != 1) return api_fail(1, "jg_dc_series_set_island_mode: mode is 0 (a bridge candidate is skipped: status 3) or 1 (screened on the slack's island)");
-    if (mode == 1 && !d->nbr) return api_fail(1, "jg_dc_series_set_island_mode: jg_dc_set_branches first");
-    d->series_shed = mode;
-    return 0;
+    return jg::dc_phi_set_island_mode(d, "series", mode, d->series_shed);
 }
 
 int jg_dc_series_get_shed_table(int64_t h, int64_t k0, int64_t k1, int64_t* count, int64_t* labels, int64_t* buses, int64_t* m, int64_t* side) {
     DC_ENTER(h);
-    if (!d->series) return api_fail(4, "jg_dc_series_get_shed_table: jg_dc_series_build first");
-    if (!count || k0 < 0 || k1 < k0 || k1 > d->series->phi->nk) return api_fail(1, "jg_dc_series_get_shed_table: bad argument");
-    *count = jg::dc_series_shed_table(d, d->series->phi, (int)k0, (int)k1, labels, buses, m, side);
-    return 0;
+    return jg::dc_phi_get_shed_table(d, "series", d->series ? &d->series->phi : nullptr, k0, k1, count, labels, buses, m, side);
 }
 
 int jg_dc_series_get_shed(int64_t h, int64_t k0, int64_t k1, double* flow) {
     DC_ENTER(h);
     if (!d->series) return api_fail(4, "jg_dc_series_get_shed: jg_dc_series_build first");
-    if (!flow || k0 < 0 || k1 < k0 || k1 > d->series->phi->nk) return api_fail(1, "jg_dc_series_get_shed: bad argument");
-    DC_RET(jg::dc_series_shed_gather(d, d->series->phi, (int)k0, (int)k1, d->series->F0, d->series->ldt, d->series->T, flow));
+    if (!flow || k0 < 0 || k1 < k0 || k1 > d->series->phi.nk) return api_fail(1, "jg_dc_series_get_shed: bad argument");
+    DC_RET(jg::dc_phi_shed_gather(d, &d->series->phi, (int)k0, (int)k1, d->series->F0, d->series->ldt, d->series->T, flow));
     return 0;
 }
 

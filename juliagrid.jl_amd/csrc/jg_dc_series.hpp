@@ -1,10 +1,10 @@
 // jg_dc_series.hpp -- the DC N-1 screen over a SERIES of injection profiles, on the ONE factor of a DcHandle (jg_dc.hpp) and the outage sensitivities
-// the N-2 build keeps (jg_dc_pair.hpp).
+// the builds of the screens keep (a DcPhi, jg_dc_phi.hpp).
 //
 // Reference counterpart: the user loop
 //     for t in profiles:   updateBus!(...; active) / updateGenerator!(...; active)
 //       for k in branches: updateBranch!(...; label = k, status = 0); solve!; power!; updateBranch!(...; status = 1)
-// With Phi[m,k] = y_m a_m' B^-1 a_k (jg_dc_pair.hpp) and the base flows of profile t, F0[m,t] = y_m (a_m' theta_t - shiftAngle_m), theta_t = B^-1 rhs_t:
+// With Phi[m,k] = y_m a_m' B^-1 a_k (jg_dc_pair.hpp has the algebra) and the base flows of profile t, F0[m,t] = y_m (a_m' theta_t - shiftAngle_m), theta_t = B^-1 rhs_t:
 //     d_k      = 1 - Phi[k,k]                   |d_k| < DC_SINGULAR: k is a bridge (status 3 in every profile, the loading is NaN)
 //     c_kt     = F0[k,t] / d_k
 //     f_m(k,t) = F0[m,t] + Phi[m,k] c_kt        (m != k),   f_k(k,t) = 0
@@ -18,15 +18,14 @@
 // k is the only branch between S and M, so a row other than k left exactly when lo_k <= preorder[from_l] <= hi_k.  A non-bridge with |d_k| < DC_SINGULAR
 // keeps status 3 and NaN.
 //
-// What is kept: Phi [rows][ldk] exactly as the pair build makes it (a DcPairState of the series' own: the pair screen's h->pair is not touched), and
+// What is kept: Phi [rows][ldk] as dc_phi_build makes it (a DcPhi of the series' own: the pair screen's h->pair is not touched), and
 // F0 [rows][ldt] doubles on the same rows, ldt = profiles rounded up to 64, 0 behind the last profile.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <cstdint>
 #include <vector>
 
-#include "jg_dc_pair.hpp"
+#include "jg_dc_phi.hpp"
 
 namespace jg {
 
@@ -37,7 +36,7 @@ constexpr int DC_SERIES_TILE = JG_DC_SERIES_TILE;   // candidates k a wave of k_
 static_assert(DC_SERIES_TILE == 4 || DC_SERIES_TILE == 8, "a tile of k is one or two 32-byte scalar loads of a row of Phi");
 
 struct DcSeriesState {
-    DcPairState* phi = nullptr;              // Phi and the row / candidate tables of the shared build
+    DcPhi phi;                               // Phi and the row / candidate tables of the shared build
     int T = 0, ldt = 0;                      // profiles, rounded up to 64
     double* F0 = nullptr;                    // [rows][ldt]
     std::vector<char> h_bridge;              // [nk] 1: |1 - Phi[k,k]| < DC_SINGULAR
@@ -49,23 +48,9 @@ struct DcSeriesState {
     double* base = nullptr;                  // [ldt][3] the profiles' base case: worst loading, its branch, the count
     double* rec = nullptr; long long rec_cap = 0;       // [rec_cap][5]
     double build_ms[3] = {0, 0, 0};          // F0 of the last build: total, sweep pairs, F0 kernel (HIP events)
+    DcMem mem;                               // the device memory of the fields above (not the DcPhi's): what release frees
 };
 
 void dc_series_free(DcHandle* h);            // releases what the series screen holds (jg_dc_destroy, jg_dc_series_release)
-
-// The lane-batch loop of the build is shared with the transfer screen (jg_dc_transfer.hpp):
-//   dc_series_row_flows     F [rows of p][ldt] from `T` right-hand sides rhs [T][n] (the slack's entry is taken as 0): uploads DC_PAIR_LANES of them at a
-//                           time, runs the sweep pair and turns the angles into row flows y_m (a_m' theta - shiftAngle_m); shift false: y_m a_m' theta,
-//                           the sensitivity of the flow to the right-hand side.  Scratch of its own (dc_series_flows_scratch bytes), released on return;
-//                           ms [2] gets the milliseconds of the sweep pairs and of the flow kernel added (HIP events).  Not 0: the text is in h->error
-//   dc_series_bridges       bridge [nk] 1: |1 - Phi[k,k]| < DC_SINGULAR
-//   dc_series_shed_table    the bridge candidates (shed mode) among the positions [k0, k1): their number, and per bridge the label, the buses that leave,
-//                           m (1-based) and the side; null outputs are skipped
-//   dc_series_shed_gather   out [bridges in [k0, k1)][T] on the host = s_k F[row of k][t], from the device (k_shed_gather: one thread per value)
-size_t dc_series_flows_scratch(const DcHandle* h, int ldt);
-int dc_series_shed_table(const DcHandle* h, const DcPairState* p, int k0, int k1, int64_t* labels, int64_t* buses, int64_t* m, int64_t* side);
-int dc_series_shed_gather(DcHandle* h, const DcPairState* p, int k0, int k1, const double* F, int ldt, int T, double* out);
-int dc_series_row_flows(DcHandle* h, const DcPairState* p, int T, const double* rhs, bool shift, double* F, int ldt, double* ms);
-int dc_series_bridges(DcHandle* h, const DcPairState* p, std::vector<char>& bridge);
 
 }  // namespace jg

@@ -1,7 +1,8 @@
 // jg_dc_sweep.hpp -- internal: the scalar factorisation of ONE matrix on a static pivot order and the level-scheduled sweeps on that shared factor,
 // lanes = scenarios / realisations.  The kernels and their launchers are compiled once, in jg_dc_sweep.hip; this header declares the factor they work on
 // (DcFactor), what a handle allocates through (DcDevice) and the argument blocks and constants the includers' own kernels share.  Used by jg_dc.hip (the
-// DC nodal matrix), jg_dcse.hip (the gain matrix of DC state estimation), jg_dc_pair.hip, jg_dc_series.hip and jg_dc_transfer.hip (sweeps on the DC handle's factor).
+// DC nodal matrix), jg_dcse.hip (the gain matrix of DC state estimation) and jg_dc_phi.hip (the sweeps of the pair, series and transfer screens' builds on the DC
+// handle's factor; the screens' own kernels in jg_dc_pair.hip, jg_dc_series.hip and jg_dc_transfer.hip share the typedefs and constants).
 //
 // What runs: the elimination order, fill pattern, update terms and dependency levels come from jg_symbolic (no top tasks); the factorisation is a launch
 // per dependency level with a thread per entry; the sweeps give a wavefront one row x 64 lanes, read the premultiplied factor values and the column

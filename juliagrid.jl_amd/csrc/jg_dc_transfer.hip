@@ -1,9 +1,9 @@
 // jg_dc_transfer.hip -- the DC transfer-capability screen over transfers x N-1 outages (jg_dc_transfer.hpp has the algebra and the reference loop it
 // stands for).
 //
-// Build: Phi by the build the pair screen shares (jg_dc_pair.hip), into a state of the screen's own; then the sweep pair of jg_dc_sweep.hip over the
-// directions, DC_PAIR_LANES at a time, through the lane-batch loop the series build shares (dc_series_row_flows, without the shift angle); the base flows
-// are the pair state's, or one more such batch of one lane for a base profile.  Screen of a row block [k0, k1): k_transfer_screen walks the rows once (lanes
+// Build: Phi by the build the three screens share (dc_phi_build, jg_dc_phi.hip), into a state of the screen's own; then G, the row flows of the
+// directions without the shift angle (dc_phi_row_flows: the sweep pair of jg_dc_sweep.hip, DC_PAIR_LANES directions at a time); the base flows
+// are the build's own, or one more such batch of one lane for a base profile.  Screen of a row block [k0, k1): k_transfer_screen walks the rows once (lanes
 // = 64 consecutive candidates k of a chunk, a wave keeps DC_TRANSFER_TILE transfers in registers, the waves of a workgroup share the chunk so its Phi rows
 // meet in the vector L1; 1 / rating_m, F0[m], the row's candidate position and G[m, t..t+3] through scalar loads, Phi[m, k..k+63] one coalesced vector load
 // reused for every transfer of the tile; nothing is written per m).  The summaries come out of the block's dense result without atomics: per candidate and
@@ -14,15 +14,10 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
-#include <cstdio>
-#include <cstring>
 #include <limits>
 #include <type_traits>
 
 #include "../../include/jgrid.h"
-#include "jg_dc.hpp"
-#include "jg_dc_abi.hpp"
-#include "jg_dc_series.hpp"
 
 namespace jg {
 
@@ -204,22 +199,10 @@ __global__ void k_transfer_pick(const double* F, double* f0, int rows, int ld) {
     if (r < rows) f0[r] = F[(size_t)r * ld];
 }
 
-void transfer_release(DcHandle* h) {
-    DcTransferState* s = h->transfer;
-    if (!s) return;
-    hipStreamSynchronize(h->stream);
-    dc_pair_state_free(h, s->phi);
-    dev_release(h, s->G); dev_release(h, s->f0); dev_release(h, s->b_tc); dev_release(h, s->b_row);
-    dev_release(h, s->r_rec); dev_release(h, s->r_min); dev_release(h, s->r_off); dev_release(h, s->c_min); dev_release(h, s->c_at); dev_release(h, s->c_row);
-    dev_release(h, s->amount); dev_release(h, s->base); dev_release(h, s->rec);
-    delete s;
-    h->transfer = nullptr;
-}
-
 // dirs [T][n]: net injection per unit of transfer; base_rhs [n] nullable: the right-hand side of a base profile as jg_dc_set_rhs takes it
 int transfer_build(DcHandle* h, const std::vector<int>& cand, const std::vector<int>& mon, int T, const double* dirs, const double* base_rhs, int64_t budget,
                    double* info) {
-    transfer_release(h);
+    dc_state_release(h, h->transfer);
     const bool shed = h->transfer_shed == 1;
     h->transfer_shed = 0;
     const int ldt = (T + 63) / 64 * 64;
@@ -232,39 +215,38 @@ int transfer_build(DcHandle* h, const std::vector<int>& cand, const std::vector<
     }
     const int nr = (int)label.size();
     const size_t g_bytes = (size_t)nr * ldt * sizeof(double);
-    const size_t scratch = dc_series_flows_scratch(h, ldt) + (base_rhs ? (size_t)nr * 64 * sizeof(double) : 0);
+    const size_t scratch = dc_phi_flows_scratch(h, ldt) + (base_rhs ? (size_t)nr * 64 * sizeof(double) : 0);
     for (int j = 8; j < 12; ++j) info[j] = 0.0;
     info[8] = (double)g_bytes;
-    DcTransferState* s = new DcTransferState();
-    h->transfer = s;
+    DcTransferState* s = h->transfer = new DcTransferState();
     s->T = T; s->ldt = ldt; s->h_row_label = label;
-    const std::string extra = "; G needs " + dc_pair_bytes_text(g_bytes) + " (" + std::to_string(nr) + " rows x " + std::to_string(ldt) + " transfers x 8) and " +
-                              dc_pair_bytes_text(scratch) + " of scratch";
-    int rc = dc_pair_state_build(h, s->phi, "jg_dc_transfer_build", cand, mon, budget, g_bytes + scratch, extra, info, shed);
-    if (rc) { const std::string msg = h->error; transfer_release(h); h->error = msg; return rc; }
-    DcPairState* p = s->phi;
+    const std::string extra = "; G needs " + dc_bytes_text(g_bytes) + " (" + std::to_string(nr) + " rows x " + std::to_string(ldt) + " transfers x 8) and " +
+                              dc_bytes_text(scratch) + " of scratch";
+    DcPhi* p = &s->phi;
+    int rc = 0;
     auto step = [&](int r) { if (r && !rc) rc = r; return rc == 0; };
     auto hip = [&](hipError_t e, const char* what) { if (e != hipSuccess && !rc) { rc = 2; h->error = std::string(what) + ": " + hipGetErrorString(e); } return rc == 0; };
     double ms[2] = {0.0, 0.0};
-    if (step(dev_alloc(h, &s->G, (size_t)nr * ldt, (const double*)nullptr, true)) && step(dev_alloc(h, &s->f0, (size_t)nr, (const double*)nullptr, true)) &&
-        step(dev_alloc(h, &s->c_min, (size_t)ldt, (const double*)nullptr, true)) && step(dev_alloc(h, &s->c_at, (size_t)ldt, (const int*)nullptr, true)) &&
-        step(dev_alloc(h, &s->c_row, (size_t)ldt, (const int*)nullptr, true)) && step(dev_alloc(h, &s->amount, (size_t)ldt, (const double*)nullptr, true)) &&
-        step(dev_alloc(h, &s->base, (size_t)ldt * 3, (const double*)nullptr, true))) {
+    if (step(dc_phi_build(h, p, "jg_dc_transfer_build", cand, mon, budget, g_bytes + scratch, extra, info, shed)) &&
+        step(dev_alloc(h, s->mem, &s->G, (size_t)nr * ldt, (const double*)nullptr, true)) && step(dev_alloc(h, s->mem, &s->f0, (size_t)nr, (const double*)nullptr, true)) &&
+        step(dev_alloc(h, s->mem, &s->c_min, (size_t)ldt, (const double*)nullptr, true)) && step(dev_alloc(h, s->mem, &s->c_at, (size_t)ldt, (const int*)nullptr, true)) &&
+        step(dev_alloc(h, s->mem, &s->c_row, (size_t)ldt, (const int*)nullptr, true)) && step(dev_alloc(h, s->mem, &s->amount, (size_t)ldt, (const double*)nullptr, true)) &&
+        step(dev_alloc(h, s->mem, &s->base, (size_t)ldt * 3, (const double*)nullptr, true))) {
         if (base_rhs) {
             double* Fb = nullptr;                                // [nr][64]: one lane batch of one lane
             double unused[2] = {0.0, 0.0};
-            if (step(dev_alloc(h, &Fb, (size_t)nr * 64, (const double*)nullptr, true)) && step(dc_series_row_flows(h, p, 1, base_rhs, true, Fb, 64, unused))) {
+            if (step(dev_alloc(h, s->mem, &Fb, (size_t)nr * 64, (const double*)nullptr, true)) && step(dc_phi_row_flows(h, p, 1, base_rhs, true, Fb, 64, unused))) {
                 hipLaunchKernelGGL(k_transfer_pick, dim3((nr + 255) / 256), dim3(256), 0, h->stream, Fb, s->f0, nr, 64);
                 hip(hipGetLastError(), "launch") && hip(hipStreamSynchronize(h->stream), "hipStreamSynchronize");
             }
-            dev_release(h, Fb);
+            dev_release(h, s->mem, Fb);
         } else {
             hip(sync_copy(s->f0, p->row_f0, (size_t)nr * sizeof(double), hipMemcpyDeviceToDevice, h->stream), "copy of the base flows");
         }
-        if (!rc) step(dc_series_row_flows(h, p, T, dirs, false, s->G, ldt, ms));
-        if (!rc) step(dc_series_bridges(h, p, s->h_bridge));
+        if (!rc) step(dc_phi_row_flows(h, p, T, dirs, false, s->G, ldt, ms));
+        if (!rc) step(dc_phi_bridges(h, p, s->h_bridge));
     }
-    if (rc) { const std::string msg = h->error; transfer_release(h); h->error = msg; return rc; }
+    if (rc) return dc_build_failed(h, h->transfer, rc);
     s->build_ms[0] = ms[0] + ms[1]; s->build_ms[1] = ms[0]; s->build_ms[2] = ms[1];
     info[9] = s->build_ms[0]; info[10] = ms[0]; info[11] = ms[1];
     return 0;
@@ -274,30 +256,16 @@ int transfer_build(DcHandle* h, const std::vector<int>& cand, const std::vector<
 int transfer_block(DcHandle* h, int rb, long long rec_cap) {
     DcTransferState* s = h->transfer;
     if (rb > s->blk_rows) {
-        const size_t cells = (size_t)rb * s->ldt, need = cells * 12;
-        dev_release(h, s->b_tc); dev_release(h, s->b_row); dev_release(h, s->r_rec); dev_release(h, s->r_min); dev_release(h, s->r_off);
-        s->blk_rows = 0;
-        size_t free_b = 0, total_b = 0;
-        DC_HIP(hipMemGetInfo(&free_b, &total_b));
-        if (need > free_b) {
-            h->error = "jg_dc_transfer_screen: a block of " + std::to_string(rb) + " rows needs " + dc_pair_bytes_text(need) + ", " + dc_pair_bytes_text(free_b) +
-                       " are free: screen fewer rows per call";
-            return 5;
-        }
-        DC_TRY(dev_alloc(h, &s->b_tc, cells, (const double*)nullptr, true));
-        DC_TRY(dev_alloc(h, &s->b_row, cells, (const int*)nullptr, true));
-        DC_TRY(dev_alloc(h, &s->r_rec, (size_t)rb, (const int*)nullptr, true));
-        DC_TRY(dev_alloc(h, &s->r_min, (size_t)rb, (const double*)nullptr, true));
-        DC_TRY(dev_alloc(h, &s->r_off, (size_t)rb, (const long long*)nullptr, true));
-        s->blk_rows = rb;
+        const size_t cells = (size_t)rb * s->ldt, r = (size_t)rb;
+        DC_TRY(dc_block_grow(h, s->mem, "jg_dc_transfer_screen", rb, s->blk_rows, cells * 12, dc_blk(s->b_tc, cells), dc_blk(s->b_row, cells), dc_blk(s->r_rec, r),
+                             dc_blk(s->r_min, r), dc_blk(s->r_off, r)));
     }
-    if (rec_cap > s->rec_cap) { dev_release(h, s->rec); s->rec_cap = 0; DC_TRY(dev_alloc(h, &s->rec, (size_t)rec_cap * 5, (const double*)nullptr, true)); s->rec_cap = rec_cap; }
-    return 0;
+    return dc_list_grow(h, s->mem, s->rec, s->rec_cap, rec_cap, 5);
 }
 
 TransferScreenArgs screen_args(DcHandle* h, int k0, int k1, double cutoff) {
     DcTransferState* s = h->transfer;
-    DcPairState* p = s->phi;
+    const DcPhi* p = &s->phi;
     TransferScreenArgs a{};
     a.Phi = p->Phi; a.G = s->G; a.f0 = s->f0; a.rinv = p->row_rinv; a.pos = p->row_pos; a.crow = p->cand_row; a.cdiag = p->cand_diag;
     a.tc = s->b_tc; a.row = s->b_row;
@@ -313,7 +281,7 @@ void launch_screen(DcHandle* h, const TransferScreenArgs& a) {
 }
 TransferListArgs list_args(DcHandle* h, int k0, int k1, long long rec_cap) {
     DcTransferState* s = h->transfer;
-    DcPairState* p = s->phi;
+    const DcPhi* p = &s->phi;
     TransferListArgs a{};
     a.tc = s->b_tc; a.row = s->b_row; a.amount = s->amount; a.clabel = p->cand_label; a.rbranch = p->row_branch;
     a.Phi = p->Phi; a.G = s->G; a.crow = p->cand_row; a.cdiag = p->cand_diag; a.cisl = p->shed ? p->cand_isl : nullptr;
@@ -334,7 +302,7 @@ struct TransferOut {
 };
 int transfer_screen(DcHandle* h, int k0, int k1, double cutoff, long long rec_cap, const TransferOut& o) {
     DcTransferState* s = h->transfer;
-    DcPairState* p = s->phi;
+    DcPhi* p = &s->phi;
     const int rb = k1 - k0, T = s->T, ldt = s->ldt;
     const double inf = std::numeric_limits<double>::infinity();
     DC_TRY(transfer_block(h, rb, rec_cap));
@@ -343,7 +311,7 @@ int transfer_screen(DcHandle* h, int k0, int k1, double cutoff, long long rec_ca
         if (o.amount) std::copy(o.amount, o.amount + T, am.begin());
         DC_HIP(sync_copy(s->amount, am.data(), (size_t)ldt * sizeof(double), hipMemcpyHostToDevice, h->stream));
     }
-    dc_pair_state_rinv(h, p);
+    dc_phi_rinv(h, p);
     launch_screen(h, screen_args(h, k0, k1, cutoff));
     TransferListArgs la = list_args(h, k0, k1, rec_cap);
     launch_stats(h, la);
@@ -357,12 +325,11 @@ int transfer_screen(DcHandle* h, int k0, int k1, double cutoff, long long rec_ca
     DC_HIP(hipMemcpyAsync(crow.data(), s->c_row, ldt * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     if (o.base) DC_HIP(hipMemcpyAsync(base.data(), s->base, (size_t)T * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     DC_HIP(sync_copy(cmin.data(), s->c_min, ldt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    std::vector<long long> off(rb);
-    long long below = 0, isl = 0;
-    for (int i = 0; i < rb; ++i) {
-        off[i] = below; below += nv[i];
+    std::vector<long long> off;
+    const long long below = dc_prefix(nv, off);
+    long long isl = 0;
+    for (int i = 0; i < rb; ++i)
         if (s->h_bridge[k0 + i]) { if (o.islanding) o.islanding[isl] = p->h_cand[k0 + i] + 1; ++isl; }
-    }
     const long long nrec = std::min(below, rec_cap);
     if (nrec) {
         DC_HIP(hipMemcpyAsync(s->r_off, off.data(), rb * sizeof(long long), hipMemcpyHostToDevice, h->stream));
@@ -383,23 +350,14 @@ int transfer_screen(DcHandle* h, int k0, int k1, double cutoff, long long rec_ca
             const int r = (int)base[(size_t)t * 3 + 1];
             o.base[(size_t)t * 3] = base[(size_t)t * 3]; o.base[(size_t)t * 3 + 1] = r < 0 ? 0.0 : (double)s->h_row_label[r]; o.base[(size_t)t * 3 + 2] = base[(size_t)t * 3 + 2];
         }
-    if (o.d_tc) {
-        std::vector<double> v((size_t)rb * ldt);
-        DC_HIP(sync_copy(v.data(), s->b_tc, v.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        for (int i = 0; i < rb; ++i) std::copy(v.begin() + (size_t)i * ldt, v.begin() + (size_t)i * ldt + T, o.d_tc + (size_t)i * T);
-    }
-    if (o.d_branch) {
-        std::vector<int> v((size_t)rb * ldt);
-        DC_HIP(sync_copy(v.data(), s->b_row, v.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        for (int i = 0; i < rb; ++i)
-            for (int t = 0; t < T; ++t) { const int r = v[(size_t)i * ldt + t]; o.d_branch[(size_t)i * T + t] = r < 0 ? 0 : s->h_row_label[r]; }
-    }
+    if (o.d_tc) DC_TRY(dc_dense(h, o.d_tc, (const double*)s->b_tc, rb, ldt, T, [](int, int, double v) { return v; }));
+    if (o.d_branch) DC_TRY(dc_dense(h, o.d_branch, (const int*)s->b_row, rb, ldt, T, [s](int, int, int r) { return r < 0 ? 0 : s->h_row_label[r]; }));    // a row's label
     return 0;
 }
 
 }  // namespace
 
-void dc_transfer_free(DcHandle* h) { transfer_release(h); }
+void dc_transfer_free(DcHandle* h) { dc_state_release(h, h->transfer); }
 
 }  // namespace jg
 
@@ -417,7 +375,7 @@ int jg_dc_transfer_build(int64_t h, int64_t nk, const int64_t* candidates, int64
     if (nk < 1 || !candidates || !info || nm < 0 || (nm && !monitored)) return api_fail(1, "jg_dc_transfer_build: one or more candidates, and info, are needed");
     if (transfers < 1 || transfers > (1 << 24) || !directions) return api_fail(1, "jg_dc_transfer_build: one or more transfer directions are needed");
     std::vector<int> cand, mon;
-    DC_RET(jg::dc_pair_lists(d, "jg_dc_transfer_build", nk, candidates, nm, monitored, cand, mon));
+    DC_RET(jg::dc_phi_lists(d, "jg_dc_transfer_build", nk, candidates, nm, monitored, cand, mon));
     DC_RET(jg::transfer_build(d, cand, mon, (int)transfers, directions, base_rhs, budget_bytes, info));
     return 0;
 }
@@ -428,7 +386,7 @@ int jg_dc_transfer_screen(int64_t h, int64_t k0, int64_t k1, double cutoff, cons
     DC_ENTER(h);
     if (!d->transfer) return api_fail(4, "jg_dc_transfer_screen: jg_dc_transfer_build first");
     if (!d->b_rating) return api_fail(1, "jg_dc_transfer_screen: jg_dc_set_rating first (a branch limits at |from| = rating)");
-    if (k0 < 0 || k1 <= k0 || k1 > d->transfer->phi->nk) return api_fail(1, "jg_dc_transfer_screen: rows [k0, k1) out of range");
+    if (k0 < 0 || k1 <= k0 || k1 > d->transfer->phi.nk) return api_fail(1, "jg_dc_transfer_screen: rows [k0, k1) out of range");
     if (!(cutoff > 0.0) || capacity < 0 || (capacity && !records) || !totals) return api_fail(1, "jg_dc_transfer_screen: bad argument");
     if ((capability || limiting_outage || limiting_branch) && !(capability && limiting_outage && limiting_branch))
         return api_fail(1, "jg_dc_transfer_screen: capability, limiting_outage and limiting_branch go together");
@@ -439,42 +397,33 @@ int jg_dc_transfer_screen(int64_t h, int64_t k0, int64_t k1, double cutoff, cons
 
 int jg_dc_transfer_time_kernel(int64_t h, int kernel, int64_t k0, int64_t k1, int reps, double* ms) {
     DC_ENTER(h);
-    if (!d->transfer) return api_fail(4, "jg_dc_transfer_time_kernel: jg_dc_transfer_build first");
-    if (!ms || reps < 1 || kernel < 0 || kernel > 1 || k0 < 0 || k1 <= k0 || k1 > d->transfer->phi->nk) return api_fail(1, "jg_dc_transfer_time_kernel: bad argument");
-    if (k1 - k0 > d->transfer->blk_rows) return api_fail(4, "jg_dc_transfer_time_kernel: jg_dc_transfer_screen with a block of at least these rows first");
-    const jg::TransferScreenArgs sa = jg::screen_args(d, (int)k0, (int)k1, 1e-6);
-    const jg::TransferListArgs la = jg::list_args(d, (int)k0, (int)k1, 0);
-    DC_RET(jg::time_events(d->stream, reps, ms, d->error, [&]() -> int {
-        if (kernel == 0) jg::launch_screen(d, sa);
-        else jg::launch_stats(d, la);
-        return 0;
-    }));
-    return 0;
+    jg::DcTransferState* s = d->transfer;
+    return jg::dc_phi_time_kernel(d, "transfer", s ? &s->phi : nullptr, s ? s->blk_rows : 0, kernel, k0, k1, reps, ms,
+                                  [&] {
+        return [d, sa = jg::screen_args(d, (int)k0, (int)k1, 1e-6), la = jg::list_args(d, (int)k0, (int)k1, 0)](int which) {
+            if (which == 0) jg::launch_screen(d, sa);
+            else jg::launch_stats(d, la);
+        };
+    });
 }
 
 int jg_dc_transfer_set_island_mode(int64_t h, int mode) {
     DC_ENTER(h);
-    if (mode != 0 && mode != 1) return api_fail(1, "jg_dc_transfer_set_island_mode: mode is 0 (a bridge candidate is skipped: status 3) or 1 (screened on the slack's island)");
-    if (mode == 1 && !d->nbr) return api_fail(1, "jg_dc_transfer_set_island_mode: jg_dc_set_branches first");
-    d->transfer_shed = mode;
-    return 0;
+    return jg::dc_phi_set_island_mode(d, "transfer", mode, d->transfer_shed);
 }
 
 int jg_dc_transfer_get_shed_table(int64_t h, int64_t k0, int64_t k1, int64_t* count, int64_t* labels, int64_t* buses, int64_t* m, int64_t* side) {
     DC_ENTER(h);
-    if (!d->transfer) return api_fail(4, "jg_dc_transfer_get_shed_table: jg_dc_transfer_build first");
-    if (!count || k0 < 0 || k1 < k0 || k1 > d->transfer->phi->nk) return api_fail(1, "jg_dc_transfer_get_shed_table: bad argument");
-    *count = jg::dc_series_shed_table(d, d->transfer->phi, (int)k0, (int)k1, labels, buses, m, side);
-    return 0;
+    return jg::dc_phi_get_shed_table(d, "transfer", d->transfer ? &d->transfer->phi : nullptr, k0, k1, count, labels, buses, m, side);
 }
 
 int jg_dc_transfer_get_shed(int64_t h, int64_t k0, int64_t k1, double* flow, double* transfer) {
     DC_ENTER(h);
     jg::DcTransferState* s = d->transfer;
     if (!s) return api_fail(4, "jg_dc_transfer_get_shed: jg_dc_transfer_build first");
-    if (!flow || !transfer || k0 < 0 || k1 < k0 || k1 > s->phi->nk) return api_fail(1, "jg_dc_transfer_get_shed: bad argument");
-    DC_RET(jg::dc_series_shed_gather(d, s->phi, (int)k0, (int)k1, s->f0, 1, 1, flow));
-    DC_RET(jg::dc_series_shed_gather(d, s->phi, (int)k0, (int)k1, s->G, s->ldt, s->T, transfer));
+    if (!flow || !transfer || k0 < 0 || k1 < k0 || k1 > s->phi.nk) return api_fail(1, "jg_dc_transfer_get_shed: bad argument");
+    DC_RET(jg::dc_phi_shed_gather(d, &s->phi, (int)k0, (int)k1, s->f0, 1, 1, flow));
+    DC_RET(jg::dc_phi_shed_gather(d, &s->phi, (int)k0, (int)k1, s->G, s->ldt, s->T, transfer));
     return 0;
 }
 

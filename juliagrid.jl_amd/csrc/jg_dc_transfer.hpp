@@ -1,5 +1,5 @@
 // jg_dc_transfer.hpp -- the DC transfer-capability screen over transfers x N-1 outages, on the ONE factor of a DcHandle (jg_dc.hpp) and the outage
-// sensitivities the N-2 build keeps (jg_dc_pair.hpp).
+// sensitivities the builds of the screens keep (a DcPhi, jg_dc_phi.hpp).
 //
 // Reference counterpart: the user loop
 //     repeat: updateBus!(...; active) / updateGenerator!(...; active) along a direction
@@ -7,7 +7,7 @@
 //     until a monitored branch reaches its rating
 // Base operating point: the handle's right-hand side (jg_dc_set_rhs), or a base profile given at build time.  Transfer t is a direction d_t [buses] of net
 // active injection per unit of transfer, as setInjection_ means it: the injection is P0 + lambda d_t.  A direction need not sum to zero: the slack takes
-// the rest, as the reference's solve! would have it.  With Phi[m,k] = y_m a_m' B^-1 a_k (jg_dc_pair.hpp) and the base flows F0[m]:
+// the rest, as the reference's solve! would have it.  With Phi[m,k] = y_m a_m' B^-1 a_k (jg_dc_pair.hpp has the algebra) and the base flows F0[m]:
 //     G[m,t]    = y_m a_m' B^-1 d_t                  flow sensitivity of row m to transfer t: NO shift angle, NO shunt / shiftPower term, slack entry 0
 //     d_k       = 1 - Phi[k,k]                       |d_k| < DC_SINGULAR: k is a bridge (status 3, NaN for all its transfers, never in a minimum or a record)
 //     f_m(k)    = F0[m] + Phi[m,k] F0[k] / d_k       post-outage flow at zero transfer (m != k)
@@ -22,21 +22,21 @@
 // The kernel works in loading space: with rinv = 1 / r_m, limit_m = (1 - copysign(f rinv, g)) / (|g| rinv) = num / den with den > 0, the running minimum
 // is a (num, den, row) triple compared by cross-multiplication, and the one division of a case comes after the last row.  (1, 0) is +inf.
 //
-// What is kept: Phi [rows][ldk] exactly as the pair build makes it (a DcPairState of the screen's own: h->pair and h->series are not touched), the base
+// What is kept: Phi [rows][ldk] as dc_phi_build makes it (a DcPhi of the screen's own: h->pair and h->series are not touched), the base
 // flows f0 [rows], and G [rows][ldt] doubles on the same rows, ldt = transfers rounded up to 64, 0 behind the last transfer.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <vector>
 
-#include "jg_dc_pair.hpp"
+#include "jg_dc_phi.hpp"
 
 namespace jg {
 
 constexpr int DC_TRANSFER_TILE = 4;          // transfers t a wave of k_transfer_screen keeps in registers: G[m, t..t+3] is one 32-byte scalar load
 
 struct DcTransferState {
-    DcPairState* phi = nullptr;              // Phi and the row / candidate tables of the shared build
+    DcPhi phi;                               // Phi and the row / candidate tables of the shared build
     int T = 0, ldt = 0;                      // transfers, rounded up to 64
     double* G = nullptr;                     // [rows][ldt]
     double* f0 = nullptr;                    // [rows] base flows: of the handle's right-hand side, or of the build's base profile
@@ -51,6 +51,7 @@ struct DcTransferState {
     double* base = nullptr;                  // [ldt][3] the transfers' base case: TC, the limiting row, branches above their rating at zero transfer
     double* rec = nullptr; long long rec_cap = 0;       // [rec_cap][5]
     double build_ms[3] = {0, 0, 0};          // G of the last build: total, sweep pairs, G kernel (HIP events)
+    DcMem mem;                               // the device memory of the fields above (not the DcPhi's): what release frees
 };
 
 void dc_transfer_free(DcHandle* h);          // releases what the transfer screen holds (jg_dc_destroy, jg_dc_transfer_release)

@@ -16,6 +16,7 @@ All numerics run in libjgrid_hip.so (csrc/jg_dc.hip); the O(n) bus / generator b
 from __future__ import annotations
 
 import ctypes as C
+from contextlib import contextmanager
 from types import SimpleNamespace as NS
 
 import numpy as np
@@ -356,6 +357,77 @@ def _pair_lists(system: PowerSystem, candidates, monitored, rating, who: str = "
             raise IndexError(f"{who}: monitored branch label out of range")
     return np.sort(cand), mon, rating
 
+SCREEN_INFO = ("rows", "ld", "phiBytes", "freeBytes", "budgetBytes", "buildMs", "sweepMs", "phiMs")     # info [0 .. 7] of every screen's build: the kept sensitivities
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data_as(_lib.VP)
+
+
+def _screen_rows(who: str, last: int, rows, block, block_bytes: int, row_bytes: int):
+    """(k0, k1, step) of a screen call: the candidate positions [k0, k1) it covers (`rows`, cut at `last`; default all of them) and the rows of one
+    device call (`block`; default: `block_bytes` of dense result at `row_bytes` a row)"""
+    k0, k1 = (0, last) if rows is None else (int(rows[0]), min(int(rows[1]), last))
+    if k0 < 0 or k1 < k0:
+        raise ValueError(f"{who}: rows = (k0, k1) with 0 <= k0 <= k1 <= candidates")
+    step = max(1, block_bytes // row_bytes) if block is None else int(block)
+    if step < 1:
+        raise ValueError(f"{who}: block >= 1")
+    return k0, k1, step
+
+
+@contextmanager
+def _screen_analysis(analysis_or_system, which: str, rating, device: int):
+    """(analysis, library) of a screen call, the base right-hand side and the rating set: the caller's analysis, whose screen state (jg_dc_<which>_*) is
+    released afterwards, or for a PowerSystem one of the call's own, closed afterwards"""
+    own = isinstance(analysis_or_system, PowerSystem)
+    an = dcPowerFlow(analysis_or_system, device=device) if own else analysis_or_system
+    L = _lib.lib()
+    try:
+        if an._rhs is None:
+            an._rhs = np.ascontiguousarray(_base_rhs(an.system), dtype=np.float64)
+            _lib.check(L.jg_dc_set_rhs(an._h, an._rhs))
+        _set_rating(an, rating)
+        yield an, L
+    finally:
+        if own:
+            an.close()
+        else:
+            _lib.check(getattr(L, f"jg_dc_{which}_release")(an._h))
+
+
+def _screen_blocks(k0: int, k1: int, step: int, rec: np.ndarray, full: dict, screen):
+    """The device calls of a screen, `step` rows at a time: screen(b0, b1, capacity, records, part) screens the rows [b0, b1) into what is left of the
+    record buffer `rec` and the row slices `part` of the dense arrays `full`, and returns the call's totals ([:3] add up, [3] = records written).
+    Returns (totals [3], records written)."""
+    tot, nrec = np.zeros(3, dtype=np.int64), 0
+    for b0 in range(k0, k1, step):
+        b1 = min(b0 + step, k1)
+        part = {name: a[b0 - k0:b1 - k0] for name, a in full.items()}                         # (row slices of a C-contiguous array are contiguous)
+        r = rec[nrec:]
+        t = screen(b0, b1, r.shape[0], _ptr(r) if r.shape[0] else None, part)
+        tot += t[:3]
+        nrec += int(t[3])
+    return tot, nrec
+
+
+def _shed_block(L, an, which: str, b0: int, b1: int, *shapes):
+    """(labels, buses, m, ...) of the bridge candidates among the positions [b0, b1) of a screen built in shed mode, then what jg_dc_<which>_get_shed
+    gives for them: one array of shape (bridges,) + s per s of `shapes`"""
+    n = np.zeros(1, dtype=np.int64)
+    lab, buses, m, side = (np.zeros(b1 - b0, dtype=np.int64) for _ in range(4))
+    _lib.check(getattr(L, f"jg_dc_{which}_get_shed_table")(an._h, b0, b1, n, lab, buses, m, side))
+    c = int(n[0])
+    flows = [np.zeros((c,) + s) for s in shapes]
+    if c:
+        _lib.check(getattr(L, f"jg_dc_{which}_get_shed")(an._h, b0, b1, *(f.reshape(-1) for f in flows)))
+    return (lab[:c], buses[:c], m[:c], *flows)
+
+
+def _concat(blocks, *empty):
+    """the columns of the blocks' tuples concatenated; `empty`: what a column is when there was no block"""
+    return [np.concatenate([x[j] for x in blocks]) if blocks else e for j, e in enumerate(empty)]
+
 
 PAIR_BLOCK_BYTES = 256 << 20                                           # default bound of the dense result of one device call (16 bytes per pair)
 
@@ -379,56 +451,33 @@ def dcPairScreen(analysis_or_system, candidates=None, monitored=None, rating=Non
         dcModel_(system)
     cand, mon, rating = _pair_lists(system, candidates, monitored, rating)
     nk = int(cand.size)
-    k0, k1 = (0, nk - 1) if rows is None else (int(rows[0]), min(int(rows[1]), nk - 1))     # (the last candidate is the first branch of no pair)
-    if k0 < 0 or k1 < k0:
-        raise ValueError("dcPairScreen: rows = (k0, k1) with 0 <= k0 <= k1 <= candidates")
-    ld = (nk + 63) // 64 * 64
-    step = max(1, PAIR_BLOCK_BYTES // (ld * (24 if dense else 16))) if block is None else int(block)
-    if step < 1:
-        raise ValueError("dcPairScreen: block >= 1")
-    an = dcPowerFlow(system, device=device) if own else analysis_or_system
-    L = _lib.lib()
-    try:
-        if an._rhs is None:
-            an._rhs = np.ascontiguousarray(_base_rhs(system), dtype=np.float64)
-            _lib.check(L.jg_dc_set_rhs(an._h, an._rhs))
-        _set_rating(an, rating)
+    k0, k1, step = _screen_rows("dcPairScreen", nk - 1, rows, block, PAIR_BLOCK_BYTES, (nk + 63) // 64 * 64 * (24 if dense else 16))     # (the last candidate is the first branch of no pair)
+    with _screen_analysis(analysis_or_system, "pair", rating, device) as (an, L):
         info = np.zeros(8)
-        _lib.check(L.jg_dc_pair_build(an._h, nk, cand, int(mon.size), mon.ctypes.data_as(_lib.VP), int(budget or 0), info))
-        ptr = lambda a: None if a is None else a.ctypes.data_as(_lib.VP)
+        _lib.check(L.jg_dc_pair_build(an._h, nk, cand, int(mon.size), _ptr(mon), int(budget or 0), info))
         rec = np.zeros((max(int(capacity), 0), 5))
         isl = np.zeros((max(int(islandCapacity), 0), 2), dtype=np.int64)
         worst = np.zeros(nk)
-        tot = np.zeros(3, dtype=np.int64)
-        nrec = nisl = 0
-        full = {name: np.zeros((k1 - k0, nk), dtype=dt) for name, dt in (("loading", np.float64), ("branch", np.int32), ("count", np.int32), ("determinant", np.float64))} if dense else None
-        for b0 in range(k0, k1, step):
-            b1 = min(b0 + step, k1)
-            t6 = np.zeros(6, dtype=np.int64)
-            part = {name: np.zeros((b1 - b0, nk), dtype=a.dtype) for name, a in full.items()} if dense else {}
-            r, i = rec[nrec:], isl[nisl:]
-            _lib.check(L.jg_dc_pair_screen(an._h, b0, b1, float(threshold), r.shape[0], ptr(r) if r.shape[0] else None, i.shape[0], ptr(i) if i.shape[0] else None,
-                                           t6, ptr(worst), ptr(part.get("loading")), ptr(part.get("branch")), ptr(part.get("count")), ptr(part.get("determinant"))))
-            tot += t6[:3]
-            nrec += int(t6[3])
+        nisl = 0
+        full = {name: np.zeros((k1 - k0, nk), dtype=dt) for name, dt in (("loading", np.float64), ("branch", np.int32), ("count", np.int32), ("determinant", np.float64))} if dense else {}
+
+        def screen(b0, b1, cap, r, part):
+            nonlocal nisl
+            t6, i = np.zeros(6, dtype=np.int64), isl[nisl:]
+            _lib.check(L.jg_dc_pair_screen(an._h, b0, b1, float(threshold), cap, r, i.shape[0], _ptr(i) if i.shape[0] else None, t6, _ptr(worst),
+                                           _ptr(part.get("loading")), _ptr(part.get("branch")), _ptr(part.get("count")), _ptr(part.get("determinant"))))
             nisl += int(t6[4])
-            for name, a in part.items():
-                full[name][b0 - k0:b1 - k0] = a
+            return t6
+        tot, nrec = _screen_blocks(k0, k1, step, rec, full, screen)
         res = DcPairScreen(candidates=cand, monitored=mon, records=rec[:nrec].copy(), islanding=isl[:nisl].copy(), worst=worst, threshold=float(threshold),
                            totals=dict(pairs=int(tot[0]), violating=int(tot[1]), islanding=int(tot[2])), overflow=bool(tot[1] > nrec),
-                           islandingOverflow=bool(tot[2] > nisl), rows=(k0, k1),
-                           info=dict(zip(("rows", "ld", "phiBytes", "freeBytes", "budgetBytes", "buildMs", "sweepMs", "phiMs"), (float(x) for x in info))))
-        for name, a in (full or {}).items():
+                           islandingOverflow=bool(tot[2] > nisl), rows=(k0, k1), info=dict(zip(SCREEN_INFO, (float(x) for x in info))))
+        for name, a in full.items():
             if rows is None:                                            # the upper triangle, mirrored ([nk - 1, nk] rows came back: the last candidate has none)
                 a = np.vstack([a, np.zeros((1, nk), dtype=a.dtype)])
                 a = (a + a.T).astype(a.dtype)
             setattr(res, name, a)
         return res
-    finally:
-        if own:
-            an.close()
-        else:
-            _lib.check(L.jg_dc_pair_release(an._h))
 
 
 class DcSeriesScreen:
@@ -456,15 +505,6 @@ class DcSeriesScreen:
 
 
 SERIES_BLOCK_BYTES = 256 << 20                                         # default bound of the dense result of one device call (16 bytes per case)
-
-
-def _shed_block(L, an, which: str, b0: int, b1: int):
-    """(labels, buses, m) of the bridge candidates among the positions [b0, b1) of a screen built in shed mode"""
-    n = np.zeros(1, dtype=np.int64)
-    lab, buses, m, side = (np.zeros(b1 - b0, dtype=np.int64) for _ in range(4))
-    _lib.check(getattr(L, f"jg_dc_{which}_get_shed_table")(an._h, b0, b1, n, lab, buses, m, side))
-    c = int(n[0])
-    return lab[:c], buses[:c], m[:c]
 
 
 def _shed_demand(system: PowerSystem, labels: np.ndarray, demand: np.ndarray) -> np.ndarray:
@@ -519,70 +559,42 @@ def dcSeriesScreen(analysis_or_system, injections, candidates=None, monitored=No
         dcModel_(system)
     cand, mon, rating = _pair_lists(system, candidates, monitored, rating, who="dcSeriesScreen", least=1, shed=bool(mode))
     nk, T = int(cand.size), int(inj.shape[0])
-    k0, k1 = (0, nk) if rows is None else (int(rows[0]), min(int(rows[1]), nk))
-    if k0 < 0 or k1 < k0:
-        raise ValueError("dcSeriesScreen: rows = (k0, k1) with 0 <= k0 <= k1 <= candidates")
-    ldt = (T + 63) // 64 * 64
-    step = max(1, SERIES_BLOCK_BYTES // (ldt * 16)) if block is None else int(block)
-    if step < 1:
-        raise ValueError("dcSeriesScreen: block >= 1")
-    an = dcPowerFlow(system, device=device) if own else analysis_or_system
-    L = _lib.lib()
-    try:
-        if an._rhs is None:
-            an._rhs = np.ascontiguousarray(_base_rhs(system), dtype=np.float64)
-            _lib.check(L.jg_dc_set_rhs(an._h, an._rhs))
-        _set_rating(an, rating)
+    k0, k1, step = _screen_rows("dcSeriesScreen", nk, rows, block, SERIES_BLOCK_BYTES, (T + 63) // 64 * 64 * 16)
+    with _screen_analysis(analysis_or_system, "series", rating, device) as (an, L):
         rhs = np.ascontiguousarray(inj - system.bus.shunt.conductance[None, :] - system.model.dc.shiftPower[None, :])
         info = np.zeros(12)
         _lib.check(L.jg_dc_series_set_island_mode(an._h, mode))
-        _lib.check(L.jg_dc_series_build(an._h, nk, cand, int(mon.size), mon.ctypes.data_as(_lib.VP), T, rhs.reshape(-1), int(budget or 0), info))
+        _lib.check(L.jg_dc_series_build(an._h, nk, cand, int(mon.size), _ptr(mon), T, rhs.reshape(-1), int(budget or 0), info))
         del rhs
-        ptr = lambda a: None if a is None else a.ctypes.data_as(_lib.VP)
         rec = np.zeros((max(int(capacity), 0), 5))
         worst, worstProfile, violatingProfile, base = np.zeros(nk), np.zeros(T), np.zeros(T, dtype=np.int64), np.zeros((T, 3))
-        tot = np.zeros(3, dtype=np.int64)
-        nrec, bridges, shed = 0, [], []
+        bridges, shed = [], []
         full = {name: np.zeros((k1 - k0, T), dtype=dt) for name, dt in (("loading", np.float64), ("branch", np.int32), ("count", np.int32))} if dense else {}
-        for b0 in range(k0, k1, step):
-            b1 = min(b0 + step, k1)
-            t5 = np.zeros(5, dtype=np.int64)
-            isl = np.zeros(b1 - b0, dtype=np.int64)
-            part = {name: a[b0 - k0:b1 - k0] for name, a in full.items()}                     # (row slices of a C-contiguous array are contiguous)
-            r = rec[nrec:]
-            _lib.check(L.jg_dc_series_screen(an._h, b0, b1, float(threshold), r.shape[0], ptr(r) if r.shape[0] else None, ptr(isl), t5, ptr(worst),
-                                             ptr(worstProfile), ptr(violatingProfile), ptr(base) if b0 == k0 else None,
-                                             ptr(part.get("loading")), ptr(part.get("branch")), ptr(part.get("count"))))
-            tot += t5[:3]
-            nrec += int(t5[3])
+
+        def screen(b0, b1, cap, r, part):
+            t5, isl = np.zeros(5, dtype=np.int64), np.zeros(b1 - b0, dtype=np.int64)
+            _lib.check(L.jg_dc_series_screen(an._h, b0, b1, float(threshold), cap, r, _ptr(isl), t5, _ptr(worst), _ptr(worstProfile), _ptr(violatingProfile),
+                                             _ptr(base) if b0 == k0 else None, _ptr(part.get("loading")), _ptr(part.get("branch")), _ptr(part.get("count"))))
             bridges.append(isl[:int(t5[2])])
             if mode:
-                lab, buses, m = _shed_block(L, an, "series", b0, b1)
-                flow = np.zeros((lab.size, T))
-                if lab.size:
-                    _lib.check(L.jg_dc_series_get_shed(an._h, b0, b1, flow.reshape(-1)))
-                shed.append((lab, buses, m, flow))
+                shed.append(_shed_block(L, an, "series", b0, b1, (T,)))
+            return t5
+        tot, nrec = _screen_blocks(k0, k1, step, rec, full, screen)
+        none = np.zeros(0, dtype=np.int64)
         res = DcSeriesScreen(candidates=cand, monitored=mon, profiles=T, threshold=float(threshold), rows=(k0, k1), records=rec[:nrec].copy(),
-                             overflow=bool(tot[1] > nrec), islanding=np.concatenate(bridges) if bridges else np.zeros(0, dtype=np.int64),
+                             overflow=bool(tot[1] > nrec), islanding=np.concatenate(bridges) if bridges else none,
                              totals=dict(cases=int(tot[0]), violating=int(tot[1]), islanding=int(tot[2])), worst=worst, worstProfile=worstProfile,
                              violatingProfile=violatingProfile, base=base,
-                             info=dict(zip(("rows", "ld", "phiBytes", "freeBytes", "budgetBytes", "buildMs", "sweepMs", "phiMs", "f0Bytes", "f0BuildMs",
-                                            "f0SweepMs", "f0KernelMs"), (float(x) for x in info))))
+                             info=dict(zip(SCREEN_INFO + ("f0Bytes", "f0BuildMs", "f0SweepMs", "f0KernelMs"), (float(x) for x in info))))
         for name, a in full.items():
             setattr(res, name, a)
         res.shed = res.shedBuses = res.shedM = res.shedFlow = res.shedDemand = res.unserved = None
         if mode:
-            res.shed, res.shedBuses, res.shedM = (np.concatenate([x[j] for x in shed]) if shed else np.zeros(0, dtype=np.int64) for j in range(3))
-            res.shedFlow = np.concatenate([x[3] for x in shed]) if shed else np.zeros((0, T))
+            res.shed, res.shedBuses, res.shedM, res.shedFlow = _concat(shed, none, none, none, np.zeros((0, T)))
             if demand is not None:
                 res.shedDemand = _shed_demand(system, res.shed, demand)
                 res.unserved = res.shedDemand.sum(axis=1)
         return res
-    finally:
-        if own:
-            an.close()
-        else:
-            _lib.check(L.jg_dc_series_release(an._h))
 
 
 class DcTransferScreen:
@@ -673,69 +685,38 @@ def dcTransferScreen(analysis_or_system, transfers, candidates=None, monitored=N
         dcModel_(system)
     cand, mon, rating = _pair_lists(system, candidates, monitored, rating, who=who, least=1, shed=bool(mode))
     nk = int(cand.size)
-    k0, k1 = (0, nk) if rows is None else (int(rows[0]), min(int(rows[1]), nk))
-    if k0 < 0 or k1 < k0:
-        raise ValueError(f"{who}: rows = (k0, k1) with 0 <= k0 <= k1 <= candidates")
-    ldt = (T + 63) // 64 * 64
-    step = max(1, TRANSFER_BLOCK_BYTES // (ldt * 12)) if block is None else int(block)
-    if step < 1:
-        raise ValueError(f"{who}: block >= 1")
-    an = dcPowerFlow(system, device=device) if own else analysis_or_system
-    L = _lib.lib()
-    try:
-        if an._rhs is None:
-            an._rhs = np.ascontiguousarray(_base_rhs(system), dtype=np.float64)
-            _lib.check(L.jg_dc_set_rhs(an._h, an._rhs))
-        _set_rating(an, rating)
-        ptr = lambda a: None if a is None else a.ctypes.data_as(_lib.VP)
+    k0, k1, step = _screen_rows(who, nk, rows, block, TRANSFER_BLOCK_BYTES, (T + 63) // 64 * 64 * 12)
+    with _screen_analysis(analysis_or_system, "transfer", rating, device) as (an, L):
         base_rhs = None if injection is None else np.ascontiguousarray(injection - system.bus.shunt.conductance - system.model.dc.shiftPower)
         info = np.zeros(12)
         _lib.check(L.jg_dc_transfer_set_island_mode(an._h, mode))
-        _lib.check(L.jg_dc_transfer_build(an._h, nk, cand, int(mon.size), mon.ctypes.data_as(_lib.VP), T, np.ascontiguousarray(d).reshape(-1), ptr(base_rhs),
-                                          int(budget or 0), info))
+        _lib.check(L.jg_dc_transfer_build(an._h, nk, cand, int(mon.size), _ptr(mon), T, np.ascontiguousarray(d).reshape(-1), _ptr(base_rhs), int(budget or 0), info))
         rec = np.zeros((max(int(capacity), 0) if amount is not None else 0, 5))
         worst, base = np.full(nk, np.inf), np.zeros((T, 3))
         cap, capOutage, capBranch = np.full(T, np.inf), np.zeros(T, dtype=np.int64), np.zeros(T, dtype=np.int64)
-        tot = np.zeros(3, dtype=np.int64)
-        nrec, bridges, shed = 0, [], []
+        bridges, shed = [], []
         full = {name: np.zeros((k1 - k0, T), dtype=dt) for name, dt in (("capabilityCases", np.float64), ("branch", np.int32))} if dense else {}
-        for b0 in range(k0, k1, step):
-            b1 = min(b0 + step, k1)
-            t5 = np.zeros(5, dtype=np.int64)
-            isl = np.zeros(b1 - b0, dtype=np.int64)
-            part = {name: a[b0 - k0:b1 - k0] for name, a in full.items()}                     # (row slices of a C-contiguous array are contiguous)
-            r = rec[nrec:]
-            _lib.check(L.jg_dc_transfer_screen(an._h, b0, b1, float(cutoff), ptr(amount), r.shape[0], ptr(r) if r.shape[0] else None, ptr(isl), t5, ptr(worst),
-                                               ptr(cap), ptr(capOutage), ptr(capBranch), ptr(base) if b0 == k0 else None,
-                                               ptr(part.get("capabilityCases")), ptr(part.get("branch"))))
-            tot += t5[:3]
-            nrec += int(t5[3])
+
+        def screen(b0, b1, room, r, part):
+            t5, isl = np.zeros(5, dtype=np.int64), np.zeros(b1 - b0, dtype=np.int64)
+            _lib.check(L.jg_dc_transfer_screen(an._h, b0, b1, float(cutoff), _ptr(amount), room, r, _ptr(isl), t5, _ptr(worst), _ptr(cap), _ptr(capOutage),
+                                               _ptr(capBranch), _ptr(base) if b0 == k0 else None, _ptr(part.get("capabilityCases")), _ptr(part.get("branch"))))
             bridges.append(isl[:int(t5[2])])
             if mode:
-                lab, buses, m = _shed_block(L, an, "transfer", b0, b1)
-                flow, per = np.zeros(lab.size), np.zeros((lab.size, T))
-                if lab.size:
-                    _lib.check(L.jg_dc_transfer_get_shed(an._h, b0, b1, flow, per.reshape(-1)))
-                shed.append((lab, buses, m, flow, per))
+                shed.append(_shed_block(L, an, "transfer", b0, b1, (), (T,)))
+            return t5
+        tot, nrec = _screen_blocks(k0, k1, step, rec, full, screen)
+        none = np.zeros(0, dtype=np.int64)
         first = base[:, 0] <= cap                                       # ties go to the base case
         res = DcTransferScreen(candidates=cand, monitored=mon, transfers=T, cutoff=float(cutoff), rows=(k0, k1),
                                capability=np.where(first, base[:, 0], cap), limitingOutage=np.where(first, 0, capOutage),
                                limitingBranch=np.where(first, base[:, 1].astype(np.int64), capBranch), base=base, worst=worst, records=rec[:nrec].copy(),
-                               overflow=bool(tot[1] > nrec),
-                               islanding=np.concatenate(bridges) if bridges else np.zeros(0, dtype=np.int64),
+                               overflow=bool(tot[1] > nrec), islanding=np.concatenate(bridges) if bridges else none,
                                totals=dict(cases=int(tot[0]), limited=int(tot[1]), islanding=int(tot[2])),
-                               info=dict(zip(("rows", "ld", "phiBytes", "freeBytes", "budgetBytes", "buildMs", "sweepMs", "phiMs", "gBytes", "gBuildMs",
-                                              "gSweepMs", "gKernelMs"), (float(x) for x in info))))
+                               info=dict(zip(SCREEN_INFO + ("gBytes", "gBuildMs", "gSweepMs", "gKernelMs"), (float(x) for x in info))))
         for name, a in full.items():
             setattr(res, name, a)
         res.shed = res.shedBuses = res.shedM = res.shedFlow = res.shedTransfer = None
         if mode:
-            res.shed, res.shedBuses, res.shedM = (np.concatenate([x[j] for x in shed]) if shed else np.zeros(0, dtype=np.int64) for j in range(3))
-            res.shedFlow = np.concatenate([x[3] for x in shed]) if shed else np.zeros(0)
-            res.shedTransfer = np.concatenate([x[4] for x in shed]) if shed else np.zeros((0, T))
+            res.shed, res.shedBuses, res.shedM, res.shedFlow, res.shedTransfer = _concat(shed, none, none, none, np.zeros(0), np.zeros((0, T)))
         return res
-    finally:
-        if own:
-            an.close()
-        else:
-            _lib.check(L.jg_dc_transfer_release(an._h))

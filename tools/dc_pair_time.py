@@ -22,7 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-TILE, WAVES = 4, 4                                                      # DC_PAIR_TILE, DC_PAIR_WAVES of csrc/jg_dc_pair.hpp
+TILE, WAVES = 4, 4                                                      # DC_PAIR_TILE of csrc/jg_dc_pair.hpp, DC_PAIR_WAVES of csrc/jg_dc_phi.hpp
 
 
 def stats(ms, reps):

@@ -27,7 +27,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-TILE, WAVES = 4, 4                                                      # DC_SERIES_TILE of csrc/jg_dc_series.hpp, DC_PAIR_WAVES of csrc/jg_dc_pair.hpp
+TILE, WAVES = 4, 4                                                      # DC_SERIES_TILE of csrc/jg_dc_series.hpp, DC_PAIR_WAVES of csrc/jg_dc_phi.hpp
 BLOCK_BYTES = 256 << 20                                                 # SERIES_BLOCK_BYTES of dcpowerflow.py
 
 
