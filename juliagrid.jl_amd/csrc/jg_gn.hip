@@ -668,9 +668,8 @@ struct jg_gn : jg::Lanes {             // Lanes: stream, batch, ld, the staging 
     // device
     RowDesc* d_rows = nullptr; int* d_slot_bus = nullptr; BranchP* d_br = nullptr; int* d_items = nullptr; int n_items = 0;
     int* d_rowptr = nullptr; double* d_G = nullptr; double* d_B = nullptr; int* d_ydiag = nullptr;
-    void* d_arena = nullptr;                    // one allocation behind the per-handle state below (jg_gn_create)
     double* d_vm = nullptr; double* d_va = nullptr; double* d_mean = nullptr; double* d_w = nullptr;
-    double* d_Hs = nullptr; double* d_res = nullptr; double* d_rhs = nullptr; double* d_inc = nullptr;
+    double* d_Hs = nullptr; double* d_res = nullptr; double* d_rhs = nullptr; double* d_inc = nullptr;   // (d_vm ... d_group: ONE arena, jg_gn_create)
     GainRec* d_grec = nullptr; int* d_gwave = nullptr; GainRec* d_rrec = nullptr; int* d_rwave = nullptr;   // gain + rhs records of the items that are NOT staged (k_gn_gain), rhs records alone
     // bad-data test (built on first use)
     std::vector<RowDesc> rows_host; std::vector<int> slot_bus_host;
@@ -686,7 +685,7 @@ struct jg_gn : jg::Lanes {             // Lanes: stream, batch, ld, the staging 
     double* d_obj = nullptr; double* d_objpart = nullptr; int* d_corr = nullptr; int obj_chunks = 0;   // objective per scenario (first use: jg_gn_get_objective / jg_gn_pack_results_device)
     bool ran = false;                                   // d_iters / d_status hold the verdicts of a stateEstimation! run
     jg::Engine eng;
-    hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
+    jg::Graph graph;                                    // one iteration (jg_gn_run)
 };
 
 namespace {
@@ -878,8 +877,9 @@ int jg_gn_create(jg_gn** out, int64_t n, const int64_t* colptr, const int64_t* r
     // with half the update terms)
     // bit 49: Jordan rows for the pivots of the top tasks (jg_symbolic.hpp).  What reads the in-task triangle of U -- the forward elimination
     // of the orthogonal method, the selected inverse of the bad-data test -- factorises with Engine::jordan off (below).
+    struct Unwind { jg_gn* h; ~Unwind() { if (h) jg_gn_destroy(h); } } unwind{h};   // every failure from here on: the half-built handle goes
     rc = h->eng.create((int)n, h->gi_rowptr.data(), h->gi_col.data(), h->ld, 3 | 1LL << 49, h->stream);
-    if (rc) { std::string msg = h->eng.error; jg_gn_destroy(h); return failg(rc, msg); }
+    if (rc) return failg(rc, h->eng.error);
     const std::vector<int>& ip = h->eng.plan->S.iperm;
     // wave records (see k_gn_gain): bus rows in PIVOT order -- the postorder of the elimination tree keeps electrical
     // neighbours together whatever the bus numbering of the case is, and neighbours are what shares measurement rows
@@ -971,36 +971,23 @@ int jg_gn_create(jg_gn** out, int64_t n, const int64_t* colptr, const int64_t* r
         br[k] = BranchP{p[0], p[1], 0.5 * p[2], 0.5 * p[3], 1.0 / p[4], p[5], (int)(from[k] - 1), (int)(to[k] - 1), 0.0};
     }
     // ---- device -------------------------------------------------------------------------------------
-    std::string err;
-    if (jg::upload(&h->d_rows, rows, err, h->stream) || jg::upload(&h->d_items, items, err, h->stream) || jg::upload(&h->d_slot_bus, slot_bus, err, h->stream) || jg::upload(&h->d_br, br, err, h->stream) ||
-        jg::upload(&h->d_rowptr, rp, err, h->stream) || jg::upload(&h->d_G, G, err, h->stream) || jg::upload(&h->d_B, B, err, h->stream) || jg::upload(&h->d_ydiag, ydiag, err, h->stream) ||
-        jg::upload(&h->d_grec, grec, err, h->stream) || jg::upload(&h->d_gwave, gwave, err, h->stream) || jg::upload(&h->d_rrec, rrec, err, h->stream) ||
-        jg::upload(&h->d_rwave, rwave, err, h->stream)) {
-        jg_gn_destroy(h); return failg(2, err);
-    }
+    if (h->upload(&h->d_rows, rows) || h->upload(&h->d_items, items) || h->upload(&h->d_slot_bus, slot_bus) || h->upload(&h->d_br, br) || h->upload(&h->d_rowptr, rp) ||
+        h->upload(&h->d_G, G) || h->upload(&h->d_B, B) || h->upload(&h->d_ydiag, ydiag) || h->upload(&h->d_grec, grec) || h->upload(&h->d_gwave, gwave) ||
+        h->upload(&h->d_rrec, rrec) || h->upload(&h->d_rwave, rwave)) return 2;
     const size_t ld = h->ld;
     h->nchunk = (h->n + NORM_ROWS - 1) / NORM_ROWS;
-    // the per-handle state as ONE allocation and ONE fill (as in jg_nr_create), every array on a 256-byte boundary.  (Where the arrays sit against each
+    // the per-handle state as ONE allocation and ONE fill (Lanes::arena), every array on a 256-byte boundary.  (Where the arrays sit against each
     // other does not matter to the kernels: offsets of 0 ... 260 kB between consecutive arrays modulo 2 MiB measured the same k_gn_rows, 0.89 - 0.93 ms on
     // the estimate's state -- profiles/r04_gn_skew_probe.txt.)
     const size_t nw = (size_t)m + (size_t)std::max<int64_t>(n_corr, 0);
-    struct Part { void** p; size_t bytes; };
-    const Part parts[] = {
-        {(void**)&h->d_vm, n * ld * 8}, {(void**)&h->d_va, n * ld * 8}, {(void**)&h->d_mean, (size_t)m * ld * 8}, {(void**)&h->d_w, nw * ld * 8},
-        {(void**)&h->d_Hs, (size_t)h->nslots * 2 * ld * 8}, {(void**)&h->d_res, (size_t)m * ld * 8}, {(void**)&h->d_rhs, n * 2 * ld * 8},
-        {(void**)&h->d_inc, n * 2 * ld * 8}, {(void**)&h->d_part, (size_t)h->nchunk * ld * 8}, {(void**)&h->d_maxinc, ld * 8}, {(void**)&h->d_params, 16},
-        {(void**)&h->d_active, ld * 4}, {(void**)&h->d_iters, ld * 4}, {(void**)&h->d_status, ld * 4}, {(void**)&h->d_counter, 4},
-        {(void**)&h->d_group, (ld / 64) * 4}};
-    size_t arena_bytes = 0;
-    for (const Part& q : parts) arena_bytes += (q.bytes + 255) / 256 * 256;
-    bool ok = hipMalloc((void**)&h->d_arena, arena_bytes) == hipSuccess && jg::sync_fill(h->d_arena, 0, arena_bytes, h->stream) == hipSuccess;
-    if (ok) {
-        size_t off = 0;
-        for (const Part& q : parts) { *q.p = (char*)h->d_arena + off; off += (q.bytes + 255) / 256 * 256; }
-    }
-    if (!ok || hipHostMalloc((void**)&h->h_counter, sizeof(int)) != hipSuccess) {
-        jg_gn_destroy(h); return failg(2, "jg_gn_create: device allocation failed");
-    }
+    const hipError_t e = h->arena({
+        {&h->d_vm, n * ld * 8}, {&h->d_va, n * ld * 8}, {&h->d_mean, (size_t)m * ld * 8}, {&h->d_w, nw * ld * 8},
+        {&h->d_Hs, (size_t)h->nslots * 2 * ld * 8}, {&h->d_res, (size_t)m * ld * 8}, {&h->d_rhs, n * 2 * ld * 8},
+        {&h->d_inc, n * 2 * ld * 8}, {&h->d_part, (size_t)h->nchunk * ld * 8}, {&h->d_maxinc, ld * 8}, {&h->d_params, 16},
+        {&h->d_active, ld * 4}, {&h->d_iters, ld * 4}, {&h->d_status, ld * 4}, {&h->d_counter, 4},
+        {&h->d_group, (ld / 64) * 4}});
+    if (e != hipSuccess || h->pin(&h->h_counter, 1) != hipSuccess) return failg(2, "jg_gn_create: device allocation failed");
+    unwind.h = nullptr;
     *out = h;
     return 0;
 }
@@ -1009,17 +996,9 @@ void jg_gn_destroy(jg_gn* h) {
     if (!h) return;
     hipSetDevice(h->device);
     if (h->stream) hipStreamSynchronize(h->stream);
-    if (h->exec) hipGraphExecDestroy(h->exec);
-    if (h->graph) hipGraphDestroy(h->graph);
     h->eng.destroy();
-    hipFree(h->d_rows); hipFree(h->d_items); hipFree(h->d_slot_bus); hipFree(h->d_br); hipFree(h->d_rowptr); hipFree(h->d_G); hipFree(h->d_B); hipFree(h->d_ydiag);
-    hipFree(h->d_vm0); hipFree(h->d_va0); hipFree(h->d_rho); hipFree(h->d_rhs2); hipFree(h->d_inc2);
-    hipFree(h->d_arena);                                         // V, theta, z, weights, slots, residual, rhs, increment, norms, lane bookkeeping: one allocation (jg_gn_create)
-    hipFree(h->d_pair_ptr); hipFree(h->d_pa); hipFree(h->d_pb); hipFree(h->d_pz); hipFree(h->d_nres); hipFree(h->d_amax_v); hipFree(h->d_amax_i);
-    hipFree(h->d_bad_v); hipFree(h->d_bad_i);
-    hipFree(h->d_obj); hipFree(h->d_objpart); hipFree(h->d_corr); hipFree(h->d_noise); hipFree(h->d_noise_bad); hipFree(h->d_stage);
-    hipFree(h->d_grec); hipFree(h->d_gwave); hipFree(h->d_rrec); hipFree(h->d_rwave);
-    if (h->h_counter) hipHostFree(h->h_counter);
+    h->graph.reset();
+    h->release_all();
     if (h->stream) hipStreamDestroy(h->stream);
     delete h;
 }
@@ -1039,14 +1018,10 @@ int jg_gn_set_method(jg_gn* h, int method) {
     GN_HIP(hipStreamSynchronize(h->stream));
     if (method == 1 && !h->d_rho) {
         const size_t ld = h->ld;
-        auto dmalloc = [&](void** p, size_t bytes) -> bool { return hipMalloc(p, bytes) == hipSuccess && jg::sync_fill(*p, 0, bytes, h->stream) == hipSuccess; };
-        if (!dmalloc((void**)&h->d_rho, (size_t)h->m * ld * 8) || !dmalloc((void**)&h->d_rhs2, (size_t)h->n * 2 * ld * 8) || !dmalloc((void**)&h->d_inc2, (size_t)h->n * 2 * ld * 8))
-            return failg(2, "jg_gn_set_method: device allocation failed");
+        if (h->alloc(&h->d_rho, (size_t)h->m * ld, true) != hipSuccess || h->alloc(&h->d_rhs2, (size_t)h->n * 2 * ld, true) != hipSuccess ||
+            h->alloc(&h->d_inc2, (size_t)h->n * 2 * ld, true) != hipSuccess) return failg(2, "jg_gn_set_method: device allocation failed");
     }
-    if (method != h->method && h->exec) {               // the captured iteration holds the other launch sequence
-        hipGraphExecDestroy(h->exec); hipGraphDestroy(h->graph);
-        h->exec = nullptr; h->graph = nullptr;
-    }
+    if (method != h->method) h->graph.reset();          // the captured iteration holds the other launch sequence
     h->method = method;
     h->eng.jordan = method == 0 && h->eng.plan->S.jordan && jg::knob("JORDAN", 1) != 0;   // method 1 runs forward() on the factor
     return 0;
@@ -1083,10 +1058,8 @@ int jg_gn_set_readings(jg_gn* h, int64_t ndev, const int64_t* row, const int8_t*
     }
     for (int r = 0; r < h->m; ++r) if (!seen[r]) return failg(1, "jg_gn_set_readings: a row of the model belongs to no device");
     GN_HIP(hipStreamSynchronize(h->stream));
-    hipFree(h->d_noise); h->d_noise = nullptr;
-    GN_HIP(hipMalloc((void**)&h->d_noise, t.size() * sizeof(NoiseDev)));
-    GN_HIP(jg::sync_copy(h->d_noise, t.data(), t.size() * sizeof(NoiseDev), hipMemcpyHostToDevice, h->stream));
-    if (!h->d_noise_bad) GN_HIP(hipMalloc((void**)&h->d_noise_bad, sizeof(int)));
+    if (int rc = h->upload(&h->d_noise, t)) return rc;
+    if (!h->d_noise_bad) GN_HIP(h->alloc(&h->d_noise_bad, 1));
     h->n_noise = (int)ndev;
     return 0;
 }
@@ -1173,20 +1146,18 @@ int jg_gn_solve(jg_gn* h) {
 int jg_gn_run(jg_gn* h, int64_t max_iter, double tol, int32_t* iters, int32_t* status) {
     if (!h || max_iter < 0 || !(tol > 0.0)) return failg(1, "jg_gn_run: bad argument");
     if (int rc = set_device(h)) return rc;
-    if (!h->exec) {
-        std::lock_guard<std::mutex> lk(jg::capture_mutex());
-        GN_HIP(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-        hipMemsetAsync(h->d_counter, 0, sizeof(int), h->stream);
-        // the first pass must see every group active: the flags of the PREVIOUS check drive group skipping
-        int rc = launch_increment(h, h->d_group);
-        hipMemsetAsync(h->d_group, 0, (size_t)(h->ld / 64) * sizeof(int), h->stream);
-        launch_check(h, 1);
-        launch_update(h, h->d_active);
-        hipMemcpyAsync(h->h_counter, h->d_counter, sizeof(int), hipMemcpyDeviceToHost, h->stream);
-        hipError_t e = hipStreamEndCapture(h->stream, &h->graph);
+    if (!h->graph) {
+        const int rc = h->graph.capture(h->stream, [&] {
+            hipMemsetAsync(h->d_counter, 0, sizeof(int), h->stream);
+            // the first pass must see every group active: the flags of the PREVIOUS check drive group skipping
+            if (int rc = launch_increment(h, h->d_group)) return rc;
+            hipMemsetAsync(h->d_group, 0, (size_t)(h->ld / 64) * sizeof(int), h->stream);
+            launch_check(h, 1);
+            launch_update(h, h->d_active);
+            hipMemcpyAsync(h->h_counter, h->d_counter, sizeof(int), hipMemcpyDeviceToHost, h->stream);
+            return 0;
+        });
         if (rc) return rc;
-        GN_HIP(e);
-        GN_HIP(hipGraphInstantiate(&h->exec, h->graph, nullptr, nullptr, 0));
     }
     const double params[2] = {tol, (double)max_iter};
     GN_HIP(hipMemcpyAsync(h->d_params, params, sizeof(params), hipMemcpyHostToDevice, h->stream));
@@ -1195,7 +1166,7 @@ int jg_gn_run(jg_gn* h, int64_t max_iter, double tol, int32_t* iters, int32_t* s
     GN_HIP(hipMemsetAsync(h->d_group, 0xff, (size_t)(h->ld / 64) * sizeof(int), h->stream));
     for (int64_t it = 0; it <= max_iter; ++it) {                                   // :1303
         h->arm();                                                                  // the verdict lands in the pinned word: polled while the iterations are short (jg_lanes.hpp)
-        GN_HIP(hipGraphLaunch(h->exec, h->stream));
+        GN_HIP(h->graph.launch(h->stream));
         GN_HIP(h->wait());
         if (*h->h_counter == 0) break;
     }
@@ -1211,10 +1182,9 @@ namespace {
 int launch_objective(jg_gn* h) {
     if (!h->d_obj) {
         h->obj_chunks = (h->m + OBJ_ROWS - 1) / OBJ_ROWS;
-        GN_HIP(hipMalloc((void**)&h->d_obj, (size_t)h->ld * 8));
-        GN_HIP(hipMalloc((void**)&h->d_objpart, (size_t)h->obj_chunks * h->ld * 8));
-        std::string err;
-        if (jg::upload(&h->d_corr, h->corr_row, err, h->stream)) return failg(2, err);
+        GN_HIP(h->alloc(&h->d_obj, (size_t)h->ld));
+        GN_HIP(h->alloc(&h->d_objpart, (size_t)h->obj_chunks * h->ld));
+        if (int rc = h->upload(&h->d_corr, h->corr_row)) return rc;
     }
     hipLaunchKernelGGL(k_gn_obj_partial, dim3(h->obj_chunks, h->ld / 64), dim3(64, 16), 0, h->stream, h->d_res, h->d_w, h->d_objpart, h->m, h->ld, h->batch);
     hipLaunchKernelGGL(k_gn_obj_final, dim3(h->ld / 64), dim3(64), 0, h->stream, h->d_objpart, h->obj_chunks, h->d_res, h->d_w + (size_t)h->m * h->ld, h->d_corr, h->ncorr,
@@ -1359,15 +1329,13 @@ int jg_gn_residual_test(jg_gn* h, double* max_nres, int32_t* index) {
             pp[r + 1] = (int)pa.size();
         }
         if (pa.empty()) { pa.push_back(0); pb.push_back(0); pz.push_back(0); }
-        std::string err;
         h->amax_chunks = (h->m + ROWS_PER - 1) / ROWS_PER;
-        if (jg::upload(&h->d_pair_ptr, pp, err, h->stream) || jg::upload(&h->d_pa, pa, err, h->stream) || jg::upload(&h->d_pb, pb, err, h->stream) ||
-            jg::upload(&h->d_pz, pz, err, h->stream)) return failg(2, err);
-        GN_HIP(hipMalloc((void**)&h->d_nres, (size_t)h->m * h->ld * 8));
-        GN_HIP(hipMalloc((void**)&h->d_amax_v, (size_t)h->amax_chunks * h->ld * 8));
-        GN_HIP(hipMalloc((void**)&h->d_amax_i, (size_t)h->amax_chunks * h->ld * 4));
-        GN_HIP(hipMalloc((void**)&h->d_bad_v, (size_t)h->ld * 8));
-        GN_HIP(hipMalloc((void**)&h->d_bad_i, (size_t)h->ld * 4));
+        if (h->upload(&h->d_pair_ptr, pp) || h->upload(&h->d_pa, pa) || h->upload(&h->d_pb, pb) || h->upload(&h->d_pz, pz)) return 2;
+        GN_HIP(h->alloc(&h->d_nres, (size_t)h->m * h->ld));
+        GN_HIP(h->alloc(&h->d_amax_v, (size_t)h->amax_chunks * h->ld));
+        GN_HIP(h->alloc(&h->d_amax_i, (size_t)h->amax_chunks * h->ld));
+        GN_HIP(h->alloc(&h->d_bad_v, (size_t)h->ld));
+        GN_HIP(h->alloc(&h->d_bad_i, (size_t)h->ld));
     }
     GN_HIP(hipMemsetAsync(h->eng.status, 0, (size_t)h->ld * 4, h->stream));
     {

@@ -1,9 +1,11 @@
-// jg_lanes.hip -- the lane I/O, the staging buffer, the verdict wait and the voltage snapshot of the NR and GN handles (jg_lanes.hpp).
+// jg_lanes.hip -- the memory, the captured graphs, the lane I/O, the staging buffer, the verdict wait and the voltage snapshot of the NR and GN handles
+// (jg_lanes.hpp).
 #include "jg_lanes.hpp"
 
 #include <chrono>
+#include <mutex>
+#include <string>
 #include <thread>
-#include <vector>
 
 #include "jg_engine.hpp"
 
@@ -53,6 +55,73 @@ bool poll_enabled() { static const bool on = knob("POLL", 1) != 0; return on; }
 
 }  // namespace
 
+int Graph::begin(hipStream_t st) {
+    reset();
+    capture_mutex().lock();
+    const hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
+    if (e == hipSuccess) return 0;
+    capture_mutex().unlock();
+    return api_fail(2, std::string("hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal): ") + hipGetErrorString(e));
+}
+
+int Graph::end(hipStream_t st, int rc) {
+    const char* what = "hipStreamEndCapture(st, &g)";
+    hipError_t e = hipStreamEndCapture(st, &g);        // whatever the body did: the stream must not stay in capture mode
+    if (!rc && e == hipSuccess) { what = "hipGraphInstantiate(&x, g, nullptr, nullptr, 0)"; e = hipGraphInstantiate(&x, g, nullptr, nullptr, 0); }
+    if (!rc && e != hipSuccess) rc = api_fail(2, std::string(what) + ": " + hipGetErrorString(e));
+    capture_mutex().unlock();
+    if (rc) reset();
+    return rc;
+}
+
+void Graph::reset() {
+    if (x) hipGraphExecDestroy(x);
+    if (g) hipGraphDestroy(g);
+    x = nullptr; g = nullptr;
+}
+
+hipError_t Lanes::block(void** p, size_t bytes, const void* src, size_t src_bytes, bool zero) {
+    drop(p);
+    hipError_t e = hipMalloc(p, bytes);
+    if (e != hipSuccess) { *p = nullptr; return e; }
+    if (std::find(dev_.begin(), dev_.end(), p) == dev_.end()) dev_.push_back(p);
+    if (zero) e = sync_fill(*p, 0, bytes, stream);
+    if (e == hipSuccess && src_bytes) e = sync_copy(*p, src, src_bytes, hipMemcpyHostToDevice, stream);
+    return e;
+}
+
+hipError_t Lanes::pinned(void** p, size_t bytes) {
+    drop(p);
+    const hipError_t e = hipHostMalloc(p, bytes);
+    if (e != hipSuccess) { *p = nullptr; return e; }
+    if (std::find(pinned_.begin(), pinned_.end(), p) == pinned_.end()) pinned_.push_back(p);
+    return e;
+}
+
+void Lanes::drop(void** p) {                            // (a pointer stays registered: an empty one costs release_all nothing)
+    if (!*p) return;
+    if (std::find(pinned_.begin(), pinned_.end(), p) != pinned_.end()) hipHostFree(*p); else hipFree(*p);
+    *p = nullptr;
+}
+
+void Lanes::release_all() {
+    for (void** p : dev_) drop(p);
+    for (void** p : pinned_) drop(p);
+    dev_.clear(); pinned_.clear();
+    stage_bytes = 0;
+}
+
+hipError_t Lanes::arena(std::initializer_list<Part> parts) {
+    size_t bytes = 0, off = 0;
+    for (const Part& q : parts) bytes += (q.bytes + 255) / 256 * 256;
+    const hipError_t e = block(&d_arena, bytes, nullptr, 0, true);
+    if (e != hipSuccess) return e;
+    for (const Part& q : parts) { *q.p = (char*)d_arena + off; off += (q.bytes + 255) / 256 * 256; }
+    return hipSuccess;
+}
+
+int Lanes::upload_fail(hipError_t e) { return e == hipSuccess ? 0 : api_fail(2, std::string("upload: ") + hipGetErrorString(e)); }
+
 void Lanes::collect(const double* src, double* dst, int rows) const {
     hipLaunchKernelGGL(k_lanes_collect, dim3((rows + 63) / 64, ld / 64), dim3(64, 8), 0, stream, src, src, dst, rows, ld, batch, (long long)rows);
 }
@@ -60,13 +129,13 @@ void Lanes::collect2(const double* a, const double* b, double* dst, int rows, lo
     hipLaunchKernelGGL(k_lanes_collect, dim3((rows + 63) / 64, ld / 64, 2), dim3(64, 8), 0, stream, a, b, dst, rows, ld, batch, stride);
 }
 
-// grows, is never freed before the handle (a hipFree per call would synchronise the device -- while another host thread of a pipeline may be capturing its
-// hipGraph); whatever still reads the old buffer on the stream finishes first
+// grows only (freeing it after every call would synchronise the device each time -- while another host thread of a pipeline may be capturing its hipGraph);
+// a grow frees the old block, after whatever still reads it on the stream has finished
 int Lanes::stage_room(size_t bytes) {
     if (bytes <= stage_bytes) return 0;
     JG_API_HIP(hipStreamSynchronize(stream));
-    hipFree(d_stage); d_stage = nullptr; stage_bytes = 0;
-    JG_API_HIP(hipMalloc((void**)&d_stage, bytes));
+    stage_bytes = 0;
+    JG_API_HIP(alloc(&d_stage, (bytes + sizeof(double) - 1) / sizeof(double)));
     stage_bytes = bytes;
     return 0;
 }
@@ -108,9 +177,8 @@ int Lanes::get_rows2(const double* src, double* dst, size_t rows) const {
     return 0;
 }
 
-int Lanes::snapshot(const double* a, const double* b, double** a0, double** b0, int rows) const {
-    const size_t bytes = (size_t)rows * ld * 8;
-    if (!*a0) { JG_API_HIP(hipMalloc((void**)a0, bytes)); JG_API_HIP(hipMalloc((void**)b0, bytes)); }
+int Lanes::snapshot(const double* a, const double* b, double** a0, double** b0, int rows) {
+    if (!*a0) { JG_API_HIP(alloc(a0, (size_t)rows * ld)); JG_API_HIP(alloc(b0, (size_t)rows * ld)); }
     if (int rc = restore(*a0, *b0, a, b, rows)) return rc;
     JG_API_HIP(hipStreamSynchronize(stream));
     return 0;

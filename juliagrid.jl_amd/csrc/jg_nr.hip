@@ -26,6 +26,7 @@
 #include <string>
 #include <system_error>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/jgrid.h"
@@ -908,14 +909,13 @@ struct jg_nr : jg::Lanes {             // Lanes: stream, batch, ld, the staging 
     // device
     int* d_rowptr = nullptr; int* d_col = nullptr; double* d_G = nullptr; double* d_B = nullptr; double2* d_GB = nullptr; int* d_rowtype = nullptr; int* d_rowtype_pre = nullptr;   // _pre: type | (pivot + 1) << 2 for the pivots of the plan's level 0
     signed char* d_type = nullptr; signed char* d_flags = nullptr;
-    void* d_arena = nullptr;                   // one allocation behind the per-handle state below (jg_nr_create)
     double* d_vm = nullptr; double* d_va = nullptr; double* d_p = nullptr; double* d_q = nullptr;
     int* d_ppos = nullptr; double* d_pdg = nullptr; double* d_pdb = nullptr;
     int* d_dst = nullptr; double* d_F = nullptr; double* d_inc = nullptr; double* d_part = nullptr;
     double* d_normp = nullptr; double* d_normq = nullptr; double* d_params = nullptr;
     double* d_vm0 = nullptr; double* d_va0 = nullptr;   // snapshot of the start point
     int* d_active = nullptr; int* d_iters = nullptr; int* d_status = nullptr; int* d_counter = nullptr; int* d_group = nullptr;
-    int* d_lid = nullptr; int* d_dest = nullptr; int* d_cflags = nullptr; int* d_itmp = nullptr; int* d_glist = nullptr;   // scenario compaction
+    int* d_lid = nullptr; int* d_dest = nullptr; int* d_cflags = nullptr; int* d_itmp = nullptr; int* d_glist = nullptr;   // scenario compaction (d_vm ... d_glist without d_dst, d_vm0, d_va0: ONE arena, jg_nr_create)
     bool refine = false;                              // one step of iterative refinement per Newton step (jg_nr_set_refine)
     bool fast = false;                                // fast decoupled mode (jg_nr_fast_setup): constant B', B'' factorised once
     std::vector<double> fast_blk;                     // ... the shared block matrix diag(B', B'') as set up [nnz][4] (engine block order)
@@ -924,15 +924,14 @@ struct jg_nr : jg::Lanes {             // Lanes: stream, batch, ld, the staging 
     double* d_R = nullptr;                            // rhs of the half-iterations
     double* d_inc2[2] = {nullptr, nullptr};           // increments of the theta / V half-iterations
     const int* fast_mask = nullptr;                   // scenarios that take the update (nullptr: all)
-    hipGraph_t graphFA = nullptr, graphFB = nullptr; hipGraphExec_t execFA = nullptr, execFB = nullptr;
+    jg::Graph gFA, gFB;                               // mismatch + verdict / the two half-iterations (jg_nr_fast_run)
     int nb = 0;                                       // post-processing (jg_nr_set_branches)
     int* d_bfrom = nullptr; int* d_bto = nullptr; signed char* d_bstatus = nullptr; double* d_bparam = nullptr; int* d_outage = nullptr;
     double* d_post = nullptr; size_t post_bytes = 0;  // staging for branch / bus quantities, grown on demand
     double* d_rating = nullptr; double* d_screen = nullptr; double* d_screc = nullptr;   // contingency screen: ratings [nb], partial maxima, the record [batch][10]
     jg::Engine eng;
-    hipGraph_t graphA = nullptr, graphB = nullptr, graphBm = nullptr, graphJ = nullptr;
-    hipGraphExec_t execA = nullptr, execB = nullptr, execBm = nullptr, execJ = nullptr;   // Bm / J: an iteration whose verdict assembles NO Jacobian / the Jacobian alone (run_loop)
-    hipGraph_t graphM = nullptr; hipGraphExec_t execM = nullptr; int m_iters = 0;          // ONE scenario: a whole solve of m_iters iterations as one graph (run_whole)
+    jg::Graph gA, gB, gBm, gJ;                        // build_graphs; Bm / J: an iteration whose verdict assembles NO Jacobian / the Jacobian alone (run_loop)
+    jg::Graph gM; int m_iters = 0;                    // ONE scenario: a whole solve of m_iters iterations as one graph (run_whole)
     int stop_hint = 0, iter_graphs = 0;               // iteration graphs after which the last run of this handle stopped / launched by the current run
     long long last_guess_hit = 0, last_guess_miss = 0;
     bool jac_valid = false;
@@ -953,8 +952,7 @@ struct jg_nr : jg::Lanes {             // Lanes: stream, batch, ld, the staging 
     std::vector<unsigned char> patch_state;           // [batch] 0 no edit, 1 edits within two adjacent buses (compensable), 2 other
     bool inj_checked = false, inj_equal = false;      // the lanes' injections were compared with the base's / equal it
     int* d_cmp = nullptr;                             // one word: mismatching injections (inj check)
-    hipGraph_t graphA2 = nullptr, graphC = nullptr;
-    hipGraphExec_t execA2 = nullptr, execC = nullptr;
+    jg::Graph gA2, gC;                                // build_comp_graphs
     long long first_comp = 0, first_full = 0;         // runs whose first iteration went the one / the other way (jg_nr_first_iteration_counts)
     // ---- bus types per scenario (jg_nr_set_bus_type, jg_nr_reactive_limit) ----
     unsigned long long* d_lt = nullptr;               // [ceil(n / 32)][ld] lane words, 2 bits per bus; moves with the lanes (launch_compact)
@@ -1005,6 +1003,18 @@ unsigned char classify_patch(const jg_nr* h, const int* pos, int k) {
 
 jg::GroupSel active_groups(jg_nr* h) { return jg::GroupSel{nullptr, h->d_glist, h->d_cflags + 3}; }
 
+// The runtime mp (0, 4, anything else = 8) and jac of a launch as template arguments: f(std::integral_constant<int, MP>{}[, std::bool_constant<JAC>{}])
+template <class F> void with_mp(int mp, F&& f) {
+    switch (mp) {
+        case 0: f(std::integral_constant<int, 0>{}); break;
+        case 4: f(std::integral_constant<int, 4>{}); break;
+        default: f(std::integral_constant<int, 8>{}); break;
+    }
+}
+template <class F> void with_mp_jac(int mp, bool jac, F&& f) {
+    with_mp(mp, [&](auto m) { if (jac) f(m, std::true_type{}); else f(m, std::false_type{}); });
+}
+
 // level0: the assembly also finishes level 0 of the engine's plan (factorised diagonal blocks + rhs rows of the pivots nobody
 // updates); the factorisation that follows must be told (h->level0_done).  Plain assemblies (getters, jg_nr_mismatch) leave it off.
 void launch_assemble(jg_nr* h, const jg::GroupSel& sel = jg::GroupSel{}, bool jac = true, double* pq_out = nullptr, int fd_mode = 0, const int* only_if = nullptr,
@@ -1016,62 +1026,27 @@ void launch_assemble(jg_nr* h, const jg::GroupSel& sel = jg::GroupSel{}, bool ja
     if (jac && !only_if) h->level0_done = pre;
     const bool lt = h->lt_on;                                     // scenarios with bus types of their own (jg_nr_set_bus_type): the lane-typed variant
     dim3 grid(jg::grid_blocks(h->ld / 64, h->nchunk)), block(64, ASM_WAVES);
+    auto go = [&](auto kernel, dim3 g, dim3 b) { hipLaunchKernelGGL(kernel, g, b, 0, h->stream, a); };
     const bool single_env = jg::knob("SINGLE", 1) != 0;           // (read at every capture: bench.py holds the two forms against each other in one process)
     if (h->ld == 64 && h->batch == 1 && !fd_mode && !pq_out && !only_if && single_env) {      // ONE scenario: a quad of lanes per bus row (k_assemble1)
         const dim3 g1(jg::grid_blocks(1, (h->n + 63) / 64));
-        if (jac) {
-            switch (h->mp) {
-                case 0: hipLaunchKernelGGL((k_assemble1<0, true>), g1, dim3(256), 0, h->stream, a); break;
-                case 4: hipLaunchKernelGGL((k_assemble1<4, true>), g1, dim3(256), 0, h->stream, a); break;
-                default: hipLaunchKernelGGL((k_assemble1<8, true>), g1, dim3(256), 0, h->stream, a); break;
-            }
-        } else {
-            switch (h->mp) {
-                case 0: hipLaunchKernelGGL((k_assemble1<0, false>), g1, dim3(256), 0, h->stream, a); break;
-                case 4: hipLaunchKernelGGL((k_assemble1<4, false>), g1, dim3(256), 0, h->stream, a); break;
-                default: hipLaunchKernelGGL((k_assemble1<8, false>), g1, dim3(256), 0, h->stream, a); break;
-            }
-        }
+        with_mp_jac(h->mp, jac, [&](auto m, auto j) { go(k_assemble1<decltype(m)::value, decltype(j)::value>, g1, dim3(256)); });
         return;
     }
     if (h->ld == 64 && h->batch <= 32 && !fd_mode && !pq_out) {      // a handful of scenarios: one row per wave (k_assemble: WAVES = 16); same arithmetic per row, same chunk maxima
         const bool w16 = h->nchunk <= 512;                          // grids whose workgroups are all resident at once: one row per wave; larger ones: two
         const dim3 wide(64, w16 ? 16 : 8);
-#define JG_ASM_WIDE1(MPV, JACV, LTV) do { if (w16) hipLaunchKernelGGL((k_assemble<MPV, JACV, 16, LTV>), grid, wide, 0, h->stream, a); else hipLaunchKernelGGL((k_assemble<MPV, JACV, 8, LTV>), grid, wide, 0, h->stream, a); } while (0)
-#define JG_ASM_WIDE(MPV, JACV) do { if (lt) JG_ASM_WIDE1(MPV, JACV, true); else JG_ASM_WIDE1(MPV, JACV, false); } while (0)
-        if (jac) {
-            switch (h->mp) {
-                case 0: JG_ASM_WIDE(0, true); break;
-                case 4: JG_ASM_WIDE(4, true); break;
-                default: JG_ASM_WIDE(8, true); break;
-            }
-        } else {
-            switch (h->mp) {
-                case 0: JG_ASM_WIDE(0, false); break;
-                case 4: JG_ASM_WIDE(4, false); break;
-                default: JG_ASM_WIDE(8, false); break;
-            }
-        }
-#undef JG_ASM_WIDE
-#undef JG_ASM_WIDE1
+        with_mp_jac(h->mp, jac, [&](auto m, auto j) {
+            constexpr int MP = decltype(m)::value; constexpr bool JAC = decltype(j)::value;
+            if (lt) { if (w16) go(k_assemble<MP, JAC, 16, true>, grid, wide); else go(k_assemble<MP, JAC, 8, true>, grid, wide); }
+            else { if (w16) go(k_assemble<MP, JAC, 16, false>, grid, wide); else go(k_assemble<MP, JAC, 8, false>, grid, wide); }
+        });
         return;
     }
-#define JG_ASM(MPV, JACV) do { if (lt) hipLaunchKernelGGL((k_assemble<MPV, JACV, ASM_WAVES, true>), grid, block, 0, h->stream, a); \
-                               else hipLaunchKernelGGL((k_assemble<MPV, JACV>), grid, block, 0, h->stream, a); } while (0)
-    if (jac) {
-        switch (h->mp) {
-            case 0: JG_ASM(0, true); break;
-            case 4: JG_ASM(4, true); break;
-            default: JG_ASM(8, true); break;
-        }
-    } else {
-        switch (h->mp) {
-            case 0: JG_ASM(0, false); break;
-            case 4: JG_ASM(4, false); break;
-            default: JG_ASM(8, false); break;
-        }
-    }
-#undef JG_ASM
+    with_mp_jac(h->mp, jac, [&](auto m, auto j) {
+        constexpr int MP = decltype(m)::value; constexpr bool JAC = decltype(j)::value;
+        if (lt) go(k_assemble<MP, JAC, ASM_WAVES, true>, grid, block); else go(k_assemble<MP, JAC>, grid, block);
+    });
 }
 
 // The verdict of a handle of ONE lane group in one launch (round 6): k_check's norms and loop control, then what k_compact comes to when there is nothing to pack --
@@ -1143,17 +1118,25 @@ __global__ __launch_bounds__(1024) void k_verdict64(CheckArgs a, CompactArgs p) 
     }
 }
 
+CheckArgs check_args(jg_nr* h, const int* group, int mode) {
+    return CheckArgs{h->d_part, h->nchunk, h->ld, h->batch, h->d_params, h->d_normp, h->d_normq, h->d_active, h->d_iters, h->d_status, h->eng.status, h->d_counter, group, mode};
+}
+// report: the count of active scenarios goes to the pinned verdict word -- and, from a handle of ONE lane group, iterations | status behind it (host_res)
+CompactArgs compact_args(jg_nr* h, int restore, bool report) {
+    return CompactArgs{h->d_active, h->d_iters, h->d_status, h->eng.status, h->d_lid, h->d_ppos, h->mp, h->d_dest, h->d_group, h->d_glist, h->d_cflags, h->d_itmp, h->ld, restore,
+                       report ? h->h_counter_dev : nullptr, report && h->ld == 64 ? h->h_counter_dev + 1 : nullptr, h->d_params};
+}
+void launch_verdict64(jg_nr* h, bool report) {         // (handles of one lane group only)
+    hipLaunchKernelGGL(k_verdict64, dim3(1), dim3(64, 16), 0, h->stream, check_args(h, h->d_group, 1), compact_args(h, 0, report));
+}
+
 void launch_check(jg_nr* h, int mode, const int* group = nullptr) {
-    CheckArgs c{h->d_part, h->nchunk, h->ld, h->batch, h->d_params, h->d_normp, h->d_normq, h->d_active,
-                h->d_iters, h->d_status, h->eng.status, h->d_counter, group, mode};
-    hipLaunchKernelGGL(k_check, dim3(h->ld / 64), dim3(64, 16), 0, h->stream, c);
+    hipLaunchKernelGGL(k_check, dim3(h->ld / 64), dim3(64, 16), 0, h->stream, check_args(h, group, mode));
 }
 
 // pack the active scenarios into the leading lanes (restore = 1: send every lane back home)
 void launch_compact(jg_nr* h, int restore, bool report = false) {
-    CompactArgs c{h->d_active, h->d_iters, h->d_status, h->eng.status, h->d_lid, h->d_ppos, h->mp, h->d_dest, h->d_group,
-                  h->d_glist, h->d_cflags, h->d_itmp, h->ld, restore, report ? h->h_counter_dev : nullptr, report && h->ld == 64 ? h->h_counter_dev + 1 : nullptr, h->d_params};
-    hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, h->stream, c);
+    hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, h->stream, compact_args(h, restore, report));
     if (h->ld == 64) return;                       // one lane group: nothing to pack, lanes never leave their home order
     double* tmp = h->eng.X;                        // the factor is dead here (rebuilt by the next factorisation)
     const dim3 block(256), gy((unsigned)((h->ld + 255) / 256));
@@ -1211,11 +1194,7 @@ int newton_step(jg_nr* h, const jg::GroupSel& sel, const int* active) {
     RefineArgs a{h->d_rowptr, h->d_col, h->d_GB, h->d_rowtype, h->d_vm, h->d_va, h->d_ppos, h->d_pdg, h->d_pdb,
                  h->d_F, h->d_inc2[1], h->d_R, sel, h->n, h->ld, h->mp, h->nchunk, h->batch};
     dim3 grid(jg::grid_blocks(h->ld / 64, h->nchunk)), block(64, ASM_WAVES);
-    switch (h->mp) {
-        case 0: hipLaunchKernelGGL((k_refine_residual<0>), grid, block, 0, h->stream, a); break;
-        case 4: hipLaunchKernelGGL((k_refine_residual<4>), grid, block, 0, h->stream, a); break;
-        default: hipLaunchKernelGGL((k_refine_residual<8>), grid, block, 0, h->stream, a); break;
-    }
+    with_mp(h->mp, [&](auto m) { hipLaunchKernelGGL((k_refine_residual<decltype(m)::value>), grid, block, 0, h->stream, a); });
     if (int rc = h->eng.forward(h->stream, h->d_R, sel)) return rc;
     if (int rc = h->eng.backsolve(h->stream, h->d_inc2[0], none, sel)) return rc;
     hipLaunchKernelGGL(k_refine_apply, dim3(jg::grid_blocks(h->ld / 64, (h->n + 15) / 16)), dim3(64, 16), 0, h->stream,
@@ -1223,22 +1202,15 @@ int newton_step(jg_nr* h, const jg::GroupSel& sel, const int* active) {
     return 0;
 }
 
+// A, B, Bm and J are built all or nothing: a failure leaves the four empty and the next call builds again.
 int build_graphs(jg_nr* h) {
-    if (h->execA) return 0;
-    std::lock_guard<std::mutex> lk(jg::capture_mutex());
-    NR_HIP(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
+    if (h->gA) return 0;
     // One pass decides AND prepares: mismatch + Jacobian in one assembly (the Jacobian of a finished batch is the only waste:
     // one write stream per solve, against a second walk over Ybus per iteration), verdict per scenario, compaction of the
     // still-active lanes.  A compaction moves lanes (and stages them in the factor storage), so the assembly is repeated
     // on the packed lanes -- a launch that returns at once unless the compaction flag is set.
     auto check_and_compact = [&]() {
-        if (h->ld == 64) {                             // one lane group: ONE launch (k_verdict64)
-            CheckArgs c{h->d_part, h->nchunk, h->ld, h->batch, h->d_params, h->d_normp, h->d_normq, h->d_active, h->d_iters, h->d_status, h->eng.status, h->d_counter, h->d_group, 1};
-            CompactArgs p{h->d_active, h->d_iters, h->d_status, h->eng.status, h->d_lid, h->d_ppos, h->mp, h->d_dest, h->d_group,
-                          h->d_glist, h->d_cflags, h->d_itmp, h->ld, 0, h->h_counter_dev, h->h_counter_dev + 1, h->d_params};
-            hipLaunchKernelGGL(k_verdict64, dim3(1), dim3(64, 16), 0, h->stream, c, p);
-            return;
-        }
+        if (h->ld == 64) { launch_verdict64(h, true); return; }     // one lane group: ONE launch (k_verdict64)
         launch_check(h, 1, h->d_group);
         launch_compact(h, 0, true);                    // also reports the number of active scenarios to the host word
     };
@@ -1247,41 +1219,29 @@ int build_graphs(jg_nr* h) {
         check_and_compact();
         if (h->ld > 64) launch_assemble(h, active_groups(h), true, nullptr, 0, h->d_cflags, true);
     };
+    auto step = [&]() { const int rc = newton_step(h, active_groups(h), h->d_active); return rc ? fail(rc, h->eng.error) : 0; };
     // graph A: the verdict on the start point
-    verdict();
-    NR_HIP(hipStreamEndCapture(h->stream, &h->graphA));
-    NR_HIP(hipGraphInstantiate(&h->execA, h->graphA, nullptr, nullptr, 0));
-    NR_HIP(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
+    int rc = h->gA.capture(h->stream, [&] { verdict(); return 0; });
     // graph B: one iteration on the packed lanes (factorise the Jacobian that is already in place, solve, update), then the
     // verdict on the new state
-    int rc = newton_step(h, active_groups(h), h->d_active);
-    verdict();
-    hipError_t e = hipStreamEndCapture(h->stream, &h->graphB);
-    if (rc) return fail(rc, h->eng.error);
-    NR_HIP(e);
-    NR_HIP(hipGraphInstantiate(&h->execB, h->graphB, nullptr, nullptr, 0));
+    if (!rc) rc = h->gB.capture(h->stream, [&] { if (int rc = step()) return rc; verdict(); return 0; });
     // graph Bm: the same iteration with a verdict from a MISMATCH-ONLY pass -- for the iteration the handle expects to be the last of its run (run_loop): the
     // Jacobian a verdict assembles is wasted on every scenario that converges (nobody factorises it) and on every scenario that leaves for a pool (jg_nr_resume
     // assembles where they arrive), 0.87 GB of a 512-scenario batch against 0.26 GB for the mismatch pass.  graph J: the Jacobian alone, when the guess was wrong.
-    NR_HIP(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-    rc = newton_step(h, active_groups(h), h->d_active);
-    launch_assemble(h, active_groups(h), false);
-    check_and_compact();
-    if (h->ld > 64) launch_assemble(h, active_groups(h), false, nullptr, 0, h->d_cflags);
-    e = hipStreamEndCapture(h->stream, &h->graphBm);
-    if (rc) return fail(rc, h->eng.error);
-    NR_HIP(e);
-    NR_HIP(hipGraphInstantiate(&h->execBm, h->graphBm, nullptr, nullptr, 0));
-    NR_HIP(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-    launch_assemble(h, active_groups(h), true, nullptr, 0, nullptr, true);
-    NR_HIP(hipStreamEndCapture(h->stream, &h->graphJ));
-    NR_HIP(hipGraphInstantiate(&h->execJ, h->graphJ, nullptr, nullptr, 0));
-    return 0;
+    if (!rc) rc = h->gBm.capture(h->stream, [&] {
+        if (int rc = step()) return rc;
+        launch_assemble(h, active_groups(h), false);
+        check_and_compact();
+        if (h->ld > 64) launch_assemble(h, active_groups(h), false, nullptr, 0, h->d_cflags);
+        return 0;
+    });
+    if (!rc) rc = h->gJ.capture(h->stream, [&] { launch_assemble(h, active_groups(h), true, nullptr, 0, nullptr, true); return 0; });
+    if (rc) for (jg::Graph* g : {&h->gA, &h->gB, &h->gBm, &h->gJ}) g->reset();
+    return rc;
 }
 
 void drop_iteration_graphs(jg_nr* h) {
-    for (hipGraphExec_t* e : {&h->execA, &h->execB, &h->execBm, &h->execJ, &h->execM}) if (*e) { hipGraphExecDestroy(*e); *e = nullptr; }
-    for (hipGraph_t* g : {&h->graphA, &h->graphB, &h->graphBm, &h->graphJ, &h->graphM}) if (*g) { hipGraphDestroy(*g); *g = nullptr; }
+    for (jg::Graph* g : {&h->gA, &h->gB, &h->gBm, &h->gJ, &h->gM}) g->reset();
     h->m_iters = 0;
 }
 
@@ -1291,40 +1251,23 @@ void drop_iteration_graphs(jg_nr* h) {
 // in one graph -- only the LAST verdict reports to the host, from a mismatch-only pass as in graph Bm; an iteration behind the convergence runs as launches that return
 // at once (the group list is empty).  Fewer iterations than expected: nothing to do; more: graph J supplies the Jacobian and run_loop carries on.
 int build_whole_graph(jg_nr* h, int k) {
-    if (h->execM && h->m_iters == k) return 0;
-    if (h->execM) { hipGraphExecDestroy(h->execM); h->execM = nullptr; }
-    if (h->graphM) { hipGraphDestroy(h->graphM); h->graphM = nullptr; }
+    if (h->gM && h->m_iters == k) return 0;
     h->m_iters = 0;
-    std::lock_guard<std::mutex> lk(jg::capture_mutex());
-    NR_HIP(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-    auto verdict64 = [&](bool report) {
-        CheckArgs c{h->d_part, h->nchunk, h->ld, h->batch, h->d_params, h->d_normp, h->d_normq, h->d_active, h->d_iters, h->d_status, h->eng.status, h->d_counter, h->d_group, 1};
-        CompactArgs p{h->d_active, h->d_iters, h->d_status, h->eng.status, h->d_lid, h->d_ppos, h->mp, h->d_dest, h->d_group,
-                      h->d_glist, h->d_cflags, h->d_itmp, h->ld, 0, report ? h->h_counter_dev : nullptr, report ? h->h_counter_dev + 1 : nullptr, h->d_params};
-        hipLaunchKernelGGL(k_verdict64, dim3(1), dim3(64, 16), 0, h->stream, c, p);
-    };
-    launch_assemble(h, active_groups(h), true, nullptr, 0, nullptr, true);       // the verdict on the start point (graph A)
-    verdict64(false);
-    int rc = 0;
-    for (int it = 1; it <= k && !rc; ++it) {
-        rc = newton_step(h, active_groups(h), h->d_active);
-        if (it < k) { launch_assemble(h, active_groups(h), true, nullptr, 0, nullptr, true); verdict64(false); }      // graph B
-        else { launch_assemble(h, active_groups(h), false); verdict64(true); }                                         // graph Bm: the expected last iteration
-    }
-    hipError_t e = hipStreamEndCapture(h->stream, &h->graphM);
-    if (rc) return fail(rc, h->eng.error);
-    NR_HIP(e);
-    NR_HIP(hipGraphInstantiate(&h->execM, h->graphM, nullptr, nullptr, 0));
-    h->m_iters = k;
-    return 0;
+    const int rc = h->gM.capture(h->stream, [&] {
+        launch_assemble(h, active_groups(h), true, nullptr, 0, nullptr, true);       // the verdict on the start point (graph A)
+        launch_verdict64(h, false);
+        for (int it = 1; it <= k; ++it) {
+            if (int rc = newton_step(h, active_groups(h), h->d_active)) return fail(rc, h->eng.error);
+            if (it < k) { launch_assemble(h, active_groups(h), true, nullptr, 0, nullptr, true); launch_verdict64(h, false); }      // graph B
+            else { launch_assemble(h, active_groups(h), false); launch_verdict64(h, true); }                                         // graph Bm: the expected last iteration
+        }
+        return 0;
+    });
+    if (!rc) h->m_iters = k;
+    return rc;
 }
 
-void drop_comp_graphs(jg_nr* h) {
-    if (h->execA2) { hipGraphExecDestroy(h->execA2); h->execA2 = nullptr; }
-    if (h->graphA2) { hipGraphDestroy(h->graphA2); h->graphA2 = nullptr; }
-    if (h->execC) { hipGraphExecDestroy(h->execC); h->execC = nullptr; }
-    if (h->graphC) { hipGraphDestroy(h->graphC); h->graphC = nullptr; }
-}
+void drop_comp_graphs(jg_nr* h) { h->gA2.reset(); h->gC.reset(); }
 
 void release_base(jg_nr_base* b) {
     if (!b) return;
@@ -1340,7 +1283,7 @@ void detach_base(jg_nr* h) {
     if (!h->base) return;
     if (h->stream) hipStreamSynchronize(h->stream);
     drop_comp_graphs(h);
-    hipFree(h->d_cw); h->d_cw = nullptr;
+    h->release(&h->d_cw);
     release_base(h->base);
     h->base = nullptr;
     h->start_is_base = false;
@@ -1350,31 +1293,29 @@ void detach_base(jg_nr* h) {
 // factorises it).  C: the first iteration -- per-scenario correction of the right-hand side, ONE sweep pair on the base's factor with the state update
 // fused in, then the usual verdict on the new state (which assembles the Jacobian the second iteration factorises).
 int build_comp_graphs(jg_nr* h) {
-    if (h->execC) return 0;
+    if (h->gC) return 0;
     const jg::CompBase& cb = h->base->cb;
-    std::lock_guard<std::mutex> lk(jg::capture_mutex());
-    NR_HIP(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-    launch_assemble(h, active_groups(h), false);
-    launch_check(h, 1, h->d_group);
-    launch_compact(h, 0, true);
-    if (h->ld > 64) launch_assemble(h, active_groups(h), false, nullptr, 0, h->d_cflags);      // lanes moved: their mismatch rows again
-    NR_HIP(hipStreamEndCapture(h->stream, &h->graphA2));
-    NR_HIP(hipGraphInstantiate(&h->execA2, h->graphA2, nullptr, nullptr, 0));
-    NR_HIP(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-    jg::CompFixArgs fa{h->d_ppos, h->d_pdg, h->d_pdb, h->mp, cb.rowptr, cb.colm, cb.posrow, cb.rowtype, cb.v0, cb.th0, cb.y0, cb.Zc,
-                       h->d_F, h->eng.status, h->d_active, h->ld, h->batch};
-    if (h->mp > 0) jg::launch_comp_fix(fa, h->stream);
-    jg::StateUpdate upd{h->d_va, h->d_vm, h->d_flags, h->d_active, -1.0};
-    const int rc = cb.solve(cb.split, h->stream, h->d_F, h->d_cw, h->d_inc, h->ld, h->batch, upd, active_groups(h));
-    launch_assemble(h, active_groups(h), true, nullptr, 0, nullptr, true);
-    launch_check(h, 1, h->d_group);
-    launch_compact(h, 0, true);
-    if (h->ld > 64) launch_assemble(h, active_groups(h), true, nullptr, 0, h->d_cflags, true);
-    hipError_t e = hipStreamEndCapture(h->stream, &h->graphC);
-    if (rc) return fail(rc, "the shared-factor sweep could not be captured");
-    NR_HIP(e);
-    NR_HIP(hipGraphInstantiate(&h->execC, h->graphC, nullptr, nullptr, 0));
-    return 0;
+    int rc = h->gA2.capture(h->stream, [&] {
+        launch_assemble(h, active_groups(h), false);
+        launch_check(h, 1, h->d_group);
+        launch_compact(h, 0, true);
+        if (h->ld > 64) launch_assemble(h, active_groups(h), false, nullptr, 0, h->d_cflags);      // lanes moved: their mismatch rows again
+        return 0;
+    });
+    if (!rc) rc = h->gC.capture(h->stream, [&] {
+        jg::CompFixArgs fa{h->d_ppos, h->d_pdg, h->d_pdb, h->mp, cb.rowptr, cb.colm, cb.posrow, cb.rowtype, cb.v0, cb.th0, cb.y0, cb.Zc,
+                           h->d_F, h->eng.status, h->d_active, h->ld, h->batch};
+        if (h->mp > 0) jg::launch_comp_fix(fa, h->stream);
+        jg::StateUpdate upd{h->d_va, h->d_vm, h->d_flags, h->d_active, -1.0};
+        if (int rc = cb.solve(cb.split, h->stream, h->d_F, h->d_cw, h->d_inc, h->ld, h->batch, upd, active_groups(h))) return fail(rc, "the shared-factor sweep could not be captured");
+        launch_assemble(h, active_groups(h), true, nullptr, 0, nullptr, true);
+        launch_check(h, 1, h->d_group);
+        launch_compact(h, 0, true);
+        if (h->ld > 64) launch_assemble(h, active_groups(h), true, nullptr, 0, h->d_cflags, true);
+        return 0;
+    });
+    if (rc) drop_comp_graphs(h);
+    return rc;
 }
 
 // mismatching injections between the lanes and the base (one word)
@@ -1427,8 +1368,7 @@ int ensure_lane_types(jg_nr* h) {
     std::vector<unsigned long long> one(rows), all((size_t)rows * h->ld);
     pack_types(h->type.data(), h->n, one.data(), rows, 1);
     for (int r = 0; r < rows; ++r) for (int b = 0; b < h->ld; ++b) all[(size_t)r * h->ld + b] = one[r];
-    std::string err;
-    if (jg::upload(&h->d_lt, all, err, h->stream) || jg::upload(&h->d_flags_all, std::vector<signed char>(h->n, 3), err, h->stream)) return fail(2, err);
+    if (h->upload(&h->d_lt, all) || h->upload(&h->d_flags_all, std::vector<signed char>(h->n, 3))) return 2;
     h->lt_set.assign(h->batch, 0);
     h->dead.assign(h->batch, 0);
     return 0;
@@ -1521,7 +1461,8 @@ int jg_nr_create(jg_nr** out, int64_t n, const int64_t* colptr, const int64_t* r
     };
     std::thread eng_thread;
     try { eng_thread = std::thread(eng_work); } catch (const std::system_error&) { eng_work(); }     // no thread to be had: the analysis first, then the rest
-    struct JoinEng { std::thread& t; ~JoinEng() { if (t.joinable()) t.join(); } } join_eng{eng_thread};     // every early return waits for it before the handle goes
+    // every failure from here on waits for the analysis thread, then the half-built handle goes
+    struct Unwind { jg_nr* h; std::thread& t; ~Unwind() { if (t.joinable()) t.join(); if (h) jg_nr_destroy(h); } } unwind{h, eng_thread};
     h->csr_col = cl;
     h->csr_row.assign(nnz, 0);
     for (int i = 0; i < n; ++i) for (int p = rp[i]; p < rp[i + 1]; ++p) h->csr_row[p] = i;
@@ -1533,7 +1474,7 @@ int jg_nr_create(jg_nr** out, int64_t n, const int64_t* colptr, const int64_t* r
             const int64_t r = rowval[p] - 1;
             int64_t lo = colptr[r] - 1, hi = colptr[r + 1] - 2, q = -1;
             while (lo <= hi) { int64_t m = (lo + hi) >> 1; if (rowval[m] - 1 < c) lo = m + 1; else if (rowval[m] - 1 > c) hi = m - 1; else { q = m; break; } }
-            if (q < 0) { if (eng_thread.joinable()) eng_thread.join(); jg_nr_destroy(h); return fail(1, "jg_nr_create: Ybus pattern is not structurally symmetric"); }
+            if (q < 0) return fail(1, "jg_nr_create: Ybus pattern is not structurally symmetric");
             h->tperm[p] = (int)q;
         }
     // ---- newtonJacobian (acPowerFlow.jl:89-175), integer only -------------------------------
@@ -1581,7 +1522,7 @@ int jg_nr_create(jg_nr** out, int64_t n, const int64_t* colptr, const int64_t* r
     }
     // ---- device upload ----------------------------------------------------------------------
     while (stream_state.load() == 0) std::this_thread::yield();
-    if (stream_state.load() < 0) { if (eng_thread.joinable()) eng_thread.join(); std::string m = h->eng.error; jg_nr_destroy(h); return fail(2, m); }
+    if (stream_state.load() < 0) return fail(2, h->eng.error);
     if (jg::knob_set("PLAN_TIMING")) fprintf(stderr, "[jg nr create] reference maps done at                  %6.1f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count() - tc0);
     std::vector<double> G(nnz), B(nnz);
     for (int p = 0; p < nnz; ++p) { G[p] = yt_reim[2 * p]; B[p] = yt_reim[2 * p + 1]; }
@@ -1596,62 +1537,50 @@ int jg_nr_create(jg_nr** out, int64_t n, const int64_t* colptr, const int64_t* r
     for (int p = 0; p < nnz; ++p) GBv[p] = double2{G[p], B[p]};
     // consistency of the two value arrays the reference keeps (T1): yT[p] must equal y[tperm[p]]
     for (int p = 0; p < nnz; ++p)
-        if (y_reim[2 * (size_t)h->tperm[p]] != yt_reim[2 * p] || y_reim[2 * (size_t)h->tperm[p] + 1] != yt_reim[2 * p + 1]) {
-            if (eng_thread.joinable()) eng_thread.join(); jg_nr_destroy(h); return fail(4, "jg_nr_create: nodalMatrix and nodalMatrixTranspose disagree (stale model)");
-        }
+        if (y_reim[2 * (size_t)h->tperm[p]] != yt_reim[2 * p] || y_reim[2 * (size_t)h->tperm[p] + 1] != yt_reim[2 * p + 1])
+            return fail(4, "jg_nr_create: nodalMatrix and nodalMatrixTranspose disagree (stale model)");
     std::vector<signed char> flags(n);
     for (int i = 0; i < n; ++i) flags[i] = (signed char)((type[i] != 3 ? 1 : 0) | (type[i] == 1 ? 2 : 0));
-    std::string err;
     std::vector<signed char> tp(type, type + n);
-    if (jg::upload(&h->d_rowptr, rp, err, h->stream) || jg::upload(&h->d_col, colm, err, h->stream) || jg::upload(&h->d_G, G, err, h->stream) ||
-        jg::upload(&h->d_B, B, err, h->stream) || jg::upload(&h->d_GB, GBv, err, h->stream) || jg::upload(&h->d_rowtype, std::vector<int>(type, type + n), err, h->stream) || jg::upload(&h->d_type, tp, err, h->stream) || jg::upload(&h->d_flags, flags, err, h->stream)) {
-        if (eng_thread.joinable()) eng_thread.join(); jg_nr_destroy(h); return fail(2, err);
-    }
+    if (h->upload(&h->d_rowptr, rp) || h->upload(&h->d_col, colm) || h->upload(&h->d_G, G) || h->upload(&h->d_B, B) || h->upload(&h->d_GB, GBv) ||
+        h->upload(&h->d_rowtype, std::vector<int>(type, type + n)) || h->upload(&h->d_type, tp) || h->upload(&h->d_flags, flags)) return 2;
     h->nchunk = (h->n + ASM_ROWS - 1) / ASM_ROWS;
     const size_t ld = h->ld;
     // the per-handle state as ONE allocation and ONE fill (round 4: 23 x (hipMalloc + fill + stream synchronisation) were 2 of the 4 ms a handle on a
     // cached plan costs); every array starts on a 256-byte boundary
     const size_t mpn = h->mp > 0 ? h->mp : 1;
-    struct Part { void** p; size_t bytes; };
-    const Part parts[] = {
-        {(void**)&h->d_vm, n * ld * 8}, {(void**)&h->d_va, n * ld * 8}, {(void**)&h->d_p, n * ld * 8}, {(void**)&h->d_q, n * ld * 8},
-        {(void**)&h->d_ppos, mpn * ld * 4}, {(void**)&h->d_pdg, mpn * ld * 8}, {(void**)&h->d_pdb, mpn * ld * 8},
-        {(void**)&h->d_F, n * 2 * ld * 8}, {(void**)&h->d_inc, n * 2 * ld * 8}, {(void**)&h->d_part, (size_t)h->nchunk * 2 * ld * 8},
-        {(void**)&h->d_normp, ld * 8}, {(void**)&h->d_normq, ld * 8}, {(void**)&h->d_params, 4 * 8}, {(void**)&h->d_active, ld * 4},
-        {(void**)&h->d_iters, ld * 4}, {(void**)&h->d_status, ld * 4}, {(void**)&h->d_counter, 4}, {(void**)&h->d_group, (ld / 64) * 4},
-        {(void**)&h->d_lid, ld * 4}, {(void**)&h->d_dest, ld * 4}, {(void**)&h->d_cflags, 32}, {(void**)&h->d_itmp, ld * 4},
-        {(void**)&h->d_glist, std::max<size_t>(ld / 64, 8) * 4}};    // map_block reads the first eight entries in one scalar load
-    size_t arena_bytes = 0;
-    for (const Part& q : parts) arena_bytes += (q.bytes + 255) / 256 * 256;
-    bool ok = hipMalloc((void**)&h->d_arena, arena_bytes) == hipSuccess && jg::sync_fill(h->d_arena, 0, arena_bytes, h->stream) == hipSuccess;
-    if (ok) {
-        size_t off = 0;
-        for (const Part& q : parts) { *q.p = (char*)h->d_arena + off; off += (q.bytes + 255) / 256 * 256; }
-    }
-    if (!ok) { if (eng_thread.joinable()) eng_thread.join(); jg_nr_destroy(h); return fail(2, "jg_nr_create: device allocation failed"); }
+    const hipError_t arena_err = h->arena({
+        {&h->d_vm, n * ld * 8}, {&h->d_va, n * ld * 8}, {&h->d_p, n * ld * 8}, {&h->d_q, n * ld * 8},
+        {&h->d_ppos, mpn * ld * 4}, {&h->d_pdg, mpn * ld * 8}, {&h->d_pdb, mpn * ld * 8},
+        {&h->d_F, n * 2 * ld * 8}, {&h->d_inc, n * 2 * ld * 8}, {&h->d_part, (size_t)h->nchunk * 2 * ld * 8},
+        {&h->d_normp, ld * 8}, {&h->d_normq, ld * 8}, {&h->d_params, 4 * 8}, {&h->d_active, ld * 4},
+        {&h->d_iters, ld * 4}, {&h->d_status, ld * 4}, {&h->d_counter, 4}, {&h->d_group, (ld / 64) * 4},
+        {&h->d_lid, ld * 4}, {&h->d_dest, ld * 4}, {&h->d_cflags, 32}, {&h->d_itmp, ld * 4},
+        {&h->d_glist, std::max<size_t>(ld / 64, 8) * 4}});    // map_block reads the first eight entries in one scalar load
+    if (arena_err != hipSuccess) return fail(2, "jg_nr_create: device allocation failed");
     if (jg::sync_fill(h->d_ppos, 0xff, mpn * ld * 4, h->stream) != hipSuccess ||     // -1 = no patch
-        hipHostMalloc((void**)&h->h_counter, 129 * sizeof(int)) != hipSuccess) {       // the verdict word + iterations | status of one lane group (k_compact: host_res)
-        if (eng_thread.joinable()) eng_thread.join(); jg_nr_destroy(h); return fail(2, "jg_nr_create: pinned allocation failed");
-    }
-    if (hipHostGetDevicePointer((void**)&h->h_counter_dev, h->h_counter, 0) != hipSuccess) { if (eng_thread.joinable()) eng_thread.join(); jg_nr_destroy(h); return fail(2, "jg_nr_create: pinned host word is not device-visible"); }
+        h->pin(&h->h_counter, 129) != hipSuccess)                                    // the verdict word + iterations | status of one lane group (k_compact: host_res)
+        return fail(2, "jg_nr_create: pinned allocation failed");
+    if (hipHostGetDevicePointer((void**)&h->h_counter_dev, h->h_counter, 0) != hipSuccess) return fail(2, "jg_nr_create: pinned host word is not device-visible");
     const bool timing = jg::knob_set("PLAN_TIMING");
     auto tnow = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     if (timing) fprintf(stderr, "[jg nr create] maps, model upload, state arena done at %6.1f ms\n", tnow() - tc0);
     if (eng_thread.joinable()) eng_thread.join();
     if (timing) fprintf(stderr, "[jg nr create] engine joined at                        %6.1f ms\n", tnow() - tc0);
-    if (eng_rc) { std::string m = h->eng.error; jg_nr_destroy(h); return fail(eng_rc, m); }
+    if (eng_rc) return fail(eng_rc, h->eng.error);
     // Every reader of this handle's factor other than the Jordan sweep -- forward() of a refined or fast step, the compact factor of jg_nr_base_create -- switches
     // Engine::jordan off for its factorisation, and with it this flag: the iteration graphs then leave the top tasks' dead entries unstored (JG_SWEEP_ONLY=0: stored)
     h->eng.sweep_only = jg::knob("SWEEP_ONLY", 1) != 0;
-    if (jg::upload(&h->d_dst, h->eng.plan->S.src_entry, err, h->stream)) { jg_nr_destroy(h); return fail(2, err); }
+    if (int rc = h->upload(&h->d_dst, h->eng.plan->S.src_entry)) return rc;
     if (h->eng.plan->S.prefactor) {                            // the row table of the assemblies that also finish the plan's level 0
         std::vector<int> rt(type, type + n);
         for (int k = 0; k < (int)n; ++k) if (h->eng.plan->S.pre_pivot[k]) rt[h->eng.plan->S.perm[k]] |= (k + 1) << 2;
-        if (jg::upload(&h->d_rowtype_pre, rt, err, h->stream)) { jg_nr_destroy(h); return fail(2, err); }
+        if (int rc = h->upload(&h->d_rowtype_pre, rt)) return rc;
     }
     h->eng.lanes = h->batch;
     for (int64_t k = 0; k < h->nnzJ; ++k) h->jmap[k] = (int64_t)h->eng.plan->S.src_entry[h->jmap[k] >> 2] * 4 + (h->jmap[k] & 3);
     if (timing) fprintf(stderr, "[jg nr create] done at                                 %6.1f ms\n", tnow() - tc0);
+    unwind.h = nullptr;
     *out = h;
     return 0;
 }
@@ -1664,26 +1593,12 @@ void jg_nr_destroy(jg_nr* h) {
     hipSetDevice(h->device);
     if (h->stream) hipStreamSynchronize(h->stream);
     detach_base(h);
-    hipFree(h->d_cmp);
-    if (h->d_move) { hipFree(h->d_move); hipHostFree(h->h_move); }
-    drop_iteration_graphs(h);
     h->eng.destroy();
-    hipFree(h->d_stage);
-    hipFree(h->d_R); hipFree(h->d_inc2[0]); hipFree(h->d_inc2[1]);
-    hipFree(h->d_fp_entry); hipFree(h->d_fp_dp); hipFree(h->d_fp_dq);
-    if (h->execFA) hipGraphExecDestroy(h->execFA);
-    if (h->execFB) hipGraphExecDestroy(h->execFB);
-    if (h->graphFA) hipGraphDestroy(h->graphFA);
-    if (h->graphFB) hipGraphDestroy(h->graphFB);
-    hipFree(h->d_bfrom); hipFree(h->d_bto); hipFree(h->d_bstatus); hipFree(h->d_bparam); hipFree(h->d_outage); hipFree(h->d_post);
-    hipFree(h->d_rating); hipFree(h->d_screen); hipFree(h->d_screc);
-    hipFree(h->d_rowptr); hipFree(h->d_col); hipFree(h->d_G); hipFree(h->d_B); hipFree(h->d_GB); hipFree(h->d_rowtype); hipFree(h->d_rowtype_pre); hipFree(h->d_type); hipFree(h->d_flags);
-    hipFree(h->d_arena);                                         // V, theta, P, Q, patches, mismatch, increment, norms, lane bookkeeping: one allocation (jg_nr_create)
-    hipFree(h->d_dst);
-    hipFree(h->d_vm0); hipFree(h->d_va0);
-    hipFree(h->d_lt); hipFree(h->d_flags_all); hipFree(h->d_skip); hipFree(h->d_shift);
     h->qt.destroy();
-    if (h->h_counter) hipHostFree(h->h_counter);
+    drop_iteration_graphs(h);
+    drop_comp_graphs(h);
+    h->gFA.reset(); h->gFB.reset();
+    h->release_all();
     if (h->stream) hipStreamDestroy(h->stream);
     delete h;
 }
@@ -1901,13 +1816,7 @@ int jg_nr_set_refine(jg_nr* h, int mode) {
     if (int rc = set_device(h)) return rc;
     NR_HIP(hipStreamSynchronize(h->stream));
     if (mode && !h->d_R) {
-        const size_t vec = (size_t)h->n * 2 * h->ld * 8;
-        NR_HIP(hipMalloc((void**)&h->d_R, vec));
-        NR_HIP(hipMalloc((void**)&h->d_inc2[0], vec));
-        if (!h->d_inc2[1]) NR_HIP(hipMalloc((void**)&h->d_inc2[1], vec));
-        NR_HIP(jg::sync_fill(h->d_R, 0, vec, h->stream));
-        NR_HIP(jg::sync_fill(h->d_inc2[0], 0, vec, h->stream));
-        NR_HIP(jg::sync_fill(h->d_inc2[1], 0, vec, h->stream));
+        for (double** p : {&h->d_R, &h->d_inc2[0], &h->d_inc2[1]}) NR_HIP(h->alloc(p, (size_t)h->n * 2 * h->ld, true));
     }
     if ((mode != 0) != h->refine) {                              // the iteration graph is captured for one mode
         drop_iteration_graphs(h);
@@ -1959,7 +1868,7 @@ int run_loop(jg_nr* h, int64_t max_iter, int defer_at) {
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (trace) { hipEventCreate(&e0); hipEventCreate(&e1); hipEventRecord(e0, h->stream); }
         if (!trace) h->arm();
-        NR_HIP(hipGraphLaunch(guess_last ? h->execBm : h->execB, h->stream));  // solve!, then mismatch! and the verdict on the new state
+        NR_HIP((guess_last ? h->gBm : h->gB).launch(h->stream));  // solve!, then mismatch! and the verdict on the new state
         const double tl = now_us();
         if (trace) hipEventRecord(e1, h->stream);
         NR_HIP(trace ? hipStreamSynchronize(h->stream) : h->wait());
@@ -1967,7 +1876,7 @@ int run_loop(jg_nr* h, int64_t max_iter, int defer_at) {
         if (guess_last) {
             const bool stops = *h->h_counter == 0 || (defer_at > 0 && *h->h_counter <= defer_at) || it + 1 > max_iter;
             if (stops) h->last_guess_hit += 1;
-            else { h->last_guess_miss += 1; NR_HIP(hipGraphLaunch(h->execJ, h->stream)); }     // the scenarios that go on need their Jacobian after all
+            else { h->last_guess_miss += 1; NR_HIP(h->gJ.launch(h->stream)); }     // the scenarios that go on need their Jacobian after all
         }
         if (trace) {
             float ms = 0.f; hipEventElapsedTime(&ms, e0, e1); fprintf(stderr, "[jg_nr_run] graph on the device: %.1f us\n", 1e3 * ms); hipEventDestroy(e0); hipEventDestroy(e1);
@@ -1989,7 +1898,7 @@ int run_start(jg_nr* h, int64_t max_iter) {
     h->start_is_base = false;                                                  // whatever follows moves the state
     h->iter_graphs = 0;
     h->arm();
-    NR_HIP(hipGraphLaunch(comp ? h->execA2 : h->execA, h->stream));
+    NR_HIP((comp ? h->gA2 : h->gA).launch(h->stream));
     NR_HIP(h->wait());
     if (!comp) { h->first_full += 1; return 0; }
     h->first_comp += 1;
@@ -2000,7 +1909,7 @@ int run_start(jg_nr* h, int64_t max_iter) {
     const bool trace = jg::knob_set("TRACE");
     const double t0 = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
     h->arm();
-    NR_HIP(hipGraphLaunch(h->execC, h->stream));
+    NR_HIP(h->gC.launch(h->stream));
     NR_HIP(h->wait());
     h->iter_graphs = 1;
     if (trace) fprintf(stderr, "[jg_nr_run] iteration 1 on the shared base factor: %.1f us, %d scenarios still active\n",
@@ -2020,12 +1929,12 @@ int run_whole(jg_nr* h, int64_t max_iter) {
     h->start_is_base = false;
     h->first_full += 1;
     h->arm();
-    NR_HIP(hipGraphLaunch(h->execM, h->stream));
+    NR_HIP(h->gM.launch(h->stream));
     NR_HIP(h->wait(true));
     h->iter_graphs = k;
     if (*h->h_counter != 0) {                                    // more iterations than the last run took: the Jacobian of the new state, then the loop
         h->last_guess_miss += 1;
-        NR_HIP(hipGraphLaunch(h->execJ, h->stream));
+        NR_HIP(h->gJ.launch(h->stream));
         return run_loop(h, max_iter, 0);
     }
     h->last_guess_hit += 1;
@@ -2172,10 +2081,8 @@ int jg_nr_attach_base(jg_nr* h, jg_nr_base* b) {
     if (h->fast) return fail(1, "jg_nr_attach_base: fast Newton-Raphson factorises constant matrices once anyway");
     if (b->device != h->device || b->n != h->n || b->nnz != h->nnz || b->colptr != h->colptr || b->rowval != h->rowval || b->type != h->type)
         return fail(1, "jg_nr_attach_base: the base was built for another grid (pattern, bus types) or device");
-    const size_t bytes = b->cb.scratch_rows(b->cb.split) * (size_t)h->ld * 2 * sizeof(double);
-    NR_HIP(hipMalloc((void**)&h->d_cw, bytes));
-    NR_HIP(jg::sync_fill(h->d_cw, 0, bytes, h->stream));
-    if (!h->d_cmp) NR_HIP(hipMalloc((void**)&h->d_cmp, sizeof(int)));
+    NR_HIP(h->alloc(&h->d_cw, b->cb.scratch_rows(b->cb.split) * (size_t)h->ld * 2, true));
+    if (!h->d_cmp) NR_HIP(h->alloc(&h->d_cmp, 1));
     b->refs.fetch_add(1);
     h->base = b;
     h->inj_checked = false;
@@ -2256,8 +2163,8 @@ int jg_nr_move_lanes(jg_nr* dst, int64_t dst_lane0, jg_nr* src, int32_t* home, i
     if (int rc = set_device(dst)) return rc;
     for (jg_nr* h : {dst, src})
         if (!h->d_move) {
-            NR_HIP(hipMalloc((void**)&h->d_move, 193 * sizeof(int)));
-            NR_HIP(hipHostMalloc((void**)&h->h_move, 65 * sizeof(int)));
+            NR_HIP(h->alloc(&h->d_move, 193));
+            NR_HIP(h->pin(&h->h_move, 65));
         }
     NR_HIP(hipStreamSynchronize(src->stream));
     int* map = dst->d_move; int* d_home = dst->d_move + 64; int* d_count = dst->d_move + 128;
@@ -2410,9 +2317,9 @@ static int fast_refactor(jg_nr* h) {
         // other pipeline threads in the middle of a graph capture
         const size_t cnt = h->fp_entry.size();
         if (!h->d_fp_entry) {
-            NR_HIP(hipMalloc((void**)&h->d_fp_entry, cnt * sizeof(int)));
-            NR_HIP(hipMalloc((void**)&h->d_fp_dp, cnt * sizeof(double)));
-            NR_HIP(hipMalloc((void**)&h->d_fp_dq, cnt * sizeof(double)));
+            NR_HIP(h->alloc(&h->d_fp_entry, cnt));
+            NR_HIP(h->alloc(&h->d_fp_dp, cnt));
+            NR_HIP(h->alloc(&h->d_fp_dq, cnt));
         }
         NR_HIP(hipMemcpyAsync(h->d_fp_entry, h->fp_entry.data(), cnt * sizeof(int), hipMemcpyHostToDevice, h->stream));
         NR_HIP(hipMemcpyAsync(h->d_fp_dp, h->fp_dp.data(), cnt * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -2449,9 +2356,7 @@ int jg_nr_fast_setup(jg_nr* h, const double* bp, const double* bq) {
     // (engine block q sits at row = the column that pointer q belongs to, col = rowval[q]; tperm[p of (r, c)] = pointer of (c, r))
     h->fp_entry.assign((size_t)FAST_MP * h->batch, -1); h->fp_dp.assign((size_t)FAST_MP * h->batch, 0.0); h->fp_dq.assign((size_t)FAST_MP * h->batch, 0.0);   // new matrices: no edits
     const size_t vec = (size_t)h->n * 2 * h->ld * 8;
-    if (!h->d_R) NR_HIP(hipMalloc((void**)&h->d_R, vec));
-    if (!h->d_inc2[0]) NR_HIP(hipMalloc((void**)&h->d_inc2[0], vec));
-    if (!h->d_inc2[1]) NR_HIP(hipMalloc((void**)&h->d_inc2[1], vec));
+    for (double** p : {&h->d_R, &h->d_inc2[0], &h->d_inc2[1]}) if (!*p) NR_HIP(h->alloc(p, vec / 8));
     NR_HIP(jg::sync_fill(h->d_R, 0, vec, h->stream));
     if (int rc = fast_refactor(h)) return rc;
     std::vector<int> st(h->ld);
@@ -2533,23 +2438,20 @@ int jg_nr_fast_get_increment(jg_nr* h, double* incr) {
 int jg_nr_fast_run(jg_nr* h, int64_t max_iter, double tol, int32_t* iters, int32_t* status) {
     if (!h || !h->fast || max_iter < 0 || !(tol > 0.0)) return fail(1, "jg_nr_fast_run: bad argument (or jg_nr_fast_setup missing)");
     if (int rc = set_device(h)) return rc;
-    if (!h->execFA) {
-        std::lock_guard<std::mutex> lk(jg::capture_mutex());
-        NR_HIP(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-        hipMemsetAsync(h->d_counter, 0, sizeof(int), h->stream);
-        launch_assemble(h, jg::GroupSel{}, false, nullptr, 1);                  // mismatch! (:687-730)
-        launch_check(h, 1);                                                     // powerFlow! accounting (:1406-1420)
-        hipMemcpyAsync(h->h_counter, h->d_counter, sizeof(int), hipMemcpyDeviceToHost, h->stream);
-        NR_HIP(hipStreamEndCapture(h->stream, &h->graphFA));
-        NR_HIP(hipGraphInstantiate(&h->execFA, h->graphFA, nullptr, nullptr, 0));
-        NR_HIP(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-        h->fast_mask = h->d_active;                                             // solve! (:913-983) on the scenarios still iterating
-        int rc = fast_half(h, 1);
-        if (!rc) rc = fast_half(h, 2);
-        hipError_t e = hipStreamEndCapture(h->stream, &h->graphFB);
-        if (rc) return rc;
-        NR_HIP(e);
-        NR_HIP(hipGraphInstantiate(&h->execFB, h->graphFB, nullptr, nullptr, 0));
+    if (!h->gFA) {
+        int rc = h->gFA.capture(h->stream, [&] {
+            hipMemsetAsync(h->d_counter, 0, sizeof(int), h->stream);
+            launch_assemble(h, jg::GroupSel{}, false, nullptr, 1);                  // mismatch! (:687-730)
+            launch_check(h, 1);                                                     // powerFlow! accounting (:1406-1420)
+            hipMemcpyAsync(h->h_counter, h->d_counter, sizeof(int), hipMemcpyDeviceToHost, h->stream);
+            return 0;
+        });
+        if (!rc) rc = h->gFB.capture(h->stream, [&] {
+            h->fast_mask = h->d_active;                                             // solve! (:913-983) on the scenarios still iterating
+            if (int rc = fast_half(h, 1)) return rc;
+            return fast_half(h, 2);
+        });
+        if (rc) { h->gFA.reset(); return rc; }
     }
     const double params[2] = {tol, (double)max_iter};
     NR_HIP(hipMemcpyAsync(h->d_params, params, sizeof(params), hipMemcpyHostToDevice, h->stream));
@@ -2563,10 +2465,10 @@ int jg_nr_fast_run(jg_nr* h, int64_t max_iter, double tol, int32_t* iters, int32
         NR_HIP(hipStreamSynchronize(h->stream));
     }
     for (int64_t it = 0; it <= max_iter; ++it) {
-        NR_HIP(hipGraphLaunch(h->execFA, h->stream));
+        NR_HIP(h->gFA.launch(h->stream));
         NR_HIP(hipStreamSynchronize(h->stream));
         if (*h->h_counter == 0) break;
-        NR_HIP(hipGraphLaunch(h->execFB, h->stream));
+        NR_HIP(h->gFB.launch(h->stream));
     }
     NR_HIP(hipStreamSynchronize(h->stream));
     if (iters) NR_HIP(jg::sync_copy(iters, h->d_iters, (size_t)h->batch * 4, hipMemcpyDeviceToHost, h->stream));
@@ -2583,21 +2485,11 @@ int jg_nr_set_branches(jg_nr* h, int64_t nb, const int64_t* from, const int64_t*
         f[k] = (int)(from[k] - 1); t[k] = (int)(to[k] - 1);
     }
     NR_HIP(hipStreamSynchronize(h->stream));
-    hipFree(h->d_bfrom); hipFree(h->d_bto); hipFree(h->d_bstatus); hipFree(h->d_bparam);
-    h->d_bfrom = h->d_bto = nullptr; h->d_bstatus = nullptr; h->d_bparam = nullptr;
-    std::string err;
-    if (jg::upload(&h->d_bfrom, f, err, h->stream) || jg::upload(&h->d_bto, t, err, h->stream) ||
-        jg::upload(&h->d_bstatus, std::vector<signed char>(status, status + nb), err, h->stream) ||
-        jg::upload(&h->d_bparam, std::vector<double>(param, param + nb * 16), err, h->stream))
-        return fail(2, err);
-    if (!h->d_outage) {
-        NR_HIP(hipMalloc((void**)&h->d_outage, (size_t)h->ld * sizeof(int)));
-        NR_HIP(jg::sync_fill(h->d_outage, 0, (size_t)h->ld * sizeof(int), h->stream));
-    }
-    if ((int)nb != h->nb) {                                      //  the screen's partial maxima are sized by the branch count and a rating
-        hipFree(h->d_screen); hipFree(h->d_screc); hipFree(h->d_rating);   // belongs to the branch table it was installed for: both go with the old table
-        h->d_screen = h->d_screc = h->d_rating = nullptr;
-    }
+    if (h->upload(&h->d_bfrom, f) || h->upload(&h->d_bto, t) || h->upload(&h->d_bstatus, std::vector<signed char>(status, status + nb)) ||
+        h->upload(&h->d_bparam, std::vector<double>(param, param + nb * 16))) return 2;
+    if (!h->d_outage) NR_HIP(h->alloc(&h->d_outage, (size_t)h->ld, true));
+    if ((int)nb != h->nb)                                        //  the screen's partial maxima are sized by the branch count and a rating
+        for (double** p : {&h->d_screen, &h->d_screc, &h->d_rating}) h->release(p);   // belongs to the branch table it was installed for: both go with the old table
     h->nb = (int)nb;
     return 0;
 }
@@ -2618,8 +2510,8 @@ int jg_nr_set_outage_labels(jg_nr* h, const int64_t* label) {
 
 static int post_staging(jg_nr* h, size_t bytes) {
     if (bytes <= h->post_bytes) return 0;
-    hipFree(h->d_post); h->d_post = nullptr; h->post_bytes = 0;
-    NR_HIP(hipMalloc((void**)&h->d_post, bytes));
+    h->post_bytes = 0;
+    NR_HIP(h->alloc(&h->d_post, (bytes + sizeof(double) - 1) / sizeof(double)));
     h->post_bytes = bytes;
     return 0;
 }
@@ -2663,11 +2555,10 @@ int jg_nr_set_screen(jg_nr* h, const double* rating) {
     if (!h) return fail(1, "jg_nr_set_screen: bad argument");
     if (!h->d_bparam) return fail(1, "jg_nr_set_screen: call jg_nr_set_branches first");
     if (int rc = set_device(h)) return rc;
-    hipFree(h->d_rating); h->d_rating = nullptr;
+    h->release(&h->d_rating);
     if (rating) {
         for (int k = 0; k < h->nb; ++k) if (!(rating[k] >= 0.0)) return fail(1, "jg_nr_set_screen: a rating is negative or not a number (0 = no limit)");
-        std::string err;
-        if (jg::upload(&h->d_rating, std::vector<double>(rating, rating + h->nb), err, h->stream)) return fail(2, err);
+        if (int rc = h->upload(&h->d_rating, std::vector<double>(rating, rating + h->nb))) return rc;
     }
     return 0;
 }
@@ -2676,8 +2567,8 @@ static int screen_launch(jg_nr* h) {
     if (!h->d_bparam) return fail(1, "jg_nr_screen: call jg_nr_set_branches first");
     const int bchunks = (h->nb + SCREEN_BR - 1) / SCREEN_BR, vchunks = (h->n + SCREEN_BUS - 1) / SCREEN_BUS;
     if (!h->d_screen) {
-        NR_HIP(hipMalloc((void**)&h->d_screen, (size_t)(bchunks + vchunks) * 4 * h->ld * sizeof(double)));
-        NR_HIP(hipMalloc((void**)&h->d_screc, (size_t)h->ld * 10 * sizeof(double)));
+        NR_HIP(h->alloc(&h->d_screen, (size_t)(bchunks + vchunks) * 4 * h->ld));
+        NR_HIP(h->alloc(&h->d_screc, (size_t)h->ld * 10));
     }
     ScreenArgs a{h->d_bfrom, h->d_bto, h->d_bstatus, h->d_bparam, h->d_rating, h->d_vm, h->d_va, h->d_outage, h->d_screen, h->d_iters, h->d_status,
                  h->d_screc, h->nb, h->n, h->ld, h->batch, bchunks, vchunks};
@@ -2806,7 +2697,7 @@ int jg_nr_reactive_limit(jg_nr* h, int flags, int8_t* violate, int32_t* count) {
     if (int rc = set_device(h)) return rc;
     NR_HIP(hipStreamSynchronize(h->stream));
     if (int rc = ensure_lane_types(h)) return rc;
-    if (!h->d_skip) NR_HIP(hipMalloc((void**)&h->d_skip, (size_t)h->ld * 4));
+    if (!h->d_skip) NR_HIP(h->alloc(&h->d_skip, (size_t)h->ld));
     std::vector<int> skip(h->ld, 0);
     for (int b = 0; b < h->batch; ++b) skip[b] = h->dead[b];
     NR_HIP(hipMemcpyAsync(h->d_skip, skip.data(), skip.size() * 4, hipMemcpyHostToDevice, h->stream));
@@ -2840,7 +2731,7 @@ int jg_nr_reactive_limit(jg_nr* h, int flags, int8_t* violate, int32_t* count) {
 int jg_nr_adjust_angle(jg_nr* h, int64_t bus, double angle) {
     if (!h || bus < 1 || bus > h->n) return fail(1, "jg_nr_adjust_angle: bad argument (bus: 1-based index)");
     if (int rc = set_device(h)) return rc;
-    if (!h->d_shift) NR_HIP(hipMalloc((void**)&h->d_shift, (size_t)h->ld * 8));
+    if (!h->d_shift) NR_HIP(h->alloc(&h->d_shift, (size_t)h->ld));
     jg::adjust_angle_launch(h->d_shift, h->d_va, h->n, h->ld, h->batch, (int)bus - 1, angle, h->stream);
     NR_HIP(hipGetLastError());
     NR_HIP(hipStreamSynchronize(h->stream));
