@@ -184,8 +184,12 @@ __global__ __launch_bounds__(64 * CTOP_WAVES) void k_ctop(CTopArgs a) {
         for (int r = 0; r < 4; ++r) part[wave][j][r][lane] = acc[j][r];
     __syncthreads();
     // wave j finishes scenario block j: row 16 rb + kq + 4 r = component (kq & 1) of top pivot 8 rb + (kq >> 1) + 2 r
+    // A lane beyond the batch only fed the instruction a clamped operand: it stores nothing.  (Clamped here as well, the padded lanes of every wave met on the
+    // last scenario, and a wave that read its state after another wave's store applied the top increment twice.)
     const int j = wave;
-    const size_t b = (size_t)min(grp * 64 + 16 * j + col, a.lanes - 1);
+    const int lb = grp * 64 + 16 * j + col;
+    if (lb >= a.lanes) return;
+    const size_t b = (size_t)lb;
     const bool act = a.upd.va ? (a.upd.active ? (a.upd.active[b] != 0) : true) : true;
     const int c = kq & 1;
 #pragma unroll
@@ -297,6 +301,7 @@ __global__ __launch_bounds__(64) void k_comp_fix(CompFixArgs a) {
         if (j != ba && bb < 0) bb = j;
     }
     const bool two = bb >= 0;
+    if (two && bb < ba) { const int t = ba; ba = bb; bb = t; }     // the pair in bus order: the 4 x 4 system, and with it the rounding, does not depend on the order of the entries
     if (!two) bb = ba;
     const int bus[2] = {ba, bb};
     double v[2], th[2]; int ty[2];

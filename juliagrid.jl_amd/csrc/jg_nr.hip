@@ -2189,6 +2189,7 @@ int jg_nr_move_lanes(jg_nr* dst, int64_t dst_lane0, jg_nr* src, int32_t* home, i
     *src->h_counter = 0;
     src->res_pinned = false;                                    // (the source's last verdict saw active scenarios: nothing stands behind its pinned word -- jg_nr_finish copies)
     dst->jac_valid = false;
+    dst->start_is_base = false;                                 // its lanes hold the states of the moved scenarios, not the base's
     return 0;
 }
 
@@ -2198,6 +2199,7 @@ int jg_nr_resume(jg_nr* h, int64_t lanes, int64_t max_iter, double tol, int32_t*
     if (int rc = set_device(h)) return rc;
     // lanes [0, lanes) hold moved scenarios (active, their iteration counts with them); the others are idle
     if (int rc = run_setup(h, max_iter, tol, (int)lanes, true)) return rc;
+    h->start_is_base = false;                                                  // the iterations below move the state
     if (lanes < h->ld) {
         NR_HIP(hipMemsetAsync(h->d_active + lanes, 0, (size_t)(h->ld - lanes) * 4, h->stream));
         NR_HIP(hipMemsetAsync(h->eng.status + lanes, 0, (size_t)(h->ld - lanes) * 4, h->stream));
