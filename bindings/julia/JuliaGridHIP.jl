@@ -1424,6 +1424,24 @@ end
 seriesScreenRelease!(b::DcPowerFlowBatch) = check(ccall((:jg_dc_series_release, lib), Cint, (Int64,), b.token))
 "island mode of the NEXT `seriesScreenBuild!`: 0 a bridge candidate is skipped (status 3), 1 it is screened on the slack's island (jgrid.h)"
 seriesScreenIslandMode!(b::DcPowerFlowBatch, mode::Int) = check(ccall((:jg_dc_series_set_island_mode, lib), Cint, (Int64, Cint), b.token, mode))
+"island mode of the NEXT `pairScreenBuild!`: 0 a pair with a bridge is singular (status 3), 1 its bridges are shed and it is screened on the slack's island (jgrid.h)"
+pairScreenIslandMode!(b::DcPowerFlowBatch, mode::Int) = check(ccall((:jg_dc_pair_set_island_mode, lib), Cint, (Int64, Cint), b.token, mode))
+"""
+    pairScreenShed(b, k0, k1) -> (branches, buses, m, side, flow [bridges])
+
+The bridge candidates among the positions k0 .. k1 - 1 (0-based) of a pair screen built in island mode 1: the branch, the number of buses that leave, the
+bridge's end on the slack's side, which end that is (+1 from, -1 to), and the flow that left that end over the bridge in the base case.
+"""
+function pairScreenShed(b::DcPowerFlowBatch, k0::Int64, k1::Int64)
+    count = zeros(Int64, 1)
+    branches = zeros(Int64, max(k1 - k0, 1)); buses = zeros(Int64, max(k1 - k0, 1)); m = zeros(Int64, max(k1 - k0, 1)); side = zeros(Int64, max(k1 - k0, 1))
+    check(ccall((:jg_dc_pair_get_shed_table, lib), Cint, (Int64, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}),
+        b.token, k0, k1, count, branches, buses, m, side))
+    c = count[1]
+    flow = zeros(Float64, max(c, 1))
+    c > 0 && check(ccall((:jg_dc_pair_get_shed, lib), Cint, (Int64, Int64, Int64, Ptr{Float64}), b.token, k0, k1, flow))
+    return branches[1:c], buses[1:c], m[1:c], side[1:c], flow[1:c]
+end
 """
     seriesScreenShed(b, k0, k1, profiles) -> (branches, buses, m, side, flow [T, bridges])
 
@@ -1692,6 +1710,6 @@ export HIP, HIPOrthogonal, NewtonRaphsonBatch, BaseCase, baseInfo, baseInverseOn
        largestNormalizedResidual, normalizedResiduals, commUniqueId, Comm, shard, contingencyAnalysis, clearPlanCache,
        deviceCount, dims, setRefinement!, deviceMaps, setOutage!, snapshotVoltage!, restoreVoltage!, iterations, voltageDevice!, packResults!, packRows!,
        allgatherDevice, commRank, commWorld, timeKernel, setBusType!, busType, GaussNewtonBatch, setRealisations!, monteCarloEstimation, fastPatch!, setReadings!, drawNoise!, measurementDevice,
-       DcPowerFlowBatch, setInjections!, setOutagePairs!, pairScreenBuild!, pairScreen, pairTimeKernel, pairScreenRelease!, seriesScreenIslandMode!, seriesScreenShed, transferScreenIslandMode!, transferScreenShed, seriesScreenBuild!, seriesScreen, seriesTimeKernel, seriesScreenRelease!, setIslandMode!, islands, islandTable, fromPower, angleDevice, DcStateEstimationBatch, removedRows, removeRows!
+       DcPowerFlowBatch, setInjections!, setOutagePairs!, pairScreenBuild!, pairScreen, pairTimeKernel, pairScreenRelease!, pairScreenIslandMode!, pairScreenShed, seriesScreenIslandMode!, seriesScreenShed, transferScreenIslandMode!, transferScreenShed, seriesScreenBuild!, seriesScreen, seriesTimeKernel, seriesScreenRelease!, setIslandMode!, islands, islandTable, fromPower, angleDevice, DcStateEstimationBatch, removedRows, removeRows!
 
 end # module

@@ -530,7 +530,7 @@ int jg_dc_set_outage_pairs(int64_t h, int64_t lane0, int64_t count, const int64_
  *                       that holds the slack: status 4, the angles of the buses that leave are NaN, flows are 0 on the outaged branch and on every
  *                       branch with an end among those buses, and the screen record covers the branches that stay.  The same sweep pair as any lane
  *                       (right-hand side e_m, m the bridge's end on the slack's side) and a combine without a denominator (csrc/jg_dc.hpp).  Lanes with
- *                       TWO outages and jg_dc_pair_screen keep status 3 for whatever islands.  Every other lane is bitwise what it is in mode 0.
+ *                       TWO outages keep status 3 for whatever islands (jg_dc_pair_screen has a mode of its own).  Every other lane is bitwise what it is in mode 0.
  *                       Needs jg_dc_set_branches.
  *   jg_dc_get_islands   rec [batch][4] after jg_dc_solve: buses shed, the lane's right-hand side summed over them, m (1-based), g = the flow that left m
  *                       over the bridge before the outage; zeros on lanes that shed nothing.
@@ -563,6 +563,16 @@ int jg_dc_island_table(int64_t n, int64_t nbr, const int64_t* from, const int64_
  *   jg_dc_pair_time_kernel   milliseconds of `reps` runs on rows [k0, k1) (a block jg_dc_pair_screen has held): 0 the screen kernel, 1 the row / column
  *                       summaries behind it
  *   jg_dc_pair_release  frees what the screen holds on the device
+ * Pairs with a bridge screened on the slack's island (csrc/jg_dc_pair.hpp, "shed mode"):
+ *   jg_dc_pair_set_island_mode     the island mode of the NEXT jg_dc_pair_build, which takes it and sets it back to 0.  0: a pair with a bridge is
+ *                       singular (status 3, as above).  1: a candidate the graph calls a bridge (the table of jg_dc_island_table on the handle's branches)
+ *                       is shed as jg_dc_set_island_mode 1 sheds a lane's: in a pair that holds one or two bridges the buses behind them leave, a
+ *                       branch with an end among them carries 0, the other branch (if it stays) is solved on what is left, and the pair enters the
+ *                       records, the counts and worst like any other.  `islanding` keeps the joint cuts of two non-bridges and the pairs with a
+ *                       non-bridge whose |1 - Phi[l,l]| < 1e-9.  A pair of two non-bridges is bitwise what it is after a build in mode 0.  dense_det of
+ *                       a pair with a bridge: the denominator of the branch that is solved, 1 where there is none.
+ *   jg_dc_pair_get_shed_table      as jg_dc_series_get_shed_table.
+ *   jg_dc_pair_get_shed            flow [count]: what left m over the bridge in the base case, per bridge of [k0, k1) in the order of the table.
  */
 int jg_dc_pair_build(int64_t h, int64_t nk, const int64_t* candidates, int64_t nm, const int64_t* monitored, int64_t budget_bytes, double* info8);
 int jg_dc_pair_screen(int64_t h, int64_t k0, int64_t k1, double threshold, int64_t capacity, double* records, int64_t island_capacity,
@@ -570,6 +580,9 @@ int jg_dc_pair_screen(int64_t h, int64_t k0, int64_t k1, double threshold, int64
                       double* dense_det);
 int jg_dc_pair_time_kernel(int64_t h, int kernel, int64_t k0, int64_t k1, int reps, double* ms);
 int jg_dc_pair_release(int64_t h);
+int jg_dc_pair_set_island_mode(int64_t h, int mode);
+int jg_dc_pair_get_shed_table(int64_t h, int64_t k0, int64_t k1, int64_t* count, int64_t* branches, int64_t* buses, int64_t* m, int64_t* side);
+int jg_dc_pair_get_shed(int64_t h, int64_t k0, int64_t k1, double* flow);
 /*
  * The DC N-1 screen over a SERIES of injection profiles (csrc/jg_dc_series.hpp): the user loop updateBus!(...; active) / updateGenerator!(...; active) per
  * profile t around updateBranch!(k, status = 0), solve!, power!, updateBranch!(k, status = 1) per branch k.  No sweep per case: with Phi of

@@ -4,7 +4,7 @@ Host-side mirror of the JuliaGrid interface for the hot path only (see DESIGN.md
 in libjgrid_hip.so (hand-written HIP for gfx950) through the C ABI of include/jgrid.h.
 """
 from .system import PowerSystem, CscMatrix, powerSystem, acModel_, dcModel_          # noqa: F401
-from .dcpowerflow import DcPowerFlow, dcPowerFlow, DcPairScreen, dcPairScreen, pairCandidates, shedCandidates, DcSeriesScreen, dcSeriesScreen, DcTransferScreen, dcTransferScreen, transferDirection          # noqa: F401
+from .dcpowerflow import DcPowerFlow, dcPowerFlow, DcPairScreen, dcPairScreen, pairCandidates, shedCandidates, pairShed, DcSeriesScreen, dcSeriesScreen, DcTransferScreen, dcTransferScreen, transferDirection          # noqa: F401
 from .system import addBranch_ as addBranchSystem_, dropZeros_ as dropZerosSystem_   # noqa: F401
 from .system import (updateBranch_ as updateBranchSystem_, updateBus_ as updateBusSystem_,   # noqa: F401
                      updateGenerator_ as updateGeneratorSystem_)
@@ -33,5 +33,5 @@ __all__ = [
     "outagePatch", "fastOutagePatch", "initializeACPowerFlow", "bridges", "islandTable", "outageList", "shard", "deviceBatching", "recommendedLanes", "contingencyAnalysis", "gatherResults", "gatherResultsDevice", "unpackResults",
     "WlsMethod", "Normal", "LU", "KLU", "QR", "LDLt", "LL", "Orthogonal", "PetersWilkinson",
     "addBranch_", "dropZeros_", "addBranchSystem_", "dropZerosSystem_", "pegaseShaped", "case9241synth", "ContingencyPipeline", "MonteCarloPipeline", "gatherEstimates", "gatherEstimatesDevice", "unpackEstimates", "setOutages_", "power_", "current_", "screenSummary_", "reactiveLimit_", "adjustAngle_",
-    "dcModel_", "DcPowerFlow", "dcPowerFlow", "DcPairScreen", "dcPairScreen", "pairCandidates", "shedCandidates", "DcSeriesScreen", "dcSeriesScreen", "DcTransferScreen", "dcTransferScreen", "transferDirection", "DcStateEstimation", "dcStateEstimation", "setReadings_", "removed", "removeMeasurement_", "BaseCase", "startFromBase_", "setFirstIteration_", "firstIterationCounts", "setBusType_", "busType", "powerFlowLimits_",
+    "dcModel_", "DcPowerFlow", "dcPowerFlow", "DcPairScreen", "dcPairScreen", "pairCandidates", "shedCandidates", "pairShed", "DcSeriesScreen", "dcSeriesScreen", "DcTransferScreen", "dcTransferScreen", "transferDirection", "DcStateEstimation", "dcStateEstimation", "setReadings_", "removed", "removeMeasurement_", "BaseCase", "startFromBase_", "setFirstIteration_", "firstIterationCounts", "setBusType_", "busType", "powerFlowLimits_",
 ]

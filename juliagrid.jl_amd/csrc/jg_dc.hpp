@@ -56,9 +56,9 @@ struct DcHandle : DcDevice {
     DcPairState* pair = nullptr;                                               // the N-2 screen over all pairs of a candidate list (jg_dc_pair.hpp)
     DcSeriesState* series = nullptr;                                           // the N-1 screen over a series of injection profiles (jg_dc_series.hpp)
     DcTransferState* transfer = nullptr;                                       // the transfer-capability screen over transfers x N-1 outages (jg_dc_transfer.hpp)
-    // island mode of the NEXT series / transfer build (the build takes it and sets it back to 0).  A sticky flag beside the build call is awkward -- the mode
+    // island mode of the NEXT pair / series / transfer build (the build takes it and sets it back to 0).  A sticky flag beside the build call is awkward -- the mode
     // belongs among the build's arguments -- but jg_dc_*_set_island_mode is part of the C ABI, so the flags stay
-    int series_shed = 0, transfer_shed = 0;
+    int pair_shed = 0, series_shed = 0, transfer_shed = 0;
     // bridge outages solved on the slack's island (jg_dc_set_island_mode 1): allocated by the first such call, a handle without it holds none of it
     int island_mode = 0, n_isl = 0;                                            // n_isl: lanes whose ONE outage is a bridge, set while the mode was 1
     std::vector<int> h_pre, h_blo, h_bhi, h_bside;                             // dc_island_table of the handle's branch table

@@ -4,7 +4,8 @@
 // walks the rows of Phi once (a wave = DC_PAIR_TILE candidates k in registers x 64 consecutive l; Phi[m, k..], f0_m, 1 / rating_m through scalar loads,
 // Phi[m, l..l+63] one coalesced vector load reused for every k of the tile; nothing is written per m); the records come out of the block's dense result by
 // count (k_pair_rows<false>) / prefix sum over the rows (host, a few thousand integers) / ordered scatter (k_pair_rows<true>: ballot ranks, no atomics),
-// so the list is sorted by (k, l) and a list that overflows keeps the first.  Every store is a vector store.
+// so the list is sorted by (k, l) and a list that overflows keeps the first.  Every store is a vector store.  A screen built in shed mode launches the
+// second instance of k_pair_screen, which sheds the bridges of a pair (jg_dc_pair.hpp has the table); the summaries are the same.
 #include "jg_dc_pair.hpp"
 
 #include <algorithm>
@@ -25,7 +26,14 @@ struct PairScreenArgs {
     double* load; int* branch; int* count; double* det;         // [k1 - k0][ldk]; det nullable
     double thr; int rows, ldk, nk, k0, k1, kbase;                // kbase: k0 rounded down to a multiple of the tile (the scalar loads of a tile are 32-byte aligned)
 };
-__global__ __launch_bounds__(64 * DC_PAIR_WAVES) void k_pair_screen(PairScreenArgs a) {
+struct PairShedArgs : PairScreenArgs {                           // what the SHED instance takes (the other one's argument block is the plain one, as it was)
+    const int* cisl; const int* rpre;                            // the candidates' (side, lo, hi, 0) and the rows' preorder[from]
+};
+// SHED (a screen built in shed mode, jg_dc_pair.hpp): a bridge candidate's column of Phi holds Z[:,c] and its coefficient is g_c = s_c f0_c without a solve; a
+// row whose from end lies in the preorder interval of either bridge left with it and carries 0.  The tile's intervals and the row's number are wave-uniform
+// (scalar loads, scalar compares, and only a row inside one of them takes the slow path); the lane's interval masks 1 / rating once per row, not per pair.
+template <bool SHED>
+__global__ __launch_bounds__(64 * DC_PAIR_WAVES) void k_pair_screen(std::conditional_t<SHED, PairShedArgs, PairScreenArgs> a) {
     constexpr int T = DC_PAIR_TILE;
     const int wave = uniform(threadIdx.y);
     const int kt = a.kbase + (blockIdx.y * DC_PAIR_WAVES + wave) * T;
@@ -39,6 +47,12 @@ __global__ __launch_bounds__(64 * DC_PAIR_WAVES) void k_pair_screen(PairScreenAr
     double ck[T], cl[T], wl[T], dt[T];
     int il[T], cnt[T];
     bool ok[T], sing[T];
+    int lo[T], hi[T];                                            // SHED: the tile's intervals
+    int sl = 0, lol = 1, hil = 0, prl = 0;                       // SHED: the lane's side and interval, and the preorder number of its row
+    if constexpr (SHED) {
+        const I4 q = ((const I4*)a.cisl)[l];
+        sl = q[0]; lol = q[1]; hil = q[2]; prl = a.rpre[rl];
+    }
 #pragma unroll
     for (int t = 0; t < T; ++t) {
         const int k = kt + t;                                    // < ldk: the per-candidate arrays are [ldk], 0 behind nk
@@ -47,16 +61,37 @@ __global__ __launch_bounds__(64 * DC_PAIR_WAVES) void k_pair_screen(PairScreenAr
         const double pkl = a.Phi[(size_t)rk * ldk + l];          // Phi[k, l]: a row, coalesced
         const double plk = a.Phi[(size_t)rl * ldk + k];          // Phi[l, k]: a gather, once per pair
         const double a11 = 1.0 - dk, a22 = 1.0 - dl;
-        const double det = a11 * a22 - pkl * plk;
+        // SHED spells out the fused forms the plain expressions contract to: which product the compiler fuses depends on what else uses the operands, and a
+        // pair of two non-bridges has to round as it does in the other instance (held bitwise by tests/test_dc_pair_shed_gpu.py)
+        const double det = SHED ? fma(a11, a22, -(pkl * plk)) : a11 * a22 - pkl * plk;
         ok[t] = k >= a.k0 && k < a.k1 && lane_ok && l > k;
         sing[t] = fabs(det) < DC_SINGULAR;
         const bool live = ok[t] && !sing[t];
-        ck[t] = live ? (a22 * fk + pkl * fl) / det : 0.0;
-        cl[t] = live ? (plk * fk + a11 * fl) / det : 0.0;
+        ck[t] = live ? (SHED ? fma(pkl, fl, a22 * fk) : a22 * fk + pkl * fl) / det : 0.0;
+        cl[t] = live ? (SHED ? fma(a11, fl, plk * fk) : plk * fk + a11 * fl) / det : 0.0;
         dt[t] = det; wl[t] = 0.0; il[t] = -1; cnt[t] = 0;
+        lo[t] = 1; hi[t] = 0;
+        if constexpr (SHED) {
+            const I4 q = ((CI4)a.cisl)[k];
+            const int prk = ((CInt)a.rpre)[rk];
+            lo[t] = q[1]; hi[t] = q[2];
+            const bool bk = q[0] != 0, bl = sl != 0;
+            if (bk || bl) {                                      // a pair with a bridge: no 2 x 2 solve (the table of jg_dc_pair.hpp)
+                const double gk = q[0] < 0 ? -fk : fk, gl = sl < 0 ? -fl : fl;      // what left m over the bridge before the outage
+                const bool l_behind = prl >= q[1] && prl <= q[2], k_behind = prk >= lol && prk <= hil;     // (an empty interval holds nothing)
+                const bool behind = l_behind || k_behind;
+                const double den = bk == bl ? 1.0 : (bk ? a22 : a11);                // the one non-bridge's own denominator
+                const double cm = (bk ? fma(plk, gk, fl) : fma(pkl, gl, fk)) / den;  // ... and its coefficient on M, the bridge's island shed first
+                sing[t] = !behind && fabs(den) < DC_SINGULAR;
+                const bool on = ok[t] && !sing[t];
+                ck[t] = (!on || k_behind) ? 0.0 : (bk ? gk : cm);
+                cl[t] = (!on || l_behind) ? 0.0 : (bl ? gl : cm);
+                dt[t] = behind ? 1.0 : den;
+            }
+        }
     }
     const double thr = a.thr;
-    auto row = [&](int r, int pk, auto hit_c) {
+    auto row = [&](int r, int pk, int pr, auto hit_c) {
         constexpr bool HIT = decltype(hit_c)::value;
         const double f0 = ((CDbl)a.f0)[r], ri = ((CDbl)a.rinv)[r];
         const double* prow = a.Phi + (size_t)r * ldk;
@@ -68,11 +103,14 @@ __global__ __launch_bounds__(64 * DC_PAIR_WAVES) void k_pair_screen(PairScreenAr
             pt[4] = q1[0]; pt[5] = q1[1]; pt[6] = q1[2]; pt[7] = q1[3];
         }
         const double pl = prow[l];
+        double ril = ri;
+        if constexpr (SHED) ril = (pr >= lol && pr <= hil) ? 0.0 : ri;       // a row that left with the lane's bridge: loading 0, once per row
 #pragma unroll
         for (int t = 0; t < T; ++t) {
             double v = fma(pt[t], ck[t], fma(pl, cl[t], f0));
             if (HIT && (pk == kt + t || pk == l)) v = 0.0;       // the two outaged branches carry nothing
-            const double ld = fabs(v) * ri;
+            double ld = fabs(v) * ril;
+            if (SHED && HIT && pr >= lo[t] && pr <= hi[t]) ld = 0.0;         // nor does a row that left with the tile's bridge
             if (ld > wl[t]) { wl[t] = ld; il[t] = r; }           // rows ascend by branch index, strict comparison: ties go to the lowest branch (k_dc_flows)
             cnt[t] += ld > thr ? 1 : 0;
         }
@@ -80,8 +118,15 @@ __global__ __launch_bounds__(64 * DC_PAIR_WAVES) void k_pair_screen(PairScreenAr
     for (int r = 0; r < a.rows; ++r) {
         const int pk = ((CInt)a.pos)[r];
         // only a row whose branch is one of this wave's candidates (at most T + 64 of the rows) needs the test per lane
-        if ((unsigned)(pk - kt) < (unsigned)T || (unsigned)(pk - l0) < 64u) row(r, pk, std::true_type{});
-        else row(r, pk, std::false_type{});
+        bool hit = (unsigned)(pk - kt) < (unsigned)T || (unsigned)(pk - l0) < 64u;
+        int pr = 0;
+        if constexpr (SHED) {                                    // ... or, in shed mode, a row inside the interval of one of the tile's bridges
+            pr = ((CInt)a.rpre)[r];
+#pragma unroll
+            for (int t = 0; t < T; ++t) hit = hit || (pr >= lo[t] && pr <= hi[t]);
+        }
+        if (hit) row(r, pk, pr, std::true_type{});
+        else row(r, pk, pr, std::false_type{});
     }
     const double nan = __longlong_as_double(0x7ff8000000000000LL);
 #pragma unroll
@@ -157,10 +202,10 @@ __global__ void k_pair_colmax(const double* load, double* c_max, int ldk, int nk
     c_max[l] = mx;
 }
 
-int pair_build(DcHandle* h, const std::vector<int>& cand, const std::vector<int>& mon, int64_t budget, double* info) {
+int pair_build(DcHandle* h, const std::vector<int>& cand, const std::vector<int>& mon, int64_t budget, double* info, bool shed) {
     dc_state_release(h, h->pair);
     DcPairState* p = h->pair = new DcPairState();
-    int rc = dc_phi_build(h, &p->phi, "jg_dc_pair_build", cand, mon, budget, 0, "", info);
+    int rc = dc_phi_build(h, &p->phi, "jg_dc_pair_build", cand, mon, budget, 0, "", info, shed);
     if (!rc) rc = dev_alloc(h, p->mem, &p->c_max, (size_t)p->phi.ldk, (const double*)nullptr, true);
     return rc ? dc_build_failed(h, h->pair, rc) : 0;
 }
@@ -180,18 +225,21 @@ int pair_block(DcHandle* h, int rb, bool want_det, long long rec_cap, long long 
     return dc_list_grow(h, p->mem, p->isl, p->isl_cap, isl_cap, 2);
 }
 
-PairScreenArgs screen_args(DcHandle* h, int k0, int k1, double thr, bool det) {
+PairShedArgs screen_args(DcHandle* h, int k0, int k1, double thr, bool det) {
     DcPairState* p = h->pair;
-    PairScreenArgs a{};
+    PairShedArgs a{};
     a.Phi = p->phi.Phi; a.f0 = p->phi.row_f0; a.rinv = p->phi.row_rinv; a.pos = p->phi.row_pos; a.rbranch = p->phi.row_branch;
     a.crow = p->phi.cand_row; a.cdiag = p->phi.cand_diag; a.cf0 = p->phi.cand_f0;
     a.load = p->b_load; a.branch = p->b_branch; a.count = p->b_count; a.det = det ? p->b_det : nullptr;
     a.thr = thr; a.rows = p->phi.rows; a.ldk = p->phi.ldk; a.nk = p->phi.nk; a.k0 = k0; a.k1 = k1; a.kbase = k0 / DC_PAIR_TILE * DC_PAIR_TILE;
+    a.cisl = p->phi.shed ? p->phi.cand_isl : nullptr; a.rpre = p->phi.shed ? p->phi.row_pre : nullptr;
     return a;
 }
-void launch_screen(DcHandle* h, const PairScreenArgs& a) {
+void launch_screen(DcHandle* h, const PairShedArgs& a) {
     const int tiles = (a.k1 - a.kbase + DC_PAIR_TILE - 1) / DC_PAIR_TILE;
-    hipLaunchKernelGGL(k_pair_screen, dim3(a.ldk / 64, (tiles + DC_PAIR_WAVES - 1) / DC_PAIR_WAVES), dim3(64, DC_PAIR_WAVES), 0, h->stream, a);
+    const dim3 grid(a.ldk / 64, (tiles + DC_PAIR_WAVES - 1) / DC_PAIR_WAVES), block(64, DC_PAIR_WAVES);
+    if (a.cisl) hipLaunchKernelGGL(k_pair_screen<true>, grid, block, 0, h->stream, a);
+    else hipLaunchKernelGGL(k_pair_screen<false>, grid, block, 0, h->stream, (const PairScreenArgs&)a);
 }
 PairListArgs list_args(DcHandle* h, int k0, int k1, double thr, long long rec_cap, long long isl_cap) {
     DcPairState* p = h->pair;
@@ -271,12 +319,14 @@ extern "C" {
 
 int jg_dc_pair_build(int64_t h, int64_t nk, const int64_t* candidates, int64_t nm, const int64_t* monitored, int64_t budget_bytes, double* info) {
     DC_ENTER(h);
+    const bool shed = d->pair_shed == 1;                         // the mode of THIS build alone, also when it is refused below
+    d->pair_shed = 0;
     if (!d->nbr) return api_fail(1, "jg_dc_pair_build: jg_dc_set_branches first");
     if (d->h_rhs.empty()) return api_fail(1, "jg_dc_pair_build: jg_dc_set_rhs first");
     if (nk < 2 || !candidates || !info || nm < 0 || (nm && !monitored)) return api_fail(1, "jg_dc_pair_build: two or more candidates, and info, are needed");
     std::vector<int> cand, mon;
     DC_RET(jg::dc_phi_lists(d, "jg_dc_pair_build", nk, candidates, nm, monitored, cand, mon));
-    DC_RET(jg::pair_build(d, cand, mon, budget_bytes, info));
+    DC_RET(jg::pair_build(d, cand, mon, budget_bytes, info, shed));
     return 0;
 }
 
@@ -303,6 +353,24 @@ int jg_dc_pair_time_kernel(int64_t h, int kernel, int64_t k0, int64_t k1, int re
             else jg::launch_stats(d, la);
         };
     });
+}
+
+int jg_dc_pair_set_island_mode(int64_t h, int mode) {
+    DC_ENTER(h);
+    return jg::dc_phi_set_island_mode(d, "pair", mode, d->pair_shed);
+}
+
+int jg_dc_pair_get_shed_table(int64_t h, int64_t k0, int64_t k1, int64_t* count, int64_t* labels, int64_t* buses, int64_t* m, int64_t* side) {
+    DC_ENTER(h);
+    return jg::dc_phi_get_shed_table(d, "pair", d->pair ? &d->pair->phi : nullptr, k0, k1, count, labels, buses, m, side);
+}
+
+int jg_dc_pair_get_shed(int64_t h, int64_t k0, int64_t k1, double* flow) {
+    DC_ENTER(h);
+    if (!d->pair) return api_fail(4, "jg_dc_pair_get_shed: jg_dc_pair_build first");
+    if (!flow || k0 < 0 || k1 < k0 || k1 > d->pair->phi.nk) return api_fail(1, "jg_dc_pair_get_shed: bad argument");
+    DC_RET(jg::dc_phi_shed_gather(d, &d->pair->phi, (int)k0, (int)k1, d->pair->phi.row_f0, 1, 1, flow));      // the base flows: one "profile"
+    return 0;
 }
 
 int jg_dc_pair_release(int64_t h) {

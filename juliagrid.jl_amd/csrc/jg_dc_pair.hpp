@@ -10,6 +10,19 @@
 // so a pair costs no sweep: a 2 x 2 solve and one pass over the monitored branches.  |det| < DC_SINGULAR: the pair islands a part of the grid (also when
 // neither branch alone is a bridge): status 3, the worst loading is NaN.
 //
+// Shed mode (jg_dc_pair_set_island_mode 1 before the build; jg_dc_series.hpp has the single outage): a candidate c the handle's island table calls a bridge
+// has s_c = +1 / -1 (its end m on the slack's side is the from / to end), the preorder interval [lo_c, hi_c] of the buses S_c that leave, the column
+// Z[:,c] = y_l a_l' B^-1 e_m in place of Phi[:,c], and g_c = s_c f0_c, the flow that left m over it in the base case.  S_c hangs on the rest M as a stub:
+// the sensitivities between branches of M do not see it, the flow over c is the net injection behind it whatever happens in M, and two such intervals are
+// nested or disjoint.  So a pair with a bridge needs no 2 x 2 solve: it is f_m = f0_m + P[m,k] c_k + P[m,l] c_l with (the roles of k and l exchange)
+//     k bridge, l not, l behind k (lo_k <= preorder[from_l] <= hi_k)     c_k = g_k   c_l = 0
+//     k bridge, l not, l in M                                            c_k = g_k   c_l = (f0_l + Z[l,k] g_k) / (1 - Phi[l,l]); |1 - Phi[l,l]| < DC_SINGULAR: status 3
+//     both bridges, disjoint intervals                                   c_k = g_k   c_l = g_l
+//     both bridges, l's interval inside k's                              c_k = g_k   c_l = 0
+// and 0 on the two branches and on every row whose from end lies in either interval.  "Behind" is one test for every kind of l: preorder[from_l] lies in
+// k's interval exactly when l, bridge or not, leaves with k.  A pair of two non-bridges is the system above, bitwise.  What stays status 3: the joint cuts
+// of two non-bridges (their S is no stub) and the pairs with a singular non-bridge.
+//
 // What is kept: Phi and its tables, a DcPhi (jg_dc_phi.hpp has the layout and the build, shared with the series and the transfer screen).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -39,7 +39,7 @@ struct DcPhi {
     int* cand_label = nullptr;               // [ldk] 1-based branch label of a candidate
     double* cand_diag = nullptr;             // [ldk] Phi[k,k]
     double* cand_f0 = nullptr;               // [ldk]
-    // shed mode of the series / transfer build (jg_dc_series.hpp): a bridge candidate's column holds Z[:,k] = y_l a_l' B^-1 e_m instead of Phi[:,k]
+    // shed mode of a build (jg_dc_series.hpp; the pair screen: jg_dc_pair.hpp): a bridge candidate's column holds Z[:,k] = y_l a_l' B^-1 e_m instead of Phi[:,k]
     bool shed = false;
     std::vector<int> h_side, h_lo, h_hi;     // [nk] dc_island_table of the candidates: side 0: not a bridge; lo .. hi the preorder interval of what leaves
     int* cand_isl = nullptr;                 // [ldk][4] side, lo, hi, 0 ((0, 1, 0, 0): not a bridge, the interval is empty)
@@ -103,8 +103,8 @@ int dc_phi_row_flows(DcHandle* h, const DcPhi* p, int T, const double* rhs, bool
 int dc_phi_bridges(DcHandle* h, const DcPhi* p, std::vector<char>& bridge);
 int dc_phi_shed_gather(DcHandle* h, const DcPhi* p, int k0, int k1, const double* F, int ldt, int T, double* out);
 
-// ---- exports the series and the transfer screen share: `screen` is "series" / "transfer" (/ "pair"), `p` null before the screen's build -----
-// jg_dc_<screen>_set_island_mode.  `flag` (DcHandle::series_shed / transfer_shed) is the mode of the NEXT build, which takes it and sets it back to 0
+// ---- exports the three screens share: `screen` is "pair" / "series" / "transfer", `p` null before the screen's build ---------------------------
+// jg_dc_<screen>_set_island_mode.  `flag` (DcHandle::pair_shed / series_shed / transfer_shed) is the mode of the NEXT build, which takes it and sets it back to 0
 int dc_phi_set_island_mode(DcHandle* d, const std::string& screen, int mode, int& flag);
 // jg_dc_<screen>_get_shed_table: the bridge candidates (shed mode) among the positions [k0, k1): their number, and per bridge the label, the buses that
 // leave, m (1-based) and the side; null outputs are skipped

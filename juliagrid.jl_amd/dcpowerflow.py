@@ -308,16 +308,41 @@ class DcPairScreen:
       candidates  [K] branch labels (1-based, ascending); monitored rows are those of the call
       records     [m, 5] the pairs whose worst loading exceeds the threshold, sorted by (k, l): label k, label l, worst branch, worst |from| / rating,
                   number of monitored branches above the threshold
-      islanding   [i, 2] int64 labels of the pairs that island a part of the grid (status 3)
+      islanding   [i, 2] int64 labels of the pairs that island a part of the grid (status 3); with islands="shed" only the pairs that STAY status 3: the
+                  joint cuts of two non-bridges, and the pairs with a non-bridge whose |1 - Phi[l,l]| vanishes
       totals      dict(pairs, violating, islanding): exact also when a list overflowed
       overflow / islandingOverflow   a list was cut at its capacity: it holds the FIRST entries by (k, l)
       worst       [K] the worst loading over all screened pairs of each candidate (ranking)
       loading, branch, count, determinant   with dense=True: [K, K], the upper triangle mirrored (NaN loading on islanding pairs, diagonal 0); with
                   rows=(k0, k1): the block [k1 - k0, K] as screened, 0 where l <= k
+      shed, shedBuses, shedM, shedFlow   with islands="shed" (else None), one entry per bridge among ALL the candidates (whatever `rows`): their labels
+                  ascending, the number of buses that leave [S] int64, the bridge's end on the slack's side [S] (1-based bus) and the flow that left
+                  that end over the bridge in the base case [S] (from the device).  A pair that holds a bridge is then screened on the slack's island:
+                  finite loading, in the records, the counts and `worst` like any other
+      recordShed  with islands="shed" (else None): [m, 2] int64, per record what pairShed gives for its pair
       info        dict(rows, ld, phiBytes, freeBytes, budgetBytes, buildMs, sweepMs, phiMs)"""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
+
+
+def pairShed(system: PowerSystem, pairs, table=None) -> np.ndarray:
+    """[m, 2] int64 for the pairs (k, l) of branch labels `pairs` [m, 2]: the labels of the bridges whose island leaves when both go out of service with
+    islands="shed" -- column 0 holds k and column 1 holds l where that branch is a bridge, 0 where it is none; of two NESTED bridges only the outer one
+    is named (what leaves behind the inner one is part of what leaves behind the outer).  Host only, from islandTable(system) (or `table`)."""
+    from .contingency import islandTable
+    tb = islandTable(system) if table is None else table
+    p = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    out = np.zeros(p.shape, dtype=np.int64)
+    if not p.shape[0]:
+        return out
+    k, l = p[:, 0] - 1, p[:, 1] - 1
+    bk, bl = tb.side[k] != 0, tb.side[l] != 0
+    k_in_l = bk & bl & (tb.lo[l] <= tb.lo[k]) & (tb.hi[k] <= tb.hi[l])
+    l_in_k = bk & bl & (tb.lo[k] <= tb.lo[l]) & (tb.hi[l] <= tb.hi[k])
+    out[:, 0] = np.where(bk & ~k_in_l, p[:, 0], 0)
+    out[:, 1] = np.where(bl & ~l_in_k, p[:, 1], 0)
+    return out
 
 
 def pairCandidates(system: PowerSystem) -> np.ndarray:
@@ -433,27 +458,36 @@ PAIR_BLOCK_BYTES = 256 << 20                                           # default
 
 
 def dcPairScreen(analysis_or_system, candidates=None, monitored=None, rating=None, threshold: float = 1.0, rows=None, capacity: int = 1 << 20,
-                 dense: bool = False, islandCapacity: int = 1 << 16, block=None, budget=None, device: int = 0) -> DcPairScreen:
+                 dense: bool = False, islandCapacity: int = 1 << 16, block=None, budget=None, device: int = 0, islands: str = "skip") -> DcPairScreen:
     """The DC N-2 screen: every pair k < l of `candidates` (labels; default pairCandidates(system)) out of service together, the worst |from| / rating over
     `monitored` (default: every in-service branch with a rating > 0) per pair -- the loop updateBranch!(k), updateBranch!(l), solve!, power! over all
     pairs, from ONE factor and one sweep pair per candidate (csrc/jg_dc_pair.hpp).
       rows       (k0, k1): only the pairs whose FIRST branch is candidate position k0 .. k1 - 1 (what one rank of a sharded screen takes: shard())
       block      candidate rows per device call (bounds the memory of a call; default: 256 MiB of dense result); the result does not depend on it
       capacity / islandCapacity   most records / islanding pairs kept (the first by (k, l); the totals stay exact)
-      budget     bytes the kept sensitivities may take (default: 0.8 of the free device memory); JGridError code 5 with the sizes when they do not fit"""
+      budget     bytes the kept sensitivities may take (default: 0.8 of the free device memory); JGridError code 5 with the sizes when they do not fit
+      islands    "skip": a pair that holds a bridge is singular (status 3: `islanding`, NaN loading).  "shed": a candidate the graph calls a bridge
+                 is shed as setOutages_(..., islands="shed") sheds a lane's -- the buses behind it leave with their injections, the pair's other
+                 branch (where it stays) is solved on what is left, the worst loading, its branch and the count cover the branches that stay --
+                 and the pair is screened like any other (no 2 x 2 solve: csrc/jg_dc_pair.hpp has the table).  The default candidates are then
+                 shedCandidates(system), the result names what was shed (DcPairScreen: shed .. shedFlow, recordShed), and `islanding` keeps the
+                 joint cuts of two non-bridges and the pairs with a singular non-bridge.  A pair of two non-bridges is bitwise what it is without
+                 the keyword.  With dense=True the determinant of a pair with a bridge is the denominator of the branch that is solved (1: none)"""
     own = isinstance(analysis_or_system, PowerSystem)
     system = analysis_or_system if own else analysis_or_system.system
+    mode = _island_mode(islands)                                        # refused on the host, before the device is touched
     if rating is None:
         raise ValueError("dcPairScreen: rating (per branch, per unit of active power) is needed")
     if not threshold >= 0:
         raise ValueError("dcPairScreen: threshold >= 0")
     if own and system.model.dc.nodalMatrix is None:
         dcModel_(system)
-    cand, mon, rating = _pair_lists(system, candidates, monitored, rating)
+    cand, mon, rating = _pair_lists(system, candidates, monitored, rating, shed=bool(mode))
     nk = int(cand.size)
     k0, k1, step = _screen_rows("dcPairScreen", nk - 1, rows, block, PAIR_BLOCK_BYTES, (nk + 63) // 64 * 64 * (24 if dense else 16))     # (the last candidate is the first branch of no pair)
     with _screen_analysis(analysis_or_system, "pair", rating, device) as (an, L):
         info = np.zeros(8)
+        _lib.check(L.jg_dc_pair_set_island_mode(an._h, mode))
         _lib.check(L.jg_dc_pair_build(an._h, nk, cand, int(mon.size), _ptr(mon), int(budget or 0), info))
         rec = np.zeros((max(int(capacity), 0), 5))
         isl = np.zeros((max(int(islandCapacity), 0), 2), dtype=np.int64)
@@ -477,6 +511,10 @@ def dcPairScreen(analysis_or_system, candidates=None, monitored=None, rating=Non
                 a = np.vstack([a, np.zeros((1, nk), dtype=a.dtype)])
                 a = (a + a.T).astype(a.dtype)
             setattr(res, name, a)
+        res.shed = res.shedBuses = res.shedM = res.shedFlow = res.recordShed = None
+        if mode:
+            res.shed, res.shedBuses, res.shedM, res.shedFlow = _shed_block(L, an, "pair", 0, nk, ())
+            res.recordShed = pairShed(system, res.records[:, :2])
         return res
 
 
