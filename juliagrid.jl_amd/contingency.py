@@ -10,12 +10,17 @@ Scenarios shard across GPUs contiguously with no communication (see shard()).
 """
 from __future__ import annotations
 
+import queue
+import threading
+from types import SimpleNamespace as NS
+
 import numpy as np
 
-import threading
-
 from . import _lib
-from .powerflow import AcPowerFlow, BaseCase, newtonRaphson, powerFlow_, setOutage_, setOutages_, startFromBase_, setFirstIteration_, _push_voltage
+from .dcpowerflow import dcContingencyAnalysis
+from .pipeline import OrderedRun, gatherBlocks
+from .powerflow import (AcPowerFlow, BaseCase, fastNewtonRaphsonBX, fastNewtonRaphsonXB, newtonRaphson, powerFlow_, powerFlowLimits_, setBusType_, setInjection_,
+                        setOutages_, startFromBase_, setFirstIteration_, _push_voltage, _upload_branches)
 from .system import PowerSystem
 
 
@@ -69,7 +74,6 @@ def islandTable(system: PowerSystem):
       side [nb]      +1 / -1: the from / to end of the bridge stays on the slack's side; 0: not a bridge
       m [nb]         that end (1-based bus, 0: not a bridge)
       order [n]      the buses by preorder number (reached buses only): order[lo[k]:hi[k] + 1] are the buses that leave"""
-    from types import SimpleNamespace as NS
     n, nb, lay = system.bus.number, system.branch.number, system.branch.layout
     pre = np.zeros(n, dtype=np.int32)
     lo, hi, side = (np.zeros(nb, dtype=np.int32) for _ in range(3))
@@ -150,12 +154,10 @@ def contingencyAnalysis(system: PowerSystem, labels, device: int = 0, method: st
     if method != "dc" and any(isinstance(lab, (tuple, list)) for lab in labels):
         raise ValueError("contingencyAnalysis: a tuple (k, l) of two outages is a DC scenario (method='dc'); nr / bx / xb take one branch per scenario")
     if method == "dc":                                          # the pre-filter of a screen: solved on return, one factor for the whole batch (dcpowerflow.py)
-        from .dcpowerflow import dcContingencyAnalysis
         return dcContingencyAnalysis(system, labels, device=device, rating=rating, islands=islands)
     if reactiveLimit and (method != "nr" or len(labels) < 2):
         raise ValueError("contingencyAnalysis: reactiveLimit needs method='nr' and two or more scenarios")
     if method in ("bx", "xb"):
-        from .powerflow import fastNewtonRaphsonBX, fastNewtonRaphsonXB
         an = (fastNewtonRaphsonBX if method == "bx" else fastNewtonRaphsonXB)(system, batch=len(labels), device=device, max_patch=4)
     elif method == "nr":
         an = newtonRaphson(system, batch=len(labels), device=device, max_patch=4)
@@ -163,7 +165,6 @@ def contingencyAnalysis(system: PowerSystem, labels, device: int = 0, method: st
         raise ValueError("method: nr | bx | xb | dc")
     setOutages_(an, [int(lab) if lab else 0 for lab in labels])
     if reactiveLimit:
-        from .powerflow import powerFlowLimits_
         if start is not None:
             _push_voltage(an, *start)
         powerFlowLimits_(an, int(reactiveLimit), iteration=iteration, tolerance=tolerance)
@@ -175,11 +176,120 @@ class _Pool:
 
     def __init__(self, handle):
         self.handle = handle
-        self.fill = 0
-        self.routes = []                    # (job, scenario numbers in the job's batch, first lane in the pool)
         self.idle = threading.Event()
-        self.idle.set()
+        self.clear()
+
+    def clear(self):
+        self.routes = []                    # (job, scenario numbers in the job's batch, first lane in the pool)
+        self.fill = 0
         self.queued = False
+        self.idle.set()
+
+
+class _StragglerPools:
+    """The two pool handles of a ContingencyPipeline, filled in turn, and the thread that finishes what they hold (one thread: the pools' turns run one
+    after the other).  A worker pauses its batch (solve: run_defer), moves the scenarios that are left into the filling pool (take_lanes) and goes on; the
+    pool thread resumes a flushed pool and writes each straggler's iteration count, status and record row back to its job.  Joins one OrderedRun between
+    start() and stop().  Handles are used by duck type: run_defer, finish, take_lanes, resume, pack_rows_device, screen_rows_device, batch, _outage_labels."""
+
+    def __init__(self, pools, defer_at: int):
+        self.pools, self.defer_at = pools, int(defer_at)
+        self.lock = threading.Lock()
+
+    def start(self, run, iteration: int, tolerance: float, record=None, summary: bool = False):
+        for p in self.pools:
+            p.clear()                       # a run that failed leaves its routes and fill behind: they must not leak into this one
+        self.run, self.iteration, self.tolerance, self.record, self.summary = run, iteration, tolerance, record, summary
+        self.filling = 0                    # index of the pool that is being filled
+        self.pending = {}                   # job -> Event of the jobs that handed scenarios to a pool
+        self.flush_q = queue.Queue()
+        self.thread = threading.Thread(target=self._serve, daemon=True)
+        self.thread.start()
+
+    def stop(self):
+        self.flush_q.put(None)
+        self.thread.join()
+
+    def release(self):
+        """The run has failed: nobody keeps waiting for a pool."""
+        for ev in list(self.pending.values()):
+            ev.set()
+        for p in self.pools:
+            p.idle.set()
+
+    def defers(self, j: int) -> bool:
+        """The LAST job of a handle finishes its own stragglers in lockstep: the hand-off pays when it frees the handle for its next job; at the end of a
+        run the pools' turns (one thread resumes them one after the other) would only queue the tails of the batches that end together (round 6:
+        a rank of the 8-GPU run at the driver's K = 20 -- two 640-lane batches, both the last of their handle)."""
+        return j + self.run.nh < self.run.nj
+
+    def _submit(self, p):                   # under `lock`
+        if p.fill > 0 and not p.queued:
+            p.queued = True
+            p.idle.clear()
+            self.flush_q.put(p)
+
+    def flush_filling(self):
+        with self.lock:
+            self._submit(self.pools[self.filling])
+
+    def solve(self, an, j: int) -> bool:
+        """Job j on its own handle `an` until at most defer_at scenarios are active; those go on in a pool.  False: the run has failed meanwhile."""
+        left = an.run_defer(self.iteration, self.tolerance, self.defer_at)
+        if left > 0:
+            with self.lock:
+                p = self.pools[self.filling]
+                if p.queued or p.fill + left > p.handle.batch:
+                    self._submit(p)
+                    self.filling ^= 1
+                    p = self.pools[self.filling]
+                p.idle.wait()               # the other pool has long finished in a steady pipeline
+                if self.run.failed:
+                    return False
+                home = p.handle.take_lanes(an, p.fill)
+                p.handle._outage_labels[p.fill:p.fill + home.size] = an._outage_labels[home]     # (the screen summary leaves the branch that is out aside)
+                self.pending[j] = threading.Event()
+                p.routes.append((j, home, p.fill))
+                p.fill += home.size
+        an.finish()
+        return True
+
+    def complete(self, j: int):
+        """On the caller's thread, before job j is delivered: its stragglers are back."""
+        ev = self.pending.get(j)
+        if ev is None:
+            return
+        run = self.run
+        if j == run.nj - 1 or all(run.solved(i) for i in range(j, run.nj)):
+            self.flush_filling()            # nobody is left to fill the pool
+        while not ev.wait(0.05):
+            if run.failed:
+                break
+            if all(run.solved(i) for i in range(run.nj)):
+                self.flush_filling()
+
+    def _serve(self):
+        try:
+            while True:
+                p = self.flush_q.get()
+                if p is None:
+                    return
+                it, st = p.handle.resume(p.fill, self.iteration, self.tolerance)
+                for j, home, off in p.routes:
+                    result = self.run.wait_solved(j)      # the batch's own record / arrays are written first
+                    if result is None:
+                        break
+                    result[0][home] = it[off:off + home.size]
+                    result[1][home] = st[off:off + home.size]
+                    if self.record is not None:
+                        if self.summary:
+                            p.handle.screen_rows_device(self.record(j), off, home)
+                        else:
+                            p.handle.pack_rows_device(self.record(j), off, home)
+                    self.pending[j].set()
+                p.clear()                   # no lock: a worker may hold it while it waits for this pool; _submit() sees either queued (skips) or an empty pool (skips)
+        except BaseException as e:
+            self.run.fail(e)
 
 
 class ContingencyPipeline:
@@ -227,6 +337,7 @@ class ContingencyPipeline:
             # beside batches of 128 / 192 would run the one-lane-group plan; jg_nr_move_lanes now refuses a hand-off between different plans)
             lanes = max(lanes, 256) if -(-self.batch // 64) * 64 >= 256 else min(max(lanes, 128), 192)
             self.pools = [_Pool(newtonRaphson(system, batch=lanes, device=device, max_patch=4)) for _ in range(2)]
+        self._stragglers = _StragglerPools(self.pools, self.defer_at) if self.pools else None
         if len(self.handles) + len(self.pools) > 1:      # several batches share the GPU: the top launches leave room for the others' workgroups
             for an in self.handles + [p.handle for p in self.pools]:
                 _lib.check(_lib.lib().jg_nr_set_shared(an._h, 1))
@@ -267,11 +378,10 @@ class ContingencyPipeline:
         if self.base is not None:
             self.base.close()
             self.base = None
-        self.handles, self.pools = [], []
+        self.handles, self.pools, self._stragglers = [], [], None
 
     def setRating(self, rating):
         """Branch ratings (pu of apparent power, 0 = no limit) of the screen summaries (`run(..., summary=True)`), on every handle."""
-        from .powerflow import _upload_branches
         r = None if rating is None else np.ascontiguousarray(np.asarray(rating, dtype=np.float64))
         if r is not None and r.shape != (self.system.branch.number,):
             raise ValueError("rating: one value per branch")
@@ -294,185 +404,78 @@ class ContingencyPipeline:
         setRating's limits, largest flow, voltage extremes, iterations, status), reduced on the device by the handle that finished the scenario:
         what a sharded screen gathers is 80 bytes per scenario, not 16 n + 16."""
         jobs = list(jobs)
-        nj = len(jobs)
-        results = [None] * nj
-        main_done = [threading.Event() for _ in jobs]
-        pool_done = [None] * nj                                   # Event of the jobs that handed scenarios to a pool
-        released = [threading.Event() for _ in jobs]              # the handle of job j may start job j + nh
-        delivered = [threading.Event() for _ in jobs]             # on_done(j) has returned
-        nh = len(self.handles)
-        use_pool = bool(self.pools)
-        if use_pool and on_done is not None and record is None:
+        pools = self._stragglers
+        if pools is not None and on_done is not None and record is None:
             raise ValueError("a pipeline with a straggler pool delivers results through `record`")
         ring = int(records) if (record is not None and records) else 0
-        errors = []
-        lock = threading.Lock()
-        state = {"fill": 0}                                       # index of the pool that is being filled
-        import queue
-        flush_q = queue.Queue()
+        run = OrderedRun(self.handles, len(jobs), hold=self._hold(pools is not None, record, on_done), ring=ring)
 
-        def submit(p):                                            # under `lock`
-            if p.fill > 0 and not p.queued:
-                p.queued = True
-                p.idle.clear()
-                flush_q.put(p)
+        def solve(k, j):
+            return self._solve(self.handles[k], j, jobs[j], iteration, tolerance, fetch, record, summary)
 
-        def flush_filling():
-            with lock:
-                submit(self.pools[state["fill"]])
-
-        def pool_worker():
-            try:
-                while True:
-                    p = flush_q.get()
-                    if p is None:
-                        return
-                    it, st = p.handle.resume(p.fill, iteration, tolerance)
-                    for j, home, off in p.routes:
-                        main_done[j].wait()                       # the batch's own record / arrays are written first
-                        if errors:
-                            break
-                        results[j][0][home] = it[off:off + home.size]
-                        results[j][1][home] = st[off:off + home.size]
-                        if record is not None:
-                            if summary:
-                                p.handle.screen_rows_device(record(j), off, home)
-                            else:
-                                p.handle.pack_rows_device(record(j), off, home)
-                        pool_done[j].set()
-                    p.routes = []                                 # no lock: a worker may hold it while it waits for this pool; submit() sees
-                    p.fill = 0                                    # either queued (skips) or an empty pool (skips)
-                    p.queued = False
-                    p.idle.set()
-            except BaseException as e:
-                errors.append(e)
-                for ev in main_done + delivered + [x for x in pool_done if x is not None]:
-                    ev.set()
-                for p in self.pools:
-                    p.idle.set()
-
-        def worker(k):
-            try:
-                for j in range(k, nj, nh):
-                    if j - nh >= 0:
-                        released[j - nh].wait()
-                    if ring and j - ring >= 0 and not delivered[j - ring].is_set():
-                        if use_pool:
-                            flush_filling()                       # what the caller is waiting for may sit in the pool that is filling
-                        delivered[j - ring].wait()
-                    if errors:
-                        return
-                    an = self.handles[k]
-                    job = jobs[j]
-                    if getattr(an, "_limits_applied", False):     # the last job's reactive limits: create-time types and injections again
-                        from .powerflow import setBusType_, setInjection_
-                        setBusType_(an, None)
-                        an._lane_types = False
-                        if an._injection is not None:
-                            setInjection_(an, *an._injection)
-                        else:
-                            setInjection_(an)
-                        an._limits_applied = False
-                    if isinstance(job, dict):                     # a Monte-Carlo job: per-scenario injections (load / generation variations), outages optional
-                        if job.get("labels") is not None:
-                            labels = [int(x) if x else 0 for x in job["labels"]]
-                            setOutages_(an, labels + [0] * (self.batch - len(labels)))
-                        if job.get("active") is not None or job.get("reactive") is not None:
-                            from .powerflow import setInjection_
-                            setInjection_(an, job.get("active"), job.get("reactive"))
-                    elif job is not None:
-                        labels = [int(x) if x else 0 for x in job]
-                        setOutages_(an, labels + [0] * (self.batch - len(labels)))
-                    if self.base is not None:
-                        startFromBase_(an)                        # device-side broadcast of the base state; the run takes its first iteration on the shared factor when it can
-                    else:
-                        an.restore_voltage()
-                    # the LAST job of a handle finishes its own stragglers in lockstep: the hand-off pays when it frees the handle for its next job; at the end of a
-                    # run the pools' turns (one worker resumes them one after the other) would only queue the tails of the batches that end together (round 6:
-                    # a rank of the 8-GPU run at the driver's K = 20 -- two 640-lane batches, both the last of their handle)
-                    if use_pool and j + nh < nj:
-                        left = an.run_defer(iteration, tolerance, self.defer_at)
-                        if left > 0:
-                            with lock:
-                                p = self.pools[state["fill"]]
-                                if p.queued or p.fill + left > p.handle.batch:
-                                    submit(p)
-                                    state["fill"] ^= 1
-                                    p = self.pools[state["fill"]]
-                                p.idle.wait()                     # the other pool has long finished in a steady pipeline
-                                if errors:
-                                    return
-                                home = p.handle.take_lanes(an, p.fill)
-                                p.handle._outage_labels[p.fill:p.fill + home.size] = an._outage_labels[home]     # (the screen summary leaves the branch that is out aside)
-                                pool_done[j] = threading.Event()
-                                p.routes.append((j, home, p.fill))
-                                p.fill += home.size
-                        an.finish()
-                        if fetch:
-                            an._pull_voltage()
-                    elif self.reactive_limit:
-                        from .powerflow import powerFlowLimits_
-                        an._limits_applied = True
-                        powerFlowLimits_(an, self.reactive_limit, iteration=iteration, tolerance=tolerance, fetch=fetch)
-                    else:
-                        powerFlow_(an, iteration=iteration, tolerance=tolerance, fetch=fetch)
-                    results[j] = (np.array(an.method.iteration), np.array(an.status))
-                    if record is not None:
-                        if summary:
-                            an.screen_device(record(j))
-                        else:
-                            an.pack_results_device(record(j))
-                    main_done[j].set()
-                    if use_pool or record is not None and on_done is None:
-                        released[j].set()                         # nothing of this job lives in the handle any more
-                if use_pool:
-                    flush_filling()                               # this worker adds nothing more
-            except BaseException as e:                             # surface in the caller, never hang it
-                errors.append(e)
-                for ev in main_done + delivered + released + [x for x in pool_done if x is not None]:
-                    ev.set()
-                for p in self.pools:
-                    p.idle.set()
-
-        threads = [threading.Thread(target=worker, args=(k,), daemon=True) for k in range(nh)]
-        pthread = threading.Thread(target=pool_worker, daemon=True) if use_pool else None
-        if pthread:
-            pthread.start()
-        for t in threads:
-            t.start()
+        if pools is None:
+            return run.run(solve, on_done)
+        pools.start(run, iteration, tolerance, record, summary)
         try:
-            for j in range(nj):
-                main_done[j].wait()
-                if not errors and pool_done[j] is not None:
-                    if j == nj - 1 or all(main_done[i].is_set() for i in range(j, nj)):
-                        flush_filling()                           # nobody is left to fill the pool
-                    while not pool_done[j].wait(0.05):
-                        if errors:
-                            break
-                        if all(ev.is_set() for ev in main_done):
-                            flush_filling()
-                if errors:
-                    break
-                if on_done is not None:
-                    on_done(j, self.handles[j % nh])
-                delivered[j].set()
-                released[j].set()
-        except BaseException as e:                                 # the caller's own on_done failed: the workers must not wait for deliveries that never come
-            errors.insert(0, e)
+            # (ring wait) what the caller is waiting for may sit in the pool that is filling
+            return run.run(solve, on_done, before_ring_wait=pools.flush_filling, complete=pools.complete, on_fail=pools.release)
         finally:
-            if errors:
-                for ev in released + delivered + [x for x in pool_done if x is not None]:
-                    ev.set()
-                for p in self.pools:
-                    p.idle.set()
-            for t in threads:
-                t.join()
-            if pthread:
-                flush_q.put(None)
-                pthread.join()
-        if errors:
-            raise errors[0]
-        return results
+            pools.stop()
+
+    @staticmethod
+    def _hold(pool: bool, record, on_done) -> bool:
+        """Whether the handle of job j waits for the delivery of j before it starts job j + nh.  Not with a pool (results are delivered through `record`:
+        nothing of a solved job lives in its handle any more), and not with a record nobody is called for; otherwise on_done, or the caller after run(),
+        may still read the handle."""
+        return not (pool or (record is not None and on_done is None))
+
+    def _prepare(self, an, job):
+        """The handle as job `job` needs it: create-time types and injections, the job's outages / injections, the start point."""
+        if getattr(an, "_limits_applied", False):     # the last job's reactive limits: create-time types and injections again
+            setBusType_(an, None)
+            an._lane_types = False
+            if an._injection is not None:
+                setInjection_(an, *an._injection)
+            else:
+                setInjection_(an)
+            an._limits_applied = False
+        if isinstance(job, dict):                     # a Monte-Carlo job: per-scenario injections (load / generation variations), outages optional
+            if job.get("labels") is not None:
+                labels = [int(x) if x else 0 for x in job["labels"]]
+                setOutages_(an, labels + [0] * (self.batch - len(labels)))
+            if job.get("active") is not None or job.get("reactive") is not None:
+                setInjection_(an, job.get("active"), job.get("reactive"))
+        elif job is not None:
+            labels = [int(x) if x else 0 for x in job]
+            setOutages_(an, labels + [0] * (self.batch - len(labels)))
+        if self.base is not None:
+            startFromBase_(an)                        # device-side broadcast of the base state; the run takes its first iteration on the shared factor when it can
+        else:
+            an.restore_voltage()
+
+    def _solve(self, an, j, job, iteration, tolerance, fetch, record, summary):
+        """Job j on handle `an` (a worker's thread): (iterations, status) per scenario, and the job's record written."""
+        pools = self._stragglers
+        self._prepare(an, job)
+        if pools is not None and pools.defers(j):
+            if not pools.solve(an, j):
+                return None
+            if fetch:
+                an._pull_voltage()
+        elif self.reactive_limit:
+            an._limits_applied = True
+            powerFlowLimits_(an, self.reactive_limit, iteration=iteration, tolerance=tolerance, fetch=fetch)
+        else:
+            powerFlow_(an, iteration=iteration, tolerance=tolerance, fetch=fetch)
+        result = (np.array(an.method.iteration), np.array(an.status))
+        if record is not None:
+            if summary:
+                an.screen_device(record(j))
+            else:
+                an.pack_results_device(record(j))
+        if pools is not None and not pools.defers(j):
+            pools.flush_filling()                     # this handle adds nothing more
+        return result
 
     def screen(self, labels, iteration: int = 20, tolerance: float = 1e-8):
         """N-1 screen of an arbitrary list of branch labels: (iterations, status) per label, in order."""
@@ -490,19 +493,13 @@ def gatherResults(dist, packed):
     scenarios and receives the global block in scenario order.  `dist` is an initialised torch.distributed module (backend
     "nccl" = RCCL over xGMI on the GPU box, "gloo" in CPU tests); the tensor must live on the backend's device.
     Returns (iterations, status, magnitude, angle) views of the gathered block."""
-    import torch
-    world = dist.get_world_size()
-    packed = packed.contiguous()
-    g = torch.empty((world * packed.shape[0], packed.shape[1]), dtype=packed.dtype, device=packed.device)
-    dist.all_gather_into_tensor(g, packed)
-    return unpackResults(g)
+    return unpackResults(gatherBlocks(dist, packed))
 
 
 def gatherResultsDevice(an: AcPowerFlow, comm, out_ptr: int):
     """The same gather through the C ABI alone (jg_nr_allgather_results: pack + ncclAllGather of RCCL on the handle's stream): `comm` is a
     juliagrid.jl_amd._lib.Comm, `out_ptr` a device pointer to [world x batch][2 n + 2] doubles owned by the caller.  Every rank calls
     it with the same batch; on return the record of the whole screen is in scenario order on every rank."""
-    from . import _lib
     _lib.check(_lib.lib().jg_nr_allgather_results(an._h, comm.h, _lib.VP(int(out_ptr))))
 
 

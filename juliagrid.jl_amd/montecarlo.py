@@ -9,12 +9,11 @@ ContingencyPipeline is for the power flow).
 """
 from __future__ import annotations
 
-import threading
-
 import numpy as np
 
 from . import _lib
 from .measurement import Measurement
+from .pipeline import OrderedRun, gatherBlocks
 from .stateestimation import AcStateEstimation, drawNoise_, gaussNewton, setNoise_, stateEstimation_
 
 RECORD_TAIL = 3         # iterations | status | objective behind magnitude[n] | angle[n]
@@ -54,73 +53,39 @@ class MonteCarloPipeline:
         on_done(job, .) is called; the caller owns a ring of `records` buffers (job j + records is not written before on_done(j) has returned).
         Returns per-job (iterations, status) arrays."""
         jobs = list(jobs)
-        nj, nh = len(jobs), len(self.handles)
-        results = [None] * nj
-        done = [threading.Event() for _ in jobs]
-        delivered = [threading.Event() for _ in jobs]
         ring = int(records) if (record is not None and records) else 0
-        errors = []
+        run = OrderedRun(self.handles, len(jobs), hold=self._hold(record, on_done), ring=ring)
+        return run.run(lambda k, j: self._solve(self.handles[k], j, jobs[j], iteration, tolerance, record), on_done)
 
-        def worker(k):
-            try:
-                for j in range(k, nj, nh):
-                    if j - nh >= 0 and on_done is not None and record is None:
-                        delivered[j - nh].wait()                  # without a record the results live in the handle until the caller has seen them
-                    if ring and j - ring >= 0:
-                        delivered[j - ring].wait()
-                    if errors:
-                        return
-                    h = self.handles[k]
-                    if jobs[j] is not None:
-                        seed, first = (jobs[j] if isinstance(jobs[j], (tuple, list)) else (jobs[j], 0))
-                        if self.host_noise:
-                            setNoise_(h, np.random.Generator(np.random.PCG64(int(seed))), scale=self.scale)
-                        else:
-                            drawNoise_(h, int(seed), scale=self.scale, first=int(first))
-                    h.restore_voltage()
-                    stateEstimation_(h, iteration=iteration, tolerance=tolerance, fetch=False)
-                    results[j] = (np.array(h.method.iteration), np.array(h.status))
-                    if record is not None:
-                        h.pack_results_device(record(j))
-                    done[j].set()
-            except BaseException as e:                             # surface in the caller, never hang it
-                errors.append(e)
-                for ev in done + delivered:
-                    ev.set()
+    @staticmethod
+    def _hold(record, on_done) -> bool:
+        """Whether the handle of job j waits for the delivery of j before it starts job j + nh: without a record the results live in the handle until the
+        caller's on_done has seen them.  (Not ContingencyPipeline's rule: with a record AND an on_done this handle goes on, and with neither it goes on too.)"""
+        return on_done is not None and record is None
 
-        threads = [threading.Thread(target=worker, args=(k,), daemon=True) for k in range(nh)]
-        for t in threads:
-            t.start()
-        try:
-            for j in range(nj):
-                done[j].wait()
-                if errors:
-                    break
-                if on_done is not None:
-                    on_done(j, self.handles[j % nh])
-                delivered[j].set()
-        except BaseException as e:                                 # the caller's own on_done failed: the workers must not wait for deliveries that never come
-            errors.insert(0, e)
-        finally:
-            if errors:
-                for ev in delivered:
-                    ev.set()
-            for t in threads:
-                t.join()
-        if errors:
-            raise errors[0]
-        return results
+    def _prepare(self, h, job):
+        if job is not None:
+            seed, first = (job if isinstance(job, (tuple, list)) else (job, 0))
+            if self.host_noise:
+                setNoise_(h, np.random.Generator(np.random.PCG64(int(seed))), scale=self.scale)
+            else:
+                drawNoise_(h, int(seed), scale=self.scale, first=int(first))
+        h.restore_voltage()
+
+    def _solve(self, h, j, job, iteration, tolerance, record):
+        """Job j on handle `h` (a worker's thread): (iterations, status) per realisation, and the job's record written."""
+        self._prepare(h, job)
+        stateEstimation_(h, iteration=iteration, tolerance=tolerance, fetch=False)
+        result = (np.array(h.method.iteration), np.array(h.status))
+        if record is not None:
+            h.pack_results_device(record(j))
+        return result
 
 
 def gatherEstimates(dist, packed):
     """Final gather of a sharded Monte-Carlo batch: ONE collective.  `packed` is this rank's [realisations, 2 n + 3] record
     (AcStateEstimation.pack_results_device); returns (iterations, status, objective, magnitude, angle) of the global block in realisation order."""
-    import torch
-    world = dist.get_world_size()
-    packed = packed.contiguous()
-    g = torch.empty((world * packed.shape[0], packed.shape[1]), dtype=packed.dtype, device=packed.device)
-    dist.all_gather_into_tensor(g, packed)
-    return unpackEstimates(g)
+    return unpackEstimates(gatherBlocks(dist, packed))
 
 
 def gatherEstimatesDevice(an: AcStateEstimation, comm, out_ptr: int):
