@@ -37,7 +37,7 @@ module JuliaGridHIP
 
 using JuliaGrid
 using SparseArrays
-import JuliaGrid: newtonRaphson, fastNewtonRaphsonBX, fastNewtonRaphsonXB, gaussNewton, pmuStateEstimation, mismatch!, solve!, increment!,
+import JuliaGrid: newtonRaphson, fastNewtonRaphsonBX, fastNewtonRaphsonXB, gaussSeidel, gaussNewton, pmuStateEstimation, mismatch!, solve!, increment!,
                   powerFlow!, stateEstimation!, setInitialPoint!, power!, current!, chiTest,
                   updateBus!, updateBranch!, updateGenerator!, reactiveLimit!, adjustAngle!,
                   updateVoltmeter!, updateAmmeter!, updateWattmeter!, updateVarmeter!, updatePmu!,
@@ -1706,10 +1706,172 @@ function timeKernel(b::DcStateEstimationBatch, kernel::Int, reps::Int = 20)
     return ms
 end
 
+# ---- Gauss-Seidel power flow, one scenario per lane (jgrid.h: jg_gs_*; csrc/jg_gs.hip) ---------------------------------------------------
+# gaussSeidel / mismatch! / solve! / powerFlow! (src/powerFlow/acPowerFlow.jl:563-619, 732-764, 985-1041, 1389-1433) for `batch` scenarios of one grid: a
+# sweep is sequential over the buses of a scenario, so a lane runs the reference's update sequence unchanged and a powerFlow! is ONE launch.  The C
+# handle is an Int64 token.  Matrices are [bus, batch].
+"""
+    gaussSeidel(system, HIP; batch = 1, device = 0) -> GaussSeidelBatch
+
+`magnitude`, `angle`, `voltage` (the reference's complex `method.voltage`), `pq`, `pv`, `iteration` and `status` per scenario (0 converged, 1 the
+iteration limit, 3 a mismatch that is not finite).  `power!` / `current!` / `reactiveLimit!` are not offered: `setInitialPoint!(newtonRaphson(system, HIP), b)`.
+"""
+mutable struct GaussSeidelBatch
+    token::Int64
+    system::PowerSystem
+    batch::Int64
+    magnitude::Matrix{Float64}
+    angle::Matrix{Float64}
+    voltage::Matrix{ComplexF64}
+    pq::Vector{Int64}
+    pv::Vector{Int64}
+    iteration::Vector{Int32}
+    status::Vector{Int32}
+    topology::Int64                                   # the signature of acPowerFlow.jl:611-614
+    type::Int64
+    outages::Vector{Int64}
+end
+"generator.voltage.magnitude of the first in-service generator of every bus that has one (acPowerFlow.jl:1032-1033), 0 elsewhere"
+function gsSetpoint(system::PowerSystem)
+    g = zeros(Float64, system.bus.number)
+    for (i, gens) in system.bus.supply.generator
+        g[i] = system.generator.voltage.magnitude[gens[1]]
+    end
+    return g
+end
+function gaussSeidel(system::PowerSystem, ::Type{HIP}; batch::Int64 = 1, device::Int64 = 0)
+    JuliaGrid.checkSlackBus(system)
+    JuliaGrid.model!(system, system.model.ac)
+    magnitude, angle = JuliaGrid.initializeACPowerFlow(system)
+    ac, bus = system.model.ac, system.bus
+    token = Ref{Int64}(0)
+    yt = collect(reinterpret(Float64, ac.nodalMatrixTranspose.nzval))
+    check(ccall((:jg_gs_create, lib), Cint, (Ref{Int64}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int8}, Int64, Ptr{Float64}, Int64, Cint),
+        token, bus.number, ac.nodalMatrix.colptr, ac.nodalMatrix.rowval, yt, bus.layout.type, bus.layout.slack, gsSetpoint(system), batch, device))
+    b = GaussSeidelBatch(token[], system, batch, zeros(bus.number, batch), zeros(bus.number, batch), zeros(ComplexF64, bus.number, batch),
+        findall(==(1), bus.layout.type), findall(==(2), bus.layout.type), zeros(Int32, batch), zeros(Int32, batch),
+        copy(system.model.revision.topology), copy(system.model.revision.type), zeros(Int64, batch))
+    finalizer(x -> (x.token != 0 && ccall((:jg_gs_destroy, lib), Cvoid, (Int64,), x.token); x.token = 0), b)
+    pushInjection!(b)
+    check(ccall((:jg_gs_set_voltage, lib), Cint, (Int64, Ptr{Float64}, Ptr{Float64}, Int64), b.token, magnitude, angle, 0))
+    pullVoltage!(b)
+    return b
+end
+"bus.supply - bus.demand of the system into every lane"
+function pushInjection!(b::GaussSeidelBatch)
+    bus = b.system.bus
+    check(ccall((:jg_gs_set_injection, lib), Cint, (Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Int64),
+        b.token, 0, b.batch, bus.supply.active .- bus.demand.active, bus.supply.reactive .- bus.demand.reactive, 0))
+end
+"""
+    setInjections!(b, active, reactive; lane0 = 0)
+
+Lanes lane0 .. lane0 + size(active, 2) - 1 (0-based) get net injections supply - demand of their own, [bus, count] each.
+"""
+function setInjections!(b::GaussSeidelBatch, active::Matrix{Float64}, reactive::Matrix{Float64}; lane0::Int64 = 0)
+    check(ccall((:jg_gs_set_injection, lib), Cint, (Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Int64),
+        b.token, lane0, size(active, 2), active, reactive, size(active, 1)))
+end
+function pullVoltage!(b::GaussSeidelBatch)
+    re, im = similar(b.magnitude), similar(b.magnitude)
+    check(ccall((:jg_gs_get_voltage, lib), Cint, (Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), b.token, b.magnitude, b.angle, re, im))
+    b.voltage .= complex.(re, im)
+    return nothing
+end
+"the system's nodal matrix again (updateBranch! / updateBus!(shunt) on the system, branch.jl:473-475); the lanes' outages follow the new values"
+function pushYbus!(b::GaussSeidelBatch)
+    yt = collect(reinterpret(Float64, b.system.model.ac.nodalMatrixTranspose.nzval))
+    check(ccall((:jg_gs_set_ybus, lib), Cint, (Int64, Ptr{Float64}), b.token, yt))
+    any(!=(0), b.outages) && setOutages!(b, b.outages)
+    return nothing
+end
+"scenario `lane0 + s` (0-based lanes) loses branch `labels[s]` (index, 0 = none): 4 positions in the TRANSPOSED values and 4 complex deltas per lane"
+function setOutages!(b::GaussSeidelBatch, labels::Vector{Int64}; lane0::Int64 = 0)
+    ac, br = b.system.model.ac, b.system.branch
+    Y = ac.nodalMatrix
+    pos(r, c) = first(searchsorted(view(Y.rowval, Y.colptr[c]:(Y.colptr[c + 1] - 1)), r)) + Y.colptr[c] - 1
+    position = zeros(Int64, 4, length(labels))
+    delta = zeros(ComplexF64, 4, length(labels))
+    for (s, k) in enumerate(labels)
+        k == 0 && continue
+        i, j = br.layout.from[k], br.layout.to[k]
+        position[:, s] = [pos(i, i), pos(j, j), pos(j, i), pos(i, j)]        # Ybus entry (i, j) sits where nodalMatrix holds (j, i)
+        delta[:, s] = -[ac.nodalFromFrom[k], ac.nodalToTo[k], ac.nodalFromTo[k], ac.nodalToFrom[k]]
+    end
+    check(ccall((:jg_gs_set_outages, lib), Cint, (Int64, Int64, Int64, Ptr{Int64}, Ptr{Float64}),
+        b.token, lane0, length(labels), position, collect(reinterpret(Float64, vec(delta)))))
+    b.outages[(lane0 + 1):(lane0 + length(labels))] .= labels
+    return nothing
+end
+function staleCheck(b::GaussSeidelBatch)                       # acPowerFlow.jl:993-995
+    rev = b.system.model.revision
+    if rev.topology != b.topology || rev.type != b.type
+        JuliaGrid.errorTypeConversion()
+    end
+end
+"mismatch!(analysis) of every scenario (acPowerFlow.jl:732-764) -> (stopP, stopQ), [batch] each"
+function mismatch!(b::GaussSeidelBatch)
+    p, q = zeros(Float64, b.batch), zeros(Float64, b.batch)
+    check(ccall((:jg_gs_mismatch, lib), Cint, (Int64, Ptr{Float64}, Ptr{Float64}), b.token, p, q))
+    return p, q
+end
+"the maxima of the last mismatch! / of the last check of powerFlow!"
+function lastMismatch(b::GaussSeidelBatch)
+    p, q = zeros(Float64, b.batch), zeros(Float64, b.batch)
+    check(ccall((:jg_gs_get_mismatch, lib), Cint, (Int64, Ptr{Float64}, Ptr{Float64}), b.token, p, q))
+    return p, q
+end
+"solve!(analysis) of every scenario: one sweep (acPowerFlow.jl:985-1041)"
+function solve!(b::GaussSeidelBatch)
+    staleCheck(b)
+    check(ccall((:jg_gs_solve, lib), Cint, (Int64,), b.token))
+    b.iteration .+= 1
+    pullVoltage!(b)
+    return nothing
+end
+"powerFlow!(analysis; iteration, tolerance) of every scenario in one launch (acPowerFlow.jl:1389-1433)"
+function powerFlow!(b::GaussSeidelBatch; iteration::Int64 = 20, tolerance::Float64 = 1e-8)
+    staleCheck(b)
+    check(ccall((:jg_gs_run, lib), Cint, (Int64, Int64, Float64, Ptr{Int32}, Ptr{Int32}), b.token, iteration, tolerance, b.iteration, b.status))
+    pullVoltage!(b)
+    return nothing
+end
+"setInitialPoint!(target, source) (acPowerFlow.jl:1281-1295): `magnitude`, `angle` [bus] for every scenario or [bus, batch]"
+function setInitialPoint!(b::GaussSeidelBatch, magnitude::VecOrMat{Float64}, angle::VecOrMat{Float64})
+    check(ccall((:jg_gs_set_voltage, lib), Cint, (Int64, Ptr{Float64}, Ptr{Float64}, Int64), b.token, magnitude, angle, ndims(magnitude) == 1 ? 0 : size(magnitude, 1)))
+    pullVoltage!(b)
+    return nothing
+end
+"method.voltage[idx] = magnitude[s] * cis(angle[s]) in every scenario s: what _updateBus! (bus.jl:350-362) and _updateGenerator! (generator.jl:425-430) set"
+function setBusVoltage!(b::GaussSeidelBatch, idx::Int64, magnitude::Vector{Float64}, angle::Vector{Float64})
+    check(ccall((:jg_gs_set_bus_voltage, lib), Cint, (Int64, Int64, Ptr{Float64}, Ptr{Float64}), b.token, idx, magnitude, angle))
+    pullVoltage!(b)
+    return nothing
+end
+"updateGenerator!(analysis; ...) after the system changed (generator.jl:410-431): injections, set-points, and the bus at its new magnitude"
+function refreshGenerator!(b::GaussSeidelBatch, idx::Int64)
+    staleCheck(b)
+    pushInjection!(b)
+    bus = b.system.generator.layout.bus[idx]
+    if b.system.bus.layout.type[bus] in (2, 3)
+        g = gsSetpoint(b.system)
+        check(ccall((:jg_gs_set_setpoint, lib), Cint, (Int64, Ptr{Float64}), b.token, g))
+        setBusVoltage!(b, bus, fill(g[bus], b.batch), b.angle[bus, :])
+    end
+    return nothing
+end
+"milliseconds of `reps` runs (HIP events): 0 powerFlow!'s launch with `sweeps` as the limit and tolerance 0, 1 the mismatch, 2 one sweep"
+function timeKernel(b::GaussSeidelBatch, kernel::Int, sweeps::Int64, reps::Int = 10)
+    ms = zeros(Float64, reps)
+    check(ccall((:jg_gs_time_kernel, lib), Cint, (Int64, Cint, Int64, Cint, Ptr{Float64}), b.token, kernel, sweeps, reps, ms))
+    return ms
+end
+
 export HIP, HIPOrthogonal, NewtonRaphsonBatch, BaseCase, baseInfo, baseInverseOnPattern, attach!, startFromBase!, firstIteration!, firstIterationCounts, setOutages!, shareDevice!, branchQuantities, screenSummary, powerFlowDefer!, moveLanes!, finish!, resume!, jacobian!,
        largestNormalizedResidual, normalizedResiduals, commUniqueId, Comm, shard, contingencyAnalysis, clearPlanCache,
        deviceCount, dims, setRefinement!, deviceMaps, setOutage!, snapshotVoltage!, restoreVoltage!, iterations, voltageDevice!, packResults!, packRows!,
        allgatherDevice, commRank, commWorld, timeKernel, setBusType!, busType, GaussNewtonBatch, setRealisations!, monteCarloEstimation, fastPatch!, setReadings!, drawNoise!, measurementDevice,
-       DcPowerFlowBatch, setInjections!, setOutagePairs!, pairScreenBuild!, pairScreen, pairTimeKernel, pairScreenRelease!, pairScreenIslandMode!, pairScreenShed, seriesScreenIslandMode!, seriesScreenShed, transferScreenIslandMode!, transferScreenShed, seriesScreenBuild!, seriesScreen, seriesTimeKernel, seriesScreenRelease!, setIslandMode!, islands, islandTable, fromPower, angleDevice, DcStateEstimationBatch, removedRows, removeRows!
+       DcPowerFlowBatch, setInjections!, setOutagePairs!, pairScreenBuild!, pairScreen, pairTimeKernel, pairScreenRelease!, pairScreenIslandMode!, pairScreenShed, seriesScreenIslandMode!, seriesScreenShed, transferScreenIslandMode!, transferScreenShed, seriesScreenBuild!, seriesScreen, seriesTimeKernel, seriesScreenRelease!, setIslandMode!, islands, islandTable, fromPower, angleDevice, DcStateEstimationBatch, removedRows, removeRows!,
+       GaussSeidelBatch, lastMismatch, setBusVoltage!, refreshGenerator!
 
 end # module

@@ -745,6 +745,54 @@ int jg_dcse_get_flows(int64_t h, double* from);
 int jg_dcse_time_kernel(int64_t h, int kernel, int reps, double* ms);
 
 /* ---------------------------------------------------------------------------------------------
+ * Gauss-Seidel AC power flow, one scenario per lane (csrc/jg_gs.hip).  The handle is an int64 token, as for jg_dc_*.
+ *
+ * A sweep is sequential over the buses of a scenario and scenarios are independent, so a lane runs the reference's update sequence unchanged on its own
+ * column of the batch-minor voltages, and a whole powerFlow! is ONE launch: every lane runs mismatch, verdict, sweep until it converges, reaches the
+ * limit or turns non-finite.  Indices and positions are 1-based; complex values are (re, im) pairs; per-lane arrays are [batch][n].
+ *
+ *   jg_gs_create         gaussSeidel(system) (src/powerFlow/acPowerFlow.jl:563-619).  colptr / rowval: the pattern of nodalMatrix; yt: the values of
+ *                        nodalMatrixTranspose -- row i of Ybus is yt[j], rowval[j] for j in colptr[i] .. colptr[i + 1] - 1, the walk of :742-744 and
+ *                        :1002-1009; type [n]: 1 demand, 2 generator, 3 on the slack bus alone (pq / pv of :575-584 are the buses of type 1 / 2 in bus
+ *                        order); setpoint [n]: generator.voltage.magnitude of the FIRST in-service generator of a bus (:1032-1033), read at type-2 buses
+ *   jg_gs_destroy
+ *   jg_gs_set_ybus       new values on the same pattern, after updateBranch! / updateBus!(shunt) (src/powerSystem/branch.jl:473-475: the analysis reads
+ *                        the system's matrix)
+ *   jg_gs_set_injection  bus.supply - bus.demand (active, reactive) of lanes lane0 .. lane0 + count - 1, as :747-750 and :998-1000 read them; stride 0:
+ *                        one [n] pair for every lane of the range, stride n: [count][n]
+ *   jg_gs_set_setpoint   setpoint [n] again, after updateGenerator!(...; magnitude) (src/powerSystem/generator.jl:410-431)
+ *   jg_gs_set_voltage    method.voltage = magnitude * cis(angle) (:576, setInitialPoint! :1243-1245, :1289-1291); stride 0: one [n] pair for all lanes
+ *   jg_gs_set_bus_voltage  method.voltage[bus] = magnitude[s] * cis(angle[s]) of every lane s, the other buses untouched: _updateBus!
+ *                        (src/powerSystem/bus.jl:350-362) and _updateGenerator! (generator.jl:425-430)
+ *   jg_gs_get_voltage    magnitude, angle = absang(method.voltage) (:1012, :1035) and / or method.voltage itself as re, im; either pair may be NULL
+ *   jg_gs_set_outages    lane lane0 + s = the grid with one branch out of service (updateBranch!(analysis; label, status = 0), branch.jl:344-350): its 4
+ *                        positions in yt (0: none) and the 4 complex values added there.  The position of Ybus entry (row, col) in yt is the position of
+ *                        (col, row) in nodalMatrix
+ *   jg_gs_mismatch       mismatch!(analysis) (:732-764) of every lane -> stop_p, stop_q [batch]
+ *   jg_gs_solve          solve!(analysis) (:997-1038) of every lane: one sweep, the lanes' iteration counts go up by one
+ *   jg_gs_run            powerFlow!(analysis; iteration, tolerance) (:1389-1433) of every lane in one launch -> iterations, status [batch]: 0 converged,
+ *                        1 the iteration limit, 3 a mismatch maximum that is not finite (an outage left a bus without admittance)
+ *   jg_gs_get_mismatch   the maxima of the last jg_gs_mismatch / the last check of jg_gs_run
+ *   jg_gs_time_kernel    milliseconds (HIP events) of `reps` runs of: 0 jg_gs_run's launch with `sweeps` as the limit and tolerance 0 (no lane leaves
+ *                        early), 1 the mismatch, 2 one sweep; ms [reps].  The voltages move on as they do in the calls timed
+ * ------------------------------------------------------------------------------------------- */
+int jg_gs_create(int64_t* h, int64_t n, const int64_t* colptr, const int64_t* rowval, const double* yt, const int8_t* type, int64_t slack,
+                 const double* setpoint, int64_t batch, int device);
+void jg_gs_destroy(int64_t h);
+int jg_gs_set_ybus(int64_t h, const double* yt);
+int jg_gs_set_injection(int64_t h, int64_t lane0, int64_t count, const double* active, const double* reactive, int64_t stride);
+int jg_gs_set_setpoint(int64_t h, const double* setpoint);
+int jg_gs_set_voltage(int64_t h, const double* magnitude, const double* angle, int64_t stride);
+int jg_gs_set_bus_voltage(int64_t h, int64_t bus, const double* magnitude, const double* angle);
+int jg_gs_get_voltage(int64_t h, double* magnitude, double* angle, double* re, double* im);
+int jg_gs_set_outages(int64_t h, int64_t lane0, int64_t count, const int64_t* position, const double* delta);
+int jg_gs_mismatch(int64_t h, double* stop_p, double* stop_q);
+int jg_gs_solve(int64_t h);
+int jg_gs_run(int64_t h, int64_t iteration, double tolerance, int32_t* iterations, int32_t* status);
+int jg_gs_get_mismatch(int64_t h, double* stop_p, double* stop_q);
+int jg_gs_time_kernel(int64_t h, int kernel, int64_t sweeps, int reps, double* ms);
+
+/* ---------------------------------------------------------------------------------------------
  * Symbolic analysis only (no device needed): the static schedule that replaces the symbolic half
  * of `lu`/`klu` (src/backend/utility.jl:470-476, 486-492).  Used by the CPU test-suite to replay
  * and race-check the schedule.  pattern: 0-based int32 block CSR, structurally symmetric, full

@@ -11,6 +11,7 @@ from .system import (updateBranch_ as updateBranchSystem_, updateBus_ as updateB
 from .powerflow import (AcPowerFlow, newtonRaphson, fastNewtonRaphsonBX, fastNewtonRaphsonXB, mismatch_, solve_, powerFlow_, setInitialPoint_, setRefinement_,   # noqa: F401
                         updateBranch_, updateBus_, updateGenerator_, addBranch_, dropZeros_, setOutage_, setOutages_, setInjection_, outagePatch, fastOutagePatch, initializeACPowerFlow, power_, current_, screenSummary_, reactiveLimit_, adjustAngle_,
                         BaseCase, startFromBase_, setFirstIteration_, firstIterationCounts, setBusType_, busType, powerFlowLimits_)
+from .gaussseidel import GaussSeidelPowerFlow, gaussSeidel          # noqa: F401
 from .contingency import bridges, islandTable, outageList, shard, deviceBatching, recommendedLanes, contingencyAnalysis, gatherResults, gatherResultsDevice, unpackResults, ContingencyPipeline   # noqa: F401
 from .measurement import (Measurement, measurement, ems, addVoltmeter_, addAmmeter_, addWattmeter_, addVarmeter_,   # noqa: F401
                           addPmu_, exactQuantities)
@@ -21,7 +22,7 @@ from .stateestimation import (WlsMethod, Normal, LU, KLU, QR, LDLt, LL, Orthogon
 from .dcstateestimation import DcStateEstimation, dcStateEstimation, setReadings_, removed, removeMeasurement_          # noqa: F401
 from .montecarlo import MonteCarloPipeline, gatherEstimates, gatherEstimatesDevice, unpackEstimates   # noqa: F401
 from .synthetic import pegaseShaped, case9241synth                          # noqa: F401
-from . import powerflow, stateestimation, dcpowerflow, dcstateestimation   # noqa: F401
+from . import powerflow, stateestimation, dcpowerflow, dcstateestimation, gaussseidel   # noqa: F401
 from . import _lib                                                           # noqa: F401
 
 __all__ = [
@@ -34,4 +35,5 @@ __all__ = [
     "WlsMethod", "Normal", "LU", "KLU", "QR", "LDLt", "LL", "Orthogonal", "PetersWilkinson",
     "addBranch_", "dropZeros_", "addBranchSystem_", "dropZerosSystem_", "pegaseShaped", "case9241synth", "ContingencyPipeline", "MonteCarloPipeline", "gatherEstimates", "gatherEstimatesDevice", "unpackEstimates", "setOutages_", "power_", "current_", "screenSummary_", "reactiveLimit_", "adjustAngle_",
     "dcModel_", "DcPowerFlow", "dcPowerFlow", "DcPairScreen", "dcPairScreen", "pairCandidates", "shedCandidates", "pairShed", "DcSeriesScreen", "dcSeriesScreen", "DcTransferScreen", "dcTransferScreen", "transferDirection", "DcStateEstimation", "dcStateEstimation", "setReadings_", "removed", "removeMeasurement_", "BaseCase", "startFromBase_", "setFirstIteration_", "firstIterationCounts", "setBusType_", "busType", "powerFlowLimits_",
+    "GaussSeidelPowerFlow", "gaussSeidel",
 ]

@@ -191,6 +191,20 @@ def lib():
         "jg_dcse_set_branches": [C.c_int64, C.c_int64, I64P, I64P, F64P, F64P],
         "jg_dcse_get_flows": [C.c_int64, F64P],
         "jg_dcse_time_kernel": [C.c_int64, C.c_int, C.c_int, F64P],
+        # Gauss-Seidel power flow: an int64 token too
+        "jg_gs_create": [C.POINTER(C.c_int64), C.c_int64, I64P, I64P, F64P, I8P, C.c_int64, F64P, C.c_int64, C.c_int],
+        "jg_gs_set_ybus": [C.c_int64, F64P],
+        "jg_gs_set_injection": [C.c_int64, C.c_int64, C.c_int64, F64P, F64P, C.c_int64],
+        "jg_gs_set_setpoint": [C.c_int64, F64P],
+        "jg_gs_set_voltage": [C.c_int64, F64P, F64P, C.c_int64],
+        "jg_gs_set_bus_voltage": [C.c_int64, C.c_int64, F64P, F64P],
+        "jg_gs_get_voltage": [C.c_int64, VP, VP, VP, VP],
+        "jg_gs_set_outages": [C.c_int64, C.c_int64, C.c_int64, I64P, F64P],
+        "jg_gs_mismatch": [C.c_int64, F64P, F64P],
+        "jg_gs_solve": [C.c_int64],
+        "jg_gs_run": [C.c_int64, C.c_int64, C.c_double, I32P, I32P],
+        "jg_gs_get_mismatch": [C.c_int64, F64P, F64P],
+        "jg_gs_time_kernel": [C.c_int64, C.c_int, C.c_int64, C.c_int, F64P],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -206,6 +220,8 @@ def lib():
     L.jg_dc_destroy.restype = None
     L.jg_dcse_destroy.argtypes = [C.c_int64]
     L.jg_dcse_destroy.restype = None
+    L.jg_gs_destroy.argtypes = [C.c_int64]
+    L.jg_gs_destroy.restype = None
     L.jg_plan_cache_clear.argtypes = []
     L.jg_plan_cache_clear.restype = None
     L.jg_comm_destroy.argtypes = [VP]

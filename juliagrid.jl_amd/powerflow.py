@@ -7,6 +7,7 @@ Reference surface (paths relative to /root/reference)      here
   powerFlow!(analysis; ...)    acPowerFlow.jl:1389-1433      powerFlow_(analysis, iteration=20, tolerance=1e-8)
   setInitialPoint!(analysis)   acPowerFlow.jl:1226-1249      setInitialPoint_(analysis[, source])
   updateBranch!(analysis; ...) branch.jl:453-459             updateBranch_(analysis, label, status=...)
+  gaussSeidel(system)          acPowerFlow.jl:563-619        gaussseidel.py; the calls below dispatch on its analysis type
   analysis.voltage.{magnitude,angle}, analysis.method.{jacobian,mismatch,increment,pq,pvpq,iteration}
 
 (`!` is spelled with a trailing underscore.)  The only addition is `batch`: B independent scenarios
@@ -24,6 +25,7 @@ import numpy as np
 
 from . import _lib
 from . import dcpowerflow as _dc
+from . import gaussseidel as _gs
 from .system import (CscMatrix, PowerSystem, acModel_, updateBranch_ as _update_branch_system,
                      updateBus_ as _update_bus_system, updateGenerator_ as _update_generator_system)
 
@@ -305,6 +307,8 @@ def setInjection_(an: AcPowerFlow, active=None, reactive=None, scenario0: int = 
         if reactive is not None:
             raise ValueError("setInjection_: a DcPowerFlow has no reactive injections")
         return _dc.setInjection_(an, active, scenario0)                # (scenario0: the DC analysis only -- lanes scenario0 .. get injections of their own)
+    if isinstance(an, _gs.GaussSeidelPowerFlow):
+        return _gs.setInjection_(an, active, reactive, scenario0)
     if scenario0:
         raise ValueError("setInjection_: scenario0 belongs to a DcPowerFlow; an AC analysis takes [n] or [batch, n]")
     bus = an.system.bus
@@ -467,6 +471,8 @@ def fastNewtonRaphsonXB(system: PowerSystem, batch: int = 1, device: int = 0, ma
 
 def mismatch_(an: AcPowerFlow):
     """mismatch!(analysis) -> (max|f_P|, max|f_Q|); arrays of length batch when batch > 1."""
+    if isinstance(an, _gs.GaussSeidelPowerFlow):
+        return _gs.mismatch_(an)
     if an.system.model.revision.acPattern != an.method.signature.acPattern:
         _rebuild(an)                                              # the device copy of Ybus has the old pattern
     p = np.zeros(an.batch)
@@ -518,6 +524,8 @@ def solve_(an: AcPowerFlow):
     """solve!(analysis): Jacobian fill + refactorization + solve + state update on the device (a DcPowerFlow: dcpowerflow.solve_)."""
     if isinstance(an, _dc.DcPowerFlow):
         return _dc.solve_(an)
+    if isinstance(an, _gs.GaussSeidelPowerFlow):
+        return _gs.solve_(an)
     _check_signature(an)
     fn = _lib.lib().jg_nr_fast_solve if getattr(an.method, "fast", False) else _lib.lib().jg_nr_solve
     _lib.check(fn(an._h))
@@ -532,6 +540,10 @@ def powerFlow_(an: AcPowerFlow, iteration: int = 20, tolerance: float = 1e-8, fe
     power=True: power!(analysis) follows.  A DcPowerFlow is solved directly (dcpowerflow.powerFlow_)."""
     if isinstance(an, _dc.DcPowerFlow):
         return _dc.powerFlow_(an, power=power)
+    if isinstance(an, _gs.GaussSeidelPowerFlow):
+        if power:
+            _gs_unsupported("power_")
+        return _gs.powerFlow_(an, iteration, tolerance, fetch)
     _check_signature(an)
     it = np.zeros(an.batch, dtype=np.int32)
     st = np.zeros(an.batch, dtype=np.int32)
@@ -545,8 +557,14 @@ def powerFlow_(an: AcPowerFlow, iteration: int = 20, tolerance: float = 1e-8, fe
         power_(an)
 
 
+def _gs_unsupported(what: str):
+    raise TypeError(f"{what} is not offered on a Gauss-Seidel analysis: hand its state to a Newton-Raphson analysis with setInitialPoint_(nr, gs)")
+
+
 def setInitialPoint_(an: AcPowerFlow, source=None):
     """setInitialPoint!(analysis) / setInitialPoint!(target, source) (acPowerFlow.jl:1226-1295)."""
+    if isinstance(an, _gs.GaussSeidelPowerFlow):
+        return _gs.setInitialPoint_(an, source)
     bus, gen = an.system.bus, an.system.generator
     if source is not None:
         _push_voltage(an, source.voltage.magnitude, source.voltage.angle)
@@ -559,6 +577,8 @@ def setInitialPoint_(an: AcPowerFlow, source=None):
 
 
 def _upload_ybus(an: AcPowerFlow):
+    if isinstance(an, _gs.GaussSeidelPowerFlow):
+        return _gs._upload_ybus(an)
     if an.system.model.revision.acPattern != an.method.signature.acPattern:
         return                                                    # new pattern: the next solve rebuilds the device model (_rebuild)
     ac = an.system.model.ac
@@ -615,6 +635,8 @@ def _refresh_fast(an: AcPowerFlow):
 def updateBus_(an: AcPowerFlow, label: int, **kwargs):
     """updateBus!(analysis; label, active, reactive, conductance, susceptance, magnitude, angle) (bus.jl:343-420):
     demand -> injections, shunt -> nodal matrix diagonal; magnitude / angle are start values (setInitialPoint_)."""
+    if isinstance(an, _gs.GaussSeidelPowerFlow):
+        return _gs.updateBus_(an, label, **kwargs)
     _update_bus_system(an.system, label, **kwargs)
     if "conductance" in kwargs or "susceptance" in kwargs:
         _upload_ybus(an)
@@ -626,6 +648,8 @@ def updateBus_(an: AcPowerFlow, label: int, **kwargs):
 def updateGenerator_(an: AcPowerFlow, label: int, **kwargs):
     """updateGenerator!(analysis; label, status, active, reactive, magnitude) (generator.jl:382-408): supply ->
     injections; a generator bus that would lose its last unit needs a new analysis (errorTypeConversion)."""
+    if isinstance(an, _gs.GaussSeidelPowerFlow):
+        return _gs.updateGenerator_(an, label, **kwargs)
     sysm = an.system
     k = int(label) - 1
     if 0 <= k < sysm.generator.number and kwargs.get("status") == 0 and sysm.generator.layout.status[k] == 1:
@@ -679,6 +703,8 @@ def outagePatchTable(system: PowerSystem):
 def setOutage_(an: AcPowerFlow, scenario: int, label: int | None):
     """Scenario `scenario` of a batched analysis = base grid with branch `label` out of service
     (None restores the base grid)."""
+    if isinstance(an, _gs.GaussSeidelPowerFlow):
+        return _gs.setOutages_(an, [int(label) if label else 0], int(scenario))
     if getattr(an.method, "fast", False):                        # Ybus AND the two constant matrices: one path (setOutages_)
         return setOutages_(an, [int(label) if label else 0], int(scenario))
     if label is None:
@@ -697,6 +723,8 @@ def setOutages_(an: AcPowerFlow, labels, scenario0: int = 0, islands: str = "ski
         return _dc.setOutages_(an, labels, scenario0, islands=islands)
     if islands != "skip":
         raise ValueError("setOutages_: islands belongs to a DcPowerFlow")
+    if isinstance(an, _gs.GaussSeidelPowerFlow):
+        return _gs.setOutages_(an, labels, scenario0)
     lab = np.array([int(x) if x else 0 for x in labels], dtype=np.int64)
     labels = [int(x) for x in lab]
     tptr, tdy = outagePatchTable(an.system)
@@ -763,6 +791,8 @@ def power_(an: AcPowerFlow):
         return _dcse.power_(an)
     if isinstance(an, _dc.DcPowerFlow):
         return _dc.power_(an)
+    if isinstance(an, _gs.GaussSeidelPowerFlow):
+        _gs_unsupported("power_")
     system, bus, gen = an.system, an.system.bus, an.system.generator
     if an.batch > 1 and getattr(an, "_lane_types", False):
         typ_lanes, _ = busType(an)
@@ -841,6 +871,8 @@ def power_(an: AcPowerFlow):
 
 def current_(an: AcPowerFlow):
     """current!(analysis) (acAnalysis.jl:672-704): injection, from, to and series currents (magnitude, angle)."""
+    if isinstance(an, _gs.GaussSeidelPowerFlow):
+        _gs_unsupported("current_")
     system = an.system
     L = _lib.lib()
     if not an._branches_on_device:
@@ -898,6 +930,8 @@ def reactiveLimit_(an: AcPowerFlow):
     reactive output violates its limits pins Q at the limit and turns its bus into a demand bus; a converted slack
     hands over to the first generator bus.  Mutates `an.system` like the reference; returns the violate vector.
     The caller then builds a new analysis (`newtonRaphson(system)`) and solves again."""
+    if isinstance(an, _gs.GaussSeidelPowerFlow):
+        _gs_unsupported("reactiveLimit_")
     if an.batch != 1:
         return _reactive_limit_batch(an)
     system, bus, gen = an.system, an.system.bus, an.system.generator
