@@ -3,9 +3,8 @@
 // Build: Phi by dc_phi_build (jg_dc_phi.hip).  Screen of a row block [k0, k1): k_pair_screen solves the 2 x 2 systems and
 // walks the rows of Phi once (a wave = DC_PAIR_TILE candidates k in registers x 64 consecutive l; Phi[m, k..], f0_m, 1 / rating_m through scalar loads,
 // Phi[m, l..l+63] one coalesced vector load reused for every k of the tile; nothing is written per m); the records come out of the block's dense result by
-// count (k_pair_rows<false>) / prefix sum over the rows (host, a few thousand integers) / ordered scatter (k_pair_rows<true>: ballot ranks, no atomics),
-// so the list is sorted by (k, l) and a list that overflows keeps the first.  Every store is a vector store.  A screen built in shed mode launches the
-// second instance of k_pair_screen, which sheds the bridges of a pair (jg_dc_pair.hpp has the table); the summaries are the same.
+// k_dc_rows and dc_block_records (jg_dc_records.hpp has the protocol) under the policy PairRows, sorted by (k, l).  Every store is a vector store.  A screen
+// built in shed mode launches the second instance of k_pair_screen, which sheds the bridges of a pair (jg_dc_pair.hpp has the table); the summaries are the same.
 #include "jg_dc_pair.hpp"
 
 #include <algorithm>
@@ -140,55 +139,27 @@ __global__ __launch_bounds__(64 * DC_PAIR_WAVES) void k_pair_screen(std::conditi
     }
 }
 
-// ---- records out of the block's dense result: count, (prefix sum on the host), ordered scatter -----------------------------------------------
-struct PairListArgs {
+// ---- records out of the block's dense result: the pair's policy of k_dc_rows (jg_dc_records.hpp) --------------------------------------------------
+// Row k's columns are the triangle l > k; two lists, the violators v > thr and the islanding pairs (v is NaN); the row's maximum from 0.
+struct PairRows {
+    static constexpr int LISTS = 2;
     const double* load; const int* branch; const int* count; const int* clabel;
-    int* r_viol; int* r_isl; double* r_max;                      // per row of the block
-    const long long* r_off; const long long* r_ioff;             // scatter: the row's first record / islanding entry
-    double* rec; long long rec_cap; long long* isl; long long isl_cap;
+    DcRecords list[2]; double* r_red;
     double thr; int ldk, nk, k0, k1;
+    __device__ int first(int k) const { return (k + 1) / 64 * 64; }
+    __device__ int cols() const { return nk; }
+    __device__ bool valid(int k, int l) const { return l > k && l < nk; }
+    __device__ double value(int i, int l) const { return load[(size_t)i * ldk + l]; }
+    __device__ bool hit(int q, double v, int) const { return q ? v != v : v > thr; }
+    __device__ void write(int q, long long at, int klab, int i, int, int l, double v) const {
+        if (q) { long long* e = (long long*)list[1].rec + at * 2; e[0] = klab; e[1] = clabel[l]; return; }
+        double* e = (double*)list[0].rec + at * 5;
+        e[0] = (double)klab; e[1] = (double)clabel[l]; e[2] = (double)branch[(size_t)i * ldk + l]; e[3] = v; e[4] = (double)count[(size_t)i * ldk + l];
+    }
+    static __device__ double identity() { return 0.0; }
+    static __device__ bool better(double v, double m) { return v > m; }
+    static __device__ double combine(double x, double y) { return fmax(x, y); }
 };
-template <bool SCATTER>
-__global__ __launch_bounds__(256) void k_pair_rows(PairListArgs a) {
-    const int wave = uniform(threadIdx.y), lane = threadIdx.x;
-    const int i = blockIdx.x * 4 + wave;
-    const int k = a.k0 + i;
-    if (k >= a.k1) return;
-    const size_t ldk = (size_t)a.ldk;
-    int nv = 0, ni = 0;
-    double mx = 0.0;
-    long long vb = SCATTER ? a.r_off[i] : 0, ib = SCATTER ? a.r_ioff[i] : 0;
-    const int klab = ((CInt)a.clabel)[k];
-    for (int l0 = (k + 1) / 64 * 64; l0 < a.nk; l0 += 64) {
-        const int l = l0 + lane;
-        const bool valid = l > k && l < a.nk;
-        const double v = valid ? a.load[(size_t)i * ldk + l] : 0.0;
-        const bool island = valid && v != v, viol = valid && v > a.thr;
-        const unsigned long long mv = __ballot(viol), mi = __ballot(island);
-        if (SCATTER) {
-            const unsigned long long below = (1ull << lane) - 1ull;
-            if (viol) {
-                const long long at = vb + __popcll(mv & below);
-                if (at < a.rec_cap) {
-                    double* q = a.rec + at * 5;
-                    q[0] = (double)klab; q[1] = (double)a.clabel[l]; q[2] = (double)a.branch[(size_t)i * ldk + l]; q[3] = v; q[4] = (double)a.count[(size_t)i * ldk + l];
-                }
-            }
-            if (island) {
-                const long long at = ib + __popcll(mi & below);
-                if (at < a.isl_cap) { a.isl[at * 2] = klab; a.isl[at * 2 + 1] = a.clabel[l]; }
-            }
-            vb += __popcll(mv); ib += __popcll(mi);
-        } else {
-            nv += __popcll(mv); ni += __popcll(mi);
-            if (valid && v > mx) mx = v;                        // (a NaN compares false)
-        }
-    }
-    if (!SCATTER) {
-        for (int s = 32; s; s >>= 1) mx = fmax(mx, __shfl_xor(mx, s, 64));
-        if (lane == 0) { a.r_viol[i] = nv; a.r_isl[i] = ni; a.r_max[i] = mx; }
-    }
-}
 // worst loading over the block's pairs (k, l) per l: with r_max (per k) the per-candidate ranking
 __global__ void k_pair_colmax(const double* load, double* c_max, int ldk, int nk, int k0, int k1) {
     const int l = blockIdx.x * blockDim.x + threadIdx.x;
@@ -217,12 +188,11 @@ int pair_block(DcHandle* h, int rb, bool want_det, long long rec_cap, long long 
         const int rows = std::max(rb, p->blk_rows);
         const bool det = want_det || p->b_det != nullptr;
         const size_t cells = (size_t)rows * p->phi.ldk, r = (size_t)rows;
-        DC_TRY(dc_block_grow(h, p->mem, "jg_dc_pair_screen", rows, p->blk_rows, cells * (det ? 24 : 16), dc_blk(p->b_load, cells), dc_blk(p->b_branch, cells),
-                             dc_blk(p->b_count, cells), dc_blk(p->b_det, det ? cells : 0), dc_blk(p->r_viol, r), dc_blk(p->r_isl, r), dc_blk(p->r_max, r),
-                             dc_blk(p->r_off, r), dc_blk(p->r_ioff, r)));
+        DC_TRY(dc_block_grow(h, p->mem, "jg_dc_pair_screen", rows, p->blk_rows, cells * (det ? 24 : 16), {&p->viol, &p->isl}, dc_blk(p->b_load, cells), dc_blk(p->b_branch, cells),
+                             dc_blk(p->b_count, cells), dc_blk(p->b_det, det ? cells : 0), dc_blk(p->r_max, r)));
     }
-    DC_TRY(dc_list_grow(h, p->mem, p->rec, p->rec_cap, rec_cap, 5));
-    return dc_list_grow(h, p->mem, p->isl, p->isl_cap, isl_cap, 2);
+    DC_TRY(dc_list_grow(h, p->mem, p->viol, rec_cap));
+    return dc_list_grow(h, p->mem, p->isl, isl_cap);
 }
 
 PairShedArgs screen_args(DcHandle* h, int k0, int k1, double thr, bool det) {
@@ -241,18 +211,17 @@ void launch_screen(DcHandle* h, const PairShedArgs& a) {
     if (a.cisl) hipLaunchKernelGGL(k_pair_screen<true>, grid, block, 0, h->stream, a);
     else hipLaunchKernelGGL(k_pair_screen<false>, grid, block, 0, h->stream, (const PairScreenArgs&)a);
 }
-PairListArgs list_args(DcHandle* h, int k0, int k1, double thr, long long rec_cap, long long isl_cap) {
+PairRows list_args(DcHandle* h, int k0, int k1, double thr, long long rec_cap, long long isl_cap) {
     DcPairState* p = h->pair;
-    PairListArgs a{};
+    PairRows a{};
     a.load = p->b_load; a.branch = p->b_branch; a.count = p->b_count; a.clabel = p->phi.cand_label;
-    a.r_viol = p->r_viol; a.r_isl = p->r_isl; a.r_max = p->r_max; a.r_off = p->r_off; a.r_ioff = p->r_ioff;
-    a.rec = p->rec; a.rec_cap = rec_cap; a.isl = p->isl; a.isl_cap = isl_cap;
+    a.list[0] = p->viol.limited(rec_cap); a.list[1] = p->isl.limited(isl_cap); a.r_red = p->r_max;
     a.thr = thr; a.ldk = p->phi.ldk; a.nk = p->phi.nk; a.k0 = k0; a.k1 = k1;
     return a;
 }
-void launch_stats(DcHandle* h, const PairListArgs& a) {
+void launch_stats(DcHandle* h, const PairRows& a) {
     DcPairState* p = h->pair;
-    hipLaunchKernelGGL((k_pair_rows<false>), dim3((a.k1 - a.k0 + 3) / 4), dim3(64, 4), 0, h->stream, a);
+    dc_launch_rows<false>(h, a);
     hipLaunchKernelGGL(k_pair_colmax, dim3((a.ldk + 255) / 256), dim3(256), 0, h->stream, p->b_load, p->c_max, a.ldk, a.nk, a.k0, a.k1);
 }
 
@@ -266,31 +235,19 @@ int pair_screen(DcHandle* h, int k0, int k1, double thr, long long rec_cap, long
     DC_TRY(pair_block(h, rb, o.d_det != nullptr, rec_cap, isl_cap));
     dc_phi_rinv(h, &p->phi);
     launch_screen(h, screen_args(h, k0, k1, thr, o.d_det != nullptr));
-    PairListArgs la = list_args(h, k0, k1, thr, rec_cap, isl_cap);
+    const PairRows la = list_args(h, k0, k1, thr, rec_cap, isl_cap);
     launch_stats(h, la);
-    DC_HIP(hipGetLastError());
-    std::vector<int> nv(rb), ni(rb);
     std::vector<double> rmax(rb), cmax(ldk);
-    DC_HIP(hipMemcpyAsync(nv.data(), p->r_viol, rb * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    DC_HIP(hipMemcpyAsync(ni.data(), p->r_isl, rb * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    DC_HIP(hipMemcpyAsync(rmax.data(), p->r_max, rb * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    DC_HIP(sync_copy(cmax.data(), p->c_max, ldk * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    std::vector<long long> off, ioff;
-    const long long viol = dc_prefix(nv, off), isl = dc_prefix(ni, ioff);
+    DcListCall viol{&p->viol, rec_cap, o.records}, isl{&p->isl, isl_cap, o.islanding};
+    DC_TRY(dc_block_records(h, rb, {&viol, &isl}, [&] {
+        DC_HIP(hipMemcpyAsync(rmax.data(), p->r_max, rb * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        DC_HIP(sync_copy(cmax.data(), p->c_max, ldk * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        return 0;
+    }, [&] { dc_launch_rows<true>(h, la); }));
     long long pairs = 0;
     for (int i = 0; i < rb; ++i) pairs += nk - 1 - (k0 + i);
-    const long long nrec = std::min(viol, rec_cap), nisl = std::min(isl, isl_cap);
-    if (nrec || nisl) {
-        DC_HIP(hipMemcpyAsync(p->r_off, off.data(), rb * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-        DC_HIP(hipMemcpyAsync(p->r_ioff, ioff.data(), rb * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-        hipLaunchKernelGGL((k_pair_rows<true>), dim3((rb + 3) / 4), dim3(64, 4), 0, h->stream, la);
-        DC_HIP(hipGetLastError());
-        if (nrec) DC_HIP(hipMemcpyAsync(o.records, p->rec, (size_t)nrec * 5 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        if (nisl) DC_HIP(hipMemcpyAsync(o.islanding, p->isl, (size_t)nisl * 2 * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-        DC_HIP(hipStreamSynchronize(h->stream));                // (off / ioff go out of scope behind it)
-    }
-    o.totals[0] = pairs; o.totals[1] = viol; o.totals[2] = isl; o.totals[3] = nrec; o.totals[4] = nisl;
-    o.totals[5] = (viol > rec_cap ? 1 : 0) | (isl > isl_cap ? 2 : 0);
+    o.totals[0] = pairs; o.totals[1] = viol.total; o.totals[2] = isl.total; o.totals[3] = viol.kept; o.totals[4] = isl.kept;
+    o.totals[5] = (viol.total > rec_cap ? 1 : 0) | (isl.total > isl_cap ? 2 : 0);
     if (o.worst)
         for (int j = 0; j < nk; ++j) {
             double w = cmax[j];

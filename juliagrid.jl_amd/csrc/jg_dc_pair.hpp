@@ -27,7 +27,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "jg_dc_phi.hpp"
+#include "jg_dc_records.hpp"
 
 namespace jg {
 
@@ -42,10 +42,9 @@ struct DcPairState {
     // the row block of a screen call (grown on demand)
     int blk_rows = 0;
     double* b_load = nullptr; int* b_branch = nullptr; int* b_count = nullptr; double* b_det = nullptr;     // [blk_rows][ldk]; b_det only on request
-    int* r_viol = nullptr; int* r_isl = nullptr; double* r_max = nullptr; long long* r_off = nullptr; long long* r_ioff = nullptr;    // [blk_rows]
+    double* r_max = nullptr;                 // [blk_rows]
     double* c_max = nullptr;                 // [ldk]
-    double* rec = nullptr; long long rec_cap = 0;       // [rec_cap][5]
-    long long* isl = nullptr; long long isl_cap = 0;    // [isl_cap][2]
+    DcRecords viol{5 * sizeof(double)}, isl{2 * sizeof(long long)};       // the violators [5] and the islanding pairs [2]
     DcMem mem;                               // the device memory of the fields above (not the DcPhi's): what release frees
 };
 

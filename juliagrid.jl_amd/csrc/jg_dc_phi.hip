@@ -277,6 +277,17 @@ int dc_phi_row_flows(DcHandle* h, const DcPhi* p, int T, const double* rhs, bool
     return rc;
 }
 
+std::vector<int> dc_phi_row_labels(const DcHandle* h, const std::vector<int>& cand, const std::vector<int>& mon, int ldt, double* info) {
+    std::vector<char> in(h->nbr, 0);
+    for (int m : mon) in[m] = 1;
+    for (int m : cand) in[m] = 1;
+    std::vector<int> label;
+    for (int m = 0; m < h->nbr; ++m) if (in[m]) label.push_back(m + 1);
+    for (int j = 8; j < 12; ++j) info[j] = 0.0;
+    info[8] = (double)(label.size() * ldt * sizeof(double));
+    return label;
+}
+
 int dc_phi_bridges(DcHandle* h, const DcPhi* p, std::vector<char>& bridge) {
     std::vector<double> diag(p->ldk);
     DC_HIP(sync_copy(diag.data(), p->cand_diag, diag.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));

@@ -1,6 +1,7 @@
-// jg_dc_phi.hpp -- the kept outage sensitivities Phi of a DcHandle (jg_dc.hpp), with ONE owner, and the host side of a screen call that the three screens on
-// them share: the N-2 pair screen (jg_dc_pair.hpp, which has the algebra of Phi), the N-1 screen over a series of profiles (jg_dc_series.hpp) and the
-// transfer-capability screen (jg_dc_transfer.hpp).  Each screen's state owns a DcPhi beside its own call-time buffers; nothing here knows a screen.
+// jg_dc_phi.hpp -- the kept outage sensitivities Phi of a DcHandle (jg_dc.hpp), with ONE owner, shared by the three screens on them: the N-2 pair screen
+// (jg_dc_pair.hpp, which has the algebra of Phi), the N-1 screen over a series of profiles (jg_dc_series.hpp) and the transfer-capability screen
+// (jg_dc_transfer.hpp).  Each screen's state owns a DcPhi beside its own call-time buffers; nothing here knows a screen.  The host side of a screen call and
+// the records of its row block: jg_dc_records.hpp.
 //
 // What is kept: Phi on the rows R = monitored u candidates (ascending branch index), columns = candidates, [rows][ldk] doubles with ldk = candidates
 // rounded up to 64 -- the sweep pair of jg_dc_sweep.hip runs once per candidate (a lane batch at a time), never per case.
@@ -92,6 +93,9 @@ int dc_build_failed(DcHandle* h, S*& s, int rc) {
 //                       ms [2] gets the milliseconds of the sweep pairs and of the flow kernel added (HIP events).  Not 0: the text is in h->error
 //   dc_phi_bridges      bridge [nk] 1: |1 - Phi[k,k]| < DC_SINGULAR (and not a bridge the shed mode solves)
 //   dc_phi_shed_gather  out [bridges in [k0, k1)][T] on the host = s_k F[row of k][t], from the device (k_shed_gather: one thread per value)
+//   dc_phi_row_labels   a build with row flows [rows][ldt] beside Phi (F0, G) opens: the rows, monitored u candidates, as 1-based labels ascending; info [8]
+//                       the row flows' bytes, [9..11] 0.  It ends with dc_phi_flows_ms: build_ms [3] and info [9..11] from ms [2] of dc_phi_row_flows
+//   dc_hip              a HIP call's result as a step of such a build: 0, or 2 and "`what`: ..." in h->error
 int dc_phi_lists(DcHandle* h, const std::string& who, int64_t nk, const int64_t* candidates, int64_t nm, const int64_t* monitored, std::vector<int>& cand,
                  std::vector<int>& mon);
 int dc_phi_build(DcHandle* h, DcPhi* p, const char* who, const std::vector<int>& cand, const std::vector<int>& mon, int64_t budget, size_t extra,
@@ -102,6 +106,14 @@ size_t dc_phi_flows_scratch(const DcHandle* h, int ldt);
 int dc_phi_row_flows(DcHandle* h, const DcPhi* p, int T, const double* rhs, bool shift, double* F, int ldt, double* ms);
 int dc_phi_bridges(DcHandle* h, const DcPhi* p, std::vector<char>& bridge);
 int dc_phi_shed_gather(DcHandle* h, const DcPhi* p, int k0, int k1, const double* F, int ldt, int T, double* out);
+std::vector<int> dc_phi_row_labels(const DcHandle* h, const std::vector<int>& cand, const std::vector<int>& mon, int ldt, double* info);
+inline void dc_phi_flows_ms(const double* ms, double* build_ms, double* info) {
+    build_ms[0] = info[9] = ms[0] + ms[1]; build_ms[1] = info[10] = ms[0]; build_ms[2] = info[11] = ms[1];
+}
+inline int dc_hip(DcHandle* h, hipError_t e, const char* what) {
+    if (e != hipSuccess) h->error = std::string(what) + ": " + hipGetErrorString(e);
+    return e == hipSuccess ? 0 : 2;
+}
 
 // ---- exports the three screens share: `screen` is "pair" / "series" / "transfer", `p` null before the screen's build ---------------------------
 // jg_dc_<screen>_set_island_mode.  `flag` (DcHandle::pair_shed / series_shed / transfer_shed) is the mode of the NEXT build, which takes it and sets it back to 0
@@ -121,53 +133,6 @@ int dc_phi_time_kernel(DcHandle* d, const std::string& screen, const DcPhi* p, i
     const auto enqueue = make();
     const int rc = time_events(d->stream, reps, ms, d->error, [&]() -> int { enqueue(kernel); return 0; });
     return rc ? api_fail(rc, d->error) : 0;
-}
-
-// ---- the host side of a screen call ---------------------------------------------------------------------------------------------------------
-// The row block of a call, grown and never shrunk (the caller asks only when `rows` exceed blk_rows): the arrays listed (dc_blk: pointer, elements; 0
-// elements: not wanted) are released, `need` bytes are held against the free device memory (code 5 with the sizes, blk_rows 0), then allocated and zeroed.
-template <typename T> struct DcBlk { T** p; size_t count; };
-template <typename T> DcBlk<T> dc_blk(T*& p, size_t count) { return {&p, count}; }
-template <typename... T>
-int dc_block_grow(DcHandle* h, DcMem& own, const char* who, int rows, int& blk_rows, size_t need, DcBlk<T>... a) {
-    (dev_release(h, own, *a.p), ...);
-    blk_rows = 0;
-    size_t free_b = 0, total_b = 0;
-    DC_HIP(hipMemGetInfo(&free_b, &total_b));
-    if (need > free_b) {
-        h->error = std::string(who) + ": a block of " + std::to_string(rows) + " rows needs " + dc_bytes_text(need) + ", " + dc_bytes_text(free_b) + " are free: screen fewer rows per call";
-        return 5;
-    }
-    int rc = 0;
-    ((rc = rc || !a.count ? rc : dev_alloc(h, own, a.p, a.count, (const T*)nullptr, true)), ...);
-    if (!rc) blk_rows = rows;
-    return rc;
-}
-// a record list [cap][width] on the device, grown to `want` entries and never shrunk
-template <typename T>
-int dc_list_grow(DcHandle* h, DcMem& own, T*& p, long long& cap, long long want, int width) {
-    if (want <= cap) return 0;
-    dev_release(h, own, p);
-    cap = 0;
-    DC_TRY(dev_alloc(h, own, &p, (size_t)want * width, (const T*)nullptr, true));
-    cap = want;
-    return 0;
-}
-// the block's dense result of one quantity on the host: the device's [rb][ld] of V as [rb][T] of D, dst[i][j] = map(i, j, src[i][j])
-template <typename V, typename D, typename Map>
-int dc_dense(DcHandle* h, D* dst, const V* src, int rb, int ld, int T, Map&& map) {
-    std::vector<V> t((size_t)rb * ld);
-    DC_HIP(sync_copy(t.data(), src, t.size() * sizeof(V), hipMemcpyDeviceToHost, h->stream));
-    for (int i = 0; i < rb; ++i)
-        for (int j = 0; j < T; ++j) dst[(size_t)i * T + j] = (D)map(i, j, t[(size_t)i * ld + j]);
-    return 0;
-}
-// off[i] = the first record of row i from the rows' counts; returns their total
-inline long long dc_prefix(const std::vector<int>& count, std::vector<long long>& off) {
-    long long sum = 0;
-    off.resize(count.size());
-    for (size_t i = 0; i < count.size(); ++i) { off[i] = sum; sum += count[i]; }
-    return sum;
 }
 
 }  // namespace jg

@@ -4,8 +4,8 @@
 // right-hand sides (dc_phi_row_flows: the sweep pair of jg_dc_sweep.hip, DC_PAIR_LANES profiles at a time).  Screen of a row block [k0, k1):
 // k_series_screen walks the rows once (a wave = DC_SERIES_TILE candidates k in registers x 64 consecutive profiles; Phi[m, k..], 1 / rating_m and the
 // row's candidate position through scalar loads, F0[m, t..t+63] one coalesced vector load reused for every k of the tile; nothing is written per m); the
-// records come out of the block's dense result by count (k_series_rows<false>) / prefix sum over the rows (host) / ordered scatter
-// (k_series_rows<true>: ballot ranks, no atomics), so the list is sorted by (k, t) and a list that overflows keeps the first.  Every store is a vector store.
+// records come out of the block's dense result by k_dc_rows and dc_block_records (jg_dc_records.hpp has the protocol) under the policy SeriesRows, sorted
+// by (k, t).  Every store is a vector store.
 #include "jg_dc_series.hpp"
 
 #include <algorithm>
@@ -101,50 +101,26 @@ __global__ __launch_bounds__(64 * DC_PAIR_WAVES) void k_series_screen(SeriesScre
     }
 }
 
-// ---- summaries out of the block's dense result: count, (prefix sum on the host), ordered scatter ---------------------------------------------
-struct SeriesListArgs {
+// ---- summaries out of the block's dense result: the series' policy of k_dc_rows (jg_dc_records.hpp) ------------------------------------------------
+// Row k's columns are the profiles 0 .. T; one list, the violators v > thr (a NaN, the loading of a bridge candidate, compares false); the row's maximum from 0.
+struct SeriesRows {
+    static constexpr int LISTS = 1;
     const double* load; const int* branch; const int* count; const int* clabel;
-    int* r_viol; double* r_max;                                  // per row of the block
-    const long long* r_off;                                      // scatter: the row's first record
-    double* rec; long long rec_cap;
+    DcRecords list[1]; double* r_red;
     double thr; int ldt, T, k0, k1;
+    __device__ int first(int) const { return 0; }
+    __device__ int cols() const { return T; }
+    __device__ bool valid(int, int t) const { return t < T; }
+    __device__ double value(int i, int t) const { return load[(size_t)i * ldt + t]; }
+    __device__ bool hit(int, double v, int) const { return v > thr; }
+    __device__ void write(int, long long at, int klab, int i, int, int t, double v) const {
+        double* e = (double*)list[0].rec + at * 5;
+        e[0] = (double)klab; e[1] = (double)t; e[2] = (double)branch[(size_t)i * ldt + t]; e[3] = v; e[4] = (double)count[(size_t)i * ldt + t];
+    }
+    static __device__ double identity() { return 0.0; }
+    static __device__ bool better(double v, double m) { return v > m; }
+    static __device__ double combine(double x, double y) { return fmax(x, y); }
 };
-template <bool SCATTER>
-__global__ __launch_bounds__(256) void k_series_rows(SeriesListArgs a) {
-    const int wave = uniform(threadIdx.y), lane = threadIdx.x;
-    const int i = blockIdx.x * 4 + wave;
-    const int k = a.k0 + i;
-    if (k >= a.k1) return;
-    const size_t ldt = (size_t)a.ldt;
-    int nv = 0;
-    double mx = 0.0;
-    long long vb = SCATTER ? a.r_off[i] : 0;
-    const int klab = ((CInt)a.clabel)[k];
-    for (int t0 = 0; t0 < a.T; t0 += 64) {
-        const int t = t0 + lane;
-        const bool valid = t < a.T;
-        const double v = valid ? a.load[(size_t)i * ldt + t] : 0.0;
-        const bool viol = valid && v > a.thr;                    // (a NaN, the loading of a bridge candidate, compares false)
-        const unsigned long long mv = __ballot(viol);
-        if (SCATTER) {
-            if (viol) {
-                const long long at = vb + __popcll(mv & ((1ull << lane) - 1ull));
-                if (at < a.rec_cap) {
-                    double* q = a.rec + at * 5;
-                    q[0] = (double)klab; q[1] = (double)t; q[2] = (double)a.branch[(size_t)i * ldt + t]; q[3] = v; q[4] = (double)a.count[(size_t)i * ldt + t];
-                }
-            }
-            vb += __popcll(mv);
-        } else {
-            nv += __popcll(mv);
-            if (valid && v > mx) mx = v;
-        }
-    }
-    if (!SCATTER) {
-        for (int s = 32; s; s >>= 1) mx = fmax(mx, __shfl_xor(mx, s, 64));
-        if (lane == 0) { a.r_viol[i] = nv; a.r_max[i] = mx; }
-    }
-}
 // per profile over the block's candidates: the worst loading (bridges aside) and the number of candidates whose outage violates
 __global__ void k_series_cols(const double* load, double* c_max, int* c_viol, double thr, int ldt, int T, int rb) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -180,16 +156,8 @@ int series_build(DcHandle* h, const std::vector<int>& cand, const std::vector<in
     const bool shed = h->series_shed == 1;
     h->series_shed = 0;
     const int ldt = (T + 63) / 64 * 64;
-    int nr = 0;
-    {
-        std::vector<char> in(h->nbr, 0);
-        for (int m : mon) in[m] = 1;
-        for (int m : cand) in[m] = 1;
-        for (char c : in) nr += c;
-    }
-    const size_t f0_bytes = (size_t)nr * ldt * sizeof(double), scratch = dc_phi_flows_scratch(h, ldt);
-    for (int j = 8; j < 12; ++j) info[j] = 0.0;
-    info[8] = (double)f0_bytes;
+    const int nr = (int)dc_phi_row_labels(h, cand, mon, ldt, info).size();
+    const size_t f0_bytes = (size_t)info[8], scratch = dc_phi_flows_scratch(h, ldt);
     DcSeriesState* s = h->series = new DcSeriesState();
     s->T = T; s->ldt = ldt;
     const std::string extra = "; F0 needs " + dc_bytes_text(f0_bytes) + " (" + std::to_string(nr) + " rows x " + std::to_string(ldt) + " profiles x 8) and " +
@@ -202,8 +170,7 @@ int series_build(DcHandle* h, const std::vector<int>& cand, const std::vector<in
         step(dev_alloc(h, s->mem, &s->c_viol, (size_t)ldt, (const int*)nullptr, true)) && step(dev_alloc(h, s->mem, &s->base, (size_t)ldt * 3, (const double*)nullptr, true)) &&
         step(dc_phi_row_flows(h, &s->phi, T, rhs, true, s->F0, ldt, ms)) && step(dc_phi_bridges(h, &s->phi, s->h_bridge));
     if (rc) return dc_build_failed(h, h->series, rc);
-    s->build_ms[0] = ms[0] + ms[1]; s->build_ms[1] = ms[0]; s->build_ms[2] = ms[1];
-    info[9] = s->build_ms[0]; info[10] = ms[0]; info[11] = ms[1];
+    dc_phi_flows_ms(ms, s->build_ms, info);
     return 0;
 }
 
@@ -212,10 +179,10 @@ int series_block(DcHandle* h, int rb, long long rec_cap) {
     DcSeriesState* s = h->series;
     if (rb > s->blk_rows) {
         const size_t cells = (size_t)rb * s->ldt, r = (size_t)rb;
-        DC_TRY(dc_block_grow(h, s->mem, "jg_dc_series_screen", rb, s->blk_rows, cells * 16, dc_blk(s->b_load, cells), dc_blk(s->b_branch, cells), dc_blk(s->b_count, cells),
-                             dc_blk(s->r_viol, r), dc_blk(s->r_max, r), dc_blk(s->r_off, r)));
+        DC_TRY(dc_block_grow(h, s->mem, "jg_dc_series_screen", rb, s->blk_rows, cells * 16, {&s->viol}, dc_blk(s->b_load, cells), dc_blk(s->b_branch, cells), dc_blk(s->b_count, cells),
+                             dc_blk(s->r_max, r)));
     }
-    return dc_list_grow(h, s->mem, s->rec, s->rec_cap, rec_cap, 5);
+    return dc_list_grow(h, s->mem, s->viol, rec_cap);
 }
 
 SeriesScreenArgs screen_args(DcHandle* h, int k0, int k1, double thr) {
@@ -234,17 +201,17 @@ void launch_screen(DcHandle* h, const SeriesScreenArgs& a) {
     if (a.cisl) hipLaunchKernelGGL(k_series_screen<true>, grid, block, 0, h->stream, a);
     else hipLaunchKernelGGL(k_series_screen<false>, grid, block, 0, h->stream, a);
 }
-SeriesListArgs list_args(DcHandle* h, int k0, int k1, double thr, long long rec_cap) {
+SeriesRows list_args(DcHandle* h, int k0, int k1, double thr, long long rec_cap) {
     DcSeriesState* s = h->series;
-    SeriesListArgs a{};
+    SeriesRows a{};
     a.load = s->b_load; a.branch = s->b_branch; a.count = s->b_count; a.clabel = s->phi.cand_label;
-    a.r_viol = s->r_viol; a.r_max = s->r_max; a.r_off = s->r_off; a.rec = s->rec; a.rec_cap = rec_cap;
+    a.list[0] = s->viol.limited(rec_cap); a.r_red = s->r_max;
     a.thr = thr; a.ldt = s->ldt; a.T = s->T; a.k0 = k0; a.k1 = k1;
     return a;
 }
-void launch_stats(DcHandle* h, const SeriesListArgs& a) {
+void launch_stats(DcHandle* h, const SeriesRows& a) {
     DcSeriesState* s = h->series;
-    hipLaunchKernelGGL((k_series_rows<false>), dim3((a.k1 - a.k0 + 3) / 4), dim3(64, 4), 0, h->stream, a);
+    dc_launch_rows<false>(h, a);
     hipLaunchKernelGGL(k_series_cols, dim3((s->ldt + 255) / 256), dim3(256), 0, h->stream, s->b_load, s->c_max, s->c_viol, a.thr, s->ldt, s->T, a.k1 - a.k0);
 }
 
@@ -259,31 +226,21 @@ int series_screen(DcHandle* h, int k0, int k1, double thr, long long rec_cap, co
     DC_TRY(series_block(h, rb, rec_cap));
     dc_phi_rinv(h, p);
     launch_screen(h, screen_args(h, k0, k1, thr));
-    SeriesListArgs la = list_args(h, k0, k1, thr, rec_cap);
+    const SeriesRows la = list_args(h, k0, k1, thr, rec_cap);
     launch_stats(h, la);
     if (o.base) hipLaunchKernelGGL(k_series_base, dim3((T + 63) / 64), dim3(64), 0, h->stream, s->F0, p->row_rinv, p->row_branch, s->base, thr, p->rows, ldt, T);
-    DC_HIP(hipGetLastError());
-    std::vector<int> nv(rb), cviol(ldt);
+    std::vector<int> cviol(ldt);
     std::vector<double> rmax(rb), cmax(ldt);
-    DC_HIP(hipMemcpyAsync(nv.data(), s->r_viol, rb * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    DC_HIP(hipMemcpyAsync(rmax.data(), s->r_max, rb * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    DC_HIP(hipMemcpyAsync(cviol.data(), s->c_viol, ldt * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    if (o.base) DC_HIP(hipMemcpyAsync(o.base, s->base, (size_t)T * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    DC_HIP(sync_copy(cmax.data(), s->c_max, ldt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    std::vector<long long> off;
-    const long long viol = dc_prefix(nv, off);
-    long long isl = 0;
-    for (int i = 0; i < rb; ++i)
-        if (s->h_bridge[k0 + i]) { if (o.islanding) o.islanding[isl] = p->h_cand[k0 + i] + 1; ++isl; }
-    const long long nrec = std::min(viol, rec_cap);
-    if (nrec) {
-        DC_HIP(hipMemcpyAsync(s->r_off, off.data(), rb * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-        hipLaunchKernelGGL((k_series_rows<true>), dim3((rb + 3) / 4), dim3(64, 4), 0, h->stream, la);
-        DC_HIP(hipGetLastError());
-        DC_HIP(hipMemcpyAsync(o.records, s->rec, (size_t)nrec * 5 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        DC_HIP(hipStreamSynchronize(h->stream));                // (off goes out of scope behind it)
-    }
-    o.totals[0] = (long long)rb * T; o.totals[1] = viol; o.totals[2] = isl; o.totals[3] = nrec; o.totals[4] = viol > rec_cap ? 1 : 0;
+    DcListCall viol{&s->viol, rec_cap, o.records};
+    DC_TRY(dc_block_records(h, rb, {&viol}, [&] {
+        DC_HIP(hipMemcpyAsync(rmax.data(), s->r_max, rb * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        DC_HIP(hipMemcpyAsync(cviol.data(), s->c_viol, ldt * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        if (o.base) DC_HIP(hipMemcpyAsync(o.base, s->base, (size_t)T * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        DC_HIP(sync_copy(cmax.data(), s->c_max, ldt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        return 0;
+    }, [&] { dc_launch_rows<true>(h, la); }));
+    o.totals[0] = (long long)rb * T; o.totals[1] = viol.total; o.totals[2] = dc_bridge_list(*p, s->h_bridge, k0, k1, o.islanding); o.totals[3] = viol.kept;
+    o.totals[4] = viol.total > rec_cap ? 1 : 0;
     if (o.worst) for (int i = 0; i < rb; ++i) o.worst[k0 + i] = rmax[i];
     if (o.worst_profile) for (int t = 0; t < T; ++t) o.worst_profile[t] = std::max(o.worst_profile[t], cmax[t]);
     if (o.viol_profile) for (int t = 0; t < T; ++t) o.viol_profile[t] += cviol[t];

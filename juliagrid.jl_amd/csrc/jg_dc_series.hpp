@@ -25,7 +25,7 @@
 
 #include <vector>
 
-#include "jg_dc_phi.hpp"
+#include "jg_dc_records.hpp"
 
 namespace jg {
 
@@ -43,10 +43,10 @@ struct DcSeriesState {
     // the row block of a screen call (grown on demand)
     int blk_rows = 0;
     double* b_load = nullptr; int* b_branch = nullptr; int* b_count = nullptr;      // [blk_rows][ldt]
-    int* r_viol = nullptr; double* r_max = nullptr; long long* r_off = nullptr;     // [blk_rows]
+    double* r_max = nullptr;                 // [blk_rows]
     double* c_max = nullptr; int* c_viol = nullptr;                                 // [ldt] over the block's candidates, per profile
     double* base = nullptr;                  // [ldt][3] the profiles' base case: worst loading, its branch, the count
-    double* rec = nullptr; long long rec_cap = 0;       // [rec_cap][5]
+    DcRecords viol{5 * sizeof(double)};      // the violators [5]
     double build_ms[3] = {0, 0, 0};          // F0 of the last build: total, sweep pairs, F0 kernel (HIP events)
     DcMem mem;                               // the device memory of the fields above (not the DcPhi's): what release frees
 };

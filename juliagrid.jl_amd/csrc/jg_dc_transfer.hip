@@ -7,8 +7,8 @@
 // = 64 consecutive candidates k of a chunk, a wave keeps DC_TRANSFER_TILE transfers in registers, the waves of a workgroup share the chunk so its Phi rows
 // meet in the vector L1; 1 / rating_m, F0[m], the row's candidate position and G[m, t..t+3] through scalar loads, Phi[m, k..k+63] one coalesced vector load
 // reused for every transfer of the tile; nothing is written per m).  The summaries come out of the block's dense result without atomics: per candidate and
-// per transfer minima, the records by count (k_transfer_rows<false>) / prefix sum over the rows (host) / ordered scatter (k_transfer_rows<true>: ballot
-// ranks), so the list is sorted by (k, t) and a list that overflows keeps the first.  Every store is a vector store.
+// per transfer minima, the records by k_dc_rows and dc_block_records (jg_dc_records.hpp has the protocol) under the policy TransferRows, sorted by (k, t).
+// Every store is a vector store.
 #include "jg_dc_transfer.hpp"
 
 #include <algorithm>
@@ -114,57 +114,35 @@ __global__ __launch_bounds__(64 * DC_PAIR_WAVES) void k_transfer_screen(Transfer
     }
 }
 
-// ---- summaries out of the block's dense result: count, (prefix sum on the host), ordered scatter ---------------------------------------------
-struct TransferListArgs {
+// ---- summaries out of the block's dense result: the transfer screen's policy of k_dc_rows (jg_dc_records.hpp) ------------------------------------
+// Row k's columns are the transfers 0 .. T; one list, the cases with TC < amount[t] (a NaN, the capability of a bridge candidate, compares false); the
+// row's minimum from +inf.  A record carries g of the limiting branch, formed as the screen kernel forms it; a case without one (+inf below an infinite
+// amount) takes its slot and is not written.
+struct TransferRows {
+    static constexpr int LISTS = 1;
     const double* tc; const int* row; const double* amount; const int* clabel; const int* rbranch;
-    const double* Phi; const double* G; const int* crow; const double* cdiag;      // scatter: g of the limiting branch, formed as the screen kernel forms it
-    const int* cisl;                                             // shed mode (else null): the candidates' (side, lo, hi, 0)
-    int* r_rec; double* r_min;                                   // per row of the block
-    const long long* r_off;                                      // scatter: the row's first record
-    double* rec; long long rec_cap;
+    const double* Phi; const double* G; const int* crow; const double* cdiag; const int* cisl;      // cisl: shed mode (else null), the candidates' (side, lo, hi, 0)
+    DcRecords list[1]; double* r_red;
     int ldk, ldt, T, k0, k1;
+    __device__ int first(int) const { return 0; }
+    __device__ int cols() const { return T; }
+    __device__ bool valid(int, int t) const { return t < T; }
+    __device__ double value(int i, int t) const { return tc[(size_t)i * ldt + t]; }
+    __device__ bool hit(int, double v, int t) const { return v < amount[t]; }
+    __device__ void write(int, long long at, int klab, int i, int k, int t, double v) const {
+        const int r = row[(size_t)i * ldt + t];
+        if (r < 0) return;
+        const int rk = crow[k];
+        const int sd = cisl ? cisl[4 * k] : 0;
+        const double cgk = sd ? (sd > 0 ? 1.0 : -1.0) * G[(size_t)rk * ldt + t] : G[(size_t)rk * ldt + t] / (1.0 - cdiag[k]);
+        const double g = fma(Phi[(size_t)r * ldk + k], cgk, G[(size_t)r * ldt + t]);
+        double* e = (double*)list[0].rec + at * 5;
+        e[0] = (double)klab; e[1] = (double)t; e[2] = (double)(rbranch[r] + 1); e[3] = v; e[4] = g;
+    }
+    static __device__ double identity() { return __longlong_as_double(0x7ff0000000000000LL); }
+    static __device__ bool better(double v, double m) { return v < m; }
+    static __device__ double combine(double x, double y) { return fmin(x, y); }
 };
-template <bool SCATTER>
-__global__ __launch_bounds__(256) void k_transfer_rows(TransferListArgs a) {
-    const int wave = uniform(threadIdx.y), lane = threadIdx.x;
-    const int i = blockIdx.x * 4 + wave;
-    const int k = a.k0 + i;
-    if (k >= a.k1) return;
-    const size_t ldt = (size_t)a.ldt, ldk = (size_t)a.ldk;
-    int nv = 0;
-    double mn = __longlong_as_double(0x7ff0000000000000LL);
-    long long vb = SCATTER ? a.r_off[i] : 0;
-    const int klab = ((CInt)a.clabel)[k];
-    for (int t0 = 0; t0 < a.T; t0 += 64) {
-        const int t = t0 + lane;
-        const bool valid = t < a.T;
-        const double v = valid ? a.tc[(size_t)i * ldt + t] : 0.0;
-        const bool below = valid && v < a.amount[t];             // (a NaN, the capability of a bridge candidate, compares false)
-        const unsigned long long mv = __ballot(below);
-        if (SCATTER) {
-            if (below) {
-                const long long at = vb + __popcll(mv & ((1ull << lane) - 1ull));
-                const int r = a.row[(size_t)i * ldt + t];
-                if (at < a.rec_cap && r >= 0) {
-                    const int rk = a.crow[k];
-                    const int sd = a.cisl ? a.cisl[4 * k] : 0;
-                    const double cgk = sd ? (sd > 0 ? 1.0 : -1.0) * a.G[(size_t)rk * ldt + t] : a.G[(size_t)rk * ldt + t] / (1.0 - a.cdiag[k]);
-                    const double g = fma(a.Phi[(size_t)r * ldk + k], cgk, a.G[(size_t)r * ldt + t]);
-                    double* q = a.rec + at * 5;
-                    q[0] = (double)klab; q[1] = (double)t; q[2] = (double)(a.rbranch[r] + 1); q[3] = v; q[4] = g;
-                }
-            }
-            vb += __popcll(mv);
-        } else {
-            nv += __popcll(mv);
-            if (valid && v < mn) mn = v;
-        }
-    }
-    if (!SCATTER) {
-        for (int s = 32; s; s >>= 1) mn = fmin(mn, __shfl_xor(mn, s, 64));
-        if (lane == 0) { a.r_rec[i] = nv; a.r_min[i] = mn; }
-    }
-}
 // per transfer over the block's candidates, rows ascending and strict: the least capability (bridges aside), the block row that gives it (-1: none), its limiting row
 __global__ void k_transfer_cols(const double* tc, const int* row, double* c_min, int* c_at, int* c_row, int ldt, int T, int rb) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -206,18 +184,10 @@ int transfer_build(DcHandle* h, const std::vector<int>& cand, const std::vector<
     const bool shed = h->transfer_shed == 1;
     h->transfer_shed = 0;
     const int ldt = (T + 63) / 64 * 64;
-    std::vector<int> label;
-    {
-        std::vector<char> in(h->nbr, 0);
-        for (int m : mon) in[m] = 1;
-        for (int m : cand) in[m] = 1;
-        for (int m = 0; m < h->nbr; ++m) if (in[m]) label.push_back(m + 1);
-    }
+    const std::vector<int> label = dc_phi_row_labels(h, cand, mon, ldt, info);
     const int nr = (int)label.size();
-    const size_t g_bytes = (size_t)nr * ldt * sizeof(double);
+    const size_t g_bytes = (size_t)info[8];
     const size_t scratch = dc_phi_flows_scratch(h, ldt) + (base_rhs ? (size_t)nr * 64 * sizeof(double) : 0);
-    for (int j = 8; j < 12; ++j) info[j] = 0.0;
-    info[8] = (double)g_bytes;
     DcTransferState* s = h->transfer = new DcTransferState();
     s->T = T; s->ldt = ldt; s->h_row_label = label;
     const std::string extra = "; G needs " + dc_bytes_text(g_bytes) + " (" + std::to_string(nr) + " rows x " + std::to_string(ldt) + " transfers x 8) and " +
@@ -225,7 +195,6 @@ int transfer_build(DcHandle* h, const std::vector<int>& cand, const std::vector<
     DcPhi* p = &s->phi;
     int rc = 0;
     auto step = [&](int r) { if (r && !rc) rc = r; return rc == 0; };
-    auto hip = [&](hipError_t e, const char* what) { if (e != hipSuccess && !rc) { rc = 2; h->error = std::string(what) + ": " + hipGetErrorString(e); } return rc == 0; };
     double ms[2] = {0.0, 0.0};
     if (step(dc_phi_build(h, p, "jg_dc_transfer_build", cand, mon, budget, g_bytes + scratch, extra, info, shed)) &&
         step(dev_alloc(h, s->mem, &s->G, (size_t)nr * ldt, (const double*)nullptr, true)) && step(dev_alloc(h, s->mem, &s->f0, (size_t)nr, (const double*)nullptr, true)) &&
@@ -237,18 +206,17 @@ int transfer_build(DcHandle* h, const std::vector<int>& cand, const std::vector<
             double unused[2] = {0.0, 0.0};
             if (step(dev_alloc(h, s->mem, &Fb, (size_t)nr * 64, (const double*)nullptr, true)) && step(dc_phi_row_flows(h, p, 1, base_rhs, true, Fb, 64, unused))) {
                 hipLaunchKernelGGL(k_transfer_pick, dim3((nr + 255) / 256), dim3(256), 0, h->stream, Fb, s->f0, nr, 64);
-                hip(hipGetLastError(), "launch") && hip(hipStreamSynchronize(h->stream), "hipStreamSynchronize");
+                step(dc_hip(h, hipGetLastError(), "launch")) && step(dc_hip(h, hipStreamSynchronize(h->stream), "hipStreamSynchronize"));
             }
             dev_release(h, s->mem, Fb);
         } else {
-            hip(sync_copy(s->f0, p->row_f0, (size_t)nr * sizeof(double), hipMemcpyDeviceToDevice, h->stream), "copy of the base flows");
+            step(dc_hip(h, sync_copy(s->f0, p->row_f0, (size_t)nr * sizeof(double), hipMemcpyDeviceToDevice, h->stream), "copy of the base flows"));
         }
         if (!rc) step(dc_phi_row_flows(h, p, T, dirs, false, s->G, ldt, ms));
         if (!rc) step(dc_phi_bridges(h, p, s->h_bridge));
     }
     if (rc) return dc_build_failed(h, h->transfer, rc);
-    s->build_ms[0] = ms[0] + ms[1]; s->build_ms[1] = ms[0]; s->build_ms[2] = ms[1];
-    info[9] = s->build_ms[0]; info[10] = ms[0]; info[11] = ms[1];
+    dc_phi_flows_ms(ms, s->build_ms, info);
     return 0;
 }
 
@@ -257,10 +225,9 @@ int transfer_block(DcHandle* h, int rb, long long rec_cap) {
     DcTransferState* s = h->transfer;
     if (rb > s->blk_rows) {
         const size_t cells = (size_t)rb * s->ldt, r = (size_t)rb;
-        DC_TRY(dc_block_grow(h, s->mem, "jg_dc_transfer_screen", rb, s->blk_rows, cells * 12, dc_blk(s->b_tc, cells), dc_blk(s->b_row, cells), dc_blk(s->r_rec, r),
-                             dc_blk(s->r_min, r), dc_blk(s->r_off, r)));
+        DC_TRY(dc_block_grow(h, s->mem, "jg_dc_transfer_screen", rb, s->blk_rows, cells * 12, {&s->below}, dc_blk(s->b_tc, cells), dc_blk(s->b_row, cells), dc_blk(s->r_min, r)));
     }
-    return dc_list_grow(h, s->mem, s->rec, s->rec_cap, rec_cap, 5);
+    return dc_list_grow(h, s->mem, s->below, rec_cap);
 }
 
 TransferScreenArgs screen_args(DcHandle* h, int k0, int k1, double cutoff) {
@@ -279,19 +246,19 @@ void launch_screen(DcHandle* h, const TransferScreenArgs& a) {
     if (a.cisl) hipLaunchKernelGGL(k_transfer_screen<true>, grid, block, 0, h->stream, a);
     else hipLaunchKernelGGL(k_transfer_screen<false>, grid, block, 0, h->stream, a);
 }
-TransferListArgs list_args(DcHandle* h, int k0, int k1, long long rec_cap) {
+TransferRows list_args(DcHandle* h, int k0, int k1, long long rec_cap) {
     DcTransferState* s = h->transfer;
     const DcPhi* p = &s->phi;
-    TransferListArgs a{};
+    TransferRows a{};
     a.tc = s->b_tc; a.row = s->b_row; a.amount = s->amount; a.clabel = p->cand_label; a.rbranch = p->row_branch;
     a.Phi = p->Phi; a.G = s->G; a.crow = p->cand_row; a.cdiag = p->cand_diag; a.cisl = p->shed ? p->cand_isl : nullptr;
-    a.r_rec = s->r_rec; a.r_min = s->r_min; a.r_off = s->r_off; a.rec = s->rec; a.rec_cap = rec_cap;
+    a.list[0] = s->below.limited(rec_cap); a.r_red = s->r_min;
     a.ldk = p->ldk; a.ldt = s->ldt; a.T = s->T; a.k0 = k0; a.k1 = k1;
     return a;
 }
-void launch_stats(DcHandle* h, const TransferListArgs& a) {
+void launch_stats(DcHandle* h, const TransferRows& a) {
     DcTransferState* s = h->transfer;
-    hipLaunchKernelGGL((k_transfer_rows<false>), dim3((a.k1 - a.k0 + 3) / 4), dim3(64, 4), 0, h->stream, a);
+    dc_launch_rows<false>(h, a);
     hipLaunchKernelGGL(k_transfer_cols, dim3((s->ldt + 255) / 256), dim3(256), 0, h->stream, s->b_tc, s->b_row, s->c_min, s->c_at, s->c_row, s->ldt, s->T, a.k1 - a.k0);
 }
 
@@ -313,32 +280,22 @@ int transfer_screen(DcHandle* h, int k0, int k1, double cutoff, long long rec_ca
     }
     dc_phi_rinv(h, p);
     launch_screen(h, screen_args(h, k0, k1, cutoff));
-    TransferListArgs la = list_args(h, k0, k1, rec_cap);
+    const TransferRows la = list_args(h, k0, k1, rec_cap);
     launch_stats(h, la);
     if (o.base) hipLaunchKernelGGL(k_transfer_base, dim3((T + 63) / 64), dim3(64), 0, h->stream, s->G, s->f0, p->row_rinv, s->base, cutoff, p->rows, ldt, T);
-    DC_HIP(hipGetLastError());
-    std::vector<int> nv(rb), cat(ldt), crow(ldt);
+    std::vector<int> cat(ldt), crow(ldt);
     std::vector<double> rmin(rb), cmin(ldt), base(o.base ? (size_t)T * 3 : 0);
-    DC_HIP(hipMemcpyAsync(nv.data(), s->r_rec, rb * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    DC_HIP(hipMemcpyAsync(rmin.data(), s->r_min, rb * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    DC_HIP(hipMemcpyAsync(cat.data(), s->c_at, ldt * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    DC_HIP(hipMemcpyAsync(crow.data(), s->c_row, ldt * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    if (o.base) DC_HIP(hipMemcpyAsync(base.data(), s->base, (size_t)T * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    DC_HIP(sync_copy(cmin.data(), s->c_min, ldt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    std::vector<long long> off;
-    const long long below = dc_prefix(nv, off);
-    long long isl = 0;
-    for (int i = 0; i < rb; ++i)
-        if (s->h_bridge[k0 + i]) { if (o.islanding) o.islanding[isl] = p->h_cand[k0 + i] + 1; ++isl; }
-    const long long nrec = std::min(below, rec_cap);
-    if (nrec) {
-        DC_HIP(hipMemcpyAsync(s->r_off, off.data(), rb * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-        hipLaunchKernelGGL((k_transfer_rows<true>), dim3((rb + 3) / 4), dim3(64, 4), 0, h->stream, la);
-        DC_HIP(hipGetLastError());
-        DC_HIP(hipMemcpyAsync(o.records, s->rec, (size_t)nrec * 5 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        DC_HIP(hipStreamSynchronize(h->stream));                // (off goes out of scope behind it)
-    }
-    o.totals[0] = (long long)rb * T; o.totals[1] = below; o.totals[2] = isl; o.totals[3] = nrec; o.totals[4] = below > rec_cap ? 1 : 0;
+    DcListCall below{&s->below, rec_cap, o.records};
+    DC_TRY(dc_block_records(h, rb, {&below}, [&] {
+        DC_HIP(hipMemcpyAsync(rmin.data(), s->r_min, rb * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        DC_HIP(hipMemcpyAsync(cat.data(), s->c_at, ldt * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        DC_HIP(hipMemcpyAsync(crow.data(), s->c_row, ldt * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        if (o.base) DC_HIP(hipMemcpyAsync(base.data(), s->base, (size_t)T * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        DC_HIP(sync_copy(cmin.data(), s->c_min, ldt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        return 0;
+    }, [&] { dc_launch_rows<true>(h, la); }));
+    o.totals[0] = (long long)rb * T; o.totals[1] = below.total; o.totals[2] = dc_bridge_list(*p, s->h_bridge, k0, k1, o.islanding); o.totals[3] = below.kept;
+    o.totals[4] = below.total > rec_cap ? 1 : 0;
     if (o.worst) for (int i = 0; i < rb; ++i) o.worst[k0 + i] = s->h_bridge[k0 + i] ? std::numeric_limits<double>::quiet_NaN() : rmin[i];
     if (o.capability && o.cap_outage && o.cap_branch)
         for (int t = 0; t < T; ++t)

@@ -29,7 +29,7 @@
 
 #include <vector>
 
-#include "jg_dc_phi.hpp"
+#include "jg_dc_records.hpp"
 
 namespace jg {
 
@@ -45,11 +45,11 @@ struct DcTransferState {
     // the row block of a screen call (grown on demand)
     int blk_rows = 0;
     double* b_tc = nullptr; int* b_row = nullptr;                                   // [blk_rows][ldt] TC and the limiting ROW (-1: none)
-    int* r_rec = nullptr; double* r_min = nullptr; long long* r_off = nullptr;      // [blk_rows]
+    double* r_min = nullptr;                 // [blk_rows]
     double* c_min = nullptr; int* c_at = nullptr; int* c_row = nullptr;             // [ldt] over the block's candidates, per transfer: the least TC, its block row, its limiting row
     double* amount = nullptr;                // [ldt] the record threshold of a screen call
     double* base = nullptr;                  // [ldt][3] the transfers' base case: TC, the limiting row, branches above their rating at zero transfer
-    double* rec = nullptr; long long rec_cap = 0;       // [rec_cap][5]
+    DcRecords below{5 * sizeof(double)};     // the cases below their amount [5]
     double build_ms[3] = {0, 0, 0};          // G of the last build: total, sweep pairs, G kernel (HIP events)
     DcMem mem;                               // the device memory of the fields above (not the DcPhi's): what release frees
 };

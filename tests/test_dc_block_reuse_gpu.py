@@ -1,5 +1,5 @@
 """The row block of a screen call, REUSED: jg_dc_pair_screen, jg_dc_series_screen and jg_dc_transfer_screen called several times on ONE build with blocks
-of 3, then 8, then 3 rows, so the block's buffers are allocated, grown, and used again larger than the call needs (csrc/jg_dc_phi.hpp: dc_block_grow,
+of 3, then 8, then 3 rows, so the block's buffers are allocated, grown, and used again larger than the call needs (csrc/jg_dc_records.hpp: dc_block_grow,
 dc_list_grow).  The Python drivers never do that (they release after every call and only their last block is smaller), so the calls go through the
 library's C entry points directly, on one dcPowerFlow handle that stays open.
 
