@@ -82,6 +82,24 @@ __host__ __device__ inline bool groups_balanced(int groups) { return JG_BALANCED
 __host__ inline unsigned grid_blocks(int groups, long long nx) {
     return groups_balanced(groups) ? (unsigned)(((long long)groups * nx + 7) / 8 * 8) : (unsigned)(nx * group_stride(groups));
 }
+// Workgroup id -> (slot in the list of the gact active groups, chunk x) of an nx-chunk launch; false: this workgroup has nothing to do.  The index arithmetic of
+// map_block below, on its own so that a host program can walk it (tools/map_check.cpp: every pair exactly once for every handle count, active count and chunk count,
+// whichever mapping class the grid was sized for).
+__host__ __device__ inline bool map_slot(int gact, int nx, int id, int& slot, int& x) {
+    if (groups_balanced(gact)) {
+        const int total = gact * nx, chunk = (total + 7) >> 3;
+        const int j = id >> 3, flat = (id & 7) * chunk + j;
+        if (j >= chunk || flat >= total) return false;
+        slot = flat / nx;
+        x = flat - slot * nx;
+    } else {
+        const int gs = group_stride(gact);
+        slot = id % gs;
+        x = id / gs;
+        if (slot >= gact || x >= nx) return false;
+    }
+    return true;
+}
 
 #ifdef __HIPCC__
 __device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
@@ -175,18 +193,7 @@ __device__ __forceinline__ bool map_block(const GroupSel& sel, int ld, int nx, i
     SelInt8 first{};
     if (sel.list) { first = *(SelInt8Ptr)sel.list; gact = *(SelIntPtr)sel.count; }
     int slot;
-    if (groups_balanced(gact)) {
-        const int total = gact * nx, chunk = (total + 7) >> 3;
-        const int j = id >> 3, flat = (id & 7) * chunk + j;
-        if (j >= chunk || flat >= total) return false;
-        slot = flat / nx;
-        x = flat - slot * nx;
-    } else {
-        const int gs = group_stride(gact);
-        slot = id % gs;
-        x = id / gs;
-        if (slot >= gact || x >= nx) return false;
-    }
+    if (!map_slot(gact, nx, id, slot, x)) return false;
     if (sel.list) {
         if (gact <= 8) {
             g = first[0];
