@@ -1529,6 +1529,80 @@ function transferScreenShed(b::DcPowerFlowBatch, k0::Int64, k1::Int64, transfers
     c > 0 && check(ccall((:jg_dc_transfer_get_shed, lib), Cint, (Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}), b.token, k0, k1, flow, per))
     return branches[1:c], buses[1:c], m[1:c], side[1:c], flow[1:c], per[:, 1:c]
 end
+"""
+    generatorScreenBuild!(b, candidates, buses, colptr, rowidx, values; monitored = nothing, budget = 0) -> info [16]
+
+The DC generator-outage screen (jgrid.h: jg_dc_generator_*): G-1 and generator x branch cases, the loop `updateGenerator!(system, analysis; label = g,
+status = 0)`, `solve!`, `power!` around `updateBranch!(...; label = k, status = 0)` per branch.  `buses` are the distinct generator buses (indices, strictly
+ascending, the slack aside); `colptr` (from 0), `rowidx` (0-based positions in `buses`) and `values` are the sparse matrix A in CSC, one column per outage:
+`-Pg` at the unit's bus (the slack then picks the loss up, the reference's semantics) and whatever other units add at theirs.  One sweep pair per candidate
+branch and one per generator bus, never per generator.  The loss of the slack bus's last unit is the caller's to refuse, as `updateGenerator!` does.
+"""
+function generatorScreenBuild!(b::DcPowerFlowBatch, candidates::Vector{Int64}, buses::Vector{Int64}, colptr::Vector{Int64}, rowidx::Vector{Int64},
+                               values::Vector{Float64}; monitored::Union{Nothing, Vector{Int64}} = nothing, budget::Int64 = 0)
+    length(colptr) >= 2 || throw(DimensionMismatch("colptr has one entry per generator outage and one more"))
+    uploadRhs!(b)
+    info = zeros(Float64, 16)
+    mon = monitored === nothing ? Int64[] : monitored
+    check(ccall((:jg_dc_generator_build, lib), Cint, (Int64, Int64, Ptr{Int64}, Int64, Ptr{Int64}, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64},
+                                                      Ptr{Float64}, Int64, Ptr{Float64}),
+        b.token, length(candidates), candidates, length(mon), monitored === nothing ? C_NULL : mon, length(colptr) - 1, length(buses), buses, colptr,
+        rowidx, values, budget, info))
+    return info
+end
+"""
+    generatorScreen(b, k0, k1, candidates, generators; rating, threshold = 1.0, capacity = 2^20) -> (records [5, m], islanding, totals [5], worst, worstGenerator, violatingGenerator, base [3, G])
+
+All cases (k, g) of the candidate positions k0 .. k1 - 1 (0-based) and every generator outage, and with k0 = 0 the G-1 cases as row 0: the records of the
+cases above `threshold` sorted by (k, g) (branch k, 0 for a G-1 case; generator column g (0-based); worst branch; worst |from| / rating; overloaded
+branches), the bridge candidates of the block, the totals, the worst loading per candidate and per generator, the violating candidates per generator and
+the G-1 cases.
+"""
+function generatorScreen(b::DcPowerFlowBatch, k0::Int64, k1::Int64, candidates::Vector{Int64}, generators::Int64; rating::Vector{Float64},
+                         threshold::Float64 = 1.0, capacity::Int64 = 2^20)
+    check(ccall((:jg_dc_set_rating, lib), Cint, (Int64, Ptr{Float64}), b.token, rating))
+    records = Matrix{Float64}(undef, 5, capacity)
+    islanding = zeros(Int64, max(k1 - k0, 1))
+    totals = zeros(Int64, 5)
+    worst = zeros(Float64, length(candidates))
+    worstGenerator = zeros(Float64, generators); violatingGenerator = zeros(Int64, generators); base = zeros(Float64, 3, generators)
+    check(ccall((:jg_dc_generator_screen, lib), Cint, (Int64, Int64, Int64, Float64, Int64, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64},
+                                                       Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}),
+        b.token, k0, k1, threshold, capacity, records, islanding, totals, worst, worstGenerator, violatingGenerator, base, C_NULL, C_NULL, C_NULL))
+    return records[:, 1:totals[4]], islanding[1:totals[3]], totals, worst, worstGenerator, violatingGenerator, base
+end
+"the from-end flows of every G-1 case, `[generators, rows]` on the rows of the build (monitored and candidate branches, ascending)"
+function generatorScreenFlows(b::DcPowerFlowBatch, rows::Int64, generators::Int64)
+    flows = zeros(Float64, generators, rows)
+    check(ccall((:jg_dc_generator_get_flows, lib), Cint, (Int64, Ptr{Float64}), b.token, flows))
+    return flows
+end
+"milliseconds of `reps` runs (HIP events): 0 the screen kernel and 1 its summaries on candidate rows k0 .. k1 - 1, 2 the kernel that forms the G-1 flows"
+function generatorTimeKernel(b::DcPowerFlowBatch, kernel::Int, k0::Int64, k1::Int64, reps::Int = 20)
+    ms = zeros(Float64, reps)
+    check(ccall((:jg_dc_generator_time_kernel, lib), Cint, (Int64, Cint, Int64, Int64, Cint, Ptr{Float64}), b.token, kernel, k0, k1, reps, ms))
+    return ms
+end
+"frees what a generator screen keeps on the device"
+generatorScreenRelease!(b::DcPowerFlowBatch) = check(ccall((:jg_dc_generator_release, lib), Cint, (Int64,), b.token))
+"island mode of the NEXT `generatorScreenBuild!`: 0 a bridge candidate is skipped (status 3), 1 it is screened on the slack's island (jgrid.h)"
+generatorScreenIslandMode!(b::DcPowerFlowBatch, mode::Int) = check(ccall((:jg_dc_generator_set_island_mode, lib), Cint, (Int64, Cint), b.token, mode))
+"""
+    generatorScreenShed(b, k0, k1, generators) -> (branches, buses, m, side, flow [G, bridges])
+
+The bridge candidates among the positions k0 .. k1 - 1 (0-based) of a generator screen built in island mode 1, as `seriesScreenShed`: the flow that left
+the bridge's end on the slack's side before the branch outage, per generator outage.
+"""
+function generatorScreenShed(b::DcPowerFlowBatch, k0::Int64, k1::Int64, generators::Int64)
+    count = zeros(Int64, 1)
+    branches = zeros(Int64, max(k1 - k0, 1)); buses = zeros(Int64, max(k1 - k0, 1)); m = zeros(Int64, max(k1 - k0, 1)); side = zeros(Int64, max(k1 - k0, 1))
+    check(ccall((:jg_dc_generator_get_shed_table, lib), Cint, (Int64, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}),
+        b.token, k0, k1, count, branches, buses, m, side))
+    c = count[1]
+    flow = zeros(Float64, generators, max(c, 1))
+    c > 0 && check(ccall((:jg_dc_generator_get_shed, lib), Cint, (Int64, Int64, Int64, Ptr{Float64}), b.token, k0, k1, flow))
+    return branches[1:c], buses[1:c], m[1:c], side[1:c], flow[:, 1:c]
+end
 
 # ---- DC state estimation with batched bad-data removal (jgrid.h: jg_dcse_*; csrc/jg_dcse.hip) ------------------------------------------------
 # dcStateEstimation / solve! / power! / residualTest! / chiTest (src/stateEstimation/dcStateEstimation.jl:42-151, 342-434, badData.jl:48-117, 963-977) for
@@ -1871,7 +1945,7 @@ export HIP, HIPOrthogonal, NewtonRaphsonBatch, BaseCase, baseInfo, baseInverseOn
        largestNormalizedResidual, normalizedResiduals, commUniqueId, Comm, shard, contingencyAnalysis, clearPlanCache,
        deviceCount, dims, setRefinement!, deviceMaps, setOutage!, snapshotVoltage!, restoreVoltage!, iterations, voltageDevice!, packResults!, packRows!,
        allgatherDevice, commRank, commWorld, timeKernel, setBusType!, busType, GaussNewtonBatch, setRealisations!, monteCarloEstimation, fastPatch!, setReadings!, drawNoise!, measurementDevice,
-       DcPowerFlowBatch, setInjections!, setOutagePairs!, pairScreenBuild!, pairScreen, pairTimeKernel, pairScreenRelease!, pairScreenIslandMode!, pairScreenShed, seriesScreenIslandMode!, seriesScreenShed, transferScreenIslandMode!, transferScreenShed, seriesScreenBuild!, seriesScreen, seriesTimeKernel, seriesScreenRelease!, setIslandMode!, islands, islandTable, fromPower, angleDevice, DcStateEstimationBatch, removedRows, removeRows!,
+       DcPowerFlowBatch, setInjections!, setOutagePairs!, pairScreenBuild!, pairScreen, pairTimeKernel, pairScreenRelease!, pairScreenIslandMode!, pairScreenShed, seriesScreenIslandMode!, seriesScreenShed, transferScreenIslandMode!, transferScreenShed, generatorScreenBuild!, generatorScreen, generatorScreenFlows, generatorTimeKernel, generatorScreenRelease!, generatorScreenIslandMode!, generatorScreenShed, seriesScreenBuild!, seriesScreen, seriesTimeKernel, seriesScreenRelease!, setIslandMode!, islands, islandTable, fromPower, angleDevice, DcStateEstimationBatch, removedRows, removeRows!,
        GaussSeidelBatch, lastMismatch, setBusVoltage!, refreshGenerator!
 
 end # module

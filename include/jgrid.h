@@ -683,6 +683,58 @@ int jg_dc_transfer_release(int64_t h);
 int jg_dc_transfer_set_island_mode(int64_t h, int mode);
 int jg_dc_transfer_get_shed_table(int64_t h, int64_t k0, int64_t k1, int64_t* count, int64_t* branches, int64_t* buses, int64_t* m, int64_t* side);
 int jg_dc_transfer_get_shed(int64_t h, int64_t k0, int64_t k1, double* flow, double* transfer);
+/*
+ * The DC generator-outage screen: G-1 and generator x branch cases (csrc/jg_dc_generator.hpp).  The user loop
+ *     updateGenerator!(system, analysis; label = g, status = 0); solve!; power!                                (src/powerSystem/generator.jl:262-360, :433-446;
+ *                                                                                                              src/powerFlow/dcPowerFlow.jl:63-134: row 0, G-1)
+ *       updateBranch!(system, analysis; label = k, status = 0); solve!; power!; updateBranch!(...; status = 1)  (src/powerSystem/branch.jl: row k, per branch k)
+ *     updateGenerator!(...; label = g, status = 1)
+ * per generator g.  The loss of a unit moves the right-hand side alone, so a G-1 case needs no sweep of its own: with Psi[m,b], the flow on row m per unit
+ * of injection at the generator bus b (ONE sweep pair per distinct generator bus), and A [generator buses x generators], the net change of the bus
+ * injections per outage, F0[m,g] = f0[m] + sum_b Psi[m,b] A[b,g]; the case (k, g) is then f_m(k,g) = F0[m,g] + Phi[m,k] F0[k,g] / (1 - Phi[k,k]), the
+ * arithmetic of jg_dc_series_screen with F0's columns for the profiles.  The reference refuses the loss of the slack bus's last unit
+ * (generator.jl:441-445) and so does the caller of this screen; nothing here picks a new slack.  Needs jg_dc_set_branches and jg_dc_set_rhs; neither the
+ * lanes of the handle nor what the other screens' builds keep are touched.
+ *   jg_dc_generator_build  candidates [nk] and monitored [nm] as jg_dc_series_build takes them (nk >= 1).  buses [nbus]: the distinct generator buses
+ *                       (1-based, strictly ascending; the slack's entry of a right-hand side is dropped, so the slack bus gets a zero column and is best
+ *                       left out).  A in CSC: colptr [generators + 1] from 0, rowidx [colptr[generators]] 0-based POSITIONS in `buses`, values: column g
+ *                       holds -Pg at g's bus (updateGenerator!(...; status = 0) takes Pg out of bus.supply.active) and what the units that pick the loss
+ *                       up add at theirs; an empty column is the base case.  Phi by the build of jg_dc_pair_build, Psi [rows][nbus rounded up to 64] by
+ *                       one sweep pair per generator bus (512 at a time, scratch of the build's own), then F0 [rows][generators rounded up to 64] by one
+ *                       kernel.  budget_bytes as jg_dc_pair_build, for Phi + Psi + A + F0 + the scratch: return code 5 with the sizes in the message and
+ *                       nothing allocated when they do not fit.  info [16]: the eight of jg_dc_pair_build, bytes of F0, the milliseconds of Psi's build:
+ *                       total, sweep pairs, flow kernel, bytes of Psi, the milliseconds of the F0 kernel, generator buses swept, entries of A.  A second
+ *                       build replaces the first.
+ *   jg_dc_generator_screen  the cases (k, g) of the candidate POSITIONS k in [k0, k1) (0-based; the row block bounds the memory of a call, 16 bytes per
+ *                       case) x all generators against the ratings of jg_dc_set_rating; a call with k0 = 0 also walks row 0, the G-1 cases.
+ *                       records [capacity][5]: the cases whose worst loading exceeds threshold, sorted by (k, g) with row 0 first: branch k (1-based;
+ *                       0: the G-1 case), generator column g (0-based), worst branch, worst |from| / rating, number of monitored branches above
+ *                       threshold.  islanding [k1 - k0] (nullable): the candidates of the block that are bridges, as jg_dc_series_screen.
+ *                       totals [5]: cases screened (row 0 counted where walked), violating, bridge candidates, records written, 1 when the record list
+ *                       overflowed -- the counts are exact also then, and the records kept are the FIRST by (k, g).
+ *                       worst [nk] (nullable): positions k0 .. k1 - 1 get the worst loading over the generators.  worst_generator [generators]
+ *                       (nullable, in/out): max-merged with the worst loading over the rows walked, row 0 included; violating_generator [generators]
+ *                       (nullable, in/out): the block's candidates whose outage beside the unit's violates are added.  base [generators][3] (nullable):
+ *                       the G-1 cases -- worst loading, its branch, branches above threshold.  dense_* (each nullable) [k1 - k0][generators].
+ *   jg_dc_generator_get_flows  flows [rows][generators]: F0, the from-end flows of every G-1 case on the rows of the build (info [0]: monitored and
+ *                       candidate branches, ascending)
+ *   jg_dc_generator_time_kernel  milliseconds of `reps` runs: 0 the screen kernel and 1 the summaries on rows [k0, k1) (a block
+ *                       jg_dc_generator_screen has held), 2 the F0 kernel (k0, k1 ignored)
+ *   jg_dc_generator_release  frees what the screen holds on the device
+ *   jg_dc_generator_set_island_mode / _get_shed_table / _get_shed   as jg_dc_series_set_island_mode / _get_shed_table / _get_shed, with flow
+ *                       [count][generators]: a unit behind a bridge candidate leaves with it, and its column is the shed case without the outage.
+ */
+int jg_dc_generator_build(int64_t h, int64_t nk, const int64_t* candidates, int64_t nm, const int64_t* monitored, int64_t generators, int64_t nbus,
+                          const int64_t* buses, const int64_t* colptr, const int64_t* rowidx, const double* values, int64_t budget_bytes, double* info16);
+int jg_dc_generator_screen(int64_t h, int64_t k0, int64_t k1, double threshold, int64_t capacity, double* records, int64_t* islanding, int64_t* totals5,
+                           double* worst, double* worst_generator, int64_t* violating_generator, double* base, double* dense_load, int32_t* dense_branch,
+                           int32_t* dense_count);
+int jg_dc_generator_get_flows(int64_t h, double* flows);
+int jg_dc_generator_time_kernel(int64_t h, int kernel, int64_t k0, int64_t k1, int reps, double* ms);
+int jg_dc_generator_release(int64_t h);
+int jg_dc_generator_set_island_mode(int64_t h, int mode);
+int jg_dc_generator_get_shed_table(int64_t h, int64_t k0, int64_t k1, int64_t* count, int64_t* branches, int64_t* buses, int64_t* m, int64_t* side);
+int jg_dc_generator_get_shed(int64_t h, int64_t k0, int64_t k1, double* flow);
 
 /* ---------------------------------------------------------------------------------------------
  * DC state estimation with batched bad-data removal (csrc/jg_dcse.hip)

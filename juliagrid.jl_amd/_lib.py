@@ -178,6 +178,14 @@ def lib():
         "jg_dc_transfer_set_island_mode": [C.c_int64, C.c_int],
         "jg_dc_transfer_get_shed_table": [C.c_int64, C.c_int64, C.c_int64, I64P, I64P, I64P, I64P, I64P],
         "jg_dc_transfer_get_shed": [C.c_int64, C.c_int64, C.c_int64, F64P, F64P],
+        "jg_dc_generator_build": [C.c_int64, C.c_int64, I64P, C.c_int64, VP, C.c_int64, C.c_int64, I64P, I64P, I64P, F64P, C.c_int64, F64P],
+        "jg_dc_generator_screen": [C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_int64, VP, VP, I64P, VP, VP, VP, VP, VP, VP, VP],
+        "jg_dc_generator_get_flows": [C.c_int64, F64P],
+        "jg_dc_generator_time_kernel": [C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int, F64P],
+        "jg_dc_generator_release": [C.c_int64],
+        "jg_dc_generator_set_island_mode": [C.c_int64, C.c_int],
+        "jg_dc_generator_get_shed_table": [C.c_int64, C.c_int64, C.c_int64, I64P, I64P, I64P, I64P, I64P],
+        "jg_dc_generator_get_shed": [C.c_int64, C.c_int64, C.c_int64, F64P],
         "jg_dcse_create": [C.POINTER(C.c_int64), C.c_int64, C.c_int64, I64P, I64P, F64P, F64P, I32P, C.c_int64, C.c_double, C.c_int64, C.c_int],
         "jg_dcse_dims": [C.c_int64, I64P],
         "jg_dcse_set_weights": [C.c_int64, F64P, I32P],

@@ -7,6 +7,7 @@
 #include "jg_dc_pair.hpp"
 #include "jg_dc_series.hpp"
 #include "jg_dc_transfer.hpp"
+#include "jg_dc_generator.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -284,6 +285,7 @@ void dc_destroy(DcHandle* h) {
     dc_pair_free(h);
     dc_series_free(h);
     dc_transfer_free(h);
+    dc_generator_free(h);
     for (void* p : h->allocs) hipFree(p);
     if (h->stream) hipStreamDestroy(h->stream);
     delete h;

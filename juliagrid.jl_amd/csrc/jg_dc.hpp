@@ -35,6 +35,7 @@ constexpr double DC_SINGULAR = 1e-9;   // |1 - y_k a' z_s| below it: bridge.  Th
 struct DcPairState;
 struct DcSeriesState;
 struct DcTransferState;
+struct DcGeneratorState;
 
 struct DcHandle : DcDevice {
     int n = 0, nbr = 0, batch = 0, ld = 0, slack = 0;
@@ -56,9 +57,10 @@ struct DcHandle : DcDevice {
     DcPairState* pair = nullptr;                                               // the N-2 screen over all pairs of a candidate list (jg_dc_pair.hpp)
     DcSeriesState* series = nullptr;                                           // the N-1 screen over a series of injection profiles (jg_dc_series.hpp)
     DcTransferState* transfer = nullptr;                                       // the transfer-capability screen over transfers x N-1 outages (jg_dc_transfer.hpp)
-    // island mode of the NEXT pair / series / transfer build (the build takes it and sets it back to 0).  A sticky flag beside the build call is awkward -- the mode
+    DcGeneratorState* generator = nullptr;                                     // the generator-outage screen: G-1 and generator x branch cases (jg_dc_generator.hpp)
+    // island mode of the NEXT pair / series / transfer / generator build (the build takes it and sets it back to 0).  A sticky flag beside the build call is awkward -- the mode
     // belongs among the build's arguments -- but jg_dc_*_set_island_mode is part of the C ABI, so the flags stay
-    int pair_shed = 0, series_shed = 0, transfer_shed = 0;
+    int pair_shed = 0, series_shed = 0, transfer_shed = 0, generator_shed = 0;
     // bridge outages solved on the slack's island (jg_dc_set_island_mode 1): allocated by the first such call, a handle without it holds none of it
     int island_mode = 0, n_isl = 0;                                            // n_isl: lanes whose ONE outage is a bridge, set while the mode was 1
     std::vector<int> h_pre, h_blo, h_bhi, h_bside;                             // dc_island_table of the handle's branch table

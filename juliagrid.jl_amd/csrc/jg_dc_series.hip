@@ -185,15 +185,18 @@ int series_block(DcHandle* h, int rb, long long rec_cap) {
     return dc_list_grow(h, s->mem, s->viol, rec_cap);
 }
 
-SeriesScreenArgs screen_args(DcHandle* h, int k0, int k1, double thr) {
-    DcSeriesState* s = h->series;
-    const DcPhi* p = &s->phi;
+SeriesScreenArgs screen_args(const DcSeriesBlock& b, int k0, int k1, double thr) {
+    const DcPhi* p = b.phi;
     SeriesScreenArgs a{};
-    a.Phi = p->Phi; a.F0 = s->F0; a.rinv = p->row_rinv; a.pos = p->row_pos; a.rbranch = p->row_branch; a.crow = p->cand_row; a.cdiag = p->cand_diag;
-    a.load = s->b_load; a.branch = s->b_branch; a.count = s->b_count;
-    a.thr = thr; a.rows = p->rows; a.ldk = p->ldk; a.ldt = s->ldt; a.T = s->T; a.k0 = k0; a.k1 = k1; a.kbase = k0 / DC_SERIES_TILE * DC_SERIES_TILE;
+    a.Phi = p->Phi; a.F0 = b.F0; a.rinv = p->row_rinv; a.pos = p->row_pos; a.rbranch = p->row_branch; a.crow = p->cand_row; a.cdiag = p->cand_diag;
+    a.load = b.load; a.branch = b.branch; a.count = b.count;
+    a.thr = thr; a.rows = p->rows; a.ldk = p->ldk; a.ldt = b.ldt; a.T = b.T; a.k0 = k0; a.k1 = k1; a.kbase = k0 / DC_SERIES_TILE * DC_SERIES_TILE;
     a.cisl = p->shed ? p->cand_isl : nullptr; a.rpre = p->shed ? p->row_pre : nullptr;
     return a;
+}
+DcSeriesBlock series_blk(DcHandle* h) {
+    DcSeriesState* s = h->series;
+    return DcSeriesBlock{&s->phi, s->F0, s->ldt, s->T, s->b_load, s->b_branch, s->b_count};
 }
 void launch_screen(DcHandle* h, const SeriesScreenArgs& a) {
     const int tiles = (a.k1 - a.kbase + DC_SERIES_TILE - 1) / DC_SERIES_TILE;
@@ -212,7 +215,7 @@ SeriesRows list_args(DcHandle* h, int k0, int k1, double thr, long long rec_cap)
 void launch_stats(DcHandle* h, const SeriesRows& a) {
     DcSeriesState* s = h->series;
     dc_launch_rows<false>(h, a);
-    hipLaunchKernelGGL(k_series_cols, dim3((s->ldt + 255) / 256), dim3(256), 0, h->stream, s->b_load, s->c_max, s->c_viol, a.thr, s->ldt, s->T, a.k1 - a.k0);
+    dc_series_launch_cols(h, series_blk(h), s->c_max, s->c_viol, a.thr, a.k1 - a.k0);
 }
 
 struct SeriesOut {
@@ -225,10 +228,10 @@ int series_screen(DcHandle* h, int k0, int k1, double thr, long long rec_cap, co
     const int rb = k1 - k0, T = s->T, ldt = s->ldt;
     DC_TRY(series_block(h, rb, rec_cap));
     dc_phi_rinv(h, p);
-    launch_screen(h, screen_args(h, k0, k1, thr));
+    launch_screen(h, screen_args(series_blk(h), k0, k1, thr));
     const SeriesRows la = list_args(h, k0, k1, thr, rec_cap);
     launch_stats(h, la);
-    if (o.base) hipLaunchKernelGGL(k_series_base, dim3((T + 63) / 64), dim3(64), 0, h->stream, s->F0, p->row_rinv, p->row_branch, s->base, thr, p->rows, ldt, T);
+    if (o.base) dc_series_launch_base(h, series_blk(h), s->base, thr);
     std::vector<int> cviol(ldt);
     std::vector<double> rmax(rb), cmax(ldt);
     DcListCall viol{&s->viol, rec_cap, o.records};
@@ -254,6 +257,14 @@ int series_screen(DcHandle* h, int k0, int k1, double thr, long long rec_cap, co
 }  // namespace
 
 void dc_series_free(DcHandle* h) { dc_state_release(h, h->series); }
+
+void dc_series_launch_screen(DcHandle* h, const DcSeriesBlock& b, int k0, int k1, double thr) { launch_screen(h, screen_args(b, k0, k1, thr)); }
+void dc_series_launch_cols(DcHandle* h, const DcSeriesBlock& b, double* c_max, int* c_viol, double thr, int rb) {
+    hipLaunchKernelGGL(k_series_cols, dim3((b.ldt + 255) / 256), dim3(256), 0, h->stream, b.load, c_max, c_viol, thr, b.ldt, b.T, rb);
+}
+void dc_series_launch_base(DcHandle* h, const DcSeriesBlock& b, double* base, double thr) {
+    hipLaunchKernelGGL(k_series_base, dim3((b.T + 63) / 64), dim3(64), 0, h->stream, b.F0, b.phi->row_rinv, b.phi->row_branch, base, thr, b.phi->rows, b.ldt, b.T);
+}
 
 }  // namespace jg
 
@@ -294,7 +305,7 @@ int jg_dc_series_time_kernel(int64_t h, int kernel, int64_t k0, int64_t k1, int 
     jg::DcSeriesState* s = d->series;
     return jg::dc_phi_time_kernel(d, "series", s ? &s->phi : nullptr, s ? s->blk_rows : 0, kernel, k0, k1, reps, ms,
                                   [&] {
-        return [d, sa = jg::screen_args(d, (int)k0, (int)k1, 1.0), la = jg::list_args(d, (int)k0, (int)k1, 1.0, 0)](int which) {
+        return [d, sa = jg::screen_args(jg::series_blk(d), (int)k0, (int)k1, 1.0), la = jg::list_args(d, (int)k0, (int)k1, 1.0, 0)](int which) {
             if (which == 0) jg::launch_screen(d, sa);
             else jg::launch_stats(d, la);
         };

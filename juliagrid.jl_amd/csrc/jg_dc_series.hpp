@@ -51,6 +51,17 @@ struct DcSeriesState {
     DcMem mem;                               // the device memory of the fields above (not the DcPhi's): what release frees
 };
 
+// The series' arithmetic on the arrays of ANY state that keeps a DcPhi and column flows on its rows (the series' own profiles, the generator screen's
+// outage columns: jg_dc_generator.hpp): F0 [rows of phi][ldt], T columns, 0 behind them; the block's dense result load / branch / count [k1 - k0][ldt].
+//   dc_series_launch_screen   k_series_screen on the candidate rows [k0, k1) (the <true> instance where phi was built in shed mode)
+//   dc_series_launch_cols     per column over the `rb` rows of the block: c_max / c_viol [ldt], the worst loading (NaN aside) and the rows above thr
+//   dc_series_launch_base     base [T][3]: a column's case without an outage -- worst loading, its branch (1-based, 0: none), branches above thr
+// Launches on the handle's stream; phi->row_rinv is the caller's to set first (dc_phi_rinv).
+struct DcSeriesBlock { const DcPhi* phi; const double* F0; int ldt, T; double* load; int* branch; int* count; };
+void dc_series_launch_screen(DcHandle* h, const DcSeriesBlock& b, int k0, int k1, double thr);
+void dc_series_launch_cols(DcHandle* h, const DcSeriesBlock& b, double* c_max, int* c_viol, double thr, int rb);
+void dc_series_launch_base(DcHandle* h, const DcSeriesBlock& b, double* base, double thr);
+
 void dc_series_free(DcHandle* h);            // releases what the series screen holds (jg_dc_destroy, jg_dc_series_release)
 
 }  // namespace jg

@@ -9,6 +9,7 @@
   the same loop over ALL pairs of a candidate list          dcPairScreen (the DC N-2 screen: csrc/jg_dc_pair.hpp)
   the N-1 loop inside a loop over injection profiles        dcSeriesScreen (csrc/jg_dc_series.hpp)
   the N-1 loop while the injections move along a direction  dcTransferScreen (the transfer capability: csrc/jg_dc_transfer.hpp)
+  updateGenerator!(g, status = 0) alone and around the N-1 loop   dcGeneratorScreen (dcgenerator.py; csrc/jg_dc_generator.hpp)
 
 All numerics run in libjgrid_hip.so (csrc/jg_dc.hip); the O(n) bus / generator bookkeeping of power! runs here.  A batched analysis keeps
 `batch` scenarios of ONE grid on the device; arrays are [batch, ...] (1-D for batch 1), as in the AC analysis.

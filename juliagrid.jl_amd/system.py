@@ -66,7 +66,9 @@ class PowerSystem:
             layout=NS(bus=t["gen_bus"].astype(np.int64), status=t["gen_status"].astype(np.int8)),
             output=NS(active=t["gen_pg"].astype(np.float64), reactive=t["gen_qg"].astype(np.float64)),
             voltage=NS(magnitude=t["gen_vg"].astype(np.float64)),
-            capability=NS(minReactive=t.get("gen_qmin", np.zeros(ng)), maxReactive=t.get("gen_qmax", np.zeros(ng))),
+            # maxActive: the table's gen_pmax, else addGenerator!'s default, 5 x the output (generator.jl:40-44)
+            capability=NS(minReactive=t.get("gen_qmin", np.zeros(ng)), maxReactive=t.get("gen_qmax", np.zeros(ng)),
+                          maxActive=np.asarray(t["gen_pmax"], dtype=np.float64).copy() if "gen_pmax" in t else 5.0 * t["gen_pg"].astype(np.float64)),
         )
         # bus.supply = sum of in-service generator outputs, generator lists in index order
         # (load.jl:271-277, 589-596)
@@ -157,7 +159,7 @@ def _matpower_tables(path: str) -> dict:
         br_b=col(br, 4), br_tap=tap, br_shift=col(br, 9) * d2r,
         gen_bus=np.array([lab[int(r[0])] for r in gen]), gen_status=col(gen, 7).astype(np.int8),
         gen_pg=col(gen, 1) * binv, gen_qg=col(gen, 2) * binv, gen_vg=col(gen, 5),
-        gen_qmax=col(gen, 3) * binv, gen_qmin=col(gen, 4) * binv,
+        gen_qmax=col(gen, 3) * binv, gen_qmin=col(gen, 4) * binv, gen_pmax=col(gen, 8) * binv,
         slack_rule=np.array(["last"]),
     )
 
