@@ -6,6 +6,7 @@
 // vector traffic is the right-hand sides -- 16 bytes per (row, scenario).  The factor being constant also allows what a refactorising iteration
 // cannot afford: the sequential top of the elimination tree is ONE dense product with the explicit inverse of its Schur complement.
 #include "jg_comp.hpp"
+#include "jg_pf.hpp"
 
 #include <algorithm>
 #include <cstdio>
@@ -312,25 +313,17 @@ __global__ __launch_bounds__(64) void k_comp_fix(CompFixArgs a) {
         const int si = i == ba ? 0 : 1, sj = j == ba ? 0 : 1;
         double sn, cs;
         sincos(th[si] - th[sj], &sn, &cs);
-        const double ac = dg[e] * cs + db[e] * sn, ad = dg[e] * sn - db[e] * cs;
-        ds1[si] += v[sj] * ac; ds2[si] += v[sj] * ad;
+        const pf::Terms t = pf::entry_terms(dg[e], db[e], sn, cs);
+        ds1[si] += v[sj] * t.ac; ds2[si] += v[sj] * t.ad;
         if (i == j) { dgii[si] = dg[e]; dbii[si] = db[e]; continue; }
-        const double vi = v[si], vj = v[sj];
-        M[2 * si][2 * sj] += (mk & 1) ? vi * vj * ad : 0.0;          // dP_i/dtheta_j   equations.jl:109-111
-        M[2 * si][2 * sj + 1] += (mk & 2) ? vi * ac : 0.0;           // dP_i/dV_j       equations.jl:117-119
-        M[2 * si + 1][2 * sj] += (mk & 4) ? -(vi * vj) * ac : 0.0;   // dQ_i/dtheta_j   equations.jl:134-136
-        M[2 * si + 1][2 * sj + 1] += (mk & 8) ? vi * ad : 0.0;       // dQ_i/dV_j       equations.jl:142-144
+        const Blk o = pf::offdiag(mk, v[si], v[sj], t.ac, t.ad);
+        M[2 * si][2 * sj] += o.v00; M[2 * si][2 * sj + 1] += o.v01; M[2 * si + 1][2 * sj] += o.v10; M[2 * si + 1][2 * sj + 1] += o.v11;
     }
     double df[4] = {0.0, 0.0, 0.0, 0.0};
     for (int s = 0; s < (two ? 2 : 1); ++s) {
-        const double vi = v[s];
-        double d00 = -vi * ds2[s] - dbii[s] * (vi * vi), d01 = ds1[s] + dgii[s] * vi;      // equations.jl:105-107, 113-115
-        double d10 = vi * ds1[s] - dgii[s] * (vi * vi), d11 = ds2[s] - dbii[s] * vi;       // equations.jl:130-132, 138-140
-        double fp = vi * ds1[s], fq = vi * ds2[s];                                          // acPowerFlow.jl:676, 679
-        if (ty[s] == 3) { d00 = d01 = d10 = d11 = 0.0; fp = fq = 0.0; }                     // identity rows of the padded Jacobian do not move
-        else if (ty[s] == 2) { d01 = d10 = d11 = 0.0; fq = 0.0; }
-        M[2 * s][2 * s] += d00; M[2 * s][2 * s + 1] += d01; M[2 * s + 1][2 * s] += d10; M[2 * s + 1][2 * s + 1] += d11;
-        df[2 * s] = fp; df[2 * s + 1] = fq;
+        const pf::Row r = pf::pad(ty[s], 0.0, pf::row_closure(v[s], ds1[s], ds2[s], dgii[s], dbii[s], 0.0, 0.0));     // identity rows do not move; P, Q cancel in f_s - f_0
+        M[2 * s][2 * s] += r.d.v00; M[2 * s][2 * s + 1] += r.d.v01; M[2 * s + 1][2 * s] += r.d.v10; M[2 * s + 1][2 * s + 1] += r.d.v11;
+        df[2 * s] = r.fp; df[2 * s + 1] = r.fq;
     }
     // S = F' J_0^-1 E: the blocks of J_0^-1 at the positions (a,a), (a,b), (b,a), (b,b) of the Ybus pattern
     double S[4][4] = {{0.0}};

@@ -101,11 +101,13 @@ __host__ __device__ inline bool map_slot(int gact, int nx, int id, int& slot, in
     return true;
 }
 
+// 2x2 block of one scenario (outside the device half: the host check of jg_pf.hpp forms blocks too)
+struct Blk { double v00, v01, v10, v11; };
+
 #ifdef __HIPCC__
 __device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
 // 2x2 block / 2-vector of one scenario: two (one) 16-byte accesses
-struct Blk { double v00, v01, v10, v11; };
 // Addresses are formed as (wave-uniform base of the item) + (32-bit byte offset of the lane): the item index comes from a record in scalar
 // registers, so the base is scalar arithmetic and every access of a wave shares ONE offset register (global_load ... v_off, s[base] instead of a
 // 64-bit address pair computed per access on the vector ALU).  A batch row is at most 2^32 bytes: ld < 2^28 scenarios.

@@ -31,6 +31,7 @@
 
 #include "../../include/jgrid.h"
 #include "jg_engine.hpp"
+#include "jg_pf.hpp"
 #include "jg_comp.hpp"
 #include "jg_lanes.hpp"
 #include "jg_qlim.hpp"
@@ -42,6 +43,7 @@ thread_local std::string g_error;
 int fail(int code, const std::string& msg) { return jg::api_fail(code, msg); }
 #define NR_HIP JG_API_HIP
 using jg::uniform;
+namespace pf = jg::pf;             // the equations of the kernels below
 
 constexpr int ASM_ROWS = 16;   // bus rows per workgroup
 constexpr int ASM_WAVES = 4;
@@ -132,70 +134,50 @@ __global__ __launch_bounds__(64 * WAVES) void k_assemble(AsmArgs a) {
                 if (k >= cnt) break;
                 const int p = pc + k;
                 const int j = cm[k] & 0xffffff;
-                int mk = cm[k] >> 24;                          // bit0 dP/dth, bit1 dP/dV, bit2 dQ/dth, bit3 dQ/dV exist
+                int mk = cm[k] >> 24;                          // the existence bits of the entry (pf::offdiag)
                 if constexpr (LT) {                            // the host's rule (jg_nr_create) on the lane's types
                     const int tj = lane_type(lw[k], j);
                     const int rpm = ti != 3, rq = ti == 1, ct = tj != 3, cv = tj == 1;
                     mk = (rpm & ct) | ((rpm & cv) << 1) | ((rq & ct) << 2) | ((rq & cv) << 3);
                 }
                 double g = gb[k].x, bb = gb[k].y;
-#pragma unroll
-                for (int m = 0; m < MP; ++m)
-                    if (ppos[m] == p) { g += a.pdg[(size_t)m * ld + b]; bb += a.pdb[(size_t)m * ld + b]; }
+                pf::patched<MP>(p, ppos, a.pdg, a.pdb, ld, b, g, bb);
                 const double vj = vv[k];
                 double s, c;
                 sincos(thi - tt[k], &s, &c);
-                const double ac = g * c + bb * s;      // G cos + B sin
-                const double ad = g * s - bb * c;      // G sin - B cos
-                s1 += vj * ac;
-                s2 += vj * ad;
+                const pf::Terms t = pf::entry_terms(g, bb, s, c);
+                s1 += vj * t.ac; s2 += vj * t.ad;
                 if (j == i) { pd = de[k]; gii = g; bii = bb; continue; }
                 if (!JAC) continue;
-                // rows: P exists unless slack, Q exists for PQ; cols: theta unless slack, V for PQ (mask from the host)
                 // write-once stream (read back by the factorisation only): nontemporal, so the V/theta gathers keep the L2
-                jg::store_blk_nt(a.A, (size_t)de[k], b, ld,
-                                 (mk & 1) ? vi * vj * ad : 0.0,            // dP_i/dtheta_j   equations.jl:109-111
-                                 (mk & 2) ? vi * ac : 0.0,                 // dP_i/dV_j       equations.jl:117-119
-                                 (mk & 4) ? -(vi * vj) * ac : 0.0,         // dQ_i/dtheta_j   equations.jl:134-136
-                                 (mk & 8) ? vi * ad : 0.0);                // dQ_i/dV_j       equations.jl:142-144
+                const jg::Blk o = pf::offdiag(mk, vi, vj, t.ac, t.ad);
+                jg::store_blk_nt(a.A, (size_t)de[k], b, ld, o.v00, o.v01, o.v10, o.v11);
             }
         }
         if (!JAC && a.pq_out) jg::store_vec(a.pq_out, (size_t)i, b, ld, vi * s1, vi * s2);     // PiQi (acAnalysis.jl:891-896)
-        double fp = vi * s1 - pinj;                        // acPowerFlow.jl:676
-        double fq = vi * s2 - qinj;                        // acPowerFlow.jl:679
+        pf::Row r = pf::row_closure(vi, s1, s2, gii, bii, pinj, qinj);
         if (!JAC && a.fd_mode) {                           // fast Newton-Raphson: calc - spec / V  (acPowerFlow.jl:720-726, 952-961)
             const double vinv = 1.0 / vi;
-            fp = s1 - pinj * vinv;
-            fq = s2 - qinj * vinv;
+            r.fp = s1 - pinj * vinv; r.fq = s2 - qinj * vinv;
         }
-        double d00 = -vi * s2 - bii * (vi * vi);           // equations.jl:105-107, acPowerFlow.jl:872
-        double d01 = s1 + gii * vi;                        // equations.jl:113-115
-        double d10 = vi * s1 - gii * (vi * vi);            // equations.jl:130-132
-        double d11 = s2 - bii * vi;                        // equations.jl:138-140
-        if (ti == 3) { d00 = 1.0; d01 = 0.0; d10 = 0.0; d11 = 1.0; fp = 0.0; fq = 0.0; }
-        else if (ti == 2) { d01 = 0.0; d10 = 0.0; d11 = 1.0; fq = 0.0; }
+        r = pf::pad(ti, 1.0, r);
         if (JAC) {
             if (pre) {                                     // nobody updates this block: its 2x2 LU is the factorisation's whole work on it
-                const jg::Blk raw{d00, d01, d10, d11};
                 bool bad;
-                const jg::Blk f = jg::diag_lu(raw, jg::row_max(raw), bad);
-                if (bad) fp = __builtin_nan("");           // a singular block marks its scenario through the mismatch (k_check: NaN -> status 3)
-                d00 = f.v00; d01 = f.v01; d10 = f.v10; d11 = f.v11;
-                store_vec_nt(a.W, (size_t)pre - 1, b, ld, fp, fq);   // nontemporal like every other store of this pass: a plain store here
-                                                                       // cost 0.09 ms per pass at 512 scenarios (the V / theta gathers lost their L2 lines)
+                r.d = jg::diag_lu(r.d, jg::row_max(r.d), bad);
+                if (bad) r.fp = __builtin_nan("");         // a singular block marks its scenario through the mismatch (k_check: NaN -> status 3)
+                store_vec_nt(a.W, (size_t)pre - 1, b, ld, r.fp, r.fq);   // nontemporal like every other store of this pass: a plain store here
+                                                                           // cost 0.09 ms per pass at 512 scenarios (the V / theta gathers lost their L2 lines)
             }
-            jg::store_blk_nt(a.A, (size_t)pd, b, ld, d00, d01, d10, d11);
+            jg::store_blk_nt(a.A, (size_t)pd, b, ld, r.d.v00, r.d.v01, r.d.v10, r.d.v11);
         }
         if (!JAC && a.fd_mode) {
-            if (a.fd_mode == 1) { jg::store_vec(a.F, (size_t)i, b, ld, fp, fq); jg::store_vec(a.R, (size_t)i, b, ld, fp, 0.0); }
-            else jg::store_vec(a.R, (size_t)i, b, ld, 0.0, fq);
+            if (a.fd_mode == 1) { jg::store_vec(a.F, (size_t)i, b, ld, r.fp, r.fq); jg::store_vec(a.R, (size_t)i, b, ld, r.fp, 0.0); }
+            else jg::store_vec(a.R, (size_t)i, b, ld, 0.0, r.fq);
         } else {
-            store_vec_nt(a.F, (size_t)i, b, ld, fp, fq);
+            store_vec_nt(a.F, (size_t)i, b, ld, r.fp, r.fq);
         }
-        // NaN-propagating max: a NaN mismatch must not look converged
-        const double afp = fabs(fp), afq = fabs(fq);
-        maxp = (afp > maxp || afp != afp) ? afp : maxp;
-        maxq = (afq > maxq || afq != afq) ? afq : maxq;
+        maxp = pf::nanmax(fabs(r.fp), maxp); maxq = pf::nanmax(fabs(r.fq), maxq);
     }
     red[0][wave][lane] = maxp;
     red[1][wave][lane] = maxq;
@@ -203,9 +185,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_assemble(AsmArgs a) {
     if (wave == 0) {
 #pragma unroll
         for (int w = 1; w < WAVES; ++w) {
-            const double x = red[0][w][lane], y = red[1][w][lane];
-            maxp = (x > maxp || x != x) ? x : maxp;
-            maxq = (y > maxq || y != y) ? y : maxq;
+            maxp = pf::nanmax(red[0][w][lane], maxp); maxq = pf::nanmax(red[1][w][lane], maxq);
         }
         a.part[((size_t)bx * 2) * ld + b] = maxp;
         a.part[((size_t)bx * 2 + 1) * ld + b] = maxq;
@@ -261,20 +241,16 @@ __global__ __launch_bounds__(256) void k_assemble1(AsmArgs a) {
                 const int j = cm[k] & 0xffffff;
                 const int mk = cm[k] >> 24;
                 double g = gb[k].x, bb = gb[k].y;
-#pragma unroll
-                for (int m = 0; m < MP; ++m)
-                    if (ppos[m] == p) { g += a.pdg[(size_t)m * ld + b]; bb += a.pdb[(size_t)m * ld + b]; }
+                pf::patched<MP>(p, ppos, a.pdg, a.pdb, ld, b, g, bb);
                 const double vj = vv[k];
                 double s, c;
                 sincos(thi - tt[k], &s, &c);
-                const double ac = g * c + bb * s;
-                const double ad = g * s - bb * c;
-                s1 += vj * ac;
-                s2 += vj * ad;
+                const pf::Terms t = pf::entry_terms(g, bb, s, c);
+                s1 += vj * t.ac; s2 += vj * t.ad;
                 if (j == i) { pd = de[k]; gii = g; bii = bb; }
                 else if (JAC) {
-                    jg::store_blk(a.A, (size_t)de[k], b, ld,
-                                  (mk & 1) ? vi * vj * ad : 0.0, (mk & 2) ? vi * ac : 0.0, (mk & 4) ? -(vi * vj) * ac : 0.0, (mk & 8) ? vi * ad : 0.0);
+                    const jg::Blk o = pf::offdiag(mk, vi, vj, t.ac, t.ad);
+                    jg::store_blk(a.A, (size_t)de[k], b, ld, o.v00, o.v01, o.v10, o.v11);
                 }
             }
         }
@@ -285,35 +261,25 @@ __global__ __launch_bounds__(256) void k_assemble1(AsmArgs a) {
         s1 += __shfl_xor(s1, d); s2 += __shfl_xor(s2, d);
         gii += __shfl_xor(gii, d); bii += __shfl_xor(bii, d); pd += __shfl_xor(pd, d);
     }
-    double fp = vi * s1 - pinj;
-    double fq = vi * s2 - qinj;
-    double d00 = -vi * s2 - bii * (vi * vi);
-    double d01 = s1 + gii * vi;
-    double d10 = vi * s1 - gii * (vi * vi);
-    double d11 = s2 - bii * vi;
-    if (ti == 3) { d00 = 1.0; d01 = 0.0; d10 = 0.0; d11 = 1.0; fp = 0.0; fq = 0.0; }
-    else if (ti == 2) { d01 = 0.0; d10 = 0.0; d11 = 1.0; fq = 0.0; }
+    pf::Row r = pf::pad(ti, 1.0, pf::row_closure(vi, s1, s2, gii, bii, pinj, qinj));
     if (JAC && pre) {
-        const jg::Blk raw{d00, d01, d10, d11};
         bool bad;
-        const jg::Blk f = jg::diag_lu(raw, jg::row_max(raw), bad);
-        if (bad) fp = __builtin_nan("");
-        d00 = f.v00; d01 = f.v01; d10 = f.v10; d11 = f.v11;
+        r.d = jg::diag_lu(r.d, jg::row_max(r.d), bad);
+        if (bad) r.fp = __builtin_nan("");
     }
     if (live && q == 0) {
         if (JAC) {
-            if (pre) jg::store_vec(a.W, (size_t)pre - 1, b, ld, fp, fq);
-            jg::store_blk(a.A, (size_t)pd, b, ld, d00, d01, d10, d11);
+            if (pre) jg::store_vec(a.W, (size_t)pre - 1, b, ld, r.fp, r.fq);
+            jg::store_blk(a.A, (size_t)pd, b, ld, r.d.v00, r.d.v01, r.d.v10, r.d.v11);
         }
-        jg::store_vec(a.F, (size_t)i, b, ld, fp, fq);
+        jg::store_vec(a.F, (size_t)i, b, ld, r.fp, r.fq);
     }
     // chunk maxima: ASM_ROWS consecutive rows = 4 ASM_ROWS consecutive lanes = one wave (NaN-propagating: a NaN mismatch must not look converged)
     static_assert(ASM_ROWS == 16, "a chunk of rows is one wave of quads");
-    double maxp = live ? fabs(fp) : 0.0, maxq = live ? fabs(fq) : 0.0;
+    double maxp = live ? fabs(r.fp) : 0.0, maxq = live ? fabs(r.fq) : 0.0;
     for (int d = 4; d < 64; d <<= 1) {
         const double x = __shfl_xor(maxp, d), y = __shfl_xor(maxq, d);
-        maxp = (x > maxp || x != x) ? x : maxp;
-        maxq = (y > maxq || y != y) ? y : maxq;
+        maxp = pf::nanmax(x, maxp); maxq = pf::nanmax(y, maxq);
     }
     if (live && ((int)threadIdx.x & 63) == 0) {
         const size_t ck = (size_t)(i0 / ASM_ROWS);
@@ -360,25 +326,21 @@ __global__ __launch_bounds__(64 * ASM_WAVES) void k_refine_residual(RefineArgs a
             const int cm = uniform(a.colm[p]);
             const int j = cm & 0xffffff, mk = cm >> 24;
             double2 gb = a.GB[p];
-#pragma unroll
-            for (int m = 0; m < MP; ++m)
-                if (ppos[m] == p) { gb.x += a.pdg[(size_t)m * ld + b]; gb.y += a.pdb[(size_t)m * ld + b]; }
+            pf::patched<MP>(p, ppos, a.pdg, a.pdb, ld, b, gb.x, gb.y);
             const double vj = a.vm[(size_t)j * ld + b];
             double s, c;
             sincos(thi - a.va[(size_t)j * ld + b], &s, &c);
-            const double ac = gb.x * c + gb.y * s, ad = gb.x * s - gb.y * c;
-            s1 += vj * ac;
-            s2 += vj * ad;
+            const pf::Terms t = pf::entry_terms(gb.x, gb.y, s, c);
+            s1 += vj * t.ac; s2 += vj * t.ad;
             if (j == i) { gii = gb.x; bii = gb.y; continue; }
             const double2 dj = jg::load_vec(a.inc, (size_t)j, b, ld);
-            rp -= ((mk & 1) ? vi * vj * ad : 0.0) * dj.x + ((mk & 2) ? vi * ac : 0.0) * dj.y;
-            rq -= ((mk & 4) ? -(vi * vj) * ac : 0.0) * dj.x + ((mk & 8) ? vi * ad : 0.0) * dj.y;
+            const jg::Blk o = pf::offdiag(mk, vi, vj, t.ac, t.ad);
+            rp -= o.v00 * dj.x + o.v01 * dj.y;
+            rq -= o.v10 * dj.x + o.v11 * dj.y;
         }
-        double d00 = -vi * s2 - bii * (vi * vi), d01 = s1 + gii * vi, d10 = vi * s1 - gii * (vi * vi), d11 = s2 - bii * vi;
-        if (ti == 3) { d00 = 1.0; d01 = 0.0; d10 = 0.0; d11 = 1.0; }
-        else if (ti == 2) { d01 = 0.0; d10 = 0.0; d11 = 1.0; }
-        rp -= d00 * di.x + d01 * di.y;
-        rq -= d10 * di.x + d11 * di.y;
+        const pf::Row r = pf::pad(ti, 1.0, pf::row_closure(vi, s1, s2, gii, bii, 0.0, 0.0));     // the block alone: the mismatch came in as F
+        rp -= r.d.v00 * di.x + r.d.v01 * di.y;
+        rq -= r.d.v10 * di.x + r.d.v11 * di.y;
         jg::store_vec(a.R, (size_t)i, b, ld, rp, rq);
     }
 }
@@ -426,22 +388,20 @@ __global__ __launch_bounds__(1024) void k_branch_quantities(BranchArgs a) {
     double si, ci, sj, cj;
     sincos(a.va[(size_t)i * ld + b], &si, &ci);
     sincos(a.va[(size_t)j * ld + b], &sj, &cj);
-    const double vir = Vi * ci, vii = Vi * si, vjr = Vj * cj, vji = Vj * sj;
-    // Iij = Vi yff + Vj yft, Iji = Vi ytf + Vj ytt (:921-927);  Vij = tij Vi - Vj (:846-851), Is = y Vij (:929-931)
-    const double ifr = vir * p[0] - vii * p[1] + vjr * p[2] - vji * p[3], ifi = vir * p[1] + vii * p[0] + vjr * p[3] + vji * p[2];
-    const double itr = vir * p[4] - vii * p[5] + vjr * p[6] - vji * p[7], iti = vir * p[5] + vii * p[4] + vjr * p[7] + vji * p[6];
-    const double wr = p[10] * vir - p[11] * vii - vjr, wi = p[10] * vii + p[11] * vir - vji;
+    const pf::BranchEnds e = pf::branch_ends(pf::TwoPort{{p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7]}}, Vi, Vj, si, ci, sj, cj);
+    // Vij = tij Vi - Vj (:846-851), Is = y Vij (:929-931)
+    const double wr = p[10] * e.vir - p[11] * e.vii - e.vjr, wi = p[10] * e.vii + p[11] * e.vir - e.vji;
     const double isr = p[8] * wr - p[9] * wi, isi = p[8] * wi + p[9] * wr;
     const double z = on ? 1.0 : 0.0;                                         // out of service: zeros, like initialize! (:66, :688)
-    if (a.from_pq) jg::store_vec(a.from_pq, (size_t)k, b, ld, z * (vir * ifr + vii * ifi), z * (vii * ifr - vir * ifi));      // Vi conj(Iij)
-    if (a.to_pq) jg::store_vec(a.to_pq, (size_t)k, b, ld, z * (vjr * itr + vji * iti), z * (vji * itr - vjr * iti));          // Vj conj(Iji)
+    if (a.from_pq) jg::store_vec(a.from_pq, (size_t)k, b, ld, z * e.pf, z * e.qf);                                            // Vi conj(Iij)
+    if (a.to_pq) jg::store_vec(a.to_pq, (size_t)k, b, ld, z * e.pt, z * e.qt);                                                // Vj conj(Iji)
     if (a.series_pq) jg::store_vec(a.series_pq, (size_t)k, b, ld, z * (wr * isr + wi * isi), z * (wi * isr - wr * isi));      // Vij conj(y Vij)
     if (a.charging_pq) {                                                     // 0.5 conj(g + jb) ((Vi/tau)^2 + Vj^2)  (:910-919)
         const double m = 0.5 * ((p[14] * Vi) * (p[14] * Vi) + Vj * Vj);
         jg::store_vec(a.charging_pq, (size_t)k, b, ld, z * p[12] * m, -z * p[13] * m);
     }
-    if (a.from_i) jg::store_vec(a.from_i, (size_t)k, b, ld, z * hypot(ifr, ifi), on ? atan2(ifi, ifr) : 0.0);
-    if (a.to_i) jg::store_vec(a.to_i, (size_t)k, b, ld, z * hypot(itr, iti), on ? atan2(iti, itr) : 0.0);
+    if (a.from_i) jg::store_vec(a.from_i, (size_t)k, b, ld, z * hypot(e.ifr, e.ifi), on ? atan2(e.ifi, e.ifr) : 0.0);
+    if (a.to_i) jg::store_vec(a.to_i, (size_t)k, b, ld, z * hypot(e.itr, e.iti), on ? atan2(e.iti, e.itr) : 0.0);
     if (a.series_i) jg::store_vec(a.series_i, (size_t)k, b, ld, z * hypot(isr, isi), on ? atan2(isi, isr) : 0.0);
 }
 
@@ -478,10 +438,8 @@ __global__ __launch_bounds__(1024) void k_screen_partial(ScreenArgs a) {
             double si, ci, sj, cj;
             sincos(a.va[(size_t)i * ld + b], &si, &ci);
             sincos(a.va[(size_t)j * ld + b], &sj, &cj);
-            const double vir = Vi * ci, vii = Vi * si, vjr = Vj * cj, vji = Vj * sj;
-            const double ifr = vir * p[0] - vii * p[1] + vjr * p[2] - vji * p[3], ifi = vir * p[1] + vii * p[0] + vjr * p[3] + vji * p[2];
-            const double itr = vir * p[4] - vii * p[5] + vjr * p[6] - vji * p[7], iti = vir * p[5] + vii * p[4] + vjr * p[7] + vji * p[6];
-            const double sf = hypot(vir * ifr + vii * ifi, vii * ifr - vir * ifi), st = hypot(vjr * itr + vji * iti, vji * itr - vjr * iti);
+            const pf::BranchEnds e = pf::branch_ends(pf::TwoPort{{p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7]}}, Vi, Vj, si, ci, sj, cj);
+            const double sf = hypot(e.pf, e.qf), st = hypot(e.pt, e.qt);
             const double s = on ? fmax(sf, st) : 0.0;
             if (s > m1) { m1 = s; i1 = (double)(k + 1); }
             const double r = a.rating ? ((CDbl)a.rating)[k] : 0.0;
@@ -558,8 +516,7 @@ __global__ __launch_bounds__(1024) void k_check(CheckArgs a) {
         }
 #pragma unroll
         for (int u = 0; u < CU; ++u) {
-            mp = (x[u] > mp || x[u] != x[u]) ? x[u] : mp;
-            mq = (y[u] > mq || y[u] != y[u]) ? y[u] : mq;
+            mp = pf::nanmax(x[u], mp); mq = pf::nanmax(y[u], mq);
         }
     }
     red[0][wave][lane] = mp;
@@ -567,9 +524,7 @@ __global__ __launch_bounds__(1024) void k_check(CheckArgs a) {
     __syncthreads();
     if (wave != 0) return;
     for (int w = 1; w < 16; ++w) {
-        const double x = red[0][w][lane], y = red[1][w][lane];
-        mp = (x > mp || x != x) ? x : mp;
-        mq = (y > mq || y != y) ? y : mq;
+        mp = pf::nanmax(red[0][w][lane], mp); mq = pf::nanmax(red[1][w][lane], mq);
     }
     a.normp[b] = mp;
     a.normq[b] = mq;
@@ -1063,15 +1018,14 @@ __global__ __launch_bounds__(1024) void k_verdict64(CheckArgs a, CompactArgs p) 
     const int maxit = (int)a.params[1];
     const int lus = a.lu_status[b], its = a.iters[b], act0 = a.active[b], st0 = a.status[b];
     double mp = 0.0, mq = 0.0;
-    auto nmax = [](double x, double m) { return (x > m || x != x) ? x : m; };      // NaN-propagating: a NaN mismatch must not look converged
     if (a.batch == 1) {
         // ONE scenario: the threads are CHUNKS (scenario 0 of chunk t, t + 1024, ...): one round trip where 16 waves of 64 identical lanes took two to five
         for (int c = wave * 64 + lane; c < a.nchunk; c += 1024) {
-            mp = nmax(a.part[((size_t)c * 2) * a.ld], mp);
-            mq = nmax(a.part[((size_t)c * 2 + 1) * a.ld], mq);
+            mp = pf::nanmax(a.part[((size_t)c * 2) * a.ld], mp);
+            mq = pf::nanmax(a.part[((size_t)c * 2 + 1) * a.ld], mq);
         }
 #pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) { mp = nmax(__shfl_xor(mp, d), mp); mq = nmax(__shfl_xor(mq, d), mq); }
+        for (int d = 32; d >= 1; d >>= 1) { mp = pf::nanmax(__shfl_xor(mp, d), mp); mq = pf::nanmax(__shfl_xor(mq, d), mq); }
         if (lane < 16) { red[0][wave][0] = mp; red[1][wave][0] = mq; }            // (lanes 0 .. 15 write the same value)
     } else {
         constexpr int CU = 20;
@@ -1083,7 +1037,7 @@ __global__ __launch_bounds__(1024) void k_verdict64(CheckArgs a, CompactArgs p) 
                 x[u] = a.part[((size_t)c * 2) * a.ld + b]; y[u] = a.part[((size_t)c * 2 + 1) * a.ld + b];
             }
 #pragma unroll
-            for (int u = 0; u < CU; ++u) { mp = nmax(x[u], mp); mq = nmax(y[u], mq); }
+            for (int u = 0; u < CU; ++u) { mp = pf::nanmax(x[u], mp); mq = pf::nanmax(y[u], mq); }
         }
         red[0][wave][lane] = mp;
         red[1][wave][lane] = mq;
@@ -1094,7 +1048,7 @@ __global__ __launch_bounds__(1024) void k_verdict64(CheckArgs a, CompactArgs p) 
     int act = act0, it_out = its, st_out = st0;
     if (!skip) {
         const int src = a.batch == 1 ? 0 : lane;                  // one scenario: every lane takes its maxima (lanes beyond the batch alias the last scenario)
-        for (int w = a.batch == 1 ? 0 : 1; w < 16; ++w) { mp = nmax(red[0][w][src], mp); mq = nmax(red[1][w][src], mq); }
+        for (int w = a.batch == 1 ? 0 : 1; w < 16; ++w) { mp = pf::nanmax(red[0][w][src], mp); mq = pf::nanmax(red[1][w][src], mq); }
         a.normp[b] = mp;
         a.normq[b] = mq;
         const bool real = b < a.batch;
