@@ -39,9 +39,10 @@ class DcPowerFlow:
         _lib.check(_lib.lib().jg_dc_create(C.byref(h), bus.number, B.colptr, B.rowval, np.ascontiguousarray(B.nzval, dtype=np.float64),
                                            int(bus.layout.slack), float(bus.voltage.angle[bus.layout.slack - 1]), self.batch, self.device))
         self._h = h.value
-        _lib.check(_lib.lib().jg_dc_set_branches(self._h, br.number, np.ascontiguousarray(br.layout.from_, dtype=np.int64),
-                                                 np.ascontiguousarray(br.layout.to, dtype=np.int64), np.ascontiguousarray(dc.admittance),
-                                                 np.ascontiguousarray(br.parameter.shiftAngle, dtype=np.float64)))
+        if br.number:                                                   # a grid without a branch (the slack alone) has no branch table: jg_dc_set_branches refuses nbr = 0
+            _lib.check(_lib.lib().jg_dc_set_branches(self._h, br.number, np.ascontiguousarray(br.layout.from_, dtype=np.int64),
+                                                     np.ascontiguousarray(br.layout.to, dtype=np.int64), np.ascontiguousarray(dc.admittance),
+                                                     np.ascontiguousarray(br.parameter.shiftAngle, dtype=np.float64)))
         self.voltage = NS(angle=self._shape(np.tile(bus.voltage.angle, (self.batch, 1))))
         self.power = NS(injection=NS(active=None), supply=NS(active=None), generator=NS(active=None), from_=NS(active=None), to=NS(active=None))
         self.method = NS(dcmodel=True)
@@ -255,7 +256,8 @@ def power_(an: DcPowerFlow):
     shunt, which is how a lane with an outage gets it without a matrix of its own."""
     sys_, bus, gen, br = an.system, an.system.bus, an.system.generator, an.system.branch
     fr = np.zeros((an.batch, br.number))
-    _lib.check(_lib.lib().jg_dc_get_flows(an._h, fr.reshape(-1)))
+    if br.number:                                                       # no branch: no flow kernel to launch (its grid would be empty), the flows are empty
+        _lib.check(_lib.lib().jg_dc_get_flows(an._h, fr.reshape(-1)))
     slack = bus.layout.slack - 1
     inj = np.tile(bus.supply.active - bus.demand.active, (an.batch, 1))
     if an._injection is not None:
