@@ -522,11 +522,6 @@ __global__ __launch_bounds__(64) void k_gn_obj_final(const double* part, int chu
     }
     obj[b] = acc;
 }
-// the columns of the scenario-major result record behind V | theta (jg::Lanes::collect2)
-__global__ void k_gn_pack_tail(const int* iters, const int* status, const double* obj, double* dst, int batch, long long stride, int off) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < batch) { double* q = dst + (size_t)b * stride + off; q[0] = (double)iters[b]; q[1] = (double)status[b]; q[2] = obj[b]; }
-}
 
 // max |increment| per scenario (partial per bus chunk); forces increment[slack theta] = 0 (:899)
 __global__ __launch_bounds__(256) void k_gn_norm(double* inc, double* part, int n, int slack, int ld) {
@@ -628,12 +623,10 @@ __global__ void k_gn_check(GnCheckArgs a) {
     if (a.mode == 0) return;
     const double tol = a.params[0];
     const int maxit = (int)a.params[1];
-    const bool conv = mx < tol;                                   // acStateEstimation.jl:1307
-    const bool bad = (a.lu_status[b] & 4) || mx != mx;
-    const bool act = b < a.batch && !conv && !bad && a.iters[b] < maxit;   // :1311
-    a.active[b] = act ? 1 : 0;
-    a.status[b] = conv ? 0 : (bad ? 3 : 1);
-    if (act) { a.iters[b] += 1; atomicAdd(a.counter, 1); atomicOr(a.group + (b >> 6), 1); }
+    const jg::Verdict v = jg::verdict(mx < tol, a.lu_status[b], mx != mx, a.iters + b, maxit, b < a.batch);
+    a.active[b] = v.go ? 1 : 0;
+    a.status[b] = v.status;
+    if (v.go) { a.iters[b] += 1; atomicAdd(a.counter, 1); atomicOr(a.group + (b >> 6), 1); }
 }
 
 // solve!: theta += inc[1:n], V += inc[n+1:2n] on active scenarios (:1040-1043)
@@ -647,11 +640,6 @@ __global__ __launch_bounds__(256) void k_gn_update(const double* inc, double* vm
         va[(size_t)i * ld + b] += iv.x;
         vm[(size_t)i * ld + b] += iv.y;
     }
-}
-
-__global__ void k_gn_add_iter(int* iters, int n) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < n) iters[b] += 1;
 }
 
 }  // namespace
@@ -1137,7 +1125,7 @@ int jg_gn_solve(jg_gn* h) {
     if (!h) return failg(1, "jg_gn_solve: bad argument");
     if (int rc = set_device(h)) return rc;
     launch_update(h, nullptr);
-    hipLaunchKernelGGL(k_gn_add_iter, dim3((h->ld + 255) / 256), dim3(256), 0, h->stream, h->d_iters, h->ld);
+    h->add_iter(h->d_iters);
     GN_HIP(hipGetLastError());
     GN_HIP(hipStreamSynchronize(h->stream));
     return 0;
@@ -1196,7 +1184,7 @@ int launch_pack(jg_gn* h, double* dst) {
     if (int rc = launch_objective(h)) return rc;
     const long long stride = 2LL * h->n + 3;
     h->collect2(h->d_vm, h->d_va, dst, h->n, stride);
-    hipLaunchKernelGGL(k_gn_pack_tail, dim3((h->batch + 255) / 256), dim3(256), 0, h->stream, h->d_iters, h->d_status, h->d_obj, dst, h->batch, stride, 2 * h->n);
+    h->pack_tail(h->d_iters, h->d_status, h->d_obj, dst, stride, 2 * h->n);
     GN_HIP(hipGetLastError());
     return 0;
 }

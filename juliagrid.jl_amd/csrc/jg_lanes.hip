@@ -50,6 +50,18 @@ __global__ __launch_bounds__(512) void k_lanes_collect(const double* vm, const d
     }
 }
 
+// The packed result of a batch is a scenario-major record [batch][stride]: V | theta | iterations | status [| objective] per scenario, one buffer for the one
+// gather of a sharded run.  V | theta: collect2; the columns behind them:
+__global__ void k_pack_tail(const int* iters, const int* status, const double* obj, double* dst, int batch, long long stride, int off) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < batch) { double* q = dst + (size_t)b * stride + off; q[0] = (double)iters[b]; q[1] = (double)status[b]; if (obj) q[2] = obj[b]; }
+}
+
+__global__ void k_add_iter(int* iters, int n) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < n) iters[b] += 1;
+}
+
 constexpr double POLL_BELOW_US = 800.0;   // a handle whose waits average more than this blocks in hipStreamSynchronize instead
 bool poll_enabled() { static const bool on = knob("POLL", 1) != 0; return on; }
 
@@ -128,6 +140,10 @@ void Lanes::collect(const double* src, double* dst, int rows) const {
 void Lanes::collect2(const double* a, const double* b, double* dst, int rows, long long stride) const {
     hipLaunchKernelGGL(k_lanes_collect, dim3((rows + 63) / 64, ld / 64, 2), dim3(64, 8), 0, stream, a, b, dst, rows, ld, batch, stride);
 }
+void Lanes::pack_tail(const int* iters, const int* status, const double* obj, double* dst, long long stride, int off) const {
+    hipLaunchKernelGGL(k_pack_tail, dim3((batch + 255) / 256), dim3(256), 0, stream, iters, status, obj, dst, batch, stride, off);
+}
+void Lanes::add_iter(int* iters) const { hipLaunchKernelGGL(k_add_iter, dim3((ld + 255) / 256), dim3(256), 0, stream, iters, ld); }
 
 // grows only (freeing it after every call would synchronise the device each time -- while another host thread of a pipeline may be capturing its hipGraph);
 // a grow frees the old block, after whatever still reads it on the stream has finished

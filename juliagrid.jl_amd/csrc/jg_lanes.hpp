@@ -33,6 +33,18 @@ private:
     int end(hipStream_t st, int rc);                    // ends the capture, instantiates if rc == 0, unlocks
 };
 
+// The loop control of powerFlow! and stateEstimation! for one scenario, after a check: converged = every norm STRICTLY below the tolerance
+// (acPowerFlow.jl:1410, acStateEstimation.jl:1307); bad = a zero or non-finite pivot (LU status bit 4) or a NaN norm; the scenario goes on while it is real,
+// neither converged nor bad and below the iteration limit (acPowerFlow.jl:1414, acStateEstimation.jl:1311).  A scenario that goes on counts its next solve!
+// at once (iteration += 1, acPowerFlow.jl:908) and is counted among the active ones: the caller's stores.  Status 0 converged, 3 numeric failure, 1 neither.
+// iters by address: it is read only where the rest of the rule leaves the question open, as k_check and k_gn_check always read it (a reference would let
+// the compiler load it ahead of the branch).
+struct Verdict { int go; int status; };          // go: 0 or 1 (an int: a bool member comes back through a byte and costs k_gn_check a register)
+__device__ __forceinline__ Verdict verdict(bool conv, int lu_status, bool nan, const int* iters, int maxit, bool real) {
+    const bool bad = (lu_status & 4) || nan;
+    return Verdict{real && !conv && !bad && *iters < maxit, conv ? 0 : (bad ? 3 : 1)};
+}
+
 struct Part {                                           // one array of an arena: where its pointer goes, how many bytes it takes
     void** p; size_t bytes;
     template <class T> Part(T** p_, size_t bytes_) : p((void**)p_), bytes(bytes_) {}
@@ -62,6 +74,9 @@ struct Lanes {
     // [0, rows) and [rows, 2 rows) of a record dst [batch][stride]
     void collect(const double* src, double* dst, int rows) const;
     void collect2(const double* a, const double* b, double* dst, int rows, long long stride) const;
+    // the columns behind them, at off: iterations | status and, obj not null, the objective -- of every scenario; stream-ordered
+    void pack_tail(const int* iters, const int* status, const double* obj, double* dst, long long stride, int off) const;
+    void add_iter(int* iters) const;                                   // one solve! outside the loop: iteration += 1 in every lane; stream-ordered
 
     // host [batch][rows] (stride = rows), ONE [rows] for every scenario (stride 0) or rows at a pitch of the caller's own -> device dst [rows][ld]; lanes
     // beyond the batch repeat the last scenario.  Synchronised.

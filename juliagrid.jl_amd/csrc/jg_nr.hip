@@ -33,6 +33,7 @@
 #include "jg_engine.hpp"
 #include "jg_pf.hpp"
 #include "jg_comp.hpp"
+#include "jg_compact.hpp"
 #include "jg_lanes.hpp"
 #include "jg_qlim.hpp"
 
@@ -531,308 +532,12 @@ __global__ __launch_bounds__(1024) void k_check(CheckArgs a) {
     if (a.mode == 0) return;
     const double tol = a.params[0];
     const int maxit = (int)a.params[1];
-    const bool real = b < a.batch;
-    const bool conv = mp < tol && mq < tol;                       // acPowerFlow.jl:1410 (strict)
-    const bool bad = (a.lu_status[b] & 4) || mp != mp || mq != mq;
-    const bool act = real && !conv && !bad && a.iters[b] < maxit; // acPowerFlow.jl:1414
-    a.active[b] = act ? 1 : 0;
-    a.status[b] = conv ? 0 : (bad ? 3 : 1);
-    if (act) { a.iters[b] += 1; atomicAdd(a.counter, 1); }        // solve! follows: iteration += 1 (:908)
+    const jg::Verdict v = jg::verdict(mp < tol && mq < tol, a.lu_status[b], mp != mp || mq != mq, a.iters + b, maxit, b < a.batch);
+    a.active[b] = v.go ? 1 : 0;
+    a.status[b] = v.status;
+    if (v.go) { a.iters[b] += 1; atomicAdd(a.counter, 1); }
 }
 
-// ---- scenario compaction ------------------------------------------------------------------------
-// Scenarios converge after different iteration counts (2..10 on N-1 sets).  Once enough have finished,
-// the still-active ones are packed into the leading lanes (stable partition) so whole 64-lane groups
-// drop out of every later launch.  flags: [0] permute this iteration, [1] active lanes, [2] groups in use,
-// [3] length of glist (the ids of the groups that still hold an active lane; the launches spread exactly those).
-struct CompactArgs {
-    int* active; int* iters; int* status; int* lu_status; int* lid; int* ppos; int mp;
-    int* dest; int* group; int* glist; int* flags; int* tmp; int ld; int restore;
-    int* host_count;           // nullable: pinned host word that receives the number of active scenarios (what the host loop polls:
-                               // a store from this kernel instead of a memset node and a 4-byte copy node per iteration, ~20 us each)
-    int* host_res;             // nullable (handles of ONE lane group): pinned host words [128] that receive iterations | status of the 64 lanes when the last scenario
-                               // has finished -- jg_nr_run then returns them without two blocking 4-byte-per-lane copies (~25 us each: a tenth of a single instance's solve
-                               // went into run_setup's and run_finish's small transfers, round 6)
-    const double* params;      // [2] = defer_at of the run (jg_nr_run_defer; 0: none).  Once at most that many scenarios are active the host stops the batch and
-                               // hands them to a pool (jg_nr_move_lanes): packing them into the first lane group -- and sending every lane home again when the
-                               // batch finishes -- moved every row of the handle twice for lanes that leave anyway (round 6: k_lanes_permute was 5.8 % of the GPU
-                               // time of the pipeline).  The lanes stay where they are; dest[0 .. n_active) lists them for the hand-off, flags[4] says so.
-};
-
-// inclusive scan over the 1024 threads of the workgroup: shuffles inside a wave, the 16 wave totals through LDS (two barriers; the
-// Hillis-Steele loop it replaces had twenty and made the verdict of a single instance 12 us long)
-__device__ __forceinline__ int block_scan_1024(int v, int* wsum, int t, int& total) {
-    const int lane = t & 63, w = t >> 6;
-    int x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const int y = __shfl_up(x, d, 64); if (lane >= d) x += y; }
-    if (lane == 63) wsum[w] = x;
-    __syncthreads();
-    int off = 0;
-    total = 0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) { const int q = wsum[k]; off += k < w ? q : 0; total += q; }
-    __syncthreads();
-    return x + off;
-}
-
-// run_setup on the device: parameters of the run, every real scenario active with zero iterations, lanes in home order, all lane groups in use
-__global__ void k_run_setup(double* params, double tol, double max_iter, double defer_at, int* iters, int* lu_status, int* active, int* lid, int* cflags, int* group, int* glist,
-                            int ld, int lanes, int keep_iters) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < ld) {
-        if (!keep_iters) { iters[b] = 0; lu_status[b] = 0; active[b] = b < lanes ? 1 : 0; }
-        lid[b] = b;
-    }
-    if (b < ld / 64) { group[b] = 1; glist[b] = b; }
-    if (b == 0) {
-        params[0] = tol; params[1] = max_iter; params[2] = defer_at;
-        cflags[0] = 0; cflags[1] = lanes; cflags[2] = ld / 64; cflags[3] = ld / 64; cflags[4] = 0; cflags[5] = 0; cflags[6] = 0; cflags[7] = 0;
-    }
-}
-
-__global__ __launch_bounds__(1024) void k_compact(CompactArgs a) {
-    __shared__ int wsum[16];
-    const int t = threadIdx.x;
-    const int ld = a.ld, ngroups = ld / 64;
-    const int per = (ld + 1023) / 1024;
-    const int b0 = t * per, b1 = min(b0 + per, ld);
-    int cnt = 0;
-    for (int b = b0; b < b1; ++b) cnt += a.active[b] != 0;
-    int n_active;
-    (void)block_scan_1024(cnt, wsum, t, n_active);
-    const int groups_new = (n_active + 63) / 64;
-    const int groups_cur = a.flags[2];
-    const int defer_at = a.params ? (int)a.params[2] : 0;
-    const bool hold = !a.restore && defer_at > 0 && n_active > 0 && n_active <= defer_at;
-    bool moved = false;
-    if (a.restore) {                                              // lanes that never left home need no pass over the rows
-        int away = 0;
-        for (int b = b0; b < b1; ++b) away += a.lid[b] != b;
-        int any;
-        (void)block_scan_1024(away, wsum, t, any);
-        moved = any > 0;
-    }
-    const bool permute = a.restore ? moved : (!hold && n_active > 0 && groups_new < groups_cur);
-    if (a.host_res && n_active == 0 && t < 64) { a.host_res[t] = a.iters[t]; a.host_res[64 + t] = a.status[t]; __threadfence_system(); }   // ... ahead of the word the host polls
-    __syncthreads();
-    if (t == 0) { a.flags[0] = permute ? 1 : 0; a.flags[1] = n_active; a.flags[4] = hold ? 1 : 0; if (permute) a.flags[2] = a.restore ? ngroups : groups_new; if (a.host_count) *a.host_count = n_active; }
-    if (a.restore && !permute) {
-        for (int g = t; g < ngroups; g += 1024) { a.group[g] = 1; a.glist[g] = g; }
-        if (t == 0) { a.flags[2] = ngroups; a.flags[3] = ngroups; }
-        return;
-    }
-    if (hold) {                                                   // the hand-off's list of the lanes that leave, in lane order
-        int tot;
-        const int incl = block_scan_1024(cnt, wsum, t, tot);
-        int r = incl - cnt;
-        for (int b = b0; b < b1; ++b) if (a.active[b] != 0) a.dest[r++] = b;
-    }
-    if (!permute) {                                               // groups = those that still hold an active lane
-        for (int g = t; g < ngroups; g += 1024) {
-            int any = 0;
-            for (int l = 0; l < 64; ++l) any |= a.active[g * 64 + l];
-            a.group[g] = any;
-        }
-        __syncthreads();
-        if (t == 0) {
-            int m = 0;
-            for (int g = 0; g < ngroups; ++g) if (a.group[g]) a.glist[m++] = g;
-            a.flags[3] = m;
-        }
-        return;
-    }
-    if (a.restore) {
-        for (int b = b0; b < b1; ++b) a.dest[b] = a.lid[b];      // send every lane home
-    } else {
-        // Minimal moves: an active lane inside the leading groups_new groups stays where it is; the k-th active lane behind them
-        // swaps with the k-th inactive lane inside them.  (A stable partition shifted almost every lane: 1 GB of lane rows per
-        // compaction of 512 scenarios of a 10 000-bus grid, and again for the way home; 37 stragglers of 512 now move 64 lanes.)
-        const int L = groups_new * 64;
-        int holes = 0, outs = 0;
-        for (int b = b0; b < b1; ++b) { const bool act = a.active[b] != 0; holes += (b < L && !act); outs += (b >= L && act); a.dest[b] = b; }
-        int both;
-        const int incl = block_scan_1024(holes | outs << 16, wsum, t, both);   // both counts in one scan: ld < 65 536
-        int hr = (incl & 0xffff) - holes, orank = (incl >> 16) - outs;         // holes / outside actives in front of this thread's chunk
-        int* hole_at = a.tmp;                                     // [k] position of the k-th hole, [ld / 2 + k] of the k-th outside active lane
-        int* out_at = a.tmp + ld / 2;
-        const int n_out = both >> 16;                             // <= min(L, ld - L) <= ld / 2; the leading groups hold at least as many holes
-        for (int b = b0; b < b1; ++b) {
-            const bool act = a.active[b] != 0;
-            if (b < L && !act) { if (hr < n_out) hole_at[hr] = b; ++hr; }
-            if (b >= L && act) out_at[orank++] = b;
-        }
-        __syncthreads();
-        for (int k = t; k < n_out; k += 1024) { const int hpos = hole_at[k], opos = out_at[k]; a.dest[opos] = hpos; a.dest[hpos] = opos; }
-    }
-    __syncthreads();
-    int* arrays[5] = {a.active, a.iters, a.status, a.lu_status, a.lid};
-    for (int k = 0; k < 5 + a.mp; ++k) {
-        int* x = k < 5 ? arrays[k] : a.ppos + (size_t)(k - 5) * ld;
-        for (int b = b0; b < b1; ++b) a.tmp[a.dest[b]] = x[b];
-        __syncthreads();
-        for (int b = b0; b < b1; ++b) x[b] = a.tmp[b];
-        __syncthreads();
-    }
-    for (int g = t; g < ngroups; g += 1024) { a.group[g] = a.restore ? 1 : (g < groups_new); a.glist[g] = g; }
-    if (t == 0) a.flags[3] = a.restore ? ngroups : groups_new;
-}
-
-// dst[row][dest[b]] = src[row][b] for `rows` rows (no-op unless flags[0]); then the copy back
-// ELEM doubles per (row, lane): 1 for V / theta / P / Q rows, 2 for the interleaved mismatch / increment rows
-template <int ELEM>
-__global__ void k_lane_permute(const double* src, double* dst, const int* dest, const int* flags, int rows, int ld) {
-    if (!flags[0]) return;
-    const int b = blockIdx.y * 256 + threadIdx.x;
-    if (b >= ld) return;
-    const int d = dest[b];
-    if (d == b) return;
-    for (int r = blockIdx.x; r < rows; r += gridDim.x)
-#pragma unroll
-        for (int e = 0; e < ELEM; ++e) dst[((size_t)r * ld + d) * ELEM + e] = src[((size_t)r * ld + b) * ELEM + e];
-}
-
-template <int ELEM>
-__global__ void k_lane_copy(const double* src, double* dst, const int* dest, const int* flags, int rows, int ld) {
-    if (!flags[0]) return;
-    const int b = blockIdx.y * 256 + threadIdx.x;
-    if (b >= ld || dest[b] == b) return;
-    for (int r = blockIdx.x; r < rows; r += gridDim.x)
-#pragma unroll
-        for (int e = 0; e < ELEM; ++e) dst[((size_t)r * ld + b) * ELEM + e] = src[((size_t)r * ld + b) * ELEM + e];
-}
-
-// All per-scenario arrays of a compaction in TWO launches (scatter into the staging area, copy back) instead of two per array:
-// the launches are predicated on flags[0] and mostly return at once, so what they cost is their number.
-struct LaneSet { double* x[8]; int rows[8]; int elem[8]; long long off[8]; };
-__global__ void k_lanes_move(LaneSet s, double* tmp, const int* dest, const int* flags, int ld, int back) {
-    if (!flags[0]) return;
-    const int b = blockIdx.y * 256 + threadIdx.x;
-    if (b >= ld) return;
-    const int a = blockIdx.z;
-    const int rows = s.rows[a], E = s.elem[a];
-    double* x = s.x[a];
-    double* t = tmp + s.off[a];
-    const int d = dest[b];
-    if (d == b) return;                            // this lane stays (a permutation maps the lanes that move onto themselves)
-    if (E == 2) {                                  // interleaved 2-vectors: one 16-byte access per lane
-        double2* x2 = (double2*)x;
-        double2* t2 = (double2*)t;
-        for (int r = blockIdx.x; r < rows; r += gridDim.x) {
-            if (back) x2[(size_t)r * ld + b] = t2[(size_t)r * ld + b];
-            else t2[(size_t)r * ld + d] = x2[(size_t)r * ld + b];
-        }
-        return;
-    }
-    for (int r = blockIdx.x; r < rows; r += gridDim.x) {
-        if (back) x[(size_t)r * ld + b] = t[(size_t)r * ld + b];
-        else t[(size_t)r * ld + d] = x[(size_t)r * ld + b];
-    }
-}
-
-// The same move IN PLACE, one launch (round 5): dest is a permutation of the lanes (k_compact: swaps of a hole with a straggler; restore: every lane to its home), so a
-// workgroup that holds ALL lanes of a row reads what moves, waits for the values, meets at a barrier and writes them to their new lanes -- no staging area, half
-// the traffic and half the launches of the two-pass move (which remains for handles of more than LANES_INPLACE lanes).
-constexpr int LANES_INPLACE = 4096;
-__global__ __launch_bounds__(1024) void k_lanes_permute(LaneSet s, const int* dest, const int* flags, int ld) {
-    if (!flags[0]) return;
-    constexpr int NL = LANES_INPLACE / 1024;
-    const int a = blockIdx.z;
-    const int rows = s.rows[a], E = s.elem[a];
-    int b[NL], d[NL];
-#pragma unroll
-    for (int k = 0; k < NL; ++k) { b[k] = (int)threadIdx.x + k * 1024; d[k] = b[k] < ld ? dest[b[k]] : b[k]; }
-    if (E == 2) {
-        double2* x = (double2*)s.x[a];
-        for (int r = blockIdx.x; r < rows; r += gridDim.x) {
-            double2 v[NL];
-#pragma unroll
-            for (int k = 0; k < NL; ++k) if (d[k] != b[k]) v[k] = x[(size_t)r * ld + b[k]];
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the values are HERE before any lane of the row is overwritten
-            __syncthreads();
-#pragma unroll
-            for (int k = 0; k < NL; ++k) if (d[k] != b[k]) x[(size_t)r * ld + d[k]] = v[k];
-        }
-        return;
-    }
-    double* x = s.x[a];
-    for (int r = blockIdx.x; r < rows; r += gridDim.x) {
-        double v[NL];
-#pragma unroll
-        for (int k = 0; k < NL; ++k) if (d[k] != b[k]) v[k] = x[(size_t)r * ld + b[k]];
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < NL; ++k) if (d[k] != b[k]) x[(size_t)r * ld + d[k]] = v[k];
-    }
-}
-
-// [n][ld] batch-minor -> [batch][n] scenario-major, tiled through LDS so both sides stay coalesced.  What jg::Lanes::collect does on 64 x 64 tiles; kept for
-// jg_nr_get_voltage_device until the two have been timed against each other on that call (10k-bus grid, 512 lanes).
-__global__ void k_to_scenario_major(const double* src, double* dst, int n, int ld, int batch) {
-    __shared__ double tile[32][33];
-    const int i0 = blockIdx.x * 32, b0 = blockIdx.y * 32;
-    for (int r = threadIdx.y; r < 32; r += blockDim.y) {
-        const int i = i0 + r, b = b0 + threadIdx.x;
-        tile[r][threadIdx.x] = (i < n && b < ld) ? src[(size_t)i * ld + b] : 0.0;
-    }
-    __syncthreads();
-    for (int r = threadIdx.y; r < 32; r += blockDim.y) {
-        const int b = b0 + r, i = i0 + threadIdx.x;
-        if (b < batch && i < n) dst[(size_t)b * n + i] = tile[threadIdx.x][r];
-    }
-}
-
-// The packed result of a batch is a scenario-major record [batch][stride]: V | theta | iterations | status per scenario, one buffer for the one gather of a
-// sharded run.  V | theta: jg::Lanes::collect2; the two columns behind them:
-__global__ void k_pack_tail(const int* iters, const int* status, double* dst, int batch, long long stride, int off) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < batch) { dst[(size_t)b * stride + off] = (double)iters[b]; dst[(size_t)b * stride + off + 1] = (double)status[b]; }
-}
-
-// ---- straggler hand-off (jg_nr_move_lanes): the scenarios of a paused batch that are still active -- all inside its first
-// lane group -- continue in another handle of the same grid (a pool that collects the stragglers of several batches).
-// k_move_plan (one wave): pool lane of every active position, the per-lane integers, the home lane of each moved scenario; the
-// source lanes become inactive with status 4 (deferred).  k_move_rows: the per-lane rows (V, theta, P, Q, patch values).
-struct MovePlanArgs {
-    int* s_active; int* s_iters; int* s_status; const int* s_lid; const int* s_ppos; int s_ld;
-    int* d_active; int* d_iters; int* d_status; int* d_lu; int* d_ppos; int d_ld;
-    int* map; int* home; int* count; int mp; int lane0; int cap;
-    const int* s_flags; const int* s_list; int* srcl;          // the source's compaction flags / list of the lanes that leave (k_compact: hold); [64] source lane of candidate p
-};
-__global__ __launch_bounds__(64) void k_move_plan(MovePlanArgs a) {
-    const int p0 = threadIdx.x;
-    // where the p-th candidate sits: packed into the first lane group by a compaction, or -- the batch stopped for this hand-off (k_compact: hold) -- wherever
-    // it was, listed in the source's dest[]
-    const bool listed = a.s_flags[4] != 0;
-    const int p = listed ? (p0 < a.s_flags[1] ? a.s_list[p0] : -1) : p0;
-    a.srcl[p0] = p;
-    const bool act = p >= 0 && a.s_active[p] != 0;
-    const unsigned long long m = __ballot(act);
-    const int r = __popcll(m & ((1ull << p0) - 1ull));
-    const int total = __popcll(m);
-    const bool fits = a.lane0 + total <= a.cap;
-    if (p0 == 0) a.count[0] = fits ? total : -1;
-    a.map[p0] = -1;
-    if (!act || !fits) return;
-    const int d = a.lane0 + r;
-    a.map[p0] = d;
-    a.home[r] = a.s_lid[p];
-    a.d_active[d] = 1; a.d_iters[d] = a.s_iters[p]; a.d_status[d] = 1; a.d_lu[d] = 0;
-    for (int k = 0; k < a.mp; ++k) a.d_ppos[(size_t)k * a.d_ld + d] = a.s_ppos[(size_t)k * a.s_ld + p];
-    a.s_active[p] = 0; a.s_status[p] = 4;
-}
-struct MoveRowsArgs { const double* src[6]; double* dst[6]; int rows[6]; int s_ld; int d_ld; const int* map; const int* srcl; };
-__global__ __launch_bounds__(256) void k_move_rows(MoveRowsArgs a) {
-    const int p0 = threadIdx.x & 63, sub = threadIdx.x >> 6;
-    const int d = a.map[p0];
-    if (d < 0) return;
-    const int p = a.srcl[p0];
-    const int arr = blockIdx.y;
-    const double* s = a.src[arr];
-    double* t = a.dst[arr];
-    for (int r = blockIdx.x * 4 + sub; r < a.rows[arr]; r += gridDim.x * 4) t[(size_t)r * a.d_ld + d] = s[(size_t)r * a.s_ld + p];
-}
 // rows of a result record [.][stride] <- V | theta | iterations | status of lanes lane0 .. lane0 + count - 1 (rows[i] = record row)
 __global__ __launch_bounds__(256) void k_pack_rows(const double* vm, const double* va, const int* iters, const int* status, const int* rows,
                                                    double* dst, int n, int ld, int lane0, long long stride) {
@@ -841,11 +546,6 @@ __global__ __launch_bounds__(256) void k_pack_rows(const double* vm, const doubl
     double* out = dst + (size_t)rows[i] * stride;
     for (int j = blockIdx.x * 256 + threadIdx.x; j < n; j += gridDim.x * 256) { out[j] = vm[(size_t)j * ld + b]; out[n + j] = va[(size_t)j * ld + b]; }
     if (blockIdx.x == 0 && threadIdx.x == 0) { out[2 * n] = (double)iters[b]; out[2 * n + 1] = (double)status[b]; }
-}
-
-__global__ void k_add_iter(int* iters, int n) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < n) iters[b] += 1;
 }
 
 }  // namespace
@@ -871,6 +571,7 @@ struct jg_nr : jg::Lanes {             // Lanes: stream, batch, ld, the staging 
     double* d_vm0 = nullptr; double* d_va0 = nullptr;   // snapshot of the start point
     int* d_active = nullptr; int* d_iters = nullptr; int* d_status = nullptr; int* d_counter = nullptr; int* d_group = nullptr;
     int* d_lid = nullptr; int* d_dest = nullptr; int* d_cflags = nullptr; int* d_itmp = nullptr; int* d_glist = nullptr;   // scenario compaction (d_vm ... d_glist without d_dst, d_vm0, d_va0: ONE arena, jg_nr_create)
+    jg::Compaction cmp{};                             // ... what it works on (jg_compact.hpp), filled once by jg_nr_create
     bool refine = false;                              // one step of iterative refinement per Newton step (jg_nr_set_refine)
     bool fast = false;                                // fast decoupled mode (jg_nr_fast_setup): constant B', B'' factorised once
     std::vector<double> fast_blk;                     // ... the shared block matrix diag(B', B'') as set up [nnz][4] (engine block order)
@@ -956,7 +657,7 @@ unsigned char classify_patch(const jg_nr* h, const int* pos, int k) {
     return (b < 0 || joined) ? 1 : 2;
 }
 
-jg::GroupSel active_groups(jg_nr* h) { return jg::GroupSel{nullptr, h->d_glist, h->d_cflags + 3}; }
+jg::GroupSel active_groups(jg_nr* h) { return jg::GroupSel{nullptr, h->d_glist, h->d_cflags + jg::CF_LIST}; }
 
 // The runtime mp (0, 4, anything else = 8) and jac of a launch as template arguments: f(std::integral_constant<int, MP>{}[, std::bool_constant<JAC>{}])
 template <class F> void with_mp(int mp, F&& f) {
@@ -1007,7 +708,7 @@ void launch_assemble(jg_nr* h, const jg::GroupSel& sel = jg::GroupSel{}, bool ja
 // The verdict of a handle of ONE lane group in one launch (round 6): k_check's norms and loop control, then what k_compact comes to when there is nothing to pack --
 // the count of active scenarios for the host, the group list of the next launches, iterations | status for jg_nr_run when the last scenario has finished.  Two
 // launches (12.5 + 4 us of a single instance's 330 us iteration: five trips of dependent loads over the 625 chunk norms, a launch boundary) become one of two trips.
-__global__ __launch_bounds__(1024) void k_verdict64(CheckArgs a, CompactArgs p) {
+__global__ __launch_bounds__(1024) void k_verdict64(CheckArgs a, jg::CompactArgs p) {
     __shared__ double red[2][16][64];
     const int lane = threadIdx.x, wave = threadIdx.y;
     const int b = lane;
@@ -1051,15 +752,12 @@ __global__ __launch_bounds__(1024) void k_verdict64(CheckArgs a, CompactArgs p) 
         for (int w = a.batch == 1 ? 0 : 1; w < 16; ++w) { mp = pf::nanmax(red[0][w][src], mp); mq = pf::nanmax(red[1][w][src], mq); }
         a.normp[b] = mp;
         a.normq[b] = mq;
-        const bool real = b < a.batch;
-        const bool conv = mp < tol && mq < tol;                   // acPowerFlow.jl:1410 (strict)
-        const bool bad = (lus & 4) || mp != mp || mq != mq;
-        const bool go = real && !conv && !bad && its < maxit;     // acPowerFlow.jl:1414
-        act = go ? 1 : 0;
+        const jg::Verdict v = jg::verdict(mp < tol && mq < tol, lus, mp != mp || mq != mq, &its, maxit, b < a.batch);
+        act = v.go ? 1 : 0;
         a.active[b] = act;
-        st_out = conv ? 0 : (bad ? 3 : 1);
+        st_out = v.status;
         a.status[b] = st_out;
-        if (go) { it_out = its + 1; a.iters[b] = it_out; atomicAdd(a.counter, 1); }     // solve! follows: iteration += 1 (:908)
+        if (v.go) { it_out = its + 1; a.iters[b] = it_out; atomicAdd(a.counter, 1); }
     }
     const int n_active = __popcll(__ballot(act != 0));
     if (p.host_res && n_active == 0) { p.host_res[lane] = it_out; p.host_res[64 + lane] = st_out; __threadfence_system(); }   // ... ahead of the word the host polls
@@ -1075,63 +773,21 @@ __global__ __launch_bounds__(1024) void k_verdict64(CheckArgs a, CompactArgs p) 
 CheckArgs check_args(jg_nr* h, const int* group, int mode) {
     return CheckArgs{h->d_part, h->nchunk, h->ld, h->batch, h->d_params, h->d_normp, h->d_normq, h->d_active, h->d_iters, h->d_status, h->eng.status, h->d_counter, group, mode};
 }
-// report: the count of active scenarios goes to the pinned verdict word -- and, from a handle of ONE lane group, iterations | status behind it (host_res)
-CompactArgs compact_args(jg_nr* h, int restore, bool report) {
-    return CompactArgs{h->d_active, h->d_iters, h->d_status, h->eng.status, h->d_lid, h->d_ppos, h->mp, h->d_dest, h->d_group, h->d_glist, h->d_cflags, h->d_itmp, h->ld, restore,
-                       report ? h->h_counter_dev : nullptr, report && h->ld == 64 ? h->h_counter_dev + 1 : nullptr, h->d_params};
-}
 void launch_verdict64(jg_nr* h, bool report) {         // (handles of one lane group only)
-    hipLaunchKernelGGL(k_verdict64, dim3(1), dim3(64, 16), 0, h->stream, check_args(h, h->d_group, 1), compact_args(h, 0, report));
+    hipLaunchKernelGGL(k_verdict64, dim3(1), dim3(64, 16), 0, h->stream, check_args(h, h->d_group, 1), h->cmp.args(0, report));
 }
 
 void launch_check(jg_nr* h, int mode, const int* group = nullptr) {
     hipLaunchKernelGGL(k_check, dim3(h->ld / 64), dim3(64, 16), 0, h->stream, check_args(h, group, mode));
 }
 
-// pack the active scenarios into the leading lanes (restore = 1: send every lane back home)
+// pack the active scenarios into the leading lanes (restore = 1: send every lane back home), with everything a scenario owns
 void launch_compact(jg_nr* h, int restore, bool report = false) {
-    hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, h->stream, compact_args(h, restore, report));
-    if (h->ld == 64) return;                       // one lane group: nothing to pack, lanes never leave their home order
-    double* tmp = h->eng.X;                        // the factor is dead here (rebuilt by the next factorisation)
-    const dim3 block(256), gy((unsigned)((h->ld + 255) / 256));
-    {
-        LaneSet ls{};
-        int na = 0, max_rows = 0;
-        long long off = 0;
-        auto add = [&](double* x, int rows, int elem) {
-            ls.x[na] = x; ls.rows[na] = rows; ls.elem[na] = elem; ls.off[na] = off;
-            off += (long long)rows * elem * h->ld; max_rows = std::max(max_rows, rows); ++na;
-        };
-        add(h->d_vm, h->n, 1); add(h->d_va, h->n, 1); add(h->d_p, h->n, 1); add(h->d_q, h->n, 1);
-        if (h->mp > 0) { add(h->d_pdg, h->mp, 1); add(h->d_pdb, h->mp, 1); }
-        add(h->d_inc, h->n, 2);                    // a finished scenario keeps ITS last increment (method.increment) wherever its lane goes
-        if (h->lt_on) add((double*)h->d_lt, (h->n + 31) / 32, 1);      // the types of a scenario travel with it (8th and last slot)
-        static const bool inplace_env = jg::knob("LANES_INPLACE", 1) != 0;
-        if (h->ld <= LANES_INPLACE && inplace_env) {                      // one launch, in place (k_lanes_permute); JG_LANES_INPLACE=0: the two-pass move
-            hipLaunchKernelGGL(k_lanes_permute, dim3((unsigned)std::min(max_rows, 2048), 1, (unsigned)na), dim3((unsigned)std::min(1024, h->ld)), 0, h->stream, ls, h->d_dest, h->d_cflags, h->ld);
-            return;
-        }
-        if ((size_t)off * sizeof(double) <= h->eng.factor_bytes()) {      // always, except for grids of a handful of buses
-            const dim3 grid((unsigned)std::min(max_rows, 1024), gy.x, (unsigned)na);
-            hipLaunchKernelGGL(k_lanes_move, grid, block, 0, h->stream, ls, tmp, h->d_dest, h->d_cflags, h->ld, 0);
-            hipLaunchKernelGGL(k_lanes_move, grid, block, 0, h->stream, ls, tmp, h->d_dest, h->d_cflags, h->ld, 1);
-            return;
-        }
-    }
-    auto permute = [&](double* x, int rows) {
-        const dim3 grid((unsigned)std::min(rows, 2048), gy.x);
-        hipLaunchKernelGGL(k_lane_permute<1>, grid, block, 0, h->stream, x, tmp, h->d_dest, h->d_cflags, rows, h->ld);
-        hipLaunchKernelGGL(k_lane_copy<1>, grid, block, 0, h->stream, tmp, x, h->d_dest, h->d_cflags, rows, h->ld);
-    };
-    auto permute2 = [&](double* x, int rows) {                 // rows of interleaved 2-vectors
-        const dim3 grid((unsigned)std::min(rows, 2048), gy.x);
-        hipLaunchKernelGGL(k_lane_permute<2>, grid, block, 0, h->stream, x, tmp, h->d_dest, h->d_cflags, rows, h->ld);
-        hipLaunchKernelGGL(k_lane_copy<2>, grid, block, 0, h->stream, tmp, x, h->d_dest, h->d_cflags, rows, h->ld);
-    };
-    permute(h->d_vm, h->n); permute(h->d_va, h->n); permute(h->d_p, h->n); permute(h->d_q, h->n);
-    if (h->mp > 0) { permute(h->d_pdg, h->mp); permute(h->d_pdb, h->mp); }
-    permute2(h->d_inc, h->n);
-    if (h->lt_on) permute((double*)h->d_lt, (h->n + 31) / 32);
+    std::vector<jg::LaneRows> rows{{h->d_vm, h->n, 1}, {h->d_va, h->n, 1}, {h->d_p, h->n, 1}, {h->d_q, h->n, 1}};
+    if (h->mp > 0) { rows.push_back({h->d_pdg, h->mp, 1}); rows.push_back({h->d_pdb, h->mp, 1}); }
+    rows.push_back({h->d_inc, h->n, 2});           // a finished scenario keeps ITS last increment (method.increment) wherever its lane goes
+    if (h->lt_on) rows.push_back({(double*)h->d_lt, (h->n + 31) / 32, 1});      // the types of a scenario travel with it (8th and last slot)
+    h->cmp.launch_compact(h->stream, restore, report, rows);
 }
 
 // solve! numerics on the groups of `sel`: factorise the Jacobian that is in place, solve, update the state (active: nullable)
@@ -1171,7 +827,7 @@ int build_graphs(jg_nr* h) {
     auto verdict = [&]() {
         launch_assemble(h, active_groups(h), true, nullptr, 0, nullptr, true);
         check_and_compact();
-        if (h->ld > 64) launch_assemble(h, active_groups(h), true, nullptr, 0, h->d_cflags, true);
+        if (h->ld > 64) launch_assemble(h, active_groups(h), true, nullptr, 0, h->d_cflags + jg::CF_PERMUTE, true);
     };
     auto step = [&]() { const int rc = newton_step(h, active_groups(h), h->d_active); return rc ? fail(rc, h->eng.error) : 0; };
     // graph A: the verdict on the start point
@@ -1186,7 +842,7 @@ int build_graphs(jg_nr* h) {
         if (int rc = step()) return rc;
         launch_assemble(h, active_groups(h), false);
         check_and_compact();
-        if (h->ld > 64) launch_assemble(h, active_groups(h), false, nullptr, 0, h->d_cflags);
+        if (h->ld > 64) launch_assemble(h, active_groups(h), false, nullptr, 0, h->d_cflags + jg::CF_PERMUTE);
         return 0;
     });
     if (!rc) rc = h->gJ.capture(h->stream, [&] { launch_assemble(h, active_groups(h), true, nullptr, 0, nullptr, true); return 0; });
@@ -1253,7 +909,7 @@ int build_comp_graphs(jg_nr* h) {
         launch_assemble(h, active_groups(h), false);
         launch_check(h, 1, h->d_group);
         launch_compact(h, 0, true);
-        if (h->ld > 64) launch_assemble(h, active_groups(h), false, nullptr, 0, h->d_cflags);      // lanes moved: their mismatch rows again
+        if (h->ld > 64) launch_assemble(h, active_groups(h), false, nullptr, 0, h->d_cflags + jg::CF_PERMUTE);      // lanes moved: their mismatch rows again
         return 0;
     });
     if (!rc) rc = h->gC.capture(h->stream, [&] {
@@ -1265,7 +921,7 @@ int build_comp_graphs(jg_nr* h) {
         launch_assemble(h, active_groups(h), true, nullptr, 0, nullptr, true);
         launch_check(h, 1, h->d_group);
         launch_compact(h, 0, true);
-        if (h->ld > 64) launch_assemble(h, active_groups(h), true, nullptr, 0, h->d_cflags, true);
+        if (h->ld > 64) launch_assemble(h, active_groups(h), true, nullptr, 0, h->d_cflags + jg::CF_PERMUTE, true);
         return 0;
     });
     if (rc) drop_comp_graphs(h);
@@ -1532,6 +1188,9 @@ int jg_nr_create(jg_nr** out, int64_t n, const int64_t* colptr, const int64_t* r
         if (int rc = h->upload(&h->d_rowtype_pre, rt)) return rc;
     }
     h->eng.lanes = h->batch;
+    h->cmp = jg::Compaction{h->d_active, h->d_iters, h->d_status, h->eng.status, h->d_lid, h->d_ppos, h->d_dest, h->d_group, h->d_glist, h->d_cflags, h->d_itmp,
+                            h->mp, h->ld, h->d_params, h->h_counter_dev, h->eng.X, h->eng.factor_bytes()};
+    if (!h->cmp.fits(2 * (size_t)n)) return fail(1, "jg_nr_create: the factor storage does not hold one increment (the staging area of the lane moves)");
     for (int64_t k = 0; k < h->nnzJ; ++k) h->jmap[k] = (int64_t)h->eng.plan->S.src_entry[h->jmap[k] >> 2] * 4 + (h->jmap[k] & 3);
     if (timing) fprintf(stderr, "[jg nr create] done at                                 %6.1f ms\n", tnow() - tc0);
     unwind.h = nullptr;
@@ -1612,9 +1271,8 @@ int jg_nr_restore_voltage(jg_nr* h) {
 int jg_nr_get_voltage_device(jg_nr* h, double* vm_dev, double* va_dev) {
     if (!h || !vm_dev || !va_dev) return fail(1, "jg_nr_get_voltage_device: bad argument");
     if (int rc = set_device(h)) return rc;
-    dim3 grid((h->n + 31) / 32, (h->ld + 31) / 32), block(32, 8);
-    hipLaunchKernelGGL(k_to_scenario_major, grid, block, 0, h->stream, h->d_vm, vm_dev, h->n, h->ld, h->batch);
-    hipLaunchKernelGGL(k_to_scenario_major, grid, block, 0, h->stream, h->d_va, va_dev, h->n, h->ld, h->batch);
+    h->collect(h->d_vm, vm_dev, h->n);
+    h->collect(h->d_va, va_dev, h->n);
     NR_HIP(hipGetLastError());
     NR_HIP(hipStreamSynchronize(h->stream));
     return 0;
@@ -1625,7 +1283,7 @@ int jg_nr_pack_results_device(jg_nr* h, double* dst_dev) {
     if (int rc = set_device(h)) return rc;
     const long long stride = 2LL * h->n + 2;
     h->collect2(h->d_vm, h->d_va, dst_dev, h->n, stride);
-    hipLaunchKernelGGL(k_pack_tail, dim3((h->batch + 255) / 256), dim3(256), 0, h->stream, h->d_iters, h->d_status, dst_dev, h->batch, stride, 2 * h->n);
+    h->pack_tail(h->d_iters, h->d_status, nullptr, dst_dev, stride, 2 * h->n);
     NR_HIP(hipGetLastError());
     NR_HIP(hipStreamSynchronize(h->stream));
     return 0;
@@ -1639,7 +1297,7 @@ int jg_nr_allgather_results(jg_nr* h, jg_comm* c, double* dst_dev) {
     const size_t count = (size_t)h->batch * stride;
     double* mine = dst_dev + (size_t)jg::comm_rank(c) * count;   // in-place all-gather: this rank's record sits in its own block
     h->collect2(h->d_vm, h->d_va, mine, h->n, stride);
-    hipLaunchKernelGGL(k_pack_tail, dim3((h->batch + 255) / 256), dim3(256), 0, h->stream, h->d_iters, h->d_status, mine, h->batch, stride, 2 * h->n);
+    h->pack_tail(h->d_iters, h->d_status, nullptr, mine, stride, 2 * h->n);
     NR_HIP(hipGetLastError());
     if (int rc = jg::comm_allgather(c, mine, dst_dev, count, h->stream)) return rc;
     NR_HIP(hipStreamSynchronize(h->stream));
@@ -1753,7 +1411,7 @@ int jg_nr_solve(jg_nr* h) {
     h->f_stale = false;                                          // method.mismatch = the mismatch this step started from, for every scenario
     NR_HIP(hipMemsetAsync(h->eng.status, 0, (size_t)h->ld * 4, h->stream));
     if (int rc = newton_step(h, jg::GroupSel{}, nullptr)) return fail(rc, h->eng.error);
-    hipLaunchKernelGGL(k_add_iter, dim3((h->ld + 255) / 256), dim3(256), 0, h->stream, h->d_iters, h->ld);
+    h->add_iter(h->d_iters);
     NR_HIP(hipGetLastError());
     NR_HIP(hipStreamSynchronize(h->stream));
     h->jac_valid = false;
@@ -1800,8 +1458,7 @@ namespace {
 // ~90 us on the host's side of every solve, 7 % of a single instance's.
 int run_setup(jg_nr* h, int64_t max_iter, double tol, int lanes, bool keep_iters, int defer_at = 0) {
     if (int rc = build_graphs(h)) return rc;
-    hipLaunchKernelGGL(k_run_setup, dim3((unsigned)((h->ld + 255) / 256)), dim3(256), 0, h->stream, h->d_params, tol, (double)max_iter, (double)defer_at,   // defer_at: see CompactArgs
-                       h->d_iters /* acPowerFlow.jl:1401 */, h->eng.status, h->d_active, h->d_lid, h->d_cflags, h->d_group, h->d_glist, h->ld, lanes, keep_iters ? 1 : 0);
+    h->cmp.run_setup(h->stream, tol, (double)max_iter, (double)defer_at, lanes, keep_iters);      // defer_at: see jg::CompactArgs
     NR_HIP(hipGetLastError());
     h->res_pinned = h->ld == 64;
     return 0;
@@ -1837,7 +1494,7 @@ int run_loop(jg_nr* h, int64_t max_iter, int defer_at) {
             int cf[4];
             jg::sync_copy(cf, h->d_cflags, sizeof(cf), hipMemcpyDeviceToHost, h->stream);
             fprintf(stderr, "[jg_nr_run] iteration %lld: %.1f us, %d scenarios still active, %d of %d lane groups in use%s%s\n", (long long)it + 1,
-                    now_us() - tc, *h->h_counter, cf[2], h->ld / 64, cf[0] ? " (compacted)" : "", guess_last ? " (verdict without a Jacobian)" : "");
+                    now_us() - tc, *h->h_counter, cf[jg::CF_GROUPS], h->ld / 64, cf[jg::CF_PERMUTE] ? " (compacted)" : "", guess_last ? " (verdict without a Jacobian)" : "");
         }
     }
     h->stop_hint = h->iter_graphs;
@@ -2117,24 +1774,16 @@ int jg_nr_move_lanes(jg_nr* dst, int64_t dst_lane0, jg_nr* src, int32_t* home, i
     if (int rc = set_device(dst)) return rc;
     for (jg_nr* h : {dst, src})
         if (!h->d_move) {
-            NR_HIP(h->alloc(&h->d_move, 193));
+            NR_HIP(h->alloc(&h->d_move, jg::MOVE_WORDS));
             NR_HIP(h->pin(&h->h_move, 65));
         }
     NR_HIP(hipStreamSynchronize(src->stream));
-    int* map = dst->d_move; int* d_home = dst->d_move + 64; int* d_count = dst->d_move + 128;
-    MovePlanArgs pa{src->d_active, src->d_iters, src->d_status, src->d_lid, src->d_ppos, src->ld,
-                    dst->d_active, dst->d_iters, dst->d_status, dst->eng.status, dst->d_ppos, dst->ld,
-                    map, d_home, d_count, src->mp, (int)dst_lane0, dst->batch, src->d_cflags, src->d_dest, dst->d_move + 129};
-    hipLaunchKernelGGL(k_move_plan, dim3(1), dim3(64), 0, dst->stream, pa);
-    MoveRowsArgs ra{};
-    int na = 0;
-    auto add = [&](const double* s, double* t, int rows) { ra.src[na] = s; ra.dst[na] = t; ra.rows[na] = rows; ++na; };
-    add(src->d_vm, dst->d_vm, src->n); add(src->d_va, dst->d_va, src->n); add(src->d_p, dst->d_p, src->n); add(src->d_q, dst->d_q, src->n);
-    if (src->mp > 0) { add(src->d_pdg, dst->d_pdg, src->mp); add(src->d_pdb, dst->d_pdb, src->mp); }
-    ra.s_ld = src->ld; ra.d_ld = dst->ld; ra.map = map; ra.srcl = dst->d_move + 129;
-    hipLaunchKernelGGL(k_move_rows, dim3((unsigned)std::min((src->n + 3) / 4, 1024), (unsigned)na), dim3(256), 0, dst->stream, ra);
+    src->cmp.launch_move_plan(dst->stream, dst->cmp, dst->d_move, (int)dst_lane0, dst->batch);
+    std::vector<jg::LanePair> rows{{src->d_vm, dst->d_vm, src->n}, {src->d_va, dst->d_va, src->n}, {src->d_p, dst->d_p, src->n}, {src->d_q, dst->d_q, src->n}};
+    if (src->mp > 0) { rows.push_back({src->d_pdg, dst->d_pdg, src->mp}); rows.push_back({src->d_pdb, dst->d_pdb, src->mp}); }
+    src->cmp.launch_move_rows(dst->stream, dst->cmp, dst->d_move, rows);
     NR_HIP(hipGetLastError());
-    NR_HIP(hipMemcpyAsync(dst->h_move, d_home, 65 * sizeof(int), hipMemcpyDeviceToHost, dst->stream));
+    NR_HIP(hipMemcpyAsync(dst->h_move, dst->d_move + jg::MOVE_HOME, 65 * sizeof(int), hipMemcpyDeviceToHost, dst->stream));
     NR_HIP(hipStreamSynchronize(dst->stream));
     const int c = dst->h_move[64];
     if (c < 0) return fail(1, "jg_nr_move_lanes: the destination has not enough free lanes");
@@ -2368,7 +2017,7 @@ int jg_nr_fast_solve(jg_nr* h) {
     h->fast_mask = nullptr;
     if (int rc = fast_half(h, 1)) return rc;
     if (int rc = fast_half(h, 2)) return rc;
-    hipLaunchKernelGGL(k_add_iter, dim3((h->ld + 255) / 256), dim3(256), 0, h->stream, h->d_iters, h->ld);
+    h->add_iter(h->d_iters);
     NR_HIP(hipGetLastError());
     NR_HIP(hipStreamSynchronize(h->stream));
     return 0;

@@ -1,7 +1,7 @@
 """Batches of 1 024 to 4 160 lanes -- what contingency.recommendedLanes hands every grid below 5 000 buses -- held against the oracle, lane by lane.
 
 Everything here depends on the LANE count, not on the grid, so the grids are small (14, 118 and 1 354 buses) and the oracle solves a scenario in well under a
-millisecond.  What these widths reach and narrower tests do not (csrc/jg_engine.hpp: map_block; csrc/jg_nr.hip: k_compact, k_lanes_permute, k_lanes_move, k_check;
+millisecond.  What these widths reach and narrower tests do not (csrc/jg_engine.hpp: map_block; csrc/jg_compact.hip: k_compact, k_lanes_permute, k_lanes_move; csrc/jg_nr.hip: k_check;
 csrc/jg_gn.hip: k_gn_gain; csrc/jg_comp.hip: k_csweep, k_ctop):
   * 16, 32 and 64 pinned lane groups; 17 and 65 balanced groups with the group list read from memory; after compaction a count of the OTHER mapping class under
     a grid sized for the handle's class (9..15 groups under 16, the eight-entry scalar list under 17, ...);
@@ -198,6 +198,94 @@ def test_every_lane_of_a_wide_batch_equals_the_oracle(jg, oracle, lanes):
         r = ref[b]
         assert np.abs(inc[b] - r.inc).max() <= 1e-9 * max(1.0, np.abs(r.inc).max()) + 1e-12, b
         assert np.abs(f[b]).max() < 1e-8 and np.abs(r.f).max() < 1e-8
+    an.close()
+
+
+# ---- the lane move one array at a time (csrc/jg_compact.hip: Compaction::launch_compact) ----------------------------------------------------------------
+# Above 4 096 lanes the lanes move in two passes through the factor storage, all arrays at once when they fit it together: 6 n + 2 max_patch doubles per lane (V, theta,
+# P, Q, the increment, the patch values) against 4 (factor entries + Jordan rows).  Only grids of a handful of buses miss that, and move one array at a time.
+#   ring of 3 buses, max_patch 8: 34 staged doubles per lane against 4 (9 + 0) = 36: all arrays at once (the smallest meshed grid; nothing meshed falls below);
+#   path of 3 buses, max_patch 8: 34 against 4 (7 + 0) = 28: ONE ARRAY AT A TIME.
+# Scenario b scales the demand by a factor from a hash of b and starts from the flat start perturbed by _amp(b) x noise_b.
+TINY = {"ring 3": [(0, 1), (1, 2), (2, 0)], "path 3": [(0, 1), (1, 2)]}
+TINY_LANES, TINY_PATCH, TINY_SEED, TINY_NOISE = 4097, 8, 3, 981      # the noise seed was chosen on the oracle alone, for the margins (as NOISE_SEED above)
+
+
+def _tiny(jg, oracle, name):
+    """slack, one PV bus, one PQ bus (tests/dc_grids.py: table, with a reactive demand added); the scenario family of TINY_LANES lanes, built once"""
+    key = "tiny:" + name
+    if key not in _CTX:
+        from dc_grids import table
+        t = table(3, TINY[name], 0, TINY_SEED, units=1)
+        t["bus_qd"] = 0.4 * t["bus_pd"]
+        s = jg.powerSystem(t)
+        jg.acModel_(s)
+        osys = oracle.OracleSystem(t)
+        flat = oracle.OracleNR(osys)
+        n = osys.n
+        b = np.arange(TINY_LANES)
+        b[-1] = 3                                                  # the last lane repeats lane 3
+        factor = 0.5 + 1.5 * _hash01(b, 3)
+        rng = np.random.default_rng(TINY_NOISE)
+        noise_v, noise_a = rng.uniform(-1, 1, (TINY_LANES, n)), rng.uniform(-1, 1, (TINY_LANES, n))
+        noise_v[-1], noise_a[-1] = noise_v[3], noise_a[3]
+        amp = _amp(b)[:, None]
+        Y = s.model.ac.nodalMatrix
+        entries = len(jg._lib.Plan(n, Y.colptr - 1, Y.rowval - 1).get("e_row"))
+        _CTX[key] = NS(t=t, s=s, osys=osys, n=n, pd=osys.pd[None, :] * factor[:, None], qd=osys.qd[None, :] * factor[:, None],
+                       vm=flat.vm[None, :] * (1.0 + 0.04 * amp * noise_v), va=flat.va[None, :] + 0.15 * amp * noise_a, oracle=oracle,
+                       staged=6 * n + 2 * TINY_PATCH, factor=4 * entries, ref=None)
+    return _CTX[key]
+
+
+def _tiny_preconditions(jg, oracle, name):
+    """The oracle's runs alone: every lane converges clear of the tolerance, and the lane groups in use fall at least once to a count >= 1 -- a compaction that
+    permutes while lanes are active, and a restore that sends lanes home."""
+    g = _tiny(jg, oracle, name)
+    if g.ref is None:
+        g.ref = []
+        for b in range(TINY_LANES):
+            o = oracle.OracleNR(g.osys)
+            o.set_power(g.osys.ps, g.osys.qs, g.pd[b], g.qd[b])
+            o.set_voltage(g.vm[b], g.va[b])
+            g.ref.append(_finish(o, o.power_flow(iteration=ITERATION, tolerance=TOLERANCE)))
+    st, it = np.array([r.status for r in g.ref]), np.array([r.iteration for r in g.ref])
+    assert np.all(st == 0), np.flatnonzero(st != 0)[:10]
+    bad = [b for b, r in enumerate(g.ref) if not _margins_hold(r)]
+    assert not bad, f"oracle runs that stop within {MARGIN:g} of the tolerance: lanes {bad[:10]}, last two checks {[g.ref[b].history[-2:].tolist() for b in bad[:10]]}"
+    seq = _groups_in_use(it)
+    assert any(1 <= b < a for a, b in zip(seq, seq[1:])), seq
+    assert (g.staged > g.factor) == (name == "path 3"), (name, g.staged, g.factor)      # which of the two staged moves the width takes
+    return g, it, seq
+
+
+@pytest.mark.parametrize("name", list(TINY))
+def test_the_oracle_side_of_the_tiny_grids_holds_its_preconditions(jg, oracle, name):
+    g, it, seq = _tiny_preconditions(jg, oracle, name)
+    print(f"[tiny {name}] oracle: iterations {np.bincount(it).tolist()}, groups in use {seq}; {g.staged} staged doubles per lane against {g.factor} of the factor")
+
+
+@gpu
+@pytest.mark.parametrize("name", list(TINY))
+def test_lanes_of_a_tiny_grid_move_through_a_factor_too_small_for_all_arrays(jg, oracle, name):
+    """4 097 lanes (65 groups: the two-pass move) of a 3-bus grid.  On the path all arrays together exceed the factor storage (34 doubles per lane against 28), so
+    every compaction and the restore move ONE ARRAY AT A TIME; on the ring they just fit (34 against 36) and go at once.  Either way: status and iteration count of every
+    lane equal the oracle's, V and theta within 1e-8, the duplicate of lane 3 bitwise lane 3."""
+    g, it, seq = _tiny_preconditions(jg, oracle, name)
+    an = jg.newtonRaphson(g.s, batch=TINY_LANES, max_patch=TINY_PATCH)
+    jg.setInjection_(an, g.osys.ps[None, :] - g.pd, g.osys.qs[None, :] - g.qd)
+    jg.powerflow._push_voltage(an, g.vm, g.va)
+    jg.powerFlow_(an, iteration=ITERATION, tolerance=TOLERANCE)
+    dit, dst = np.array(an.method.iteration), np.array(an.status)
+    vm, va = np.array(an.voltage.magnitude), np.array(an.voltage.angle)
+    dv = np.abs(vm - np.array([r.vm for r in g.ref])).max()
+    da = np.abs(va - np.array([r.va for r in g.ref])).max()
+    print(f"[tiny {name}] max |dV| {dv:.2e}, |dtheta| {da:.2e}; iterations {np.bincount(it).tolist()} (device {np.bincount(dit).tolist()}); groups in use {seq}; "
+          f"{g.staged} staged doubles per lane against {g.factor} of the factor")
+    assert np.array_equal(dst, np.zeros(TINY_LANES, dtype=dst.dtype)), np.flatnonzero(dst != 0)[:10]
+    assert np.array_equal(dit, it), [(int(b), int(dit[b]), int(it[b])) for b in np.flatnonzero(dit != it)[:10]]
+    assert dv <= 1e-8 and da <= 1e-8
+    assert np.array_equal(vm[-1], vm[3]) and np.array_equal(va[-1], va[3]) and dit[-1] == dit[3]
     an.close()
 
 

@@ -3,9 +3,9 @@
 
 Units and corrections (MI355X_MICROARCH.md, HBM section): FETCH_SIZE/WRITE_SIZE are in KiB; on gfx950 FETCH_SIZE
 counts wide coalesced reads at half their bytes and other access widths / WRITE_SIZE are uncalibrated, so every
-pattern is calibrated on a kernel of OUR access pattern whose byte count is known exactly: k_lane_copy (the lane
-permutation copy-back: reads rows*ld*8 bytes, writes the same, 8-byte lanes in 512-byte segments, the same shape
-as every hot kernel here).  traffic = counter * 1024 * (known_bytes / (counter_cal * 1024)).
+pattern is calibrated on launches of OUR access pattern whose byte count is known exactly: the device-to-device
+copies of V / theta, or the copy-back launch of k_lanes_move (csrc/jg_compact.hip: reads rows*ld*8 bytes, writes the
+same, 8-byte lanes in 512-byte segments, the same shape as every hot kernel here).  traffic = counter * 1024 * (known_bytes / (counter_cal * 1024)).
 """
 import csv
 import json
@@ -21,7 +21,7 @@ def load(path):
 
 
 def short(name):
-    for k in ("k_assemble", "k_fact_level", "k_fact_task", "k_fact_top", "k_bwd_level", "k_check", "k_compact", "k_lane_permute", "k_lane_copy", "k_lanes_move",
+    for k in ("k_assemble", "k_fact_level", "k_fact_task", "k_fact_top", "k_bwd_level", "k_check", "k_compact", "k_lanes_permute", "k_lanes_move",
               "k_gn_rows", "k_gn_gain", "k_gn_hdelta", "k_gn_norm", "k_gn_update", "k_sel_level", "k_gn_project"):
         if k in name:
             if k == "k_assemble":
@@ -32,17 +32,8 @@ def short(name):
 
 def main(fetch_csv, write_csv, n, ld, solves, out_json, grid="case_ACTIVSg10k"):
     f, w = load(fetch_csv), load(write_csv)
-    # calibration on the n-row lane permutation launches (known: n*ld*8 bytes read and written)
     from collections import Counter
-    keys = [k for k in f if "k_lane_permute" in k]
-    if keys:                                     # older builds: one launch per array, the n-row launches are the most frequent large value
-        known = n * ld * 8
-        key = keys[0]
-        cf = sorted(v[0] for v in f[key] if v[0] > 1000)
-        cw = sorted(v[0] for v in w[key] if v[0] > 1000)
-        cal_f_raw = Counter(round(x) for x in cf).most_common(1)[0][0] * 1024.0
-        cal_w_raw = Counter(round(x) for x in cw).most_common(1)[0][0] * 1024.0
-    elif any("copyBuffer" in k for k in f) and any(v[0] * 1024.0 > 0.4 * n * ld * 8 for k in f if "copyBuffer" in k for v in f[k]):
+    if any("copyBuffer" in k for k in f) and any(v[0] * 1024.0 > 0.4 * n * ld * 8 for k in f if "copyBuffer" in k for v in f[k]):
         # device-to-device copies of V / theta at the end of tools/profile_kernels.py (snapshot + restore: four launches of n x ld x 8
         # bytes read and written).  (The lane movers used before only touch the lanes that change place since the minimal-move compaction.)
         key = [k for k in f if "copyBuffer" in k][0]
