@@ -401,7 +401,7 @@ class OracleGN:
         return float(_se_lib().jgo_gn_objective(self.h))
 
     # ---- increment!(::AcStateEstimation{GaussNewton{Orthogonal}}) / {PetersWilkinson} restated in dense numpy / scipy
-    # (acStateEstimation.jl:906-932 and :934-971; small cases only).  Both start from normalEquation! (the C restatement,
+    # (acStateEstimation.jl:906-932 and :934-971; pinned up to 300 buses / 5 610 rows, tests/test_oracle_methods.py).  Both start from normalEquation! (the C restatement,
     # through increment()), remove the slack angle column (:914 / :947) and scale by sqrt(W) (sqrtPrecision!,
     # dcStateEstimation.jl:488-492: diagonal precision only).
     def _scaled_system(self):
@@ -439,12 +439,15 @@ class OracleGN:
         return inc
 
     def state_estimation_with(self, increment, iteration=40, tolerance=1e-8):
-        """stateEstimation! (:1286-1329) around one of the two increments above; returns (converged, iterations)."""
+        """stateEstimation! (:1286-1329) around one of the two increments above; returns (converged, iterations).
+        self.checks keeps maximum(abs, increment) of every check, the last one last."""
         n = self.sys.n
         it = 0
+        self.checks = []
         for _ in range(iteration + 1):
             inc = increment()
             self.last_increment = inc
+            self.checks.append(float(np.max(np.abs(inc))))
             if np.max(np.abs(inc)) < tolerance:
                 return True, it
             if it == iteration:
