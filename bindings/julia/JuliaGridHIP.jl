@@ -1375,6 +1375,73 @@ end
 "frees the sensitivities a pair screen keeps on the device"
 pairScreenRelease!(b::DcPowerFlowBatch) = check(ccall((:jg_dc_pair_release, lib), Cint, (Int64,), b.token))
 """
+    groupScreenBuild!(b, groups; monitored = nothing, budget = 0) -> info [8]
+
+The DC common-mode screen (jgrid.h: jg_dc_group_*): `groups` is a vector of vectors of 1 to 8 branch indices (in service, none twice within a group), each
+group one case.  The candidates of the kept outage sensitivities are the sorted union of all members; `monitored` and `budget` as `pairScreenBuild!`.
+"""
+function groupScreenBuild!(b::DcPowerFlowBatch, groups::Vector{Vector{Int64}}; monitored::Union{Nothing, Vector{Int64}} = nothing, budget::Int64 = 0)
+    uploadRhs!(b)
+    info = zeros(Float64, 8)
+    offsets = Int64[0; cumsum(length.(groups))]
+    members = reduce(vcat, groups; init = Int64[])
+    if monitored === nothing
+        check(ccall((:jg_dc_group_build, lib), Cint, (Int64, Int64, Ptr{Int64}, Ptr{Int64}, Int64, Ptr{Int64}, Int64, Ptr{Float64}),
+            b.token, length(groups), offsets, members, 0, C_NULL, budget, info))
+    else
+        check(ccall((:jg_dc_group_build, lib), Cint, (Int64, Int64, Ptr{Int64}, Ptr{Int64}, Int64, Ptr{Int64}, Int64, Ptr{Float64}),
+            b.token, length(groups), offsets, members, length(monitored), monitored, budget, info))
+    end
+    return info
+end
+"dims [6] of the group screen built last: groups, their leading dimension, candidates, rows of Phi, monitored branches, members of the largest group"
+function groupScreenDims(b::DcPowerFlowBatch)
+    dims = zeros(Int64, 6)
+    check(ccall((:jg_dc_group_get_dims, lib), Cint, (Int64, Ptr{Int64}), b.token, dims))
+    return dims
+end
+"the candidates of the group screen built last: the union of the members, ascending"
+function groupScreenCandidates(b::DcPowerFlowBatch)
+    labels = zeros(Int64, groupScreenDims(b)[3])
+    check(ccall((:jg_dc_group_get_candidates, lib), Cint, (Int64, Ptr{Int64}), b.token, labels))
+    return labels
+end
+"the base-case flows of the monitored branches of the group screen built last, ascending by branch"
+function groupScreenBase(b::DcPowerFlowBatch)
+    flow = zeros(Float64, groupScreenDims(b)[5])
+    check(ccall((:jg_dc_group_get_base, lib), Cint, (Int64, Ptr{Float64}), b.token, flow))
+    return flow
+end
+"""
+    groupScreen(b, g0, g1; rating, threshold = 1.0, capacity = 2^20, dense = false) -> (status, worst, worstBranch, count, records [4, m], islanding, totals [6], flows, ms)
+
+The groups g0 .. g1 - 1 (0-based): per group the status (3: it islands a part of the grid), the worst |from| / rating over the monitored branches that stay,
+its branch and the number of branches above `threshold`; the violating branches sorted by (group, branch) (group, branch, flow, loading); the islanding
+groups; the totals; with `dense` the flows [monitored, g1 - g0] (0 on the members, NaN for status 3); the milliseconds of the solves and the screen kernel.
+"""
+function groupScreen(b::DcPowerFlowBatch, g0::Int64, g1::Int64; rating::Vector{Float64}, threshold::Float64 = 1.0, capacity::Int64 = 2^20, dense::Bool = false)
+    check(ccall((:jg_dc_set_rating, lib), Cint, (Int64, Ptr{Float64}), b.token, rating))
+    rb = g1 - g0
+    records = Matrix{Float64}(undef, 4, capacity)
+    islanding = zeros(Int64, rb)
+    totals = zeros(Int64, 6)
+    status = zeros(Int32, rb); worst = zeros(Float64, rb); branch = zeros(Int32, rb); count = zeros(Int32, rb)
+    flows = dense ? zeros(Float64, groupScreenDims(b)[5], rb) : zeros(Float64, 0, 0)
+    ms = zeros(Float64, 1)
+    check(ccall((:jg_dc_group_screen, lib), Cint, (Int64, Int64, Int64, Float64, Int64, Ptr{Float64}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int32}, Ptr{Float64},
+                                                   Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}),
+        b.token, g0, g1, threshold, capacity, records, rb, islanding, totals, status, worst, branch, count, dense ? pointer(flows) : Ptr{Float64}(C_NULL), ms))
+    return status, worst, branch, count, records[:, 1:totals[4]], islanding[1:totals[5]], totals, flows, ms[1]
+end
+"milliseconds of `reps` runs on the groups g0 .. g1 - 1 (HIP events): 0 the group screen kernel, 1 the k x k solves"
+function groupTimeKernel(b::DcPowerFlowBatch, kernel::Int, g0::Int64, g1::Int64, reps::Int = 20)
+    ms = zeros(Float64, reps)
+    check(ccall((:jg_dc_group_time_kernel, lib), Cint, (Int64, Cint, Int64, Int64, Cint, Ptr{Float64}), b.token, kernel, g0, g1, reps, ms))
+    return ms
+end
+"frees what a group screen keeps on the device"
+groupScreenRelease!(b::DcPowerFlowBatch) = check(ccall((:jg_dc_group_release, lib), Cint, (Int64,), b.token))
+"""
     seriesScreenBuild!(b, candidates, rhs; monitored = nothing, budget = 0) -> info [12]
 
 The DC N-1 screen over a series of injection profiles (jgrid.h: jg_dc_series_*): `rhs` is `[buses, T]`, one right-hand side per profile as
@@ -1945,7 +2012,7 @@ export HIP, HIPOrthogonal, NewtonRaphsonBatch, BaseCase, baseInfo, baseInverseOn
        largestNormalizedResidual, normalizedResiduals, commUniqueId, Comm, shard, contingencyAnalysis, clearPlanCache,
        deviceCount, dims, setRefinement!, deviceMaps, setOutage!, snapshotVoltage!, restoreVoltage!, iterations, voltageDevice!, packResults!, packRows!,
        allgatherDevice, commRank, commWorld, timeKernel, setBusType!, busType, GaussNewtonBatch, setRealisations!, monteCarloEstimation, fastPatch!, setReadings!, drawNoise!, measurementDevice,
-       DcPowerFlowBatch, setInjections!, setOutagePairs!, pairScreenBuild!, pairScreen, pairTimeKernel, pairScreenRelease!, pairScreenIslandMode!, pairScreenShed, seriesScreenIslandMode!, seriesScreenShed, transferScreenIslandMode!, transferScreenShed, generatorScreenBuild!, generatorScreen, generatorScreenFlows, generatorTimeKernel, generatorScreenRelease!, generatorScreenIslandMode!, generatorScreenShed, seriesScreenBuild!, seriesScreen, seriesTimeKernel, seriesScreenRelease!, setIslandMode!, islands, islandTable, fromPower, angleDevice, DcStateEstimationBatch, removedRows, removeRows!,
+       DcPowerFlowBatch, setInjections!, setOutagePairs!, pairScreenBuild!, pairScreen, pairTimeKernel, pairScreenRelease!, pairScreenIslandMode!, pairScreenShed, seriesScreenIslandMode!, seriesScreenShed, transferScreenIslandMode!, transferScreenShed, generatorScreenBuild!, generatorScreen, generatorScreenFlows, generatorTimeKernel, generatorScreenRelease!, generatorScreenIslandMode!, generatorScreenShed, groupScreenBuild!, groupScreenDims, groupScreenCandidates, groupScreenBase, groupScreen, groupTimeKernel, groupScreenRelease!, seriesScreenBuild!, seriesScreen, seriesTimeKernel, seriesScreenRelease!, setIslandMode!, islands, islandTable, fromPower, angleDevice, DcStateEstimationBatch, removedRows, removeRows!,
        GaussSeidelBatch, lastMismatch, setBusVoltage!, refreshGenerator!
 
 end # module

@@ -584,6 +584,38 @@ int jg_dc_pair_set_island_mode(int64_t h, int mode);
 int jg_dc_pair_get_shed_table(int64_t h, int64_t k0, int64_t k1, int64_t* count, int64_t* branches, int64_t* buses, int64_t* m, int64_t* side);
 int jg_dc_pair_get_shed(int64_t h, int64_t k0, int64_t k1, double* flow);
 /*
+ * The DC common-mode screen over named outage GROUPS of 1 to 8 branches, each group one case (csrc/jg_dc_group.hpp): the user loop updateBranch!(s, status = 0)
+ * for every member s, solve!, power! per group.  With Phi of jg_dc_pair_build on the candidates = the sorted union of all members, a group S costs a
+ * |S| x |S| solve (I - Phi_SS) c = f0_S and one pass f_m(S) = f0_m + sum_s Phi[m,s] c_s over the rows, 0 on the members -- no sweep per case.  Needs
+ * jg_dc_set_branches and jg_dc_set_rhs; neither the lanes of the handle nor what the other screens keep are touched.
+ *   jg_dc_group_build   the groups as a CSR: offsets [ngroups + 1] (offsets [0] = 0), members (1-based branches, in service, no branch twice within a
+ *                       group, 1 to 8 per group; return code 1 names the offending group, 0-based).  monitored, budget_bytes and info [8] as jg_dc_pair_build.
+ *                       A second build replaces the first.
+ *   jg_dc_group_screen  the groups [g0, g1) (0-based; the block bounds the memory of a call) against the ratings of jg_dc_set_rating.  Per group of the
+ *                       block (each nullable): status (0, or 3: a pivot of the LU with partial pivoting of I - Phi_SS is below 1e-9 in magnitude -- the
+ *                       group holds a bridge or its members form a joint cut), worst (the largest |from| / rating over the monitored branches that
+ *                       stay; NaN for status 3), worst_branch (1-based, ties to the lowest index; 0: none), count (monitored branches above threshold).
+ *                       records [capacity][4]: the violating branches, sorted by (group, branch): group (0-based), branch (1-based), flow, loading.
+ *                       islanding [island_capacity]: the status-3 groups (0-based), ascending.  totals [6]: groups screened, violating branches,
+ *                       islanding groups, records written, islanding groups written, flags (1: the record list overflowed, 2: the islanding list did)
+ *                       -- the counts are exact also then, and the entries kept are the FIRST.  dense_flow (nullable) [g1 - g0][monitored ascending]:
+ *                       the flows, 0 on the members, NaN for status 3.  ms (nullable): the milliseconds of the call's solves and screen kernel (HIP events).
+ *   jg_dc_group_get_dims         dims [6]: groups, their leading dimension, candidates, rows of Phi, monitored branches, members of the largest group
+ *   jg_dc_group_get_candidates   labels [candidates]: the union of the members, 1-based ascending
+ *   jg_dc_group_get_base         flow [monitored]: the base-case flows of the monitored branches, ascending
+ *   jg_dc_group_time_kernel      milliseconds of `reps` runs on the groups [g0, g1) (a block jg_dc_group_screen has held): 0 the screen kernel, 1 the solves
+ *   jg_dc_group_release          frees what the screen holds on the device
+ */
+int jg_dc_group_build(int64_t h, int64_t ngroups, const int64_t* offsets, const int64_t* members, int64_t nm, const int64_t* monitored, int64_t budget_bytes,
+                      double* info8);
+int jg_dc_group_screen(int64_t h, int64_t g0, int64_t g1, double threshold, int64_t capacity, double* records, int64_t island_capacity, int64_t* islanding,
+                       int64_t* totals6, int32_t* status, double* worst, int32_t* worst_branch, int32_t* count, double* dense_flow, double* ms);
+int jg_dc_group_get_dims(int64_t h, int64_t* dims6);
+int jg_dc_group_get_candidates(int64_t h, int64_t* labels);
+int jg_dc_group_get_base(int64_t h, double* flow);
+int jg_dc_group_time_kernel(int64_t h, int kernel, int64_t g0, int64_t g1, int reps, double* ms);
+int jg_dc_group_release(int64_t h);
+/*
  * The DC N-1 screen over a SERIES of injection profiles (csrc/jg_dc_series.hpp): the user loop updateBus!(...; active) / updateGenerator!(...; active) per
  * profile t around updateBranch!(k, status = 0), solve!, power!, updateBranch!(k, status = 1) per branch k.  No sweep per case: with Phi of
  * jg_dc_pair_build and the profiles' base flows F0[m,t], f_m(k,t) = F0[m,t] + Phi[m,k] F0[k,t] / (1 - Phi[k,k]).  Needs jg_dc_set_branches and

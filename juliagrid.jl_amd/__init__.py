@@ -6,6 +6,7 @@ in libjgrid_hip.so (hand-written HIP for gfx950) through the C ABI of include/jg
 from .system import PowerSystem, CscMatrix, powerSystem, acModel_, dcModel_          # noqa: F401
 from .dcpowerflow import DcPowerFlow, dcPowerFlow, DcPairScreen, dcPairScreen, pairCandidates, shedCandidates, pairShed, DcSeriesScreen, dcSeriesScreen, DcTransferScreen, dcTransferScreen, transferDirection          # noqa: F401
 from .dcgenerator import DcGeneratorScreen, dcGeneratorScreen, generatorCandidates, pickupShare, PickupShare, shareLoss          # noqa: F401
+from .dcgroup import dcGroupScreen, parallelGroups, DC_GROUP_MAX          # noqa: F401
 from .system import addBranch_ as addBranchSystem_, dropZeros_ as dropZerosSystem_   # noqa: F401
 from .system import (updateBranch_ as updateBranchSystem_, updateBus_ as updateBusSystem_,   # noqa: F401
                      updateGenerator_ as updateGeneratorSystem_)
@@ -23,7 +24,7 @@ from .stateestimation import (WlsMethod, Normal, LU, KLU, QR, LDLt, LL, Orthogon
 from .dcstateestimation import DcStateEstimation, dcStateEstimation, setReadings_, removed, removeMeasurement_          # noqa: F401
 from .montecarlo import MonteCarloPipeline, gatherEstimates, gatherEstimatesDevice, unpackEstimates   # noqa: F401
 from .synthetic import pegaseShaped, case9241synth                          # noqa: F401
-from . import powerflow, stateestimation, dcpowerflow, dcgenerator, dcstateestimation, gaussseidel   # noqa: F401
+from . import powerflow, stateestimation, dcpowerflow, dcgenerator, dcgroup, dcstateestimation, gaussseidel   # noqa: F401
 from . import _lib                                                           # noqa: F401
 
 __all__ = [
@@ -37,4 +38,5 @@ __all__ = [
     "addBranch_", "dropZeros_", "addBranchSystem_", "dropZerosSystem_", "pegaseShaped", "case9241synth", "ContingencyPipeline", "MonteCarloPipeline", "gatherEstimates", "gatherEstimatesDevice", "unpackEstimates", "setOutages_", "power_", "current_", "screenSummary_", "reactiveLimit_", "adjustAngle_",
     "dcModel_", "DcPowerFlow", "dcPowerFlow", "DcPairScreen", "dcPairScreen", "pairCandidates", "shedCandidates", "pairShed", "DcSeriesScreen", "dcSeriesScreen", "DcTransferScreen", "dcTransferScreen", "transferDirection", "DcGeneratorScreen", "dcGeneratorScreen", "generatorCandidates", "pickupShare", "PickupShare", "shareLoss", "DcStateEstimation", "dcStateEstimation", "setReadings_", "removed", "removeMeasurement_", "BaseCase", "startFromBase_", "setFirstIteration_", "firstIterationCounts", "setBusType_", "busType", "powerFlowLimits_",
     "GaussSeidelPowerFlow", "gaussSeidel",
+    "dcGroupScreen", "parallelGroups", "DC_GROUP_MAX",
 ]

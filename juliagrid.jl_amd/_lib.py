@@ -164,6 +164,13 @@ def lib():
         "jg_dc_pair_set_island_mode": [C.c_int64, C.c_int],
         "jg_dc_pair_get_shed_table": [C.c_int64, C.c_int64, C.c_int64, I64P, I64P, I64P, I64P, I64P],
         "jg_dc_pair_get_shed": [C.c_int64, C.c_int64, C.c_int64, F64P],
+        "jg_dc_group_build": [C.c_int64, C.c_int64, I64P, I64P, C.c_int64, VP, C.c_int64, F64P],
+        "jg_dc_group_screen": [C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_int64, VP, C.c_int64, VP, I64P, VP, VP, VP, VP, VP, VP],
+        "jg_dc_group_get_dims": [C.c_int64, I64P],
+        "jg_dc_group_get_candidates": [C.c_int64, I64P],
+        "jg_dc_group_get_base": [C.c_int64, F64P],
+        "jg_dc_group_time_kernel": [C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int, F64P],
+        "jg_dc_group_release": [C.c_int64],
         "jg_dc_series_build": [C.c_int64, C.c_int64, I64P, C.c_int64, VP, C.c_int64, F64P, C.c_int64, F64P],
         "jg_dc_series_screen": [C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_int64, VP, VP, I64P, VP, VP, VP, VP, VP, VP, VP],
         "jg_dc_series_time_kernel": [C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int, F64P],

@@ -8,6 +8,7 @@
 #include "jg_dc_series.hpp"
 #include "jg_dc_transfer.hpp"
 #include "jg_dc_generator.hpp"
+#include "jg_dc_group.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -286,6 +287,7 @@ void dc_destroy(DcHandle* h) {
     dc_series_free(h);
     dc_transfer_free(h);
     dc_generator_free(h);
+    dc_group_free(h);
     for (void* p : h->allocs) hipFree(p);
     if (h->stream) hipStreamDestroy(h->stream);
     delete h;

@@ -124,15 +124,21 @@ int dc_phi_get_shed_table(DcHandle* d, const std::string& screen, const DcPhi* p
                           int64_t* m, int64_t* side);
 // jg_dc_<screen>_time_kernel for the rows [k0, k1) of a block of `blk_rows` the screen has held: `make`, called once behind the checks, builds the argument
 // blocks and returns what enqueues kernel 0 (the screen kernel) or 1 (the summaries) from them
+// dc_phi_time_kernel_rows: the same for a screen whose block rows are not the candidates (the group screen's groups): `count` of them
 template <typename Make>
-int dc_phi_time_kernel(DcHandle* d, const std::string& screen, const DcPhi* p, int blk_rows, int kernel, int64_t k0, int64_t k1, int reps, double* ms, Make&& make) {
+int dc_phi_time_kernel_rows(DcHandle* d, const std::string& screen, const DcPhi* p, int count, int blk_rows, int kernel, int64_t k0, int64_t k1, int reps, double* ms,
+                            Make&& make) {
     const std::string me = "jg_dc_" + screen + "_time_kernel: ", of = "jg_dc_" + screen;
     if (!p) return api_fail(4, me + of + "_build first");
-    if (!ms || reps < 1 || kernel < 0 || kernel > 1 || k0 < 0 || k1 <= k0 || k1 > p->nk) return api_fail(1, me + "bad argument");
+    if (!ms || reps < 1 || kernel < 0 || kernel > 1 || k0 < 0 || k1 <= k0 || k1 > count) return api_fail(1, me + "bad argument");
     if (k1 - k0 > blk_rows) return api_fail(4, me + of + "_screen with a block of at least these rows first");
     const auto enqueue = make();
     const int rc = time_events(d->stream, reps, ms, d->error, [&]() -> int { enqueue(kernel); return 0; });
     return rc ? api_fail(rc, d->error) : 0;
+}
+template <typename Make>
+int dc_phi_time_kernel(DcHandle* d, const std::string& screen, const DcPhi* p, int blk_rows, int kernel, int64_t k0, int64_t k1, int reps, double* ms, Make&& make) {
+    return dc_phi_time_kernel_rows(d, screen, p, p ? p->nk : 0, blk_rows, kernel, k0, k1, reps, ms, make);
 }
 
 }  // namespace jg
