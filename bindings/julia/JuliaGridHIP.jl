@@ -1442,6 +1442,67 @@ end
 "frees what a group screen keeps on the device"
 groupScreenRelease!(b::DcPowerFlowBatch) = check(ccall((:jg_dc_group_release, lib), Cint, (Int64,), b.token))
 """
+    chanceScreenBuild!(b, factors, candidates; monitored = nothing, injection = nothing, budget = 0) -> info [12]
+
+The DC probabilistic N-1 screen under Gaussian injection uncertainty (jgrid.h: jg_dc_chance_*): `factors` is `[buses, r]` with 1 <= r <= 32, the injections
+are p0 + factors * xi with xi ~ N(0, I); one sweep pair per factor and one per candidate branch (indices, in service, ascending), no sample.  `injection`
+is the right-hand side of p0 `[buses]` as `setInjections!` takes it (default: the base case of `b`); `monitored` and `budget` as `pairScreenBuild!`.
+"""
+function chanceScreenBuild!(b::DcPowerFlowBatch, factors::Matrix{Float64}, candidates::Vector{Int64}; monitored::Union{Nothing, Vector{Int64}} = nothing,
+                            injection::Union{Nothing, Vector{Float64}} = nothing, budget::Int64 = 0)
+    uploadRhs!(b)
+    info = zeros(Float64, 12)
+    mon = monitored === nothing ? Int64[] : monitored
+    check(ccall((:jg_dc_chance_build, lib), Cint, (Int64, Int64, Ptr{Float64}, Int64, Ptr{Int64}, Int64, Ptr{Int64}, Ptr{Float64}, Int64, Ptr{Float64}),
+        b.token, size(factors, 2), factors, length(candidates), candidates, length(mon), monitored === nothing ? Ptr{Int64}(C_NULL) : pointer(mon),
+        injection === nothing ? Ptr{Float64}(C_NULL) : pointer(injection), budget, info))
+    return info
+end
+"dims [6] of the chance screen built last: candidates, their leading dimension, rows of Phi, monitored branches, factors, leading dimension of S"
+function chanceScreenDims(b::DcPowerFlowBatch)
+    dims = zeros(Int64, 6)
+    check(ccall((:jg_dc_chance_get_dims, lib), Cint, (Int64, Ptr{Int64}), b.token, dims))
+    return dims
+end
+"the base case of the chance screen built last, no outage: (mean, std, probability) per monitored branch, ascending by branch"
+function chanceScreenBase(b::DcPowerFlowBatch; rating::Vector{Float64})
+    check(ccall((:jg_dc_set_rating, lib), Cint, (Int64, Ptr{Float64}), b.token, rating))
+    nm = chanceScreenDims(b)[4]
+    mean = zeros(Float64, nm); std = zeros(Float64, nm); probability = zeros(Float64, nm)
+    check(ccall((:jg_dc_chance_get_base, lib), Cint, (Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), b.token, mean, std, probability))
+    return mean, std, probability
+end
+"""
+    chanceScreen(b, k0, k1; rating, probability = 0.05, capacity = 2^20, dense = false) -> (status, worst, worstBranch, count, records [5, m], totals [5], mean, std, p)
+
+The candidates k0 .. k1 - 1 (0-based positions): per candidate the status (3: a bridge), the largest probability that a monitored branch exceeds its rating,
+that branch and the number of branches with P >= `probability`; the records (k, m, mean, std, P) sorted by (k, m); the totals; with `dense` the mean, the
+standard deviation and the probability [monitored, k1 - k0] (NaN for status 3).
+"""
+function chanceScreen(b::DcPowerFlowBatch, k0::Int64, k1::Int64; rating::Vector{Float64}, probability::Float64 = 0.05, capacity::Int64 = 2^20, dense::Bool = false)
+    check(ccall((:jg_dc_set_rating, lib), Cint, (Int64, Ptr{Float64}), b.token, rating))
+    rb = k1 - k0
+    records = Matrix{Float64}(undef, 5, capacity)
+    totals = zeros(Int64, 5)
+    status = zeros(Int32, rb); worst = zeros(Float64, rb); branch = zeros(Int32, rb); count = zeros(Int32, rb)
+    nm = dense ? chanceScreenDims(b)[4] : 0
+    mean = zeros(Float64, nm, dense ? rb : 0); std = zeros(Float64, nm, dense ? rb : 0); p = zeros(Float64, nm, dense ? rb : 0)
+    none = Ptr{Float64}(C_NULL)
+    check(ccall((:jg_dc_chance_screen, lib), Cint, (Int64, Int64, Int64, Float64, Int64, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32},
+                                                    Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        b.token, k0, k1, probability, capacity, records, totals, worst, branch, count, status, dense ? pointer(mean) : none, dense ? pointer(std) : none,
+        dense ? pointer(p) : none))
+    return status, worst, branch, count, records[:, 1:totals[4]], totals, mean, std, p
+end
+"milliseconds of `reps` runs on the candidates k0 .. k1 - 1 (HIP events): 0 the chance screen kernel, 1 the base-case kernel"
+function chanceTimeKernel(b::DcPowerFlowBatch, kernel::Int, k0::Int64, k1::Int64, reps::Int = 20)
+    ms = zeros(Float64, reps)
+    check(ccall((:jg_dc_chance_time_kernel, lib), Cint, (Int64, Cint, Int64, Int64, Cint, Ptr{Float64}), b.token, kernel, k0, k1, reps, ms))
+    return ms
+end
+"frees what a chance screen keeps on the device"
+chanceScreenRelease!(b::DcPowerFlowBatch) = check(ccall((:jg_dc_chance_release, lib), Cint, (Int64,), b.token))
+"""
     seriesScreenBuild!(b, candidates, rhs; monitored = nothing, budget = 0) -> info [12]
 
 The DC N-1 screen over a series of injection profiles (jgrid.h: jg_dc_series_*): `rhs` is `[buses, T]`, one right-hand side per profile as

@@ -616,6 +616,38 @@ int jg_dc_group_get_base(int64_t h, double* flow);
 int jg_dc_group_time_kernel(int64_t h, int kernel, int64_t g0, int64_t g1, int reps, double* ms);
 int jg_dc_group_release(int64_t h);
 /*
+ * The DC probabilistic N-1 screen under Gaussian injection uncertainty (csrc/jg_dc_chance.hpp): with branch k out of service, how likely is branch m to
+ * exceed its rating?  Injections are p0 + L' xi, xi ~ N(0, I_r); the flows are linear in them, so with Phi of jg_dc_pair_build, the base flows f0 and the
+ * factor sensitivities S[m,j] = y_m a_m' B^-1 L_j (ONE sweep pair per factor) the post-contingency flow of m is Gaussian with
+ *     g = Phi[m,k] / (1 - Phi[k,k]),   mu = f0[m] + g f0[k],   sigma = sqrt(sum_j (S[m,j] + g S[k,j])^2),
+ *     P = 1/2 erfc((rating - mu) / (sigma sqrt 2)) + 1/2 erfc((rating + mu) / (sigma sqrt 2))          (sigma == 0: 1 if |mu| > rating, else 0)
+ * and no sample is drawn.  Needs jg_dc_set_branches and jg_dc_set_rhs; neither the lanes of the handle nor what the other screens keep are touched.
+ *   jg_dc_chance_build   factors [r][n], 1 <= r <= 32 (return code 1 otherwise): net active injection per unit of xi_j, the slack's entry is taken as 0.
+ *                        candidates [nk] (nk >= 1), monitored [nm] and budget_bytes as jg_dc_series_build takes them.  injection_rhs (nullable) [n]: the
+ *                        right-hand side of p0 as jg_dc_set_rhs takes it; null: the handle's base case.  info [12]: [0..7] as jg_dc_pair_build, [8] the
+ *                        bytes of S, [9..11] the milliseconds of S: total, sweep pairs, flow kernel.  A second build replaces the first.
+ *   jg_dc_chance_screen  the candidates [k0, k1) (positions; the block bounds the memory of a call) against the ratings of jg_dc_set_rating; an unrated or
+ *                        unmonitored branch has P = 0 and enters nothing.  0 < probability <= 1.  Per candidate of the block (each nullable): worst (the
+ *                        largest P over the monitored branches; NaN for status 3), worst_branch (1-based, ties to the lowest index; 0: none), count
+ *                        (branches with P >= probability), status (0, or 3: |1 - Phi[k,k]| < 1e-9, a bridge; no shedding).  records [capacity][5]: the
+ *                        (k, m) with P >= probability, sorted by (k, m): label k, label m, mu, sigma, P.  totals [5]: candidates screened, records,
+ *                        bridges, records written, 1 when the list overflowed -- the counts are exact also then, and the entries kept are the FIRST.
+ *                        dense_mu / dense_sigma / dense_p (nullable) [k1 - k0][monitored ascending]: 0 at m = k, NaN for status 3.
+ *   jg_dc_chance_get_dims         dims [6]: candidates, their leading dimension, rows of Phi, monitored branches, factors, leading dimension of S
+ *   jg_dc_chance_get_base         mean / std_dev / probability (each nullable) [monitored]: the base case, no outage (needs jg_dc_set_rating)
+ *   jg_dc_chance_time_kernel      milliseconds of `reps` runs on the candidates [k0, k1) (a block jg_dc_chance_screen has held): 0 the screen kernel,
+ *                                 1 the base-case kernel
+ *   jg_dc_chance_release          frees what the screen holds on the device
+ */
+int jg_dc_chance_build(int64_t h, int64_t r, const double* factors, int64_t nk, const int64_t* candidates, int64_t nm, const int64_t* monitored,
+                       const double* injection_rhs, int64_t budget_bytes, double* info12);
+int jg_dc_chance_screen(int64_t h, int64_t k0, int64_t k1, double probability, int64_t capacity, double* records, int64_t* totals5, double* worst,
+                        int32_t* worst_branch, int32_t* count, int32_t* status, double* dense_mu, double* dense_sigma, double* dense_p);
+int jg_dc_chance_get_dims(int64_t h, int64_t* dims6);
+int jg_dc_chance_get_base(int64_t h, double* mean, double* std_dev, double* probability);
+int jg_dc_chance_time_kernel(int64_t h, int kernel, int64_t k0, int64_t k1, int reps, double* ms);
+int jg_dc_chance_release(int64_t h);
+/*
  * The DC N-1 screen over a SERIES of injection profiles (csrc/jg_dc_series.hpp): the user loop updateBus!(...; active) / updateGenerator!(...; active) per
  * profile t around updateBranch!(k, status = 0), solve!, power!, updateBranch!(k, status = 1) per branch k.  No sweep per case: with Phi of
  * jg_dc_pair_build and the profiles' base flows F0[m,t], f_m(k,t) = F0[m,t] + Phi[m,k] F0[k,t] / (1 - Phi[k,k]).  Needs jg_dc_set_branches and

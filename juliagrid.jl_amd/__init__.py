@@ -7,6 +7,7 @@ from .system import PowerSystem, CscMatrix, powerSystem, acModel_, dcModel_     
 from .dcpowerflow import DcPowerFlow, dcPowerFlow, DcPairScreen, dcPairScreen, pairCandidates, shedCandidates, pairShed, DcSeriesScreen, dcSeriesScreen, DcTransferScreen, dcTransferScreen, transferDirection          # noqa: F401
 from .dcgenerator import DcGeneratorScreen, dcGeneratorScreen, generatorCandidates, pickupShare, PickupShare, shareLoss          # noqa: F401
 from .dcgroup import dcGroupScreen, parallelGroups, DC_GROUP_MAX          # noqa: F401
+from .dcchance import dcChanceScreen, injectionFactors, DC_CHANCE_MAX          # noqa: F401
 from .system import addBranch_ as addBranchSystem_, dropZeros_ as dropZerosSystem_   # noqa: F401
 from .system import (updateBranch_ as updateBranchSystem_, updateBus_ as updateBusSystem_,   # noqa: F401
                      updateGenerator_ as updateGeneratorSystem_)
@@ -24,7 +25,7 @@ from .stateestimation import (WlsMethod, Normal, LU, KLU, QR, LDLt, LL, Orthogon
 from .dcstateestimation import DcStateEstimation, dcStateEstimation, setReadings_, removed, removeMeasurement_          # noqa: F401
 from .montecarlo import MonteCarloPipeline, gatherEstimates, gatherEstimatesDevice, unpackEstimates   # noqa: F401
 from .synthetic import pegaseShaped, case9241synth                          # noqa: F401
-from . import powerflow, stateestimation, dcpowerflow, dcgenerator, dcgroup, dcstateestimation, gaussseidel   # noqa: F401
+from . import powerflow, stateestimation, dcpowerflow, dcgenerator, dcgroup, dcchance, dcstateestimation, gaussseidel   # noqa: F401
 from . import _lib                                                           # noqa: F401
 
 __all__ = [
@@ -39,4 +40,5 @@ __all__ = [
     "dcModel_", "DcPowerFlow", "dcPowerFlow", "DcPairScreen", "dcPairScreen", "pairCandidates", "shedCandidates", "pairShed", "DcSeriesScreen", "dcSeriesScreen", "DcTransferScreen", "dcTransferScreen", "transferDirection", "DcGeneratorScreen", "dcGeneratorScreen", "generatorCandidates", "pickupShare", "PickupShare", "shareLoss", "DcStateEstimation", "dcStateEstimation", "setReadings_", "removed", "removeMeasurement_", "BaseCase", "startFromBase_", "setFirstIteration_", "firstIterationCounts", "setBusType_", "busType", "powerFlowLimits_",
     "GaussSeidelPowerFlow", "gaussSeidel",
     "dcGroupScreen", "parallelGroups", "DC_GROUP_MAX",
+    "dcChanceScreen", "injectionFactors", "DC_CHANCE_MAX",
 ]

@@ -171,6 +171,12 @@ def lib():
         "jg_dc_group_get_base": [C.c_int64, F64P],
         "jg_dc_group_time_kernel": [C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int, F64P],
         "jg_dc_group_release": [C.c_int64],
+        "jg_dc_chance_build": [C.c_int64, C.c_int64, F64P, C.c_int64, I64P, C.c_int64, VP, VP, C.c_int64, F64P],
+        "jg_dc_chance_screen": [C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_int64, VP, I64P, VP, VP, VP, VP, VP, VP, VP],
+        "jg_dc_chance_get_dims": [C.c_int64, I64P],
+        "jg_dc_chance_get_base": [C.c_int64, VP, VP, VP],
+        "jg_dc_chance_time_kernel": [C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int, F64P],
+        "jg_dc_chance_release": [C.c_int64],
         "jg_dc_series_build": [C.c_int64, C.c_int64, I64P, C.c_int64, VP, C.c_int64, F64P, C.c_int64, F64P],
         "jg_dc_series_screen": [C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_int64, VP, VP, I64P, VP, VP, VP, VP, VP, VP, VP],
         "jg_dc_series_time_kernel": [C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int, F64P],

@@ -9,6 +9,7 @@
 #include "jg_dc_transfer.hpp"
 #include "jg_dc_generator.hpp"
 #include "jg_dc_group.hpp"
+#include "jg_dc_chance.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -288,6 +289,7 @@ void dc_destroy(DcHandle* h) {
     dc_transfer_free(h);
     dc_generator_free(h);
     dc_group_free(h);
+    dc_chance_free(h);
     for (void* p : h->allocs) hipFree(p);
     if (h->stream) hipStreamDestroy(h->stream);
     delete h;

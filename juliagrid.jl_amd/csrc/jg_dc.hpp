@@ -37,6 +37,7 @@ struct DcSeriesState;
 struct DcTransferState;
 struct DcGeneratorState;
 struct DcGroupState;
+struct DcChanceState;
 
 struct DcHandle : DcDevice {
     int n = 0, nbr = 0, batch = 0, ld = 0, slack = 0;
@@ -60,6 +61,7 @@ struct DcHandle : DcDevice {
     DcTransferState* transfer = nullptr;                                       // the transfer-capability screen over transfers x N-1 outages (jg_dc_transfer.hpp)
     DcGeneratorState* generator = nullptr;                                     // the generator-outage screen: G-1 and generator x branch cases (jg_dc_generator.hpp)
     DcGroupState* group = nullptr;                                             // the common-mode screen over named outage groups of up to 8 branches (jg_dc_group.hpp)
+    DcChanceState* chance = nullptr;                                           // the probabilistic N-1 screen under Gaussian injection uncertainty (jg_dc_chance.hpp)
     // island mode of the NEXT pair / series / transfer / generator build (the build takes it and sets it back to 0).  A sticky flag beside the build call is awkward -- the mode
     // belongs among the build's arguments -- but jg_dc_*_set_island_mode is part of the C ABI, so the flags stay
     int pair_shed = 0, series_shed = 0, transfer_shed = 0, generator_shed = 0;
