@@ -1442,6 +1442,77 @@ end
 "frees what a group screen keeps on the device"
 groupScreenRelease!(b::DcPowerFlowBatch) = check(ccall((:jg_dc_group_release, lib), Cint, (Int64,), b.token))
 """
+    cascadeScreenBuild!(b, events; monitored = nothing, budget = 0) -> info [8]
+
+The DC cascading-outage screen (jgrid.h: jg_dc_cascade_*): `events` is a vector of vectors of 1 to 8 branch indices (in service, none twice within an
+event), each the initiating outage of one cascade.  `monitored` are the branches that can trip and that are reported (nothing: every branch in service).
+The candidates of the kept outage sensitivities are the sorted union of all members and the monitored branches in service; they cannot be blocked, a
+build that does not fit `budget` is refused with the bytes needed and available.
+"""
+function cascadeScreenBuild!(b::DcPowerFlowBatch, events::Vector{Vector{Int64}}; monitored::Union{Nothing, Vector{Int64}} = nothing, budget::Int64 = 0)
+    uploadRhs!(b)
+    info = zeros(Float64, 8)
+    offsets = Int64[0; cumsum(length.(events))]
+    members = reduce(vcat, events; init = Int64[])
+    if monitored === nothing
+        check(ccall((:jg_dc_cascade_build, lib), Cint, (Int64, Int64, Ptr{Int64}, Ptr{Int64}, Int64, Ptr{Int64}, Int64, Ptr{Float64}),
+            b.token, length(events), offsets, members, 0, C_NULL, budget, info))
+    else
+        check(ccall((:jg_dc_cascade_build, lib), Cint, (Int64, Int64, Ptr{Int64}, Ptr{Int64}, Int64, Ptr{Int64}, Int64, Ptr{Float64}),
+            b.token, length(events), offsets, members, length(monitored), monitored, budget, info))
+    end
+    return info
+end
+"dims [6] of the cascade screen built last: events, their leading dimension, candidates, rows of Phi, monitored branches, members of the largest event"
+function cascadeScreenDims(b::DcPowerFlowBatch)
+    dims = zeros(Int64, 6)
+    check(ccall((:jg_dc_cascade_get_dims, lib), Cint, (Int64, Ptr{Int64}), b.token, dims))
+    return dims
+end
+"the candidates of the cascade screen built last: the union of the initiating members and the monitored branches in service, ascending"
+function cascadeScreenCandidates(b::DcPowerFlowBatch)
+    labels = zeros(Int64, cascadeScreenDims(b)[3])
+    check(ccall((:jg_dc_cascade_get_candidates, lib), Cint, (Int64, Ptr{Int64}), b.token, labels))
+    return labels
+end
+"the base-case flows of the monitored branches of the cascade screen built last, ascending by branch"
+function cascadeScreenBase(b::DcPowerFlowBatch)
+    flow = zeros(Float64, cascadeScreenDims(b)[5])
+    check(ccall((:jg_dc_cascade_get_base, lib), Cint, (Int64, Ptr{Float64}), b.token, flow))
+    return flow
+end
+"""
+    cascadeScreen(b, c0, c1; rating, trip = 1.0, rule = 0, most = 8, dense = false)
+        -> (status, stages, size, tripped [most, m], stage [most, m], loading [most, m], worst, worstBranch, pending, flows, ms)
+
+The cascades c0 .. c1 - 1 (0-based), each run to its end in one kernel launch: a monitored rated branch trips when |from| / rating > trip; rule 0: every
+overloaded branch leaves at once, rule 1: only the most loaded one.  Per cascade the status (0: stable, 3: the set islands a part of the grid, 5: truncated,
+the next stage would exceed `most`), the stages of trips applied, the branches out at the end, the branches in the order they left with the stage and the
+loading that tripped each (0 / -1 / NaN on unused slots, stage 0 and NaN on the initiating members), the worst loading of the final state and its branch,
+the overloaded branches of a truncated cascade; with `dense` the final flows [monitored, c1 - c0]; the milliseconds of the kernel.
+"""
+function cascadeScreen(b::DcPowerFlowBatch, c0::Int64, c1::Int64; rating::Vector{Float64}, trip::Float64 = 1.0, rule::Int = 0, most::Int = 8, dense::Bool = false)
+    check(ccall((:jg_dc_set_rating, lib), Cint, (Int64, Ptr{Float64}), b.token, rating))
+    rb = c1 - c0
+    status = zeros(Int32, rb); stages = zeros(Int32, rb); size = zeros(Int32, rb); pending = zeros(Int32, rb)
+    tripped = zeros(Int64, most, rb); stage = zeros(Int32, most, rb); loading = zeros(Float64, most, rb)
+    worst = zeros(Float64, rb); branch = zeros(Int32, rb)
+    flows = dense ? zeros(Float64, cascadeScreenDims(b)[5], rb) : zeros(Float64, 0, 0)
+    ms = zeros(Float64, 1)
+    check(ccall((:jg_dc_cascade_run, lib), Cint, (Int64, Int64, Int64, Float64, Cint, Cint, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int64}, Ptr{Int32}, Ptr{Float64},
+                                                  Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}),
+        b.token, c0, c1, trip, rule, most, status, stages, size, tripped, stage, loading, worst, branch, pending, dense ? pointer(flows) : Ptr{Float64}(C_NULL), ms))
+    return status, stages, size, tripped, stage, loading, worst, branch, pending, flows, ms[1]
+end
+"milliseconds of `reps` runs on the cascades c0 .. c1 - 1 with the trip and most of the last run (HIP events): 0 rule 0 (all), 1 rule 1 (worst)"
+function cascadeTimeKernel(b::DcPowerFlowBatch, kernel::Int, c0::Int64, c1::Int64, reps::Int = 20)
+    ms = zeros(Float64, reps)
+    check(ccall((:jg_dc_cascade_time_kernel, lib), Cint, (Int64, Cint, Int64, Int64, Cint, Ptr{Float64}), b.token, kernel, c0, c1, reps, ms))
+    return ms
+end
+"frees what a cascade screen keeps on the device"
+cascadeScreenRelease!(b::DcPowerFlowBatch) = check(ccall((:jg_dc_cascade_release, lib), Cint, (Int64,), b.token))
+"""
     chanceScreenBuild!(b, factors, candidates; monitored = nothing, injection = nothing, budget = 0) -> info [12]
 
 The DC probabilistic N-1 screen under Gaussian injection uncertainty (jgrid.h: jg_dc_chance_*): `factors` is `[buses, r]` with 1 <= r <= 32, the injections
@@ -2073,7 +2144,7 @@ export HIP, HIPOrthogonal, NewtonRaphsonBatch, BaseCase, baseInfo, baseInverseOn
        largestNormalizedResidual, normalizedResiduals, commUniqueId, Comm, shard, contingencyAnalysis, clearPlanCache,
        deviceCount, dims, setRefinement!, deviceMaps, setOutage!, snapshotVoltage!, restoreVoltage!, iterations, voltageDevice!, packResults!, packRows!,
        allgatherDevice, commRank, commWorld, timeKernel, setBusType!, busType, GaussNewtonBatch, setRealisations!, monteCarloEstimation, fastPatch!, setReadings!, drawNoise!, measurementDevice,
-       DcPowerFlowBatch, setInjections!, setOutagePairs!, pairScreenBuild!, pairScreen, pairTimeKernel, pairScreenRelease!, pairScreenIslandMode!, pairScreenShed, seriesScreenIslandMode!, seriesScreenShed, transferScreenIslandMode!, transferScreenShed, generatorScreenBuild!, generatorScreen, generatorScreenFlows, generatorTimeKernel, generatorScreenRelease!, generatorScreenIslandMode!, generatorScreenShed, groupScreenBuild!, groupScreenDims, groupScreenCandidates, groupScreenBase, groupScreen, groupTimeKernel, groupScreenRelease!, seriesScreenBuild!, seriesScreen, seriesTimeKernel, seriesScreenRelease!, setIslandMode!, islands, islandTable, fromPower, angleDevice, DcStateEstimationBatch, removedRows, removeRows!,
+       DcPowerFlowBatch, setInjections!, setOutagePairs!, pairScreenBuild!, pairScreen, pairTimeKernel, pairScreenRelease!, pairScreenIslandMode!, pairScreenShed, seriesScreenIslandMode!, seriesScreenShed, transferScreenIslandMode!, transferScreenShed, generatorScreenBuild!, generatorScreen, generatorScreenFlows, generatorTimeKernel, generatorScreenRelease!, generatorScreenIslandMode!, generatorScreenShed, groupScreenBuild!, groupScreenDims, groupScreenCandidates, groupScreenBase, groupScreen, groupTimeKernel, groupScreenRelease!, cascadeScreenBuild!, cascadeScreen, cascadeScreenDims, cascadeScreenCandidates, cascadeScreenBase, cascadeTimeKernel, cascadeScreenRelease!, seriesScreenBuild!, seriesScreen, seriesTimeKernel, seriesScreenRelease!, setIslandMode!, islands, islandTable, fromPower, angleDevice, DcStateEstimationBatch, removedRows, removeRows!,
        GaussSeidelBatch, lastMismatch, setBusVoltage!, refreshGenerator!
 
 end # module

@@ -648,6 +648,43 @@ int jg_dc_chance_get_base(int64_t h, double* mean, double* std_dev, double* prob
 int jg_dc_chance_time_kernel(int64_t h, int kernel, int64_t k0, int64_t k1, int reps, double* ms);
 int jg_dc_chance_release(int64_t h);
 /*
+ * The DC cascading-outage screen (csrc/jg_dc_cascade.hpp): the user loop updateBranch!(s, status = 0) for an initiating outage, solve!, power!, then
+ * updateBranch! for every overloaded branch, solve!, power! again, until nothing is overloaded -- per initiating event.  Here an event is an outage set S
+ * that grows on the device: the algebra of jg_dc_group_build per stage, (I - Phi_SS) c = f0_S by LU with partial pivoting, f_m = f0_m + sum_s Phi[m,s] c_s,
+ * and ONE kernel launch runs a block of cascades to their ends.  Needs jg_dc_set_branches and jg_dc_set_rhs; neither the lanes of the handle nor what the
+ * other screens keep are touched.
+ *   jg_dc_cascade_build  the initiating events as a CSR, as jg_dc_group_build takes its groups (return code 1 names the event).  monitored [nm] (null:
+ *                        every branch in service): the branches that can trip and that are reported.  The candidates are the sorted union of all members
+ *                        and of the monitored branches in service -- whatever can trip needs its column -- so Phi is not blocked over candidates:
+ *                        return code 5 and the bytes needed and available when it does not fit budget_bytes (0: 80 % of the free memory), before any
+ *                        sweep.  info [8] as jg_dc_pair_build.  A second build replaces the first.
+ *   jg_dc_cascade_run    the cascades [c0, c1) (0-based; the block bounds the memory of a call) against the ratings of jg_dc_set_rating.  A monitored,
+ *                        rated branch trips when |flow| / rating > trip (strict; trip >= 0).  rule 0: every overloaded branch leaves at once, ascending
+ *                        by branch within a stage; rule 1: only the most loaded one (ties to the lowest branch).  most (2 to 8): branches out of service
+ *                        in one cascade, initiating ones included (an event with more members: return code 1).  Per cascade (each nullable): status
+ *                        (0: stable, 3: the set islands a part of the grid, 5: truncated -- the next stage would exceed `most`, the set stays), stages
+ *                        (stages of trips applied), size (branches out at the end), tripped / stage / loading [c1 - c0][most] (labels in the order they
+ *                        left, 0 unused; the stage each left at, 0 initiating, -1 unused; the loading that tripped it, NaN for initiating and unused
+ *                        slots), worst / worst_branch (the final state; NaN and 0 for status 3), pending (status 5: the overloaded branches).
+ *                        dense_flow (nullable) [c1 - c0][monitored ascending]: the final flows, 0 on what is out, NaN for status 3.  ms (nullable): the
+ *                        milliseconds of the kernel (HIP events).
+ *   jg_dc_cascade_get_dims         dims [6]: events, their leading dimension, candidates, rows of Phi, monitored branches, members of the largest event
+ *   jg_dc_cascade_get_candidates   labels [candidates], 1-based ascending
+ *   jg_dc_cascade_get_base         flow [monitored]: the base-case flows of the monitored branches, ascending
+ *   jg_dc_cascade_time_kernel      milliseconds of `reps` runs on the cascades [c0, c1) (a block jg_dc_cascade_run has held) with the trip and most of
+ *                                  the last run: kernel 0 rule 0, kernel 1 rule 1
+ *   jg_dc_cascade_release          frees what the screen holds on the device
+ */
+int jg_dc_cascade_build(int64_t h, int64_t nevents, const int64_t* offsets, const int64_t* members, int64_t nm, const int64_t* monitored, int64_t budget_bytes,
+                        double* info8);
+int jg_dc_cascade_run(int64_t h, int64_t c0, int64_t c1, double trip, int rule, int most, int32_t* status, int32_t* stages, int32_t* size, int64_t* tripped,
+                      int32_t* stage, double* loading, double* worst, int32_t* worst_branch, int32_t* pending, double* dense_flow, double* ms);
+int jg_dc_cascade_get_dims(int64_t h, int64_t* dims6);
+int jg_dc_cascade_get_candidates(int64_t h, int64_t* labels);
+int jg_dc_cascade_get_base(int64_t h, double* flow);
+int jg_dc_cascade_time_kernel(int64_t h, int kernel, int64_t c0, int64_t c1, int reps, double* ms);
+int jg_dc_cascade_release(int64_t h);
+/*
  * The DC N-1 screen over a SERIES of injection profiles (csrc/jg_dc_series.hpp): the user loop updateBus!(...; active) / updateGenerator!(...; active) per
  * profile t around updateBranch!(k, status = 0), solve!, power!, updateBranch!(k, status = 1) per branch k.  No sweep per case: with Phi of
  * jg_dc_pair_build and the profiles' base flows F0[m,t], f_m(k,t) = F0[m,t] + Phi[m,k] F0[k,t] / (1 - Phi[k,k]).  Needs jg_dc_set_branches and

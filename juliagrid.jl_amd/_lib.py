@@ -177,6 +177,13 @@ def lib():
         "jg_dc_chance_get_base": [C.c_int64, VP, VP, VP],
         "jg_dc_chance_time_kernel": [C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int, F64P],
         "jg_dc_chance_release": [C.c_int64],
+        "jg_dc_cascade_build": [C.c_int64, C.c_int64, I64P, I64P, C.c_int64, VP, C.c_int64, F64P],
+        "jg_dc_cascade_run": [C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_int, C.c_int, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP],
+        "jg_dc_cascade_get_dims": [C.c_int64, I64P],
+        "jg_dc_cascade_get_candidates": [C.c_int64, I64P],
+        "jg_dc_cascade_get_base": [C.c_int64, F64P],
+        "jg_dc_cascade_time_kernel": [C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int, F64P],
+        "jg_dc_cascade_release": [C.c_int64],
         "jg_dc_series_build": [C.c_int64, C.c_int64, I64P, C.c_int64, VP, C.c_int64, F64P, C.c_int64, F64P],
         "jg_dc_series_screen": [C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_int64, VP, VP, I64P, VP, VP, VP, VP, VP, VP, VP],
         "jg_dc_series_time_kernel": [C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int, F64P],

@@ -10,6 +10,7 @@
 #include "jg_dc_generator.hpp"
 #include "jg_dc_group.hpp"
 #include "jg_dc_chance.hpp"
+#include "jg_dc_cascade.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -290,6 +291,7 @@ void dc_destroy(DcHandle* h) {
     dc_generator_free(h);
     dc_group_free(h);
     dc_chance_free(h);
+    dc_cascade_free(h);
     for (void* p : h->allocs) hipFree(p);
     if (h->stream) hipStreamDestroy(h->stream);
     delete h;

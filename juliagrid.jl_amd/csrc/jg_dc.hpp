@@ -38,6 +38,7 @@ struct DcTransferState;
 struct DcGeneratorState;
 struct DcGroupState;
 struct DcChanceState;
+struct DcCascadeState;
 
 struct DcHandle : DcDevice {
     int n = 0, nbr = 0, batch = 0, ld = 0, slack = 0;
@@ -62,6 +63,7 @@ struct DcHandle : DcDevice {
     DcGeneratorState* generator = nullptr;                                     // the generator-outage screen: G-1 and generator x branch cases (jg_dc_generator.hpp)
     DcGroupState* group = nullptr;                                             // the common-mode screen over named outage groups of up to 8 branches (jg_dc_group.hpp)
     DcChanceState* chance = nullptr;                                           // the probabilistic N-1 screen under Gaussian injection uncertainty (jg_dc_chance.hpp)
+    DcCascadeState* cascade = nullptr;                                         // the cascading-outage screen: overload trips followed stage by stage (jg_dc_cascade.hpp)
     // island mode of the NEXT pair / series / transfer / generator build (the build takes it and sets it back to 0).  A sticky flag beside the build call is awkward -- the mode
     // belongs among the build's arguments -- but jg_dc_*_set_island_mode is part of the C ABI, so the flags stay
     int pair_shed = 0, series_shed = 0, transfer_shed = 0, generator_shed = 0;

@@ -10,6 +10,7 @@
 // which writes a violating row at the group's offset + the violators of the rows before it: sorted by (group, branch) without atomics, the first `capacity`
 // kept, the totals exact.  Every store is a vector store.
 #include "jg_dc_group.hpp"
+#include "jg_dc_group_lu.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -31,68 +32,19 @@ struct GroupArgs {
 };
 
 // ---- the k x k solve ----------------------------------------------------------------------------------------------------------------------
-// One lane per group.  The matrix lives in registers: every index below is a constant once the loops are unrolled, a row exchange is a select per entry
-// (no array is indexed by a runtime value, which would send the matrix to scratch).  A slot behind the group's last member is an identity row and column
-// with right-hand side 0: its pivot is 1 and its coefficient 0.  Partial pivoting: row j takes the entry of largest magnitude of column j among the rows
-// i >= j (ties: the upper row stays).
+// One lane per group; the solve itself is dc_group_lu (jg_dc_group_lu.hpp), which the cascade screen shares.
 template <int K>
 __global__ __launch_bounds__(64) void k_group_solve(GroupArgs a) {
     const int g = a.g0 + blockIdx.x * 64 + threadIdx.x;
     if (g >= a.g1) return;
-    const size_t ldk = (size_t)a.ldk, ldg = (size_t)a.ldg;
-    int p[K];
-    bool on[K];
-    double A[K][K], b[K], x[K];
+    const size_t ldg = (size_t)a.ldg;
+    int q[K];
+    double c[K];
 #pragma unroll
-    for (int i = 0; i < K; ++i) {
-        const int q = a.gpos[i * ldg + g];
-        on[i] = q >= 0;
-        p[i] = on[i] ? q : 0;
-        b[i] = on[i] ? a.cf0[p[i]] : 0.0;
-    }
+    for (int i = 0; i < K; ++i) q[i] = a.gpos[i * ldg + g];
+    const bool sing = dc_group_lu<K>(a.Phi, (size_t)a.ldk, a.crow, a.cf0, q, c);
 #pragma unroll
-    for (int i = 0; i < K; ++i) {
-        const double* prow = a.Phi + (size_t)a.crow[p[i]] * ldk;
-#pragma unroll
-        for (int j = 0; j < K; ++j) {
-            const double v = prow[p[j]];                         // Phi[s_i, s_j]: K gathers inside one row
-            A[i][j] = (i == j ? 1.0 : 0.0) - ((on[i] && on[j]) ? v : 0.0);
-        }
-    }
-    bool sing = false;
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-#pragma unroll
-        for (int i = j + 1; i < K; ++i) {
-            const bool sw = fabs(A[i][j]) > fabs(A[j][j]);
-#pragma unroll
-            for (int k = j; k < K; ++k) {
-                const double u = A[j][k], w = A[i][k];
-                A[j][k] = sw ? w : u; A[i][k] = sw ? u : w;
-            }
-            const double u = b[j], w = b[i];
-            b[j] = sw ? w : u; b[i] = sw ? u : w;
-        }
-        const bool bad = !(fabs(A[j][j]) >= DC_SINGULAR);       // (a NaN is singular too)
-        sing = sing || bad;
-        if (bad) A[j][j] = 1.0;                                  // the lane goes on with finite numbers; its result is not delivered
-#pragma unroll
-        for (int i = j + 1; i < K; ++i) {
-            const double l = A[i][j] / A[j][j];
-#pragma unroll
-            for (int k = j + 1; k < K; ++k) A[i][k] = fma(-l, A[j][k], A[i][k]);
-            b[i] = fma(-l, b[j], b[i]);
-        }
-    }
-#pragma unroll
-    for (int j = K - 1; j >= 0; --j) {
-        double s = b[j];
-#pragma unroll
-        for (int k = j + 1; k < K; ++k) s = fma(-A[j][k], x[k], s);
-        x[j] = s / A[j][j];
-    }
-#pragma unroll
-    for (int i = 0; i < K; ++i) a.c[i * ldg + g] = (sing || !on[i]) ? 0.0 : x[i];
+    for (int i = 0; i < K; ++i) a.c[i * ldg + g] = c[i];
     a.status[g] = sing ? 3 : 0;
 }
 
