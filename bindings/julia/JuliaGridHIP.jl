@@ -1978,6 +1978,34 @@ function timeKernel(b::DcStateEstimationBatch, kernel::Int, reps::Int = 20)
     check(ccall((:jg_dcse_time_kernel, lib), Cint, (Int64, Cint, Cint, Ptr{Float64}), b.token, kernel, reps, ms))
     return ms
 end
+"""
+    criticalScreen(b::DcStateEstimationBatch; correlation = nothing, capacity = 65536)
+
+The critical measurements and critical pairs of the full measurement set (jgrid.h: jg_dcse_critical_screen): `critical` rows, `pairs` [3, k] = (i, j, gamma)
+sorted by (i, j) with gamma = +-1 for the critical pairs and only for them, the exact totals, per row the `partner` of the largest |gamma| (0: none) with
+its `partnerCorrelation`, and the `variance` Omega_ii.  The lanes must not have removed rows.
+"""
+function criticalScreen(b::DcStateEstimationBatch; correlation::Union{Nothing, Float64} = nothing, capacity::Int64 = 65536)
+    m = b.se.number
+    records = zeros(Float64, 3, max(capacity, 1))
+    totals = zeros(Int64, 3)
+    single = zeros(Int32, m)
+    partner = zeros(Int32, m)
+    gamma = zeros(Float64, m)
+    variance = zeros(Float64, m)
+    check(ccall((:jg_dcse_critical_screen, lib), Cint, (Int64, Float64, Int64, Ptr{Float64}, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}),
+                b.token, correlation === nothing ? -1.0 : correlation, capacity, records, totals, single, partner, gamma))
+    check(ccall((:jg_dcse_get_variance, lib), Cint, (Int64, Ptr{Float64}), b.token, variance))
+    kept = min(totals[2] + totals[3], capacity)
+    return (critical = findall(single .== 1), pairs = records[:, 1:kept], totalSingles = totals[1], totalPairs = totals[2], totalCorrelated = totals[3],
+            partner = partner, partnerCorrelation = gamma, variance = variance)
+end
+"milliseconds of `reps` runs (HIP events) of the screen's cross pass over all rows against the first block of 512 columns"
+function criticalTimeKernel(b::DcStateEstimationBatch, reps::Int = 20)
+    ms = zeros(Float64, reps)
+    check(ccall((:jg_dcse_critical_time_kernel, lib), Cint, (Int64, Cint, Ptr{Float64}), b.token, reps, ms))
+    return ms
+end
 
 # ---- Gauss-Seidel power flow, one scenario per lane (jgrid.h: jg_gs_*; csrc/jg_gs.hip) ---------------------------------------------------
 # gaussSeidel / mismatch! / solve! / powerFlow! (src/powerFlow/acPowerFlow.jl:563-619, 732-764, 985-1041, 1389-1433) for `batch` scenarios of one grid: a
@@ -2144,7 +2172,7 @@ export HIP, HIPOrthogonal, NewtonRaphsonBatch, BaseCase, baseInfo, baseInverseOn
        largestNormalizedResidual, normalizedResiduals, commUniqueId, Comm, shard, contingencyAnalysis, clearPlanCache,
        deviceCount, dims, setRefinement!, deviceMaps, setOutage!, snapshotVoltage!, restoreVoltage!, iterations, voltageDevice!, packResults!, packRows!,
        allgatherDevice, commRank, commWorld, timeKernel, setBusType!, busType, GaussNewtonBatch, setRealisations!, monteCarloEstimation, fastPatch!, setReadings!, drawNoise!, measurementDevice,
-       DcPowerFlowBatch, setInjections!, setOutagePairs!, pairScreenBuild!, pairScreen, pairTimeKernel, pairScreenRelease!, pairScreenIslandMode!, pairScreenShed, seriesScreenIslandMode!, seriesScreenShed, transferScreenIslandMode!, transferScreenShed, generatorScreenBuild!, generatorScreen, generatorScreenFlows, generatorTimeKernel, generatorScreenRelease!, generatorScreenIslandMode!, generatorScreenShed, groupScreenBuild!, groupScreenDims, groupScreenCandidates, groupScreenBase, groupScreen, groupTimeKernel, groupScreenRelease!, cascadeScreenBuild!, cascadeScreen, cascadeScreenDims, cascadeScreenCandidates, cascadeScreenBase, cascadeTimeKernel, cascadeScreenRelease!, seriesScreenBuild!, seriesScreen, seriesTimeKernel, seriesScreenRelease!, setIslandMode!, islands, islandTable, fromPower, angleDevice, DcStateEstimationBatch, removedRows, removeRows!,
+       DcPowerFlowBatch, setInjections!, setOutagePairs!, pairScreenBuild!, pairScreen, pairTimeKernel, pairScreenRelease!, pairScreenIslandMode!, pairScreenShed, seriesScreenIslandMode!, seriesScreenShed, transferScreenIslandMode!, transferScreenShed, generatorScreenBuild!, generatorScreen, generatorScreenFlows, generatorTimeKernel, generatorScreenRelease!, generatorScreenIslandMode!, generatorScreenShed, groupScreenBuild!, groupScreenDims, groupScreenCandidates, groupScreenBase, groupScreen, groupTimeKernel, groupScreenRelease!, cascadeScreenBuild!, cascadeScreen, cascadeScreenDims, cascadeScreenCandidates, cascadeScreenBase, cascadeTimeKernel, cascadeScreenRelease!, seriesScreenBuild!, seriesScreen, seriesTimeKernel, seriesScreenRelease!, setIslandMode!, islands, islandTable, fromPower, angleDevice, DcStateEstimationBatch, removedRows, removeRows!, criticalScreen, criticalTimeKernel,
        GaussSeidelBatch, lastMismatch, setBusVoltage!, refreshGenerator!
 
 end # module

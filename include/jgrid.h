@@ -896,6 +896,25 @@ int jg_dcse_get_removed(int64_t h, int32_t* rows, int32_t* count);
 int jg_dcse_set_branches(int64_t h, int64_t nbr, const int64_t* from, const int64_t* to, const double* admittance, const double* shift_angle);
 int jg_dcse_get_flows(int64_t h, double* from);
 int jg_dcse_time_kernel(int64_t h, int kernel, int reps, double* ms);
+/* The critical-measurement and critical-pair screen of the handle's measurement set (csrc/jg_dcse_critical.hpp), on the same factor.  With
+ * Omega = W^-1 - H G^-1 H': row i is CRITICAL when w_i Omega_ii <= 1e-6 (its residual is always 0; it takes part in no pair and is nobody's partner); a
+ * pair i < j of other rows in service is CRITICAL when w_j (Omega_jj - Omega_ij^2 / Omega_ii) <= 1e-6 -- the pivot a lane meets that removes i, then j
+ * (status 1); gamma_ij = Omega_ij / sqrt(Omega_ii Omega_jj) otherwise.
+ *   jg_dcse_critical_screen   correlation < 0: critical pairs only; otherwise also the pairs with |gamma| >= correlation.  records [capacity][3]: the first
+ *                             min(total, capacity) records (i, j, gamma), rows 1-based, sorted by (i, j), gamma = +-1 for the critical pairs and only for
+ *                             them; totals [3] = {critical rows, critical pairs, further pairs at or above the correlation}, exact whatever the capacity;
+ *                             single [m] (1: critical); partner [m] (the row of the largest |gamma_ij|, first on ties, 0: none -- out of service, critical,
+ *                             or alone) and partner_gamma [m] (NaN where partner is 0).  records (capacity 0), single, partner, partner_gamma may be NULL.
+ *                             Code 4 when lanes have removed rows: the screen is a property of the full set (jg_dcse_set_weights forgets the removals
+ *                             and the screen then sees the new set).
+ *   jg_dcse_critical_time_kernel   milliseconds (HIP events) of `reps` runs of the cross pass over all rows of H against the first block of 512 columns
+ *   jg_dcse_get_variance      omega [m]: the Omega_ii of the full set the test and the screen use (formed if the factor is new; 1 / w_i for a row out
+ *                             of service)
+ */
+int jg_dcse_critical_screen(int64_t h, double correlation, int64_t capacity, double* records, int64_t* totals, int32_t* single, int32_t* partner,
+                            double* partner_gamma);
+int jg_dcse_critical_time_kernel(int64_t h, int reps, double* ms);
+int jg_dcse_get_variance(int64_t h, double* omega);
 
 /* ---------------------------------------------------------------------------------------------
  * Gauss-Seidel AC power flow, one scenario per lane (csrc/jg_gs.hip).  The handle is an int64 token, as for jg_dc_*.

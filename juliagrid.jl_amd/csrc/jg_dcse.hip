@@ -421,6 +421,13 @@ int dcse_create(DcseHandle* h, int64_t n64, int64_t m64, const int64_t* rowptr, 
     return 0;
 }
 
+}  // namespace
+
+// (jg_dcse_critical.hip fills its right-hand sides with the same kernel)
+void launch_row_rhs(DcseHandle* h, const int* rowid, double* B, int ld) {
+    hipLaunchKernelGGL(k_dcse_row_rhs, dim3((ld + 255) / 256), dim3(256), 0, h->stream, rowid, h->r_ptr, h->r_col, h->r_val, h->st, B, ld, h->slack);
+}
+
 // Omega_ii = 1 / w_i - h_i G^-1 h_i' for every row, rows of H as the lanes of the shared sweep pair, DCSE_OMEGA_LD rows per pair
 int compute_omega(DcseHandle* h) {
     const int ldo = DCSE_OMEGA_LD;
@@ -450,6 +457,8 @@ int compute_omega(DcseHandle* h) {
     h->omega_runs++;
     return 0;
 }
+
+namespace {
 
 int run_test_pass(DcseHandle* h, double* NRM) {
     if (!h->omega_valid) DC_TRY(compute_omega(h));

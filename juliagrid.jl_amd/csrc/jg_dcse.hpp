@@ -63,4 +63,9 @@ struct DcseHandle : DcDevice {
     bool solved = false, have_z = false;
 };
 
+// jg_dcse.hip, for jg_dcse_critical.hip: the Omega diagonal of the full set into h->omega (omega_valid), and k_dcse_row_rhs on the handle's stream --
+// lane bl of B [n][ld] (zero on entry) gets row rowid[bl] of H (-1 or out of service: none) without the slack's entry
+int compute_omega(DcseHandle* h);
+void launch_row_rhs(DcseHandle* h, const int* rowid, double* B, int ld);
+
 }  // namespace jg
