@@ -409,6 +409,16 @@ leaves room on a compute unit for the other batches' workgroups.  Results are bi
 shareDevice!(b::NewtonRaphsonBatch, on::Bool = true) =
     check(ccall((:jg_nr_set_shared, lib), Cint, (Ptr{Cvoid}, Cint), b.handle.ptr, on ? 1 : 0))
 
+"""
+    keepIncrement!(batch, on = true)
+
+`on = false`: the batch no longer stores `method.increment` in bus order (`jg_nr_set_keep_increment`): every sweep and lane compaction moves 16 bytes per
+bus and scenario less, voltages, iteration counts and status are bitwise unchanged, and reading the increment raises until the switch is on again and
+the batch has run.  A screen that reads voltages and branch records only switches it off.
+"""
+keepIncrement!(b::NewtonRaphsonBatch, on::Bool = true) =
+    check(ccall((:jg_nr_set_keep_increment, lib), Cint, (Ptr{Cvoid}, Cint), b.handle.ptr, on ? 1 : 0))
+
 "scenario s (1-based) = base grid with branch labels[s] out of service (0: base case); one upload for the whole batch"
 function setOutages!(b::NewtonRaphsonBatch, labels::Vector{Int64})
     length(labels) == b.batch || throw(DimensionMismatch("one label per scenario"))
@@ -2168,7 +2178,7 @@ function timeKernel(b::GaussSeidelBatch, kernel::Int, sweeps::Int64, reps::Int =
     return ms
 end
 
-export HIP, HIPOrthogonal, NewtonRaphsonBatch, BaseCase, baseInfo, baseInverseOnPattern, attach!, startFromBase!, firstIteration!, firstIterationCounts, setOutages!, shareDevice!, branchQuantities, screenSummary, powerFlowDefer!, moveLanes!, finish!, resume!, jacobian!,
+export HIP, HIPOrthogonal, NewtonRaphsonBatch, BaseCase, baseInfo, baseInverseOnPattern, attach!, startFromBase!, firstIteration!, firstIterationCounts, setOutages!, shareDevice!, keepIncrement!, branchQuantities, screenSummary, powerFlowDefer!, moveLanes!, finish!, resume!, jacobian!,
        largestNormalizedResidual, normalizedResiduals, commUniqueId, Comm, shard, contingencyAnalysis, clearPlanCache,
        deviceCount, dims, setRefinement!, deviceMaps, setOutage!, snapshotVoltage!, restoreVoltage!, iterations, voltageDevice!, packResults!, packRows!,
        allgatherDevice, commRank, commWorld, timeKernel, setBusType!, busType, GaussNewtonBatch, setRealisations!, monteCarloEstimation, fastPatch!, setReadings!, drawNoise!, measurementDevice,

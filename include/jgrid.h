@@ -111,7 +111,9 @@ int jg_nr_solve(jg_nr* h);
  * UMFPACK's solve behind ldiv! (src/backend/utility.jl:576-586; UMFPACK refines by default, KLU does not).  J d is formed from
  * Ybus and the state (the factor has overwritten J); costs one more pass over the rows, a forward-only and a backward sweep
  * (~ +45 % per iteration).  Independent of the mode a pivot block that cancels to rounding level marks its scenario (status 3).
- * mode 0 (default): no refinement -- Newton's iteration corrects a rounding-level error of one step in the next. */
+ * mode 0 (default): no refinement -- Newton's iteration corrects a rounding-level error of one step in the next.
+ * Refinement writes the increment: mode 1 switches jg_nr_set_keep_increment back to 1 on a handle that had it at 0, and fails on such a handle while
+ * it is paused (jg_nr_run_defer). */
 int jg_nr_set_refine(jg_nr* h, int mode);
 /* Performance hint, no counterpart in the reference (one analysis at a time).  mode 1: this handle is one of SEVERAL batches in flight on
  * its GPU (a pipeline of contingency batches): the multifrontal top of the factorisation always runs its 4-wave kernel variant, which
@@ -119,6 +121,15 @@ int jg_nr_set_refine(jg_nr* h, int mode);
  * handle that runs alone).  Results are bitwise the same either way (tests/test_top_variants_gpu.py).  mode 0 (default): by the size of
  * each launch. */
 int jg_nr_set_shared(jg_nr* h, int mode);
+/* Performance switch, no counterpart in the reference.  mode 1 (default): every Newton step leaves method.increment in bus order for
+ * jg_nr_get_increment, and a scenario's last increment travels with its lane.  mode 0: the batched sweeps (the refactorising iteration and the
+ * first step on a shared base factor) write the increment in pivot order and into the state only -- 16 bytes x buses x lanes less per sweep and
+ * per lane compaction; jg_nr_get_increment then fails (it never returns an older run's values).  V, theta, iteration counts and status are
+ * bitwise the same either way (tests/test_sweep_diet_gpu.py).  Switching back to 1 holds from the next run; until that run jg_nr_get_increment
+ * still fails.  jg_nr_set_refine(h, 1) switches the handle back to 1 (refinement writes the increment), and mode 0 is refused while refinement
+ * is on or the handle is paused.  A single-instance handle accepts the switch but its sweep stores as before.  A pipeline of contingency batches
+ * sets 0 on its batch and pool handles: it reads V, theta and branch records, never the increment. */
+int jg_nr_set_keep_increment(jg_nr* h, int mode);
 /* powerFlow!(analysis; iteration, tolerance) -- acPowerFlow.jl:1389-1433, per scenario, with the
  * reference's loop accounting.  iters/status: [batch]; status 0 converged, 1 iteration limit,
  * 3 numeric failure, 4 deferred to a pool (jg_nr_run_defer), 5 no slack bus left after jg_nr_reactive_limit (the reference's

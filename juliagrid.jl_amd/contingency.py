@@ -341,6 +341,8 @@ class ContingencyPipeline:
         if len(self.handles) + len(self.pools) > 1:      # several batches share the GPU: the top launches leave room for the others' workgroups
             for an in self.handles + [p.handle for p in self.pools]:
                 _lib.check(_lib.lib().jg_nr_set_shared(an._h, 1))
+        for an in self.handles + [p.handle for p in self.pools]:      # a screen reads V, theta and branch records, never method.increment: the sweeps
+            _lib.check(_lib.lib().jg_nr_set_keep_increment(an._h, 0))  # and lane moves stop writing its bus-order copy (same bits; `an.increment` raises)
         if start is not None:
             self.setStart(*start)
         else:                                            # default restart point of every solve: the start newtonRaphson() built

@@ -42,6 +42,7 @@ struct CSweepArgs {
     GroupSel sel; StateUpdate upd;
     int ld, seg_begin, lanes;
     int s0_base, s0_nchunks, s0_wpi, s0_rpw;
+    int dead_ok;                   // backward: a row marked in w2 (BWD_DEAD_BIT) keeps its pivot-order store back (CompBase::solve)
 };
 
 // one record: up to COMP_T terms  acc -= M(entry) * W[row]; every vector operand requested before the first use (jg_engine.hpp: gload16)
@@ -85,7 +86,7 @@ __global__ __launch_bounds__(512, 4) void k_csweep(CSweepArgs a) {
     const size_t ri = (size_t)base + ((size_t)bx * 8 + wave) * rpw;
     const RecS first = load_rec(a.rec, ri);
     const int sub = wave & (wpi - 1);
-    const int k = first[0], src = first[1], dg = first[2];
+    const int k = first[0], src = first[1], dgw = first[2], dg = dgw & BWD_ENTRY_MASK;     // (forward: w2 = -1, unused)
     double a0 = 0.0, a1 = 0.0;
     int fl = 0; bool act = true; double va = 0.0, vm = 0.0;
     if (k >= 0) {
@@ -116,9 +117,9 @@ __global__ __launch_bounds__(512, 4) void k_csweep(CSweepArgs a) {
     if (wpi > 1) __syncthreads();
     if (k >= 0 && sub == 0) {
         for (int w = 1; w < wpi; ++w) { const double2 p = ((const double2*)red)[(size_t)(wave + w) * 64 + lane]; a0 += p.x; a1 += p.y; }
-        store_vec(a.W, (size_t)k, b, ld, a0, a1);
+        if (!(BWD && a.dead_ok && ((dgw >> BWD_DEAD_BIT) & 1))) store_vec(a.W, (size_t)k, b, ld, a0, a1);
         if (BWD) {
-            if (!a.upd.va || act) store_vec(a.out, (size_t)src, b, ld, a0, a1);     // a finished scenario keeps its last increment
+            if (a.out && (!a.upd.va || act)) store_vec(a.out, (size_t)src, b, ld, a0, a1);     // a finished scenario keeps its last increment (out = nullptr: nobody reads it)
             if (a.upd.va) {
                 if (act && (fl & 1)) a.upd.va[(size_t)src * ld + b] = va + a.upd.sign * a0;
                 if (act && (fl & 2)) a.upd.vm[(size_t)src * ld + b] = vm + a.upd.sign * a1;
@@ -140,6 +141,7 @@ struct CTopArgs {
     const int* piv; const int* bus;
     double* W; double* out; GroupSel sel; StateUpdate upd;
     int ld, lanes, n, n_top, n_rb;
+    int dead_ok;                                                 // a top pivot marked in piv (BWD_DEAD_BIT) is handed down to nobody: its pivot-order store is skipped
 };
 typedef double d4v __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(64 * CTOP_WAVES) void k_ctop(CTopArgs a) {
@@ -200,9 +202,9 @@ __global__ __launch_bounds__(64 * CTOP_WAVES) void k_ctop(CTopArgs a) {
 #pragma unroll
         for (int w = 0; w < CTOP_WAVES; ++w) x += part[w][j][r][lane];
         if (t >= a.n_top) continue;
-        const int k = a.piv[t], bus = a.bus[t];
-        a.W[((size_t)k * ld + b) * 2 + c] = x;
-        if (!a.upd.va || act) a.out[((size_t)bus * ld + b) * 2 + c] = x;
+        const int kw = a.piv[t], k = kw & BWD_ENTRY_MASK, bus = a.bus[t];
+        if (!(a.dead_ok && ((kw >> BWD_DEAD_BIT) & 1))) a.W[((size_t)k * ld + b) * 2 + c] = x;
+        if (a.out && (!a.upd.va || act)) a.out[((size_t)bus * ld + b) * 2 + c] = x;
         if (a.upd.va && act) {
             const int fl = (int)a.upd.flags[bus];
             double* st = c == 0 ? a.upd.va : a.upd.vm;
@@ -257,7 +259,7 @@ __global__ void k_unit_clear(double* rhs, const int* row, const int* comp, int l
 __global__ void k_take_sinv(const double* W, const int* piv, double* Sinv, int n_ks, int n_top, int ld, int col0, int count) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
     if (b >= count || i >= n_top) return;
-    const double2 x = *(const double2*)(W + ((size_t)piv[i] * ld + b) * 2);
+    const double2 x = *(const double2*)(W + ((size_t)(piv[i] & BWD_ENTRY_MASK) * ld + b) * 2);
     const int kc = col0 + b, ks = kc >> 2, kq = kc & 3;
     for (int c = 0; c < 2; ++c) {
         const int r = 2 * i + c, rb = r >> 4, rr = r & 15;
@@ -395,8 +397,13 @@ int CompSweep::upload_tables(const BlockSymbolic& S, int top_cap, hipStream_t st
     build_comp_tables(S, top_cap, T);
     std::vector<int> bus(T.top.size());
     for (size_t i = 0; i < T.top.size(); ++i) bus[i] = S.perm[T.top[i]];
-    if (upload(&fwd_rec, T.fwd_rec, err, st) || upload(&fwd_seg, T.fwd_seg, err, st) || upload(&bwd_rec, T.bwd_rec, err, st) || upload(&bwd_seg, T.bwd_seg, err, st) ||
-        upload(&top_piv, T.top, err, st) || upload(&top_bus, bus, err, st)) return 2;
+    // device copies with the marks of the rows of the scratch no backward record reads (CompTables::dead): w2 of a backward record, a top pivot
+    std::vector<Rec> bwd_dev = T.bwd_rec;
+    std::vector<int> top_dev = T.top;
+    for (Rec& r : bwd_dev) if (r.w[0] >= 0 && T.dead[r.w[0]]) r.w[2] |= 1 << BWD_DEAD_BIT;
+    for (int& k : top_dev) if (T.dead[k]) k |= 1 << BWD_DEAD_BIT;
+    if (upload(&fwd_rec, T.fwd_rec, err, st) || upload(&fwd_seg, T.fwd_seg, err, st) || upload(&bwd_rec, bwd_dev, err, st) || upload(&bwd_seg, T.bwd_seg, err, st) ||
+        upload(&top_piv, top_dev, err, st) || upload(&top_bus, bus, err, st)) return 2;
     auto launches = [](const std::vector<Segment>& segs, std::vector<DevLaunch>& out) {
         out.clear();
         size_t s = 0;
@@ -421,8 +428,8 @@ void CompSweep::free_tables() {
     fwd_rec = bwd_rec = nullptr; fwd_seg = bwd_seg = nullptr; top_piv = top_bus = nullptr;
 }
 
-int CompBase::solve(const CompSweep& sw, hipStream_t st, const double* rhs, double* Wc, double* out, int ld, int lanes, const StateUpdate& upd, const GroupSel& sel) const {
-    CSweepArgs a{sw.fwd_rec, sw.fwd_seg, Mc, rhs, Wc, out, sel, StateUpdate{}, ld, 0, lanes, 0, 0, 1, 1};
+int CompBase::solve(const CompSweep& sw, hipStream_t st, const double* rhs, double* Wc, double* out, int ld, int lanes, const StateUpdate& upd, const GroupSel& sel, bool dead_ok) const {
+    CSweepArgs a{sw.fwd_rec, sw.fwd_seg, Mc, rhs, Wc, out, sel, StateUpdate{}, ld, 0, lanes, 0, 0, 1, 1, dead_ok ? 1 : 0};
     for (const DevLaunch& L : sw.fwd) {
         a.seg_begin = L.seg_begin;
         { const Segment& g = sw.T.fwd_seg[L.seg_begin]; a.s0_base = g.rec_base; a.s0_nchunks = g.nchunks; a.s0_wpi = g.wpi; a.s0_rpw = g.rpw; }
@@ -430,7 +437,7 @@ int CompBase::solve(const CompSweep& sw, hipStream_t st, const double* rhs, doub
     }
     if (sw.T.n_top > 0) {
         const int n_rb = (2 * sw.T.n_top + 15) / 16;
-        CTopArgs t{Sinv, lds, sw.top_piv, sw.top_bus, Wc, out, sel, upd, ld, lanes, n, sw.T.n_top, n_rb};
+        CTopArgs t{Sinv, lds, sw.top_piv, sw.top_bus, Wc, out, sel, upd, ld, lanes, n, sw.T.n_top, n_rb, dead_ok ? 1 : 0};
         hipLaunchKernelGGL(k_ctop, dim3(grid_blocks(ld / 64, n_rb)), dim3(64, CTOP_WAVES), 0, st, t);
     }
     a.rec = sw.bwd_rec; a.seg = sw.bwd_seg; a.upd = upd;

@@ -38,7 +38,9 @@ struct CompBase {
     int create(const BlockSymbolic& S, const double* Xsrc, int ldx, int top_cap, hipStream_t st);
     void destroy();
     // x = J_0^-1 rhs for the scenarios of `sel`: rhs [n][ld][2] bus order, Wc scratch [(n + n_top_pad)][ld][2], out [n][ld][2] bus order; optional fused state update
-    int solve(const CompSweep& sw, hipStream_t st, const double* rhs, double* Wc, double* out, int ld, int lanes, const StateUpdate& upd, const GroupSel& sel) const;
+    // (out = nullptr: the bus-order copy is not written -- the backward rows and the top's epilogue store pivot order and state only)
+    int solve(const CompSweep& sw, hipStream_t st, const double* rhs, double* Wc, double* out, int ld, int lanes, const StateUpdate& upd, const GroupSel& sel, bool dead_ok = false) const;
+    // dead_ok: nobody reads the scratch as a whole after this solve -- the rows no backward record names (CompTables::dead) are not stored in pivot order either
     size_t scratch_rows(const CompSweep& sw) const { return (size_t)n + (size_t)((sw.T.n_top + 7) & ~7); }      // the top's partial rows, padded (zero) to the k steps k_ctop reads: 16 values = 8 rows
 };
 

@@ -39,6 +39,7 @@ struct BwdArgs {
     int ld, seg_begin;
     int lanes;
     int s0_base, s0_nchunks, s0_wpi, s0_rpw;
+    int dead_ok;               // 1 = a row marked in its diagonal-entry word (BWD_DEAD_BIT) keeps its pivot-order store back: nothing reads it (Engine::backsolve grants it)
 };
 
 
@@ -227,11 +228,13 @@ __device__ __forceinline__ UpdPre upd_prefetch(const BwdArgs& a, int bus, size_t
     }
     return p;
 }
-__device__ __forceinline__ double2 bwd_finish(const BwdArgs& a, const Blk& d, double y0, double y1, int k, int bus, size_t b, size_t ld, const UpdPre& p) {
+// dgw: the row's diagonal-entry word as the tables hold it (the mark of a row nobody reads back sits in BWD_DEAD_BIT; uniform)
+__device__ __forceinline__ double2 bwd_finish(const BwdArgs& a, const Blk& d, double y0, double y1, int k, int bus, int dgw, size_t b, size_t ld, const UpdPre& p) {
     double x0, x1;
     dsolve(d, y0, y1, x0, x1);
-    store_vec(a.W, (size_t)k, b, ld, x0, x1);
-    if (!a.upd.va || p.act) store_vec(a.out, (size_t)bus, b, ld, x0, x1);      // a finished scenario keeps its last increment
+    if (!(a.dead_ok && ((dgw >> BWD_DEAD_BIT) & 1))) store_vec(a.W, (size_t)k, b, ld, x0, x1);
+    // out == nullptr (a kernel argument: uniform): nobody reads the bus-order copy of this handle (jg_nr_set_keep_increment) -- 16 B x n x lanes less per sweep
+    if (a.out && (!a.upd.va || p.act)) store_vec(a.out, (size_t)bus, b, ld, x0, x1);      // a finished scenario keeps its last increment
     if (a.upd.va) {
         if (p.act && (p.fl & 1)) a.upd.va[(size_t)bus * ld + b] = p.va + a.upd.sign * x0;
         if (p.act && (p.fl & 2)) a.upd.vm[(size_t)bus * ld + b] = p.vm + a.upd.sign * x1;
@@ -300,7 +303,7 @@ __device__ __forceinline__ void bwd_chain_task(const BwdArgs& a, double* lds, co
     Blk mb[CHAIN_PF][2], db[CHAIN_PF];
     auto request = [&](int c, Blk (&m)[2], Blk& d) {
         if (c < 0) return;
-        if (wave == (c & 15)) d = load_blk(a.X, (size_t)rows[3 * c + 2], b, ld);
+        if (wave == (c & 15)) d = load_blk(a.X, (size_t)(rows[3 * c + 2] & BWD_ENTRY_MASK), b, ld);
 #pragma unroll
         for (int i = 0; i < 2; ++i) { const int p = wave + 16 * i; if (p < c) m[i] = load_blk(a.X, (size_t)uin[p * nb + c], b, ld); }
     };
@@ -314,7 +317,7 @@ __device__ __forceinline__ void bwd_chain_task(const BwdArgs& a, double* lds, co
                 double2* slot = xc + (c & 1) * 64;
                 if (wave == (c & 15)) {
                     const double2 y = acc[c * 64 + lane];
-                    slot[lane] = bwd_finish(a, db[s], y.x, y.y, rows[3 * c], rows[3 * c + 1], b, ld, c < 16 ? up0 : up1);
+                    slot[lane] = bwd_finish(a, db[s], y.x, y.y, rows[3 * c], rows[3 * c + 1], rows[3 * c + 2], b, ld, c < 16 ? up0 : up1);
                 }
                 __syncthreads();
                 const double2 x = slot[lane];
@@ -355,14 +358,15 @@ __device__ __forceinline__ void bwd_chain_small(const BwdArgs& a, double* lds, c
     UpdPre up{0, false, 0.0, 0.0};
     double y0 = 0.0, y1 = 0.0;
     Blk d{0.0, 0.0, 0.0, 0.0};
-    int k = 0, bus = 0;
+    int k = 0, bus = 0, dgw = 0;
     Blk mb[CHAIN_PF];
     auto request = [&](int c, Blk& m) { if (owner && c > p) m = load_blk(a.X, (size_t)uin[p * nb + c], b, ld); };
     if (owner) {
         k = rows[3 * p]; bus = rows[3 * p + 1];
         up = upd_prefetch(a, bus, b, ld);
         const double2 y = load_vec(a.W, (size_t)k, b, ld); y0 = y.x; y1 = y.y;
-        d = load_blk(a.X, (size_t)rows[3 * p + 2], b, ld);
+        dgw = rows[3 * p + 2];
+        d = load_blk(a.X, (size_t)(dgw & BWD_ENTRY_MASK), b, ld);
     }
 #pragma unroll
     for (int s = 0; s < CHAIN_PF; ++s) request(nb - 1 - s, mb[s]);
@@ -395,7 +399,7 @@ __device__ __forceinline__ void bwd_chain_small(const BwdArgs& a, double* lds, c
             const int c = c0 - s;
             if (c >= 0) {                                        // uniform across the workgroup
                 double2* slot = xc + (c & 1) * 64;
-                if (owner && p == c) slot[lane] = bwd_finish(a, d, y0, y1, k, bus, b, ld, up);
+                if (owner && p == c) slot[lane] = bwd_finish(a, d, y0, y1, k, bus, dgw, b, ld, up);
                 if (c > 0) {
                     __syncthreads();
                     if (owner && p < c) {
@@ -415,7 +419,7 @@ __device__ __forceinline__ void bwd_chain_small(const BwdArgs& a, double* lds, c
 __device__ __forceinline__ void bwd_chunk(const BwdArgs& a, double* red, const RecS& first, size_t rec_index, int rpw, int wpi,
                                           int wave, int lane, size_t b, size_t ld) {
     const int sub = wave & (wpi - 1);
-    const int k = rec_word(first, 0), bus = rec_word(first, 1), dg = rec_word(first, 2);
+    const int k = rec_word(first, 0), bus = rec_word(first, 1), dgw = rec_word(first, 2), dg = dgw & BWD_ENTRY_MASK;
     double y0 = 0.0, y1 = 0.0;
     Blk d{0.0, 0.0, 0.0, 0.0};
     UpdPre up{0, false, 0.0, 0.0};
@@ -438,7 +442,7 @@ __device__ __forceinline__ void bwd_chunk(const BwdArgs& a, double* red, const R
     if (wpi > 1) __syncthreads();
     if (k >= 0 && sub == 0) {
         for (int w = 1; w < wpi; ++w) { const double2 p = ((const double2*)red)[(size_t)(wave + w) * 64 + lane]; y0 += p.x; y1 += p.y; }
-        bwd_finish(a, d, y0, y1, k, bus, b, ld, up);
+        bwd_finish(a, d, y0, y1, k, bus, dgw, b, ld, up);
     }
     if (wpi > 1) __syncthreads();
 }
@@ -2089,10 +2093,25 @@ std::shared_ptr<SharedPlan> acquire_plan(int n, const int* rowptr, const int* co
     const double tu0 = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
     std::vector<int> prow(n, 0);                                 // by ORIGINAL block index: pivot + 1 where the producer finishes D and y
     for (int k = 0; k < n; ++k) if (S.prefactor && S.pre_pivot[k]) prow[S.perm[k]] = k + 1;
+    // the device copies of the Jordan sweep's tables carry the marks of the rows whose pivot-order store nobody reads (jg_symbolic.hpp: bwd_dead; the host tables stay plain)
+    std::vector<Rec> bwdj_dev = S.bwdj_rec;
+    std::vector<int> chain_dev = S.bwd_chain;
+    if (S.bwd_dead_ok)
+        for (const Segment& sg : S.bwdj_seg) {
+            if (sg.wpi <= 0) {
+                for (int x = 0; x < sg.nchunks; ++x) {
+                    const Rec& r = S.bwdj_rec[(size_t)sg.rec_base + x];
+                    for (int q = 0; q < r.w[0]; ++q) { int* row = chain_dev.data() + r.w[2] + 3 * q; if (S.bwd_dead[row[0]]) row[2] |= 1 << BWD_DEAD_BIT; }
+                }
+                continue;
+            }
+            const size_t nrec = (size_t)sg.nchunks * 16 * sg.rpw;
+            for (size_t x = 0; x < nrec; ++x) { Rec& r = bwdj_dev[(size_t)sg.rec_base + x]; if (r.w[0] >= 0 && S.bwd_dead[r.w[0]]) r.w[2] |= 1 << BWD_DEAD_BIT; }
+        }
     if (upload(&p->pre_rec, S.pre_rec, error, st) || upload(&p->pre_seg, S.pre_seg, error, st) || upload(&p->pre_row, prow, error, st) ||
         upload(&p->fact_rec, S.fact_rec, error, st) || upload(&p->bwd_rec, S.bwd_rec, error, st) || upload(&p->fact_seg, S.fact_seg, error, st) ||
-        upload(&p->bwd_seg, S.bwd_seg, error, st) || upload(&p->bwd_chain, S.bwd_chain, error, st) ||
-        (S.jordan && (upload(&p->bwdj_rec, S.bwdj_rec, error, st) || upload(&p->bwdj_seg, S.bwdj_seg, error, st))) ||
+        upload(&p->bwd_seg, S.bwd_seg, error, st) || upload(&p->bwd_chain, chain_dev, error, st) ||
+        (S.jordan && (upload(&p->bwdj_rec, bwdj_dev, error, st) || upload(&p->bwdj_seg, S.bwdj_seg, error, st))) ||
         upload(&p->fwd_rec, S.fwd_rec, error, st) || upload(&p->fwd_seg, S.fwd_seg, error, st) ||
         (S.single_fact_ok && (upload(&p->f1_rec, S.f_rec, error, st) || upload(&p->f1_wg, S.f1_wg, error, st))) ||
         (!S.top_launch.empty() && (upload(&p->top_task, S.top_task, error, st) || upload(&p->top_data, S.top_data, error, st) || upload(&p->top_wgmap, S.top_wgmap, error, st)))) {
@@ -2417,6 +2436,7 @@ int Engine::set_shared_matrix(hipStream_t st, const double* blocks_host) {
 int Engine::backsolve(hipStream_t st, double* out, const StateUpdate& upd, const GroupSel& sel) {
     if (single_bwd && jordan) {                                  // ONE scenario: rows per lane, two launches (k_bwd1_top, k_bwd1_bottom)
         const SingleTables& T = plan->single;
+        if (!out) { error = "backsolve: the single-instance sweep always stores the bus-order solution (out = nullptr is for the batched level kernels)"; return 1; }
         Bwd1Args s{plan->s1_t_row, plan->s1_t_ptr, plan->s1_t_term, plan->s1_t_level, plan->s1_b_wg, plan->s1_b_row, plan->s1_b_term, X, jc, W, out, sel, upd, ld, T.n_top_levels, T.n_wg, T.n_top,
                    plan->s1_t_jb, plan->s1_t_cslot, plan->s1_t_toff, T.max_level_terms};
         const int flat_env = knob("SINGLE", 1);                   // JG_SINGLE=2: the quad-per-row sweep (k_bwd1_top) where the terms-as-lanes one would run
@@ -2427,7 +2447,11 @@ int Engine::backsolve(hipStream_t st, double* out, const StateUpdate& upd, const
         return 0;
     }
     // jordan: the last factor() left Jordan rows (the flag must not change between a factorisation and its solves)
-    BwdArgs a{jordan ? plan->bwdj_rec : bwd_rec, jordan ? plan->bwdj_seg : bwd_seg, bwd_chain, X, W, out, sel, upd, ld, 0, lanes > 0 ? lanes : ld, 0, 0, 1, 1};
+    // Pivot-order stores nobody reads back (jg_symbolic.hpp: bwd_dead) are skipped under the conditions of the sweep-only factor -- the owner reads this factor and its
+    // solution through the Jordan sweep alone: no forward() + backsolve() of a refined step (which switches `jordan` off), no selected inverse, no Gauss-Newton handle
+    // (neither sets sweep_only) -- and JG_SWEEP_DEAD=0 keeps them (read at every capture: the tests hold both forms against each other in one process).
+    const int dead_ok = sweep_only && jordan && plan->S.jordan && plan->S.bwd_dead_ok && !Zs && knob("SWEEP_DEAD", 1) != 0 ? 1 : 0;
+    BwdArgs a{jordan ? plan->bwdj_rec : bwd_rec, jordan ? plan->bwdj_seg : bwd_seg, bwd_chain, X, W, out, sel, upd, ld, 0, lanes > 0 ? lanes : ld, 0, 0, 1, 1, dead_ok};
     const std::vector<Segment>& segs = jordan ? plan->S.bwdj_seg : plan->S.bwd_seg;
     for (const DevLaunch& L : (jordan ? bwdj : bwd)) {
         a.seg_begin = L.seg_begin;

@@ -288,7 +288,8 @@ struct Engine {
     // Fill the (in-place) factor storage with ONE shared matrix: blocks [nnz of the caller's pattern][4] (row-major 2x2),
     // replicated over every scenario; fill-in entries need nothing.
     int set_shared_matrix(hipStream_t st, const double* blocks_host);
-    // x = U^-1 D y, scattered to original order into out [n][2][ld]; optional fused state update.
+    // x = U^-1 D y, scattered to original order into out [n][2][ld]; optional fused state update.  out = nullptr: the batched sweeps leave x in pivot order (W)
+    // only and, with a state update, in the state -- nobody reads the bus-order copy (jg_nr_set_keep_increment); the single-instance sweep refuses it.
     int backsolve(hipStream_t st, double* out, const StateUpdate& upd, const GroupSel& sel);
     size_t factor_bytes() const { return ((size_t)plan->S.n_entries + (size_t)plan->S.n_jordan) * 4 * ld * sizeof(double); }   // Jordan rows sit behind the entries
 };

@@ -573,6 +573,8 @@ struct jg_nr : jg::Lanes {             // Lanes: stream, batch, ld, the staging 
     int* d_lid = nullptr; int* d_dest = nullptr; int* d_cflags = nullptr; int* d_itmp = nullptr; int* d_glist = nullptr;   // scenario compaction (d_vm ... d_glist without d_dst, d_vm0, d_va0: ONE arena, jg_nr_create)
     jg::Compaction cmp{};                             // ... what it works on (jg_compact.hpp), filled once by jg_nr_create
     bool refine = false;                              // one step of iterative refinement per Newton step (jg_nr_set_refine)
+    bool keep_inc = true;                             // jg_nr_set_keep_increment: the batched sweeps store method.increment (d_inc, bus order) and the lane moves carry it
+    bool inc_fresh = true;                            // ... and d_inc holds what a run with the switch on left (jg_nr_get_increment refuses anything else)
     bool fast = false;                                // fast decoupled mode (jg_nr_fast_setup): constant B', B'' factorised once
     std::vector<double> fast_blk;                     // ... the shared block matrix diag(B', B'') as set up [nnz][4] (engine block order)
     std::vector<int> fp_entry; std::vector<double> fp_dp, fp_dq;   // per-scenario edits of B' / B'' (jg_nr_fast_patch_batch): [FAST_MP][batch] factor entry (-1: none), deltas
@@ -656,6 +658,15 @@ unsigned char classify_patch(const jg_nr* h, const int* pos, int k) {
     if (!any) return 0;
     return (b < 0 || joined) ? 1 : 2;
 }
+
+// Where the sweeps of the iteration store the bus-order increment: nowhere while the handle keeps none (a null `out` of BwdArgs / CSweepArgs / CTopArgs).
+// The single-instance sweep (k_bwd1_*) always stores.
+// (Engine::backsolve takes the single-instance path on single_bwd && jordan and refuses a null out there: deciding on single_bwd alone errs on the storing side,
+// and that refusal is what would catch the two conditions drifting apart.)
+double* inc_out(jg_nr* h) { return h->keep_inc || h->eng.single_bwd ? h->d_inc : nullptr; }
+// The shared-factor step's scratch (d_cw) is read by its own backward rows only: under the conditions of the sweep-only factor the rows nobody names stay unstored
+// (JG_SWEEP_DEAD=0: stored; read at every capture)
+bool comp_dead_ok(jg_nr* h) { return h->eng.sweep_only && !h->refine && jg::knob("SWEEP_DEAD", 1) != 0; }
 
 jg::GroupSel active_groups(jg_nr* h) { return jg::GroupSel{nullptr, h->d_glist, h->d_cflags + jg::CF_LIST}; }
 
@@ -785,7 +796,7 @@ void launch_check(jg_nr* h, int mode, const int* group = nullptr) {
 void launch_compact(jg_nr* h, int restore, bool report = false) {
     std::vector<jg::LaneRows> rows{{h->d_vm, h->n, 1}, {h->d_va, h->n, 1}, {h->d_p, h->n, 1}, {h->d_q, h->n, 1}};
     if (h->mp > 0) { rows.push_back({h->d_pdg, h->mp, 1}); rows.push_back({h->d_pdb, h->mp, 1}); }
-    rows.push_back({h->d_inc, h->n, 2});           // a finished scenario keeps ITS last increment (method.increment) wherever its lane goes
+    if (h->keep_inc) rows.push_back({h->d_inc, h->n, 2});   // a finished scenario keeps ITS last increment (method.increment) wherever its lane goes; not kept: nothing to carry
     if (h->lt_on) rows.push_back({(double*)h->d_lt, (h->n + 31) / 32, 1});      // the types of a scenario travel with it (8th and last slot)
     h->cmp.launch_compact(h->stream, restore, report, rows);
 }
@@ -795,8 +806,9 @@ int newton_step(jg_nr* h, const jg::GroupSel& sel, const int* active) {
     if (int rc = h->eng.factor(h->stream, nullptr, h->d_F, sel, h->level0_done)) return rc;
     if (!h->refine) {
         jg::StateUpdate upd{h->d_va, h->d_vm, h->lt_on ? h->d_flags_all : h->d_flags, active, -1.0};
-        return h->eng.backsolve(h->stream, h->d_inc, upd, sel);
+        return h->eng.backsolve(h->stream, inc_out(h), upd, sel);
     }
+    // (a refining handle keeps its increment: jg_nr_set_refine switches jg_nr_set_keep_increment back on -- k_refine_apply writes d_inc)
     // the plain solve goes to a scratch vector: method.increment (d_inc) is written for ACTIVE scenarios only, by k_refine_apply -- a
     // finished scenario of an active lane group keeps its last increment, as without refinement
     jg::StateUpdate none{};
@@ -917,7 +929,7 @@ int build_comp_graphs(jg_nr* h) {
                            h->d_F, h->eng.status, h->d_active, h->ld, h->batch};
         if (h->mp > 0) jg::launch_comp_fix(fa, h->stream);
         jg::StateUpdate upd{h->d_va, h->d_vm, h->d_flags, h->d_active, -1.0};
-        if (int rc = cb.solve(cb.split, h->stream, h->d_F, h->d_cw, h->d_inc, h->ld, h->batch, upd, active_groups(h))) return fail(rc, "the shared-factor sweep could not be captured");
+        if (int rc = cb.solve(cb.split, h->stream, h->d_F, h->d_cw, inc_out(h), h->ld, h->batch, upd, active_groups(h), comp_dead_ok(h))) return fail(rc, "the shared-factor sweep could not be captured");
         launch_assemble(h, active_groups(h), true, nullptr, 0, nullptr, true);
         launch_check(h, 1, h->d_group);
         launch_compact(h, 0, true);
@@ -1411,6 +1423,7 @@ int jg_nr_solve(jg_nr* h) {
     h->f_stale = false;                                          // method.mismatch = the mismatch this step started from, for every scenario
     NR_HIP(hipMemsetAsync(h->eng.status, 0, (size_t)h->ld * 4, h->stream));
     if (int rc = newton_step(h, jg::GroupSel{}, nullptr)) return fail(rc, h->eng.error);
+    if (h->keep_inc) h->inc_fresh = true;
     h->add_iter(h->d_iters);
     NR_HIP(hipGetLastError());
     NR_HIP(hipStreamSynchronize(h->stream));
@@ -1424,6 +1437,7 @@ int jg_nr_solve(jg_nr* h) {
 int jg_nr_set_refine(jg_nr* h, int mode) {
     if (!h || mode < 0 || mode > 1) return fail(1, "jg_nr_set_refine: bad argument");
     if (h->fast) return fail(1, "jg_nr_set_refine: fast Newton-Raphson solves with constant matrices");
+    if (mode && !h->keep_inc && h->paused) return fail(1, "jg_nr_set_refine: the handle is paused (jg_nr_run_defer) and keeps no increment (jg_nr_set_keep_increment); finish it first");
     if (mode && h->lt_on) return fail(1, "jg_nr_set_refine: scenarios have bus types of their own (jg_nr_set_bus_type / jg_nr_reactive_limit); the refinement residual reads the create-time types");
     if (int rc = set_device(h)) return rc;
     NR_HIP(hipStreamSynchronize(h->stream));
@@ -1433,9 +1447,27 @@ int jg_nr_set_refine(jg_nr* h, int mode) {
     if ((mode != 0) != h->refine) {                              // the iteration graph is captured for one mode
         drop_iteration_graphs(h);
     }
+    if (mode && !h->keep_inc) {                                  // k_refine_apply writes method.increment: a refining handle keeps it
+        if (int rc = jg_nr_set_keep_increment(h, 1)) return rc;
+    }
     h->refine = mode != 0;
     // a refined step runs forward() + backsolve() on the factor of the step: plain rows (Engine::jordan); back on when refinement goes off
     h->eng.jordan = !h->refine && h->eng.plan->S.jordan && jg::knob("JORDAN", 1) != 0;
+    return 0;
+}
+
+int jg_nr_set_keep_increment(jg_nr* h, int mode) {
+    if (!h || mode < 0 || mode > 1) return fail(1, "jg_nr_set_keep_increment: bad argument");
+    if (mode == 0 && h->refine) return fail(1, "jg_nr_set_keep_increment: iterative refinement (jg_nr_set_refine) writes the increment; switch it off first");
+    if (h->paused) return fail(1, "jg_nr_set_keep_increment: the handle is paused (jg_nr_run_defer); finish it first");
+    if ((mode != 0) == h->keep_inc) return 0;
+    if (int rc = set_device(h)) return rc;
+    NR_HIP(hipStreamSynchronize(h->stream));
+    drop_iteration_graphs(h);                                    // the sweeps' `out` and the row set of the lane moves are captured
+    drop_comp_graphs(h);
+    if (mode) NR_HIP(jg::sync_fill(h->d_inc, 0, (size_t)h->n * 2 * h->ld * 8, h->stream));   // as a new handle's: nothing a run before the switch left
+    h->keep_inc = mode != 0;
+    h->inc_fresh = false;                                        // until the next run (jg_nr_get_increment never returns an older run's values)
     return 0;
 }
 
@@ -1458,6 +1490,7 @@ namespace {
 // ~90 us on the host's side of every solve, 7 % of a single instance's.
 int run_setup(jg_nr* h, int64_t max_iter, double tol, int lanes, bool keep_iters, int defer_at = 0) {
     if (int rc = build_graphs(h)) return rc;
+    if (h->keep_inc) h->inc_fresh = true;
     h->cmp.run_setup(h->stream, tol, (double)max_iter, (double)defer_at, lanes, keep_iters);      // defer_at: see jg::CompactArgs
     NR_HIP(hipGetLastError());
     h->res_pinned = h->ld == 64;
@@ -1859,6 +1892,8 @@ int jg_nr_get_mismatch(jg_nr* h, double* mism) {
 int jg_nr_get_increment(jg_nr* h, double* incr) {
     if (!h || !incr) return fail(1, "jg_nr_get_increment: bad argument");
     if (h->lt_on) return fail(1, "jg_nr_get_increment: scenarios have bus types of their own; the reference layout depends on the types");
+    if (!h->keep_inc) return fail(1, "jg_nr_get_increment: this handle keeps no bus-order increment (jg_nr_set_keep_increment(h, 0)); switch it on and run again");
+    if (!h->inc_fresh) return fail(1, "jg_nr_get_increment: jg_nr_set_keep_increment was switched on after the last run; the increment is there after the next one");
     if (int rc = set_device(h)) return rc;
     NR_HIP(hipStreamSynchronize(h->stream));
     return get_scattered(h, h->d_inc, incr);
@@ -2375,10 +2410,10 @@ int jg_nr_time_kernel(jg_nr* h, int kernel, int reps, double* mean_ms) {
                 jg::CompFixArgs fa{h->d_ppos, h->d_pdg, h->d_pdb, h->mp, cb.rowptr, cb.colm, cb.posrow, cb.rowtype, cb.v0, cb.th0, cb.y0, cb.Zc,
                                    h->d_F, h->eng.status, nullptr, h->ld, h->batch};
                 if (h->mp > 0) jg::launch_comp_fix(fa, h->stream);
-                if (int rc = cb.solve(cb.split, h->stream, h->d_F, h->d_cw, h->d_inc, h->ld, h->batch, none, jg::GroupSel{})) return fail(rc, "shared-factor sweep failed");
+                if (int rc = cb.solve(cb.split, h->stream, h->d_F, h->d_cw, inc_out(h), h->ld, h->batch, none, jg::GroupSel{}, comp_dead_ok(h))) return fail(rc, "shared-factor sweep failed");
             }
             else if (kernel == 5) launch_assemble(h, jg::GroupSel{}, false);      // the mismatch-only pass of a compensated start
-            else { if (int rc = h->eng.backsolve(h->stream, h->d_inc, none, jg::GroupSel{})) return fail(rc, h->eng.error); }
+            else { if (int rc = h->eng.backsolve(h->stream, inc_out(h), none, jg::GroupSel{})) return fail(rc, h->eng.error); }   // (the sweep as the handle's iterations run it)
         }
         NR_HIP(hipEventRecord(e1, h->stream));
     }

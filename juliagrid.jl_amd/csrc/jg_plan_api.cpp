@@ -41,6 +41,7 @@ void jg_plan_destroy(jg_plan* p) { delete p; }
 //        workgroup, terms-as-lanes form granted, most terms / rows of a level}, t_row (x4), t_ptr (x2), t_term, t_level, b_wg (x2), b_row (x6), b_term (x2), 98 - 100 t_jb (x2), t_cslot, t_toff
 //        101 per entry: 1 = stored by a top task and read by nothing of the factorisation and the Jordan sweep (jg_symbolic.hpp: top_dead), 102 {one flag may skip them all,
 //        16-byte units per scenario and factorisation it keeps from being stored, ... of those the tasks store without it}
+//        103 per pivot: 1 = nothing the Jordan sweep walks reads the row's pivot-order solution back (jg_symbolic.hpp: bwd_dead), 104 {the plan qualifies, such rows}
 // out == NULL returns the length.
 int64_t jg_plan_export(jg_plan* p, int which, int32_t* out, int64_t cap) {
     if (!p) return -1;
@@ -94,6 +95,8 @@ int64_t jg_plan_export(jg_plan* p, int which, int32_t* out, int64_t cap) {
         }
         case 101: tmp.assign(S.top_dead.begin(), S.top_dead.end()); v = &tmp; break;
         case 102: tmp = {S.top_dead_ok, (int)(S.top_dead_blocks & 0x7fffffff), (int)(S.top_store_blocks & 0x7fffffff)}; v = &tmp; break;
+        case 103: tmp.assign(S.bwd_dead.begin(), S.bwd_dead.end()); v = &tmp; break;
+        case 104: tmp = {S.bwd_dead_ok, S.bwd_dead_rows}; v = &tmp; break;
         case 75: tmp.assign(S.pre_pivot.begin(), S.pre_pivot.end()); v = &tmp; break;
         case 76: tmp.assign((const int*)S.pre_seg.data(), (const int*)S.pre_seg.data() + S.pre_seg.size() * 8); v = &tmp; break;
         case 77: tmp.assign((const int*)S.pre_rec.data(), (const int*)S.pre_rec.data() + S.pre_rec.size() * 16); v = &tmp; break;
@@ -106,9 +109,10 @@ int64_t jg_plan_export(jg_plan* p, int which, int32_t* out, int64_t cap) {
 }
 
 // Tables of the shared-factor solve (jg_symbolic.hpp: CompTables) for a dense top of at most top_cap pivots (< 0: none).
-// which: 0 {n_top, split level, forward levels, backward levels}, 1 top pivots, 2 / 3 forward segments (x8) / records (x16), 4 / 5 backward segments / records.
+// which: 0 {n_top, split level, forward levels, backward levels}, 1 top pivots, 2 / 3 forward segments (x8) / records (x16), 4 / 5 backward segments / records,
+// 6 per pivot: 1 = no backward record reads the row of the scratch (CompTables::dead), 7 {such rows, of them in the top}.
 int64_t jg_plan_comp_export(jg_plan* p, int64_t top_cap, int which, int32_t* out, int64_t cap) {
-    if (!p || which < 0 || which > 5) return -1;
+    if (!p || which < 0 || which > 7) return -1;
     jg::CompTables T;
     jg::build_comp_tables(p->S, (int)top_cap, T);
     std::vector<int> tmp;
@@ -118,6 +122,8 @@ int64_t jg_plan_comp_export(jg_plan* p, int64_t top_cap, int which, int32_t* out
         case 2: tmp.assign((const int*)T.fwd_seg.data(), (const int*)T.fwd_seg.data() + T.fwd_seg.size() * 8); break;
         case 3: tmp.assign((const int*)T.fwd_rec.data(), (const int*)T.fwd_rec.data() + T.fwd_rec.size() * 16); break;
         case 4: tmp.assign((const int*)T.bwd_seg.data(), (const int*)T.bwd_seg.data() + T.bwd_seg.size() * 8); break;
+        case 6: tmp.assign(T.dead.begin(), T.dead.end()); break;
+        case 7: tmp = {T.n_dead, T.n_dead_top}; break;
         default: tmp.assign((const int*)T.bwd_rec.data(), (const int*)T.bwd_rec.data() + T.bwd_rec.size() * 16); break;
     }
     if (!out) return (int64_t)tmp.size();

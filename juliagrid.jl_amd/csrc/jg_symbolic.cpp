@@ -20,7 +20,7 @@ namespace jg {
 
 int knob(const char* name, int unset) {
     static const char* const known[] = {"TRACE", "PLAN_CACHE", "POLL", "PLAN_THREADS", "PLAN_TIMING", "HOST_TIMING",
-                                        "TOP_PW", "TOP_FUSE", "TOP_SYM", "JORDAN", "CHAIN_SMALL", "NO_PREFACTOR", "LANES_INPLACE", "TOP_LEVEL", "ROW_TASKS", "ORDER_CHECK", "TOP_PROFILE", "SINGLE", "SWEEP_ONLY"};
+                                        "TOP_PW", "TOP_FUSE", "TOP_SYM", "JORDAN", "CHAIN_SMALL", "NO_PREFACTOR", "LANES_INPLACE", "TOP_LEVEL", "ROW_TASKS", "ORDER_CHECK", "TOP_PROFILE", "SINGLE", "SWEEP_ONLY", "SWEEP_DEAD"};
     bool ok = false;
     for (const char* k : known) ok = ok || std::strcmp(k, name) == 0;
     if (!ok) return unset;
@@ -1200,6 +1200,14 @@ void build_comp_tables(const BlockSymbolic& S, int top_cap, CompTables& out) {
             }
         }, NoExtra(), 0, 8);
     }
+    // rows of W no backward record reads (jg_symbolic.hpp: CompTables::dead)
+    out.dead.assign((size_t)n, 1);
+    for (const Rec& r : out.bwd_rec) {
+        if (r.w[0] < 0) continue;
+        for (int t = 0; t < r.w[3] && t < COMP_T; ++t) out.dead[r.w[5 + 2 * t]] = 0;
+    }
+    out.n_dead = out.n_dead_top = 0;
+    for (int r = 0; r < n; ++r) if (out.dead[r]) { out.n_dead++; if (tpos[r] >= 0) out.n_dead_top++; }
 }
 
 // Tables of the single-instance backward sweep (jg_symbolic.hpp: SingleTables).
@@ -1548,6 +1556,7 @@ int analyze(int n, const int* rowptr, const int* col, long long policy64, BlockS
     if (S.n_entries + S.n_jordan >= (1 << 24)) S.fact_tasks = 0;   // a task term packs (entry | slot << 24)
     build_tables(S);
     mark_sweep_dead(S);
+    mark_bwd_dead(S);
     lap("replay tables");
     return 0;
 }
@@ -1627,6 +1636,37 @@ void mark_sweep_dead(BlockSymbolic& S) {
     for (int en = 0; en < S.n_entries; ++en) if (S.top_dead[en]) S.top_dead_blocks++;
     S.top_store_blocks = half + 2 * cand;
     S.top_dead_blocks *= 2;                                          // both counts in half blocks (16 bytes per scenario)
+}
+
+// Which rows of the pivot-order solution does the Jordan sweep never read back (jg_symbolic.hpp: bwd_dead)?  Every row is a candidate; a row that anything the
+// sweep walks names as an x_c operand is struck: the terms of the level records, the external columns of the chain tasks and the columns of their in-chain blocks.
+void mark_bwd_dead(BlockSymbolic& S) {
+    S.bwd_dead.assign((size_t)S.n, 0);
+    S.bwd_dead_ok = 0; S.bwd_dead_rows = 0;
+    if (!S.jordan || S.symmetric || S.top_task.empty()) return;      // (as mark_sweep_dead: what Engine::sweep_only runs on)
+    std::vector<char> named((size_t)S.n, 0);
+    for (const Segment& sg : S.bwdj_seg) {
+        if (sg.wpi <= 0) {
+            for (int x = 0; x < sg.nchunks; ++x) {
+                const Rec& r = S.bwdj_rec[(size_t)sg.rec_base + x];
+                const int nb = r.w[0], nE = r.w[1];
+                const int* d = S.bwd_chain.data() + r.w[2];
+                for (int q = 0; q < nE; ++q) named[d[3 * nb + q]] = 1;
+                const int* uin = d + 3 * nb + nE + nb * nE;
+                for (int p = 0; p < nb; ++p)
+                    for (int c = 0; c < nb; ++c) if (uin[p * nb + c] >= 0) named[d[3 * c]] = 1;
+            }
+            continue;
+        }
+        const size_t nrec = (size_t)sg.nchunks * 16 * sg.rpw;
+        for (size_t x = 0; x < nrec; ++x) {
+            const Rec& r = S.bwdj_rec[(size_t)sg.rec_base + x];
+            if (r.w[0] < 0) continue;
+            for (int t = 0; t < r.w[3] && t < BWD_T; ++t) named[r.w[5 + 2 * t]] = 1;
+        }
+    }
+    S.bwd_dead_ok = 1;
+    for (int k = 0; k < S.n; ++k) if (!named[k]) { S.bwd_dead[k] = 1; S.bwd_dead_rows++; }
 }
 
 }  // namespace jg

@@ -21,7 +21,7 @@ namespace jg {
 // handles), JG_POLL=0 (the host always blocks in the stream synchronise), JG_PLAN_THREADS (host threads of the table builder), JG_PLAN_TIMING, JG_HOST_TIMING
 // (timings on stderr).  The rest are TEST HOOKS that force a code path the library also takes by itself, so that the suites can hold the variants against each
 // other (tests/test_top_variants_gpu.py, tests/test_plan_cpu.py): JG_TOP_PW, JG_TOP_FUSE, JG_TOP_SYM, JG_JORDAN, JG_CHAIN_SMALL, JG_NO_PREFACTOR, JG_LANES_INPLACE,
-// JG_TOP_LEVEL, JG_ROW_TASKS, JG_ORDER_CHECK, JG_TOP_PROFILE, JG_SINGLE, JG_SWEEP_ONLY.  Nothing else is read: the switches of retired experiments left with their kernels
+// JG_TOP_LEVEL, JG_ROW_TASKS, JG_ORDER_CHECK, JG_TOP_PROFILE, JG_SINGLE, JG_SWEEP_ONLY, JG_SWEEP_DEAD.  Nothing else is read: the switches of retired experiments left with their kernels
 // (tools/experiments/*.patch).
 int knob(const char* name, int unset);      // integer value of the environment variable JG_<name>; `unset` when it is not set (or not in the lists above)
 inline bool knob_set(const char* name) { return knob(name, -2147483647) != -2147483647; }
@@ -214,7 +214,16 @@ struct BlockSymbolic {
     int top_dead_ok = 0;
     long long top_dead_blocks = 0;      // blocks per scenario and factorisation the flag keeps from being stored ...
     long long top_store_blocks = 0;     // ... of the blocks the tasks store without it (entries, Jordan rows, update matrices; a 2-vector counts half: the sum is in HALF blocks)
+    // Pivot-order stores nobody reads back (mark_bwd_dead; same plans as top_dead).  The Jordan sweep stores x_k into W for later rows to read as x_c.  bwd_dead[k] = 1:
+    // nothing the sweep walks names row k as an operand -- no term of a level record, no external column of a chain task, no in-chain block of either chain-task
+    // form -- so with no other consumer of the whole pivot-order solution (Engine::backsolve grants it) the store of x_k may be skipped.  The engine marks such a row
+    // in its DEVICE copy of the tables: bit BWD_DEAD_BIT of the row's diagonal-entry word (w2 of a BwdRec, the third word of a chain row), which the kernels mask.
+    std::vector<char> bwd_dead;         // [n]
+    int bwd_dead_ok = 0;                // the plan qualifies (Jordan rows, not symmetric, top tasks)
+    int bwd_dead_rows = 0;
 };
+constexpr int BWD_DEAD_BIT = 30;
+constexpr int BWD_ENTRY_MASK = 0x3fffffff;
 
 // ---- shared-factor solve (compensation, jg_comp.hip): tables of x = A^-1 r for MANY right-hand sides on ONE numeric factor ----------
 // When every scenario of a batch starts from one state (an N-1 screen from the base-case solution: the reference's user loop
@@ -237,6 +246,9 @@ struct CompTables {
     std::vector<Segment> fwd_seg, bwd_seg;
     std::vector<Rec> fwd_rec, bwd_rec;
     int n_fwd_levels = 0, n_bwd_levels = 0;
+    std::vector<char> dead;             // [n] 1 = no backward record names the row of W as an operand (bottom rows and the rows the dense top hands down alike): its
+                                        // pivot-order store may be skipped (device copies: bit BWD_DEAD_BIT of w2 of a backward record / of a top pivot, CompBase::create)
+    int n_dead = 0, n_dead_top = 0;     // ... how many, and how many of them in the top
 };
 // top_cap: at most this many pivots in the dense top (the split is the lowest forward level that satisfies it); < 0: none.
 void build_comp_tables(const BlockSymbolic& S, int top_cap, CompTables& out);
@@ -303,6 +315,7 @@ void build_single_tables(const BlockSymbolic& S, SingleTables& out);
 int analyze(int n, const int* rowptr, const int* col, long long policy, BlockSymbolic& out);
 // Replay tables of the selected inverse of a SYMMETRIC matrix on the factor pattern (see jg_symbolic.cpp); idempotent.
 void build_selected_inverse(BlockSymbolic& S);
+void mark_bwd_dead(BlockSymbolic& S);          // bwd_dead, bwd_dead_ok, bwd_dead_rows (called by analyze)
 void mark_sweep_dead(BlockSymbolic& S);        // top_dead, top_dead_ok and the two counts (called by analyze)
 // entry id of block (r, c) in pivot numbering, -1 if outside the factor pattern
 int entry_of(const BlockSymbolic& S, int r, int c);
