@@ -2016,6 +2016,62 @@ function criticalTimeKernel(b::DcStateEstimationBatch, reps::Int = 20)
     check(ccall((:jg_dcse_critical_time_kernel, lib), Cint, (Int64, Cint, Ptr{Float64}), b.token, reps, ms))
     return ms
 end
+"""
+    topologyCandidates!(b::DcStateEstimationBatch, branch, ptr, row, sign)
+
+The candidate branches of the status tests and their meter columns m_k (jgrid.h: jg_dcse_topology_set): `branch` 1-based, `ptr` 0-based offsets
+[count + 1], `row` 1-based rows of the set ascending in a column, `sign` +-1 (+1 from-end wattmeters of k and injection wattmeters on from(k), -1 the
+to-end side).  Rows out of service are masked by the library.
+"""
+function topologyCandidates!(b::DcStateEstimationBatch, branch::Vector{Int64}, ptr::Vector{Int64}, row::Vector{Int64}, sign::Vector{Int32})
+    check(ccall((:jg_dcse_topology_set, lib), Cint, (Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int32}),
+                b.token, length(branch), branch, ptr, row, sign))
+    return length(branch)
+end
+"the denominators D_k, the norms m_k' W m_k and the status (0 testable, 1 critical branch, 2 unseen) of the `count` candidates, and how often they were formed"
+function topologyDenominators(b::DcStateEstimationBatch, count::Int64)
+    D = zeros(Float64, count)
+    norm = zeros(Float64, count)
+    status = zeros(Int32, count)
+    runs = zeros(Int64, 1)
+    check(ccall((:jg_dcse_topology_denominators, lib), Cint, (Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int64}), b.token, D, norm, status, runs))
+    return (denominator = D, norm = norm, status = status, runs = runs[1])
+end
+"""
+    topologyScreen(b::DcStateEstimationBatch; threshold = 3.0, capacity = 65536, dense = 0)
+
+The status test of every candidate in every lane of a solved batch whose lanes removed nothing (jgrid.h: jg_dcse_topology_screen): `records` [4, k] =
+(lane, candidate, t, phi) sorted by (lane, candidate) with the exact `total`, per lane the `best` candidate (0: none is testable) with its `statistic`
+and `flowError`, the `count` at or above the threshold, and with `dense` = the number of candidates every statistic [lane, candidate].
+"""
+function topologyScreen(b::DcStateEstimationBatch; threshold::Float64 = 3.0, capacity::Int64 = 65536, dense::Int64 = 0)
+    lanes = b.batch
+    records = zeros(Float64, 4, max(capacity, 1))
+    totals = zeros(Int64, 2)
+    best = zeros(Int32, lanes)
+    statistic = zeros(Float64, lanes)
+    flowError = zeros(Float64, lanes)
+    count = zeros(Int32, lanes)
+    all = zeros(Float64, lanes, dense)
+    check(ccall((:jg_dcse_topology_screen, lib), Cint,
+                (Int64, Float64, Int64, Ptr{Float64}, Ptr{Int64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}),
+                b.token, threshold, capacity, records, totals, best, statistic, flowError, count, dense > 0 ? pointer(all) : Ptr{Float64}(C_NULL)))
+    kept = min(totals[1], capacity)
+    return (records = records[:, 1:kept], total = totals[1], lanesWithRecords = totals[2], best = best, statistic = statistic, flowError = flowError,
+            count = count, statisticAll = all)
+end
+"the angles [bus, lane] of the lanes corrected for `candidate[lane]` (0: the lane's estimate as it is); the batch's own estimate is left untouched"
+function topologyCorrect(b::DcStateEstimationBatch, candidate::Vector{Int32})
+    angle = zeros(Float64, size(b.angle, 1), b.batch)
+    check(ccall((:jg_dcse_topology_correct, lib), Cint, (Int64, Ptr{Int32}, Ptr{Float64}), b.token, candidate, angle))
+    return angle
+end
+"milliseconds of `reps` runs (HIP events): 0 all denominators, 1 right-hand sides, 2 sweep pair, 3 denominator kernel, 4 statistic pass, 5 correction"
+function topologyTimeKernel(b::DcStateEstimationBatch, kernel::Int, reps::Int = 20)
+    ms = zeros(Float64, reps)
+    check(ccall((:jg_dcse_topology_time, lib), Cint, (Int64, Cint, Cint, Ptr{Float64}), b.token, kernel, reps, ms))
+    return ms
+end
 
 # ---- Gauss-Seidel power flow, one scenario per lane (jgrid.h: jg_gs_*; csrc/jg_gs.hip) ---------------------------------------------------
 # gaussSeidel / mismatch! / solve! / powerFlow! (src/powerFlow/acPowerFlow.jl:563-619, 732-764, 985-1041, 1389-1433) for `batch` scenarios of one grid: a
@@ -2182,7 +2238,7 @@ export HIP, HIPOrthogonal, NewtonRaphsonBatch, BaseCase, baseInfo, baseInverseOn
        largestNormalizedResidual, normalizedResiduals, commUniqueId, Comm, shard, contingencyAnalysis, clearPlanCache,
        deviceCount, dims, setRefinement!, deviceMaps, setOutage!, snapshotVoltage!, restoreVoltage!, iterations, voltageDevice!, packResults!, packRows!,
        allgatherDevice, commRank, commWorld, timeKernel, setBusType!, busType, GaussNewtonBatch, setRealisations!, monteCarloEstimation, fastPatch!, setReadings!, drawNoise!, measurementDevice,
-       DcPowerFlowBatch, setInjections!, setOutagePairs!, pairScreenBuild!, pairScreen, pairTimeKernel, pairScreenRelease!, pairScreenIslandMode!, pairScreenShed, seriesScreenIslandMode!, seriesScreenShed, transferScreenIslandMode!, transferScreenShed, generatorScreenBuild!, generatorScreen, generatorScreenFlows, generatorTimeKernel, generatorScreenRelease!, generatorScreenIslandMode!, generatorScreenShed, groupScreenBuild!, groupScreenDims, groupScreenCandidates, groupScreenBase, groupScreen, groupTimeKernel, groupScreenRelease!, cascadeScreenBuild!, cascadeScreen, cascadeScreenDims, cascadeScreenCandidates, cascadeScreenBase, cascadeTimeKernel, cascadeScreenRelease!, seriesScreenBuild!, seriesScreen, seriesTimeKernel, seriesScreenRelease!, setIslandMode!, islands, islandTable, fromPower, angleDevice, DcStateEstimationBatch, removedRows, removeRows!, criticalScreen, criticalTimeKernel,
+       DcPowerFlowBatch, setInjections!, setOutagePairs!, pairScreenBuild!, pairScreen, pairTimeKernel, pairScreenRelease!, pairScreenIslandMode!, pairScreenShed, seriesScreenIslandMode!, seriesScreenShed, transferScreenIslandMode!, transferScreenShed, generatorScreenBuild!, generatorScreen, generatorScreenFlows, generatorTimeKernel, generatorScreenRelease!, generatorScreenIslandMode!, generatorScreenShed, groupScreenBuild!, groupScreenDims, groupScreenCandidates, groupScreenBase, groupScreen, groupTimeKernel, groupScreenRelease!, cascadeScreenBuild!, cascadeScreen, cascadeScreenDims, cascadeScreenCandidates, cascadeScreenBase, cascadeTimeKernel, cascadeScreenRelease!, seriesScreenBuild!, seriesScreen, seriesTimeKernel, seriesScreenRelease!, setIslandMode!, islands, islandTable, fromPower, angleDevice, DcStateEstimationBatch, removedRows, removeRows!, criticalScreen, criticalTimeKernel, topologyCandidates!, topologyDenominators, topologyScreen, topologyCorrect, topologyTimeKernel,
        GaussSeidelBatch, lastMismatch, setBusVoltage!, refreshGenerator!
 
 end # module

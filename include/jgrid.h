@@ -926,6 +926,36 @@ int jg_dcse_critical_screen(int64_t h, double correlation, int64_t capacity, dou
                             double* partner_gamma);
 int jg_dcse_critical_time_kernel(int64_t h, int reps, double* ms);
 int jg_dcse_get_variance(int64_t h, double* omega);
+/* Branch status tests of the handle's measurement set (topology errors; csrc/jg_dcse_topology.hpp), on the same factor.  The hypothesis for branch k adds
+ * ONE unknown phi to the model, z = c + H theta + m_k phi + e: the flow k really carries from -> to minus the flow the model gives it; m_k is +1 on the
+ * from-end wattmeters of k and the injection wattmeters on from(k), -1 on the to-end wattmeters and the injection wattmeters on to(k).  With r the
+ * residuals of the full set's estimate: D_k = m_k' W m_k - (H' W m_k)' G^-1 (H' W m_k), c_kl = m_k' W r_l, phi^_kl = c_kl / D_k, t_kl = c_kl / sqrt(D_k)
+ * (N(0, 1) under "no error"; t^2 is the drop of the objective when phi is freed).  Candidates are numbered 1 .. count in the order of the call.
+ *   jg_dcse_topology_set           the candidates: branch [count] (1-based, for messages), ptr [count + 1] (0-based offsets), row [] (1-based rows of the
+ *                                  set, ascending in a column) and sign [] (+-1).  Rows out of service on the handle are masked by the library, so a
+ *                                  changed status needs no new call.  Forgets the denominators (unless the candidates are the ones the handle holds), as
+ *                                  every refactorisation does.
+ *   jg_dcse_topology_denominators  D [count], norm [count] = m_k' W m_k, status [count] (0 testable: D > 1e-6 norm; 1 critical branch: a status error on it
+ *                                  leaves no residual; 2 unseen: no meter in service sees it), formed per block of 512 candidates by one sweep pair if the
+ *                                  candidates or the factor are new and kept on the handle; runs: how often they were formed.  Every pointer may be NULL; with `runs` alone nothing is formed.
+ *   jg_dcse_topology_screen        needs a solved handle whose lanes removed nothing (code 1 otherwise).  records [capacity][4]: the first
+ *                                  min(total, capacity) records (lane, candidate, t, phi^) with |t| >= threshold, 1-based, sorted by (lane, candidate);
+ *                                  totals [2] = {records, lanes with at least one}, exact whatever the capacity; lane_best [batch] the candidate of the
+ *                                  largest |t| (the lowest on ties; 0: none is testable), lane_t, lane_phi [batch] (NaN there), lane_count [batch];
+ *                                  dense_t [count][batch] every statistic (NaN where the status is not 0).  records (capacity 0) and everything after
+ *                                  totals may be NULL.
+ *   jg_dcse_topology_correct       angle [batch][n]: the estimate of lane l corrected for candidate[l], theta' = theta^ - G^-1 H' W m_k phi^_kl, the WLS
+ *                                  estimate of the augmented problem; candidate <= 0 or not testable: the lane's estimate bit for bit as
+ *                                  jg_dcse_get_angle gives it.  The handle's estimate is left as it is.
+ *   jg_dcse_topology_time          milliseconds (HIP events) of `reps` runs of: 0 all denominators, 1 the right-hand sides, 2 the sweep pair, 3 the
+ *                                  denominator kernel (1-3: the first block of 512 candidates), 4 the screen's statistic pass, 5 the correction
+ */
+int jg_dcse_topology_set(int64_t h, int64_t count, const int64_t* branch, const int64_t* ptr, const int64_t* row, const int32_t* sign);
+int jg_dcse_topology_denominators(int64_t h, double* D, double* norm, int32_t* status, int64_t* runs);
+int jg_dcse_topology_screen(int64_t h, double threshold, int64_t capacity, double* records, int64_t* totals, int32_t* lane_best, double* lane_t,
+                            double* lane_phi, int32_t* lane_count, double* dense_t);
+int jg_dcse_topology_correct(int64_t h, const int32_t* candidate, double* angle);
+int jg_dcse_topology_time(int64_t h, int kernel, int reps, double* ms);
 
 /* ---------------------------------------------------------------------------------------------
  * Gauss-Seidel AC power flow, one scenario per lane (csrc/jg_gs.hip).  The handle is an int64 token, as for jg_dc_*.

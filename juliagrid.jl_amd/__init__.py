@@ -10,6 +10,7 @@ from .dcgroup import dcGroupScreen, parallelGroups, DC_GROUP_MAX          # noqa
 from .dcchance import dcChanceScreen, injectionFactors, DC_CHANCE_MAX          # noqa: F401
 from .dccascade import dcCascadeScreen, DC_CASCADE_MAX, DC_CASCADE_TRUNCATED          # noqa: F401
 from .dccritical import dcCriticalScreen          # noqa: F401
+from .dctopology import dcTopologyScreen, topologyRuns          # noqa: F401
 from .system import addBranch_ as addBranchSystem_, dropZeros_ as dropZerosSystem_   # noqa: F401
 from .system import (updateBranch_ as updateBranchSystem_, updateBus_ as updateBusSystem_,   # noqa: F401
                      updateGenerator_ as updateGeneratorSystem_)
@@ -27,7 +28,7 @@ from .stateestimation import (WlsMethod, Normal, LU, KLU, QR, LDLt, LL, Orthogon
 from .dcstateestimation import DcStateEstimation, dcStateEstimation, setReadings_, removed, removeMeasurement_          # noqa: F401
 from .montecarlo import MonteCarloPipeline, gatherEstimates, gatherEstimatesDevice, unpackEstimates   # noqa: F401
 from .synthetic import pegaseShaped, case9241synth                          # noqa: F401
-from . import powerflow, stateestimation, dcpowerflow, dcgenerator, dcgroup, dcchance, dccascade, dccritical, dcstateestimation, gaussseidel   # noqa: F401
+from . import powerflow, stateestimation, dcpowerflow, dcgenerator, dcgroup, dcchance, dccascade, dccritical, dctopology, dcstateestimation, gaussseidel   # noqa: F401
 from . import _lib                                                           # noqa: F401
 
 __all__ = [
@@ -45,4 +46,5 @@ __all__ = [
     "dcChanceScreen", "injectionFactors", "DC_CHANCE_MAX",
     "dcCascadeScreen", "DC_CASCADE_MAX", "DC_CASCADE_TRUNCATED",
     "dcCriticalScreen",
+    "dcTopologyScreen", "topologyRuns",
 ]

@@ -223,6 +223,11 @@ def lib():
         "jg_dcse_critical_screen": [C.c_int64, C.c_double, C.c_int64, F64P, I64P, I32P, I32P, F64P],
         "jg_dcse_critical_time_kernel": [C.c_int64, C.c_int, F64P],
         "jg_dcse_get_variance": [C.c_int64, F64P],
+        "jg_dcse_topology_set": [C.c_int64, C.c_int64, I64P, I64P, I64P, I32P],
+        "jg_dcse_topology_denominators": [C.c_int64, VP, VP, VP, VP],
+        "jg_dcse_topology_screen": [C.c_int64, C.c_double, C.c_int64, F64P, I64P, I32P, F64P, F64P, I32P, VP],
+        "jg_dcse_topology_correct": [C.c_int64, I32P, F64P],
+        "jg_dcse_topology_time": [C.c_int64, C.c_int, C.c_int, F64P],
         # Gauss-Seidel power flow: an int64 token too
         "jg_gs_create": [C.POINTER(C.c_int64), C.c_int64, I64P, I64P, F64P, I8P, C.c_int64, F64P, C.c_int64, C.c_int],
         "jg_gs_set_ybus": [C.c_int64, F64P],

@@ -61,6 +61,12 @@ struct DcseHandle : DcDevice {
     int* b_from = nullptr; int* b_to = nullptr; double* b_y = nullptr; double* b_shift = nullptr; int* o_none = nullptr;
     double* flows = nullptr; double* fpart = nullptr; int n_fchunks = 0;
     bool solved = false, have_z = false;
+    // branch status tests (jg_dcse_topology.hpp): the candidates' meter columns, their denominators cached per factor like omega
+    int t_count = 0; std::vector<long long> h_tbranch; std::vector<int> h_tstat; std::vector<double> h_tD, h_tnorm, h_tsgn; std::vector<int> h_tptr, h_trow;
+    int* t_ptr = nullptr; int* t_row = nullptr; double* t_sgn = nullptr;        // [count + 1], [entries], [entries] +-1
+    double* t_D = nullptr; double* t_norm = nullptr; int* t_stat = nullptr;     // [count]
+    bool topo_valid = false; long long topo_factor = -1, topo_runs = 0;         // the value of `refactorisations` the cache belongs to
+    double* XT = nullptr;                                                       // [n][ld] the corrected angles: never X0 / TH
 };
 
 // jg_dcse.hip, for jg_dcse_critical.hip: the Omega diagonal of the full set into h->omega (omega_valid), and k_dcse_row_rhs on the handle's stream --
