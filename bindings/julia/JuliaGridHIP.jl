@@ -2073,6 +2073,84 @@ function topologyTimeKernel(b::DcStateEstimationBatch, kernel::Int, reps::Int = 
     return ms
 end
 
+# ---- batched DC optimal power flow: ADMM on one shared factor (jgrid.h: jg_dcopf_*; csrc/jg_dcopf.hip) -------------------------------------------
+# The QP level of dcOptimalPowerFlow / solve! (src/optimalPowerFlow/dcOptimalPowerFlow.jl:44-198, 298-370): min 1/2 x'Px + q'x, l <= Ax <= u with P (its
+# diagonal), q and A (CSR, 0-based rowptr, 1-based ascending columns) shared by `batch` lanes and the bounds each lane's own.  The model rows of a
+# PowerSystem are stated by the Python package (dcoptimalpowerflow.modelRows); per-lane arrays are [rows or variables, lane].
+mutable struct DcOptimalPowerFlowBatch
+    token::Int64
+    variables::Int64
+    rows::Int64
+    batch::Int64
+end
+function dcOptimalPowerFlowBatch(P::Vector{Float64}, q::Vector{Float64}, rowptr::Vector{Int64}, col::Vector{Int64}, val::Vector{Float64}, equality::Vector{Int32};
+                                 batch::Int64 = 1, rho::Float64 = 0.1, sigma::Float64 = 1e-6, alpha::Float64 = 1.6, device::Int64 = 0)
+    token = Ref{Int64}(0)
+    check(ccall((:jg_dcopf_create, lib), Cint,
+                (Ref{Int64}, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int32}, Int64, Float64, Float64, Float64, Cint),
+                token, length(P), length(equality), P, q, rowptr, col, val, equality, batch, rho, sigma, alpha, device))
+    b = DcOptimalPowerFlowBatch(token[], length(P), length(equality), batch)
+    finalizer(x -> (x.token != 0 && ccall((:jg_dcopf_destroy, lib), Cvoid, (Int64,), x.token); x.token = 0), b)
+    return b
+end
+"no device: K = P + sigma I + A' rho A dense from the library's term lists, the objective's scale, the rows' scales"
+function opfHostModel(P::Vector{Float64}, q::Vector{Float64}, rowptr::Vector{Int64}, col::Vector{Int64}, val::Vector{Float64}, equality::Vector{Int32},
+                      rho::Float64, sigma::Float64)
+    n, m = length(P), length(equality)
+    K = zeros(Float64, n, n)
+    scale = zeros(Float64, 1)
+    E = zeros(Float64, m)
+    check(ccall((:jg_dcopf_host_model, lib), Cint,
+                (Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int32}, Float64, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                n, m, P, q, rowptr, col, val, equality, rho, sigma, K, scale, E))
+    return K, scale[1], E
+end
+"{variables, rows, batch, ld, entries of K, factor entries, factorisation levels, refactorisations, 1 if K is singular but for sigma}"
+function dims(b::DcOptimalPowerFlowBatch)
+    d = zeros(Int64, 9)
+    check(ccall((:jg_dcopf_dims, lib), Cint, (Int64, Ptr{Int64}), b.token, d))
+    return d
+end
+function opfRho(b::DcOptimalPowerFlowBatch)
+    r = zeros(Float64, 1)
+    check(ccall((:jg_dcopf_get_rho, lib), Cint, (Int64, Ptr{Float64}), b.token, r))
+    return r[1]
+end
+"l, u [rows, lane]; a bound at or beyond 1e20 (or infinite) is none"
+function setBounds!(b::DcOptimalPowerFlowBatch, l::Matrix{Float64}, u::Matrix{Float64})
+    size(l) == size(u) == (b.rows, b.batch) || throw(DimensionMismatch("bounds are [rows, lane]"))
+    check(ccall((:jg_dcopf_set_bounds, lib), Cint, (Int64, Ptr{Float64}, Ptr{Float64}), b.token, l, u))
+end
+"warm start: x [variables, lane], y [rows, lane] as `opfSolution` returns them"
+function setStart!(b::DcOptimalPowerFlowBatch, x::Matrix{Float64}, y::Matrix{Float64})
+    size(x) == (b.variables, b.batch) && size(y) == (b.rows, b.batch) || throw(DimensionMismatch("x is [variables, lane], y [rows, lane]"))
+    check(ccall((:jg_dcopf_set_start, lib), Cint, (Int64, Ptr{Float64}, Ptr{Float64}), b.token, x, y))
+end
+"iterations and status per lane (0 solved, 2 primal infeasible, 5 iteration limit, 3 singular), the refactorisations so far"
+function JuliaGrid.solve!(b::DcOptimalPowerFlowBatch; tolerance::Float64 = 1e-9, iteration::Int64 = 100000, check_every::Int64 = 25, adapt_every::Int64 = 200)
+    iterations = zeros(Int32, b.batch)
+    status = zeros(Int32, b.batch)
+    refactorisations = zeros(Int64, 1)
+    check(ccall((:jg_dcopf_run, lib), Cint, (Int64, Float64, Int64, Int64, Int64, Ptr{Int32}, Ptr{Int32}, Ptr{Int64}),
+                b.token, tolerance, iteration, check_every, adapt_every, iterations, status, refactorisations))
+    return (iterations = iterations, status = status, refactorisations = refactorisations[1])
+end
+"x [variables, lane], y, z [rows, lane] and the objective [lane] of the unscaled problem"
+function opfSolution(b::DcOptimalPowerFlowBatch)
+    x = zeros(Float64, b.variables, b.batch)
+    y = zeros(Float64, b.rows, b.batch)
+    z = zeros(Float64, b.rows, b.batch)
+    objective = zeros(Float64, b.batch)
+    check(ccall((:jg_dcopf_get, lib), Cint, (Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), b.token, x, y, z, objective))
+    return (x = x, y = y, z = z, objective = objective)
+end
+"milliseconds of `reps` runs (HIP events): 0 one iteration, 1 right-hand side, 2 sweep pair, 3 projection step, 4 residual pass and verdict, 5 assembly and refactorisation"
+function opfTimeKernel(b::DcOptimalPowerFlowBatch, kernel::Int, reps::Int = 20)
+    ms = zeros(Float64, reps)
+    check(ccall((:jg_dcopf_time, lib), Cint, (Int64, Cint, Cint, Ptr{Float64}), b.token, kernel, reps, ms))
+    return ms
+end
+
 # ---- Gauss-Seidel power flow, one scenario per lane (jgrid.h: jg_gs_*; csrc/jg_gs.hip) ---------------------------------------------------
 # gaussSeidel / mismatch! / solve! / powerFlow! (src/powerFlow/acPowerFlow.jl:563-619, 732-764, 985-1041, 1389-1433) for `batch` scenarios of one grid: a
 # sweep is sequential over the buses of a scenario, so a lane runs the reference's update sequence unchanged and a powerFlow! is ONE launch.  The C
@@ -2238,7 +2316,7 @@ export HIP, HIPOrthogonal, NewtonRaphsonBatch, BaseCase, baseInfo, baseInverseOn
        largestNormalizedResidual, normalizedResiduals, commUniqueId, Comm, shard, contingencyAnalysis, clearPlanCache,
        deviceCount, dims, setRefinement!, deviceMaps, setOutage!, snapshotVoltage!, restoreVoltage!, iterations, voltageDevice!, packResults!, packRows!,
        allgatherDevice, commRank, commWorld, timeKernel, setBusType!, busType, GaussNewtonBatch, setRealisations!, monteCarloEstimation, fastPatch!, setReadings!, drawNoise!, measurementDevice,
-       DcPowerFlowBatch, setInjections!, setOutagePairs!, pairScreenBuild!, pairScreen, pairTimeKernel, pairScreenRelease!, pairScreenIslandMode!, pairScreenShed, seriesScreenIslandMode!, seriesScreenShed, transferScreenIslandMode!, transferScreenShed, generatorScreenBuild!, generatorScreen, generatorScreenFlows, generatorTimeKernel, generatorScreenRelease!, generatorScreenIslandMode!, generatorScreenShed, groupScreenBuild!, groupScreenDims, groupScreenCandidates, groupScreenBase, groupScreen, groupTimeKernel, groupScreenRelease!, cascadeScreenBuild!, cascadeScreen, cascadeScreenDims, cascadeScreenCandidates, cascadeScreenBase, cascadeTimeKernel, cascadeScreenRelease!, seriesScreenBuild!, seriesScreen, seriesTimeKernel, seriesScreenRelease!, setIslandMode!, islands, islandTable, fromPower, angleDevice, DcStateEstimationBatch, removedRows, removeRows!, criticalScreen, criticalTimeKernel, topologyCandidates!, topologyDenominators, topologyScreen, topologyCorrect, topologyTimeKernel,
+       DcPowerFlowBatch, setInjections!, setOutagePairs!, pairScreenBuild!, pairScreen, pairTimeKernel, pairScreenRelease!, pairScreenIslandMode!, pairScreenShed, seriesScreenIslandMode!, seriesScreenShed, transferScreenIslandMode!, transferScreenShed, generatorScreenBuild!, generatorScreen, generatorScreenFlows, generatorTimeKernel, generatorScreenRelease!, generatorScreenIslandMode!, generatorScreenShed, groupScreenBuild!, groupScreenDims, groupScreenCandidates, groupScreenBase, groupScreen, groupTimeKernel, groupScreenRelease!, cascadeScreenBuild!, cascadeScreen, cascadeScreenDims, cascadeScreenCandidates, cascadeScreenBase, cascadeTimeKernel, cascadeScreenRelease!, seriesScreenBuild!, seriesScreen, seriesTimeKernel, seriesScreenRelease!, setIslandMode!, islands, islandTable, fromPower, angleDevice, DcStateEstimationBatch, removedRows, removeRows!, criticalScreen, criticalTimeKernel, topologyCandidates!, topologyDenominators, topologyScreen, topologyCorrect, topologyTimeKernel, DcOptimalPowerFlowBatch, dcOptimalPowerFlowBatch, opfHostModel, opfRho, setBounds!, setStart!, opfSolution, opfTimeKernel,
        GaussSeidelBatch, lastMismatch, setBusVoltage!, refreshGenerator!
 
 end # module

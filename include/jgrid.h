@@ -1006,6 +1006,42 @@ int jg_gs_get_mismatch(int64_t h, double* stop_p, double* stop_q);
 int jg_gs_time_kernel(int64_t h, int kernel, int64_t sweeps, int reps, double* ms);
 
 /* ---------------------------------------------------------------------------------------------
+ * Batched DC optimal power flow: ADMM (OSQP's reduced form) on one shared factor (csrc/jg_dcopf.hip).  The handle is an int64 token.
+ *
+ * Every lane solves  min 1/2 x' P x + q' x  subject to  l <= A x <= u  with P (its diagonal), q and A shared and l, u its own.  Indices are 1-based;
+ * per-lane arrays are [batch][rows or variables].  A bound at or beyond +-1e20 (or infinite) is none.
+ *
+ *   jg_dcopf_create      P [n] >= 0, q [n], A [m][n] as CSR (columns of a row ascending), equality [m] 1 on rows that are equalities in every lane (they
+ *                        get 1e3 rho); rho, sigma, alpha: the step sizes and the relaxation.  The objective is scaled by 1 / max(|P|, |q|), the rows
+ *                        of A to unit 2-norm; K = P + sigma I + A' rho A is analysed, assembled from its term lists and factorised once.
+ *   jg_dcopf_host_model  no device: the same host set-up -> K [n][n] dense from the term lists at (rho, sigma), the objective's scale, the rows' scales [m]
+ *   jg_dcopf_dims        n, m, batch, ld, entries of K, entries of the factor, factorisation levels, refactorisations, 1 if K is singular but for sigma
+ *   jg_dcopf_set_bounds  l, u [batch][m]
+ *   jg_dcopf_set_start   x [batch][n], y [batch][m] as jg_dcopf_get returns them; z = A x.  Without it a handle starts at 0 and a later run goes on
+ *                        from where the last one ended
+ *   jg_dcopf_run         iterates until every lane is solved (both residuals of the scaled problem <= tolerance + tolerance x their norms), shown
+ *                        primal infeasible, or at max_iteration; the residuals are formed every `check` iterations, rho follows the unfinished
+ *                        lanes' median residual ratio at multiples of adapt_every (0: never; a multiple of check) -> iterations, status [batch]:
+ *                        0 solved, 2 primal infeasible, 5 iteration limit, 3 K singular; the count of numeric refactorisations so far
+ *   jg_dcopf_get         x [batch][n], y, z [batch][m] and the objective [batch] of the unscaled problem (each may be NULL)
+ *   jg_dcopf_time        milliseconds (HIP events) of `reps` runs of: 0 one iteration, 1 the right-hand side, 2 the sweep pair, 3 the projection step,
+ *                        4 the residual pass and verdict, 5 assembly of K and refactorisation; ms [reps].  The iterates move on as they do in the calls timed
+ * ------------------------------------------------------------------------------------------- */
+int jg_dcopf_create(int64_t* h, int64_t n, int64_t m, const double* P, const double* q, const int64_t* rowptr, const int64_t* col, const double* val,
+                    const int32_t* equality, int64_t batch, double rho, double sigma, double alpha, int device);
+void jg_dcopf_destroy(int64_t h);
+int jg_dcopf_host_model(int64_t n, int64_t m, const double* P, const double* q, const int64_t* rowptr, const int64_t* col, const double* val,
+                        const int32_t* equality, double rho, double sigma, double* K, double* cscale, double* E);
+int jg_dcopf_dims(int64_t h, int64_t* dims);
+int jg_dcopf_get_rho(int64_t h, double* rho);
+int jg_dcopf_set_bounds(int64_t h, const double* l, const double* u);
+int jg_dcopf_set_start(int64_t h, const double* x, const double* y);
+int jg_dcopf_run(int64_t h, double tolerance, int64_t max_iteration, int64_t check, int64_t adapt_every, int32_t* iterations, int32_t* status,
+                 int64_t* refactorisations);
+int jg_dcopf_get(int64_t h, double* x, double* y, double* z, double* objective);
+int jg_dcopf_time(int64_t h, int kernel, int reps, double* ms);
+
+/* ---------------------------------------------------------------------------------------------
  * Symbolic analysis only (no device needed): the static schedule that replaces the symbolic half
  * of `lu`/`klu` (src/backend/utility.jl:470-476, 486-492).  Used by the CPU test-suite to replay
  * and race-check the schedule.  pattern: 0-based int32 block CSR, structurally symmetric, full

@@ -242,6 +242,16 @@ def lib():
         "jg_gs_run": [C.c_int64, C.c_int64, C.c_double, I32P, I32P],
         "jg_gs_get_mismatch": [C.c_int64, F64P, F64P],
         "jg_gs_time_kernel": [C.c_int64, C.c_int, C.c_int64, C.c_int, F64P],
+        # DC optimal power flow: an int64 token too
+        "jg_dcopf_create": [C.POINTER(C.c_int64), C.c_int64, C.c_int64, F64P, F64P, I64P, I64P, F64P, I32P, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_int],
+        "jg_dcopf_host_model": [C.c_int64, C.c_int64, F64P, F64P, I64P, I64P, F64P, I32P, C.c_double, C.c_double, F64P, F64P, F64P],
+        "jg_dcopf_dims": [C.c_int64, I64P],
+        "jg_dcopf_get_rho": [C.c_int64, F64P],
+        "jg_dcopf_set_bounds": [C.c_int64, F64P, F64P],
+        "jg_dcopf_set_start": [C.c_int64, F64P, F64P],
+        "jg_dcopf_run": [C.c_int64, C.c_double, C.c_int64, C.c_int64, C.c_int64, I32P, I32P, I64P],
+        "jg_dcopf_get": [C.c_int64, VP, VP, VP, VP],
+        "jg_dcopf_time": [C.c_int64, C.c_int, C.c_int, F64P],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -259,6 +269,8 @@ def lib():
     L.jg_dcse_destroy.restype = None
     L.jg_gs_destroy.argtypes = [C.c_int64]
     L.jg_gs_destroy.restype = None
+    L.jg_dcopf_destroy.argtypes = [C.c_int64]
+    L.jg_dcopf_destroy.restype = None
     L.jg_plan_cache_clear.argtypes = []
     L.jg_plan_cache_clear.restype = None
     L.jg_comm_destroy.argtypes = [VP]

@@ -57,6 +57,9 @@ class PowerSystem:
             number=nb,
             layout=NS(from_=t["br_from"].astype(np.int64), to=t["br_to"].astype(np.int64),
                       status=t["br_status"].astype(np.int8)),
+            # optimal power flow: long-term rating as the from-bus active flow limit (load.jl:495-501); absent = none
+            flow=NS(minFromBus=-_field(t, "br_rating", nb, 0.0), maxFromBus=_field(t, "br_rating", nb, 0.0)),
+            voltage=NS(minDiffAngle=_field(t, "br_angmin", nb, -2 * np.pi), maxDiffAngle=_field(t, "br_angmax", nb, 2 * np.pi)),
             parameter=NS(resistance=t["br_r"].astype(np.float64), reactance=t["br_x"].astype(np.float64),
                          conductance=t["br_g"].astype(np.float64), susceptance=t["br_b"].astype(np.float64),
                          turnsRatio=t["br_tap"].astype(np.float64), shiftAngle=t["br_shift"].astype(np.float64)),
@@ -68,7 +71,9 @@ class PowerSystem:
             voltage=NS(magnitude=t["gen_vg"].astype(np.float64)),
             # maxActive: the table's gen_pmax, else addGenerator!'s default, 5 x the output (generator.jl:40-44)
             capability=NS(minReactive=t.get("gen_qmin", np.zeros(ng)), maxReactive=t.get("gen_qmax", np.zeros(ng)),
+                          minActive=_field(t, "gen_pmin", ng, -np.inf),
                           maxActive=np.asarray(t["gen_pmax"], dtype=np.float64).copy() if "gen_pmax" in t else 5.0 * t["gen_pg"].astype(np.float64)),
+            cost=NS(active=_cost_from_tables(t, ng)),
         )
         # bus.supply = sum of in-service generator outputs, generator lists in index order
         # (load.jl:271-277, 589-596)
@@ -88,6 +93,40 @@ class PowerSystem:
     def copy(self) -> "PowerSystem":
         import copy as _copy
         return _copy.deepcopy(self)
+
+
+def _field(t, name, count, default):
+    return np.asarray(t[name], dtype=np.float64).copy() if name in t else np.full(count, float(default))
+
+
+def _cost_from_tables(t, ng):
+    """cost.active of the reference (definition/system.jl: model 1 piecewise [points, 2], model 2 polynomial, highest degree first; keys are
+    1-based generator indices) from the flat tables gen_cost_model [ng], gen_cost_ptr [ng + 1], gen_cost_data; absent = no cost (model 0)."""
+    cost = NS(model=np.zeros(ng, dtype=np.int8), polynomial={}, piecewise={})
+    if "gen_cost_model" not in t:
+        return cost
+    cost.model = np.asarray(t["gen_cost_model"]).astype(np.int8).copy()
+    ptr = np.asarray(t["gen_cost_ptr"]).astype(np.int64)
+    data = np.asarray(t["gen_cost_data"], dtype=np.float64)
+    for k in range(ng):
+        d = data[ptr[k]:ptr[k + 1]].copy()
+        if cost.model[k] == 1:
+            cost.piecewise[k + 1] = d.reshape(-1, 2)
+        elif cost.model[k] == 2:
+            cost.polynomial[k + 1] = d
+    return cost
+
+
+def costTables(system) -> dict:
+    """The flat cost tables of a system (what powerSystem(dict | npz) reads back)."""
+    c = system.generator.cost.active
+    ptr, data = [0], []
+    for k in range(system.generator.number):
+        d = c.piecewise[k + 1].reshape(-1) if c.model[k] == 1 else c.polynomial[k + 1] if c.model[k] == 2 else np.zeros(0)
+        data.append(np.asarray(d, dtype=np.float64))
+        ptr.append(ptr[-1] + data[-1].size)
+    return dict(gen_cost_model=c.model.copy(), gen_cost_ptr=np.array(ptr, dtype=np.int64),
+                gen_cost_data=np.concatenate(data) if data else np.zeros(0))
 
 
 class CscMatrix:
@@ -136,6 +175,8 @@ def _matpower_tables(path: str) -> dict:
 
     def matrix(name):
         m = re.search(r"mpc\." + name + r"\s*=\s*\[(.*?)\];", text, re.S)
+        if m is None:
+            return []
         rows = []
         for line in m.group(1).splitlines():
             line = line.split("%")[0].strip().rstrip(";").strip()
@@ -150,7 +191,27 @@ def _matpower_tables(path: str) -> dict:
     col = lambda rows, j: np.array([r[j] for r in rows], dtype=np.float64)
     tap = col(br, 8)
     tap[tap == 0.0] = 1.0
+    opf = {}
+    if all(len(r) >= 10 for r in gen):
+        opf["gen_pmin"] = col(gen, 9) * binv
+    if all(len(r) >= 13 for r in br):                 # the optimal power flow columns (load.jl:495-501)
+        opf.update(br_rating=col(br, 5) * binv, br_angmin=col(br, 11) * d2r, br_angmax=col(br, 12) * d2r)
+    cost = matrix("gencost")[:len(gen)]
+    if len(cost) == len(gen):                         # costParser (load.jl:622-658): outputs in per unit, polynomial coefficients x base^degree
+        model, ptr, data = [], [0], []
+        for r in cost:
+            kind, npt = int(r[0]), int(r[3])
+            model.append(kind)
+            if kind == 1:
+                pts = np.array(r[4:4 + 2 * npt], dtype=np.float64).reshape(-1, 2)
+                pts[:, 0] *= binv
+                data.append(pts.reshape(-1))
+            else:
+                data.append(np.array([r[4 + k] * base ** (npt - 1 - k) for k in range(npt)], dtype=np.float64))
+            ptr.append(ptr[-1] + data[-1].size)
+        opf.update(gen_cost_model=np.array(model, dtype=np.int8), gen_cost_ptr=np.array(ptr, dtype=np.int64), gen_cost_data=np.concatenate(data))
     return dict(
+        **opf,
         base_power=base * 1e6, bus_label=np.array([int(r[0]) for r in bus]),
         bus_type=col(bus, 1).astype(np.int8), bus_pd=col(bus, 2) * binv, bus_qd=col(bus, 3) * binv,
         bus_gs=col(bus, 4) * binv, bus_bs=col(bus, 5) * binv, bus_vm=col(bus, 7), bus_va=col(bus, 8) * d2r,
@@ -415,7 +476,7 @@ def dropZeros_(system: PowerSystem) -> None:
 
 
 def updateBranch_(system: PowerSystem, label: int, status: int | None = None, resistance=None, reactance=None,
-                  conductance=None, susceptance=None, turnsRatio=None, shiftAngle=None) -> None:
+                  conductance=None, susceptance=None, turnsRatio=None, shiftAngle=None, rating=None, minDiffAngle=None, maxDiffAngle=None) -> None:
     """updateBranch!(system; label, status, resistance, reactance, conductance, susceptance, turnsRatio, shiftAngle)
     (branch.jl:313-431).
 
@@ -424,6 +485,12 @@ def updateBranch_(system: PowerSystem, label: int, status: int | None = None, re
     k = int(label) - 1
     if not 0 <= k < system.branch.number:
         raise KeyError(f"The branch label {label} that has been specified does not exist.")
+    if rating is not None:                                          # the optimal power flow's limits: no part of the nodal matrices
+        system.branch.flow.minFromBus[k], system.branch.flow.maxFromBus[k] = -float(rating), float(rating)
+    if minDiffAngle is not None:
+        system.branch.voltage.minDiffAngle[k] = float(minDiffAngle)
+    if maxDiffAngle is not None:
+        system.branch.voltage.maxDiffAngle[k] = float(maxDiffAngle)
     old = int(system.branch.layout.status[k])
     new = old if status is None else int(status)
     if new not in (0, 1):
@@ -502,13 +569,17 @@ def updateBus_(system: PowerSystem, label: int, type=None, active=None, reactive
 
 
 def updateGenerator_(system: PowerSystem, label: int, status: int | None = None, active=None, reactive=None,
-                     magnitude=None) -> None:
+                     magnitude=None, minActive=None, maxActive=None) -> None:
     """updateGenerator!(system; label, status, active, reactive, magnitude) (generator.jl:262-360): the bus supply and
     the per-bus generator lists follow the status and the outputs."""
     k = int(label) - 1
     gen, bus = system.generator, system.bus
     if not 0 <= k < gen.number:
         raise KeyError(f"The generator label {label} that has been specified does not exist.")
+    if minActive is not None:
+        gen.capability.minActive[k] = float(minActive)
+    if maxActive is not None:
+        gen.capability.maxActive[k] = float(maxActive)
     old = int(gen.layout.status[k])
     new = old if status is None else int(status)
     if new not in (0, 1):
@@ -538,3 +609,25 @@ def updateGenerator_(system: PowerSystem, label: int, status: int | None = None,
     gen.layout.status[k] = new
     if magnitude is not None:
         gen.voltage.magnitude[k] = float(magnitude)
+
+
+def cost_(system: PowerSystem, generator: int, polynomial=None, piecewise=None) -> None:
+    """cost!(system; generator, active, polynomial | piecewise) (generator.jl): the active cost of one generator, in the reference's stored
+    units -- polynomial coefficients highest degree first in currency / (per-unit power)^degree, piecewise points [[output in per unit, cost], ...]."""
+    k = int(generator) - 1
+    if not 0 <= k < system.generator.number:
+        raise KeyError(f"The generator label {generator} that has been specified does not exist.")
+    if (polynomial is None) == (piecewise is None):
+        raise ValueError("cost_: give either polynomial or piecewise")
+    c = system.generator.cost.active
+    c.polynomial.pop(k + 1, None)
+    c.piecewise.pop(k + 1, None)
+    if polynomial is not None:
+        c.polynomial[k + 1] = np.asarray(polynomial, dtype=np.float64).reshape(-1).copy()
+        c.model[k] = 2
+    else:
+        pts = np.asarray(piecewise, dtype=np.float64)
+        if pts.ndim != 2 or pts.shape[1] != 2 or pts.shape[0] < 2:
+            raise ValueError("cost_: piecewise needs at least two [output, cost] points")
+        c.piecewise[k + 1] = pts.copy()
+        c.model[k] = 1
