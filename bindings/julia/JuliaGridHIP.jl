@@ -2144,7 +2144,20 @@ function opfSolution(b::DcOptimalPowerFlowBatch)
     check(ccall((:jg_dcopf_get, lib), Cint, (Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), b.token, x, y, z, objective))
     return (x = x, y = y, z = z, objective = objective)
 end
-"milliseconds of `reps` runs (HIP events): 0 one iteration, 1 right-hand side, 2 sweep pair, 3 projection step, 4 residual pass and verdict, 5 assembly and refactorisation"
+"one branch out per lane on the shared factor: the variables of its buses, their balance rows (1-based), its admittance, state 0 none / 1 outage / 3 bridge
+(the lane is not run: status 3); the caller frees the branch's own rows through the bounds.  `clearBranchOutages!` clears the set"
+function setBranchOutages!(b::DcOptimalPowerFlowBatch, fromVariable::Vector{Int64}, toVariable::Vector{Int64}, fromRow::Vector{Int64}, toRow::Vector{Int64},
+                           admittance::Vector{Float64}, state::Vector{Int32})
+    all(length(v) == b.batch for v in (fromVariable, toVariable, fromRow, toRow, admittance, state)) || throw(DimensionMismatch("one entry per lane"))
+    check(ccall((:jg_dcopf_set_branch_outages, lib), Cint, (Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int32}),
+                b.token, fromVariable, toVariable, fromRow, toRow, admittance, state))
+end
+function clearBranchOutages!(b::DcOptimalPowerFlowBatch)
+    check(ccall((:jg_dcopf_set_branch_outages, lib), Cint, (Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int32}),
+                b.token, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL))
+end
+"milliseconds of `reps` runs (HIP events): 0 one iteration, 1 right-hand side, 2 sweep pair, 3 projection step, 4 residual pass and verdict, 5 assembly and
+refactorisation, 6 the outaged lanes' correction, 7 the build of their W (6, 7: with a set of outages)"
 function opfTimeKernel(b::DcOptimalPowerFlowBatch, kernel::Int, reps::Int = 20)
     ms = zeros(Float64, reps)
     check(ccall((:jg_dcopf_time, lib), Cint, (Int64, Cint, Cint, Ptr{Float64}), b.token, kernel, reps, ms))
@@ -2316,7 +2329,7 @@ export HIP, HIPOrthogonal, NewtonRaphsonBatch, BaseCase, baseInfo, baseInverseOn
        largestNormalizedResidual, normalizedResiduals, commUniqueId, Comm, shard, contingencyAnalysis, clearPlanCache,
        deviceCount, dims, setRefinement!, deviceMaps, setOutage!, snapshotVoltage!, restoreVoltage!, iterations, voltageDevice!, packResults!, packRows!,
        allgatherDevice, commRank, commWorld, timeKernel, setBusType!, busType, GaussNewtonBatch, setRealisations!, monteCarloEstimation, fastPatch!, setReadings!, drawNoise!, measurementDevice,
-       DcPowerFlowBatch, setInjections!, setOutagePairs!, pairScreenBuild!, pairScreen, pairTimeKernel, pairScreenRelease!, pairScreenIslandMode!, pairScreenShed, seriesScreenIslandMode!, seriesScreenShed, transferScreenIslandMode!, transferScreenShed, generatorScreenBuild!, generatorScreen, generatorScreenFlows, generatorTimeKernel, generatorScreenRelease!, generatorScreenIslandMode!, generatorScreenShed, groupScreenBuild!, groupScreenDims, groupScreenCandidates, groupScreenBase, groupScreen, groupTimeKernel, groupScreenRelease!, cascadeScreenBuild!, cascadeScreen, cascadeScreenDims, cascadeScreenCandidates, cascadeScreenBase, cascadeTimeKernel, cascadeScreenRelease!, seriesScreenBuild!, seriesScreen, seriesTimeKernel, seriesScreenRelease!, setIslandMode!, islands, islandTable, fromPower, angleDevice, DcStateEstimationBatch, removedRows, removeRows!, criticalScreen, criticalTimeKernel, topologyCandidates!, topologyDenominators, topologyScreen, topologyCorrect, topologyTimeKernel, DcOptimalPowerFlowBatch, dcOptimalPowerFlowBatch, opfHostModel, opfRho, setBounds!, setStart!, opfSolution, opfTimeKernel,
+       DcPowerFlowBatch, setInjections!, setOutagePairs!, pairScreenBuild!, pairScreen, pairTimeKernel, pairScreenRelease!, pairScreenIslandMode!, pairScreenShed, seriesScreenIslandMode!, seriesScreenShed, transferScreenIslandMode!, transferScreenShed, generatorScreenBuild!, generatorScreen, generatorScreenFlows, generatorTimeKernel, generatorScreenRelease!, generatorScreenIslandMode!, generatorScreenShed, groupScreenBuild!, groupScreenDims, groupScreenCandidates, groupScreenBase, groupScreen, groupTimeKernel, groupScreenRelease!, cascadeScreenBuild!, cascadeScreen, cascadeScreenDims, cascadeScreenCandidates, cascadeScreenBase, cascadeTimeKernel, cascadeScreenRelease!, seriesScreenBuild!, seriesScreen, seriesTimeKernel, seriesScreenRelease!, setIslandMode!, islands, islandTable, fromPower, angleDevice, DcStateEstimationBatch, removedRows, removeRows!, criticalScreen, criticalTimeKernel, topologyCandidates!, topologyDenominators, topologyScreen, topologyCorrect, topologyTimeKernel, DcOptimalPowerFlowBatch, dcOptimalPowerFlowBatch, opfHostModel, opfRho, setBounds!, setStart!, opfSolution, setBranchOutages!, clearBranchOutages!, opfTimeKernel,
        GaussSeidelBatch, lastMismatch, setBusVoltage!, refreshGenerator!
 
 end # module

@@ -1025,7 +1025,15 @@ int jg_gs_time_kernel(int64_t h, int kernel, int64_t sweeps, int reps, double* m
  *                        0 solved, 2 primal infeasible, 5 iteration limit, 3 K singular; the count of numeric refactorisations so far
  *   jg_dcopf_get         x [batch][n], y, z [batch][m] and the objective [batch] of the unscaled problem (each may be NULL)
  *   jg_dcopf_time        milliseconds (HIP events) of `reps` runs of: 0 one iteration, 1 the right-hand side, 2 the sweep pair, 3 the projection step,
- *                        4 the residual pass and verdict, 5 assembly of K and refactorisation; ms [reps].  The iterates move on as they do in the calls timed
+ *                        4 the residual pass and verdict, 5 assembly of K and refactorisation, 6 the outaged lanes' correction of the solve, 7 the build
+ *                        of their W = K^-1 [a d] and 2 x 2 inverses (6, 7: with a set of outages); ms [reps].  The iterates move on as they do in the
+ *                        calls timed
+ *   jg_dcopf_set_branch_outages  one branch out per lane, without a factorisation of its own: from_variable, to_variable [batch] the variables of the
+ *                        branch's buses f, t; from_row, to_row [batch] their balance rows r_f, r_t (equality rows); admittance [batch] y_k as A holds it
+ *                        (unscaled: the library applies the rows' scales and rho); state [batch] 0 none, 1 outage, 3 the outage is a bridge (the
+ *                        lane is not run: status 3, NaN).  The lane's matrix is A + p d', p = -y_k (e_rf - e_rt), d = e_f - e_t, solved on the shared
+ *                        factor by a rank-2 correction; the caller frees the branch's own rows through their bounds.  A call replaces the set; state
+ *                        NULL clears it.  x, y, z stay (the warm start)
  * ------------------------------------------------------------------------------------------- */
 int jg_dcopf_create(int64_t* h, int64_t n, int64_t m, const double* P, const double* q, const int64_t* rowptr, const int64_t* col, const double* val,
                     const int32_t* equality, int64_t batch, double rho, double sigma, double alpha, int device);
@@ -1040,6 +1048,8 @@ int jg_dcopf_run(int64_t h, double tolerance, int64_t max_iteration, int64_t che
                  int64_t* refactorisations);
 int jg_dcopf_get(int64_t h, double* x, double* y, double* z, double* objective);
 int jg_dcopf_time(int64_t h, int kernel, int reps, double* ms);
+int jg_dcopf_set_branch_outages(int64_t h, const int64_t* from_variable, const int64_t* to_variable, const int64_t* from_row, const int64_t* to_row,
+                                const double* admittance, const int32_t* state);
 
 /* ---------------------------------------------------------------------------------------------
  * Symbolic analysis only (no device needed): the static schedule that replaces the symbolic half

@@ -26,7 +26,7 @@ from .stateestimation import (WlsMethod, Normal, LU, KLU, QR, LDLt, LL, Orthogon
                               stateEstimation_, setNoise_, drawNoise_, measurementDevice, residualTest_, normalizedResidual, chiTest,
                               updateVoltmeter_, updateAmmeter_, updateWattmeter_, updateVarmeter_, updatePmu_)
 from .dcstateestimation import DcStateEstimation, dcStateEstimation, setReadings_, removed, removeMeasurement_          # noqa: F401
-from .dcoptimalpowerflow import DcOptimalPowerFlow, dcOptimalPowerFlow, setCapability_          # noqa: F401
+from .dcoptimalpowerflow import DcOptimalPowerFlow, dcOptimalPowerFlow, setCapability_, setBranchOutages_, outageCosts          # noqa: F401
 from .system import cost_, costTables          # noqa: F401
 from .montecarlo import MonteCarloPipeline, gatherEstimates, gatherEstimatesDevice, unpackEstimates   # noqa: F401
 from .synthetic import pegaseShaped, case9241synth                          # noqa: F401
@@ -49,5 +49,5 @@ __all__ = [
     "dcCascadeScreen", "DC_CASCADE_MAX", "DC_CASCADE_TRUNCATED",
     "dcCriticalScreen",
     "dcTopologyScreen", "topologyRuns",
-    "DcOptimalPowerFlow", "dcOptimalPowerFlow", "setCapability_", "cost_", "costTables",
+    "DcOptimalPowerFlow", "dcOptimalPowerFlow", "setCapability_", "setBranchOutages_", "outageCosts", "cost_", "costTables",
 ]

@@ -252,6 +252,7 @@ def lib():
         "jg_dcopf_run": [C.c_int64, C.c_double, C.c_int64, C.c_int64, C.c_int64, I32P, I32P, I64P],
         "jg_dcopf_get": [C.c_int64, VP, VP, VP, VP],
         "jg_dcopf_time": [C.c_int64, C.c_int, C.c_int, F64P],
+        "jg_dcopf_set_branch_outages": [C.c_int64, VP, VP, VP, VP, VP, VP],
     }
     for name, args in sig.items():
         f = getattr(L, name)

@@ -110,12 +110,23 @@ __global__ void k_opf_gain(const int* g_ptr, const int* g_row, const double* g_p
     if (e < nnz) A[e] = gain_entry(g_ptr, g_row, g_prod, g_add, g_dg, rhov, sigma, e);
 }
 
+// ---- the lanes' branch outages: A_s = A + p d'.  The kernels below have a second instance (OUT) that a handle launches only while it holds an outage;
+// in it a lane adds the term of p d' where the wavefront's row is r_f or r_t, or its variable f or t.  These indices are the lane's own, not
+// wave-uniform: vector loads.  A lane without an outage carries -1 and takes no branch, so its arithmetic is the first instance's
+struct OpfOut { const int* var; const int* row; const double* p; };     // [2][ld] each
+// p' v on the lane's two balance rows, v [m][ld]
+__device__ __forceinline__ double opf_out_rows(const OpfOut& o, const double* v, size_t ld, size_t bl, int rf, int rt) {
+    return fma(o.p[bl], v[(size_t)rf * ld + bl], o.p[ld + bl] * v[(size_t)rt * ld + bl]);
+}
+
 // ---- b = sigma x - q + A' (rho o z - y): a wavefront = one variable x 64 lanes; `blend` first takes x+ = alpha x~ + (1 - alpha) x of the step before
 struct OpfRhsArgs {
     const int* c_ptr; const int* c_row; const double* c_val; const double* rhov; const double* q; const double* Z; const double* Y; const double* XT;
     double* X; double* B; const int* done; const int* groups;
     double sigma, alpha; int n, ld, blend, form;
+    OpfOut out;
 };
+template <bool OUT>
 __global__ __launch_bounds__(256) void k_opf_rhs(OpfRhsArgs a) {
     const int j = blockIdx.x * 4 + uniform(threadIdx.y);
     if (j >= a.n) return;
@@ -133,6 +144,15 @@ __global__ __launch_bounds__(256) void k_opf_rhs(OpfRhsArgs a) {
         const size_t r = (size_t)i * ld + bl;
         acc = fma(((CDbl)a.c_val)[p], fma(((CDbl)a.rhov)[i], a.Z[r], -a.Y[r]), acc);
     }
+    if (OUT) {                                                          // + d_j p' (rho o z - y)
+        const int f = a.out.var[bl], t = a.out.var[ld + bl];
+        if (j == f || j == t) {
+            const int rf = a.out.row[bl], rt = a.out.row[ld + bl];
+            const size_t qf = (size_t)rf * ld + bl, qt = (size_t)rt * ld + bl;
+            const double w = fma(a.out.p[bl], fma(a.rhov[rf], a.Z[qf], -a.Y[qf]), a.out.p[ld + bl] * fma(a.rhov[rt], a.Z[qt], -a.Y[qt]));
+            acc += j == f ? w : -w;
+        }
+    }
     a.B[at] = acc;
 }
 
@@ -141,7 +161,9 @@ struct OpfUpdateArgs {
     const int* r_ptr; const int* r_col; const double* r_val; const double* rhov; const double* rinv; const double* XT; const double* L; const double* U;
     double* Z; double* Y; double* DY; const int* done; const int* groups;
     double alpha; int m, ld, keep_dy;
+    OpfOut out;
 };
+template <bool OUT>
 __global__ __launch_bounds__(256) void k_opf_update(OpfUpdateArgs a) {
     const int i = blockIdx.x * 4 + uniform(threadIdx.y);
     if (i >= a.m) return;
@@ -149,6 +171,13 @@ __global__ __launch_bounds__(256) void k_opf_update(OpfUpdateArgs a) {
     const size_t ld = (size_t)a.ld, bl = (size_t)grp * 64 + threadIdx.x, at = (size_t)i * ld + bl;
     double zt = 0.0;
     for (int p = ((CInt)a.r_ptr)[i]; p < ((CInt)a.r_ptr)[i + 1]; ++p) zt = fma(((CDbl)a.r_val)[p], a.XT[(size_t)((CInt)a.r_col)[p] * ld + bl], zt);
+    if (OUT) {                                                          // + p_i (x~_f - x~_t)
+        const int rf = a.out.row[bl], rt = a.out.row[ld + bl];
+        if (i == rf || i == rt) {
+            const double dx = a.XT[(size_t)a.out.var[bl] * ld + bl] - a.XT[(size_t)a.out.var[ld + bl] * ld + bl];
+            zt = fma(a.out.p[(i == rf ? 0 : ld) + bl], dx, zt);
+        }
+    }
     const double rho = ((CDbl)a.rhov)[i], ri = ((CDbl)a.rinv)[i];
     const double z = a.Z[at], y = a.Y[at];
     const double zr = fma(a.alpha, zt, (1.0 - a.alpha) * z);
@@ -170,19 +199,34 @@ struct OpfResArgs {
     const int* ptr; const int* idx; const double* val;          // ROWS: A by rows; else A by columns
     const double* P; const double* q; const double* X; const double* Z; const double* Y; const double* DY; const double* L; const double* U;
     double* part; const int* groups; int count, ld;
+    OpfOut out;
 };
-template <bool ROWS>
+template <bool ROWS, bool OUT>
 __global__ __launch_bounds__(256) void k_opf_residual(OpfResArgs a) {
     const int chunk = blockIdx.x * 4 + uniform(threadIdx.y);
     const int k0 = chunk * OPF_CHUNK;
     if (k0 >= a.count) return;
     const int grp = ((CInt)a.groups)[blockIdx.y];
     const size_t ld = (size_t)a.ld, bl = (size_t)grp * 64 + threadIdx.x;
+    int of = -1, ot = -1, orf = -1, ort = -1;
+    double ow0 = 0.0, ow1 = 0.0;                                         // ROWS: x_f - x_t; else p' y and p' dy on the lane's two balance rows
+    if (OUT) {
+        of = a.out.var[bl]; ot = a.out.var[ld + bl]; orf = a.out.row[bl]; ort = a.out.row[ld + bl];
+        if (of >= 0) {
+            if (ROWS) ow0 = a.X[(size_t)of * ld + bl] - a.X[(size_t)ot * ld + bl];
+            else {
+                const size_t qf = (size_t)orf * ld + bl, qt = (size_t)ort * ld + bl;
+                ow0 = opf_out_rows(a.out, a.Y, ld, bl, orf, ort);
+                ow1 = fma(a.out.p[bl], opf_dy(a.DY[qf], a.L[qf], a.U[qf]), a.out.p[ld + bl] * opf_dy(a.DY[qt], a.L[qt], a.U[qt]));
+            }
+        }
+    }
     double r0 = 0.0, r1 = 0.0, r2 = 0.0, r3 = 0.0, r4 = 0.0;
     for (int k = k0; k < min(k0 + OPF_CHUNK, a.count); ++k) {
         if (ROWS) {                                                     // |A x - z|, |A x|, |z|, |dy|, u' dy+ + l' dy-
             double ax = 0.0;
             for (int p = ((CInt)a.ptr)[k]; p < ((CInt)a.ptr)[k + 1]; ++p) ax = fma(((CDbl)a.val)[p], a.X[(size_t)((CInt)a.idx)[p] * ld + bl], ax);
+            if (OUT && (k == orf || k == ort)) ax = fma(a.out.p[(k == orf ? 0 : ld) + bl], ow0, ax);
             const size_t at = (size_t)k * ld + bl;
             const double z = a.Z[at], l = a.L[at], u = a.U[at], dy = opf_dy(a.DY[at], l, u);
             r0 = fmax(r0, fabs(ax - z)); r1 = fmax(r1, fabs(ax)); r2 = fmax(r2, fabs(z)); r3 = fmax(r3, fabs(dy));
@@ -196,6 +240,7 @@ __global__ __launch_bounds__(256) void k_opf_residual(OpfResArgs a) {
                 aty = fma(v, a.Y[at], aty);
                 atd = fma(v, opf_dy(a.DY[at], a.L[at], a.U[at]), atd);
             }
+            if (OUT && (k == of || k == ot)) { aty += k == of ? ow0 : -ow0; atd += k == of ? ow1 : -ow1; }
             const double px = ((CDbl)a.P)[k] * a.X[(size_t)k * ld + bl];
             r0 = fmax(r0, fabs(px + ((CDbl)a.q)[k] + aty)); r1 = fmax(r1, fabs(px)); r2 = fmax(r2, fabs(aty)); r3 = fmax(r3, fabs(atd));
         }
@@ -229,22 +274,96 @@ __global__ __launch_bounds__(64) void k_opf_verdict(OpfVerdictArgs a) {
     a.rec[bl] = (double)state; a.rec[ld + bl] = prim; a.rec[2 * ld + bl] = dual; a.rec[3 * ld + bl] = pn; a.rec[4 * ld + bl] = dn;
 }
 
-// ---- host side ---------------------------------------------------------------------------------------------------------------------------------
-void launch_rhs(DcopfHandle* h, int groups, int blend, int form) {
-    OpfRhsArgs a{h->c_ptr, h->c_row, h->c_val, h->rhov, h->qd, h->Z, h->Y, h->XT, h->X, h->B, h->done, h->glist, h->sigma, h->alpha, h->n, h->ld, blend, form};
-    hipLaunchKernelGGL(k_opf_rhs, dim3((h->n + 3) / 4, groups), dim3(64, 4), 0, h->stream, a);
+// ---- the low-rank correction of an outaged lane's solve: x~ = x0 - W M U' x0, M = (C^-1 + U' W)^-1 -------------------------------------------------
+struct OpfCorrArgs {
+    const int* on; const int* var; const int* ai; const double* av; const double* s; const double* W; double* M; double* G; double* XT; double* B;
+    const int* groups;                                                  // nullable: groups 0 .. gridDim - 1
+    int n, ld, depth;
+};
+__device__ __forceinline__ size_t corr_lane(const OpfCorrArgs& a, int block) { return (size_t)(a.groups ? a.groups[block] : block) * 64 + threadIdx.x; }
+// a thread = a lane: U' x0 is a gather over the lane's short list (depth x 16 bytes of list, depth + 2 gathered doubles), then the 2 x 2 product
+__global__ __launch_bounds__(64) void k_opf_outage_g(OpfCorrArgs a) {
+    const size_t ld = (size_t)a.ld, bl = corr_lane(a, blockIdx.x);
+    double g0 = 0.0, g1 = 0.0;
+    if (a.on[bl]) {
+        double u0 = 0.0;
+        for (int q = 0; q < a.depth; ++q) u0 = fma(a.av[(size_t)q * ld + bl], a.XT[(size_t)a.ai[(size_t)q * ld + bl] * ld + bl], u0);
+        const double u1 = a.XT[(size_t)a.var[bl] * ld + bl] - a.XT[(size_t)a.var[ld + bl] * ld + bl];
+        g0 = fma(a.M[bl], u0, a.M[ld + bl] * u1);
+        g1 = fma(a.M[2 * ld + bl], u0, a.M[3 * ld + bl] * u1);
+    }
+    a.G[bl] = g0; a.G[ld + bl] = g1;
 }
-void launch_sweep(DcopfHandle* h, int groups) { sweep_pair(h->fac, h->stream, 0, h->B, nullptr, nullptr, h->W, h->XT, h->ld, groups, h->glist); }
+// a wavefront = one variable x 64 lanes, coalesced like k_opf_rhs.  Bound by memory: it streams 2 n ld doubles of W and reads and writes n ld of x~ per
+// iteration (32 bytes per variable and lane), beside the update pass's traffic; a wavefront none of whose lanes is corrected moves nothing
+__global__ __launch_bounds__(256) void k_opf_outage_apply(OpfCorrArgs a) {
+    const int j = blockIdx.x * 4 + uniform(threadIdx.y);
+    if (j >= a.n) return;
+    const size_t ld = (size_t)a.ld, bl = corr_lane(a, blockIdx.y), at = (size_t)j * ld + bl;
+    if (!a.on[bl]) return;
+    a.XT[at] = fma(-a.W[at], a.G[bl], fma(-a.W[(size_t)a.n * ld + at], a.G[ld + bl], a.XT[at]));
+}
+// the right-hand sides of W into B (zeroed before): column 0 the lane's a, column 1 its d.  A thread = a lane; a pad of the list adds 0 to variable 0
+__global__ __launch_bounds__(64) void k_opf_outage_scatter(OpfCorrArgs a, int column) {
+    const size_t ld = (size_t)a.ld, bl = corr_lane(a, blockIdx.x);
+    if (!a.on[bl]) return;
+    if (column == 0)
+        for (int q = 0; q < a.depth; ++q) a.B[(size_t)a.ai[(size_t)q * ld + bl] * ld + bl] += a.av[(size_t)q * ld + bl];
+    else { a.B[(size_t)a.var[bl] * ld + bl] = 1.0; a.B[(size_t)a.var[ld + bl] * ld + bl] = -1.0; }
+}
+// M = (C^-1 + U' W)^-1 with C^-1 = [[-s, 1], [1, 0]]; a thread = a lane.  A capacitance that cannot be inverted leaves NaN: the lane then runs to the limit
+__global__ __launch_bounds__(64) void k_opf_outage_cap(OpfCorrArgs a) {
+    const size_t ld = (size_t)a.ld, bl = corr_lane(a, blockIdx.x), nl = (size_t)a.n * ld;
+    double m00 = 0.0, m01 = 0.0, m10 = 0.0, m11 = 0.0;
+    if (a.on[bl]) {
+        double aa = 0.0, ad = 0.0;
+        for (int q = 0; q < a.depth; ++q) {
+            const size_t at = (size_t)a.ai[(size_t)q * ld + bl] * ld + bl;
+            aa = fma(a.av[(size_t)q * ld + bl], a.W[at], aa);
+            ad = fma(a.av[(size_t)q * ld + bl], a.W[nl + at], ad);
+        }
+        const size_t f = (size_t)a.var[bl] * ld + bl, t = (size_t)a.var[ld + bl] * ld + bl;
+        const double s00 = aa - a.s[bl], s01 = 1.0 + ad, s10 = 1.0 + (a.W[f] - a.W[t]), s11 = a.W[nl + f] - a.W[nl + t];
+        const double det = s00 * s11 - s01 * s10;
+        m00 = s11 / det; m01 = -s01 / det; m10 = -s10 / det; m11 = s00 / det;
+    }
+    a.M[bl] = m00; a.M[ld + bl] = m01; a.M[2 * ld + bl] = m10; a.M[3 * ld + bl] = m11;
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------------------------------------
+OpfOut out_of(const DcopfHandle* h) { return OpfOut{h->o_var, h->o_row, h->o_p}; }
+OpfCorrArgs corr_of(const DcopfHandle* h, const int* glist) {
+    return OpfCorrArgs{h->o_on, h->o_var, h->o_ai, h->o_av, h->o_s, h->o_W, h->o_M, h->o_g, h->XT, h->B, glist, h->n, h->ld, h->o_depth};
+}
+void launch_rhs(DcopfHandle* h, int groups, int blend, int form) {
+    OpfRhsArgs a{h->c_ptr, h->c_row, h->c_val, h->rhov, h->qd, h->Z, h->Y, h->XT, h->X, h->B, h->done, h->glist, h->sigma, h->alpha, h->n, h->ld, blend, form,
+                 out_of(h)};
+    if (h->outages) hipLaunchKernelGGL((k_opf_rhs<true>), dim3((h->n + 3) / 4, groups), dim3(64, 4), 0, h->stream, a);
+    else hipLaunchKernelGGL((k_opf_rhs<false>), dim3((h->n + 3) / 4, groups), dim3(64, 4), 0, h->stream, a);
+}
+void launch_correct(DcopfHandle* h, int groups) {
+    const OpfCorrArgs c = corr_of(h, h->glist);
+    hipLaunchKernelGGL(k_opf_outage_g, dim3(groups), dim3(64), 0, h->stream, c);
+    hipLaunchKernelGGL(k_opf_outage_apply, dim3((h->n + 3) / 4, groups), dim3(64, 4), 0, h->stream, c);
+}
+void launch_sweep(DcopfHandle* h, int groups) {
+    sweep_pair(h->fac, h->stream, 0, h->B, nullptr, nullptr, h->W, h->XT, h->ld, groups, h->glist);
+    if (h->outages) launch_correct(h, groups);
+}
 void launch_update(DcopfHandle* h, int groups, int keep_dy) {
-    OpfUpdateArgs a{h->r_ptr, h->r_col, h->r_val, h->rhov, h->rinv, h->XT, h->L, h->U, h->Z, h->Y, h->DY, h->done, h->glist, h->alpha, h->m, h->ld, keep_dy};
-    hipLaunchKernelGGL(k_opf_update, dim3((h->m + 3) / 4, groups), dim3(64, 4), 0, h->stream, a);
+    OpfUpdateArgs a{h->r_ptr, h->r_col, h->r_val, h->rhov, h->rinv, h->XT, h->L, h->U, h->Z, h->Y, h->DY, h->done, h->glist, h->alpha, h->m, h->ld, keep_dy,
+                    out_of(h)};
+    if (h->outages) hipLaunchKernelGGL((k_opf_update<true>), dim3((h->m + 3) / 4, groups), dim3(64, 4), 0, h->stream, a);
+    else hipLaunchKernelGGL((k_opf_update<false>), dim3((h->m + 3) / 4, groups), dim3(64, 4), 0, h->stream, a);
 }
 void launch_check(DcopfHandle* h, int groups, double tol, int iteration) {
-    OpfResArgs r{h->r_ptr, h->r_col, h->r_val, h->Pd, h->qd, h->X, h->Z, h->Y, h->DY, h->L, h->U, h->part_r, h->glist, h->m, h->ld};
-    hipLaunchKernelGGL((k_opf_residual<true>), dim3((h->chunks_r + 3) / 4, groups), dim3(64, 4), 0, h->stream, r);
+    OpfResArgs r{h->r_ptr, h->r_col, h->r_val, h->Pd, h->qd, h->X, h->Z, h->Y, h->DY, h->L, h->U, h->part_r, h->glist, h->m, h->ld, out_of(h)};
+    if (h->outages) hipLaunchKernelGGL((k_opf_residual<true, true>), dim3((h->chunks_r + 3) / 4, groups), dim3(64, 4), 0, h->stream, r);
+    else hipLaunchKernelGGL((k_opf_residual<true, false>), dim3((h->chunks_r + 3) / 4, groups), dim3(64, 4), 0, h->stream, r);
     OpfResArgs v = r;
     v.ptr = h->c_ptr; v.idx = h->c_row; v.val = h->c_val; v.part = h->part_v; v.count = h->n;
-    hipLaunchKernelGGL((k_opf_residual<false>), dim3((h->chunks_v + 3) / 4, groups), dim3(64, 4), 0, h->stream, v);
+    if (h->outages) hipLaunchKernelGGL((k_opf_residual<false, true>), dim3((h->chunks_v + 3) / 4, groups), dim3(64, 4), 0, h->stream, v);
+    else hipLaunchKernelGGL((k_opf_residual<false, false>), dim3((h->chunks_v + 3) / 4, groups), dim3(64, 4), 0, h->stream, v);
     OpfVerdictArgs w{h->part_r, h->part_v, h->rec, h->done, h->iters, tol, h->q_norm, h->chunks_r, h->chunks_v, h->ld, iteration};
     hipLaunchKernelGGL(k_opf_verdict, dim3(h->ld / 64), dim3(64), 0, h->stream, w);     // every group: a group that left keeps its record
 }
@@ -263,6 +382,58 @@ int assemble_and_factor(DcopfHandle* h, double sigma, bool compact) {
     DC_HIP(hipGetLastError());
     return 0;
 }
+// the outaged lanes' a = A' (rho o p) and s = p' (rho o p) at the handle's rho, W = K^-1 [a d] on the factor as it stands (two sweep pairs of batch
+// width through B and the sweeps' scratch, which an iteration rewrites anyway) and the lanes' 2 x 2 inverses.  After every numeric factorisation
+int build_outage(DcopfHandle* h) {
+    if (!h->outages) return 0;
+    const size_t ld = (size_t)h->ld, nb = (size_t)h->batch;
+    std::vector<double> rhov, rinv, sv(ld, 0.0);
+    rho_rows(h->h_eq, h->rho, rhov, rinv);
+    std::vector<std::vector<std::pair<int, double>>> list(nb);
+    int depth = 1;
+    for (size_t s = 0; s < nb; ++s) {
+        if (h->h_ostate[s] != 1) continue;
+        std::vector<std::pair<int, double>>& a = list[s];
+        for (int e = 0; e < 2; ++e) {
+            const int r = h->h_orow[e * nb + s];
+            const double pr = (e ? h->h_oy[s] : -h->h_oy[s]) * h->h_E[r], w = rhov[r] * pr;
+            sv[s] = std::fma(w, pr, sv[s]);
+            for (int p = h->h_rptr[r]; p < h->h_rptr[r + 1]; ++p) a.push_back({h->h_rcol[p], h->h_rval[p] * w});
+        }
+        std::sort(a.begin(), a.end());                                  // a column of both rows: its two terms added
+        size_t k = 0;
+        for (size_t q = 0; q < a.size(); ++q)
+            if (k && a[k - 1].first == a[q].first) a[k - 1].second += a[q].second;
+            else a[k++] = a[q];
+        a.resize(k);
+        depth = std::max(depth, (int)k);
+    }
+    if (depth > h->o_room) {
+        dev_release(h, h->o_ai); dev_release(h, h->o_av);
+        DC_TRY(dev_alloc(h, &h->o_ai, (size_t)depth * ld, (const int*)nullptr, true));
+        DC_TRY(dev_alloc(h, &h->o_av, (size_t)depth * ld, (const double*)nullptr, true));
+        h->o_room = depth;
+    }
+    h->o_depth = depth;
+    std::vector<int> ai((size_t)depth * ld, 0);
+    std::vector<double> av((size_t)depth * ld, 0.0);
+    for (size_t s = 0; s < nb; ++s)
+        for (size_t q = 0; q < list[s].size(); ++q) { ai[q * ld + s] = list[s][q].first; av[q * ld + s] = list[s][q].second; }
+    DC_HIP(sync_copy(h->o_ai, ai.data(), ai.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    DC_HIP(sync_copy(h->o_av, av.data(), av.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    DC_HIP(sync_copy(h->o_s, sv.data(), ld * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    const int groups = h->ld / 64;
+    const OpfCorrArgs c = corr_of(h, nullptr);
+    for (int column = 0; column < 2; ++column) {
+        DC_HIP(hipMemsetAsync(h->B, 0, (size_t)h->n * ld * sizeof(double), h->stream));
+        hipLaunchKernelGGL(k_opf_outage_scatter, dim3(groups), dim3(64), 0, h->stream, c, column);
+        sweep_pair(h->fac, h->stream, 0, h->B, nullptr, nullptr, h->W, h->o_W + (size_t)column * h->n * ld, h->ld, groups, nullptr);
+    }
+    hipLaunchKernelGGL(k_opf_outage_cap, dim3(groups), dim3(64), 0, h->stream, c);
+    DC_HIP(hipGetLastError());
+    return 0;
+}
+
 // K without sigma: a zero, negative, non-finite or vanishing pivot means variables that no row ties down
 int probe_singular(DcopfHandle* h, const OpfModel& M) {
     DC_TRY(assemble_and_factor(h, 0.0, false));
@@ -361,6 +532,8 @@ int upload_groups(DcopfHandle* h, int* groups) {
 int dcopf_run(DcopfHandle* h, double tol, long long max_iter, int check, int adapt_every) {
     const size_t ld = (size_t)h->ld;
     for (size_t s = 0; s < ld; ++s) { h->h_done[s] = s < (size_t)h->batch ? 0 : 1; h->h_iters[s] = 0; }     // padding lanes never run
+    if (h->outages)                                                     // nor do lanes whose outage is a bridge
+        for (size_t s = 0; s < (size_t)h->batch; ++s) if (h->h_ostate[s] == 3) h->h_done[s] = 3;
     h->solved = true;
     if (h->singular) { std::fill(h->h_status.begin(), h->h_status.end(), 3); return 0; }
     DC_HIP(sync_copy(h->done, h->h_done.data(), ld * sizeof(int), hipMemcpyHostToDevice, h->stream));
@@ -400,6 +573,7 @@ int dcopf_run(DcopfHandle* h, double tol, long long max_iter, int check, int ada
                 if ((r < 0.2 || r > 5.0) && rho != h->rho) {
                     h->rho = rho;
                     DC_TRY(assemble_and_factor(h, h->sigma, true));
+                    DC_TRY(build_outage(h));                          // K and a = A' (rho o p) changed: W and the lanes' 2 x 2 inverses with them
                     h->refactorisations++;
                 }
             }
@@ -407,7 +581,7 @@ int dcopf_run(DcopfHandle* h, double tol, long long max_iter, int check, int ada
     }
     DC_HIP(hipStreamSynchronize(h->stream));
     for (size_t s = 0; s < (size_t)h->batch; ++s) {
-        h->h_status[s] = h->h_done[s] == 1 ? 0 : h->h_done[s] == 2 ? 2 : 5;
+        h->h_status[s] = h->h_done[s] == 1 ? 0 : h->h_done[s] == 2 ? 2 : h->h_done[s] == 3 ? 3 : 5;
         if (!h->h_done[s]) h->h_iters[s] = (int)max_iter;
     }
     return 0;
@@ -527,11 +701,75 @@ int jg_dcopf_set_start(int64_t h, const double* x, const double* y) {
             for (int p = d->h_rptr[i]; p < d->h_rptr[i + 1]; ++p) ax = std::fma(d->h_rval[p], x[s * n + d->h_rcol[p]], ax);
             tz[i * ld + s] = ax;
         }
+        if (d->outages && d->h_ostate[s] == 1) {                        // z = A_s x
+            const size_t nb = (size_t)d->batch;
+            const double dx = x[s * n + d->h_ovar[s]] - x[s * n + d->h_ovar[nb + s]];
+            for (int e = 0; e < 2; ++e) {
+                const size_t r = (size_t)d->h_orow[e * nb + s];
+                tz[r * ld + s] = std::fma((e ? d->h_oy[s] : -d->h_oy[s]) * d->h_E[r], dx, tz[r * ld + s]);
+            }
+        }
     }
     DC_RET(jg::push_lanes(d, d->X, n, tx));
     DC_RET(jg::push_lanes(d, d->Y, m, ty));
     DC_RET(jg::push_lanes(d, d->Z, m, tz));
     d->solved = false;
+    return 0;
+}
+
+// one branch out per lane: from_variable, to_variable [batch] the variables of the branch's two buses, from_row, to_row [batch] their balance rows
+// (1-based, equality rows), admittance [batch] y_k as it stands in A, state [batch] 0 none / 1 outage / 3 the outage is a bridge: the lane is not
+// run (status 3).  A lane of state 0 or 3 is not read beyond its state.  state NULL clears the set.  x, y, z stay as they are
+int jg_dcopf_set_branch_outages(int64_t h, const int64_t* from_variable, const int64_t* to_variable, const int64_t* from_row, const int64_t* to_row,
+                                const double* admittance, const int32_t* state) {
+    OPF_ENTER(h);
+    const size_t nb = (size_t)d->batch, ld = (size_t)d->ld;
+    d->solved = false;
+    if (!state) { d->outages = false; return 0; }
+    if (!from_variable || !to_variable || !from_row || !to_row || !admittance) return api_fail(1, "jg_dcopf_set_branch_outages: null pointer");
+    std::vector<int> st(nb), var(2 * nb, -1), row(2 * nb, -1);
+    std::vector<double> y(nb, 0.0);
+    bool any = false;
+    for (size_t s = 0; s < nb; ++s) {
+        st[s] = state[s];
+        if (st[s] != 0 && st[s] != 1 && st[s] != 3) return api_fail(1, "jg_dcopf_set_branch_outages: a state is not 0, 1 or 3");
+        any = any || st[s] != 0;
+        if (st[s] != 1) continue;
+        const int64_t f = from_variable[s], t = to_variable[s], rf = from_row[s], rt = to_row[s];
+        if (f < 1 || f > d->n || t < 1 || t > d->n || f == t || rf < 1 || rf > d->m || rt < 1 || rt > d->m || rf == rt || !std::isfinite(admittance[s]))
+            return api_fail(1, "jg_dcopf_set_branch_outages: variables in 1..n and distinct, rows in 1..m and distinct, a finite admittance");
+        if (!d->h_eq[rf - 1] || !d->h_eq[rt - 1]) return api_fail(1, "jg_dcopf_set_branch_outages: the two rows must be equality rows");
+        var[s] = (int)f - 1; var[nb + s] = (int)t - 1; row[s] = (int)rf - 1; row[nb + s] = (int)rt - 1; y[s] = admittance[s];
+    }
+    if (!any) { d->outages = false; return 0; }
+    if (!d->o_on) {
+        const size_t N = (size_t)d->n;
+        DC_RET(jg::dev_alloc(d, &d->o_on, ld, (const int*)nullptr, true));
+        DC_RET(jg::dev_alloc(d, &d->o_var, 2 * ld, (const int*)nullptr, true));
+        DC_RET(jg::dev_alloc(d, &d->o_row, 2 * ld, (const int*)nullptr, true));
+        DC_RET(jg::dev_alloc(d, &d->o_p, 2 * ld, (const double*)nullptr, true));
+        DC_RET(jg::dev_alloc(d, &d->o_s, ld, (const double*)nullptr, true));
+        DC_RET(jg::dev_alloc(d, &d->o_M, 4 * ld, (const double*)nullptr, true));
+        DC_RET(jg::dev_alloc(d, &d->o_g, 2 * ld, (const double*)nullptr, true));
+        DC_RET(jg::dev_alloc(d, &d->o_W, 2 * N * ld, (const double*)nullptr, true));
+    }
+    std::vector<int> on(ld, 0), tv(2 * ld, -1), tr(2 * ld, -1);
+    std::vector<double> tp(2 * ld, 0.0);
+    for (size_t s = 0; s < nb; ++s) {
+        if (st[s] != 1) continue;
+        on[s] = 1;
+        for (int e = 0; e < 2; ++e) {
+            tv[e * ld + s] = var[e * nb + s]; tr[e * ld + s] = row[e * nb + s];
+            tp[e * ld + s] = (e ? y[s] : -y[s]) * d->h_E[row[e * nb + s]];
+        }
+    }
+    DC_API_HIP(jg::sync_copy(d->o_on, on.data(), on.size() * sizeof(int), hipMemcpyHostToDevice, d->stream));
+    DC_API_HIP(jg::sync_copy(d->o_var, tv.data(), tv.size() * sizeof(int), hipMemcpyHostToDevice, d->stream));
+    DC_API_HIP(jg::sync_copy(d->o_row, tr.data(), tr.size() * sizeof(int), hipMemcpyHostToDevice, d->stream));
+    DC_API_HIP(jg::sync_copy(d->o_p, tp.data(), tp.size() * sizeof(double), hipMemcpyHostToDevice, d->stream));
+    d->h_ostate = st; d->h_ovar = var; d->h_orow = row; d->h_oy = y;
+    d->outages = true;
+    DC_RET(jg::build_outage(d));
     return 0;
 }
 
@@ -554,13 +792,15 @@ int jg_dcopf_get(int64_t h, double* x, double* y, double* z, double* objective) 
     OPF_ENTER(h);
     if (!d->solved) return api_fail(4, "jg_dcopf_get: jg_dcopf_run first");
     const size_t m = (size_t)d->m, n = (size_t)d->n, ld = (size_t)d->ld;
+    const double nan = std::nan("");
+    auto skipped = [&](size_t s) { return d->h_status[s] == 3; };       // a lane that never ran (a bridge outage): NaN
     std::vector<double> t;
     if (x || objective) {
         DC_RET(jg::fetch_lanes(d, d->X, n, t));
         for (size_t s = 0; s < (size_t)d->batch; ++s) {
             double obj = 0.0;
             for (size_t j = 0; j < n; ++j) {
-                const double v = t[j * ld + s];
+                const double v = skipped(s) ? nan : t[j * ld + s];
                 if (x) x[s * n + j] = v;
                 obj += (0.5 * d->h_P0[j] * v + d->h_q0[j]) * v;
             }
@@ -570,21 +810,23 @@ int jg_dcopf_get(int64_t h, double* x, double* y, double* z, double* objective) 
     if (y) {
         DC_RET(jg::fetch_lanes(d, d->Y, m, t));
         for (size_t s = 0; s < (size_t)d->batch; ++s)
-            for (size_t i = 0; i < m; ++i) y[s * m + i] = t[i * ld + s] * d->h_E[i] / d->cscale;
+            for (size_t i = 0; i < m; ++i) y[s * m + i] = skipped(s) ? nan : t[i * ld + s] * d->h_E[i] / d->cscale;
     }
     if (z) {
         DC_RET(jg::fetch_lanes(d, d->Z, m, t));
         for (size_t s = 0; s < (size_t)d->batch; ++s)
-            for (size_t i = 0; i < m; ++i) z[s * m + i] = t[i * ld + s] / d->h_E[i];
+            for (size_t i = 0; i < m; ++i) z[s * m + i] = skipped(s) ? nan : t[i * ld + s] / d->h_E[i];
     }
     return 0;
 }
 
-// kernel: 0 one whole iteration, 1 right-hand side, 2 sweep pair, 3 projection step, 4 residual pass and verdict, 5 assembly of K and refactorisation.
+// kernel: 0 one whole iteration, 1 right-hand side, 2 sweep pair, 3 projection step, 4 residual pass and verdict, 5 assembly of K and refactorisation,
+// 6 the outaged lanes' correction of x~ (the gather and the pass over x~), 7 the build of W and the 2 x 2 inverses; 6 and 7 need a set of outages.
 // The timed launches advance the lanes' iterates: set the start and run again for results
 int jg_dcopf_time(int64_t h, int kernel, int reps, double* ms) {
     OPF_ENTER(h);
-    if (!ms || reps < 1 || kernel < 0 || kernel > 5) return api_fail(1, "jg_dcopf_time: bad argument");
+    if (!ms || reps < 1 || kernel < 0 || kernel > 7) return api_fail(1, "jg_dcopf_time: bad argument");
+    if (kernel >= 6 && !d->outages) return api_fail(4, "jg_dcopf_time: jg_dcopf_set_branch_outages first");
     if (!d->have_bounds) return api_fail(4, "jg_dcopf_time: jg_dcopf_set_bounds first");
     std::fill(d->h_done.begin(), d->h_done.end(), 0);
     int groups = 0;
@@ -592,7 +834,10 @@ int jg_dcopf_time(int64_t h, int kernel, int reps, double* ms) {
     DC_API_HIP(jg::sync_fill(d->done, 0, (size_t)d->ld * sizeof(int), d->stream));
     const int rc = jg::time_events(d->stream, reps, ms, d->error, [&]() -> int {
         if (kernel == 0 || kernel == 1) jg::launch_rhs(d, groups, 1, 1);
-        if (kernel == 0 || kernel == 2) jg::launch_sweep(d, groups);
+        if (kernel == 0) jg::launch_sweep(d, groups);
+        if (kernel == 2) jg::sweep_pair(d->fac, d->stream, 0, d->B, nullptr, nullptr, d->W, d->XT, d->ld, groups, d->glist);
+        if (kernel == 6) jg::launch_correct(d, groups);
+        if (kernel == 7) return jg::build_outage(d);
         if (kernel == 0 || kernel == 3) jg::launch_update(d, groups, 0);
         if (kernel == 4) jg::launch_check(d, groups, 1e-300, 0);
         if (kernel == 5) return jg::assemble_and_factor(d, d->sigma, true);

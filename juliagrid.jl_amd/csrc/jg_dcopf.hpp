@@ -16,6 +16,15 @@
 // group of 64 finished lanes leaves the launches through the sweeps' group list.  rho follows the median residual ratio of the unfinished lanes
 // (K is re-assembled from its term lists and refactorised numerically on the same tables).
 //
+// A lane may also run with ONE branch out (jg_dcopf_set_branch_outages).  With branch k (admittance y_k, buses f and t, balance rows r_f and r_t) out the
+// lane's matrix is A_s = A + p d', p = -y_k (E[r_f] e_rf - E[r_t] e_rt) in row space and d = e_f - e_t in variable space; its flow and angle rows stay in
+// A and are free rows (l = -inf, u = +inf: their multiplier stays 0).  Then K_s = K + a d' + d a' + s d d' = K + U C U' with a = A' (rho o p),
+// s = p' (rho o p), U = [a d], C = [[0, 1], [1, s]], and
+//     x~ = x0 - W (C^-1 + U' W)^-1 U' x0,   x0 = K^-1 b,   W = K^-1 U
+// K is not refactorised per lane: W is two sweep pairs of batch width after every numeric factorisation, the 2 x 2 inverse is kept per lane, and an
+// iteration pays a gather, a 2 x 2 product and one pass over x~.  Everywhere the iteration uses A such a lane adds the term of p d'.  A lane whose
+// outage is a bridge (the host says so) never iterates: status 3.  A handle without outages runs the launches it ran before there were any.
+//
 // The host scales the problem once: the objective by c = 1 / max(|P|, |q|), every row of A (with l, u) to unit 2-norm.  Residuals and tolerances are
 // those of the scaled problem; x, y, z and the objective leave the handle unscaled.
 #pragma once
@@ -57,6 +66,15 @@ struct DcopfHandle : DcDevice {
     double* part_r = nullptr; double* part_v = nullptr; int chunks_r = 0, chunks_v = 0;      // [chunks][5][ld], [chunks][4][ld]
     double* rec = nullptr;                                              // [OPF_REC][ld]
     std::vector<int> h_done, h_iters, h_status;
+    // per-lane branch outages; the device tables exist from the first jg_dcopf_set_branch_outages on, lane-fastest [.][ld]
+    bool outages = false;                                               // a lane with state 1 or 3: the second instances of the kernels run
+    int o_depth = 0, o_room = 0;                                        // longest list of a = A' (rho o p) in the batch; what o_ai / o_av hold
+    std::vector<int> h_ostate, h_ovar, h_orow; std::vector<double> h_oy;        // [batch] 0 none / 1 outage / 3 bridge, [2][batch] 0-based, [batch] y_k
+    int* o_on = nullptr;                                                // [ld] 1: the lane is corrected
+    int* o_var = nullptr; int* o_row = nullptr; double* o_p = nullptr;  // [2][ld] f, t (-1: none); r_f, r_t (-1); p on r_f, r_t
+    int* o_ai = nullptr; double* o_av = nullptr;                        // [o_room][ld] a as a padded (index, value) list: a pad is (0, 0.0)
+    double* o_s = nullptr; double* o_M = nullptr; double* o_g = nullptr;        // [ld] s; [4][ld] (C^-1 + U' W)^-1 by rows; [2][ld] its product with U' x0
+    double* o_W = nullptr;                                              // [2][n][ld] K^-1 a, K^-1 d
 };
 
 }  // namespace jg

@@ -9,7 +9,8 @@ The reference hands the model to a JuMP solver, one problem at a time.  Here `mo
 l <= A x <= u  with x = (bus angles, outputs of the in-service generators, one helper per piecewise-linear cost of more than two points) and the
 rows in the order piecewise, balance, slack, capability, flow, angle difference.  P, q and A are shared by the lanes of a batch; a lane's own data are
 its bounds: the demand profile in the balance rows, generator limits and generator outages in the capability rows.  A branch outage of one lane
-would change A, so it is no lane data here.
+changes A by a rank-1 term p d' (setBranchOutages_): the lane keeps the shared factor and corrects every solve by a rank-2 update; the branch's own
+flow and angle rows become free rows and the two balance rows lose its shift power.
 
 This module is product host code (numpy); the iteration runs in libjgrid_hip.so.
 """
@@ -155,6 +156,10 @@ class DcOptimalPowerFlow:
         self._l = np.tile(model.l, (self.batch, 1))
         self._u = np.tile(model.u, (self.batch, 1))
         self._demand = np.tile(system.bus.demand.active, (self.batch, 1))
+        self._shift = np.zeros((self.batch, system.bus.number))        # what the lanes' outaged branches take out of the balance rows' shift power
+        self.outage = np.zeros(self.batch, dtype=np.int64)             # the lanes' outaged branch (label, 0: none)
+        self._outage_state = np.zeros(self.batch, dtype=np.int32)      # 0 none, 1 outage, 3 the outage is a bridge
+        self._outage_dirty = False
         self._dirty = True
         self._x = self._y = self._z = None
 
@@ -203,8 +208,15 @@ def setInjection_(an: DcOptimalPowerFlow, demand) -> None:
     bus, dc = an.system.bus, an.system.model.dc
     d = _lanes(an, demand, bus.number, "setInjection_")
     rows = an.model.rows["balance"]
-    an._l[:, rows] = an._u[:, rows] = -(d + bus.shunt.conductance[None, :] + dc.shiftPower[None, :])
     an._demand = d.copy()
+    _balance(an)
+
+
+def _balance(an) -> None:
+    """The balance rows' right-hand sides from the lanes' demand and the shift power their outaged branches no longer carry."""
+    bus, dc = an.system.bus, an.system.model.dc
+    rows = an.model.rows["balance"]
+    an._l[:, rows] = an._u[:, rows] = -(an._demand + bus.shunt.conductance[None, :] + dc.shiftPower[None, :]) + an._shift
     an._dirty = True
 
 
@@ -224,7 +236,8 @@ def setOutages_(an: DcOptimalPowerFlow, generators=None, branches=None) -> None:
     """Per-lane generator outages: lane s runs without generator generators[s] (0 / None: none), through l = u = 0 on its capability row."""
     if branches is not None:
         raise ValueError("setOutages_: a branch outage of one lane changes the constraint matrix A, which the lanes of a DcOptimalPowerFlow share (with it "
-                         "the one factor); take the branch out of the system (updateBranchSystem_) and build an analysis of its own")
+                         "the one factor); setBranchOutages_ runs such lanes on the shared factor by a low-rank correction; or take the branch out of the system "
+                         "(updateBranchSystem_) and build an analysis of its own")
     if generators is None:
         return
     lab = [int(g) if g else 0 for g in generators]
@@ -239,6 +252,71 @@ def setOutages_(an: DcOptimalPowerFlow, generators=None, branches=None) -> None:
         if g in row_of:                                                # (one that is out of service in the system already has no row)
             an._l[s, row_of[g]] = an._u[s, row_of[g]] = 0.0
     an._dirty = True
+
+
+def setBranchOutages_(an: DcOptimalPowerFlow, branches) -> None:
+    """Per-lane branch outages: lane s runs without branch branches[s] (0 / None: none; one label: every lane), on the shared factor.  The lane's
+    matrix is A + p d' (csrc/jg_dcopf.hpp); here its bounds: the branch's flow and angle rows are free, the balance rows of its two buses lose its
+    shift power.  A lane whose branch is a bridge (islandTable) is not run: status 3, NaN.  A branch that is out of service in the system is no
+    outage.  A call replaces the set, None clears it; x, y, z stay, so the next solve_ starts from the last solution."""
+    br, dc, md = an.system.branch, an.system.model.dc, an.model
+    if branches is None or np.isscalar(branches):
+        branches = [branches] * an.batch
+    lab = np.array([int(b) if b else 0 for b in branches], dtype=np.int64)
+    if lab.shape != (an.batch,):
+        raise ValueError(f"setBranchOutages_: expected {an.batch} branch labels")
+    if np.any((lab < 0) | (lab > br.number)):
+        raise IndexError("setBranchOutages_: branch label out of range")
+    lab[lab > 0] = np.where((br.layout.status[lab[lab > 0] - 1] == 1) & (br.layout.from_[lab[lab > 0] - 1] != br.layout.to[lab[lab > 0] - 1]), lab[lab > 0], 0)
+    state = np.zeros(an.batch, dtype=np.int32)
+    if np.any(lab):
+        from .contingency import islandTable
+        tb = islandTable(an.system)
+        state[lab > 0] = np.where(tb.lo[lab[lab > 0] - 1] <= tb.hi[lab[lab > 0] - 1], 3, 1)
+    own = {}                                                            # the flow and angle rows of a branch
+    for kind in ("flow", "angle"):
+        for i in md.rows[kind]:
+            own.setdefault(md.ref[i], []).append(int(i))
+    for kind in ("flow", "angle"):                                      # the set before this one is gone
+        an._l[:, md.rows[kind]], an._u[:, md.rows[kind]] = md.l[md.rows[kind]], md.u[md.rows[kind]]
+    an._shift[:] = 0.0
+    for s in np.flatnonzero(state == 1):
+        k = int(lab[s]) - 1
+        for i in own.get(k + 1, ()):
+            an._l[s, i], an._u[s, i] = -np.inf, np.inf
+        share = float(dc.admittance[k]) * float(br.parameter.shiftAngle[k])
+        an._shift[s, br.layout.from_[k] - 1] -= share
+        an._shift[s, br.layout.to[k] - 1] += share
+    an.outage, an._outage_state, an._outage_dirty = lab, state, True
+    _balance(an)
+
+
+def _push_outages(an) -> None:
+    br, dc, md = an.system.branch, an.system.model.dc, an.model
+    L = _lib.lib()
+    if not np.any(an._outage_state):
+        _lib.check(L.jg_dcopf_set_branch_outages(an._h, None, None, None, None, None, None))
+        return
+    k = np.maximum(an.outage - 1, 0)
+    f, t = br.layout.from_[k].astype(np.int64), br.layout.to[k].astype(np.int64)            # bus i is variable i; 1-based as the ABI counts
+    rf, rt = md.rows["balance"][f - 1] + 1, md.rows["balance"][t - 1] + 1
+    y = np.ascontiguousarray(dc.admittance[k], dtype=np.float64)
+    arrays = [np.ascontiguousarray(a, dtype=np.int64) for a in (f, t, rf, rt)] + [y, np.ascontiguousarray(an._outage_state, dtype=np.int32)]
+    _lib.check(L.jg_dcopf_set_branch_outages(an._h, *[a.ctypes.data for a in arrays]))
+
+
+def outageCosts(system: PowerSystem, branches, demand=None, **kw) -> NS:
+    """What each branch outage costs: ONE analysis with lane 0 the base case and lane j the outage of branches[j - 1] (demand: [buses] for every lane).
+    Per outage its status, objective, cost (objective minus the base lane's), iterations and largest nodal price; `base` holds the base lane's."""
+    branches = [int(b) for b in branches]
+    an = dcOptimalPowerFlow(system, batch=len(branches) + 1, **kw)
+    if demand is not None:
+        setInjection_(an, np.asarray(demand, dtype=np.float64))
+    setBranchOutages_(an, [0] + branches)
+    solve_(an)
+    st, obj, it, price = np.atleast_1d(an.status), np.atleast_1d(an.objective), np.atleast_1d(an.iterations), np.atleast_2d(an.dual.balance).max(axis=1)
+    return NS(branches=np.array(branches, dtype=np.int64), status=st[1:].copy(), objective=obj[1:].copy(), cost=obj[1:] - obj[0], iterations=it[1:].copy(),
+              price=price[1:].copy(), base=NS(status=int(st[0]), objective=float(obj[0]), iterations=int(it[0]), price=float(price[0])), analysis=an)
 
 
 def setInitialPoint_(an: DcOptimalPowerFlow, source) -> None:
@@ -267,6 +345,9 @@ def solve_(an: DcOptimalPowerFlow, iteration: int | None = None, tolerance: floa
     """solve!(analysis): runs every lane until it is solved, shown infeasible or at the iteration limit.  A first solve starts at zero (or at
     setInitialPoint_'s point); a later one goes on from where the last one ended -- the warm start after new bounds."""
     L, md = _lib.lib(), an.model
+    if an._outage_dirty:
+        _push_outages(an)
+        an._outage_dirty = False
     if an._dirty:
         _lib.check(L.jg_dcopf_set_bounds(an._h, np.ascontiguousarray(an._l).reshape(-1), np.ascontiguousarray(an._u).reshape(-1)))
         an._dirty = False
@@ -278,6 +359,11 @@ def solve_(an: DcOptimalPowerFlow, iteration: int | None = None, tolerance: floa
         _lib.check(L.jg_dcopf_get(an._h, x.ctypes.data, y.ctypes.data, z.ctypes.data, obj.ctypes.data))
     else:
         x[:], y[:], z[:], obj[:] = np.nan, np.nan, np.nan, np.nan
+    out = np.flatnonzero(an._outage_state == 1)
+    for s in out:                                                       # the outaged branch's own rows are free rows: no multiplier
+        for i in np.concatenate((md.rows["flow"], md.rows["angle"])):
+            if md.ref[i] == an.outage[s]:
+                y[s, i] = 0.0
     an._x, an._y, an._z = x, y, z
     an.iterations, an.status, an.refactorisations = an._shape(it), an._shape(st), int(rf[0])
     an.objective = an._shape(obj + md.constant)
@@ -306,6 +392,9 @@ def power_(an: DcOptimalPowerFlow) -> None:
     th = an._x[:, :an.model.buses]
     f, t = br.layout.from_ - 1, br.layout.to - 1
     fr = dc.admittance[None, :] * (th[:, f] - th[:, t] - br.parameter.shiftAngle[None, :])
+    out = np.flatnonzero(getattr(an, "_outage_state", np.zeros(0)) == 1)
+    if out.size:
+        fr[out, an.outage[out] - 1] = 0.0                              # a lane's outaged branch carries nothing
     inj = np.tile(bus.shunt.conductance, (an.batch, 1))
     for s in range(an.batch):
         np.add.at(inj[s], f, fr[s])
