@@ -2164,6 +2164,110 @@ function opfTimeKernel(b::DcOptimalPowerFlowBatch, kernel::Int, reps::Int = 20)
     return ms
 end
 
+# ---- batched DC least-absolute-value state estimation (jgrid.h: jg_dclav_*; csrc/jg_dclav.hip) --------------------------------------------------
+# dcLavStateEstimation / solve! (src/stateEstimation/dcStateEstimation.jl:201-313, src/backend/expressions.jl:381-421) for `batch` realisations of one
+# measurement set: the reference hands the LP to a JuMP optimizer; here every lane runs a primal-dual interior-point method on a lane-valued factor of
+# the gain H' Q H.  The rows are those of the WLS model (dcseRows / dcseRowStatus above).  The C handle is an Int64 token.
+"""
+    DcLavStateEstimationBatch
+
+What `dcLavStateEstimation(monitoring, HIP; batch)` returns: `se` holds the rows of the reference's WLS model (coefficient, mean, index), `readings`
+[row, batch] the lanes' means, and after `solve!` `angle` [bus, batch], `status` (0 solved, 5 iteration limit, 1 unobservable, 3 a bad pivot in the lane),
+`objective`, `iterations`, `residual`, `dual` [row, batch] and `gap` per lane.
+"""
+mutable struct DcLavStateEstimationBatch
+    token::Int64
+    system::PowerSystem
+    monitoring::Measurement
+    se::Any
+    batch::Int64
+    iteration::Int64
+    tolerance::Float64
+    readings::Matrix{Float64}
+    angle::Matrix{Float64}
+    status::Vector{Int32}
+    objective::Vector{Float64}
+    iterations::Vector{Int32}
+    residual::Matrix{Float64}
+    dual::Matrix{Float64}
+    gap::Vector{Float64}
+    from::Matrix{Float64}
+    rowStatus::Vector{Int32}
+    stale::Bool
+end
+function JuliaGrid.dcLavStateEstimation(monitoring::Measurement, ::Type{HIP}; batch::Int64 = 1, iteration::Int64 = 50, tolerance::Float64 = 1e-8, device::Int64 = 0)
+    system = monitoring.system
+    coefficient, mean, precision, power, index, number, inservice = JuliaGrid.dcStateEstimationWls(system, monitoring)
+    se = (coefficient = coefficient, mean = mean, index = index, number = number, inservice = inservice)
+    rowptr, col, val = dcseRows(system, monitoring, coefficient)
+    status = dcseRowStatus(monitoring, index, number)
+    slack = system.bus.layout.slack
+    token = Ref{Int64}(0)
+    check(ccall((:jg_dclav_create, lib), Cint, (Ref{Int64}, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int32}, Int64, Float64, Int64, Cint),
+        token, system.bus.number, number, rowptr, col, val, status, slack, system.bus.voltage.angle[slack], batch, device))
+    b = DcLavStateEstimationBatch(token[], system, monitoring, se, batch, iteration, tolerance, repeat(mean, 1, batch), zeros(system.bus.number, batch),
+        zeros(Int32, batch), zeros(batch), zeros(Int32, batch), zeros(number, batch), zeros(number, batch), zeros(batch), zeros(system.branch.number, batch), status, true)
+    finalizer(x -> (x.token != 0 && ccall((:jg_dclav_destroy, lib), Cvoid, (Int64,), x.token); x.token = 0), b)
+    br = system.branch
+    check(ccall((:jg_dclav_set_branches, lib), Cint, (Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}),
+        b.token, br.number, br.layout.from, br.layout.to, system.model.dc.admittance, br.parameter.shiftAngle))
+    return b
+end
+"{n, m, batch, ld, entries of G, factor entries, factorisation levels, forward levels, backward levels, sweep launches, bytes per lane, in-service rows, factorisations, iterations of the last solve}"
+function dims(b::DcLavStateEstimationBatch)
+    d = zeros(Int64, 14)
+    check(ccall((:jg_dclav_dims, lib), Cint, (Int64, Ptr{Int64}), b.token, d))
+    return d
+end
+"the means of lanes lane0 .. (0-based), a [row, count] matrix in the order of se.mean"
+function setReadings!(b::DcLavStateEstimationBatch, z::Matrix{Float64}; lane0::Int64 = 0)
+    b.readings[:, (lane0 + 1):(lane0 + size(z, 2))] .= z
+    check(ccall((:jg_dclav_set_readings, lib), Cint, (Int64, Int64, Int64, Ptr{Float64}), b.token, lane0, size(z, 2), z))
+    return nothing
+end
+"the status of every row (0 / 1): the next solve! starts anew on the changed set, nothing symbolic is redone"
+function setRowStatus!(b::DcLavStateEstimationBatch, status::Vector{Int32})
+    check(ccall((:jg_dclav_set_status, lib), Cint, (Int64, Ptr{Int32}), b.token, status))
+    b.rowStatus .= status
+    return nothing
+end
+"setInitialPoint!: `angle` [bus, batch] replaces the unit-weight least-squares estimate in the start of the NEXT solve!"
+function JuliaGrid.setInitialPoint!(b::DcLavStateEstimationBatch, angle::Matrix{Float64})
+    check(ccall((:jg_dclav_set_initial, lib), Cint, (Int64, Ptr{Float64}), b.token, angle))
+    return nothing
+end
+"solve!(analysis) for every lane; every call starts anew (interior-point iterations are not warm-started)"
+function JuliaGrid.solve!(b::DcLavStateEstimationBatch)
+    if b.stale
+        check(ccall((:jg_dclav_set_readings, lib), Cint, (Int64, Int64, Int64, Ptr{Float64}), b.token, 0, b.batch, b.readings))
+        b.stale = false
+    end
+    check(ccall((:jg_dclav_solve, lib), Cint, (Int64, Cint, Float64), b.token, b.iteration, b.tolerance))
+    check(ccall((:jg_dclav_get_angle, lib), Cint, (Int64, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}), b.token, b.angle, b.status, b.objective, b.iterations))
+    check(ccall((:jg_dclav_get_residual, lib), Cint, (Int64, Ptr{Float64}), b.token, b.residual))
+    check(ccall((:jg_dclav_get_dual, lib), Cint, (Int64, Ptr{Float64}, Ptr{Float64}), b.token, b.dual, b.gap))
+    return nothing
+end
+"power!(analysis) branch part (dcAnalysis.jl:353-374): from [branch, batch]; to = -from"
+function JuliaGrid.power!(b::DcLavStateEstimationBatch)
+    check(ccall((:jg_dclav_get_flows, lib), Cint, (Int64, Ptr{Float64}), b.token, b.from))
+    return nothing
+end
+"the lane-valued factor alone: `q` [row, batch] the lanes' weights, `rhs` [bus, batch] -> (H' Q H)^-1 rhs [bus, batch] and the lanes' bad-pivot flags"
+function lavFactorSolve(b::DcLavStateEstimationBatch, q::Matrix{Float64}, rhs::Matrix{Float64})
+    x = zeros(Float64, size(rhs))
+    bad = zeros(Int32, b.batch)
+    check(ccall((:jg_dclav_factor_solve, lib), Cint, (Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}), b.token, q, rhs, x, bad))
+    return x, bad
+end
+"milliseconds of `reps` runs (HIP events): 0 a whole iteration but its update, 1 assembly, 2 factorisation, 3 one sweep pair, 4 the row, column and step passes"
+function lavTimeKernel(b::DcLavStateEstimationBatch, kernel::Int, reps::Int = 20)
+    ms = zeros(Float64, reps)
+    check(ccall((:jg_dclav_time_kernel, lib), Cint, (Int64, Cint, Cint, Ptr{Float64}), b.token, kernel, reps, ms))
+    return ms
+end
+export DcLavStateEstimationBatch, setRowStatus!, lavFactorSolve, lavTimeKernel
+
 # ---- Gauss-Seidel power flow, one scenario per lane (jgrid.h: jg_gs_*; csrc/jg_gs.hip) ---------------------------------------------------
 # gaussSeidel / mismatch! / solve! / powerFlow! (src/powerFlow/acPowerFlow.jl:563-619, 732-764, 985-1041, 1389-1433) for `batch` scenarios of one grid: a
 # sweep is sequential over the buses of a scenario, so a lane runs the reference's update sequence unchanged and a powerFlow! is ONE launch.  The C

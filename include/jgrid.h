@@ -1052,6 +1052,50 @@ int jg_dcopf_set_branch_outages(int64_t h, const int64_t* from_variable, const i
                                 const double* admittance, const int32_t* state);
 
 /* ---------------------------------------------------------------------------------------------
+ * Batched DC least-absolute-value state estimation: a primal-dual interior-point method per lane on a lane-valued factor of the gain
+ * (csrc/jg_dclav.hip, csrc/jg_dc_lanefactor.hip).  The handle is an int64 token.
+ *
+ * Every lane solves  min |z - H theta|_1  over the in-service rows of ONE coefficient matrix H with readings z of its own, the slack's angle fixed
+ * (the reference's dcLavStateEstimation, unweighted; a weighted model is a scaled H and z).  Indices are 1-based; per-lane arrays are [batch][rows or
+ * buses].  The gain H' Q H has a diagonal Q per lane and iteration: its pattern is analysed once, its values are assembled and factorised per lane.
+ *
+ *   jg_dclav_create        rows of H as CSR (columns of a row ascending), status [m] 0 / 1, the slack bus and its angle.  The device memory of `batch`
+ *                          lanes is computed first: a batch that does not fit is refused with code 5 and the sizes in the message
+ *   jg_dclav_dims          n, m, batch, ld, entries of G, entries of the factor, factorisation levels, forward levels, backward levels, launches of a
+ *                          sweep pair, bytes per lane, in-service rows, lane-valued factorisations so far, iterations of the last solve: dims [14]
+ *   jg_dclav_set_readings  z [count][m] of lanes lane0 .. (se.mean: the constants of the rows already taken out)
+ *   jg_dclav_set_status    status [m]: a changed row set re-runs the start of the next solve and nothing symbolic
+ *   jg_dclav_set_initial   theta [batch][n] (the slack's angle included) replaces the unit-weight least-squares estimate in the start of the NEXT solve
+ *   jg_dclav_solve         iterates until every lane is finished or at `iteration`: max |rp| <= tol (1 + max |z|), max |rd| <= tol max_j sum_i |H_ij|,
+ *                          gap <= tol (1 + |z - H theta|_1).  Every call starts anew (interior-point iterations are not warm-started)
+ *   jg_dclav_get_angle     theta [batch][n], status [batch] (0 solved, 5 iteration limit, 1 the in-service rows do not observe the grid: every lane,
+ *                          NaN; 3 a zero or non-finite pivot in a later iteration of that lane, frozen at its last iterate), objective [batch],
+ *                          iterations [batch] (each may be NULL)
+ *   jg_dclav_get_residual  z - H theta [batch][m] on in-service rows, 0 elsewhere
+ *   jg_dclav_get_dual      y [batch][m] and the complementarity gap [batch] (each may be NULL)
+ *   jg_dclav_set_branches / jg_dclav_get_flows   as jg_dcse_set_branches / jg_dcse_get_flows
+ *   jg_dclav_factor_solve  the lane-valued factor alone: q [batch][m] the lanes' weights, rhs [batch][n] -> x = (H' Q H)^-1 rhs [batch][n] (the slack's
+ *                          row and column the identity), bad [batch] 1 where the lane met a zero or non-finite pivot.  The handle needs a new solve
+ *   jg_dclav_time_kernel   milliseconds (HIP events) of `reps` runs, every lane running, of: 0 a whole iteration but its update, 1 the assembly, 2 the
+ *                          factorisation, 3 one sweep pair, 4 the row, column and step passes; ms [reps].  The iterates stay
+ * ------------------------------------------------------------------------------------------- */
+int jg_dclav_create(int64_t* h, int64_t n, int64_t m, const int64_t* rowptr, const int64_t* col, const double* val, const int32_t* status, int64_t slack,
+                    double slack_angle, int64_t batch, int device);
+void jg_dclav_destroy(int64_t h);
+int jg_dclav_dims(int64_t h, int64_t* dims);
+int jg_dclav_set_readings(int64_t h, int64_t lane0, int64_t count, const double* z);
+int jg_dclav_set_status(int64_t h, const int32_t* status);
+int jg_dclav_set_initial(int64_t h, const double* theta);
+int jg_dclav_solve(int64_t h, int iteration, double tolerance);
+int jg_dclav_get_angle(int64_t h, double* theta, int32_t* status, double* objective, int32_t* iterations);
+int jg_dclav_get_residual(int64_t h, double* r);
+int jg_dclav_get_dual(int64_t h, double* y, double* gap);
+int jg_dclav_set_branches(int64_t h, int64_t nbr, const int64_t* from, const int64_t* to, const double* admittance, const double* shift);
+int jg_dclav_get_flows(int64_t h, double* from);
+int jg_dclav_factor_solve(int64_t h, const double* q, const double* rhs, double* x, int32_t* bad);
+int jg_dclav_time_kernel(int64_t h, int kernel, int reps, double* ms);
+
+/* ---------------------------------------------------------------------------------------------
  * Symbolic analysis only (no device needed): the static schedule that replaces the symbolic half
  * of `lu`/`klu` (src/backend/utility.jl:470-476, 486-492).  Used by the CPU test-suite to replay
  * and race-check the schedule.  pattern: 0-based int32 block CSR, structurally symmetric, full

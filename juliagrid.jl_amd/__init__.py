@@ -28,6 +28,8 @@ from .stateestimation import (WlsMethod, Normal, LU, KLU, QR, LDLt, LL, Orthogon
 from .dcstateestimation import DcStateEstimation, dcStateEstimation, setReadings_, removed, removeMeasurement_          # noqa: F401
 from .dcoptimalpowerflow import DcOptimalPowerFlow, dcOptimalPowerFlow, setCapability_, setBranchOutages_, outageCosts          # noqa: F401
 from .system import cost_, costTables          # noqa: F401
+from .dclavstateestimation import DcLavStateEstimation, dcLavStateEstimation, dcLavModel          # noqa: F401
+from . import dclavstateestimation          # noqa: F401
 from .montecarlo import MonteCarloPipeline, gatherEstimates, gatherEstimatesDevice, unpackEstimates   # noqa: F401
 from .synthetic import pegaseShaped, case9241synth                          # noqa: F401
 from . import powerflow, stateestimation, dcpowerflow, dcgenerator, dcgroup, dcchance, dccascade, dccritical, dctopology, dcstateestimation, dcoptimalpowerflow, gaussseidel   # noqa: F401
@@ -50,4 +52,5 @@ __all__ = [
     "dcCriticalScreen",
     "dcTopologyScreen", "topologyRuns",
     "DcOptimalPowerFlow", "dcOptimalPowerFlow", "setCapability_", "setBranchOutages_", "outageCosts", "cost_", "costTables",
+    "DcLavStateEstimation", "dcLavStateEstimation", "dcLavModel",
 ]

@@ -253,6 +253,20 @@ def lib():
         "jg_dcopf_get": [C.c_int64, VP, VP, VP, VP],
         "jg_dcopf_time": [C.c_int64, C.c_int, C.c_int, F64P],
         "jg_dcopf_set_branch_outages": [C.c_int64, VP, VP, VP, VP, VP, VP],
+        # DC least-absolute-value state estimation: an int64 token too
+        "jg_dclav_create": [C.POINTER(C.c_int64), C.c_int64, C.c_int64, I64P, I64P, F64P, I32P, C.c_int64, C.c_double, C.c_int64, C.c_int],
+        "jg_dclav_dims": [C.c_int64, I64P],
+        "jg_dclav_set_readings": [C.c_int64, C.c_int64, C.c_int64, F64P],
+        "jg_dclav_set_status": [C.c_int64, I32P],
+        "jg_dclav_set_initial": [C.c_int64, F64P],
+        "jg_dclav_solve": [C.c_int64, C.c_int, C.c_double],
+        "jg_dclav_get_angle": [C.c_int64, VP, VP, VP, VP],
+        "jg_dclav_get_residual": [C.c_int64, F64P],
+        "jg_dclav_get_dual": [C.c_int64, VP, VP],
+        "jg_dclav_set_branches": [C.c_int64, C.c_int64, I64P, I64P, F64P, F64P],
+        "jg_dclav_get_flows": [C.c_int64, F64P],
+        "jg_dclav_factor_solve": [C.c_int64, F64P, F64P, F64P, I32P],
+        "jg_dclav_time_kernel": [C.c_int64, C.c_int, C.c_int, F64P],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -272,6 +286,8 @@ def lib():
     L.jg_gs_destroy.restype = None
     L.jg_dcopf_destroy.argtypes = [C.c_int64]
     L.jg_dcopf_destroy.restype = None
+    L.jg_dclav_destroy.argtypes = [C.c_int64]
+    L.jg_dclav_destroy.restype = None
     L.jg_plan_cache_clear.argtypes = []
     L.jg_plan_cache_clear.restype = None
     L.jg_comm_destroy.argtypes = [VP]
