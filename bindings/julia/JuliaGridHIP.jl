@@ -2268,6 +2268,115 @@ function lavTimeKernel(b::DcLavStateEstimationBatch, kernel::Int, reps::Int = 20
 end
 export DcLavStateEstimationBatch, setRowStatus!, lavFactorSolve, lavTimeKernel
 
+# ---- batched DC Huber / Schweppe-Huber state estimation (jgrid.h: jg_dchuber_*; csrc/jg_dchuber.hip) ---------------------------------------------
+# The reference has no Huber estimator; the rows are those of its DC WLS model (dcseRows / dcseRowStatus above), row i scaled by 1 / sigma_i here, and the
+# bound of row i is threshold * omega[i].  Every lane runs the interior-point method of the LAV batch on the Huber QP.  The C handle is an Int64 token.
+"""
+    DcHuberStateEstimationBatch
+
+What `dcHuberStateEstimation(monitoring, HIP; batch, threshold, omega)` returns: `se` holds the rows of the reference's WLS model, `readings` [row, batch]
+the lanes' means (unscaled), `kappa` the bounds, and after `solve!` `angle` [bus, batch], `status` (0 solved, 5 iteration limit, 1 unobservable, 3 a bad
+pivot in the lane), `objective` (the Huber loss of the scaled residuals), `iterations`, `residual` (unscaled), `weight`, `dual` [row, batch], `gap`.
+"""
+mutable struct DcHuberStateEstimationBatch
+    token::Int64
+    system::PowerSystem
+    monitoring::Measurement
+    se::Any
+    batch::Int64
+    iteration::Int64
+    tolerance::Float64
+    sigma::Vector{Float64}
+    kappa::Vector{Float64}
+    readings::Matrix{Float64}
+    angle::Matrix{Float64}
+    status::Vector{Int32}
+    objective::Vector{Float64}
+    iterations::Vector{Int32}
+    residual::Matrix{Float64}
+    weight::Matrix{Float64}
+    dual::Matrix{Float64}
+    gap::Vector{Float64}
+    from::Matrix{Float64}
+    rowStatus::Vector{Int32}
+    stale::Bool
+end
+function dcHuberStateEstimation(monitoring::Measurement, ::Type{HIP}; batch::Int64 = 1, threshold::Float64 = 1.345, omega::Union{Nothing, Vector{Float64}} = nothing,
+        floor::Float64 = 1e-3, iteration::Int64 = 50, tolerance::Float64 = 1e-8, device::Int64 = 0)
+    system = monitoring.system
+    coefficient, mean, precision, power, index, number, inservice = JuliaGrid.dcStateEstimationWls(system, monitoring)
+    se = (coefficient = coefficient, mean = mean, index = index, number = number, inservice = inservice)
+    rowptr, col, val = dcseRows(system, monitoring, coefficient)
+    status = dcseRowStatus(monitoring, index, number)
+    sigma = [1.0 / sqrt(precision[i, i]) for i in 1:number]
+    scaled = copy(val)
+    for i in 1:number, p in (rowptr[i] + 1):rowptr[i + 1]
+        scaled[p] /= sigma[i]
+    end
+    kappa = threshold .* (omega === nothing ? ones(number) : clamp.(omega, floor, 1.0))
+    slack = system.bus.layout.slack
+    token = Ref{Int64}(0)
+    check(ccall((:jg_dchuber_create, lib), Cint, (Ref{Int64}, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Int64, Float64, Int64, Cint),
+        token, system.bus.number, number, rowptr, col, scaled, status, kappa, sigma, slack, system.bus.voltage.angle[slack], batch, device))
+    b = DcHuberStateEstimationBatch(token[], system, monitoring, se, batch, iteration, tolerance, sigma, kappa, repeat(mean, 1, batch), zeros(system.bus.number, batch),
+        zeros(Int32, batch), zeros(batch), zeros(Int32, batch), zeros(number, batch), zeros(number, batch), zeros(number, batch), zeros(batch),
+        zeros(system.branch.number, batch), status, true)
+    finalizer(x -> (x.token != 0 && ccall((:jg_dchuber_destroy, lib), Cvoid, (Int64,), x.token); x.token = 0), b)
+    br = system.branch
+    check(ccall((:jg_dchuber_set_branches, lib), Cint, (Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}),
+        b.token, br.number, br.layout.from, br.layout.to, system.model.dc.admittance, br.parameter.shiftAngle))
+    return b
+end
+"as dims of the LAV batch"
+function dims(b::DcHuberStateEstimationBatch)
+    d = zeros(Int64, 14)
+    check(ccall((:jg_dchuber_dims, lib), Cint, (Int64, Ptr{Int64}), b.token, d))
+    return d
+end
+"the means of lanes lane0 .. (0-based), a [row, count] matrix in the order of se.mean, unscaled"
+function setReadings!(b::DcHuberStateEstimationBatch, z::Matrix{Float64}; lane0::Int64 = 0)
+    b.readings[:, (lane0 + 1):(lane0 + size(z, 2))] .= z
+    b.stale = true
+    return nothing
+end
+"the status of every row (0 / 1): the next solve! starts anew on the changed set, nothing symbolic is redone"
+function setRowStatus!(b::DcHuberStateEstimationBatch, status::Vector{Int32})
+    check(ccall((:jg_dchuber_set_status, lib), Cint, (Int64, Ptr{Int32}), b.token, status))
+    b.rowStatus .= status
+    return nothing
+end
+"new bounds kappa [row] (threshold * omega, all positive); the next solve! starts anew, as every solve! does"
+function setBounds!(b::DcHuberStateEstimationBatch, kappa::Vector{Float64})
+    check(ccall((:jg_dchuber_set_bounds, lib), Cint, (Int64, Ptr{Float64}), b.token, kappa))
+    b.kappa .= kappa
+    return nothing
+end
+"solve!(analysis) for every lane; every call starts anew (interior-point iterations are not warm-started)"
+function JuliaGrid.solve!(b::DcHuberStateEstimationBatch)
+    if b.stale
+        check(ccall((:jg_dchuber_set_readings, lib), Cint, (Int64, Int64, Int64, Ptr{Float64}), b.token, 0, b.batch, b.readings ./ b.sigma))
+        b.stale = false
+    end
+    check(ccall((:jg_dchuber_solve, lib), Cint, (Int64, Cint, Float64), b.token, b.iteration, b.tolerance))
+    check(ccall((:jg_dchuber_get_angle, lib), Cint, (Int64, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}), b.token, b.angle, b.status, b.objective, b.iterations))
+    check(ccall((:jg_dchuber_get_residual, lib), Cint, (Int64, Ptr{Float64}), b.token, b.residual))
+    check(ccall((:jg_dchuber_get_weight, lib), Cint, (Int64, Ptr{Float64}), b.token, b.weight))
+    check(ccall((:jg_dchuber_get_dual, lib), Cint, (Int64, Ptr{Float64}, Ptr{Float64}), b.token, b.dual, b.gap))
+    return nothing
+end
+"power!(analysis) branch part (dcAnalysis.jl:353-374): from [branch, batch]; to = -from"
+function JuliaGrid.power!(b::DcHuberStateEstimationBatch)
+    check(ccall((:jg_dchuber_get_flows, lib), Cint, (Int64, Ptr{Float64}), b.token, b.from))
+    return nothing
+end
+"milliseconds of `reps` runs (HIP events): 0 a whole iteration but its update, 1 assembly, 2 factorisation, 3 one sweep pair, 4 the row, column and step passes"
+function huberTimeKernel(b::DcHuberStateEstimationBatch, kernel::Int, reps::Int = 20)
+    ms = zeros(Float64, reps)
+    check(ccall((:jg_dchuber_time_kernel, lib), Cint, (Int64, Cint, Cint, Ptr{Float64}), b.token, kernel, reps, ms))
+    return ms
+end
+export DcHuberStateEstimationBatch, dcHuberStateEstimation, setBounds!, huberTimeKernel
+
 # ---- Gauss-Seidel power flow, one scenario per lane (jgrid.h: jg_gs_*; csrc/jg_gs.hip) ---------------------------------------------------
 # gaussSeidel / mismatch! / solve! / powerFlow! (src/powerFlow/acPowerFlow.jl:563-619, 732-764, 985-1041, 1389-1433) for `batch` scenarios of one grid: a
 # sweep is sequential over the buses of a scenario, so a lane runs the reference's update sequence unchanged and a powerFlow! is ONE launch.  The C

@@ -1096,6 +1096,46 @@ int jg_dclav_factor_solve(int64_t h, const double* q, const double* rhs, double*
 int jg_dclav_time_kernel(int64_t h, int kernel, int reps, double* ms);
 
 /* ---------------------------------------------------------------------------------------------
+ * Batched DC Huber / Schweppe-Huber state estimation: the interior-point method of jg_dclav_* on the Huber QP, per lane, on the same lane-valued factor
+ * (csrc/jg_dchuber.hip, csrc/jg_dc_lanefactor.hip).  The handle is an int64 token.
+ *
+ * Every lane solves  min sum_i rho_kappa_i(z_i - h_i theta)  (rho Huber's function: r^2 / 2 up to kappa, kappa |r| - kappa^2 / 2 beyond) over the in-service
+ * rows of ONE coefficient matrix H with readings z of its own, the slack's angle fixed.  The caller scales row i of H and z by 1 / sigma_i, so the
+ * weights are 1; kappa [m] > 0 is shared by the lanes (c for Huber, c omega_i for Schweppe's leverage weights).  Shapes are those of jg_dclav_*.
+ *
+ *   jg_dchuber_create        as jg_dclav_create, with kappa [m] and sigma [m] (NULL: 1; what a scaled residual is multiplied by on its way out)
+ *   jg_dchuber_dims          as jg_dclav_dims: dims [14]
+ *   jg_dchuber_set_readings  scaled z [count][m] of lanes lane0 ..
+ *   jg_dchuber_set_status    status [m]: a changed row set re-runs the start of the next solve and nothing symbolic
+ *   jg_dchuber_set_bounds    kappa [m]: new bounds; the next solve starts anew, as every solve does
+ *   jg_dchuber_solve         iterates until every lane is finished or at `iteration`: max |rp| <= tol (1 + max |z|), max |rd| <= tol max_j sum_i |H_ij|
+ *                            max kappa, gap <= tol (1 + y'y / 2 + kappa'(u + v))
+ *   jg_dchuber_get_angle     theta [batch][n], status [batch] (0 solved, 5 iteration limit, 1 the in-service rows do not observe the grid: every lane,
+ *                            NaN; 3 a zero or non-finite pivot in a later iteration of that lane, frozen at its last iterate), objective [batch] (the
+ *                            Huber loss of the scaled residuals), iterations [batch] (each may be NULL)
+ *   jg_dchuber_get_residual  sigma_i (z_i - h_i theta) [batch][m], the UNSCALED residual, on in-service rows, 0 elsewhere
+ *   jg_dchuber_get_weight    min(1, kappa_i / |scaled residual|) [batch][m], 1 on rows out of service
+ *   jg_dchuber_get_dual      y [batch][m] (the clipped scaled residual at the optimum) and the complementarity gap [batch] (each may be NULL)
+ *   jg_dchuber_set_branches / jg_dchuber_get_flows   as jg_dcse_set_branches / jg_dcse_get_flows
+ *   jg_dchuber_time_kernel   as jg_dclav_time_kernel
+ * ------------------------------------------------------------------------------------------- */
+int jg_dchuber_create(int64_t* h, int64_t n, int64_t m, const int64_t* rowptr, const int64_t* col, const double* val, const int32_t* status, const double* kappa,
+                      const double* sigma, int64_t slack, double slack_angle, int64_t batch, int device);
+void jg_dchuber_destroy(int64_t h);
+int jg_dchuber_dims(int64_t h, int64_t* dims);
+int jg_dchuber_set_readings(int64_t h, int64_t lane0, int64_t count, const double* z);
+int jg_dchuber_set_status(int64_t h, const int32_t* status);
+int jg_dchuber_set_bounds(int64_t h, const double* kappa);
+int jg_dchuber_solve(int64_t h, int iteration, double tolerance);
+int jg_dchuber_get_angle(int64_t h, double* theta, int32_t* status, double* objective, int32_t* iterations);
+int jg_dchuber_get_residual(int64_t h, double* r);
+int jg_dchuber_get_weight(int64_t h, double* w);
+int jg_dchuber_get_dual(int64_t h, double* y, double* gap);
+int jg_dchuber_set_branches(int64_t h, int64_t nbr, const int64_t* from, const int64_t* to, const double* admittance, const double* shift);
+int jg_dchuber_get_flows(int64_t h, double* from);
+int jg_dchuber_time_kernel(int64_t h, int kernel, int reps, double* ms);
+
+/* ---------------------------------------------------------------------------------------------
  * Symbolic analysis only (no device needed): the static schedule that replaces the symbolic half
  * of `lu`/`klu` (src/backend/utility.jl:470-476, 486-492).  Used by the CPU test-suite to replay
  * and race-check the schedule.  pattern: 0-based int32 block CSR, structurally symmetric, full

@@ -30,6 +30,8 @@ from .dcoptimalpowerflow import DcOptimalPowerFlow, dcOptimalPowerFlow, setCapab
 from .system import cost_, costTables          # noqa: F401
 from .dclavstateestimation import DcLavStateEstimation, dcLavStateEstimation, dcLavModel          # noqa: F401
 from . import dclavstateestimation          # noqa: F401
+from .dchuberstateestimation import DcHuberStateEstimation, dcHuberStateEstimation          # noqa: F401
+from . import dchuberstateestimation          # noqa: F401
 from .montecarlo import MonteCarloPipeline, gatherEstimates, gatherEstimatesDevice, unpackEstimates   # noqa: F401
 from .synthetic import pegaseShaped, case9241synth                          # noqa: F401
 from . import powerflow, stateestimation, dcpowerflow, dcgenerator, dcgroup, dcchance, dccascade, dccritical, dctopology, dcstateestimation, dcoptimalpowerflow, gaussseidel   # noqa: F401
@@ -53,4 +55,5 @@ __all__ = [
     "dcTopologyScreen", "topologyRuns",
     "DcOptimalPowerFlow", "dcOptimalPowerFlow", "setCapability_", "setBranchOutages_", "outageCosts", "cost_", "costTables",
     "DcLavStateEstimation", "dcLavStateEstimation", "dcLavModel",
+    "DcHuberStateEstimation", "dcHuberStateEstimation",
 ]

@@ -267,6 +267,20 @@ def lib():
         "jg_dclav_get_flows": [C.c_int64, F64P],
         "jg_dclav_factor_solve": [C.c_int64, F64P, F64P, F64P, I32P],
         "jg_dclav_time_kernel": [C.c_int64, C.c_int, C.c_int, F64P],
+        # DC Huber / Schweppe-Huber state estimation: an int64 token too
+        "jg_dchuber_create": [C.POINTER(C.c_int64), C.c_int64, C.c_int64, I64P, I64P, F64P, I32P, F64P, F64P, C.c_int64, C.c_double, C.c_int64, C.c_int],
+        "jg_dchuber_dims": [C.c_int64, I64P],
+        "jg_dchuber_set_readings": [C.c_int64, C.c_int64, C.c_int64, F64P],
+        "jg_dchuber_set_status": [C.c_int64, I32P],
+        "jg_dchuber_set_bounds": [C.c_int64, F64P],
+        "jg_dchuber_solve": [C.c_int64, C.c_int, C.c_double],
+        "jg_dchuber_get_angle": [C.c_int64, VP, VP, VP, VP],
+        "jg_dchuber_get_residual": [C.c_int64, F64P],
+        "jg_dchuber_get_weight": [C.c_int64, F64P],
+        "jg_dchuber_get_dual": [C.c_int64, VP, VP],
+        "jg_dchuber_set_branches": [C.c_int64, C.c_int64, I64P, I64P, F64P, F64P],
+        "jg_dchuber_get_flows": [C.c_int64, F64P],
+        "jg_dchuber_time_kernel": [C.c_int64, C.c_int, C.c_int, F64P],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -288,6 +302,8 @@ def lib():
     L.jg_dcopf_destroy.restype = None
     L.jg_dclav_destroy.argtypes = [C.c_int64]
     L.jg_dclav_destroy.restype = None
+    L.jg_dchuber_destroy.argtypes = [C.c_int64]
+    L.jg_dchuber_destroy.restype = None
     L.jg_plan_cache_clear.argtypes = []
     L.jg_plan_cache_clear.restype = None
     L.jg_comm_destroy.argtypes = [VP]

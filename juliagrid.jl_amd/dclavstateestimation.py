@@ -224,10 +224,15 @@ def updatePmu_(an: DcLavStateEstimation, label, angle=None, statusAngle=None):
 def power_(an: DcLavStateEstimation):
     """power!(analysis) for every lane, as dcstateestimation.power_: branch flows on the device (the DC flow kernel); injection = B theta + shiftPower +
     shunt conductance and supply = injection + demand on the host; generator by the rule of the DC power flow."""
+    _power(an, _lib.lib().jg_dclav_get_flows)
+
+
+def _power(an, get_flows):
+    """power_ of an analysis whose handle delivers its branch flows through `get_flows` (dchuberstateestimation shares it)"""
     sysm = an.system
     bus, gen, br, dc = sysm.bus, sysm.generator, sysm.branch, sysm.model.dc
     fr = np.zeros((an.batch, br.number))
-    _lib.check(_lib.lib().jg_dclav_get_flows(an._h, fr.reshape(-1)))
+    _lib.check(get_flows(an._h, fr.reshape(-1)))
     th = np.atleast_2d(an.voltage.angle)
     B = dc.nodalMatrix
     col_of = np.repeat(np.arange(bus.number), np.diff(B.colptr))
