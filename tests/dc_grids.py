@@ -11,6 +11,7 @@ replay of the factor's schedule -- the helper of tests/test_dc_grids_cpu.py and 
                                       form of dcModel_'s nodal matrix (structurally symmetric, diagonal included), policy 255 << 8 (no top tasks)
   launches(widths)                    build_sweep's launch rule restated: a run of levels of at most 16 rows is one chain launch, a wider level its own
   classes(levels)                     the branches of the sweep kernels these levels reach, as a set of names (COVERAGE lists all of them)
+  plan_of / plan_levels / replay_plan the three above for any analysed pattern and its row-form values (sweep_levels and replay go through them)
   replay(table, rhs)                  the schedule replayed in numpy: factorise level by level from t_ptr / t_a / t_b / t_d / e_level, sweep level by
                                       level over the padded lists (pad column n, value 0).  Every entry and every row carries a "final" flag that is
                                       set when its level is over; a term that reads a value that is not final raises ScheduleError
@@ -153,7 +154,7 @@ def _plan(t, jg=None):
     jg.dcModel_(s)
     B = s.model.dc.nodalMatrix
     n = s.bus.number
-    plan = jg._lib.Plan(n, B.colptr - 1, B.rowval - 1, policy=DC_POLICY_NO_TOP)
+    plan = plan_of(n, B.colptr - 1, B.rowval - 1, jg)
     # the pattern is structurally symmetric: entry q of the row form is the entry (column, row) of the CSC arrays, value by value
     M = sp.csc_matrix((np.asarray(B.nzval, dtype=np.float64), np.asarray(B.rowval) - 1, np.asarray(B.colptr) - 1), shape=(n, n))
     At = M.T.tocsc()                                               # CSC of the transpose: column r of it holds row r of M in ascending columns
@@ -175,15 +176,24 @@ def _forward_levels(n, l_ptr, l_col):
     return flev
 
 
-def sweep_levels(t, jg=None):
-    """dict(forward, backward: rows per level; forwardLaunches, backwardLaunches; lower, upper: list lengths per row; perm)"""
-    plan = _plan(t, jg)[0]
+def plan_of(n, rowptr, col, jg=None):
+    """the analysis of a structurally symmetric pattern with a full diagonal (row form, 0-based), asked for as the DC handles ask: no top tasks"""
+    return _jg(jg)._lib.Plan(n, rowptr, col, policy=DC_POLICY_NO_TOP)
+
+
+def plan_levels(plan):
+    """sweep_levels of an analysis, whatever matrix it is of (tests/dc_lane_grids.py: the gain pattern of the lane-valued factor)"""
     n = plan.n
     l_ptr, l_col, u_ptr = plan.get("l_ptr"), plan.get("l_col"), plan.get("u_ptr")
     flev, blev = _forward_levels(n, l_ptr, l_col), plan.get("bwd_level").astype(np.int64)
     fw, bw = np.bincount(flev, minlength=2)[1:], np.bincount(blev, minlength=2)[1:]
     return dict(forward=fw, backward=bw, forwardLaunches=launches(fw), backwardLaunches=launches(bw), lower=np.diff(l_ptr), upper=np.diff(u_ptr),
                 perm=plan.get("perm").copy(), terms=int(((np.diff(l_ptr) + DC_T - 1) // DC_T * DC_T).sum() + ((np.diff(u_ptr) + DC_T - 1) // DC_T * DC_T).sum()))
+
+
+def sweep_levels(t, jg=None):
+    """dict(forward, backward: rows per level; forwardLaunches, backwardLaunches; lower, upper: list lengths per row; perm)"""
+    return plan_levels(_plan(t, jg)[0])
 
 
 def _wpi(cnt):
@@ -254,10 +264,8 @@ def _sweep(n, level, pp, pc, val, start, W, final):
         raise ScheduleError("rows without a level")
 
 
-def replay(t, rhs=None, jg=None):
-    """the angles [n] (or [n, m] for rhs [n, m]) the schedule gives: the slack's angle added, as dc_reference.solve.  rhs: bus order, default the
-    table's own right-hand side"""
-    plan, A, slack, s = _plan(t, jg)
+def replay_plan(plan, A, r):
+    """the schedule of `plan` replayed on the row-form values A of its pattern: x = M^-1 r ([n] or [n, k]), both in the matrix's own order"""
     n = plan.n
     g = plan.get
     perm, e_src, t_ptr, t_a, t_b, t_d, e_level, diag = g("perm"), g("e_src"), g("t_ptr"), g("t_a"), g("t_b"), g("t_d"), g("e_level"), g("diag")
@@ -285,10 +293,6 @@ def replay(t, rhs=None, jg=None):
     if not (np.isfinite(piv).all() and (piv != 0).all()):
         raise ScheduleError("zero or non-finite pivot")
     dinv = 1.0 / piv
-    if rhs is None:
-        rhs = R.rhs_of(t, R.assemble(t)[2])
-    r = np.array(rhs, dtype=np.float64)
-    r[slack] = 0.0
     l_ptr, l_col = g("l_ptr"), g("l_col")
     fp, fc, fe, fd = _padded(n, ne, l_ptr, g("l_ent"), l_col, False)
     bp, bc, be, bd = _padded(n, ne, g("u_ptr"), g("u_ent"), g("u_col"), True)
@@ -301,8 +305,20 @@ def replay(t, rhs=None, jg=None):
     Y = W.copy()
     final[:n] = False                                              # the backward sweep overwrites W in place: a row not yet final holds the forward value
     _sweep(n, g("bwd_level").astype(np.int64), bp, bc, bval, lambda k: Y[k] * dinv[k], W, final)
-    th = np.zeros_like(r)
-    th[perm] = W[:n]
+    x = np.zeros_like(r)
+    x[perm] = W[:n]
+    return x
+
+
+def replay(t, rhs=None, jg=None):
+    """the angles [n] (or [n, m] for rhs [n, m]) the schedule gives: the slack's angle added, as dc_reference.solve.  rhs: bus order, default the
+    table's own right-hand side"""
+    plan, A, slack, s = _plan(t, jg)
+    if rhs is None:
+        rhs = R.rhs_of(t, R.assemble(t)[2])
+    r = np.array(rhs, dtype=np.float64)
+    r[slack] = 0.0
+    th = replay_plan(plan, A, r)
     th = th + float(np.asarray(t["bus_va"], dtype=np.float64)[slack])
     th[slack] = float(np.asarray(t["bus_va"], dtype=np.float64)[slack])
     return th

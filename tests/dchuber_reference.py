@@ -99,7 +99,9 @@ def huber_ipm(H, z, kappa, on=None, slack=0, iteration=50, tolerance=1e-8):
         rd = -(H.T @ y)
         gap = float((u * (k - y) + v * (k + y))[on].sum())
         obj = float((0.5 * y * y + k * (u + v))[on].sum())
-        tests = (np.abs(rp).max() / (tolerance * (1.0 + np.abs(z).max())), np.abs(rd).max() / (tolerance * hnorm * kmax), gap / (tolerance * (1.0 + obj)))
+        dual, dual_bound = np.abs(rd).max(), tolerance * hnorm * kmax                # (no column but the slack's: both are 0, and the device's test 0 <= 0 holds)
+        tests = (np.abs(rp).max() / (tolerance * (1.0 + np.abs(z).max())), 0.0 if dual == 0.0 else (dual / dual_bound if dual_bound > 0.0 else np.inf),
+                 gap / (tolerance * (1.0 + obj)))
         margins.append(max(tests))
         if max(tests) <= 1.0:
             status = 0

@@ -42,14 +42,16 @@ def _boundary(x, dx):
 
 
 def lav_ipm(H, z, on=None, slack=0, iteration=50, tolerance=1e-8, theta0=None):
-    """-> NS(theta, u, v, y, status, iterations, objective, gap, residual).  status 0 solved, 5 iteration limit, 1 unobservable, 3 a non-finite pivot."""
+    """-> NS(theta, u, v, y, status, iterations, objective, gap, residual, margins).  status 0 solved, 5 iteration limit, 1 unobservable, 3 a non-finite
+    pivot.  margins: per verdict, the largest of the three deciding quantities over its bound (a zero quantity on a zero bound counts 0)."""
     m, n = H.shape
     on = np.ones(m, dtype=bool) if on is None else np.asarray(on, dtype=bool)
     H = H * on[:, None]
     z = np.where(on, z, 0.0)
     m_in = int(on.sum())
     hnorm = float(np.abs(H).sum(axis=0).max())
-    nan = NS(theta=np.full(n, np.nan), u=None, v=None, y=np.full(m, np.nan), status=1, iterations=0, objective=np.nan, gap=np.nan, residual=np.full(m, np.nan))
+    nan = NS(theta=np.full(n, np.nan), u=None, v=None, y=np.full(m, np.nan), status=1, iterations=0, objective=np.nan, gap=np.nan, residual=np.full(m, np.nan),
+             margins=[])
     G = _gain(H, on.astype(np.float64), slack)
     d = np.linalg.eigvalsh(G)
     if not (d.min() > 1e-12 * d.max()):
@@ -61,13 +63,15 @@ def lav_ipm(H, z, on=None, slack=0, iteration=50, tolerance=1e-8, theta0=None):
     u = np.where(on, np.maximum(r0, 0.0) + s, 0.0)
     v = np.where(on, np.maximum(-r0, 0.0) + s, 0.0)
     y = np.zeros(m)
-    status, it = 5, 0
+    status, it, margins = 5, 0, []
     while True:
         r = z - H @ theta
         rp = np.where(on, r - u + v, 0.0)
         rd = -(H.T @ y)
         gap = float((u * (1.0 - y) + v * (1.0 + y))[on].sum())
         obj = float(np.abs(r[on]).sum())
+        tests = ((np.abs(rp).max(), tolerance * (1.0 + np.abs(z).max())), (np.abs(rd).max(), tolerance * hnorm), (gap, tolerance * (1.0 + obj)))
+        margins.append(max(0.0 if a == 0.0 else (a / b if b > 0.0 else np.inf) for a, b in tests))
         if (np.abs(rp).max() <= tolerance * (1.0 + np.abs(z).max()) and np.abs(rd).max() <= tolerance * hnorm and gap <= tolerance * (1.0 + obj)):
             status = 0
             break
@@ -104,7 +108,7 @@ def lav_ipm(H, z, on=None, slack=0, iteration=50, tolerance=1e-8, theta0=None):
         a = min(1.0, STEP_BACK * min(_boundary(u[on], du[on]), _boundary(v[on], dv[on]), _boundary(1.0 - y[on], -dy[on]), _boundary(1.0 + y[on], dy[on])))
         theta, u, v, y = theta + a * dth, u + a * du, v + a * dv, y + a * dy
         it += 1
-    return NS(theta=theta, u=u, v=v, y=y, status=status, iterations=it, objective=obj, gap=gap, residual=np.where(on, r, 0.0))
+    return NS(theta=theta, u=u, v=v, y=y, status=status, iterations=it, objective=obj, gap=gap, residual=np.where(on, r, 0.0), margins=margins)
 
 
 def lav_linprog(H, z, on=None, slack=0):
