@@ -2513,6 +2513,12 @@ function setInitialPoint!(b::GaussSeidelBatch, magnitude::VecOrMat{Float64}, ang
     pullVoltage!(b)
     return nothing
 end
+"method.voltage = `voltage` bit for bit, [bus] for every scenario or [bus, batch]: the state of a batch moved to a new handle"
+function setVoltage!(b::GaussSeidelBatch, voltage::VecOrMat{ComplexF64})
+    check(ccall((:jg_gs_set_voltage_rect, lib), Cint, (Int64, Ptr{Float64}, Ptr{Float64}, Int64), b.token, real.(voltage), imag.(voltage), ndims(voltage) == 1 ? 0 : size(voltage, 1)))
+    pullVoltage!(b)
+    return nothing
+end
 "method.voltage[idx] = magnitude[s] * cis(angle[s]) in every scenario s: what _updateBus! (bus.jl:350-362) and _updateGenerator! (generator.jl:425-430) set"
 function setBusVoltage!(b::GaussSeidelBatch, idx::Int64, magnitude::Vector{Float64}, angle::Vector{Float64})
     check(ccall((:jg_gs_set_bus_voltage, lib), Cint, (Int64, Int64, Ptr{Float64}, Ptr{Float64}), b.token, idx, magnitude, angle))

@@ -975,6 +975,8 @@ int jg_dcse_topology_time(int64_t h, int kernel, int reps, double* ms);
  *                        one [n] pair for every lane of the range, stride n: [count][n]
  *   jg_gs_set_setpoint   setpoint [n] again, after updateGenerator!(...; magnitude) (src/powerSystem/generator.jl:410-431)
  *   jg_gs_set_voltage    method.voltage = magnitude * cis(angle) (:576, setInitialPoint! :1243-1245, :1289-1291); stride 0: one [n] pair for all lanes
+ *   jg_gs_set_voltage_rect  method.voltage = re + i im, bit for bit: what moves the state of a live analysis to a new handle when the pattern of the
+ *                        nodal matrix grew (addBranch! between two buses without an entry); strides as jg_gs_set_voltage
  *   jg_gs_set_bus_voltage  method.voltage[bus] = magnitude[s] * cis(angle[s]) of every lane s, the other buses untouched: _updateBus!
  *                        (src/powerSystem/bus.jl:350-362) and _updateGenerator! (generator.jl:425-430)
  *   jg_gs_get_voltage    magnitude, angle = absang(method.voltage) (:1012, :1035) and / or method.voltage itself as re, im; either pair may be NULL
@@ -996,6 +998,7 @@ int jg_gs_set_ybus(int64_t h, const double* yt);
 int jg_gs_set_injection(int64_t h, int64_t lane0, int64_t count, const double* active, const double* reactive, int64_t stride);
 int jg_gs_set_setpoint(int64_t h, const double* setpoint);
 int jg_gs_set_voltage(int64_t h, const double* magnitude, const double* angle, int64_t stride);
+int jg_gs_set_voltage_rect(int64_t h, const double* re, const double* im, int64_t stride);
 int jg_gs_set_bus_voltage(int64_t h, int64_t bus, const double* magnitude, const double* angle);
 int jg_gs_get_voltage(int64_t h, double* magnitude, double* angle, double* re, double* im);
 int jg_gs_set_outages(int64_t h, int64_t lane0, int64_t count, const int64_t* position, const double* delta);

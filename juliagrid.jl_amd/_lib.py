@@ -234,6 +234,7 @@ def lib():
         "jg_gs_set_injection": [C.c_int64, C.c_int64, C.c_int64, F64P, F64P, C.c_int64],
         "jg_gs_set_setpoint": [C.c_int64, F64P],
         "jg_gs_set_voltage": [C.c_int64, F64P, F64P, C.c_int64],
+        "jg_gs_set_voltage_rect": [C.c_int64, F64P, F64P, C.c_int64],
         "jg_gs_set_bus_voltage": [C.c_int64, C.c_int64, F64P, F64P],
         "jg_gs_get_voltage": [C.c_int64, VP, VP, VP, VP],
         "jg_gs_set_outages": [C.c_int64, C.c_int64, C.c_int64, I64P, F64P],

@@ -336,8 +336,14 @@ int jg_gs_set_voltage(int64_t h, const double* magnitude, const double* angle, i
     const size_t m = (size_t)d->n * (stride ? (size_t)d->batch : 1);
     std::vector<double> re(m), im(m);
     for (size_t k = 0; k < m; ++k) { re[k] = magnitude[k] * std::cos(angle[k]); im[k] = magnitude[k] * std::sin(angle[k]); }   // magnitude * cis(angle)
-    DC_RET(jg::put_lanes(d, d->vr, 0, d->batch, re.data(), stride));
-    DC_RET(jg::put_lanes(d, d->vi, 0, d->batch, im.data(), stride));
+    return jg_gs_set_voltage_rect(h, re.data(), im.data(), stride);
+}
+
+int jg_gs_set_voltage_rect(int64_t h, const double* re, const double* im, int64_t stride) {
+    GS_ENTER(h);
+    if (!re || !im || (stride != 0 && stride != d->n)) return api_fail(1, "jg_gs_set_voltage_rect: bad argument");
+    DC_RET(jg::put_lanes(d, d->vr, 0, d->batch, re, stride));
+    DC_RET(jg::put_lanes(d, d->vi, 0, d->batch, im, stride));
     return 0;
 }
 

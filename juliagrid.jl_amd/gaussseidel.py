@@ -156,10 +156,11 @@ def setOutages_(an: GaussSeidelPowerFlow, labels, scenario0: int = 0):
         return
     if lab.min() < 0 or lab.max() > an.system.branch.number:
         raise IndexError("setOutages_: branch label out of range")
-    tptr, tdy = transposedOutageTable(an.system)
     on = lab > 0
-    ptr = np.where(on[:, None], tptr[np.maximum(lab, 1) - 1], 0)
-    dy = np.where(on[:, None], tdy[np.maximum(lab, 1) - 1], 0.0)
+    ptr, dy = np.zeros((lab.size, 4), dtype=np.int64), np.zeros((lab.size, 4), dtype=np.complex128)
+    if on.any():                                                  # (a grid without a branch has no table to index)
+        tptr, tdy = transposedOutageTable(an.system)
+        ptr[on], dy[on] = tptr[lab[on] - 1], tdy[lab[on] - 1]
     _lib.check(_lib.lib().jg_gs_set_outages(an._h, int(scenario0), lab.size, np.ascontiguousarray(ptr.reshape(-1)), _reim(np.ascontiguousarray(dy.reshape(-1)))))
     an._outage_labels[scenario0:scenario0 + lab.size] = lab
 
@@ -174,13 +175,17 @@ def _upload_ybus(an: GaussSeidelPowerFlow):
 
 
 def _rebuild(an: GaussSeidelPowerFlow):
-    """The Ybus pattern changed under a live analysis: a new handle, and the state moves over -- voltages, injections, outages"""
+    """The Ybus pattern changed under a live analysis (addBranch_ between two buses that had no entry): a new handle, and the state moves over --
+    voltages, injections, outages.  The reference goes on here: its solve! reads the system's nodal matrix, _addBranch! (branch.jl:190-192) only checks
+    the bus types and syncTopology! takes the new topology revision, so method.voltage stays what it was.  The voltages therefore move as re / im, bit
+    for bit, not through magnitude and angle."""
     an._pull_voltage()
-    vm, va = np.atleast_2d(an.voltage.magnitude), np.atleast_2d(an.voltage.angle)
+    v = np.atleast_2d(an.method.voltage)
     an.close()
     an._create()
     _lib.check(_lib.lib().jg_gs_set_injection(an._h, 0, an.batch, an._P.reshape(-1), an._Q.reshape(-1), an.system.bus.number))
-    _push_voltage(an, vm, va)
+    _lib.check(_lib.lib().jg_gs_set_voltage_rect(an._h, np.ascontiguousarray(v.real).reshape(-1), np.ascontiguousarray(v.imag).reshape(-1), an.system.bus.number))
+    an._pull_voltage()
     if np.any(an._outage_labels):
         setOutages_(an, an._outage_labels)
 

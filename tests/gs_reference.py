@@ -129,4 +129,5 @@ def run(g, yt, v, P, Q, iteration, tolerance):
 def margins_hold(out, tolerance, rel=1e-6):
     """every converged lane stopped clear of the tolerance on both sides: its last check at least `rel` below it, the check before at least `rel` above"""
     c = out.status == 0
-    return bool(np.all(np.maximum(out.stop[0], out.stop[1])[c] <= tolerance * (1 - rel)) and np.all(out.before[c] >= tolerance * (1 + rel)))
+    iterated = c & (out.iteration > 0)                            # a lane that converged at its first check has no check before it
+    return bool(np.all(np.maximum(out.stop[0], out.stop[1])[c] <= tolerance * (1 - rel)) and np.all(out.before[iterated] >= tolerance * (1 + rel)))
