@@ -2268,6 +2268,138 @@ function lavTimeKernel(b::DcLavStateEstimationBatch, kernel::Int, reps::Int = 20
 end
 export DcLavStateEstimationBatch, setRowStatus!, lavFactorSolve, lavTimeKernel
 
+# ---- batched PMU least-absolute-value state estimation (jgrid.h: jg_pmulav_*; csrc/jg_pmulav.hip) ------------------------------------------------
+# pmuLavStateEstimation / solve! (src/stateEstimation/pmuStateEstimation.jl:223-338, 474-512) for `batch` realisations of one PMU set: the iteration of
+# the DC LAV batch without a fixed state, on the coefficient matrix of the reference's WLS model.  Readings are polar.  The C handle is an Int64 token.
+"""
+    PmuLavStateEstimationBatch
+
+What `pmuLavStateEstimation(monitoring, HIP; batch)` returns: `magnitudeReading`, `angleReading` [pmu, batch] the lanes' phasors, and after `solve!`
+`magnitude`, `angle` [bus, batch], `status` (0 solved, 5 iteration limit, 1 a state no in-service row touches, 3 a bad pivot in the lane), `objective`,
+`iterations`, `residual`, `dual` [2 pmu, batch] and `gap` per lane.
+"""
+mutable struct PmuLavStateEstimationBatch
+    token::Int64
+    system::PowerSystem
+    monitoring::Measurement
+    batch::Int64
+    iteration::Int64
+    tolerance::Float64
+    magnitudeReading::Matrix{Float64}
+    angleReading::Matrix{Float64}
+    magnitude::Matrix{Float64}
+    angle::Matrix{Float64}
+    status::Vector{Int32}
+    objective::Vector{Float64}
+    iterations::Vector{Int32}
+    residual::Matrix{Float64}
+    dual::Matrix{Float64}
+    gap::Vector{Float64}
+    stale::Bool
+    branches::Bool
+end
+"the status of every PMU as the LAV model reads it: in the model only with both channels in service (pmuStateEstimation.jl:277, 304-306)"
+pmuLavStatus(monitoring::Measurement) = Int32.(monitoring.pmu.magnitude.status .* monitoring.pmu.angle.status)
+function JuliaGrid.pmuLavStateEstimation(monitoring::Measurement, ::Type{HIP}; batch::Int64 = 1, iteration::Int64 = 50, tolerance::Float64 = 1e-8, device::Int64 = 0)
+    system = monitoring.system
+    pmu = monitoring.pmu
+    wls = JuliaGrid.pmuStateEstimation(monitoring)
+    Ht = sparse(transpose(wls.method.coefficient))                  # CSC of H' = CSR of H, columns of a row ascending
+    rowptr = Int64.(Ht.colptr .- 1)
+    col = Int64.(Ht.rowval)
+    token = Ref{Int64}(0)
+    check(ccall((:jg_pmulav_create, lib), Cint, (Ref{Int64}, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int32}, Int64, Cint),
+        token, system.bus.number, pmu.number, rowptr, col, Ht.nzval, pmuLavStatus(monitoring), batch, device))
+    b = PmuLavStateEstimationBatch(token[], system, monitoring, batch, iteration, tolerance, repeat(pmu.magnitude.mean, 1, batch), repeat(pmu.angle.mean, 1, batch),
+        zeros(system.bus.number, batch), zeros(system.bus.number, batch), zeros(Int32, batch), zeros(batch), zeros(Int32, batch), zeros(2 * pmu.number, batch),
+        zeros(2 * pmu.number, batch), zeros(batch), true, false)
+    finalizer(x -> (x.token != 0 && ccall((:jg_pmulav_destroy, lib), Cvoid, (Int64,), x.token); x.token = 0), b)
+    return b
+end
+"{buses, pmus, batch, ld, entries of G, factor entries, factorisation levels, forward levels, backward levels, sweep launches, bytes per lane, in-service PMUs, factorisations, iterations of the last solve}"
+function dims(b::PmuLavStateEstimationBatch)
+    d = zeros(Int64, 14)
+    check(ccall((:jg_pmulav_dims, lib), Cint, (Int64, Ptr{Int64}), b.token, d))
+    return d
+end
+"the phasors of lanes lane0 .. (0-based): `magnitude`, `angle` [pmu, count] in device order"
+function setReadings!(b::PmuLavStateEstimationBatch, magnitude::Matrix{Float64}, angle::Matrix{Float64}; lane0::Int64 = 0)
+    b.magnitudeReading[:, (lane0 + 1):(lane0 + size(magnitude, 2))] .= magnitude
+    b.angleReading[:, (lane0 + 1):(lane0 + size(angle, 2))] .= angle
+    check(ccall((:jg_pmulav_set_readings, lib), Cint, (Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}), b.token, lane0, size(magnitude, 2), magnitude, angle))
+    return nothing
+end
+"the status of every PMU (0 / 1): the next solve! starts anew on the changed set, nothing symbolic is redone"
+function setPmuStatus!(b::PmuLavStateEstimationBatch, status::Vector{Int32})
+    check(ccall((:jg_pmulav_set_status, lib), Cint, (Int64, Ptr{Int32}), b.token, status))
+    return nothing
+end
+"one positive scale per row [2 pmu], the same for every lane: what a row's reading is multiplied by (the rows of H handed to the constructor are the caller's)"
+function setRowScale!(b::PmuLavStateEstimationBatch, scale::Vector{Float64})
+    check(ccall((:jg_pmulav_set_scale, lib), Cint, (Int64, Ptr{Float64}), b.token, scale))
+    return nothing
+end
+"setInitialPoint!: `magnitude`, `angle` [bus, batch] replace the unit-weight least-squares estimate in the start of the NEXT solve!"
+function JuliaGrid.setInitialPoint!(b::PmuLavStateEstimationBatch, magnitude::Matrix{Float64}, angle::Matrix{Float64})
+    check(ccall((:jg_pmulav_set_initial, lib), Cint, (Int64, Ptr{Float64}, Ptr{Float64}), b.token, magnitude, angle))
+    return nothing
+end
+"solve!(analysis) for every lane; every call starts anew (interior-point iterations are not warm-started)"
+function JuliaGrid.solve!(b::PmuLavStateEstimationBatch)
+    if b.stale
+        check(ccall((:jg_pmulav_set_readings, lib), Cint, (Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}), b.token, 0, b.batch, b.magnitudeReading, b.angleReading))
+        b.stale = false
+    end
+    check(ccall((:jg_pmulav_solve, lib), Cint, (Int64, Cint, Float64), b.token, b.iteration, b.tolerance))
+    check(ccall((:jg_pmulav_get_voltage, lib), Cint, (Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}),
+        b.token, b.magnitude, b.angle, b.status, b.objective, b.iterations))
+    check(ccall((:jg_pmulav_get_residual, lib), Cint, (Int64, Ptr{Float64}), b.token, b.residual))
+    check(ccall((:jg_pmulav_get_dual, lib), Cint, (Int64, Ptr{Float64}, Ptr{Float64}), b.token, b.dual, b.gap))
+    return nothing
+end
+"power! and current! of every lane: [2, branch, batch] from, to and series currents (magnitude, angle), from, to, series and charging powers (active, reactive) and [2, bus, batch] the injected power"
+function pmuLavFlows(b::PmuLavStateEstimationBatch)
+    system = b.system
+    br = system.branch
+    ac = system.model.ac
+    if !b.branches
+        tij = (1.0 ./ br.parameter.turnsRatio) .* exp.(-im .* br.parameter.shiftAngle)
+        param = zeros(Float64, 16, br.number)
+        for (c, z) in enumerate((ac.nodalFromFrom, ac.nodalFromTo, ac.nodalToFrom, ac.nodalToTo, ac.admittance, tij))
+            param[2 * c - 1, :] .= real.(z)
+            param[2 * c, :] .= imag.(z)
+        end
+        param[13, :] .= br.parameter.conductance
+        param[14, :] .= br.parameter.susceptance
+        param[15, :] .= 1.0 ./ br.parameter.turnsRatio
+        check(ccall((:jg_pmulav_set_branches, lib), Cint, (Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int8}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+            b.token, br.number, br.layout.from, br.layout.to, br.layout.status, param, system.bus.shunt.conductance, system.bus.shunt.susceptance))
+        b.branches = true
+    end
+    out = [zeros(Float64, 2, br.number, b.batch) for _ in 1:7]
+    injection = zeros(Float64, 2, system.bus.number, b.batch)
+    check(ccall((:jg_pmulav_get_flows, lib), Cint, (Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        b.token, out[1], out[2], out[3], out[4], out[5], out[6], out[7], injection))
+    return (fromCurrent = out[1], toCurrent = out[2], seriesCurrent = out[3], from = out[4], to = out[5], series = out[6], charging = out[7], injection = injection)
+end
+"the devices whose phasor residual exceeds `threshold` (per unit): rho and flag [pmu, batch], the count and the device (0-based) of the largest rho per lane"
+function pmuLavSuspect(b::PmuLavStateEstimationBatch, threshold::Float64)
+    number = b.monitoring.pmu.number
+    rho = zeros(Float64, number, b.batch)
+    flag = zeros(Int32, number, b.batch)
+    count = zeros(Int32, b.batch)
+    worst = zeros(Int32, b.batch)
+    check(ccall((:jg_pmulav_suspect, lib), Cint, (Int64, Float64, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}), b.token, threshold, rho, flag, count, worst))
+    return rho, flag, count, worst
+end
+"milliseconds of `reps` runs (HIP events): 0 .. 4 as lavTimeKernel, 5 polar to rectangular readings, 6 rectangular to polar voltages, 7 the branch and bus pass, 8 the suspect pass"
+function pmuLavTimeKernel(b::PmuLavStateEstimationBatch, kernel::Int, reps::Int = 20)
+    ms = zeros(Float64, reps)
+    check(ccall((:jg_pmulav_time_kernel, lib), Cint, (Int64, Cint, Cint, Ptr{Float64}), b.token, kernel, reps, ms))
+    return ms
+end
+export PmuLavStateEstimationBatch, pmuLavStatus, setPmuStatus!, setRowScale!, pmuLavFlows, pmuLavSuspect, pmuLavTimeKernel
+
 # ---- batched DC Huber / Schweppe-Huber state estimation (jgrid.h: jg_dchuber_*; csrc/jg_dchuber.hip) ---------------------------------------------
 # The reference has no Huber estimator; the rows are those of its DC WLS model (dcseRows / dcseRowStatus above), row i scaled by 1 / sigma_i here, and the
 # bound of row i is threshold * omega[i].  Every lane runs the interior-point method of the LAV batch on the Huber QP.  The C handle is an Int64 token.

@@ -1139,6 +1139,55 @@ int jg_dchuber_get_flows(int64_t h, double* from);
 int jg_dchuber_time_kernel(int64_t h, int kernel, int reps, double* ms);
 
 /* ---------------------------------------------------------------------------------------------
+ * Batched PMU least-absolute-value state estimation: the interior-point method of jg_dclav_* on the linear phasor model, WITHOUT a fixed state, per
+ * lane (csrc/jg_pmulav.hip, csrc/jg_dclav.hip, csrc/jg_dc_lanefactor.hip).  The handle is an int64 token.
+ *
+ * Every lane solves  min sum_i |z_i - h_i x|  over the in-service rows of ONE coefficient matrix H [2 pmus][2 buses] with phasor readings of its own.
+ * States: re(1 .. buses) then im(1 .. buses).  Rows: 2 i the real, 2 i + 1 the imaginary part of PMU i (0-based); status is per PMU (a PMU whose magnitude
+ * or angle channel is off leaves with both rows).  Arrays are [batch][...] on the host.
+ *
+ *   jg_pmulav_create        rows of H as CSR (columns of a row ascending, 1-based), status [pmus] 0 / 1.  The device memory of `batch` lanes is computed
+ *                           first and refused with the sizes (code 5) before anything is allocated
+ *   jg_pmulav_dims          dims [14] as jg_dclav_dims, with buses, pmus in [0], [1] and the in-service PMUs in [11]
+ *   jg_pmulav_set_readings  magnitude, angle [count][pmus] of lanes lane0 ..: z_re = magnitude cos(angle), z_im = magnitude sin(angle) are formed on the device
+ *   jg_pmulav_set_status    status [pmus]: a changed set re-runs the start of the next solve and nothing symbolic
+ *   jg_pmulav_set_scale     scale [2 pmus] > 0, ONE for every lane: what a row's reading is multiplied by (the caller scales the rows of H); the residuals
+ *                           of jg_pmulav_get_residual and the objective are the scaled rows', rho of jg_pmulav_suspect is unscaled
+ *   jg_pmulav_set_initial   magnitude, angle [batch][buses] replace the unit-weight least-squares estimate in the start of the NEXT solve
+ *   jg_pmulav_solve         as jg_dclav_solve
+ *   jg_pmulav_get_voltage   magnitude, angle [batch][buses], status [batch] (0 solved, 5 iteration limit, 1 a state no in-service row touches -- an exact
+ *                           zero pivot of the unit-weight start: every lane, NaN; 3 a zero or non-finite pivot in a later iteration of that lane),
+ *                           objective [batch], iterations [batch] (each may be NULL)
+ *   jg_pmulav_get_residual  z - H x [batch][2 pmus] on in-service rows, 0 elsewhere
+ *   jg_pmulav_get_dual      y [batch][2 pmus] and the complementarity gap [batch] (each may be NULL)
+ *   jg_pmulav_set_branches  from, to (1-based), status and param [nbr][16] as jg_nr_set_branches; the buses' shunt conductance and susceptance
+ *   jg_pmulav_get_flows     per lane and branch [batch][nbr][2]: from, to and series current (magnitude, angle), from, to, series and charging power
+ *                           (active, reactive); per lane and bus [batch][buses][2] the injected power.  Out-of-service branches give 0.  Each may be NULL
+ *   jg_pmulav_suspect       rho [batch][pmus] = |residual phasor| (0 for a PMU outside the model), flag [batch][pmus] = rho > threshold (per unit),
+ *                           count [batch] the flagged devices, worst [batch] the device (0-based) of the largest rho, the lowest on ties (each may be NULL)
+ *   jg_pmulav_time_kernel   milliseconds (HIP events) of `reps` runs: 0 .. 4 the parts of jg_dclav_time_kernel, 5 the polar -> rectangular pass, 6 the
+ *                           rectangular -> polar pass, 7 the branch and bus pass, 8 the suspect pass
+ * ------------------------------------------------------------------------------------------- */
+int jg_pmulav_create(int64_t* h, int64_t buses, int64_t pmus, const int64_t* rowptr, const int64_t* col, const double* val, const int32_t* status, int64_t batch,
+                     int device);
+void jg_pmulav_destroy(int64_t h);
+int jg_pmulav_dims(int64_t h, int64_t* dims);
+int jg_pmulav_set_readings(int64_t h, int64_t lane0, int64_t count, const double* magnitude, const double* angle);
+int jg_pmulav_set_status(int64_t h, const int32_t* status);
+int jg_pmulav_set_scale(int64_t h, const double* scale);
+int jg_pmulav_set_initial(int64_t h, const double* magnitude, const double* angle);
+int jg_pmulav_solve(int64_t h, int iteration, double tolerance);
+int jg_pmulav_get_voltage(int64_t h, double* magnitude, double* angle, int32_t* status, double* objective, int32_t* iterations);
+int jg_pmulav_get_residual(int64_t h, double* r);
+int jg_pmulav_get_dual(int64_t h, double* y, double* gap);
+int jg_pmulav_set_branches(int64_t h, int64_t nbr, const int64_t* from, const int64_t* to, const int8_t* status, const double* param, const double* shunt_g,
+                           const double* shunt_b);
+int jg_pmulav_get_flows(int64_t h, double* from_i, double* to_i, double* series_i, double* from_pq, double* to_pq, double* series_pq, double* charging_pq,
+                        double* injection_pq);
+int jg_pmulav_suspect(int64_t h, double threshold, double* rho, int32_t* flag, int32_t* count, int32_t* worst);
+int jg_pmulav_time_kernel(int64_t h, int kernel, int reps, double* ms);
+
+/* ---------------------------------------------------------------------------------------------
  * Symbolic analysis only (no device needed): the static schedule that replaces the symbolic half
  * of `lu`/`klu` (src/backend/utility.jl:470-476, 486-492).  Used by the CPU test-suite to replay
  * and race-check the schedule.  pattern: 0-based int32 block CSR, structurally symmetric, full

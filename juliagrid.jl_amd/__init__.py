@@ -32,6 +32,8 @@ from .dclavstateestimation import DcLavStateEstimation, dcLavStateEstimation, dc
 from . import dclavstateestimation          # noqa: F401
 from .dchuberstateestimation import DcHuberStateEstimation, dcHuberStateEstimation          # noqa: F401
 from . import dchuberstateestimation          # noqa: F401
+from .pmulavstateestimation import PmuLavStateEstimation, pmuLavStateEstimation, pmuLavModel, pmuCoefficient          # noqa: F401
+from . import pmulavstateestimation          # noqa: F401
 from .montecarlo import MonteCarloPipeline, gatherEstimates, gatherEstimatesDevice, unpackEstimates   # noqa: F401
 from .synthetic import pegaseShaped, case9241synth                          # noqa: F401
 from . import powerflow, stateestimation, dcpowerflow, dcgenerator, dcgroup, dcchance, dccascade, dccritical, dctopology, dcstateestimation, dcoptimalpowerflow, gaussseidel   # noqa: F401
@@ -56,4 +58,5 @@ __all__ = [
     "DcOptimalPowerFlow", "dcOptimalPowerFlow", "setCapability_", "setBranchOutages_", "outageCosts", "cost_", "costTables",
     "DcLavStateEstimation", "dcLavStateEstimation", "dcLavModel",
     "DcHuberStateEstimation", "dcHuberStateEstimation",
+    "PmuLavStateEstimation", "pmuLavStateEstimation", "pmuLavModel", "pmuCoefficient",
 ]

@@ -282,6 +282,21 @@ def lib():
         "jg_dchuber_set_branches": [C.c_int64, C.c_int64, I64P, I64P, F64P, F64P],
         "jg_dchuber_get_flows": [C.c_int64, F64P],
         "jg_dchuber_time_kernel": [C.c_int64, C.c_int, C.c_int, F64P],
+        # PMU least-absolute-value state estimation: an int64 token too
+        "jg_pmulav_create": [C.POINTER(C.c_int64), C.c_int64, C.c_int64, I64P, I64P, F64P, I32P, C.c_int64, C.c_int],
+        "jg_pmulav_dims": [C.c_int64, I64P],
+        "jg_pmulav_set_readings": [C.c_int64, C.c_int64, C.c_int64, F64P, F64P],
+        "jg_pmulav_set_status": [C.c_int64, I32P],
+        "jg_pmulav_set_scale": [C.c_int64, F64P],
+        "jg_pmulav_set_initial": [C.c_int64, F64P, F64P],
+        "jg_pmulav_solve": [C.c_int64, C.c_int, C.c_double],
+        "jg_pmulav_get_voltage": [C.c_int64, VP, VP, VP, VP, VP],
+        "jg_pmulav_get_residual": [C.c_int64, F64P],
+        "jg_pmulav_get_dual": [C.c_int64, VP, VP],
+        "jg_pmulav_set_branches": [C.c_int64, C.c_int64, I64P, I64P, VP, F64P, F64P, F64P],
+        "jg_pmulav_get_flows": [C.c_int64, VP, VP, VP, VP, VP, VP, VP, VP],
+        "jg_pmulav_suspect": [C.c_int64, C.c_double, VP, VP, VP, VP],
+        "jg_pmulav_time_kernel": [C.c_int64, C.c_int, C.c_int, F64P],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -305,6 +320,8 @@ def lib():
     L.jg_dclav_destroy.restype = None
     L.jg_dchuber_destroy.argtypes = [C.c_int64]
     L.jg_dchuber_destroy.restype = None
+    L.jg_pmulav_destroy.argtypes = [C.c_int64]
+    L.jg_pmulav_destroy.restype = None
     L.jg_plan_cache_clear.argtypes = []
     L.jg_plan_cache_clear.restype = None
     L.jg_comm_destroy.argtypes = [VP]

@@ -5,7 +5,7 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["jg_symbolic.cpp", "jg_plan_api.cpp", "jg_comm.cpp", "jg_engine.hip", "jg_comp.hip", "jg_lanes.hip", "jg_compact.hip", "jg_nr.hip", "jg_qlim.hip", "jg_gn.hip", "jg_dc.hip", "jg_dc_sweep.hip", "jg_dc_island.cpp", "jg_dc_phi.hip", "jg_dc_pair.hip", "jg_dc_series.hip", "jg_dc_transfer.hip", "jg_dc_generator.hip", "jg_dc_group.hip", "jg_dc_chance.hip", "jg_dc_cascade.hip", "jg_dcse.hip", "jg_dcse_critical.hip", "jg_dcse_topology.hip", "jg_dcopf.hip", "jg_gs.hip", "jg_dc_lanefactor.hip", "jg_dclav.hip", "jg_dchuber.hip"]
+SOURCES = ["jg_symbolic.cpp", "jg_plan_api.cpp", "jg_comm.cpp", "jg_engine.hip", "jg_comp.hip", "jg_lanes.hip", "jg_compact.hip", "jg_nr.hip", "jg_qlim.hip", "jg_gn.hip", "jg_dc.hip", "jg_dc_sweep.hip", "jg_dc_island.cpp", "jg_dc_phi.hip", "jg_dc_pair.hip", "jg_dc_series.hip", "jg_dc_transfer.hip", "jg_dc_generator.hip", "jg_dc_group.hip", "jg_dc_chance.hip", "jg_dc_cascade.hip", "jg_dcse.hip", "jg_dcse_critical.hip", "jg_dcse_topology.hip", "jg_dcopf.hip", "jg_gs.hip", "jg_dc_lanefactor.hip", "jg_dclav.hip", "jg_dchuber.hip", "jg_pmulav.hip"]
 LIB = os.environ.get("JG_LIB_OUT") or os.path.join(HERE, "libjgrid_hip.so")     # JG_LIB_OUT: build a variant somewhere else (JG_EXTRA_HIPCC_FLAGS)
 
 

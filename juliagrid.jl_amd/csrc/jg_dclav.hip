@@ -40,7 +40,7 @@ struct LavArgs {
     const int* groups;
     int m, n, ld, n_chunks, n_cchunks, m_in, batch;
 };
-constexpr int LR_OBJ = 0, LR_GAP = 1, LR_ALPHA = 2, LR_SMU = 3, LR_START = 4;
+constexpr int LR_OBJ = 0, LR_GAP = DCLAV_LRES_GAP, LR_ALPHA = 2, LR_SMU = 3, LR_START = 4;
 
 __device__ __forceinline__ double lav_dot(const LavArgs& a, int i, const double* X, size_t ld, size_t bl) {
     double s = 0.0;
@@ -411,8 +411,10 @@ int lav_apply_status(DclavHandle* h) {
     return 0;
 }
 
+// slack1 = 0: no fixed state (jg_pmulav.hip) -- no g_add entry, no zeroed column, no offset; `who` names the entry point in the budget's text and
+// `extra_b` is what that entry point holds per lane beside the iterates
 int dclav_create(DclavHandle* h, int64_t n64, int64_t m64, const int64_t* rowptr, const int64_t* col, const double* val, const int32_t* status, int64_t slack1,
-                 double slack_angle, int64_t batch, int device) {
+                 double slack_angle, int64_t batch, int device, const char* who = "jg_dclav_create", size_t extra_b = 0) {
     const int n = (int)n64, m = (int)m64;
     h->n = n; h->m = m; h->batch = (int)batch; h->ld = (int)((batch + 63) / 64 * 64); h->device = device; h->slack = (int)slack1 - 1; h->slack_angle = slack_angle;
     if (rowptr[0] != 0) { h->error = "rowptr is not 0-based"; return 1; }
@@ -466,7 +468,7 @@ int dclav_create(DclavHandle* h, int64_t n64, int64_t m64, const int64_t* rowptr
         if (pass == 0) for (int e = 0; e < nnzg; ++e) g_ptr[e + 1] += g_ptr[e];
     }
     std::vector<double> g_add(nnzg, 0.0);
-    g_add[entry(slack, slack)] = 1.0;
+    if (slack >= 0) g_add[entry(slack, slack)] = 1.0;
     // H' by state columns (rows ascending), the slack's list empty; H by rows with the slack's column zeroed
     std::vector<int> c_ptr(n + 1, 0);
     for (int64_t p = 0; p < nnz; ++p) if (h->h_rcol[p] != slack) c_ptr[h->h_rcol[p] + 1]++;
@@ -486,13 +488,13 @@ int dclav_create(DclavHandle* h, int64_t n64, int64_t m64, const int64_t* rowptr
     h->n_chunks = (m + DCLAV_ROWS - 1) / DCLAV_ROWS;
     h->n_cchunks = (n + DCLAV_COLS - 1) / DCLAV_COLS;
     const size_t fac_b = lane_factor_bytes_per_lane(nnzg, S.n_entries, n);
-    const size_t it_b = (10 * M + 5 * N + 1 + 4 * (size_t)h->n_chunks + (size_t)h->n_cchunks + 6) * sizeof(double) + 3 * sizeof(int);
+    const size_t it_b = (10 * M + 5 * N + 1 + 4 * (size_t)h->n_chunks + (size_t)h->n_cchunks + 6) * sizeof(double) + 3 * sizeof(int) + extra_b;
     h->bytes_per_lane = fac_b + it_b;
     DC_HIP(hipSetDevice(device));
     size_t free_b = 0, total_b = 0;
     DC_HIP(hipMemGetInfo(&free_b, &total_b));
     if (h->bytes_per_lane * ld > free_b) {
-        h->error = "jg_dclav_create: " + std::to_string(ld) + " lanes need " + bytes_text(h->bytes_per_lane * ld) + " (" + bytes_text(fac_b * ld) + " of lane-valued factor, " +
+        h->error = std::string(who) + ": " + std::to_string(ld) + " lanes need " + bytes_text(h->bytes_per_lane * ld) + " (" + bytes_text(fac_b * ld) + " of lane-valued factor, " +
                    bytes_text(it_b * ld) + " of iterates), " + bytes_text(free_b) + " are free: use a smaller batch";
         return 5;
     }
@@ -524,12 +526,15 @@ int dclav_create(DclavHandle* h, int64_t n64, int64_t m64, const int64_t* rowptr
     return 0;
 }
 
-void dclav_destroy(DclavHandle* h) {
+void dclav_release(DclavHandle* h) {
     hipSetDevice(h->device);
     if (h->stream) hipStreamSynchronize(h->stream);
     for (void* p : h->allocs) hipFree(p);
     if (h->p_count) hipHostFree(h->p_count);
     if (h->stream) hipStreamDestroy(h->stream);
+}
+void dclav_destroy(DclavHandle* h) {
+    dclav_release(h);
     delete h;
 }
 
@@ -553,7 +558,43 @@ int fetch_lanes(DclavHandle* d, const double* dev, size_t rows, double* out, dou
     return 0;
 }
 
+// `reps` timings of part `kernel` (0 .. 4, jgrid.h: jg_dclav_time_kernel) of an iteration of a solved, observable handle
+int lav_time_parts(DclavHandle* d, int kernel, int reps, double* ms) {
+    const int ng = d->ld / 64;
+    const LavArgs a = args_of(d, nullptr);
+    // every lane of every group runs, finished or not; nothing of a lane's state is written (the update pass is left out), so the handle stays solved
+    return time_events(d->stream, reps, ms, d->error, [&]() -> int {
+        if (kernel == 0 || kernel == 4) launch_residuals(d, a, ng);
+        if (kernel == 0 || kernel == 1) launch_gain(d, ng, nullptr);
+        if (kernel == 0 || kernel == 2) launch_factor(d, ng, nullptr);
+        if (kernel == 0) launch_steps(d, a, ng);
+        if (kernel == 3) launch_sweeps(d, d->DT, ng, nullptr);
+        if (kernel == 4) {
+            const dim3 rows = by4(d->n_chunks, ng), wg(64, 4);
+            hipLaunchKernelGGL(k_lav_step<false>, rows, wg, 0, d->stream, a);
+            hipLaunchKernelGGL(k_lav_gapaff, rows, wg, 0, d->stream, a);
+            hipLaunchKernelGGL(k_lav_corr_rows, by4(d->m, ng), wg, 0, d->stream, a);
+            hipLaunchKernelGGL(k_lav_col<false>, by4(d->n_cchunks, ng), wg, 0, d->stream, a);
+            hipLaunchKernelGGL(k_lav_step<true>, rows, wg, 0, d->stream, a);
+        }
+        return 0;
+    });
+}
+
 }  // namespace
+
+// what jg_pmulav.hip reaches the iteration through (jg_dclav.hpp)
+int lav_create(DclavHandle* h, const char* who, size_t extra_b, int64_t n, int64_t m, const int64_t* rowptr, const int64_t* col, const double* val, const int32_t* status,
+               int64_t batch, int device) {
+    return dclav_create(h, n, m, rowptr, col, val, status, 0, 0.0, batch, device, who, extra_b);
+}
+void lav_release(DclavHandle* h) { dclav_release(h); }
+int lav_set_status(DclavHandle* h) { return lav_apply_status(h); }
+int lav_run(DclavHandle* h, int maxit, double tol) { return lav_solve(h, maxit, tol); }
+int lav_time(DclavHandle* h, int kernel, int reps, double* ms) { return lav_time_parts(h, kernel, reps, ms); }
+int lav_upload(DclavHandle* h, double* dev, size_t rows, const double* src, size_t lane0, size_t count) { return upload_lanes(h, dev, rows, src, lane0, count); }
+int lav_fetch(DclavHandle* h, const double* dev, size_t rows, double* out) { return fetch_lanes(h, dev, rows, out, 0.0); }
+
 }  // namespace jg
 
 using jg::DclavHandle;
@@ -735,25 +776,7 @@ int jg_dclav_time_kernel(int64_t h, int kernel, int reps, double* ms) {
     LAV_ENTER(h);
     if (!ms || reps < 1 || kernel < 0 || kernel > 4) return api_fail(1, "jg_dclav_time_kernel: bad argument");
     if (!d->solved || d->unobservable) return api_fail(4, "jg_dclav_time_kernel: jg_dclav_solve first, on an observable set");
-    const int ng = d->ld / 64;
-    const jg::LavArgs a = jg::args_of(d, nullptr);
-    // every lane of every group runs, finished or not; nothing of a lane's state is written (the update pass is left out), so the handle stays solved
-    int rc = jg::time_events(d->stream, reps, ms, d->error, [&]() -> int {
-        if (kernel == 0 || kernel == 4) jg::launch_residuals(d, a, ng);
-        if (kernel == 0 || kernel == 1) jg::launch_gain(d, ng, nullptr);
-        if (kernel == 0 || kernel == 2) jg::launch_factor(d, ng, nullptr);
-        if (kernel == 0) jg::launch_steps(d, a, ng);
-        if (kernel == 3) jg::launch_sweeps(d, d->DT, ng, nullptr);
-        if (kernel == 4) {
-            const dim3 rows = jg::by4(d->n_chunks, ng), wg(64, 4);
-            hipLaunchKernelGGL(jg::k_lav_step<false>, rows, wg, 0, d->stream, a);
-            hipLaunchKernelGGL(jg::k_lav_gapaff, rows, wg, 0, d->stream, a);
-            hipLaunchKernelGGL(jg::k_lav_corr_rows, jg::by4(d->m, ng), wg, 0, d->stream, a);
-            hipLaunchKernelGGL(jg::k_lav_col<false>, jg::by4(d->n_cchunks, ng), wg, 0, d->stream, a);
-            hipLaunchKernelGGL(jg::k_lav_step<true>, rows, wg, 0, d->stream, a);
-        }
-        return 0;
-    });
+    const int rc = jg::lav_time(d, kernel, reps, ms);
     return rc ? api_fail(rc, d->error) : 0;
 }
 

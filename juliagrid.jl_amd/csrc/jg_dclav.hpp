@@ -35,10 +35,11 @@ constexpr int DCLAV_ROWS = 32;                  // rows of H per wavefront in th
 constexpr int DCLAV_COLS = 8;                   // state columns of H' per wavefront in the column pass
 constexpr double DCLAV_STEP_BACK = 0.995;
 constexpr double DCLAV_START_FLOOR = 1e-8;
+constexpr int DCLAV_LRES_GAP = 1;               // the row of lres that holds the gap
 
 struct DclavHandle : DcDevice {
     int n = 0, m = 0, batch = 0, ld = 0, slack = 0, nnz_gain = 0, nbr = 0, m_in = 0;
-    double slack_angle = 0.0, hnorm = 0.0;      // hnorm: max_j sum_i |H_ij| over the in-service rows
+    double slack_angle = 0.0, hnorm = 0.0;      // hnorm: max_j sum_i |H_ij| over the in-service rows; slack = -1: no fixed state (lav_create)
     DcLaneFactor fac;                           // of G = H' Q H, values per lane
     std::vector<int> h_rptr, h_rcol; std::vector<double> h_rval; std::vector<int> h_st;
     int* r_ptr = nullptr; int* r_col = nullptr; double* r_val = nullptr;            // H by rows, the slack's column zeroed
@@ -64,5 +65,17 @@ struct DclavHandle : DcDevice {
     long long factorisations = 0; int last_iterations = 0;
     bool solved = false, have_z = false, unobservable = false;
 };
+
+// The same iteration WITHOUT a fixed state, for a model that observes its own reference (jg_pmulav.hpp: phasors): the gain carries no added diagonal
+// entry, no column of H is zeroed and theta has no offset; every kernel, launch and table is the one jg_dclav_create builds.  `who` names the entry
+// point in the text of a refused budget, `extra_b` is what it holds per lane beside the iterates.  h_theta0 / have_init: [batch][n], used once.
+int lav_create(DclavHandle* h, const char* who, size_t extra_b, int64_t n, int64_t m, const int64_t* rowptr, const int64_t* col, const double* val, const int32_t* status,
+               int64_t batch, int device);
+void lav_release(DclavHandle* h);                               // everything the handle owns but the handle itself
+int lav_set_status(DclavHandle* h);                             // h_st -> the device, the in-service count and hnorm
+int lav_run(DclavHandle* h, int maxit, double tol);            // the start and the iteration of jg_dclav_solve
+int lav_time(DclavHandle* h, int kernel, int reps, double* ms); // the parts 0 .. 4 of jg_dclav_time_kernel
+int lav_upload(DclavHandle* h, double* dev, size_t rows, const double* src, size_t lane0, size_t count);      // [count][rows] -> lanes lane0 .. of [rows][ld]
+int lav_fetch(DclavHandle* h, const double* dev, size_t rows, double* out);                                   // [rows][ld] -> [batch][rows]
 
 }  // namespace jg

@@ -747,15 +747,23 @@ def setOutages_(an: AcPowerFlow, labels, scenario0: int = 0, islands: str = "ski
 
 
 # ---- post-processing (N2): power!(analysis) / current!(analysis) for every scenario of the batch ------------------
-def _upload_branches(an: AcPowerFlow):
-    system = an.system
-    ac, par, lay = system.model.ac, system.branch.parameter, system.branch.layout
+def _branch_table(system):
+    """[branches, 16] of jg_nr_set_branches: yff, yft, ytf, ytt, y, tij as (re, im), then the charging conductance and susceptance and 1 / tau"""
+    ac, par = system.model.ac, system.branch.parameter
     nb = system.branch.number
     tij = (1.0 / par.turnsRatio) * np.exp(-1j * par.shiftAngle)                     # acAnalysis.jl:846-851
     tab = np.zeros((nb, 16))
     for c, z in enumerate((ac.nodalFromFrom, ac.nodalFromTo, ac.nodalToFrom, ac.nodalToTo, ac.admittance, tij)):
         tab[:, 2 * c], tab[:, 2 * c + 1] = np.real(z), np.imag(z)
     tab[:, 12], tab[:, 13], tab[:, 14] = par.conductance, par.susceptance, 1.0 / par.turnsRatio
+    return tab
+
+
+def _upload_branches(an: AcPowerFlow):
+    system = an.system
+    lay = system.branch.layout
+    nb = system.branch.number
+    tab = _branch_table(system)
     L = _lib.lib()
     _lib.check(L.jg_nr_set_branches(an._h, nb, np.ascontiguousarray(lay.from_, dtype=np.int64), np.ascontiguousarray(lay.to, dtype=np.int64),
                                     np.ascontiguousarray(lay.status, dtype=np.int8), np.ascontiguousarray(tab.reshape(-1))))
